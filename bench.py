@@ -16,9 +16,17 @@ torch.cuda.synchronize() pairs, with HIP events on the launch stream for the ker
 Settling.  An MI355X that has been idle drops its clock when a sustained load arrives and takes about 50 ms to settle
 (tools/settle_probe.py: 0.43-0.47 ms a step during the first 10 ms, 0.355 ms from 50 ms on and for the next 8 s).  W warm-up
 steps are 2 ms.  So after the W warm-up steps untimed steps go on back to back for --settle-ms (default 200) before EXACTLY K
-steps are timed: `value` is the sustained rate.  What the first K steps after the W warm-up steps take -- how rounds 1 and 2
-measured -- is reported beside it as `cold_start` (same steps, same work; the difference is the chip's clock).  Every other
+steps are timed: `value` is the sustained rate.  With --full, what the first K steps after the W warm-up steps take -- how rounds
+1 and 2 measured -- is reported beside it as `cold_start` (same steps, same work; the difference is the chip's clock).  Every other
 timed region of this file (fp32 format, one rank's bands, config 5, the extras) is settled the same way.
+
+A plain run (no --full) does only what `value` needs: set-up, the W warm-up steps, settling, the K timed steps (at N > 1 also the
+two-stream leg, which may be `value`), --dump-outputs if given, and the line.  Everything else below -- cold start, host cameras,
+delivery, config 5, fp32 format, scaling proxy, drop-in call, CPU baseline, extras -- runs with --full only.
+
+--dump-outputs DIR writes what the last timed step left in its framebuffers (rank 0's at N > 1), as float32 .npy files: the
+step's last frame whole and a fixed, seeded sample of all its frames (see dump_outputs).  The inputs are the committed cameras,
+so two builds run with the same arguments can be compared output for output.
 
 N > 1 (one process per GPU, launched by torch.distributed.run): every frame is tiled across the ranks in
 row bands (band b -> rank b % N; 32 rows = the reference's chunk size, or 16 / 8 rows when that shares the
@@ -28,7 +36,7 @@ separately after the timed region and reported as gather_ms_per_frame / value_in
 D2H copy at N = 1 it is a delivery step, not part of `value`).
 
 One JSON line on rank 0, with the `roofline` of the dominant kernel (framebuffer write bytes vs HBM peak; `roofline.valu`:
-the instruction-issue bound that actually limits these kernels, from the committed SQ counters), `value_rgbf32` (the same
+the instruction-issue bound that actually limits these kernels, from the committed SQ counters) and, with --full, `value_rgbf32` (the same
 workload into three fp32 channels -- the format in which "colours within 1e-4" is a statement about the stored values),
 `scaling_proxy` (one rank's share of an 8-GPU run, timed on this GPU) and a `cpu_baseline` (the oracle, multi-threaded
 exactly like the reference's BlockingRenderer, on a bounded sample of the same frames).
@@ -97,8 +105,11 @@ def main():
     ap.add_argument("--frames-per-step", type=int, default=160)
     ap.add_argument("--settle-ms", type=float, default=200.0, help="untimed steps are issued back to back for at least this long before every timed region: "
                     "the chip takes ~50 ms of sustained load to settle its clock (tools/settle_probe.py); 0: time from a cold start")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: cold start, host cameras, delivery, "
+                    "config 5, fp32 format, scaling proxy, drop-in call, CPU baseline, extras (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the framebuffers of the last timed step to DIR/*.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no extra configs")
     ap.add_argument("--headline-only", action="store_true", help="only the timed headline loop (the target of the rocprofv3 --pmc passes)")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the N-rank plumbing (launcher, band split, barriers, gather over gloo): "
                     "no GPU, no kernels, no throughput -- used by tests/test_bench_launch.py")
@@ -207,16 +218,19 @@ def main():
     # ---- cold start: the first `steps` steps after `warmup` steps from an idle chip (how rounds 1 and 2 measured).  The chip is
     # then in the middle of a clock transient -- it drops its clock when the load arrives and takes ~50 ms to settle
     # (tools/settle_probe.py: 0.43-0.47 ms a step in the first 10 ms, 0.355 from 50 ms on, flat for the next 8 s) -- so this is
-    # reported as `cold_start`, and `value` is measured after `--settle-ms` of sustained load.
+    # reported as `cold_start` (--full only), and `value` is measured after `--settle-ms` of sustained load.
+    extras = args.full and not args.headline_only          # the legs beside the headline
     run(args.warmup)
-    barrier()
-    t0 = time.perf_counter()
-    run(args.steps)
-    barrier()
-    cold = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
-    if dist is not None:
-        dist.all_reduce(cold, op=dist.ReduceOp.MAX)
-    cold_ms = float(cold.item()) * 1e3 / args.steps
+    cold_ms = None
+    if args.full:
+        barrier()
+        t0 = time.perf_counter()
+        run(args.steps)
+        barrier()
+        cold = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
+        if dist is not None:
+            dist.all_reduce(cold, op=dist.ReduceOp.MAX)
+        cold_ms = float(cold.item()) * 1e3 / args.steps
     settle(torch, lambda: run(1), args.settle_ms)
     barrier()
     e0 = torch.cuda.Event(enable_timing=True)
@@ -241,6 +255,8 @@ def main():
     value = rays / wall / 1e6
     one_stream_value = value
     one_stream_ms = wall * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, fb, own_rows, fmt.pitch)
 
     # ---- the same K steps issued alternately on TWO streams (two scene handles -- each has its own device-side scratch -- and two
     # sets of framebuffers; the caller says so, nt_render_opts.overlapped, and the library shapes its launches for it: waves of 64
@@ -248,9 +264,10 @@ def main():
     # of the next.  For a full frame that is 2-3 % (the kernel is bound by vector issue); for a rank's share of a tiled frame it
     # is a quarter (tools/two_stream_probe.py: a rank's eighth 60.6 -> 46.0 us a step).  At N = 1 `value` stays the one-stream
     # figure (one kernel at a time: what the roofline and the committed profiles describe); at N > 1 the better of the two IS
-    # `value` (`config.issue` says which).  EXACTLY K steps, barrier-bracketed, MAX over ranks, like the loop above.
+    # `value` (`config.issue` says which).  EXACTLY K steps, barrier-bracketed, MAX over ranks, like the loop above.  A plain run
+    # times this leg only at N > 1, where it may be `value`; the host-camera legs run with --full only.
     two_ms = host_ms = host_two_ms = None
-    if not args.headline_only:
+    if extras or (world > 1 and not args.headline_only):
         scene2 = tracern.BoxScene(n)
         fb2 = torch.empty((F, frame_bytes), dtype=torch.uint8, device="cuda")
         stream2 = torch.cuda.Stream()
@@ -281,9 +298,10 @@ def main():
             if r < 0:
                 _lib.check(r)
         two_ms = timed_leg(step_table_two, 2 * args.warmup)
-        # ---- the PCIe-inclusive way: the cameras as host arrays on every call (packed, uploaded, launched), one stream and two
-        host_ms = timed_leg(step_host, args.warmup)
-        host_two_ms = timed_leg(step_host_two, 2 * args.warmup)
+        if extras:
+            # ---- the PCIe-inclusive way: the cameras as host arrays on every call (packed, uploaded, launched), one stream and two
+            host_ms = timed_leg(step_host, args.warmup)
+            host_two_ms = timed_leg(step_host_two, 2 * args.warmup)
         torch.cuda.synchronize()
         del fb2
     # at N > 1 both ways of issuing the steps were timed the same way and the better one IS `value` (`config.issue` says which);
@@ -294,10 +312,10 @@ def main():
         value = float(W) * H * F / (two_ms * 1e-3) / 1e6
         issue = "steps alternate between two streams (see two_streams)"
 
-    # ---- delivery step, outside `value`: gather to rank 0 (RCCL) / D2H at N = 1
+    # ---- delivery step, outside `value` (--full only): gather to rank 0 (RCCL) / D2H at N = 1
     gather_ms = None
     gather_ok = None
-    if dist is not None:
+    if args.full and dist is not None:
         dist.barrier()
         torch.cuda.synchronize()
         reps = 5
@@ -319,7 +337,7 @@ def main():
                                                  C.c_void_p(stream.cuda_stream)))
             torch.cuda.synchronize()
             gather_ok = bool(torch.equal(whole.reshape(H, fmt.pitch), full))
-    else:
+    elif args.full:
         host = torch.empty(frame_bytes, dtype=torch.uint8).pin_memory()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -333,7 +351,7 @@ def main():
     # ---- BASELINE.json configs[4], the config north_star assigns to the 8-GPU split: BoxScene(10) 4096 x 4096, tiled over the
     # ranks in row bands, RCCL gather verified (every rank takes part; reported next to the headline at every N)
     cfg5 = None
-    if not args.headline_only:
+    if extras:
         try:
             cfg5 = config5(torch, dist, ntracer_amd, tracern, _lib, ntd, rank, world, local_rank)
         except Exception as e:           # never hide the headline
@@ -408,29 +426,31 @@ def main():
             "what": "the K steps issued alternately on two streams (two scene handles, two sets of framebuffers, nt_render_opts.overlapped; cameras resident): "
                     "consecutive calls overlap (= `value` at N > 1 when it is the faster way)",
             "ms_per_step": round(two_ms, 5), "value": round(float(W) * H * F / (two_ms * 1e-3) / 1e6, 1)},
-        "cold_start": {"what": "the first %d steps after %d warm-up steps from an idle chip (no settling: the clock transient of the first ~50 ms of load)"
-                               % (args.steps, args.warmup), "ms_per_step": round(cold_ms, 5), "value": round(float(W) * H * F / (cold_ms * 1e-3) / 1e6, 1)},
+        "cold_start": None if cold_ms is None else {
+            "what": "the first %d steps after %d warm-up steps from an idle chip (no settling: the clock transient of the first ~50 ms of load)"
+                    % (args.steps, args.warmup), "ms_per_step": round(cold_ms, 5), "value": round(float(W) * H * F / (cold_ms * 1e-3) / 1e6, 1)},
         "host_cameras": None if host_ms is None else {
             "what": "the same steps with the cameras handed over as host arrays on every call (nt_render_frames_device: packed, uploaded and "
                     "launched each time -- the PCIe-inclusive rate; the reference's boundary sets a camera per frame): never `value`",
             "ms_per_step": round(host_ms, 5), "value": round(float(W) * H * F / (host_ms * 1e-3) / 1e6, 1),
             "two_streams_ms_per_step": round(host_two_ms, 5), "two_streams_value": round(float(W) * H * F / (host_two_ms * 1e-3) / 1e6, 1)},
-        "delivery": {"what": "RCCL gather to rank 0" if world > 1 else "D2H copy to pinned host memory",
-                     "ms_per_frame": round(gather_ms, 4), "verified_equal_to_single_gpu_frame": gather_ok,
-                     "value_incl_delivery": round(float(W) * H * F / ((ms_per_step + gather_ms * F) * 1e-3) / 1e6, 1)},
+        "delivery": None if gather_ms is None else {
+            "what": "RCCL gather to rank 0" if world > 1 else "D2H copy to pinned host memory",
+            "ms_per_frame": round(gather_ms, 4), "verified_equal_to_single_gpu_frame": gather_ok,
+            "value_incl_delivery": round(float(W) * H * F / ((ms_per_step + gather_ms * F) * 1e-3) / 1e6, 1)},
     }
 
     if cfg5 is not None:
         out["config5"] = cfg5
-    if args.headline_only:
+    if not extras:
         args.no_cpu_baseline = args.no_extra = True
-    if world == 1 and not args.headline_only:
+    if world == 1 and extras:
         try:
             out["value_rgbf32"] = value_rgbf32(torch, ntracer_amd, tracern, _lib, origins, axes, F)
             out["scaling_proxy"] = scaling_proxy(torch, ntracer_amd, tracern, _lib, ntd, origins, axes, F, ms_per_step, two_ms)
         except Exception as e:       # never hide the headline
             out["scaling_proxy"] = {"error": repr(e)}
-    if world == 1 and not args.headline_only:
+    if world == 1 and extras:
         try:
             out["dropin_render"] = dropin_render(torch, ntracer_amd, tracern)
         except Exception as e:
@@ -585,6 +605,23 @@ def settle(torch, fn, ms):
         k += 1
         if k % 8 == 0:
             torch.cuda.synchronize()
+
+
+DUMP_SAMPLE = 1 << 22          # bytes of the step's framebuffers sampled by --dump-outputs
+DUMP_SEED = 0
+
+
+def dump_outputs(torch, d, fb, rows, pitch):
+    """--dump-outputs: what the last timed step left in its framebuffers -- the bytes a caller of nt_render_table_device gets --
+    as float32 (each value a byte, 0..255), under 64 MB in all: `last_frame.npy` the step's last frame whole ([rows, pitch]),
+    `frames_sample.npy` DUMP_SAMPLE bytes of all its frames at positions drawn (sorted) with seed DUMP_SEED, the same every run."""
+    os.makedirs(d, exist_ok=True)
+    flat = fb.reshape(-1)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=min(DUMP_SAMPLE, flat.numel())))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    last = fb[-1].reshape(rows, pitch).cpu().numpy()
+    np.save(os.path.join(d, "frames_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(d, "last_frame.npy"), last.astype(np.float32))
 
 
 def _time_frames(torch, _lib, scene, fmt, origins, axes, frames, reps, opts=None, rows=None):

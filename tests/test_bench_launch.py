@@ -51,7 +51,7 @@ def test_single_process_dry_run_and_world_mismatch():
 
 @pytest.mark.gpu
 def test_bare_bench_gpus_2_on_one_card():
-    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
+    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"],
                     {"NTRACER_BENCH_BACKEND": "gloo", "NTRACER_BENCH_DEVICE": "0"}, timeout=900)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     assert len(lines) == 1, p.stdout
@@ -59,6 +59,36 @@ def test_bare_bench_gpus_2_on_one_card():
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0
     assert out["delivery"]["verified_equal_to_single_gpu_frame"] is True
     assert out["config5"]["n_gpus"] == 2 and out["config5"]["gather_verified_equal_to_whole_frame"] is True and out["config5"]["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_headline_and_dumps_its_frames(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and nothing beside them; --dump-outputs writes the last step's frames,
+    which must be the bytes a fresh render of the same cameras gives."""
+    import numpy as np
+    import ntracer_amd
+    from ntracer_amd import tracern
+    p, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["config"]["launches"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in out, k
+    assert out["cold_start"] is None and out["config5"] is None and "cpu_baseline" not in out and "extra" not in out
+    last = np.load(str(tmp_path / "last_frame.npy"))
+    sample = np.load(str(tmp_path / "frames_sample.npy"))
+    assert last.dtype == np.float32 and sample.dtype == np.float32
+    assert last.nbytes + sample.nbytes < 64e6
+    g = np.load(os.path.join(ROOT, "tests", "golden", "box_n6_1920x1080.npz"))
+    fmt = ntracer_amd.ImageFormat(1920, 1080, [ntracer_amd.Channel(8, 1, 0, 0), ntracer_amd.Channel(8, 0, 1, 0),
+                                               ntracer_amd.Channel(8, 0, 0, 1), ntracer_amd.Channel(8, 0, 0, 0)])
+    box = tracern.BoxScene(6)
+    f = out["config"]["frames_per_step"] - 1
+    box._set_camera_arrays(g["origins"][f % len(g["origins"])], g["axes"][f % len(g["origins"])])
+    buf = bytearray(fmt.pitch * 1080)
+    assert ntracer_amd.BlockingRenderer().render(buf, fmt, box)
+    assert np.array_equal(last, np.frombuffer(bytes(buf), np.uint8).reshape(1080, fmt.pitch).astype(np.float32))
 
 
 def test_committed_profile_gives_an_issue_bound_below_one():

@@ -8,10 +8,10 @@ raw=$root/gpurun_out/${tag}_prof
 out=$root/gpurun_out/${tag}_profiles
 mkdir -p $raw $out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $root/bench.py --no-cpu-baseline"
-S="python3 $root/bench.py --headline-only --steps 3 --warmup 1"
+B="python3 $root/bench.py --full --no-cpu-baseline"
+S="python3 $root/bench.py --full --headline-only --steps 3 --warmup 1"
 echo "[1] kernel trace of the headline loop (one stream, one kernel at a time: the timed region behind value and roofline)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $raw/kt -- python3 $root/bench.py --headline-only > $raw/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $raw/kt -- python3 $root/bench.py --full --headline-only > $raw/kt.log 2>&1
 cp $(ls $raw/kt/*/*_kernel_stats.csv | head -1) $out/${tag}_bench_kernel_stats.csv
 grep "^{" $raw/kt.log > $out/${tag}_bench_under_profiler.json
 cp $root/gpurun_out/bench_details.json $out/${tag}_bench_under_profiler_details.json
