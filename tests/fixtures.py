@@ -20,6 +20,29 @@ BOX_FIXTURES = ["box_n3_1920x1080", "box_n6_1920x1080", "box_n10_4096x4096", "bo
                 "box_n5_320x200", "box_n8_320x200", "box_n12_320x200"]
 
 
+# BoxScene's fused tile kernel (box_tile_kernel, ntracer_amd/csrc/nt_box.hpp): launches that land on each block shape
+# nt_box_tile_geom (nt_device.hpp) picks and on each split of the redo kernel (N >= 9, packed RGB), in the order
+# tests/test_box_tile_matrix.py runs them (the scratch buffers grow, then are reused by smaller launches).
+# (width, height, frames, (rows a wave, waves a block), redo split, bytes of pitch padding)
+BOX_TILE_SHAPES = [
+    (640, 360, 40, (8, 4), 2, 0),          # small multi-frame launch with lead frames
+    (1920, 1000, 40, (16, 3), 2, 64),      # three waves a block
+    (1920, 1080, 72, (64, 1), 1, 0),       # the bench's shape
+    (4100, 520, 60, (64, 1), 1, 64),       # three redo words a row (> 2048 pixels)
+    (1000, 700, 100, (16, 4), 1, 64),      # split 1 with 16-row waves, ragged last column
+    (1930, 1080, 17, (16, 4), 2, 0),       # ragged last column, no lead frames
+]
+# one rank's bands of the bench's call: (width, height, frames, band_rank, band_world, band_rows, (rows, waves), split);
+# compact buffer, 136 owned rows
+BOX_TILE_BAND = (1920, 1080, 160, 3, 8, 8, (16, 3), 2)
+
+
+def box_redo_split(width, row_count, frames):
+    """launch_box_fixed's choice between box_redo_kernel<..., 2> (two waves a redo word) and <..., 1>"""
+    redo_words = ((width + 63) // 64 + 31) // 32
+    return 2 if row_count * frames * redo_words < 48 * 1024 else 1
+
+
 def load(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"))
 
@@ -89,3 +112,48 @@ def known_answer_flat(ka):
                 materials=np.asarray([[1, 1, 1, 1, 1, 1, 1, 0, 1, 8]], np.float32),
                 aabb_start=np.asarray(ka["aabb"]["start"], np.float32), aabb_end=np.asarray(ka["aabb"]["end"], np.float32),
                 batch_size=4)
+
+
+def stress_cameras(n, rng):
+    """orientations x origins chosen to land rays on edges, faces' planes, the inside, grazing directions"""
+    cams = []
+    eye = np.eye(n, dtype=np.float32)
+    for k in range(10):
+        q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        if k == 0:
+            q = eye.copy()                                   # axis-aligned: direction components exactly 0
+        elif k == 1:
+            q = eye + 1e-7 * rng.standard_normal((n, n))     # almost axis-aligned: grazing rays
+        elif k == 2:
+            q = eye[rng.permutation(n)]
+        elif k == 3:
+            q = q.copy()
+            q[1] = q[1] + 0.8 * q[2] + 0.3 * q[0]            # `up` far from orthogonal: no quadratic |dir|^2 shortcut
+        elif k == 4:
+            q = q.copy()
+            q[0] = 3.0 * q[0]                                # stretched `right`
+            q[1] = 0.0 * q[1]                                # ... and no `up` at all: every row the same
+        q = np.ascontiguousarray(q, np.float32)
+        for dist in (0.3, 1.0, 1.0000001, 1.7, 3.0, 9.0, 60.0):
+            back = -q[2] * np.float32(dist)                  # look at the centre from `dist` away ...
+            cams.append((back.astype(np.float32), q))
+            off = back + np.float32(0.4) * q[0] + np.float32(0.25) * q[1]          # ... and off-centre
+            cams.append((off.astype(np.float32), q))
+        o = np.zeros(n, np.float32)
+        o[:3] = (-1.0, 0.3, -2.5)                            # origin exactly on the plane of a face
+        cams.append((o, q))
+        o = o.copy()
+        o[0] = 1.0
+        o[min(3, n - 1)] = 1.0                               # on two planes at once
+        cams.append((o, q))
+    return cams
+
+
+def diagonal_camera(n, dist, rng):
+    """tools/box_soak.py's diagonal camera: every coordinate of the origin equal, looking at the centre -- whole regions of
+    near-ties between faces"""
+    q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    q = np.array(q, np.float32)
+    o = np.full(n, -dist / np.sqrt(n), np.float32)
+    q[2] = -o / np.linalg.norm(o)
+    return o, np.ascontiguousarray(q, np.float32)

@@ -85,42 +85,7 @@ def test_box_full_frame_bytes_equal_oracle(n, w, h):
         assert np.array_equal(img, ref)
 
 
-def _stress_cameras(n, rng):
-    """orientations x origins chosen to land rays on edges, faces' planes, the inside, grazing directions"""
-    cams = []
-    eye = np.eye(n, dtype=np.float32)
-    for k in range(10):
-        q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-        if k == 0:
-            q = eye.copy()                                   # axis-aligned: direction components exactly 0
-        elif k == 1:
-            q = eye + 1e-7 * rng.standard_normal((n, n))     # almost axis-aligned: grazing rays
-        elif k == 2:
-            q = eye[rng.permutation(n)]
-        elif k == 3:
-            q = q.copy()
-            q[1] = q[1] + 0.8 * q[2] + 0.3 * q[0]            # `up` far from orthogonal: no quadratic |dir|^2 shortcut
-        elif k == 4:
-            q = q.copy()
-            q[0] = 3.0 * q[0]                                # stretched `right`
-            q[1] = 0.0 * q[1]                                # ... and no `up` at all: every row the same
-        q = np.ascontiguousarray(q, np.float32)
-        for dist in (0.3, 1.0, 1.0000001, 1.7, 3.0, 9.0, 60.0):
-            back = -q[2] * np.float32(dist)                  # look at the centre from `dist` away ...
-            cams.append((back.astype(np.float32), q))
-            off = back + np.float32(0.4) * q[0] + np.float32(0.25) * q[1]          # ... and off-centre
-            cams.append((off.astype(np.float32), q))
-        o = np.zeros(n, np.float32)
-        o[:3] = (-1.0, 0.3, -2.5)                            # origin exactly on the plane of a face
-        cams.append((o, q))
-        o = o.copy()
-        o[0] = 1.0
-        o[min(3, n - 1)] = 1.0                               # on two planes at once
-        cams.append((o, q))
-    return cams
-
-
-@pytest.mark.parametrize("n", [3, 4, 6, 8, 10, 11, 13, 15, 16, 20, 21, 24, 27, 40, 64])
+@pytest.mark.parametrize("n", list(range(3, 25)) + [27, 40, 64])
 def test_box_stress_cameras_bytes_and_floats_equal_oracle(n):
     """The BoxScene kernel sorts rays into clear misses, clear hits and unclear ones, and only the last get the
     reference-ordered evaluation; quantised formats also skip the sqrt and the division away from rounding
@@ -133,7 +98,7 @@ def test_box_stress_cameras_bytes_and_floats_equal_oracle(n):
                [(16, 0, 0, 1), (16, 0, 1, 0), (16, 1, 0, 0)],
                [(32, 1, 0, 0, 0, True), (32, 0, 1, 0, 0, True), (32, 0, 0, 1, 0, True)]]
     sc = tracern.BoxScene(n)
-    for k, (origin, axes) in enumerate(_stress_cameras(n, rng)):
+    for k, (origin, axes) in enumerate(fx.stress_cameras(n, rng)):
         sc._set_camera_arrays(origin, axes)
         osc = ob.OracleScene(n, origin, axes)
         chans = formats[k % len(formats)] if k % 3 else fx.RGBX8
@@ -983,7 +948,13 @@ def test_bench_workload_every_frame_equals_the_oracle():
     _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(fb.data_ptr()), h * fmt.pitch, nf,
                                                   o.ctypes.data_as(_lib.f32p), a.ctypes.data_as(_lib.f32p), C.byref(st_),
                                                   None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    # ... and bench.py's own call: the 160 cameras in a camera table, frames [0, 160)
+    from ntracer_amd.render import CameraTable
+    tb = torch.zeros_like(fb)
+    assert CameraTable(6, o, a).render(sc, tb, fmt, first=0, count=nf)
     torch.cuda.synchronize()
+    assert torch.equal(tb, fb), [f for f in range(nf) if not torch.equal(tb[f], fb[f])][:8]
+    del tb
     got = fb.cpu().numpy().reshape(nf, h, fmt.pitch)
     osc = ob.OracleScene(6, o[0], a[0])
     threads = max(1, min(63, (os.cpu_count() or 2) - 1))
