@@ -157,3 +157,99 @@ def diagonal_camera(n, dist, rng):
     o = np.full(n, -dist / np.sqrt(n), np.float32)
     q[2] = -o / np.linalg.norm(o)
     return o, np.ascontiguousarray(q, np.float32)
+
+
+# CompositeScene's kernel routes (launch_composite_fixed<N> in ntracer_amd/csrc/nt_composite.hpp, nt_launch_composite in
+# nt_var.hip), in the order tests/test_composite_matrix.py renders them at every fixed N = 3..10.  Each entry is one kernel
+# instantiation as its hipLaunchKernelGGL spells it (spaces dropped), with the ways to reach it:
+# (scene, parameter set, NTRACER_* switches, mode).  Scenes: "lean" (the N-orthoplex in batches), "mixed" (the same with four
+# loose triangles, a cube and a sphere), "deep" (hand-built combs of stack_depth 31, 32, 33, 40, ...).  Modes: "render" (a
+# 97 x 61 RGBF32 frame), "stats" (collect_stats=True) and "colors_at" (a pixel lattice).  tests/test_composite_routes.py
+# checks, without a GPU, that every launch of the two functions and every NTRACER_* switch their callers read has a row here.
+COMPOSITE_ROUTES = [
+    ("composite_packet<N,32,false,false>", [
+        ("lean", "unlit", {}, "render"),
+        ("lean", "unlit", {"NTRACER_NUMERATORS": "0", "NTRACER_TILE_ORDER": "0"}, "render"),
+        ("lean", "unlit", {"NTRACER_STRICT_REFERENCE": "1"}, "render"),
+        ("lean", "lit", {}, "render"),
+        ("lean", "reflective", {}, "render"),
+        ("deep", "unlit", {}, "render"),            # stack_depth <= 32
+    ]),
+    ("packet_numerators<N>", [
+        ("lean", "unlit", {}, "render"),
+    ]),
+    ("composite_packet<N,32,true,false>", [
+        ("lean", "lit", {"NTRACER_TWO_PASS": "0"}, "render"),
+        ("lean", "reflective", {"NTRACER_TWO_PASS": "0"}, "render"),
+    ]),
+    ("composite_packet<N,32,false,true>", [
+        ("mixed", "lit", {"NTRACER_CLEAN_NORMALS": "1"}, "render"),
+    ]),
+    ("composite_kernel<N,true,false,false>", [
+        ("lean", "lit", {}, "render"),               # second pass of the two
+        ("lean", "reflective", {}, "render"),
+        ("lean", "lit", {"NTRACER_COMPOSITE_KERNEL": "2"}, "render"),
+        ("lean", "lit", {}, "colors_at"),
+        ("deep", "lit", {}, "render"),               # alone past stack_depth 32
+    ]),
+    ("composite_kernel<N,true,false>", [
+        ("mixed", "lit", {"NTRACER_CLEAN_NORMALS": "1"}, "render"),
+        ("mixed", "lit", {"NTRACER_CLEAN_NORMALS": "1", "NTRACER_COMPOSITE_KERNEL": "2"}, "render"),
+    ]),
+    ("composite_persistent<N>", [
+        ("lean", "unlit", {"NTRACER_COMPOSITE_KERNEL": "1"}, "render"),
+        ("deep", "unlit", {}, "render"),            # kernel choice 0 past stack_depth 32
+        ("deep", "unlit", {"NTRACER_COMPOSITE_KERNEL": "1"}, "render"),
+    ]),
+    ("composite_kernel<N,false,false>", [
+        ("lean", "unlit", {"NTRACER_COMPOSITE_KERNEL": "2"}, "render"),
+        ("lean", "unlit", {}, "colors_at"),
+        ("deep", "unlit", {"NTRACER_COMPOSITE_KERNEL": "2"}, "render"),
+    ]),
+    ("composite_kernel<N,true,true>", [
+        ("lean", "unlit", {}, "stats"),
+        ("mixed", "lit", {}, "stats"),              # the counting launch beside composite_kernel_t<N,true>
+    ]),
+    ("composite_kernel_t<N,true>", [
+        ("mixed", "lit", {}, "render"),             # Solids: the reference's normal aliasing
+        ("mixed", "lit", {}, "colors_at"),
+        ("lean", "transparent", {}, "render"),
+        ("lean", "transparent", {}, "colors_at"),
+        ("mixed", "transparent", {}, "render"),
+        ("deep", "transparent", {}, "render"),
+    ]),
+    ("composite_kernel_t<N,false>", [
+        ("lean", "transparent", {"NTRACER_CLEAN_NORMALS": "1"}, "render"),
+        ("mixed", "transparent", {"NTRACER_CLEAN_NORMALS": "1"}, "render"),
+    ]),
+    ("composite_kernel_var_t<true>", [
+        ("lean", "transparent_reflective", {}, "render"),     # max_reflect_depth 6: more frames than NT_TFRAMES
+        ("mixed", "lit", {"NTRACER_FORCE_VAR": "1"}, "render"),
+    ]),
+    ("composite_kernel_var_t<false>", [
+        ("lean", "transparent_reflective", {"NTRACER_CLEAN_NORMALS": "1"}, "render"),
+    ]),
+    ("composite_kernel_var", [
+        ("lean", "unlit", {"NTRACER_FORCE_VAR": "1"}, "render"),
+        ("mixed", "lit", {"NTRACER_FORCE_VAR": "1", "NTRACER_CLEAN_NORMALS": "1"}, "render"),
+    ]),
+]
+# the multi-frame launches of tests/test_composite_matrix.py (three frames through nt_render_frames_device at N = 6 and 9)
+COMPOSITE_FRAME_ENVS = [{}, {"NTRACER_CHUNK_FRAMES": "2"}, {"NTRACER_FRAME_MAJOR": "0"}]
+# stack_depth of the deep combs: around the packet kernel's 32-entry stack at every N, and beyond 64 KB of LDS at N >= 8
+# (launch_composite_fixed: 256 * (4 * stack_depth + 8 * N + 64) bytes)
+COMPOSITE_DEEP_DEPTHS = (31, 32, 33, 40)
+COMPOSITE_DEEP_DEPTHS_WIDE = (64,)          # N = 8..10
+COMPOSITE_MAX_DEPTH_N10 = 124               # 160 KiB at N = 10; one more is refused
+
+
+def composite_route_ways():
+    """the distinct (scene, params, env, mode) of COMPOSITE_ROUTES, in table order"""
+    seen, out = set(), []
+    for _, ways in COMPOSITE_ROUTES:
+        for scene, params, env, mode in ways:
+            key = (scene, params, tuple(sorted(env.items())), mode)
+            if key not in seen:
+                seen.add(key)
+                out.append((scene, params, dict(env), mode))
+    return out

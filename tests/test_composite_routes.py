@@ -1,0 +1,88 @@
+"""The kernel routes of tests/test_composite_matrix.py, pinned to the C++ that picks them: every hipLaunchKernelGGL of
+launch_composite_fixed<N> (nt_composite.hpp) and nt_launch_composite (nt_var.hip) must have a row in
+fixtures.COMPOSITE_ROUTES, and every NTRACER_* switch that enqueue (nt_api.cpp) and those two functions read must be set by
+one of its ways, so that a kernel variant or a switch added later without a matrix row fails here, without a GPU.  The two
+thresholds the deep-tree rows are built around are pinned as well."""
+import os
+import re
+
+import fixtures as fx
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
+
+
+def _read(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _body(src, head):
+    """the text of the function that starts with `head`, up to its closing brace in column 0"""
+    start = src.index(head)
+    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
+
+
+def _launches(body):
+    """instantiations launched in `body`, spaces dropped: `hipLaunchKernelGGL((name<...>), ...` or `hipLaunchKernelGGL(name, ...`"""
+    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
+    return {re.sub(r"\s+", "", n) for n in names}
+
+
+def _fixed():
+    return _body(_read("nt_composite.hpp"), "int launch_composite_fixed(")
+
+
+def _var():
+    return _body(_read("nt_var.hip"), "int nt_launch_composite(")
+
+
+def _enqueue():
+    """enqueue up to its composite launch (the box branch after it reads switches of its own)"""
+    src = _read("nt_api.cpp")
+    start = src.index("int enqueue(")
+    return src[start:src.index("r = nt_launch_composite(", start)]
+
+
+def test_every_composite_launch_has_a_matrix_row():
+    launched = _launches(_fixed()) | _launches(_var())
+    assert len(launched) >= 14, sorted(launched)            # the scan still finds the launches
+    rows = [k for k, _ in fx.COMPOSITE_ROUTES]
+    assert len(rows) == len(set(rows)), "duplicate rows"
+    assert set(rows) == launched, ("launched without a row: %s; rows nothing launches: %s"
+                                   % (sorted(launched - set(rows)), sorted(set(rows) - launched)))
+    for kernel, ways in fx.COMPOSITE_ROUTES:
+        assert ways, kernel
+        for scene, params, env, mode in ways:
+            assert scene in ("lean", "mixed", "deep"), (kernel, scene)
+            assert params in ("unlit", "lit", "reflective", "transparent", "transparent_reflective"), (kernel, params)
+            assert mode in ("render", "stats", "colors_at"), (kernel, mode)
+            assert all(k.startswith("NTRACER_") for k in env), (kernel, env)
+
+
+def test_every_composite_switch_is_set_by_a_row():
+    read = set(re.findall(r'getenv\("(NTRACER_\w+)"\)', _enqueue() + _fixed() + _var()))
+    read -= {s for s in read if s.startswith("NTRACER_BOX_")}      # BoxScene's (read before the scene kind is known)
+    assert {"NTRACER_COMPOSITE_KERNEL", "NTRACER_TWO_PASS", "NTRACER_FRAME_MAJOR"} <= read, sorted(read)
+    set_by_rows = {k for _, ways in fx.COMPOSITE_ROUTES for _, _, env, _ in ways for k in env}
+    set_by_rows |= {k for env in fx.COMPOSITE_FRAME_ENVS for k in env}
+    assert read <= set_by_rows, "switches no matrix row sets: %s" % sorted(read - set_by_rows)
+
+
+def test_the_thresholds_the_deep_rows_are_built_around():
+    fixed = _fixed()
+    # the packet kernel takes trees of stack_depth <= 32 only: its uniform stack has 32 entries and a 32-bit `bothbits`
+    assert re.search(r"li\.kernel_choice == 0 && sc\.stack_depth <= 32\)", fixed)
+    # (launched as composite_packet<N, 32, ...>: DEPTH = 32, pinned by the rows' names)
+    hpp = _read("nt_composite.hpp")
+    assert re.search(r"if \(m_far != 0ull && sp < DEPTH\)", hpp)
+    # the per-lane kernels' LDS: 256 lanes x (4 stack_depth + 8 N + 4 NT_MBOX) bytes, refused beyond 160 KiB
+    assert re.search(r"lds = \(size_t\)4 \* 64 \* \(\(size_t\)sc\.stack_depth \* 4 \+ \(size_t\)N \* 8 \+ \(size_t\)NT_MBOX \* 4\);", fixed)
+    assert re.search(r"if \(lds > 160 \* 1024\) \{\s*snprintf\([^;]*\"k-d tree too deep for the LDS traversal stack", fixed)
+    assert re.search(r"#define NT_MBOX 16\b", hpp)
+    # ... so the deepest tree that fits at N = 10 has stack_depth 124
+    n, sd = 10, fx.COMPOSITE_MAX_DEPTH_N10
+    assert 256 * (4 * sd + 8 * n + 64) == 160 * 1024
+    # and the deep depths straddle the packet kernel's limit; 64 passes 64 KB of LDS at N >= 8
+    assert min(fx.COMPOSITE_DEEP_DEPTHS) <= 31 and 32 in fx.COMPOSITE_DEEP_DEPTHS and 33 in fx.COMPOSITE_DEEP_DEPTHS
+    assert all(256 * (4 * sd + 8 * 8 + 64) > 64 * 1024 for sd in fx.COMPOSITE_DEEP_DEPTHS_WIDE)
