@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -585,7 +586,184 @@ struct FrameJob {
     int view_w = 0, view_h = 0;
 };
 
+// The NTRACER_* render switches, read once per enqueue and never cached: a process may change its
+// environment between calls.  Unset, a switch takes the default below; set, its value goes through atoi (empty: 0).
+struct RenderSwitches {
+    bool strict_reference, clean_normals, force_var, numerators, two_pass, tile_order, box_cull, box_interleave, box_var_rows;
+    int composite_kernel, frame_major, chunk_frames, box_path;
+};
+
+int atoi_or(const char *e, int unset) { return e ? atoi(e) : unset; }
+
+RenderSwitches read_switches() {
+    RenderSwitches sw;
+    sw.strict_reference = atoi_or(getenv("NTRACER_STRICT_REFERENCE"), 0) != 0;  // 1: the reference's exact k-d walk (nt_render_opts::strict_reference)
+    sw.clean_normals = atoi_or(getenv("NTRACER_CLEAN_NORMALS"), 0) != 0;        // 1: a hit keeps the normal of what was hit (changes pixels: DESIGN.md 2)
+    sw.force_var = atoi_or(getenv("NTRACER_FORCE_VAR"), 0) != 0;                // 1: the run-time-n kernels at every dimension, for tests to compare them
+    sw.composite_kernel = atoi_or(getenv("NTRACER_COMPOSITE_KERNEL"), 0);       // NtLaunchInfo::kernel_choice: 1 persistent, 2 plain per-lane kernel
+    sw.numerators = atoi_or(getenv("NTRACER_NUMERATORS"), 1) != 0;              // 0: no per-frame plane numerators for the packet kernel
+    sw.two_pass = atoi_or(getenv("NTRACER_TWO_PASS"), 1) != 0;                  // 0: lit scenes in one packet kernel
+    sw.tile_order = atoi_or(getenv("NTRACER_TILE_ORDER"), 1) != 0;              // 0: the packet kernel's quads in row-major order
+    sw.frame_major = atoi_or(getenv("NTRACER_FRAME_MAJOR"), 1);                 // 0: the frames of a multi-frame packet launch interleaved
+    sw.chunk_frames = atoi_or(getenv("NTRACER_CHUNK_FRAMES"), INT_MAX);         // (tests) at most max(k, 1) frames per packet launch; unset: no cap
+    sw.box_path = atoi_or(getenv("NTRACER_BOX_PATH"), 1);                       // 0: BoxScene's scripted formats through the cull / box / redo kernels
+    sw.box_cull = atoi_or(getenv("NTRACER_BOX_CULL"), 1) != 0;                  // 0: no stretch codes, every BoxScene format through the general kernel
+    sw.box_interleave = atoi_or(getenv("NTRACER_BOX_INTERLEAVE"), 1) != 0;      // 0: a tile-kernel wave renders consecutive rows
+    sw.box_var_rows = atoi_or(getenv("NTRACER_BOX_VAR_ROWS"), 1) != 0;          // 0: BoxScene at run-time n through the per-pixel kernel for every format
+    return sw;
+}
+
+// enqueue's CompositeScene half: the device scene, the `checked` and frame scratch of the faithful kernels, and the packet
+// kernel's counter, cameras, numerators, hit scratch and tile order
+int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, const NtTarget &tg,
+                   const NtCamera &cam, NtLaunchInfo &li, NtCompositeDev &c) {
+    fill_composite(s, ds, c, job.stats);
+    // closest-hit walks drop subtrees beyond the current hit unless the caller (or NTRACER_STRICT_REFERENCE=1)
+    // asks for the reference's exact walk; the pixels are the same (nt_beyond_hit in nt_composite.hpp)
+    // ... and never for scenes with Solids: trees from the reference's own builder leave solids out of some cells
+    // they reach (its goldens show it), i.e. they break the invariant the shortcut relies on
+    c.prune = (job.strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;
+    if (c.root < 0) c.root = -1;
+    // Scenes with transparent materials or Solids are rendered with the reference's own handling of o_hit.normal (its
+    // first leaf loop lets every primitive test write to the current hit's normal ray, tracer.hpp:1001,1020 -- see
+    // composite_kernel_t<N, true>), which needs the reference's exact `checked` list: a bitmap column per resident
+    // lane.  NTRACER_CLEAN_NORMALS=1 selects the intended semantics instead (a hit keeps the normal of what was hit).
+    const bool faithful = !job.counters_pass && (!s->all_opaque || (s->n_solids > 0 && !sw.clean_normals));
+    if (faithful) {
+        // (transparent materials need the exact list in either mode: the reference trims its transparent hits with the
+        // distance of the LAST test, so a repeated test is not harmless there)
+        // The compile-time-N kernel keeps NT_TFRAMES ray_color frames in registers/scratch; above NT_MAX_FIXED_DIM, and
+        // for reflection deeper than that among transparent things, the run-time-n kernel with its frames in global
+        // scratch takes over (one wave per block there).
+        const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
+        const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
+        const long long lpb = var_t ? 64 : 256;           // lanes per block
+        const long long tw = var_t ? 8 : 16;              // tile edge
+        const long long words = ((long long)s->n_batches + s->n_triangles + s->n_solids + 31) / 32;
+        const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
+        long long tiles = job.colors_out ? (job.probe_count + lpb - 1) / lpb
+                                         : (long long)((tg.width + tw - 1) / tw) * ((tg.row_count + tw - 1) / tw) * job.nframes;
+        long long blocks = std::min<long long>(std::max<long long>(tiles, 1), var_t ? 8192 : 4096);
+        while (blocks > 64 && blocks * lpb * (words + fwords) * 4 > ((long long)512 << 20)) blocks /= 2;
+        if (int e = ds->checked.ensure((size_t)(blocks * lpb * words * 4))) return e;
+        c.checked = (uint32_t *)ds->checked.p;
+        c.checked_words = (int)words;
+        c.checked_lanes = (int)(blocks * lpb);
+        c.alias_normals = sw.clean_normals ? 0 : 1;
+        if (var_t) {
+            if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
+            c.tframes = (float *)ds->tframes.p;
+            c.tframe_count = nframes_stack;
+        }
+    }
+    // image renders of opaque scenes made of batches go through the packet kernel (primary rays share the
+    // camera origin): it needs the camera table in device memory (and, for the persistent variant, a counter)
+    const bool packetable = c.all_opaque != 0 && !faithful;
+    if (packetable && !job.stats && !job.colors_out && s->n <= NT_MAX_FIXED_DIM && li.kernel_choice != 2) {
+        // persistent kernel: a zeroed work counter and the camera table in device memory (stream ordered)
+        if (int e = ds->counter.ensure(8)) return e;
+        HIP_TRY(hipMemsetAsync(ds->counter.p, 0, 8, job.stream));
+        li.persist_counter = ds->counter.p;
+        if (job.cam_buf) {
+            li.persist_cams = job.cam_buf;
+        } else {
+            if (int e = ds->cams.ensure(sizeof(float) * 4 * s->n)) return e;
+            HIP_TRY(hipMemcpyAsync(ds->cams.p, cam.inl, sizeof(float) * 4 * s->n, hipMemcpyHostToDevice, job.stream));
+            li.persist_cams = (const float *)ds->cams.p;
+        }
+    }
+    if (li.persist_cams && !tg.colors_out && s->n_batches > 0 && sw.numerators) {
+        // plane numerators of the packet kernel: as many frames as fit in 256 MB, at least one
+        const size_t per_frame = (size_t)s->n_batches * NT_BATCH_SIZE * sizeof(float);
+        const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)256 << 20) / per_frame));
+        if (int e = ds->numer.ensure(frames * per_frame)) return e;
+        li.numer_buf = (float *)ds->numer.p;
+        li.numer_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+    }
+    const bool lit = !s->pl_color.empty() || !s->gl_color.empty() || c.any_reflective || c.has_scalar_prims;
+    if (li.persist_cams && !tg.colors_out && lit && sw.two_pass) {
+        // scratch for the primary hits of a two-pass render: as many frames as fit in 512 MB, at least one
+        const size_t per_frame = (size_t)16 * tg.width * tg.row_count;
+        size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / std::max<size_t>(per_frame, 1)));
+        if (int e = ds->hits.ensure(frames * per_frame)) return e;
+        li.hit_buf = ds->hits.p;
+        li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+    }
+    if (li.persist_cams && !tg.colors_out && sw.tile_order) {
+        // dispatch order of the packet kernel's quads (2x2 tiles of 8x8 pixels): the waves that walk the middle
+        // of the scene run longest, so the quad rows nearest the centre go first; row-major within a row keeps
+        // neighbouring blocks on neighbouring rays
+        const int tx = ((tg.width + 7) / 8 + 1) / 2, ty = ((tg.row_count + 7) / 8 + 1) / 2;
+        DeviceState::TileOrder *to = nullptr;
+        for (auto &e : ds->tile_orders)
+            if (e->tx == tx && e->ty == ty) to = e.get();
+        if (!to) {
+            std::vector<int> order((size_t)tx * ty);
+            for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+            auto key = [&](int t) {
+                const long long dy = 2 * (t / tx) - (ty - 1);
+                return dy < 0 ? -dy : dy;
+            };
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
+            if (ds->tile_orders.size() >= 16) {
+                // tables may still be read by launches queued on other streams
+                HIP_TRY(hipDeviceSynchronize());
+                for (auto &e : ds->tile_orders) e->buf.release();
+                ds->tile_orders.clear();
+            }
+            std::unique_ptr<DeviceState::TileOrder> e(new DeviceState::TileOrder);
+            if (int err = e->buf.ensure(order.size() * sizeof(int))) return err;
+            HIP_TRY(hipMemcpy(e->buf.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+            e->tx = tx;
+            e->ty = ty;
+            to = e.get();
+            ds->tile_orders.push_back(std::move(e));
+        }
+        li.tile_order = (const int *)to->buf.p;
+    }
+    return NT_OK;
+}
+
+// enqueue's BoxScene half: the cull buffer, whether the fused tile kernel takes the launch, its block shape and row table
+int plan_box(const nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, NtTarget &tg, NtLaunchInfo &li) {
+    if (tg.colors_out || !sw.box_cull) return NT_OK;
+    // one bit per 64-pixel stretch of a row: can any of its rays reach the cube? (box_cull_kernel)
+    const size_t words = (size_t)(((tg.width + 63) / 64 + 31) / 32);
+    // stretch codes (4 words per redo word), 16 rows of padding (box_kernel reads a wave's rows without
+    // clamping), redo bits
+    const size_t need = ((size_t)5 * job.nframes * tg.row_count + 64) * words * sizeof(uint32_t);
+    if (need > ds->cull.cap || !ds->cull.p) ds->cull_clean = false;
+    if (int e = ds->cull.ensure(need)) return e;
+    // The fused kernels keep their redo bitmap at the start of this buffer and leave it zeroed; after anything else
+    // has written there (a fresh allocation, the cull / box / redo kernels) it is zeroed here, in stream order.
+    // (the formats launch_box_fixed sends there: plain RGB of <= 10 bits in one aligned dword, or three plain fp32 channels)
+    const bool fused = li.box_path != 0 && s->n <= NT_MAX_FIXED_BOX_DIM && tg.aligned4 &&
+                       ((tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4) || (tg.plain_f32[0] >= 0 && tg.bpp == 12));
+    if (fused && !ds->cull_clean) {
+        HIP_TRY(hipMemsetAsync(ds->cull.p, 0, ds->cull.cap, job.stream));
+        ds->cull_clean = true;
+    } else if (!fused) {
+        ds->cull_clean = false;
+    }
+    li.cull_clean = fused ? 1 : 0;
+    li.cull_buf = (uint32_t *)ds->cull.p;
+    if (fused) {
+        // interleaved rows (the default for launches that start at their first owned row; NTRACER_BOX_INTERLEAVE=0: A/B):
+        // the waves of a column strip deal the rows out among themselves, so that the rows that need ray-by-ray work --
+        // which come in runs of dozens -- are spread over all of them instead of making a few waves ten times as long as
+        // the rest
+        const NtBoxTileGeom geom = nt_box_tile_geom(tg.width, tg.row_count, job.nframes, job.overlapped);
+        li.tile_rows = geom.rows;
+        li.tile_waves = geom.waves;
+        const int tile_rows = geom.rows * geom.waves;
+        tg.row_il = (tg.row_begin == 0 && sw.box_interleave) ? (tg.row_count + tile_rows - 1) / tile_rows * geom.waves : 0;
+        if (int e = row_table(ds, tg, geom.rows, tg.rowtab)) return e;
+    }
+    return NT_OK;
+}
+
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
+    const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
     if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
         // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
@@ -594,11 +772,9 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
         // was hit, 16-slot mailbox) into a scratch frame.  They describe THAT traversal: the same tree and cells, a few
         // repeated tests after mailbox evictions.  Transparent materials have no counting kernel at all: refused.
         if (s->n > NT_MAX_FIXED_DIM) return fail(NT_E_UNSUPPORTED, "collect_stats is not available above %d dimensions (the run-time-n kernels keep no counters)", NT_MAX_FIXED_DIM);
-        const char *ecl0 = getenv("NTRACER_CLEAN_NORMALS");
-        const bool clean0 = ecl0 && atoi(ecl0) != 0;
         if (!s->all_opaque)
             return fail(NT_E_UNSUPPORTED, "collect_stats is not available for scenes with transparent materials (their kernels keep no counters)");
-        if (s->n_solids > 0 && !clean0) {
+        if (s->n_solids > 0 && !sw.clean_normals) {
             const size_t bytes = (size_t)job.fmt->pitch * (size_t)(job.bands.compact ? job.bands.owned_rows : job.fmt->height);
             if (int e = ds->stats_frame.ensure(std::max<size_t>(bytes, 16))) return e;
             FrameJob cj = job;
@@ -667,183 +843,23 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     cam.n = s->n;
     if (!job.cam_buf) pack_camera(s->n, s->origin.data(), s->axes.data(), cam.inl);
     camera_dots(s->n, s->origin.data(), s->axes.data(), cam.odots);
-    NtLaunchInfo li;
+    NtLaunchInfo li{};
     li.n = s->n;
     li.nframes = job.nframes;
     li.stream = job.stream;
-    li.persist_counter = nullptr;
-    li.persist_cams = nullptr;
     li.cu_count = ds->cu_count;
-    li.kernel_choice = 0;
-    li.tile_order = nullptr;
-    li.hit_buf = nullptr;
-    li.hit_frames = 0;
-    li.numer_buf = nullptr;
-    li.numer_frames = 0;
-    li.cull_buf = nullptr;
-    li.tie_buf = nullptr;
-    li.cull_clean = 0;
-    li.tile_rows = 0;
-    li.tile_waves = 0;
-    li.box_path = 1;
-    if (const char *bp = getenv("NTRACER_BOX_PATH")) li.box_path = atoi(bp);
-    if (const char *kc = getenv("NTRACER_COMPOSITE_KERNEL")) li.kernel_choice = atoi(kc);
+    li.kernel_choice = sw.composite_kernel;
+    li.box_path = sw.box_path;
+    li.frame_major = sw.frame_major;
+    li.force_var = sw.force_var;
+    li.box_var_rows = sw.box_var_rows;
     int r;
     if (s->composite) {
         NtCompositeDev c;
-        fill_composite(s, ds, c, job.stats);
-        // closest-hit walks drop subtrees beyond the current hit unless the caller (or NTRACER_STRICT_REFERENCE=1)
-        // asks for the reference's exact walk; the pixels are the same (nt_beyond_hit in nt_composite.hpp)
-        const char *es = getenv("NTRACER_STRICT_REFERENCE");
-        const bool env_strict = es && atoi(es) != 0;
-        // ... and never for scenes with Solids: trees from the reference's own builder leave solids out of some cells
-        // they reach (its goldens show it), i.e. they break the invariant the shortcut relies on
-        c.prune = (job.strict || env_strict || s->n_solids > 0) ? 0 : 1;
-        if (c.root < 0) c.root = -1;
-        // Scenes with transparent materials or Solids are rendered with the reference's own handling of o_hit.normal (its
-        // first leaf loop lets every primitive test write to the current hit's normal ray, tracer.hpp:1001,1020 -- see
-        // composite_kernel_t<N, true>), which needs the reference's exact `checked` list: a bitmap column per resident
-        // lane.  NTRACER_CLEAN_NORMALS=1 selects the intended semantics instead (a hit keeps the normal of what was hit).
-        const char *ecl = getenv("NTRACER_CLEAN_NORMALS");
-        const bool clean = ecl && atoi(ecl) != 0;
-        const bool faithful = !job.counters_pass && (!s->all_opaque || (s->n_solids > 0 && !clean));
-        if (faithful) {
-            // (transparent materials need the exact list in either mode: the reference trims its transparent hits with the
-            // distance of the LAST test, so a repeated test is not harmless there)
-            // The compile-time-N kernel keeps NT_TFRAMES ray_color frames in registers/scratch; above NT_MAX_FIXED_DIM, and
-            // for reflection deeper than that among transparent things, the run-time-n kernel with its frames in global
-            // scratch takes over (one wave per block there).
-            const char *efv = getenv("NTRACER_FORCE_VAR");
-            const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
-            const bool var_t = s->n > NT_MAX_FIXED_DIM || (efv && atoi(efv) != 0) || nframes_stack > 6;
-            const long long lpb = var_t ? 64 : 256;           // lanes per block
-            const long long tw = var_t ? 8 : 16;              // tile edge
-            const long long words = ((long long)s->n_batches + s->n_triangles + s->n_solids + 31) / 32;
-            const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
-            long long tiles = job.colors_out ? (job.probe_count + lpb - 1) / lpb
-                                             : (long long)((tg.width + tw - 1) / tw) * ((tg.row_count + tw - 1) / tw) * job.nframes;
-            long long blocks = std::min<long long>(std::max<long long>(tiles, 1), var_t ? 8192 : 4096);
-            while (blocks > 64 && blocks * lpb * (words + fwords) * 4 > ((long long)512 << 20)) blocks /= 2;
-            if (int e = ds->checked.ensure((size_t)(blocks * lpb * words * 4))) return e;
-            c.checked = (uint32_t *)ds->checked.p;
-            c.checked_words = (int)words;
-            c.checked_lanes = (int)(blocks * lpb);
-            c.alias_normals = clean ? 0 : 1;
-            if (var_t) {
-                if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
-                c.tframes = (float *)ds->tframes.p;
-                c.tframe_count = nframes_stack;
-            }
-        }
-        // image renders of opaque scenes made of batches go through the packet kernel (primary rays share the
-        // camera origin): it needs the camera table in device memory (and, for the persistent variant, a counter)
-        const bool packetable = c.all_opaque != 0 && !faithful;
-        if (packetable && !job.stats && !job.colors_out && s->n <= NT_MAX_FIXED_DIM && li.kernel_choice != 2) {
-            // persistent kernel: a zeroed work counter and the camera table in device memory (stream ordered)
-            if (int e = ds->counter.ensure(8)) return e;
-            HIP_TRY(hipMemsetAsync(ds->counter.p, 0, 8, job.stream));
-            li.persist_counter = ds->counter.p;
-            if (job.cam_buf) {
-                li.persist_cams = job.cam_buf;
-            } else {
-                if (int e = ds->cams.ensure(sizeof(float) * 4 * s->n)) return e;
-                HIP_TRY(hipMemcpyAsync(ds->cams.p, cam.inl, sizeof(float) * 4 * s->n, hipMemcpyHostToDevice, job.stream));
-                li.persist_cams = (const float *)ds->cams.p;
-            }
-        }
-        const char *enum_ = getenv("NTRACER_NUMERATORS");
-        if (li.persist_cams && !tg.colors_out && s->n_batches > 0 && !(enum_ && atoi(enum_) == 0)) {
-            // plane numerators of the packet kernel: as many frames as fit in 256 MB, at least one
-            const size_t per_frame = (size_t)s->n_batches * NT_BATCH_SIZE * sizeof(float);
-            const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)256 << 20) / per_frame));
-            if (int e = ds->numer.ensure(frames * per_frame)) return e;
-            li.numer_buf = (float *)ds->numer.p;
-            li.numer_frames = (int)frames;
-            if (const char *cf = getenv("NTRACER_CHUNK_FRAMES")) li.numer_frames = std::max(1, std::min(li.numer_frames, atoi(cf)));   // tests
-        }
-        const bool lit = !s->pl_color.empty() || !s->gl_color.empty() || c.any_reflective || c.has_scalar_prims;
-        const char *e2p = getenv("NTRACER_TWO_PASS");
-        if (li.persist_cams && !tg.colors_out && lit && !(e2p && atoi(e2p) == 0)) {
-            // scratch for the primary hits of a two-pass render: as many frames as fit in 512 MB, at least one
-            const size_t per_frame = (size_t)16 * tg.width * tg.row_count;
-            size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / std::max<size_t>(per_frame, 1)));
-            if (int e = ds->hits.ensure(frames * per_frame)) return e;
-            li.hit_buf = ds->hits.p;
-            li.hit_frames = (int)frames;
-            if (const char *cf = getenv("NTRACER_CHUNK_FRAMES")) li.hit_frames = std::max(1, std::min(li.hit_frames, atoi(cf)));
-        }
-        const char *eto = getenv("NTRACER_TILE_ORDER");
-        if (li.persist_cams && !tg.colors_out && !(eto && atoi(eto) == 0)) {
-            // dispatch order of the packet kernel's quads (2x2 tiles of 8x8 pixels): the waves that walk the middle
-            // of the scene run longest, so the quad rows nearest the centre go first; row-major within a row keeps
-            // neighbouring blocks on neighbouring rays
-            const int tx = ((tg.width + 7) / 8 + 1) / 2, ty = ((tg.row_count + 7) / 8 + 1) / 2;
-            DeviceState::TileOrder *to = nullptr;
-            for (auto &e : ds->tile_orders)
-                if (e->tx == tx && e->ty == ty) to = e.get();
-            if (!to) {
-                std::vector<int> order((size_t)tx * ty);
-                for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-                auto key = [&](int t) {
-                    const long long dy = 2 * (t / tx) - (ty - 1);
-                    return dy < 0 ? -dy : dy;
-                };
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
-                if (ds->tile_orders.size() >= 16) {
-                    // tables may still be read by launches queued on other streams
-                    HIP_TRY(hipDeviceSynchronize());
-                    for (auto &e : ds->tile_orders) e->buf.release();
-                    ds->tile_orders.clear();
-                }
-                std::unique_ptr<DeviceState::TileOrder> e(new DeviceState::TileOrder);
-                if (int err = e->buf.ensure(order.size() * sizeof(int))) return err;
-                HIP_TRY(hipMemcpy(e->buf.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
-                e->tx = tx;
-                e->ty = ty;
-                to = e.get();
-                ds->tile_orders.push_back(std::move(e));
-            }
-            li.tile_order = (const int *)to->buf.p;
-        }
+        if (int e = plan_composite(s, ds, job, sw, tg, cam, li, c)) return e;
         r = nt_launch_composite(li, cam, c, tg);
     } else {
-        const char *ec = getenv("NTRACER_BOX_CULL");
-        if (!tg.colors_out && !(ec && atoi(ec) == 0)) {
-            // one bit per 64-pixel stretch of a row: can any of its rays reach the cube? (box_cull_kernel)
-            const size_t words = (size_t)(((tg.width + 63) / 64 + 31) / 32);
-            // stretch codes (4 words per redo word), 16 rows of padding (box_kernel reads a wave's rows without
-            // clamping), redo bits
-            const size_t need = ((size_t)5 * job.nframes * tg.row_count + 64) * words * sizeof(uint32_t);
-            if (need > ds->cull.cap || !ds->cull.p) ds->cull_clean = false;
-            if (int e = ds->cull.ensure(need)) return e;
-            // The fused kernels keep their redo bitmap at the start of this buffer and leave it zeroed; after anything else
-            // has written there (a fresh allocation, the cull / box / redo kernels) it is zeroed here, in stream order.
-            // (the formats launch_box_fixed sends there: plain RGB of <= 10 bits in one aligned dword, or three plain fp32 channels)
-            const bool fused = li.box_path != 0 && s->n <= NT_MAX_FIXED_BOX_DIM && tg.aligned4 &&
-                               ((tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4) || (tg.plain_f32[0] >= 0 && tg.bpp == 12));
-            if (fused && !ds->cull_clean) {
-                HIP_TRY(hipMemsetAsync(ds->cull.p, 0, ds->cull.cap, job.stream));
-                ds->cull_clean = true;
-            } else if (!fused) {
-                ds->cull_clean = false;
-            }
-            li.cull_clean = fused ? 1 : 0;
-            li.cull_buf = (uint32_t *)ds->cull.p;
-            if (fused) {
-                // interleaved rows (the default for launches that start at their first owned row; NTRACER_BOX_INTERLEAVE=0: A/B):
-                // the waves of a column strip deal the rows out among themselves, so that the rows that need ray-by-ray work --
-                // which come in runs of dozens -- are spread over all of them instead of making a few waves ten times as long as
-                // the rest
-                const NtBoxTileGeom geom = nt_box_tile_geom(tg.width, tg.row_count, job.nframes, job.overlapped);
-                li.tile_rows = geom.rows;
-                li.tile_waves = geom.waves;
-                const char *eil = getenv("NTRACER_BOX_INTERLEAVE");
-                const int tile_rows = geom.rows * geom.waves;
-                tg.row_il = (tg.row_begin == 0 && !(eil && atoi(eil) == 0)) ? (tg.row_count + tile_rows - 1) / tile_rows * geom.waves : 0;
-                if (int e = row_table(ds, tg, geom.rows, tg.rowtab)) return e;
-                li.tie_buf = nullptr;               // (round 2's end: the tie sets never leave the tile kernel)
-            }
-        }
+        if (int e = plan_box(s, ds, job, sw, tg, li)) return e;
         r = nt_launch_box(li, cam, tg);
     }
     if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
@@ -1264,23 +1280,11 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     // a camera table that earlier launches may still read must not be overwritten: grow-only buffer,
     // refilled only after the stream that used it has drained (same-stream ordering)
     if (int r = ds->cams.ensure(cam_floats * sizeof(float))) return r;
-    {
-        // NTRACER_CAM_UPLOAD: "kernel" (default) a copy kernel on the launch stream reading the pinned slot in place;
-        // "memcpy" hipMemcpyAsync (copy engine)
-        const char *eu = getenv("NTRACER_CAM_UPLOAD");
-        if (eu && eu[0] == 'm') {
-            HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, cam_floats * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)hip_stream));
-        } else if (nt_launch_upload(hip_stream, packed, (float *)ds->cams.p, (int)cam_floats)) {
-            return fail(NT_E_DEVICE, "%s", nt_launch_error());
-        }
-    }
-    {
-        const char *ese = getenv("NTRACER_STAGE_EVENT");     // (experiment: 0 = no event behind the upload; unsafe beyond 8 calls in flight)
-        if (!(ese && atoi(ese) == 0)) {
-            HIP_TRY(hipEventRecord(st->done, (hipStream_t)hip_stream));
-            st->in_flight = true;
-        }
-    }
+    // a copy kernel on the launch stream reads the pinned slot in place; the event keeps the slot from reuse until it has
+    // (removed: NTRACER_CAM_UPLOAD=memcpy, and NTRACER_STAGE_EVENT=0, which skipped the event: unsafe beyond 8 calls in flight)
+    if (nt_launch_upload(hip_stream, packed, (float *)ds->cams.p, (int)cam_floats)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+    HIP_TRY(hipEventRecord(st->done, (hipStream_t)hip_stream));
+    st->in_flight = true;
     const bool stats = opts && opts->collect_stats;
     if (int r = prepare_stats(ds, (hipStream_t)hip_stream, stats)) return r;
     if (stats) { s->have_stats = false; s->stats_device = dev; }

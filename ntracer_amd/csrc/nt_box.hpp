@@ -1447,16 +1447,16 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
         tg.lead_frames = li.nframes >= 8 ? (li.nframes < 96 ? li.nframes : 96) : 0;
         // ... with interleaved rows (round 3) a strip's waves are all alike and little is left for the lead to do: 160-frame call
         // 358 us without, 347 with 32, 354 with 96; 32- / 64- / 320-frame calls 1-2 % better with 8..16 than without and than
-        // with more; sixteen 4096 x 4096 frames of BoxScene(10) 3 % WORSE with 16 than without (tools/il_ab.py --var NTRACER_BOX_LEAD)
+        // with more; sixteen 4096 x 4096 frames of BoxScene(10) 3 % WORSE with 16 than without (measured with the NTRACER_BOX_LEAD
+        // override, since removed)
         if (tg.row_il > 0) tg.lead_frames = li.nframes >= 32 ? 16 : 0;
-        if (const char *e = getenv("NTRACER_BOX_LEAD")) tg.lead_frames = atoi(e) > 0 && li.nframes > 1 ? atoi(e) : 0;        // (A/B)
         if ((long long)li.nframes + tg.lead_frames > 65535) tg.lead_frames = 0;        // (grid z)
         tgrid.z += (unsigned)tg.lead_frames;
         // few rows in flight: two waves per redo word
         const long long rwords = (long long)tg.row_count * li.nframes * tg.redo_words;
-        int split = rwords < 48 * 1024 ? 2 : 1;                 // (87k words: one wave 3 % faster; 44k: even; 22k: two waves 2 % faster;
-                                                                //  four waves a word measured slower than two)
-        if (const char *e = getenv("NTRACER_BOX_SPLIT")) split = atoi(e) == 2 ? 2 : 1;        // (A/B)
+        const int split = rwords < 48 * 1024 ? 2 : 1;           // (87k words: one wave 3 % faster; 44k: even; 22k: two waves 2 % faster;
+                                                                //  four waves a word measured slower than two; NTRACER_BOX_SPLIT,
+                                                                //  the override these were measured with, has been removed)
         const int rpb = 4 / split;              // rows per block
         const dim3 rgrid((unsigned)tg.redo_words, (unsigned)((tg.row_count + rpb - 1) / rpb), (unsigned)li.nframes);
         if (fmt_rgb) {

@@ -2226,7 +2226,7 @@ int launch_composite_fixed(const NtLaunchInfo &li, const NtCamera &cam, const Nt
         pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
         pk.nframes = li.nframes;
         pk.order = li.tile_order;
-        pk.frame_major = getenv("NTRACER_FRAME_MAJOR") ? atoi(getenv("NTRACER_FRAME_MAJOR")) : 1;
+        pk.frame_major = li.frame_major;
         pk.hits_out = nullptr;
         pk.numer = nullptr;
         pk.n_batches = sc.n_batches;

@@ -2,7 +2,6 @@
 // (nt_box.hpp, nt_composite.hpp, nt_var.hip).  gfx950 only.
 #pragma once
 #include <stdint.h>
-#include <stdlib.h>
 
 #define NT_DEV_MAX_DIM 64
 #define NT_DEV_MAX_FIXED 10
@@ -175,7 +174,9 @@ struct NtLaunchInfo {
     int tile_rows, tile_waves; // BoxScene, fused path: box_tile_kernel's block shape (nt_box_tile_geom; the row table follows it)
     int box_path;             // BoxScene: 1 = fused tile kernel for the scripted formats (default), 0 = cull / box / redo kernels
     int cull_clean;           // cull_buf is all zero (the fused path's redo bitmap lives at its start)
-    uint32_t *tie_buf;        // BoxScene: scratch for the tie sets of the fused path, nframes * row_count * ceil(width/64) dwords (or nullptr)
+    int frame_major;          // packet kernel: PacketArgs::frame_major (0: the frames of a multi-frame launch interleaved)
+    int force_var;            // the run-time-n kernels at every dimension
+    int box_var_rows;         // BoxScene, run-time n: box_rows_kernel_var for packed RGB (0: box_kernel_var for every format)
     uint32_t *cull_buf;       // BoxScene: scratch for the row culling bits, 5 * nframes * row_count * ceil(ceil(width/64)/32) dwords: stretch codes, then redo bits (or nullptr)
 };
 
@@ -199,7 +200,6 @@ static inline NtBoxTileGeom nt_box_tile_geom(int width, int row_count, int nfram
     const long long waves64 = cols * ((row_count + 63) / 64) * nframes;
     bool r64 = r16 && row_count >= 512 && waves64 >= 32 * 1024;
     if (overlapped && r16 && row_count >= 64 && waves64 >= 8 * 1024) r64 = true;
-    if (const char *e = getenv("NTRACER_BOX_R64")) r64 = r16 && atoi(e) != 0;        // (A/B)
     NtBoxTileGeom g;
     g.rows = r64 ? 64 : (r16 ? 16 : 8);
     g.waves = r64 ? 1 : wpb;

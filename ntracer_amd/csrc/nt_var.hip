@@ -1585,15 +1585,8 @@ int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int coun
     return finish_launch("camera upload");
 }
 
-// NTRACER_FORCE_VAR=1: use the run-time-n kernels for every dimension (they are the only ones above
-// NT_DEV_MAX_FIXED; the switch lets tests compare them with the compile-time-N kernels on the same scene)
-static bool force_var() {
-    const char *e = getenv("NTRACER_FORCE_VAR");
-    return e && atoi(e) != 0;
-}
-
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg) {
-    switch (force_var() ? 0 : li.n) {
+    switch (li.force_var ? 0 : li.n) {
         case 3: nt_box_fixed_3(li, cam, tg); break;
         case 4: nt_box_fixed_4(li, cam, tg); break;
         case 5: nt_box_fixed_5(li, cam, tg); break;
@@ -1619,9 +1612,8 @@ int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &t
         default: {
             // packed plain RGB of <= 10 bits in one aligned dword: the rows kernel (codes + lean loops), if its n-vectors fit LDS
             const size_t lds_rows = ((size_t)li.n * 256 + (size_t)4 * li.n + 4) * sizeof(float);
-            const char *er = getenv("NTRACER_BOX_VAR_ROWS");
             if (!tg.colors_out && tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4 && tg.aligned4 && lds_rows <= 160 * 1024 &&
-                !(er && atoi(er) == 0)) {
+                li.box_var_rows) {
                 const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.row_count + 31) / 32), (unsigned)li.nframes);
                 if (lds_rows > 64 * 1024)
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(box_rows_kernel_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows);
@@ -1669,7 +1661,7 @@ int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCom
         }
         return finish_launch("composite kernel launch");
     }
-    switch (force_var() ? 0 : li.n) {
+    switch (li.force_var ? 0 : li.n) {
         case 3: r = nt_composite_fixed_3(li, cam, sc, tg); break;
         case 4: r = nt_composite_fixed_4(li, cam, sc, tg); break;
         case 5: r = nt_composite_fixed_5(li, cam, sc, tg); break;

@@ -165,7 +165,7 @@ def diagonal_camera(n, dist, rng):
 # (scene, parameter set, NTRACER_* switches, mode).  Scenes: "lean" (the N-orthoplex in batches), "mixed" (the same with four
 # loose triangles, a cube and a sphere), "deep" (hand-built combs of stack_depth 31, 32, 33, 40, ...).  Modes: "render" (a
 # 97 x 61 RGBF32 frame), "stats" (collect_stats=True) and "colors_at" (a pixel lattice).  tests/test_composite_routes.py
-# checks, without a GPU, that every launch of the two functions and every NTRACER_* switch their callers read has a row here.
+# checks, without a GPU, that every launch of the two functions and every non-BoxScene NTRACER_* switch has a row here.
 COMPOSITE_ROUTES = [
     ("composite_packet<N,32,false,false>", [
         ("lean", "unlit", {}, "render"),

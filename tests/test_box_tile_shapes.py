@@ -31,8 +31,7 @@ def test_box_tile_shapes_land_on_the_intended_block_shapes_and_splits(tmp_path):
                            os.path.join(ROOT, "tests", "box_tile_geom_probe.cpp"), "-o", exe])
     rows = _rows()
     args = [str(v) for _, w, r, f, _, _ in rows for v in (w, r, f)]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("NTRACER_")}    # (NTRACER_BOX_R64 overrides the rule)
-    out = subprocess.check_output([exe] + args, env=env).decode().split("\n")
+    out = subprocess.check_output([exe] + args).decode().split("\n")
     got = [tuple(int(v) for v in line.split()) for line in out if line.strip()]
     assert got == [geom for _, _, _, _, geom, _ in rows], list(zip([r[0] for r in rows], got))
     for label, w, r, f, _, split in rows:

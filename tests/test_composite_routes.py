@@ -1,8 +1,8 @@
 """The kernel routes of tests/test_composite_matrix.py, pinned to the C++ that picks them: every hipLaunchKernelGGL of
 launch_composite_fixed<N> (nt_composite.hpp) and nt_launch_composite (nt_var.hip) must have a row in
-fixtures.COMPOSITE_ROUTES, and every NTRACER_* switch that enqueue (nt_api.cpp) and those two functions read must be set by
-one of its ways, so that a kernel variant or a switch added later without a matrix row fails here, without a GPU.  The two
-thresholds the deep-tree rows are built around are pinned as well."""
+fixtures.COMPOSITE_ROUTES, and every NTRACER_* switch that read_switches (nt_api.cpp, the one place the render switches are
+read) reads must be set by one of its ways, so that a kernel variant or a switch added later without a matrix row fails here,
+without a GPU.  The two thresholds the deep-tree rows are built around are pinned as well."""
 import os
 import re
 
@@ -37,11 +37,8 @@ def _var():
     return _body(_read("nt_var.hip"), "int nt_launch_composite(")
 
 
-def _enqueue():
-    """enqueue up to its composite launch (the box branch after it reads switches of its own)"""
-    src = _read("nt_api.cpp")
-    start = src.index("int enqueue(")
-    return src[start:src.index("r = nt_launch_composite(", start)]
+def _reader():
+    return _body(_read("nt_api.cpp"), "RenderSwitches read_switches(")
 
 
 def test_every_composite_launch_has_a_matrix_row():
@@ -60,13 +57,24 @@ def test_every_composite_launch_has_a_matrix_row():
             assert all(k.startswith("NTRACER_") for k in env), (kernel, env)
 
 
-def test_every_composite_switch_is_set_by_a_row():
-    read = set(re.findall(r'getenv\("(NTRACER_\w+)"\)', _enqueue() + _fixed() + _var()))
+def test_every_composite_switch_the_reader_or_launchers_read_is_set_by_a_row():
+    read = set(re.findall(r'getenv\("(NTRACER_\w+)"\)', _reader() + _fixed() + _var()))
     read -= {s for s in read if s.startswith("NTRACER_BOX_")}      # BoxScene's (read before the scene kind is known)
     assert {"NTRACER_COMPOSITE_KERNEL", "NTRACER_TWO_PASS", "NTRACER_FRAME_MAJOR"} <= read, sorted(read)
     set_by_rows = {k for _, ways in fx.COMPOSITE_ROUTES for _, _, env, _ in ways for k in env}
     set_by_rows |= {k for env in fx.COMPOSITE_FRAME_ENVS for k in env}
     assert read <= set_by_rows, "switches no matrix row sets: %s" % sorted(read - set_by_rows)
+
+
+def test_render_switches_are_read_only_by_the_reader():
+    """read_switches is the one place the render switches are read: no other code in csrc calls getenv, except the k-d
+    builder for NTRACER_BUILD_THREADS (not a render switch)"""
+    reader = re.findall(r"\bgetenv\s*\(([^)]*)\)", _reader())
+    assert len(reader) >= 13 and all(re.fullmatch(r'"NTRACER_\w+"', a) for a in reader), reader
+    for name in sorted(os.listdir(CSRC)):
+        calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", _read(name))
+        want = {"nt_api.cpp": reader, "nt_builder.cpp": ['"NTRACER_BUILD_THREADS"']}.get(name, [])
+        assert calls == want, (name, calls)
 
 
 def test_the_thresholds_the_deep_rows_are_built_around():

@@ -18,4 +18,4 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 g = np.load(os.path.join(ROOT, "tests", "golden", "box_n10_4096x4096.npz"))
 fmt = ntracer_amd.ImageFormat(4096, 4096, [ntracer_amd.Channel(*c) for c in bench.RGBX8])
 ms = bench._time_frames(torch, _lib, tracern.BoxScene(10), fmt, g["origins"], g["axes"], frames, reps) / frames
-print("BoxScene(10) 4096x4096, %d frames a call: %.3f ms/frame = %.1f Grays/s (NTRACER_BOX_R64=%s)" % (frames, ms, 4096 * 4096 / ms / 1e6, os.environ.get("NTRACER_BOX_R64", "-")))
+print("BoxScene(10) 4096x4096, %d frames a call: %.3f ms/frame = %.1f Grays/s" % (frames, ms, 4096 * 4096 / ms / 1e6))
