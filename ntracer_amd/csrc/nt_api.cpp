@@ -590,7 +590,7 @@ struct FrameJob {
 // environment between calls.  Unset, a switch takes the default below; set, its value goes through atoi (empty: 0).
 struct RenderSwitches {
     bool strict_reference, clean_normals, force_var, numerators, two_pass, tile_order, box_cull, box_interleave, box_var_rows;
-    int composite_kernel, frame_major, chunk_frames, box_path;
+    int composite_kernel, frame_major, chunk_frames;
 };
 
 int atoi_or(const char *e, int unset) { return e ? atoi(e) : unset; }
@@ -606,7 +606,6 @@ RenderSwitches read_switches() {
     sw.tile_order = atoi_or(getenv("NTRACER_TILE_ORDER"), 1) != 0;              // 0: the packet kernel's quads in row-major order
     sw.frame_major = atoi_or(getenv("NTRACER_FRAME_MAJOR"), 1);                 // 0: the frames of a multi-frame packet launch interleaved
     sw.chunk_frames = atoi_or(getenv("NTRACER_CHUNK_FRAMES"), INT_MAX);         // (tests) at most max(k, 1) frames per packet launch; unset: no cap
-    sw.box_path = atoi_or(getenv("NTRACER_BOX_PATH"), 1);                       // 0: BoxScene's scripted formats through the cull / box / redo kernels
     sw.box_cull = atoi_or(getenv("NTRACER_BOX_CULL"), 1) != 0;                  // 0: no stretch codes, every BoxScene format through the general kernel
     sw.box_interleave = atoi_or(getenv("NTRACER_BOX_INTERLEAVE"), 1) != 0;      // 0: a tile-kernel wave renders consecutive rows
     sw.box_var_rows = atoi_or(getenv("NTRACER_BOX_VAR_ROWS"), 1) != 0;          // 0: BoxScene at run-time n through the per-pixel kernel for every format
@@ -729,15 +728,15 @@ int plan_box(const nt_scene *s, DeviceState *ds, const FrameJob &job, const Rend
     if (tg.colors_out || !sw.box_cull) return NT_OK;
     // one bit per 64-pixel stretch of a row: can any of its rays reach the cube? (box_cull_kernel)
     const size_t words = (size_t)(((tg.width + 63) / 64 + 31) / 32);
-    // stretch codes (4 words per redo word), 16 rows of padding (box_kernel reads a wave's rows without
-    // clamping), redo bits
-    const size_t need = ((size_t)5 * job.nframes * tg.row_count + 64) * words * sizeof(uint32_t);
+    // stretch codes (4 words per redo word) and 16 rows of padding (box_kernel reads a wave's rows without clamping); the
+    // fused route's redo bitmap, one word per redo word, fits in the codes' place
+    const size_t need = ((size_t)4 * job.nframes * tg.row_count + 64) * words * sizeof(uint32_t);
     if (need > ds->cull.cap || !ds->cull.p) ds->cull_clean = false;
     if (int e = ds->cull.ensure(need)) return e;
     // The fused kernels keep their redo bitmap at the start of this buffer and leave it zeroed; after anything else
-    // has written there (a fresh allocation, the cull / box / redo kernels) it is zeroed here, in stream order.
+    // has written there (a fresh allocation, box_cull_kernel's stretch codes) it is zeroed here, in stream order.
     // (the formats launch_box_fixed sends there: plain RGB of <= 10 bits in one aligned dword, or three plain fp32 channels)
-    const bool fused = li.box_path != 0 && s->n <= NT_MAX_FIXED_BOX_DIM && tg.aligned4 &&
+    const bool fused = s->n <= NT_MAX_FIXED_BOX_DIM && tg.aligned4 &&
                        ((tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4) || (tg.plain_f32[0] >= 0 && tg.bpp == 12));
     if (fused && !ds->cull_clean) {
         HIP_TRY(hipMemsetAsync(ds->cull.p, 0, ds->cull.cap, job.stream));
@@ -849,7 +848,6 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     li.stream = job.stream;
     li.cu_count = ds->cu_count;
     li.kernel_choice = sw.composite_kernel;
-    li.box_path = sw.box_path;
     li.frame_major = sw.frame_major;
     li.force_var = sw.force_var;
     li.box_var_rows = sw.box_var_rows;
@@ -1426,20 +1424,6 @@ int nt_calculate_color(nt_scene_t *s, int x, int y, int width, int height, float
     const int32_t xs = x, ys = y;
     return nt_colors_at(s, width, height, 1, &xs, &ys, rgb, -1);
 }
-
-#ifdef NT_DEBUG_SCRATCH
-// Diagnostic builds only (tools/box_census.py; not part of include/ntracer_hip.h): the BoxScene scratch of the last launch
-// on `device` (stretch codes / redo words of the cull / box / redo path), after the device has drained.
-long long nt_debug_box_scratch(nt_scene_t *s, int device, void *out, size_t bytes) {
-    if (!s || !out) return fail(NT_E_INVALID, "NULL argument");
-    auto it = s->devs.find(device);
-    if (it == s->devs.end() || !it->second->cull.p) return fail(NT_E_INVALID, "no BoxScene launch on this device yet");
-    if (hipSetDevice(device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(NT_E_DEVICE, "device synchronisation failed");
-    const size_t n = std::min(bytes, it->second->cull.cap);
-    if (hipMemcpy(out, it->second->cull.p, n, hipMemcpyDeviceToHost) != hipSuccess) return fail(NT_E_DEVICE, "copy failed");
-    return (long long)n;
-}
-#endif
 
 int nt_scene_last_stats(const nt_scene_t *cs, nt_stats *out) {
     nt_scene *s = const_cast<nt_scene *>(cs);

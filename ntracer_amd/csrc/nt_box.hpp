@@ -1,7 +1,9 @@
-// nt_box.hpp -- BoxScene kernels for compile-time N (fixed_geometry.hpp -> registers):
-//   box_cull_kernel<N> -> box_kernel<N,PLAIN,ROWS> -> box_redo_kernel<N>      box_scene::calculate_color (src/tracer.hpp:101-152)
-// fused with process_pixel's conversion and packing (nt_pixel.hpp), so the only HBM traffic of a frame is the packed
-// framebuffer.  Instantiated per N by nt_inst_box.hip.
+// nt_box.hpp -- BoxScene kernels for compile-time N (fixed_geometry.hpp -> registers), box_scene::calculate_color
+// (src/tracer.hpp:101-152) fused with process_pixel's conversion and packing (nt_pixel.hpp), so the only HBM traffic of a
+// frame is the packed framebuffer.  Two routes (launch_box_fixed):
+//   packed RGB of <= 10 bits a channel, three fp32 channels:  box_tile_kernel (-> box_redo_kernel for packed RGB, N > 8)
+//   every other format, probe mode:                           box_cull_kernel -> box_kernel
+// Instantiated per N by nt_inst_box.hip.
 #pragma once
 #include <type_traits>
 #include "nt_pixel.hpp"
@@ -325,7 +327,7 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
     // rowhit (wave-uniform): the culling bit of this 64-pixel stretch of the row, see box_cull_kernel
     // face (wave-uniform) >= 0: every ray of the stretch is known to hit that face (a one-face row of box_tile_kernel whose
     // cheap quantisation came too close to a rounding boundary): nothing to sort, only the exact colour is wanted
-    // (DEFER: the callers pass the code of the stretch as rowhit -- a stretch that survived the codes wave is next to the
+    // (DEFER: box_tile_kernel passes the code of the stretch as rowhit -- a stretch that survived the codes wave is next to the
     // cube, where the circumsphere test rarely spares a wave the classification and costs eight instructions every time)
     const bool maybe = redo || (rowhit && (DEFER || INL || box_may_hit(N, dots, sx, sy, sq)));
     float r, g, b;
@@ -338,8 +340,8 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
 #pragma unroll
         for (int j = 1; j < N; ++j) x = face == j ? dir[j] : x;
     } else if ((REDO || INL) && redo && (sets & 0x80000000u) != 0u) {
-        // sets (wave-uniform, box_redo_kernel): T and C of the whole stretch from the codes wave (box_stretch_code) -- the
-        // reference's arithmetic on them, as in box_resolve, without the entry times
+        // sets (wave-uniform, box_tile_kernel's near-tie stretches): T and C of the whole stretch from the codes wave
+        // (box_stretch_code, through LDS) -- the reference's arithmetic on them, as in box_resolve, without the entry times
         const float len = sqrt_wave(sq);
         float d[N];
 #pragma unroll
@@ -446,14 +448,13 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
     return true;
 }
 
-// A lane renders ROWS pixels of one image column (a block: 64 columns x 4*ROWS rows; a wave still writes 64 consecutive
-// pixels of a row at a time): forward + right*sx and the wave's set-up are shared by all of them.  ROWS = BoxRows<N>
-// (8), or 16 for the packed-RGB kernel in large launches; probe mode (listed pixels) is one pixel per lane.
+// The general kernel: every format, and probe mode.  A lane renders R = NT_BOXROWS (8) pixels of one image column (a block:
+// 64 columns x 4*R rows; a wave still writes 64 consecutive pixels of a row at a time): forward + right*sx and the wave's
+// set-up are shared by all of them.  Probe mode (listed pixels) is one pixel per lane.
 #ifndef NT_BOXROWS
 #define NT_BOXROWS 8
 #endif
-template <int N> struct BoxRows { static constexpr int value = N <= NT_DEV_MAX_FIXED_BOX ? NT_BOXROWS : 1; };
-template <int N, bool PLAIN, int ROWS = BoxRows<N>::value>
+template <int N>
 __global__ __launch_bounds__(256) void box_kernel(NtCameraFixed cam, NtTarget tg) {
     const int tid = (int)threadIdx.x;
     float org[N], right[N], up[N], fwd[N], dir[N];
@@ -469,7 +470,7 @@ __global__ __launch_bounds__(256) void box_kernel(NtCameraFixed cam, NtTarget tg
     } else {
         dots[0] = cam.odots[0]; dots[1] = cam.odots[1]; dots[2] = cam.odots[2]; dots[3] = cam.odots[3];
     }
-    if ((!PLAIN && tg.colors_out) || ROWS == 1) {
+    if (tg.colors_out) {
         // one pixel per lane: probe mode (listed pixels)
         const PixelRef pr = locate_pixel<64, 4>(tg, tid & 63, tid >> 6, tid);
         if (!pr.valid) return;
@@ -481,162 +482,12 @@ __global__ __launch_bounds__(256) void box_kernel(NtCameraFixed cam, NtTarget tg
         float sq = dir[0] * dir[0];
 #pragma unroll
         for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
-        box_pixel<N, PLAIN>(tg, pr, org, dir, sq, dots, sx, sy, margin);
+        box_pixel<N, false>(tg, pr, org, dir, sq, dots, sx, sy, margin);
         return;
     }
     // the wave's number as a scalar: everything that depends on the row alone stays on the scalar unit
-    constexpr int R = ROWS;
+    constexpr int R = NT_BOXROWS;
     const int row0 = ((int)blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(tid >> 6)) * R;
-    if (PLAIN) {
-        // ---- packed RGB, at most 10 bits a channel: the lean loop ----
-        if (row0 >= tg.row_count) return;             // (also keeps the row-code reads below inside the table's padding)
-        // Row bookkeeping is done once, one row per lane (lane l <-> row row0 + l), and read back with v_readlane:
-        // sy, up[0]*sy, the row's byte offset, whether the row exists.  Every lane stays active for that -- lanes past
-        // the right edge redo the last pixel (the same dword, the same value) instead of leaving.
-        const int lane = tid & 63;
-        const int lorow = tg.row_begin + row0 + lane;
-        int ly = lorow;
-        if (tg.band_world > 1) {
-            const int band = lorow / tg.band_rows;
-            ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
-        }
-        const uint32_t valid = (uint32_t)__builtin_amdgcn_ballot_w64(lane < R && row0 + lane < tg.row_count && ly < tg.height);
-        const float v_sy = tg.fovI * ((float)ly - tg.half_h);
-        const float v_us0 = up[0] * v_sy;
-        const long long v_off = (long long)blockIdx.z * tg.frame_stride + (long long)(tg.compact ? lorow : ly) * tg.pitch;
-        const int v_off_lo = (int)v_off, v_off_hi = (int)(v_off >> 32);
-        int x = (int)blockIdx.x * 64 + lane;
-        x = x < tg.width ? x : tg.width - 1;
-        const long long xoff = (long long)x * tg.bpp;
-        const float sx = tg.fovI * ((float)x - tg.half_w);
-        float base[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) base[j] = fwd[j] + right[j] * sx;
-        // what box_cull_kernel found out about the wave's rows, four bits a row (row rr in bits 4rr..4rr+3)
-        static_assert(R <= 16, "sixteen row codes to a qword");
-        unsigned long long rowcodes = 0ull;
-        // (rows past the last one read on into the table's padding: `valid` masks them out)
-        const uint32_t *cp = tg.cull + ((size_t)blockIdx.z * tg.row_count + row0) * tg.cull_words + (blockIdx.x >> 3);
-        const int nibble = 4 * (blockIdx.x & 7);
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr)
-            rowcodes |= (unsigned long long)((cp[rr * tg.cull_words] >> nibble) & 15u) << (4 * rr);
-        // Background rows need |dir|^2 only to ~2^-19 (see the guard below): as a quadratic in sy,
-        //   |base - up*sy|^2 = base.base - 2*sy*(base.up) + sy^2*(up.up),
-        // it costs two fma per row instead of the N-1 other components and their squares.  Its absolute error is
-        // ~2.7n*2^-24*(base.base + sy^2 up.up), and that is relative to the result as long as the cross term cannot
-        // cancel the squares: lanes check (base.up)^2 <= base.base*up.up/16 (any sane camera: up is orthogonal to
-        // forward and right), and a wave with a lane that fails it never takes the shortcut.
-        float bb = 0.0f, bu = 0.0f, uu = 0.0f;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            bb = fmaf(base[j], base[j], bb);
-            bu = fmaf(base[j], up[j], bu);
-            uu = fmaf(up[j], up[j], uu);
-        }
-        const float m2bu = -2.0f * bu;
-        const bool fastsq = __builtin_amdgcn_ballot_w64(!(bu * bu <= bb * uu * 0.0625f)) == 0ull;
-        const float maxv = (float)tg.plain_maxval;
-        // rows painted as background outright / rows that are one face throughout / rows for the full treatment, as
-        // masks with one bit per row AT THE ROW'S NIBBLE (bit 4rr): derived from the codes with a dozen scalar
-        // operations on the whole qword
-        const unsigned long long nib = 0x1111111111111111ull;
-        unsigned long long validn = valid & 0xffffu;                       // bit rr -> bit 4rr
-        validn = (validn | (validn << 24)) & 0x000000ff000000ffull;
-        validn = (validn | (validn << 12)) & 0x000f000f000f000full;
-        validn = (validn | (validn << 6)) & 0x0303030303030303ull;
-        validn = (validn | (validn << 3)) & nib;
-        unsigned long long quick = 0ull, inner = 0ull, todo = validn;
-        // up[K]*sy of the lane's row, K = its face if it is of the second kind
-        float v_usK = 0.0f;
-        if (fastsq) {
-            const unsigned long long n = rowcodes;
-            const unsigned long long nz = (n | (n >> 1) | (n >> 2) | (n >> 3)) & nib;            // code != 0
-            const unsigned long long hi3 = ((n >> 1) & (n >> 2) & (n >> 3)) & nib;               // code is 14 or 15
-            const unsigned long long full = hi3 & n, skip = hi3 & ~n;                            // 15 / 14 (box_redo_kernel's from the start)
-            quick = validn & ~nz;
-            todo = validn & full;
-            inner = validn & nz & ~hi3;
-            (void)skip;
-            const uint32_t lk = ((uint32_t)(rowcodes >> (4 * (lane & 15))) & 15u) - 1u;
-            float upK = up[0];
-#pragma unroll
-            for (int j = 1; j < N; ++j) upK = lk == (uint32_t)j ? up[j] : upK;
-            v_usK = upK * v_sy;
-        }
-        while (quick != 0ull) {
-            const int rr = __builtin_ctzll(quick) >> 2;
-            quick &= quick - 1ull;
-            const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_sy), rr));
-            const float us0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_us0), rr));
-            const float d0 = base[0] - us0;                           // dir[0], bit for bit
-            const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-            // round(|dir[0]|/len * maxval), as in box_pixel, with the guard widened for sqa: sqa is within
-            // (3.7n+4)*2^-24 of the reference's sum, so t is within ~22*2^-24 < 2^-19.4 of its value (n <= 8); guard 2^-18
-            const float t = (fabsf(d0) * __builtin_amdgcn_rsqf(sqa)) * maxv;
-            const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f);
-            if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
-                todo |= 1ull << (4 * rr);                                     // a lane too close to a rounding boundary
-                continue;
-            }
-            uint32_t q = (uint32_t)(t + 0.5f);
-            q = q < tg.plain_maxval ? q : tg.plain_maxval;
-            PixelRef pr;
-            pr.offset = (((long long)__builtin_amdgcn_readlane(v_off_hi, rr) << 32) | (unsigned)__builtin_amdgcn_readlane(v_off_lo, rr)) + xoff;
-            emit_plain(tg, pr, d0 > 0.0f ? q : 0u, q);
-        }
-        while (inner != 0ull) {
-            // every ray of the row's stretch hits face K (box_cull_kernel): the colour is |dir[K]|/len * (1, .5, .5)
-            const int rr = __builtin_ctzll(inner) >> 2;
-            inner &= inner - 1ull;
-            const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
-            const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_sy), rr));
-            const float usK = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_usK), rr));
-            float bK = base[0];
-#pragma unroll
-            for (int j = 1; j < N; ++j) bK = K == (uint32_t)j ? base[j] : bK;
-            const float dK = bK - usK;                                // dir[K], bit for bit
-            const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-            const float t = (fabsf(dK) * __builtin_amdgcn_rsqf(sqa)) * maxv, th = t * 0.5f;
-            const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f) &&
-                               fabsf(__builtin_amdgcn_fractf(th) - 0.5f) > fmaf(th, 0x1p-18f, 0x1p-18f);
-            if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
-                todo |= 1ull << (4 * rr);
-                continue;
-            }
-            uint32_t qr = (uint32_t)(t + 0.5f), qgb = (uint32_t)(th + 0.5f);
-            qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
-            qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
-            PixelRef pr;
-            pr.offset = (((long long)__builtin_amdgcn_readlane(v_off_hi, rr) << 32) | (unsigned)__builtin_amdgcn_readlane(v_off_lo, rr)) + xoff;
-            emit_plain(tg, pr, qr, qgb);
-        }
-        while (todo != 0ull) {
-            const int rr = __builtin_ctzll(todo) >> 2;
-            todo &= todo - 1ull;
-            const bool rowhit = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) != 0u;
-            const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_sy), rr));
-            PixelRef pr;
-            pr.x = x;
-            pr.y = 0;
-            pr.offset = (((long long)__builtin_amdgcn_readlane(v_off_hi, rr) << 32) | (unsigned)__builtin_amdgcn_readlane(v_off_lo, rr)) + xoff;
-            pr.hit_index = 0;
-            pr.valid = true;
-#pragma unroll
-            for (int j = 0; j < N; ++j) dir[j] = base[j] - up[j] * sy;
-            float sq = dir[0] * dir[0];
-#pragma unroll
-            for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
-            if (!box_pixel<N, true, true>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit)) {
-                // a lane needs the reference's face-by-face arithmetic: leave the stretch to box_redo_kernel
-                if (lane == 0)
-                    atomicOr(tg.redo + ((size_t)blockIdx.z * tg.row_count + row0 + rr) * tg.redo_words + (blockIdx.x >> 5),
-                             1u << (blockIdx.x & 31));
-            }
-        }
-        return;
-    }
-    // ---- any other format ----
     const int x = (int)blockIdx.x * 64 + (tid & 63);
     if (x >= tg.width) return;
     const float sx = tg.fovI * ((float)x - tg.half_w);
@@ -679,13 +530,13 @@ __global__ __launch_bounds__(256) void box_kernel(NtCameraFixed cam, NtTarget tg
     }
 }
 
-// The stretches box_kernel<N, true> left behind (tg.redo): one wave per (frame, row, word of 32 stretches), every set
-// bit rendered with the complete box_pixel -- classification, box_resolve, box_color.
-// F32: three plain fp32 channels instead of packed RGB.  ZERO: hand the word back zeroed (the fused path's bitmap is
-// marked with atomic ORs by box_tile_kernel and must be clean when the next launch starts).
-// SPLIT (small launches, ZERO only): 2 or 4 waves per word, wave k for the stretches k, k + SPLIT, ... -- the marked stretches
+// The stretches box_tile_kernel<N, false> left behind in the redo bitmap (tg.redo; packed RGB, N > 8): one wave per (frame,
+// row, word of 32 stretches), every set bit rendered with the complete box_pixel -- classification, box_resolve, box_color.
+// The wave hands its bits back zeroed: the tile kernel marks the bitmap with atomic ORs, and it must be clean when the next
+// launch starts.
+// SPLIT (small launches): 2 or 4 waves per word, wave k for the stretches k, k + SPLIT, ... -- the marked stretches
 // of a row come in runs, and with few rows in flight a run of ten is a long tail for one wave.
-template <int N, bool F32 = false, bool ZERO = false, int SPLIT = 1>
+template <int N, int SPLIT>
 __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarget tg) {
     const int tid = (int)threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -696,7 +547,7 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
     const uint32_t mine = (SPLIT == 1 ? 0xffffffffu : SPLIT == 2 ? 0x55555555u : 0x11111111u) << (wv % SPLIT);
     uint32_t todo = *word & mine;
     if (todo == 0u) return;
-    if (ZERO && (tid & 63) == 0) {
+    if ((tid & 63) == 0) {
         if (SPLIT > 1) atomicAnd(word, ~mine);  // (the other waves may not have read the word yet: each needs its own bits only)
         else *word = 0u;
     }
@@ -725,7 +576,7 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
         const int bit = __builtin_ctz(todo);
         todo &= todo - 1u;
         int x = ((int)blockIdx.x * 32 + bit) * 64 + (tid & 63);
-        x = x < tg.width ? x : tg.width - 1;            // as in box_kernel<N, true>
+        x = x < tg.width ? x : tg.width - 1;            // as in box_tile_kernel
         PixelRef pr;
         pr.x = x;
         pr.y = y;
@@ -738,12 +589,7 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
         float sq = dir[0] * dir[0];
 #pragma unroll
         for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
-        uint32_t sets = 0u;
-        if (N <= 8 && tg.tie_sets) {
-            const int stretch = (int)blockIdx.x * 32 + bit;
-            sets = (uint32_t)__builtin_amdgcn_readfirstlane((int)tg.tie_sets[((size_t)blockIdx.z * tg.row_count + row) * ((tg.width + 63) / 64) + stretch]);
-        }
-        box_pixel<N, !F32, false, true, F32>(tg, pr, org, dir, sq, dots, sx, sy, margin, true, -1, sets);
+        box_pixel<N, true, false, true>(tg, pr, org, dir, sq, dots, sx, sy, margin);
     }
 }
 
@@ -753,22 +599,24 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
 //  * code 0 -- no ray can reach the cube.  A ray that comes within h = 1 + 2m + 1e-3 of the cube in every coordinate
 //    at some tau > 0 (every ray the reference could call a hit does, see box_classify) satisfies
 //        (vc_j + g_j)*tau >= -h - o_j     and     (vc_j - g_j)*tau <= h - o_j         for every j:
-//    2n half-lines in tau; an empty intersection clears the stretch, and box_kernel paints background there without
+//    2n half-lines in tau; an empty intersection clears the stretch, and the kernels paint background there without
 //    looking further.  Convexity makes this sharp: what is left is within half a stretch of the cube's silhouette.
 //  * code K+1 -- every ray clearly hits face K, K = the face the middle ray enters last.  With v_K of one sign over
 //    the stretch, tau_K = (s_K - o_K)/v_K ranges over [tlo, thi]; if for every other j the extremes of
 //    o_j + v_j*tau over that box stay inside 1 - m*(1 + |v_j|max/|v_K|min) (less 1e-4 for the arithmetic here), then for
 //    each ray the reference's test of face K passes with room to spare, and every other slab was entered at least
 //    m/|v_K| earlier, i.e. while p_K was outside 1+m, so no face before K can pass its j = K check (the argument of
-//    box_classify).  box_kernel shades such rows from v_K alone.
-//  * code 15 -- anything else: box_kernel classifies the rays one by one;  code 14 -- box_kernel skips the stretch and
-//    box_redo_kernel renders it (its redo bit is set here).
+//    box_classify).  box_tile_kernel shades such rows from v_K alone.
+//  * code 15 -- anything else: the rays are classified one by one;  code 14 -- a near-tie stretch (the middle ray's last two
+//    entries are within m/|v_K| of each other): box_tile_kernel goes straight to the reference's arithmetic there, or leaves
+//    the stretch to box_redo_kernel (packed RGB, N > 8).
+//  box_kernel<N> only asks whether a stretch is culled (code 0) and classifies every ray of the others.
 // Reciprocals are approximate (v_rcp_f32); the slacks above are ~1000x their error.
 // The code of one 64-pixel stretch (see the comment above): row y of the image, stretch `col` of the row.
-// `sets` (box_tile_kernel): for a stretch that may end up with box_redo_kernel (codes 14 and 15), what box_resolve works out ray by ray from entry times -- the faces T that
+// `sets` (box_tile_kernel): for a stretch of code 14 or 15, what box_resolve works out ray by ray from entry times -- the faces T that
 // can still be the reference's answer and the coordinates C one of them could fail at -- as supersets valid for EVERY ray
-// of the stretch (bits 0..9: T, bits 10..19: C, bit 31: valid), so that box_redo_kernel goes straight to the reference's
-// arithmetic on them.  With [A_j, B_j] the range of slab j's entry time over the stretch's directions: every ray's last
+// of the stretch (bits 0..9: T, bits 10..19: C, bit 31: valid), so that box_tile_kernel goes straight to the reference's
+// arithmetic on them in its near-tie stretches.  With [A_j, B_j] the range of slab j's entry time over the stretch's directions: every ray's last
 // entry is at or after TN = max_j A_j; M = m / (the smallest |v_j| of an axis that can be last, B_j >= TN) is at least the
 // ray's m/|v_K|; so a face within m/|v_K| of a ray's last entry has B_j >= TN - M: that is T.  The entries of T's faces,
 // for any ray, lie in [min_{T} A_j, max_j B_j]; a coordinate that stays inside 1 - m over that span of tau, for all the
@@ -937,17 +785,12 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
         }
         code = box_stretch_code<N>(org, right, up, fwd, tg, y, col);
     }
-    const unsigned long long direct = __builtin_amdgcn_ballot_w64(code == 14u);      // redo bits set here
     // eight stretches to a dword
     uint32_t packed = code << (4 * (threadIdx.x & 7));
     packed |= (uint32_t)__shfl_xor((int)packed, 1, 64);
     packed |= (uint32_t)__shfl_xor((int)packed, 2, 64);
     packed |= (uint32_t)__shfl_xor((int)packed, 4, 64);
-    if (row < tg.row_count) {
-        if ((threadIdx.x & 7) == 0) out[((size_t)blockIdx.z * tg.row_count + row) * tg.cull_words + (col >> 3)] = packed;
-        if ((threadIdx.x & 31) == 0)
-            tg.redo[((size_t)blockIdx.z * tg.row_count + row) * tg.redo_words + word] = (threadIdx.x & 32) ? (uint32_t)(direct >> 32) : (uint32_t)direct;
-    }
+    if (row < tg.row_count && (threadIdx.x & 7) == 0) out[((size_t)blockIdx.z * tg.row_count + row) * tg.cull_words + (col >> 3)] = packed;
 }
 
 // --------------------------------------------------------------------------------------
@@ -958,10 +801,10 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
 //                                   that works out the stretch codes, box_stretch_code, and leaves them in LDS); after the
 //                                   barrier every wave renders its ROWS rows from them with the lean loops, sixteen rows (a
 //                                   qword of codes) at a time.  Per-row parameters come from the host's row table through
-//                                   scalar loads (NtTarget::rowtab).  A row it cannot settle (code 14, or a lane that needs
-//                                   the reference's face-by-face arithmetic) gets its bit set in the redo bitmap,
-//                                   [frame][row][word of 32 stretches], with an atomic OR.
-//   box_redo_kernel<N, F32>         one wave per (frame, row, word): the marked stretches with box_pixel<REDO>; it hands the
+//                                   scalar loads (NtTarget::rowtab).  Packed RGB at N > 8: a row it cannot settle (code 14,
+//                                   or a lane that needs the reference's face-by-face arithmetic) gets its bit set in the
+//                                   redo bitmap, [frame][row][word of 32 stretches], with an atomic OR.
+//   box_redo_kernel<N, SPLIT>       one wave per (frame, row, word): the marked stretches with box_pixel<REDO>; it hands the
 //                                   word back zeroed, so the bitmap is clean for the next launch (the host zeroes it once).
 // No pre-kernel; the only scratch is the bitmap (one bit per 64 pixels).
 // --------------------------------------------------------------------------------------
@@ -1064,10 +907,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 // for every row; those dimensions go without)
                 const unsigned long long cs = box_stretch_code2<N, (N <= NT_BOX_SETS_MAX_N)>(org, right, up, fwd, tg, y, (int)blockIdx.x);
                 code = (uint32_t)cs;
-                const uint32_t sets = (uint32_t)(cs >> 32);
-                // (every marked stretch gets a fresh entry: the sets here, 0 from the wave that marks a row it looked at)
-                row_sets = sets;
-                if (!ALLIN && N <= 8 && code >= 14u && tg.tie_sets) tg.tie_sets[((size_t)frame * tg.row_count + trow) * gridDim.x + blockIdx.x] = sets;
+                row_sets = (uint32_t)(cs >> 32);
             }
         }
         if (SETS_LDS) s_sets[lane] = row_sets;
@@ -1141,7 +981,11 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             // (the fp32 kernel, bound by its stores, keeps them pinned: unpinned it executes 8 % more instructions for nothing)
             if (NT_BOX_PIN_UP || F32 || j == 0) asm volatile("" : "+v"(upv[j]));
         }
-        // packed RGB: the quadratic |dir|^2 = bb - 2 bu sy + uu sy^2 of the guarded rsq quantisation (see box_kernel<N, true>)
+        // packed RGB: rows that are background or one face throughout need |dir|^2 only to ~2^-19 (see the guard below): as a
+        // quadratic in sy, |base - up*sy|^2 = bb - 2 bu sy + uu sy^2 (bb = base.base, bu = base.up, uu = up.up), it costs two fma a
+        // row instead of the N-1 other components and their squares.  Its absolute error is ~2.7n*2^-24*(bb + sy^2 uu), and that
+        // is relative to the result as long as the cross term cannot cancel the squares: lanes check bu^2 <= bb*uu/16 (any sane
+        // camera: up is orthogonal to forward and right), and a wave with a lane that fails it never takes the shortcut (fastsq).
         float bb = 0.0f, bu = 0.0f, uu = 0.0f;
         bool fastsq = true;
         if (!F32) {
@@ -1198,7 +1042,9 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                       ((unsigned)__builtin_popcount((uint32_t)(rows_tie >> (16 * half)) & valid) << 24);
 #endif
         if (!F32) {
-            // ---- packed RGB: guarded rsq quantisation (see box_kernel<N, true>)
+            // ---- packed RGB: guarded rsq quantisation.  round(|dir[K]|/len * maxval) (and its half for a hit), as in box_pixel,
+            // with the guard widened for the quadratic |dir|^2: that is within (3.7n+4)*2^-24 of the reference's sum, so t is
+            // within ~22*2^-24 < 2^-19.4 of its value at n = 8; guard 2^-18.  A wave with a lane inside it takes the row ray by ray.
             if (!fastsq) {
                 todo |= quick | inner;
                 quick = 0u;
@@ -1376,8 +1222,6 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 const int rr = __builtin_ctz(redo_bits);
                 redo_bits &= redo_bits - 1u;
                 const int mrow = il > 0 ? hfirst + il * rr : row0 + rr;
-                if (N <= 8 && tg.tie_sets && ((uint32_t)(rowcodes >> (4 * rr)) & 15u) < 14u)
-                    tg.tie_sets[((size_t)frame * tg.row_count + mrow) * gridDim.x + blockIdx.x] = 0u;
                 atomicOr(tg.redo + ((size_t)frame * tg.row_count + mrow) * tg.redo_words + (blockIdx.x >> 5), 1u << (blockIdx.x & 31));
             }
         }
@@ -1410,9 +1254,8 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
     for (int k = 0; k < 4 * N; ++k) cf.inl[k] = cam.inl[k];
     NtTarget tg = tg_in;
     dim3 grid;
-    grid_for(tg, 64, tg.colors_out ? 4 : 4 * BoxRows<N>::value, li.nframes, grid);
+    grid_for(tg, 64, tg.colors_out ? 4 : 4 * NT_BOXROWS, li.nframes, grid);
     tg.cull = nullptr;
-    tg.tie_sets = nullptr;
     tg.redo = nullptr;
     tg.cull_words = 0;
     tg.redo_words = 0;
@@ -1420,7 +1263,7 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
     // a channel in one aligned dword, and three plain fp32 channels
     const bool fmt_rgb = tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4 && tg.aligned4;
     const bool fmt_f32 = tg.plain_f32[0] >= 0 && tg.bpp == 12 && tg.aligned4;
-    if (li.cull_buf && tg.rowtab && !tg.colors_out && BoxRows<N>::value > 1 && (fmt_rgb || fmt_f32) && li.box_path != 0 && li.cull_clean) {
+    if (li.cull_buf && tg.rowtab && !tg.colors_out && (fmt_rgb || fmt_f32) && li.cull_clean) {
         hipStream_t st = (hipStream_t)li.stream;
         // rows a wave x waves a block (nt_box_tile_geom, nt_device.hpp -- the host's row table follows the same decision):
         // sixteen rows a lane once there are waves to spare (the per-wave set-up is a fifth of the work at eight), three waves a
@@ -1437,10 +1280,6 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
         dim3 tgrid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.row_count + tile_rows - 1) / tile_rows), (unsigned)li.nframes);
         tg.redo_words = ((tg.width + 63) / 64 + 31) / 32;
         tg.redo = li.cull_buf;                        // [frame][row][redo_words], all zero between launches
-        // the tie sets of the marked stretches, [frame][row][stretch] dwords (written with the mark)
-        // (a buffer of their own: the bitmap's buffer must hold nothing but the bitmap, which has to be all zero whatever the
-        // next launch's geometry is)
-        tg.tie_sets = nullptr;               // (the tie sets stay in LDS: only kernels that need no second kernel have them)
         // the middle columns 96 frames ahead of the outer ones (32 .. 96 measure alike on the 160-frame call: -4 %, and on
         // BoxScene(3): -3 %; a rank's eighth of the call: -3 % with 48, -6 % with 96; 16: half of it), in launches of 8 frames
         // or more (eight 4096 x 4096 frames of BoxScene(10): 621 -> 693 Grays/s; four: no difference)
@@ -1452,21 +1291,21 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
         if (tg.row_il > 0) tg.lead_frames = li.nframes >= 32 ? 16 : 0;
         if ((long long)li.nframes + tg.lead_frames > 65535) tg.lead_frames = 0;        // (grid z)
         tgrid.z += (unsigned)tg.lead_frames;
-        // few rows in flight: two waves per redo word
-        const long long rwords = (long long)tg.row_count * li.nframes * tg.redo_words;
-        const int split = rwords < 48 * 1024 ? 2 : 1;           // (87k words: one wave 3 % faster; 44k: even; 22k: two waves 2 % faster;
-                                                                //  four waves a word measured slower than two; NTRACER_BOX_SPLIT,
-                                                                //  the override these were measured with, has been removed)
-        const int rpb = 4 / split;              // rows per block
-        const dim3 rgrid((unsigned)tg.redo_words, (unsigned)((tg.row_count + rpb - 1) / rpb), (unsigned)li.nframes);
         if (fmt_rgb) {
             if (r64) hipLaunchKernelGGL((box_tile_kernel<N, false, 64, 1>), tgrid, dim3(64), 0, st, cf, tg);
             else if (r16 && wpb == 3) hipLaunchKernelGGL((box_tile_kernel<N, false, 16, 3>), tgrid, dim3(192), 0, st, cf, tg);
             else if (r16) hipLaunchKernelGGL((box_tile_kernel<N, false, 16, 4>), tgrid, dim3(256), 0, st, cf, tg);
             else hipLaunchKernelGGL((box_tile_kernel<N, false, 8, 4>), tgrid, dim3(256), 0, st, cf, tg);
-            if (N > NT_BOX_INLINE_MAX_N) {          // (up to there the tile kernel leaves nothing behind)
-                if (split == 2) hipLaunchKernelGGL((box_redo_kernel<N, false, true, 2>), rgrid, dim3(256), 0, st, cf, tg);
-                else hipLaunchKernelGGL((box_redo_kernel<N, false, true, 1>), rgrid, dim3(256), 0, st, cf, tg);
+            if constexpr (N > NT_BOX_INLINE_MAX_N) {          // (up to there the tile kernel leaves nothing behind)
+                // few rows in flight: two waves per redo word
+                const long long rwords = (long long)tg.row_count * li.nframes * tg.redo_words;
+                const int split = rwords < 48 * 1024 ? 2 : 1;   // (87k words: one wave 3 % faster; 44k: even; 22k: two waves 2 % faster;
+                                                                //  four waves a word measured slower than two; NTRACER_BOX_SPLIT,
+                                                                //  the override these were measured with, has been removed)
+                const int rpb = 4 / split;              // rows per block
+                const dim3 rgrid((unsigned)tg.redo_words, (unsigned)((tg.row_count + rpb - 1) / rpb), (unsigned)li.nframes);
+                if (split == 2) hipLaunchKernelGGL((box_redo_kernel<N, 2>), rgrid, dim3(256), 0, st, cf, tg);
+                else hipLaunchKernelGGL((box_redo_kernel<N, 1>), rgrid, dim3(256), 0, st, cf, tg);
             }
         } else {
             if (r64) hipLaunchKernelGGL((box_tile_kernel<N, true, 64, 1>), tgrid, dim3(64), 0, st, cf, tg);
@@ -1477,33 +1316,17 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
         }
         return 0;
     }
-    if (li.cull_buf && !tg.colors_out && BoxRows<N>::value > 1) {
+    // every other format, and probe mode: the stretch codes (when there is a cull buffer), then the general kernel.  The codes
+    // go to the start of the cull buffer, over the fused route's redo bitmap (plan_box's cull_clean accounts for that).
+    if (li.cull_buf && !tg.colors_out) {
         const int ncols = (tg.width + 63) / 64;
-        tg.redo_words = (ncols + 31) / 32;
-        tg.cull_words = 4 * tg.redo_words;
-        tg.redo = li.cull_buf + ((size_t)li.nframes * tg.row_count + 16) * tg.cull_words;        // 16 rows of padding after the codes
-        hipLaunchKernelGGL(box_cull_kernel<N>, dim3((unsigned)tg.redo_words, (unsigned)((tg.row_count + 7) / 8), (unsigned)li.nframes), dim3(256), 0,
+        const int words = (ncols + 31) / 32;                    // 32 stretches of a row to a half-wave of box_cull_kernel
+        tg.cull_words = 4 * words;
+        hipLaunchKernelGGL(box_cull_kernel<N>, dim3((unsigned)words, (unsigned)((tg.row_count + 7) / 8), (unsigned)li.nframes), dim3(256), 0,
                            (hipStream_t)li.stream, cf, tg, li.cull_buf, ncols);
         tg.cull = li.cull_buf;
     }
-    // the common packed-RGB formats get the kernel with the format tests compiled out; it leaves the stretches that
-    // need the reference's face-by-face arithmetic to a second, small launch (it needs the bitmaps for that)
-    if ((tg.redo || BoxRows<N>::value == 1) && tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4 && tg.aligned4 &&
-        !tg.colors_out) {
-        // sixteen rows a lane once there are waves to spare (the per-wave set-up is a fifth of the work at eight)
-        const long long waves8 = (long long)grid.x * grid.y * grid.z * 4;
-        if (BoxRows<N>::value > 1 && BoxRows<N>::value < 16 && waves8 >= 64 * 1024) {
-            grid_for(tg, 64, 4 * 16, li.nframes, grid);
-            hipLaunchKernelGGL((box_kernel<N, true, (BoxRows<N>::value > 1 ? 16 : 1)>), grid, dim3(256), 0, (hipStream_t)li.stream, cf, tg);
-        } else {
-            hipLaunchKernelGGL((box_kernel<N, true>), grid, dim3(256), 0, (hipStream_t)li.stream, cf, tg);
-        }
-        if (BoxRows<N>::value > 1)
-            hipLaunchKernelGGL((box_redo_kernel<N, false, false, 1>), dim3((unsigned)tg.redo_words, (unsigned)((tg.row_count + 3) / 4), (unsigned)li.nframes),
-                               dim3(256), 0, (hipStream_t)li.stream, cf, tg);
-    } else {
-        hipLaunchKernelGGL((box_kernel<N, false>), grid, dim3(256), 0, (hipStream_t)li.stream, cf, tg);
-    }
+    hipLaunchKernelGGL(box_kernel<N>, grid, dim3(256), 0, (hipStream_t)li.stream, cf, tg);
     return 0;
 }
 

@@ -56,17 +56,15 @@ struct NtTarget {
     // (dist, item, lane, -); nullptr otherwise
     const void *hits;
     // BoxScene: four bits per (frame, owned row, 64-pixel stretch), eight stretches to a dword, from box_cull_kernel:
-    //   0: no ray of the stretch can reach the cube; 1..8: every ray of it clearly hits face K = code - 1;
-    //   14: left to box_redo_kernel (redo bit already set); 15: look at each ray.  [frame][row][cull_words] dwords, or nullptr
+    //   0: no ray of the stretch can reach the cube; 1..13: every ray of it clearly hits face K = code - 1;
+    //   14 (a near-tie), 15: look at each ray.  box_kernel<N> reads them.  [frame][row][cull_words] dwords, or nullptr
     const uint32_t *cull;
     int cull_words;
-    // one bit per stretch, [frame][row][redo_words] dwords: box_kernel sets the bit of a stretch it leaves to
-    // box_redo_kernel (a lane needed the reference's own face-by-face arithmetic); cleared by box_cull_kernel
+    // the fused route's redo bitmap, one bit per stretch, [frame][row][redo_words] dwords: box_tile_kernel (packed RGB, N > 8)
+    // sets the bit of a stretch it leaves to box_redo_kernel (code 14, or a lane needed the reference's own face-by-face
+    // arithmetic), and box_redo_kernel clears it
     uint32_t *redo;
     int redo_words;
-    // box_tile_kernel -> box_redo_kernel: for a marked stretch, the faces and coordinates the reference's arithmetic is
-    // needed on, for all its rays (box_stretch_code; 0: work them out ray by ray); [frame][row][stretch] dwords, or nullptr
-    uint32_t *tie_sets;
     // BoxScene tile kernel: per owned row (index = owned-row number; 64 entries of padding) 16 bytes {float sy = fovI*(y -
     // half_h); uint32 y < height; int64 byte offset of the row within a frame}, read with scalar loads; or nullptr
     const void *rowtab;
@@ -75,9 +73,10 @@ struct NtTarget {
     // w + 2W, ... -- every wave of a strip then holds the same share of the rows that need ray-by-ray work -- and the row
     // table is in SLOT order: entry w * ROWS + rr belongs to row w + W * rr (valid = 0 past the last row).
     int row_il;
-    // Abort word (renderer::CANCEL, polled per pixel by the reference: render.cpp:412): nullptr, or a device-visible dword --
-    // pinned host memory mapped into the device's address space -- that the kernels read past the caches when a block (or a
-    // tile of a striding block) starts; non-zero: the block leaves without drawing
+    // Abort word (renderer::CANCEL, polled per pixel by the reference: render.cpp:412): nullptr, or a dword the device can read
+    // while the kernels run -- best in device memory (pinned host memory works too, but every look at it is then a PCIe round
+    // trip) -- that the kernels read past the caches when a block (or a tile of a striding block) starts; non-zero: the block
+    // leaves without drawing
     const int *abort_word;
     // box_tile_kernel: the middle columns of the image are started `lead_frames` frames ahead of the outer ones (see the kernel); 0: off
     int lead_frames;
@@ -172,12 +171,12 @@ struct NtLaunchInfo {
     float *numer_buf;         // scratch for the packet kernel's plane numerators: numer_frames * n_batches * 4 floats
     int numer_frames;
     int tile_rows, tile_waves; // BoxScene, fused path: box_tile_kernel's block shape (nt_box_tile_geom; the row table follows it)
-    int box_path;             // BoxScene: 1 = fused tile kernel for the scripted formats (default), 0 = cull / box / redo kernels
     int cull_clean;           // cull_buf is all zero (the fused path's redo bitmap lives at its start)
     int frame_major;          // packet kernel: PacketArgs::frame_major (0: the frames of a multi-frame launch interleaved)
     int force_var;            // the run-time-n kernels at every dimension
     int box_var_rows;         // BoxScene, run-time n: box_rows_kernel_var for packed RGB (0: box_kernel_var for every format)
-    uint32_t *cull_buf;       // BoxScene: scratch for the row culling bits, 5 * nframes * row_count * ceil(ceil(width/64)/32) dwords: stretch codes, then redo bits (or nullptr)
+    uint32_t *cull_buf;       // BoxScene: scratch, (4 * nframes * row_count + 64) * ceil(ceil(width/64)/32) dwords: box_cull_kernel's stretch codes and
+                              // 16 rows of padding, or the fused route's redo bitmap at its start (or nullptr)
 };
 
 // box_tile_kernel's block shape for a launch, decided in one place because the host's row table (nt_api.cpp) follows it:

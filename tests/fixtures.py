@@ -38,7 +38,7 @@ BOX_TILE_BAND = (1920, 1080, 160, 3, 8, 8, (16, 3), 2)
 
 
 def box_redo_split(width, row_count, frames):
-    """launch_box_fixed's choice between box_redo_kernel<..., 2> (two waves a redo word) and <..., 1>"""
+    """launch_box_fixed's choice between box_redo_kernel<N, 2> (two waves a redo word) and <N, 1>"""
     redo_words = ((width + 63) // 64 + 31) // 32
     return 2 if row_count * frames * redo_words < 48 * 1024 else 1
 

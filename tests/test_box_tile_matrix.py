@@ -9,7 +9,7 @@ apart (the lead of the middle columns) never share one; the oracle renders the K
 launches is compared with its camera's oracle frame byte for byte, on the device.  The destination is filled with a
 sentinel first, has padded pitches, a frame stride larger than a frame and guard bytes around it: every byte outside the
 pixels must still hold the sentinel afterwards.  One scene per dimension serves all of its cases, so its row tables and
-scratch buffers are reused across launch geometries; an RGB16 frame (cull / box / redo kernels, which leave the shared
+scratch buffers are reused across launch geometries; an RGB16 frame (the cull and general kernels, which leave the shared
 scratch dirty) is rendered and checked before each nt_render_frames_device launch."""
 import ctypes as C
 import itertools
@@ -85,7 +85,7 @@ def oracle_frames(n, cams, w, h, name, chans):
 
 
 def check_rgb16_frame(sc, n, cams, k):
-    """a frame the fused kernels do not take: the cull / box / redo kernels write the scratch the fused path shares"""
+    """a frame the fused kernels do not take: the cull and general kernels write the scratch the fused path shares"""
     w, h = 200, 72
     o, a = cams[k]
     sc._set_camera_arrays(o, a)

@@ -66,11 +66,17 @@ def test_every_composite_switch_the_reader_or_launchers_read_is_set_by_a_row():
     assert read <= set_by_rows, "switches no matrix row sets: %s" % sorted(read - set_by_rows)
 
 
-def test_render_switches_are_read_only_by_the_reader():
-    """read_switches is the one place the render switches are read: no other code in csrc calls getenv, except the k-d
-    builder for NTRACER_BUILD_THREADS (not a render switch)"""
+# every render switch read_switches reads, once each
+RENDER_SWITCHES = ("NTRACER_STRICT_REFERENCE", "NTRACER_CLEAN_NORMALS", "NTRACER_FORCE_VAR", "NTRACER_COMPOSITE_KERNEL",
+                   "NTRACER_NUMERATORS", "NTRACER_TWO_PASS", "NTRACER_TILE_ORDER", "NTRACER_FRAME_MAJOR", "NTRACER_CHUNK_FRAMES",
+                   "NTRACER_BOX_CULL", "NTRACER_BOX_INTERLEAVE", "NTRACER_BOX_VAR_ROWS")
+
+
+def test_the_reader_reads_exactly_the_render_switches_and_nothing_else_calls_getenv():
+    """read_switches is the one place the render switches are read, and it reads each of RENDER_SWITCHES once and nothing
+    else: no other code in csrc calls getenv, except the k-d builder for NTRACER_BUILD_THREADS (not a render switch)"""
     reader = re.findall(r"\bgetenv\s*\(([^)]*)\)", _reader())
-    assert len(reader) >= 13 and all(re.fullmatch(r'"NTRACER_\w+"', a) for a in reader), reader
+    assert sorted(reader) == sorted('"%s"' % k for k in RENDER_SWITCHES), reader
     for name in sorted(os.listdir(CSRC)):
         calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", _read(name))
         want = {"nt_api.cpp": reader, "nt_builder.cpp": ['"NTRACER_BUILD_THREADS"']}.get(name, [])

@@ -1418,38 +1418,35 @@ def test_camera_table_renders_the_same_frames():
     assert torch.equal(x, y)
 
 
-def test_box_kernel_paths_alternate_on_one_scene(monkeypatch):
-    """The packed-RGB formats normally take the fused tile kernel; NTRACER_BOX_PATH=0 selects the older cull -> box -> redo
-    kernels, which share the scene's scratch buffer with it (the fused path keeps a bitmap there that must be all zero between
-    launches).  The same frames on ONE scene through path 0, the fused path and path 0 again -- and the fused path with rows
-    interleaved and not -- byte for byte like the oracle, in 6 and in 10 dimensions (with and without a second kernel)."""
+def test_box_fused_and_general_paths_alternate_on_one_scene(monkeypatch):
+    """Packed RGB takes the fused tile kernel, RGB16 the cull and general kernels, and both use the scene's one scratch
+    buffer: the fused route keeps a bitmap there that must be all zero between launches, and the general route writes its
+    stretch codes over it.  The same frames on ONE scene through the two routes in turn -- the fused route with rows
+    interleaved and not -- byte for byte like the oracle in their own formats, in 6 and in 10 dimensions (with and without
+    a second kernel)."""
     import torch
     for n, name, W, H in ((6, "box_n6_1920x1080", 1920, 1080), (10, "box_n10_4096x4096", 1024, 640)):
         g = fx.load(name)
         sel = [3, 47, 101]
         o = np.ascontiguousarray(g["origins"][sel], np.float32)
         a = np.ascontiguousarray(g["axes"][sel], np.float32)
-        fmt = fmt_of(W, H, fx.RGBX8)
-        fst = fmt._as_struct()
-        refs = [ob.OracleScene(n, o[k], a[k]).render(W, H, fx.RGBX8, threads=8) for k in range(len(sel))]
+        chans = {"rgbx8": fx.RGBX8, "rgb16": fx.RGB16}
+        refs = {f: [ob.OracleScene(n, o[k], a[k]).render(W, H, c, threads=8) for k in range(len(sel))] for f, c in chans.items()}
         sc = tracern.BoxScene(n)
-        fb = torch.empty((len(sel), fmt.pitch * H), dtype=torch.uint8, device="cuda")
-        for path, il in (("0", None), (None, None), ("0", None), (None, "0"), (None, None), ("0", None)):
-            if path is None:
-                monkeypatch.delenv("NTRACER_BOX_PATH", raising=False)
-            else:
-                monkeypatch.setenv("NTRACER_BOX_PATH", path)
+        for f, il in (("rgb16", None), ("rgbx8", None), ("rgb16", None), ("rgbx8", "0"), ("rgbx8", None), ("rgb16", None)):
             if il is None:
                 monkeypatch.delenv("NTRACER_BOX_INTERLEAVE", raising=False)
             else:
                 monkeypatch.setenv("NTRACER_BOX_INTERLEAVE", il)
-            fb.fill_(0x5a)
+            fmt = fmt_of(W, H, chans[f])
+            fst = fmt._as_struct()
+            fb = torch.full((len(sel), fmt.pitch * H), 0x5a, dtype=torch.uint8, device="cuda")
             _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(fb.data_ptr()), fmt.pitch * H, len(sel), o.ctypes.data_as(_lib.f32p),
                                                           a.ctypes.data_as(_lib.f32p), C.byref(fst), None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
             torch.cuda.synchronize()
             got = fb.cpu().numpy().reshape(len(sel), H, fmt.pitch)
             for k in range(len(sel)):
-                assert np.array_equal(got[k], refs[k]), (n, path, il, k, int((got[k] != refs[k]).sum()))
+                assert np.array_equal(got[k], refs[f][k]), (n, f, il, k, int((got[k] != refs[f][k]).sum()))
 
 
 def test_render_calls_captured_in_a_hip_graph():

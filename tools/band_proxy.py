@@ -65,7 +65,7 @@ def measure(world, rank, band_rows, steps, warmup, frames=160, n=6, W=1920, H=10
     t_issue = time.perf_counter() - t0
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    return {"format": "rgbf32" if f32 else "rgbx8", "n": n, "box_path": os.environ.get("NTRACER_BOX_PATH", "1"), "world": world, "rank": rank, "band_rows": band_rows, "owned_rows": own, "frames": frames,
+    return {"format": "rgbf32" if f32 else "rgbx8", "n": n, "world": world, "rank": rank, "band_rows": band_rows, "owned_rows": own, "frames": frames,
             "event_us_per_call": round(e0.elapsed_time(e1) * 1e3 / steps, 2), "wall_us_per_call": round(wall * 1e6 / steps, 2),
             "host_issue_us_per_call": round(t_issue * 1e6 / steps, 2)}
 

@@ -12,4 +12,4 @@ for rep in 1 2; do
     python3 tools/band_proxy.py --world 1 --n 3 >> $out 2>&1
   done
 done
-grep "^{\|^#" $out | sed 's/"rank": 0, "band_rows": 8, //; s/"wall_us_per_call".*//; s/"box_path": "1", //'
+grep "^{\|^#" $out | sed 's/"rank": 0, "band_rows": 8, //; s/"wall_us_per_call".*//'
