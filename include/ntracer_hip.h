@@ -188,6 +188,23 @@ int nt_scene_get_camera(const nt_scene_t *s, float *origin, float *axes);
 /* Scene.set_fov / .fov (radians; default 0.8, tracer.hpp:91,1731) */
 int nt_scene_set_fov(nt_scene_t *s, float fov);
 float nt_scene_get_fov(const nt_scene_t *s);
+/* Supersampling (the reference has no counterpart: it draws one ray a pixel).  factor s = 1..8, default 1 = one ray a pixel,
+   nothing changes.  With s > 1 every render entry point draws, for a W x H image in any format, the box-filtered s*W x s*H
+   frame of the same scene, camera and fov: sample (i, j) of pixel (x, y) is pixel (s*x + i, s*y + j) of that frame in the
+   plain three-channel fp32 format, i.e. calculate_color's result with each component clamped to [0, 1]; the pixel's colour
+   is the fp32 sum of its s*s samples taken one after the other in row-major order, divided by (float)(s*s); that colour
+   then goes through the format's channel conversion and packing as always.  Both stages run on the device: the samples go
+   to a scratch buffer of at most nt_scene_set_supersampling_scratch_mb MiB (1..2^20, default 1024) per scene and device,
+   never more than the job needs, and larger jobs are cut into
+   frame chunks and, below one frame, into row chunks.  The samples of ONE output row, 12*s*s*W bytes, must fit that
+   buffer, and a sample row's 12*s*W bytes and the s*H sample rows must be countable in 31 bits: otherwise the render
+   fails with NT_E_UNSUPPORTED before anything is launched.  nt_calculate_color / nt_colors_at answer for one ray and
+   ignore the factor.  A view setting like fov: not part of a pickled scene.  NT_E_INVALID for a factor outside 1..8,
+   NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it. */
+int nt_scene_set_supersampling(nt_scene_t *s, int factor);
+int nt_scene_get_supersampling(const nt_scene_t *s);
+int nt_scene_set_supersampling_scratch_mb(nt_scene_t *s, int mib);
+int nt_scene_get_supersampling_scratch_mb(const nt_scene_t *s);
 /* CompositeScene.set_shadows/set_camera_light/set_max_reflect_depth/set_ambient_color/
    set_background/add_light rolled into one call */
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p);

@@ -103,6 +103,10 @@ SYMBOLS = [
     ("nt_scene_get_camera", C.c_int, [C.c_void_p, f32p, f32p]),
     ("nt_scene_set_fov", C.c_int, [C.c_void_p, C.c_float]),
     ("nt_scene_get_fov", C.c_float, [C.c_void_p]),
+    ("nt_scene_set_supersampling", C.c_int, [C.c_void_p, C.c_int]),
+    ("nt_scene_get_supersampling", C.c_int, [C.c_void_p]),
+    ("nt_scene_set_supersampling_scratch_mb", C.c_int, [C.c_void_p, C.c_int]),
+    ("nt_scene_get_supersampling_scratch_mb", C.c_int, [C.c_void_p]),
     ("nt_scene_set_params", C.c_int, [C.c_void_p, C.POINTER(NtSceneParams)]),
     ("nt_scene_lock", C.c_int, [C.c_void_p]),
     ("nt_scene_unlock", C.c_int, [C.c_void_p]),

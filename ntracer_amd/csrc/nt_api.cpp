@@ -103,6 +103,7 @@ struct DeviceState {
     DevBuf framebuffer, cams, probes, stats, counter;
     DevBuf hits;                         // primary-hit records between the two passes of a lit render
     DevBuf stats_frame;                  // where the statistics launch of a "faithful" scene draws (discarded)
+    DevBuf samples;                      // supersampling: the fp32 x 3 samples between the render and the resolve kernel
     DevBuf numer;                        // packet kernel: -(N.o + d) per (frame, simplex)
     DevBuf cull;                         // BoxScene: row culling bits
     bool cull_clean = false;             // `cull` is all zero (what the fused BoxScene path needs and leaves behind)
@@ -141,6 +142,8 @@ struct nt_scene {
     int locked = 0;
     bool busy = false;
     float fov = 0.8f;                    // tracer.hpp:91,1731
+    int supersampling = 1;               // s x s samples a pixel (nt_scene_set_supersampling; the reference has none)
+    int ss_scratch_mb = 1024;            // ... and the cap of their scratch buffer, MiB per device (nt_scene_set_supersampling_scratch_mb)
     std::vector<float> origin, axes;     // camera<Store>: origin[n], t_orientation[n][n] (camera.hpp:7-15)
 
     // composite_scene (tracer.hpp:1713-1740)
@@ -578,6 +581,7 @@ struct FrameJob {
     const int *abort_word = nullptr;   // NtTarget::abort_word
     int overlapped = 0;                // nt_render_opts::overlapped
     bool counters_pass = false;        // (enqueue's own) the statistics launch of a scene whose pixels come from the faithful kernels
+    bool samples_pass = false;         // (enqueue's own) the first stage of a supersampled render: the s*W x s*H samples
     int row_begin, row_count; // owned-row range
     // probe mode
     float *colors_out = nullptr;
@@ -761,31 +765,8 @@ int plan_box(const nt_scene *s, DeviceState *ds, const FrameJob &job, const Rend
     return NT_OK;
 }
 
-int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
-    const RenderSwitches sw = read_switches();
-    FrameJob job = job_in;
-    if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
-        // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
-        // handling (below), which keep no counters.  Asking for statistics must not change the pixels: the frame is drawn as
-        // always, and the counters come from a launch of their own -- the counting kernel (a hit keeps the normal of what
-        // was hit, 16-slot mailbox) into a scratch frame.  They describe THAT traversal: the same tree and cells, a few
-        // repeated tests after mailbox evictions.  Transparent materials have no counting kernel at all: refused.
-        if (s->n > NT_MAX_FIXED_DIM) return fail(NT_E_UNSUPPORTED, "collect_stats is not available above %d dimensions (the run-time-n kernels keep no counters)", NT_MAX_FIXED_DIM);
-        if (!s->all_opaque)
-            return fail(NT_E_UNSUPPORTED, "collect_stats is not available for scenes with transparent materials (their kernels keep no counters)");
-        if (s->n_solids > 0 && !sw.clean_normals) {
-            const size_t bytes = (size_t)job.fmt->pitch * (size_t)(job.bands.compact ? job.bands.owned_rows : job.fmt->height);
-            if (int e = ds->stats_frame.ensure(std::max<size_t>(bytes, 16))) return e;
-            FrameJob cj = job;
-            cj.counters_pass = true;
-            cj.dest_dev = ds->stats_frame.p;
-            cj.frame_stride = 0;
-            if (job.nframes > 1) return fail(NT_E_UNSUPPORTED, "collect_stats on a multi-frame launch is not available for scenes with Solids");
-            if (int e = enqueue(s, ds, cj)) return e;
-            job.stats = false;
-        }
-    }
-    NtTarget tg;
+// where the pixels of a job go: the view, the format's packing constants, the band split and the owned-row range
+int fill_target(const nt_scene *s, DeviceState *ds, const FrameJob &job, NtTarget &tg) {
     std::memset(&tg, 0, sizeof(tg));
     if (job.colors_out) {
         fill_view(tg, s, job.view_w, job.view_h);
@@ -834,8 +815,103 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
         tg.row_count = job.row_count;
         tg.aligned4 = ((uintptr_t)job.dest_dev % 4 == 0) && (f.pitch % 4 == 0) && (job.frame_stride % 4 == 0);
         tg.abort_word = job.abort_word;
-        if (tg.row_count <= 0 || f.bpp == 0) return NT_OK;      // nothing to draw
     }
+    return NT_OK;
+}
+
+int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in);
+
+// A supersampled render (nt_scene_set_supersampling), in two stages per chunk: the job once more at s*W x s*H
+// in the plain fp32 x 3 format -- the caller's owned rows [r, r + c) are sample rows [s*r, s*(r + c)) of a split into bands
+// of s*band_rows rows, same rank and world -- into the scratch buffer, then resolve_kernel into the caller's `dest`, where
+// the single-sample kernels would have written.  The scratch is capped (nt_scene_set_supersampling_scratch_mb): the job is cut into chunks
+// of whole frames and, when one frame's samples are too many, into chunks of rows, each rendered and resolved before the
+// next on the same stream.  Everything else (strict_reference, overlapped, the abort word, the counters) passes through.
+int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
+    const int ss = s->supersampling;
+    const Format &f = *job.fmt;
+    if (job.row_count <= 0 || f.bpp == 0) return NT_OK;         // nothing to draw
+    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const long long hi_w = (long long)ss * f.width, hi_h = (long long)ss * f.height;
+    const long long hi_pitch = 12 * hi_w;                        // bytes a sample row
+    const long long row_bytes = hi_pitch * ss;                   // the samples of one output row
+    if (hi_pitch > INT_MAX || hi_h > INT_MAX)
+        return fail(NT_E_UNSUPPORTED, "supersampling %d of a %d x %d image: the %lld x %lld samples are beyond the 2^31 - 1 bytes a sample row "
+                    "and the 2^31 - 1 sample rows the kernels address", ss, f.width, f.height, hi_w, hi_h);
+    if (row_bytes > cap)
+        return fail(NT_E_UNSUPPORTED, "supersampling %d of a %d pixel wide image: the samples of one row (%lld bytes) do not fit the scratch "
+                    "buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", ss, f.width, row_bytes, cap >> 20);
+    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
+    const nt_image_format hi_desc = {(int32_t)hi_w, (int32_t)hi_h, 0, 3, plain, 0};
+    Format hf;
+    if (int r = parse_format(&hi_desc, hf)) return r;
+    // (16384 rows at most: the grids of the two stages count rows in their y)
+    const long long rows_fit = std::min<long long>(cap / row_bytes, 16384);
+    const int chunk_rows = (int)std::min<long long>(rows_fit, job.row_count);
+    const int chunk_frames = chunk_rows < job.row_count ? 1 : (int)std::max<long long>(1, std::min<long long>(job.nframes, cap / (row_bytes * chunk_rows)));
+    if (int e = ds->samples.ensure((size_t)chunk_frames * chunk_rows * row_bytes)) return e;
+    NtTarget tg;
+    if (int r = fill_target(s, ds, job, tg)) return r;
+    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
+        const int nf = std::min(chunk_frames, job.nframes - f0);
+        for (int r0 = 0; r0 < job.row_count; r0 += chunk_rows) {
+            const int rc = std::min(chunk_rows, job.row_count - r0);
+            FrameJob hj = job;
+            hj.samples_pass = true;
+            hj.fmt = &hf;
+            hj.bands.rows = ss * job.bands.rows;
+            hj.bands.compact = 1;
+            hj.bands.owned_rows = ss * job.bands.owned_rows;
+            hj.row_begin = ss * (job.row_begin + r0);
+            hj.row_count = ss * rc;
+            hj.nframes = nf;
+            hj.frame_stride = (size_t)(rc * row_bytes);
+            // (compact: owned sample row o of a frame lies at o * pitch, and the chunk's first one at the start of the scratch)
+            hj.dest_dev = (char *)ds->samples.p - (long long)hj.row_begin * hi_pitch;
+            if (job.cam_buf) {
+                hj.cam_buf = job.cam_buf + (size_t)f0 * 4 * s->n;
+                hj.cam_dots = job.cam_dots + (size_t)f0 * 4;
+            }
+            if (int e = enqueue(s, ds, hj)) return e;
+            NtTarget rt = tg;
+            rt.dest = tg.dest + (long long)f0 * tg.frame_stride;
+            rt.row_begin = job.row_begin + r0;
+            rt.row_count = rc;
+            const int r = nt_launch_resolve(ss, job.stream, ds->samples.p, (long long)hj.frame_stride, hi_pitch, nf, rt);
+            if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        }
+    }
+    return NT_OK;
+}
+
+int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
+    const RenderSwitches sw = read_switches();
+    FrameJob job = job_in;
+    if (s->supersampling > 1 && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_supersampled(s, ds, job);
+    if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
+        // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
+        // handling (below), which keep no counters.  Asking for statistics must not change the pixels: the frame is drawn as
+        // always, and the counters come from a launch of their own -- the counting kernel (a hit keeps the normal of what
+        // was hit, 16-slot mailbox) into a scratch frame.  They describe THAT traversal: the same tree and cells, a few
+        // repeated tests after mailbox evictions.  Transparent materials have no counting kernel at all: refused.
+        if (s->n > NT_MAX_FIXED_DIM) return fail(NT_E_UNSUPPORTED, "collect_stats is not available above %d dimensions (the run-time-n kernels keep no counters)", NT_MAX_FIXED_DIM);
+        if (!s->all_opaque)
+            return fail(NT_E_UNSUPPORTED, "collect_stats is not available for scenes with transparent materials (their kernels keep no counters)");
+        if (s->n_solids > 0 && !sw.clean_normals) {
+            const size_t bytes = (size_t)job.fmt->pitch * (size_t)(job.bands.compact ? job.bands.owned_rows : job.fmt->height);
+            if (int e = ds->stats_frame.ensure(std::max<size_t>(bytes, 16))) return e;
+            FrameJob cj = job;
+            cj.counters_pass = true;
+            cj.dest_dev = ds->stats_frame.p;
+            cj.frame_stride = 0;
+            if (job.nframes > 1) return fail(NT_E_UNSUPPORTED, "collect_stats on a multi-frame launch is not available for scenes with Solids");
+            if (int e = enqueue(s, ds, cj)) return e;
+            job.stats = false;
+        }
+    }
+    NtTarget tg;
+    if (int r = fill_target(s, ds, job, tg)) return r;
+    if (!job.colors_out && (tg.row_count <= 0 || tg.bpp == 0)) return NT_OK;      // nothing to draw
     NtCamera cam;
     cam.buf = job.cam_buf;
     cam.dots = job.cam_dots;
@@ -1032,7 +1108,7 @@ void nt_scene_destroy(nt_scene_t *s) {
         (void)hipDeviceSynchronize();
         for (DevBuf *b : {&ds->nodes, &ds->items, &ds->batch_recs, &ds->batch_mats, &ds->tri_recs, &ds->tri_mats, &ds->solid_recs,
                           &ds->solid_types, &ds->solid_mats, &ds->materials, &ds->aabb, &ds->lights, &ds->framebuffer, &ds->cams, &ds->counter,
-                          &ds->probes, &ds->stats, &ds->hits, &ds->stats_frame, &ds->numer, &ds->cull, &ds->checked, &ds->tframes, &ds->ties})
+                          &ds->probes, &ds->stats, &ds->hits, &ds->stats_frame, &ds->samples, &ds->numer, &ds->cull, &ds->checked, &ds->tframes, &ds->ties})
             b->release();
         for (auto &t : ds->chan_tables) if (t->dev) (void)hipFree(t->dev);
         for (auto &t : ds->row_tables) if (t->dev) (void)hipFree(t->dev);
@@ -1078,6 +1154,28 @@ int nt_scene_set_fov(nt_scene_t *s, float fov) {
 }
 
 float nt_scene_get_fov(const nt_scene_t *s) { return s ? s->fov : 0.0f; }
+
+int nt_scene_set_supersampling(nt_scene_t *s, int factor) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (factor < 1 || factor > 8) return fail(NT_E_INVALID, "the supersampling factor must be between 1 and 8");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->supersampling = factor;
+    return NT_OK;
+}
+
+int nt_scene_get_supersampling(const nt_scene_t *s) { return s ? s->supersampling : fail(NT_E_INVALID, "scene is NULL"); }
+
+int nt_scene_set_supersampling_scratch_mb(nt_scene_t *s, int mib) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (mib < 1 || mib > (1 << 20)) return fail(NT_E_INVALID, "the supersampling scratch cap must be between 1 and %d MiB", 1 << 20);
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->ss_scratch_mb = mib;
+    return NT_OK;
+}
+
+int nt_scene_get_supersampling_scratch_mb(const nt_scene_t *s) { return s ? s->ss_scratch_mb : fail(NT_E_INVALID, "scene is NULL"); }
 
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");

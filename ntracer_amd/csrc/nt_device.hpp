@@ -207,6 +207,10 @@ static inline NtBoxTileGeom nt_box_tile_geom(int width, int row_count, int nfram
 
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
+// resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
+// of `nframes` frames -- 12-byte fp32 x 3 pixels as the render kernels write them, s * tg.row_count rows of `pitch_bytes` a frame
+// -- averaged and packed into tg.dest
+int nt_launch_resolve(int s, void *stream, const void *samples, long long frame_stride_bytes, long long pitch_bytes, int nframes, const NtTarget &tg);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

@@ -2,6 +2,7 @@
 // [k][lane]) and the dispatch over the dimension: nt_launch_box / nt_launch_composite.
 #include "nt_box.hpp"
 #include "nt_composite.hpp"
+#include "nt_resolve.hpp"
 
 // compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
 #define NT_DECLARE_FIXED(N)                                                                              \
@@ -1583,6 +1584,11 @@ __global__ __launch_bounds__(256) void upload_kernel(const float *__restrict__ s
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count) {
     hipLaunchKernelGGL(upload_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src_pinned, dst, count);
     return finish_launch("camera upload");
+}
+
+// the box filter of a supersampled render (nt_resolve.hpp)
+int nt_launch_resolve(int s, void *stream, const void *samples, long long frame_stride_bytes, long long pitch_bytes, int nframes, const NtTarget &tg) {
+    return launch_resolve_any(s, (hipStream_t)stream, samples, frame_stride_bytes, pitch_bytes, nframes, tg);
 }
 
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg) {

@@ -580,6 +580,31 @@ class _SceneBase(Scene):
     def set_fov(self, fov):
         _lib.check(_lib.lib().nt_scene_set_fov(self._handle, float(fov)))
 
+    @property
+    def supersampling(self):
+        """s: every pixel is the mean of s x s rays (1: one ray a pixel, the reference's only mode)"""
+        return int(_lib.lib().nt_scene_get_supersampling(self._handle))
+
+    def set_supersampling(self, factor):
+        """Render with factor x factor samples a pixel (1..8), box-filtered on the device: the s*W x s*H frame of the same view,
+        each sample's colour clamped to [0, 1], averaged in fp32 and packed as always.  A view setting like
+        fov: not pickled.  Probes (calculate_color, colors_at) answer for one ray."""
+        if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)):
+            raise ValueError("the supersampling factor must be an integer between 1 and 8")
+        _lib.check(_lib.lib().nt_scene_set_supersampling(self._handle, int(factor)))
+
+    @property
+    def supersampling_scratch_mb(self):
+        """cap of the device buffer that holds the samples, MiB per device (default 1024)"""
+        return int(_lib.lib().nt_scene_get_supersampling_scratch_mb(self._handle))
+
+    def set_supersampling_scratch_mb(self, mib):
+        """A supersampled job whose samples (12 * s * s bytes a pixel) exceed the cap is rendered in chunks of frames and,
+        below one frame, of rows -- same pixels; the samples of one row must fit."""
+        if isinstance(mib, bool) or not isinstance(mib, (int, np.integer)):
+            raise ValueError("the supersampling scratch cap must be an integer number of MiB")
+        _lib.check(_lib.lib().nt_scene_set_supersampling_scratch_mb(self._handle, int(mib)))
+
     def set_camera(self, camera):
         if not isinstance(camera, Camera) or camera.dimension != self._n:
             raise TypeError("the scene and camera must have the same dimension")
@@ -767,6 +792,8 @@ class CompositeScene(_SceneBase):
                  items=np.asarray(leaf_items, np.int32), aabb_start=lo, aabb_end=hi)
         other = CompositeScene.from_flat(n, d)
         other.set_fov(self.fov)
+        other.set_supersampling(self.supersampling)
+        other.set_supersampling_scratch_mb(self.supersampling_scratch_mb)
         other._push(_pl=list(self._point_lights), _gl=list(self._global_lights), **dict(self._p))
         cam = self.get_camera()
         other._set_camera_arrays(cam._origin, cam._axes)

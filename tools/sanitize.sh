@@ -2,7 +2,7 @@
 # Sanitizer runs of the HOST code (never on the GPU: GPU ASan is not available on this pool):   tools/sanitize.sh [log]
 #   1. oracle (the checker, plain C + pthreads): ASan + UBSan under its golden tests; TSan on its renderer pool
 #   2. host side of libntracer_hip.so (nt_api.cpp, nt_builder.cpp, nt_launch.cpp; kernels stubbed: tools/sanitize/kernel_stubs.cpp):
-#      ASan + UBSan under the CPU test files that drive it (ABI, host API, builder, reference suite, pickling);
+#      ASan + UBSan under the CPU test files that drive it (ABI, host API, builder, reference suite, pickling, the supersampling factor);
 #      TSan on the threaded k-d builder
 # Everything is built under build_ab/san/ (git-ignored).  Zero reports = every step prints OK.
 log=${1:-profiles/r03_sanitizers.log}
@@ -35,7 +35,7 @@ HOSTSRC="ntracer_amd/csrc/nt_api.cpp ntracer_amd/csrc/nt_builder.cpp ntracer_amd
 g++ -O1 -g -std=c++17 -fPIC -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -fsanitize=address,undefined -fno-omit-frame-pointer -shared \
     -o $out/libntracer_host_asan.so $HOSTSRC -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib || exit 1
 run host_asan_tests env LD_PRELOAD="$ASAN $UBSAN" ASAN_OPTIONS=detect_leaks=0 NTRACER_HIP_LIB=$out/libntracer_host_asan.so NTRACER_HIP_SYSTEM_RUNTIME=1 \
-    python3 -m pytest tests/test_abi.py tests/test_host_api.py tests/test_builder.py tests/test_reference_suite.py tests/test_pickle.py -q -x -m "not gpu" -p no:cacheprovider
+    python3 -m pytest tests/test_abi.py tests/test_host_api.py tests/test_builder.py tests/test_reference_suite.py tests/test_pickle.py tests/test_supersampling_host.py -q -x -m "not gpu" -p no:cacheprovider
 g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -fno-omit-frame-pointer -o $out/builder_asan tools/sanitize/builder_driver.cpp ntracer_amd/csrc/nt_builder.cpp tools/sanitize/last_error_stub.cpp || exit 1
 run builder_asan_driver env ASAN_OPTIONS=detect_leaks=1 $out/builder_asan 6000
 say "## threaded k-d builder: -fsanitize=thread"

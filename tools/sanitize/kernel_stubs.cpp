@@ -11,5 +11,6 @@ static int no_kernels() {
 }
 int nt_launch_box(const NtLaunchInfo &, const NtCamera &, const NtTarget &) { return no_kernels(); }
 int nt_launch_composite(const NtLaunchInfo &, const NtCamera &, const NtCompositeDev &, const NtTarget &) { return no_kernels(); }
+int nt_launch_resolve(int, void *, const void *, long long, long long, int, const NtTarget &) { return no_kernels(); }
 int nt_launch_upload(void *, const float *, float *, int) { return no_kernels(); }
 int nt_var_frame_words(int n) { return 4 * n + 16; }
