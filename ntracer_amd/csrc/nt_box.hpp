@@ -176,6 +176,91 @@ __device__ __forceinline__ void box_classify(const float (&o)[N], const float (&
     x = hit ? vK : v[0];
 }
 
+// v_max_f32 / v_min_f32 as they are (box_stretch_code2, box_classify_sets): fmaxf / fminf on a value that reaches them from another basic block come with a
+// canonicalising `v_max_f32 x, x, x` per operand (the compiler cannot see that the value is the result of arithmetic), and
+// these instructions run at half the rate of a multiply: an eighth of box_stretch_code2's instructions were such no-ops.
+// Quiet NaNs drop out of the hardware's max / min as they do out of fmaxf / fminf; every operand here is the result of
+// arithmetic or an infinity.
+__device__ __forceinline__ float nt_vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float nt_vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float nt_vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+__device__ __forceinline__ float nt_vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+__device__ __forceinline__ float nt_vmed3(float a, float b, float c) { float r; asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+__device__ __forceinline__ float nt_vmax_abs(float a, float b) { float r; asm("v_max_f32 %0, |%1|, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }   // max(|a|, b)
+
+// box_classify for a row sorted ray by ray (code 15) whose stretch has valid sets (box_stretch_code2: T in bits 0..9, C in bits
+// 10..19, wave-uniform): the same three verdicts from T's entry planes and C's coordinates alone -- |C| reciprocals, slab updates
+// and inside terms instead of N (BoxScene(6)'s bench cameras: |T| = 1.6, |C| = 2.8 on average; in 60 % of these rows T is one
+// face).  Axes are picked by scalar tests on `sets`; there is nothing per lane.  Why nothing is lost, with A_j <= near_j <= B_j
+// the range of slab j's entry over the stretch, TN = max A_j, M >= m/|v_K| (see box_stretch_code2) and tn, tn2, vK, tnp, tfp
+// as in box_classify:
+//   last axis     a ray's last entry axis K has B_K >= near_K = tn >= TN, so K is in T: tn and vK over T are tn and vK over
+//                 all axes.
+//   second entry  an axis outside T has near_j <= B_j < TN - M <= tn - m/|v_K| (M carries 1 + 1e-5 for the arithmetic): it is
+//                 neither within the `sole` margin of tn nor -- its grown entry lies before the unit one -- the grown cube's
+//                 last entry.  `sole` and tnp over T are the full ones (tn2 = -inf for a single face: sole).
+//   inside sum    a coordinate outside C stays inside 1 - m - 1e-4 < c over [t_lo, t_hi], which holds every ray's tn: its term
+//                 of box_classify's sum is exactly c, and the sum over C against |C|*c is the full sum against N*c.
+//   miss          tfp over C is at least the full tfp and tnp over T at most the full tnp: a miss here is a miss there, never
+//                 the other way round.  (A ray that does miss leaves through a slab whose coordinate is outside 1 at tn: one of C.)
+// So "hit at K" and "miss" are verdicts box_classify gives too, and everything else is unclear.  There are no entry times of
+// all N axes for box_resolve afterwards: a wave with an unclear lane takes the reference's arithmetic on the stretch's T and C
+// (box_pixel's sets branch), which is right for every ray of the stretch, and keeps its answer for every lane.
+// For N = 6 and 7 (-DNT_BOX_CLASSIFY_SETS_MAX_N=0: nowhere, the build to measure against).  Measured against the build without it,
+// alternately on one box, 160 frames of 1080p a call: BoxScene(6), the bench's cameras, 338.5 -> 331.3 us a call;
+// BoxScene(7), random cameras, +0.8 % rays a second; BoxScene(5) even; BoxScene(3) and (4) 4-5 % SLOWER -- with three or four
+// slabs there is little to restrict, and the unclear lanes' route through the stretch's sets costs more than box_resolve's
+// per-lane ones.  Every tile kernel it is in needs one to four more VGPRs, which at N = 6 and 7 stays on the occupancy step the
+// kernel is on (n = 6, 64 x 1: 71 -> 72, seven waves).  At N = 8 it does not: 79 -> 83 (16-row shapes) and 80 -> 82 (fp32,
+// 64 x 1) cross 80, six waves a SIMD to five.
+#ifndef NT_BOX_CLASSIFY_SETS_MIN_N
+#define NT_BOX_CLASSIFY_SETS_MIN_N 6
+#endif
+#ifndef NT_BOX_CLASSIFY_SETS_MAX_N
+#define NT_BOX_CLASSIFY_SETS_MAX_N 7
+#endif
+template <int N>
+__device__ __forceinline__ void box_classify_sets(const float (&o)[N], const float (&v)[N], float m, uint32_t sets, bool &hit, bool &unclear,
+                                                  float &x) {
+    // (nt_vmax & co.: these values cross basic blocks -- see there; the empty asm keeps the compiler from turning a skipped axis
+    // into computed-and-discarded)
+    float tn = -INFINITY, tn2 = -INFINITY, vK = 0.0f;
+    float tnp = -INFINITY, tfp = INFINITY;
+    const float m1p = 1.0f + m;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        if (((sets >> (10 + j)) & 1u) != 0u) {
+            const float inv = __builtin_amdgcn_rcpf(v[j]);
+            const float c0 = -o[j] * inv;
+            tfp = nt_vmin(tfp, fmaf(fabsf(inv), m1p, c0));
+            if (((sets >> j) & 1u) != 0u) {
+                const float nr = c0 - fabsf(inv);
+                tnp = nt_vmax(tnp, fmaf(-fabsf(inv), m1p, c0));
+                const bool later = nr > tn;
+                tn2 = nt_vmed3(tn, tn2, nr);
+                vK = later ? v[j] : vK;
+                tn = nt_vmax(tn, nr);
+            }
+        }
+    }
+    const bool miss = tnp > tfp || tfp < 0.0f;
+    const float c = 1.0f - m;
+    float sum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        if (((sets >> (10 + j)) & 1u) != 0u) {
+            asm volatile("" : "+v"(sum));
+            sum = sum + nt_vmax_abs(fmaf(v[j], tn, o[j]), c);
+        }
+    }
+    const bool inside = sum - (float)__builtin_popcount((sets >> 10) & 0x3ffu) * c <= 1.5f * m;
+    const bool sole = (tn - tn2) * fabsf(vK) > m;
+    const bool front = tn > 1e-3f && tn < 1e30f;
+    hit = !miss && inside && sole && front;
+    unclear = !miss && !hit;
+    x = hit ? vK : v[0];
+}
+
 // The part of box_classify that box_resolve needs: entry times into the unit cube, the last of them, its axis.
 template <int N>
 __device__ __forceinline__ void box_entries(const float (&o)[N], const float (&v)[N], float (&near)[N], float &tn, float &vK) {
@@ -335,13 +420,12 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
     float x = dir[0];
 #ifndef NT_EXP_NOCLASSIFY
     float near[N], tn = 0.0f, vK = 0.0f;
-    if (face >= 0) {
-        hit = true;
-#pragma unroll
-        for (int j = 1; j < N; ++j) x = face == j ? dir[j] : x;
-    } else if ((REDO || INL) && redo && (sets & 0x80000000u) != 0u) {
-        // sets (wave-uniform, box_tile_kernel's near-tie stretches): T and C of the whole stretch from the codes wave
-        // (box_stretch_code, through LDS) -- the reference's arithmetic on them, as in box_resolve, without the entry times
+    // sets (wave-uniform, box_tile_kernel): T and C of the whole stretch from the codes wave (box_stretch_code2, through LDS).
+    // A near-tie stretch goes straight to the reference's arithmetic on them; a stretch sorted ray by ray is sorted on them
+    // (box_classify_sets) and goes there only with an unclear lane.
+    constexpr bool CSETS = INL && N >= NT_BOX_CLASSIFY_SETS_MIN_N && N <= NT_BOX_CLASSIFY_SETS_MAX_N;
+    // the reference's arithmetic on T and C, as in box_resolve, without the entry times
+    auto exact_on_sets = [&]() {
         const float len = sqrt_wave(sq);
         float d[N];
 #pragma unroll
@@ -371,11 +455,45 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
                 }
             }
         }
-    } else if (redo) {
-        box_entries<N>(org, dir, near, tn, vK);
-        unclear = true;
-    } else if (__builtin_amdgcn_ballot_w64(maybe) != 0ull) {
-        box_classify<N>(org, dir, margin, maybe, hit, unclear, x, near, tn, vK);
+    };
+    if constexpr (CSETS) {
+        const bool have_sets = face < 0 && (sets & 0x80000000u) != 0u;
+        bool on_sets = have_sets && redo;
+        bool sorted = face >= 0;                   // (wave-uniform) nothing left to classify
+        if (face >= 0) {
+            hit = true;
+#pragma unroll
+            for (int j = 1; j < N; ++j) x = face == j ? dir[j] : x;
+        } else if (have_sets && !redo && __builtin_amdgcn_ballot_w64(maybe) != 0ull) {
+            box_classify_sets<N>(org, dir, margin, sets, hit, unclear, x);
+            on_sets = __builtin_amdgcn_ballot_w64(unclear) != 0ull;
+            unclear = false;
+            sorted = true;
+        }
+        if (on_sets) {
+            hit = false;
+            exact_on_sets();
+        } else if (sorted) {
+        } else if (redo) {
+            box_entries<N>(org, dir, near, tn, vK);
+            unclear = true;
+        } else if (__builtin_amdgcn_ballot_w64(maybe) != 0ull) {
+            box_classify<N>(org, dir, margin, maybe, hit, unclear, x, near, tn, vK);
+        }
+    } else {
+        // (as it was before there was a box_classify_sets: the device code of these dimensions has not changed)
+        if (face >= 0) {
+            hit = true;
+#pragma unroll
+            for (int j = 1; j < N; ++j) x = face == j ? dir[j] : x;
+        } else if ((REDO || INL) && redo && (sets & 0x80000000u) != 0u) {
+            exact_on_sets();
+        } else if (redo) {
+            box_entries<N>(org, dir, near, tn, vK);
+            unclear = true;
+        } else if (__builtin_amdgcn_ballot_w64(maybe) != 0ull) {
+            box_classify<N>(org, dir, margin, maybe, hit, unclear, x, near, tn, vK);
+        }
     }
     // unclear lanes: the reference's arithmetic on the faces and coordinates still in question; a lane without a
     // usable entry time (origin on or inside the cube, NaN) keeps the whole wave on box_color's full evaluation
@@ -623,17 +741,6 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
 // stretch's directions, passes every test made there: the others, and T itself, are C.  (A face of T that a given ray
 // enters long before its last entry fails at that ray's last axis, which is in T, hence in C.)  No valid sets when a candidate's v_j
 // changes sign in the stretch or TN - M is not clearly positive (rays starting on or in the cube: box_color's business).
-// v_max_f32 / v_min_f32 as they are: fmaxf / fminf on a value that reaches them from another basic block come with a
-// canonicalising `v_max_f32 x, x, x` per operand (the compiler cannot see that the value is the result of arithmetic), and
-// these instructions run at half the rate of a multiply: an eighth of box_stretch_code's instructions were such no-ops.
-// Quiet NaNs drop out of the hardware's max / min as they do out of fmaxf / fminf; every operand here is the result of
-// arithmetic or an infinity.
-__device__ __forceinline__ float nt_vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float nt_vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float nt_vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float nt_vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float nt_vmed3(float a, float b, float c) { float r; asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
 template <int N, bool SETS = false>
 __device__ __forceinline__ unsigned long long box_stretch_code2(const float (&org)[N], const float (&right)[N], const float (&up)[N],
                                                                 const float (&fwd)[N], const NtTarget &tg, int y, int col) {
