@@ -246,6 +246,12 @@ __device__ __forceinline__ void box_classify_sets(const float (&o)[N], const flo
     const bool miss = tnp > tfp || tfp < 0.0f;
     const float c = 1.0f - m;
     float sum = 0.0f;
+    // (the second loop tests the bits of `sets` again: left to itself the compiler keeps the first loop's six outcomes as lane
+    // masks -- five scalar instructions a test instead of a bit test and a branch, and six register pairs held across the loops
+    // of a kernel that already parks scalar registers in a vector one; -DNT_EXP_SETS_MASKS: without, the build to measure against)
+#ifndef NT_EXP_SETS_MASKS
+    asm volatile("" : "+s"(sets));
+#endif
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         if (((sets >> (10 + j)) & 1u) != 0u) {
@@ -934,6 +940,17 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
 #ifndef NT_BOX_PIN_UP
 #define NT_BOX_PIN_UP 1
 #endif
+// The packed-RGB lean loops take aligned groups of four slots at once where all four rows are culled, or all four are the one
+// face K0: one scalar load and one wait for the four table entries, one branch on the four guards, one instruction to clear the
+// four bits -- the vector arithmetic of every row is the one-row loop's (-DNT_BOX_LEAN_GROUPS_MAX_N=0: nowhere, the build to measure against)
+#ifndef NT_BOX_LEAN_GROUPS_MIN_N
+#define NT_BOX_LEAN_GROUPS_MIN_N 3
+#endif
+// (up to N = 20: beyond, the tile kernels are held to 168 VGPRs and already spill to scratch, and the group body's sixteen live
+// values a lane would spill more)
+#ifndef NT_BOX_LEAN_GROUPS_MAX_N
+#define NT_BOX_LEAN_GROUPS_MAX_N 20
+#endif
 template <int N, bool F32, int ROWS, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCameraFixed cam, NtTarget tg) {
     static_assert(ROWS == 8 || ROWS == 16 || ROWS == 32 || ROWS == 64, "sixteen row codes to a qword, one to four qwords a wave");
@@ -1054,6 +1071,12 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
     if (wfirst < tg.row_count) {
         typedef uint32_t nt_u32x4 __attribute__((ext_vector_type(4)));
         typedef __attribute__((address_space(4))) const nt_u32x4 *nt_rowtab;
+        // four entries in a row (the table is in slot order): one s_load_dwordx16
+        typedef uint32_t nt_u32x16 __attribute__((ext_vector_type(16), aligned(16)));
+        typedef __attribute__((address_space(4))) const nt_u32x16 *nt_rowtab4;
+        // (LEAN4: the dimensions whose scalar control is the new one; the others keep the loops they had, instruction for instruction)
+        constexpr bool LEAN4 = N >= NT_BOX_LEAN_GROUPS_MIN_N && N <= NT_BOX_LEAN_GROUPS_MAX_N;
+        constexpr bool GROUPS = !F32 && LEAN4;
         uint8_t *const frame_base = tg.dest + (long long)frame * tg.frame_stride;
         // What a row loop needs to know about its row -- sy of the ray source and the row's byte offset in a frame -- comes
         // from a table the host wrote (NtTarget::rowtab, 16 bytes per owned row: sy, -, offset), read through the scalar
@@ -1065,12 +1088,15 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         // a store goes to (row pointer: scalar registers) + (the lane's byte offset in the row: 32 bits) -- the addressing
         // mode of global_store with an SGPR base, no vector arithmetic on addresses
 #define NT_ROW_PTR() uniform_ptr(frame_base + (long long)(((unsigned long long)row_e.w << 32) | row_e.z))
+        // ... of row k of a group of four (grp_e: its four entries)
+#define NT_GROUP_PTR(k) uniform_ptr(frame_base + (long long)(((unsigned long long)grp_e[4 * (k) + 3] << 32) | grp_e[4 * (k) + 2]))
         // (instruction selection works block by block and only recognises base + zero-extended 32-bit offset when it sees the
         // extension: the empty asm keeps it from being hoisted out of the row loops)
 #define NT_LANE_OFF() ({ asm volatile("" : "+v"(xoff)); xoff; })
         // mask &= ~(1 << bit) as ONE scalar instruction (the compiler writes mask & (mask - 1) as an add and an and): the lean loops
         // run about as many scalar instructions a row as vector ones
 #define NT_CLEAR_BIT(mask, bit) asm("s_bitset0_b32 %0, %1" : "+s"(mask) : "s"(bit))
+#define NT_SET_BIT(mask, bit) asm("s_bitset1_b32 %0, %1" : "+s"(mask) : "s"(bit))
         int x = (int)blockIdx.x * 64 + lane;
         x = x < tg.width ? x : tg.width - 1;
         uint32_t xoff = (uint32_t)x * (uint32_t)tg.bpp;
@@ -1118,6 +1144,21 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m)) >> (wv * R);
         };
         const unsigned long long rows_culled = rows_of(0), rows_face = rows_of(1), rows_rays = rows_of(2), rows_tie = rows_of(3);
+        // Which of the wave's rows exist: one slot per lane (lane l <-> slot wrow0 + l), once for all the wave's halves -- the
+        // band arithmetic and the launch parameters it reads stay out of the per-half loop, whose scalar registers are short.
+        // Every lane stays active in the row loops -- lanes past the right edge redo the last pixel (same bytes, same value)
+        // instead of leaving
+        unsigned long long rows_valid = 0ull;
+        if (LEAN4) {
+            const int lrow = il > 0 ? wfirst + il * lane : wrow0 + lane;
+            const int lorow = tg.row_begin + lrow;
+            int ly = lorow;
+            if (tg.band_world > 1) {
+                const int band = lorow / tg.band_rows;
+                ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
+            }
+            rows_valid = __builtin_amdgcn_ballot_w64(lane < R && lrow < tg.row_count && ly < tg.height);
+        }
 #pragma unroll 1
         for (int half = 0; half < HALVES; ++half) {
         const int row0 = wrow0 + 16 * half;                   // slot of the half's first row
@@ -1127,16 +1168,21 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         const int cw = (R >= 32 ? (R / 8) * wv + 2 * half : 2 * wv);
         unsigned long long rowcodes = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[cw + 1]) << 32) |
                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[cw]);
-        // Which of these rows exist: one row per lane (lane l <-> row row0 + l).  Every lane stays active in the row
-        // loops -- lanes past the right edge redo the last pixel (same bytes, same value) instead of leaving
-        const int lrow = il > 0 ? hfirst + il * lane : row0 + lane;
-        const int lorow = tg.row_begin + lrow;
-        int ly = lorow;
-        if (tg.band_world > 1) {
-            const int band = lorow / tg.band_rows;
-            ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
+        uint32_t valid;
+        if (LEAN4) {
+            valid = HALVES > 1 ? (uint32_t)(rows_valid >> (16 * half)) & 0xffffu : (uint32_t)rows_valid;
+        } else {
+            // Which of these rows exist: one row per lane (lane l <-> row row0 + l).  Every lane stays active in the row
+            // loops -- lanes past the right edge redo the last pixel (same bytes, same value) instead of leaving
+            const int lrow = il > 0 ? hfirst + il * lane : row0 + lane;
+            const int lorow = tg.row_begin + lrow;
+            int ly = lorow;
+            if (tg.band_world > 1) {
+                const int band = lorow / tg.band_rows;
+                ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
+            }
+            valid = (uint32_t)__builtin_amdgcn_ballot_w64(lane < RH && lrow < tg.row_count && ly < tg.height);
         }
-        const uint32_t valid = (uint32_t)__builtin_amdgcn_ballot_w64(lane < RH && lrow < tg.row_count && ly < tg.height);
         // (interleaved rows: the table is in slot order and belongs to this launch's row range)
         const nt_rowtab tab = (nt_rowtab)tg.rowtab + (il > 0 ? row0 : tg.row_begin + row0);
         // (bit rr <-> row row0 + rr; code 14 -- a near-tie stretch -- is not looked at here unless this kernel is all there is)
@@ -1161,19 +1207,8 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             // the test is made once here, not once a row)
             auto lean_rows = [&](auto sel8) {
             constexpr bool SEL8 = decltype(sel8)::value;
-            while (quick != 0u) {
-                const int rr = __builtin_ctz(quick);
-                NT_CLEAR_BIT(quick, rr);
-                NT_ROW_LOAD(rr);
-                const float d0 = base[0] - upv[0] * sy;                   // dir[0], bit for bit
-                const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                const float t = fabsf(d0) * __builtin_amdgcn_rsqf(sqa);          // (sqa is |dir|^2 / maxval^2)
-                const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f);
-                if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
-                    todo |= 1u << rr;                                             // a lane too close to a rounding boundary
-                    continue;
-                }
-                const nt_gptr out = NT_ROW_PTR() + NT_LANE_OFF();
+            // the packed pixel of a culled row (t: the guarded quotient, d0: dir[0]) and of a one-face row (t and its half)
+            auto put_quick = [&](nt_gptr out, float t, float d0) {
                 if (SEL8) {
                     // 8-bit fields: t + 2^23 has round(t) in its low mantissa byte (t < 255.5; the guard keeps t off the
                     // half-way points, so nearest-even is the reference's rounding), which is the byte v_perm_b32 picks
@@ -1182,14 +1217,119 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                     // select sat behind a wave-uniform branch -- its sign rarely changes within a stretch -- but the branch and
                     // the jump around it are scalar instructions, and the scalar unit is the busier one in this loop: 1.4 % of
                     // the headline call)
-                    const uint32_t w = __builtin_amdgcn_perm(d0 > 0.0f ? q : 0u, q, tg.plain_sel);
-                    NT_EXP_STORE_IF NT_G32(out) = w;
-                    continue;
+                    NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(d0 > 0.0f ? q : 0u, q, tg.plain_sel);
+                    return;
                 }
                 uint32_t q = (uint32_t)(t + 0.5f);
                 q = q < tg.plain_maxval ? q : tg.plain_maxval;
                 const uint32_t w = (d0 > 0.0f ? q : 0u) * tg.plain_mul[0] + q * (tg.plain_mul[1] + tg.plain_mul[2]);      // (emit_plain)
                 NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
+            };
+            auto put_face = [&](nt_gptr out, float t, float th) {
+                if (SEL8) {
+                    NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(__float_as_uint(t + 8388608.0f), __float_as_uint(th + 8388608.0f), tg.plain_sel);
+                    return;
+                }
+                uint32_t qr = (uint32_t)(t + 0.5f), qgb = (uint32_t)(th + 0.5f);
+                qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
+                qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
+                const uint32_t w = qr * tg.plain_mul[0] + qgb * (tg.plain_mul[1] + tg.plain_mul[2]);
+                NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
+            };
+            // bit 4k of the result: bits 4k .. 4k + 3 of the mask are all set
+            auto full_groups = [](uint32_t mask) { return mask & (mask >> 1) & (mask >> 2) & (mask >> 3) & 0x1111u; };
+            if (GROUPS) {
+                // Aligned groups of four culled rows.  Every row's arithmetic and its own guard as in the one-row loop below,
+                // nothing shared between rows; the four guards' outcomes stay scalar lane masks, and one branch decides for
+                // the four stores.  Otherwise the clear rows are stored one by one and the others handed on -- on the spot: a few per
+                // cent of the rows fail their guard, so one group in ten has such a row, and a build that sent those groups through
+                // the one-row loop again measured 1.2 % slower on the headline than one without groups.  Groups that are mixed or
+                // cut by `valid` are left to the one-row loop below.
+                uint32_t full = full_groups(quick);
+                quick &= ~(full * 15u);
+                while (full != 0u) {
+                    const int g = __builtin_ctz(full);
+                    NT_CLEAR_BIT(full, g);
+                    const nt_u32x16 grp_e = *(nt_rowtab4)(tab + g);
+                    float t[4], d0[4];
+                    unsigned long long fail[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float sy = __uint_as_float(grp_e[4 * k]);
+                        d0[k] = base[0] - upv[0] * sy;                        // dir[0], bit for bit
+                        const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
+                        t[k] = fabsf(d0[k]) * __builtin_amdgcn_rsqf(sqa);
+                        const bool clear = fabsf(__builtin_amdgcn_fractf(t[k]) - 0.5f) > fmaf(t[k], 0x1p-18f, 0x1p-18f);
+                        fail[k] = __builtin_amdgcn_ballot_w64(!clear);
+                    }
+                    if (__builtin_expect(((fail[0] | fail[1]) | (fail[2] | fail[3])) == 0ull, 1)) {
+                        const uint32_t xo = NT_LANE_OFF();
+                        put_quick(NT_GROUP_PTR(0) + xo, t[0], d0[0]);
+                        put_quick(NT_GROUP_PTR(1) + xo, t[1], d0[1]);
+                        put_quick(NT_GROUP_PTR(2) + xo, t[2], d0[2]);
+                        put_quick(NT_GROUP_PTR(3) + xo, t[3], d0[3]);
+                    } else {
+                        // (rare) the rows with a lane too close to a rounding boundary go on to the ray-by-ray loop
+                        todo |= ((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (fail[k] == 0ull) {
+                                uint32_t xo = xoff;
+                                asm volatile("" : "+v"(xo));
+                                put_quick(NT_GROUP_PTR(k) + xo, t[k], d0[k]);
+                            }
+                        }
+                    }
+                }
+                uint32_t quick_stored = 0u;
+                for (uint32_t rest = quick; rest != 0u;) {
+                    const int rr = __builtin_ctz(rest);
+                    NT_CLEAR_BIT(rest, rr);
+                    NT_ROW_LOAD(rr);
+                    const float d0 = base[0] - upv[0] * sy;                   // dir[0], bit for bit
+                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
+                    const float t = fabsf(d0) * __builtin_amdgcn_rsqf(sqa);          // (sqa is |dir|^2 / maxval^2)
+                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f);
+                    // (a row with a lane too close to a rounding boundary stores nothing and is not marked: the clear row is the
+                    // straight path, one branch taken a row where an if / else was laid out with three)
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!clear) == 0ull, 1)) {
+                        put_quick(NT_ROW_PTR() + NT_LANE_OFF(), t, d0);
+                        NT_SET_BIT(quick_stored, rr);
+                    }
+                }
+                todo |= quick & ~quick_stored;
+            } else {
+                // (the one-row loop as it was)
+                while (quick != 0u) {
+                    const int rr = __builtin_ctz(quick);
+                    NT_CLEAR_BIT(quick, rr);
+                    NT_ROW_LOAD(rr);
+                    const float d0 = base[0] - upv[0] * sy;                   // dir[0], bit for bit
+                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
+                    const float t = fabsf(d0) * __builtin_amdgcn_rsqf(sqa);          // (sqa is |dir|^2 / maxval^2)
+                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f);
+                    if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
+                        todo |= 1u << rr;                                             // a lane too close to a rounding boundary
+                        continue;
+                    }
+                    const nt_gptr out = NT_ROW_PTR() + NT_LANE_OFF();
+                    if (SEL8) {
+                        // 8-bit fields: t + 2^23 has round(t) in its low mantissa byte (t < 255.5; the guard keeps t off the
+                        // half-way points, so nearest-even is the reference's rounding), which is the byte v_perm_b32 picks
+                        const uint32_t q = __float_as_uint(t + 8388608.0f);
+                        // (the red byte is zero where dir[0] is not positive: a select on every row.  Until the end of round 3 the
+                        // select sat behind a wave-uniform branch -- its sign rarely changes within a stretch -- but the branch and
+                        // the jump around it are scalar instructions, and the scalar unit is the busier one in this loop: 1.4 % of
+                        // the headline call)
+                        const uint32_t w = __builtin_amdgcn_perm(d0 > 0.0f ? q : 0u, q, tg.plain_sel);
+                        NT_EXP_STORE_IF NT_G32(out) = w;
+                        continue;
+                    }
+                    uint32_t q = (uint32_t)(t + 0.5f);
+                    q = q < tg.plain_maxval ? q : tg.plain_maxval;
+                    const uint32_t w = (d0 > 0.0f ? q : 0u) * tg.plain_mul[0] + q * (tg.plain_mul[1] + tg.plain_mul[2]);      // (emit_plain)
+                    NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
+                }
             }
             // (the one-face rows of a wave mostly share their face: its component of `base` is picked once)
             uint32_t K0 = 0u;
@@ -1202,40 +1342,110 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                     uK0 = K0 == (uint32_t)j ? upv[j] : uK0;
                 }
             }
-            while (inner != 0u) {
-                const int rr = __builtin_ctz(inner);
-                NT_CLEAR_BIT(inner, rr);
-                const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
-                NT_ROW_LOAD(rr);
-                float bK = bK0, uK = uK0;
-                if (K != K0) {
-                    bK = base[0];
-                    uK = upv[0];
+            if (GROUPS) {
+                // ... and of four rows that are face K0 throughout (the four nibbles of their codes are K0 + 1)
+                uint32_t full = full_groups(inner);
+                const uint32_t same = (K0 + 1u) * 0x1111u;
+                while (full != 0u) {
+                    const int g = __builtin_ctz(full);
+                    NT_CLEAR_BIT(full, g);
+                    if (((uint32_t)(rowcodes >> (4 * g)) & 0xffffu) != same) continue;
+                    const nt_u32x16 grp_e = *(nt_rowtab4)(tab + g);
+                    inner &= ~(15u << g);
+                    float t[4], th[4];
+                    unsigned long long fail[4];
 #pragma unroll
-                    for (int j = 1; j < N; ++j) {
-                        bK = K == (uint32_t)j ? base[j] : bK;
-                        uK = K == (uint32_t)j ? upv[j] : uK;
+                    for (int k = 0; k < 4; ++k) {
+                        const float sy = __uint_as_float(grp_e[4 * k]);
+                        const float dK = bK0 - uK0 * sy;                      // dir[K0], bit for bit
+                        const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
+                        t[k] = fabsf(dK) * __builtin_amdgcn_rsqf(sqa);
+                        th[k] = t[k] * 0.5f;
+                        const bool clear = fabsf(__builtin_amdgcn_fractf(t[k]) - 0.5f) > fmaf(t[k], 0x1p-18f, 0x1p-18f) &&
+                                           fabsf(__builtin_amdgcn_fractf(th[k]) - 0.5f) > fmaf(th[k], 0x1p-18f, 0x1p-18f);
+                        fail[k] = __builtin_amdgcn_ballot_w64(!clear);
+                    }
+                    if (__builtin_expect(((fail[0] | fail[1]) | (fail[2] | fail[3])) == 0ull, 1)) {
+                        const uint32_t xo = NT_LANE_OFF();
+                        put_face(NT_GROUP_PTR(0) + xo, t[0], th[0]);
+                        put_face(NT_GROUP_PTR(1) + xo, t[1], th[1]);
+                        put_face(NT_GROUP_PTR(2) + xo, t[2], th[2]);
+                        put_face(NT_GROUP_PTR(3) + xo, t[3], th[3]);
+                    } else {
+                        todo |= ((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (fail[k] == 0ull) {
+                                uint32_t xo = xoff;
+                                asm volatile("" : "+v"(xo));
+                                put_face(NT_GROUP_PTR(k) + xo, t[k], th[k]);
+                            }
+                        }
                     }
                 }
-                const float dK = bK - uK * sy;                            // dir[K], bit for bit
-                const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                const float t = fabsf(dK) * __builtin_amdgcn_rsqf(sqa), th = t * 0.5f;
-                const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f) &&
-                                   fabsf(__builtin_amdgcn_fractf(th) - 0.5f) > fmaf(th, 0x1p-18f, 0x1p-18f);
-                if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
-                    todo |= 1u << rr;
-                    continue;
+                uint32_t inner_stored = 0u;
+                for (uint32_t rest = inner; rest != 0u;) {
+                    const int rr = __builtin_ctz(rest);
+                    NT_CLEAR_BIT(rest, rr);
+                    const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
+                    NT_ROW_LOAD(rr);
+                    float bK = bK0, uK = uK0;
+                    if (K != K0) {
+                        bK = base[0];
+                        uK = upv[0];
+    #pragma unroll
+                        for (int j = 1; j < N; ++j) {
+                            bK = K == (uint32_t)j ? base[j] : bK;
+                            uK = K == (uint32_t)j ? upv[j] : uK;
+                        }
+                    }
+                    const float dK = bK - uK * sy;                            // dir[K], bit for bit
+                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
+                    const float t = fabsf(dK) * __builtin_amdgcn_rsqf(sqa), th = t * 0.5f;
+                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f) &&
+                                       fabsf(__builtin_amdgcn_fractf(th) - 0.5f) > fmaf(th, 0x1p-18f, 0x1p-18f);
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!clear) == 0ull, 1)) {
+                        put_face(NT_ROW_PTR() + NT_LANE_OFF(), t, th);
+                        NT_SET_BIT(inner_stored, rr);
+                    }
                 }
-                const nt_gptr out = NT_ROW_PTR() + NT_LANE_OFF();
-                if (SEL8) {
-                    NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(__float_as_uint(t + 8388608.0f), __float_as_uint(th + 8388608.0f), tg.plain_sel);
-                    continue;
+                todo |= inner & ~inner_stored;
+            } else {
+                while (inner != 0u) {
+                    const int rr = __builtin_ctz(inner);
+                    NT_CLEAR_BIT(inner, rr);
+                    const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
+                    NT_ROW_LOAD(rr);
+                    float bK = bK0, uK = uK0;
+                    if (K != K0) {
+                        bK = base[0];
+                        uK = upv[0];
+    #pragma unroll
+                        for (int j = 1; j < N; ++j) {
+                            bK = K == (uint32_t)j ? base[j] : bK;
+                            uK = K == (uint32_t)j ? upv[j] : uK;
+                        }
+                    }
+                    const float dK = bK - uK * sy;                            // dir[K], bit for bit
+                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
+                    const float t = fabsf(dK) * __builtin_amdgcn_rsqf(sqa), th = t * 0.5f;
+                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f) &&
+                                       fabsf(__builtin_amdgcn_fractf(th) - 0.5f) > fmaf(th, 0x1p-18f, 0x1p-18f);
+                    if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
+                        todo |= 1u << rr;
+                        continue;
+                    }
+                    const nt_gptr out = NT_ROW_PTR() + NT_LANE_OFF();
+                    if (SEL8) {
+                        NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(__float_as_uint(t + 8388608.0f), __float_as_uint(th + 8388608.0f), tg.plain_sel);
+                        continue;
+                    }
+                    uint32_t qr = (uint32_t)(t + 0.5f), qgb = (uint32_t)(th + 0.5f);
+                    qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
+                    qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
+                    const uint32_t w = qr * tg.plain_mul[0] + qgb * (tg.plain_mul[1] + tg.plain_mul[2]);
+                    NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
                 }
-                uint32_t qr = (uint32_t)(t + 0.5f), qgb = (uint32_t)(th + 0.5f);
-                qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
-                qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
-                const uint32_t w = qr * tg.plain_mul[0] + qgb * (tg.plain_mul[1] + tg.plain_mul[2]);
-                NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
             }
             };
             if (tg.plain_sel != 0u) lean_rows(std::true_type{});
@@ -1347,8 +1557,10 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
 #undef NT_ROW_LOAD
 #undef NT_ROW_OFF
 #undef NT_ROW_PTR
+#undef NT_GROUP_PTR
 #undef NT_LANE_OFF
 #undef NT_CLEAR_BIT
+#undef NT_SET_BIT
 }
 
 template <int N>
