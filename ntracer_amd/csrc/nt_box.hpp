@@ -632,11 +632,7 @@ __global__ __launch_bounds__(256) void box_kernel(NtCameraFixed cam, NtTarget tg
         if (row >= tg.row_count) return;
         const bool rowhit = (live >> rr) & 1u;
         const int orow = tg.row_begin + row;
-        int y = orow;
-        if (tg.band_world > 1) {
-            const int band = orow / tg.band_rows;
-            y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-        }
+        const int y = nt_image_row(tg, orow);
         if (y >= tg.height) continue;
         PixelRef pr;
         pr.x = x;
@@ -689,11 +685,7 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
         dots[0] = cam.odots[0]; dots[1] = cam.odots[1]; dots[2] = cam.odots[2]; dots[3] = cam.odots[3];
     }
     const int orow = tg.row_begin + row;
-    int y = orow;
-    if (tg.band_world > 1) {
-        const int band = orow / tg.band_rows;
-        y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-    }
+    const int y = nt_image_row(tg, orow);
     if (y >= tg.height) return;
     const float sy = tg.fovI * ((float)y - tg.half_h);
     while (todo != 0u) {
@@ -891,11 +883,7 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
     uint32_t code = 0u;
     if (row < tg.row_count && col < ncols) {
         const int orow = tg.row_begin + row;
-        int y = orow;
-        if (tg.band_world > 1) {
-            const int band = orow / tg.band_rows;
-            y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-        }
+        const int y = nt_image_row(tg, orow);
         code = box_stretch_code<N>(org, right, up, fwd, tg, y, col);
     }
     // eight stretches to a dword
@@ -942,15 +930,40 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
 #endif
 // The packed-RGB lean loops take aligned groups of four slots at once where all four rows are culled, or all four are the one
 // face K0: one scalar load and one wait for the four table entries, one branch on the four guards, one instruction to clear the
-// four bits -- the vector arithmetic of every row is the one-row loop's (-DNT_BOX_LEAN_GROUPS_MAX_N=0: nowhere, the build to measure against)
-#ifndef NT_BOX_LEAN_GROUPS_MIN_N
-#define NT_BOX_LEAN_GROUPS_MIN_N 3
-#endif
-// (up to N = 20: beyond, the tile kernels are held to 168 VGPRs and already spill to scratch, and the group body's sixteen live
-// values a lane would spill more)
+// four bits -- the vector arithmetic of every row is the one-row loop's.  Groups of four up to this N (0: nowhere, the build to
+// measure against); beyond 20 the tile kernels are held to 168 VGPRs and already spill to scratch, and the group body's sixteen
+// live values a lane would spill more.
 #ifndef NT_BOX_LEAN_GROUPS_MAX_N
 #define NT_BOX_LEAN_GROUPS_MAX_N 20
 #endif
+// The lean rows' guard: t keeps 2^-18 * (1 + t) clear of every k + 1/2, so that the cheap quotient and the reference's round to
+// the same integer (box_tile_kernel, packed RGB)
+__device__ __forceinline__ bool guard_clear(float t) { return fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f); }
+// ... and their quotient |d| * maxval / |dir| from the quadratic in sy (uu, m2bu, bb: |dir|^2 / maxval^2 = bb + m2bu sy + uu sy^2)
+__device__ __forceinline__ float lean_quotient(float d, float sy, float uu, float m2bu, float bb) {
+    return fabsf(d) * __builtin_amdgcn_rsqf(fmaf(sy, fmaf(sy, uu, m2bu), bb));
+}
+// component K (wave-uniform) of `base` and of `up`, by selects: the arrays stay in registers
+template <int N>
+__device__ __forceinline__ void pick_component(uint32_t K, const float (&base)[N], const float (&upv)[N], float &bK, float &uK) {
+    bK = base[0];
+    uK = upv[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) {
+        bK = K == (uint32_t)j ? base[j] : bK;
+        uK = K == (uint32_t)j ? upv[j] : uK;
+    }
+}
+// dir = base - up * sy and its |dir|^2, in the reference's order of operations
+template <int N>
+__device__ __forceinline__ float row_dir(const float (&base)[N], const float (&upv)[N], float sy, float (&dir)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) dir[j] = base[j] - upv[j] * sy;
+    float sq = dir[0] * dir[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
+    return sq;
+}
 template <int N, bool F32, int ROWS, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCameraFixed cam, NtTarget tg) {
     static_assert(ROWS == 8 || ROWS == 16 || ROWS == 32 || ROWS == 64, "sixteen row codes to a qword, one to four qwords a wave");
@@ -1021,11 +1034,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         const int trow = tg.row_il > 0 ? ((int)blockIdx.y * WAVES + lane / R) + tg.row_il * (lane % R) : tile_row0 + lane;
         if (lane < WAVES * R && trow < tg.row_count) {
             const int orow = tg.row_begin + trow;
-            int y = orow;
-            if (tg.band_world > 1) {
-                const int band = orow / tg.band_rows;
-                y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-            }
+            const int y = nt_image_row(tg, orow);
             if (y < tg.height) {
                 // (N > 8: the sets' arithmetic would raise the kernel's register allocation -- 124 VGPRs and spills at N = 10 --
                 // for every row; those dimensions go without)
@@ -1064,7 +1073,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
 #endif
     // Sixteen rows at a time (their codes fill a qword), once or -- R == 32 -- twice per wave: what depends on the column
     // alone (forward + right*sx, the quadratic for |dir|^2) is set up once for all the wave's rows.
-    constexpr int HALVES = R >= 32 ? R / 16 : 1, RH = R / HALVES;
+    constexpr int HALVES = R >= 32 ? R / 16 : 1;
     const int wrow0 = tile_row0 + wv * R;                     // the wave's first slot (its first row when rows are not interleaved)
     const int il = tg.row_il;                                 // (scalar) 0, or the stride between a wave's rows
     const int wfirst = il > 0 ? (int)blockIdx.y * WAVES + wv : wrow0;
@@ -1074,9 +1083,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         // four entries in a row (the table is in slot order): one s_load_dwordx16
         typedef uint32_t nt_u32x16 __attribute__((ext_vector_type(16), aligned(16)));
         typedef __attribute__((address_space(4))) const nt_u32x16 *nt_rowtab4;
-        // (LEAN4: the dimensions whose scalar control is the new one; the others keep the loops they had, instruction for instruction)
-        constexpr bool LEAN4 = N >= NT_BOX_LEAN_GROUPS_MIN_N && N <= NT_BOX_LEAN_GROUPS_MAX_N;
-        constexpr bool GROUPS = !F32 && LEAN4;
+        constexpr bool GROUPS = !F32 && N <= NT_BOX_LEAN_GROUPS_MAX_N;
         uint8_t *const frame_base = tg.dest + (long long)frame * tg.frame_stride;
         // What a row loop needs to know about its row -- sy of the ray source and the row's byte offset in a frame -- comes
         // from a table the host wrote (NtTarget::rowtab, 16 bytes per owned row: sy, -, offset), read through the scalar
@@ -1148,17 +1155,9 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         // band arithmetic and the launch parameters it reads stay out of the per-half loop, whose scalar registers are short.
         // Every lane stays active in the row loops -- lanes past the right edge redo the last pixel (same bytes, same value)
         // instead of leaving
-        unsigned long long rows_valid = 0ull;
-        if (LEAN4) {
-            const int lrow = il > 0 ? wfirst + il * lane : wrow0 + lane;
-            const int lorow = tg.row_begin + lrow;
-            int ly = lorow;
-            if (tg.band_world > 1) {
-                const int band = lorow / tg.band_rows;
-                ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
-            }
-            rows_valid = __builtin_amdgcn_ballot_w64(lane < R && lrow < tg.row_count && ly < tg.height);
-        }
+        const int lrow = il > 0 ? wfirst + il * lane : wrow0 + lane;
+        const int ly = nt_image_row(tg, tg.row_begin + lrow);
+        const unsigned long long rows_valid = __builtin_amdgcn_ballot_w64(lane < R && lrow < tg.row_count && ly < tg.height);
 #pragma unroll 1
         for (int half = 0; half < HALVES; ++half) {
         const int row0 = wrow0 + 16 * half;                   // slot of the half's first row
@@ -1168,21 +1167,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         const int cw = (R >= 32 ? (R / 8) * wv + 2 * half : 2 * wv);
         unsigned long long rowcodes = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[cw + 1]) << 32) |
                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[cw]);
-        uint32_t valid;
-        if (LEAN4) {
-            valid = HALVES > 1 ? (uint32_t)(rows_valid >> (16 * half)) & 0xffffu : (uint32_t)rows_valid;
-        } else {
-            // Which of these rows exist: one row per lane (lane l <-> row row0 + l).  Every lane stays active in the row
-            // loops -- lanes past the right edge redo the last pixel (same bytes, same value) instead of leaving
-            const int lrow = il > 0 ? hfirst + il * lane : row0 + lane;
-            const int lorow = tg.row_begin + lrow;
-            int ly = lorow;
-            if (tg.band_world > 1) {
-                const int band = lorow / tg.band_rows;
-                ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
-            }
-            valid = (uint32_t)__builtin_amdgcn_ballot_w64(lane < RH && lrow < tg.row_count && ly < tg.height);
-        }
+        const uint32_t valid = HALVES > 1 ? (uint32_t)(rows_valid >> (16 * half)) & 0xffffu : (uint32_t)rows_valid;
         // (interleaved rows: the table is in slot order and belongs to this launch's row range)
         const nt_rowtab tab = (nt_rowtab)tg.rowtab + (il > 0 ? row0 : tg.row_begin + row0);
         // (bit rr <-> row row0 + rr; code 14 -- a near-tie stretch -- is not looked at here unless this kernel is all there is)
@@ -1238,215 +1223,109 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             };
             // bit 4k of the result: bits 4k .. 4k + 3 of the mask are all set
             auto full_groups = [](uint32_t mask) { return mask & (mask >> 1) & (mask >> 2) & (mask >> 3) & 0x1111u; };
+            // The aligned group of four slots g .. g + 3.  row(sy, a, b): one row's arithmetic and its own guard as in the one-row
+            // loops below (a, b: what `put` stores; returns "clear"), nothing shared between rows; the four guards' outcomes stay
+            // scalar lane masks, and one branch decides for the four stores.  Otherwise the clear rows are stored one by one and the
+            // others handed on -- on the spot: a few per cent of the rows fail their guard, so one group in ten has such a row, and a
+            // build that sent those groups through the one-row loop again measured 1.2 % slower on the headline than one without groups.
+            auto lean_group = [&](int g, auto row, auto put) {
+                const nt_u32x16 grp_e = *(nt_rowtab4)(tab + g);
+                float a[4], b[4];
+                unsigned long long fail[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) fail[k] = __builtin_amdgcn_ballot_w64(!row(__uint_as_float(grp_e[4 * k]), a[k], b[k]));
+                if (__builtin_expect(((fail[0] | fail[1]) | (fail[2] | fail[3])) == 0ull, 1)) {
+                    const uint32_t xo = NT_LANE_OFF();
+                    put(NT_GROUP_PTR(0) + xo, a[0], b[0]);
+                    put(NT_GROUP_PTR(1) + xo, a[1], b[1]);
+                    put(NT_GROUP_PTR(2) + xo, a[2], b[2]);
+                    put(NT_GROUP_PTR(3) + xo, a[3], b[3]);
+                } else {
+                    // (rare) the rows with a lane too close to a rounding boundary go on to the ray-by-ray loop
+                    todo |= ((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (fail[k] == 0ull) {
+                            uint32_t xo = xoff;
+                            asm volatile("" : "+v"(xo));
+                            put(NT_GROUP_PTR(k) + xo, a[k], b[k]);
+                        }
+                    }
+                }
+            };
+            // a culled row: t and dir[0]
+            auto culled_row = [&](float sy, float &t, float &d0) {
+                d0 = base[0] - upv[0] * sy;                               // dir[0], bit for bit
+                t = lean_quotient(d0, sy, uu, m2bu, bb);
+                return guard_clear(t);
+            };
+            // a row of one face, bK and uK its components of `base` and `up`: t and its half
+            auto face_row = [&](float bK, float uK, float sy, float &t, float &th) {
+                const float dK = bK - uK * sy;                            // dir[K], bit for bit
+                t = lean_quotient(dK, sy, uu, m2bu, bb);
+                th = t * 0.5f;
+                return guard_clear(t) && guard_clear(th);
+            };
+            // ---- 1. aligned groups of four culled rows (groups that are mixed or cut by `valid` are left to 2.)
             if (GROUPS) {
-                // Aligned groups of four culled rows.  Every row's arithmetic and its own guard as in the one-row loop below,
-                // nothing shared between rows; the four guards' outcomes stay scalar lane masks, and one branch decides for
-                // the four stores.  Otherwise the clear rows are stored one by one and the others handed on -- on the spot: a few per
-                // cent of the rows fail their guard, so one group in ten has such a row, and a build that sent those groups through
-                // the one-row loop again measured 1.2 % slower on the headline than one without groups.  Groups that are mixed or
-                // cut by `valid` are left to the one-row loop below.
                 uint32_t full = full_groups(quick);
                 quick &= ~(full * 15u);
                 while (full != 0u) {
                     const int g = __builtin_ctz(full);
                     NT_CLEAR_BIT(full, g);
-                    const nt_u32x16 grp_e = *(nt_rowtab4)(tab + g);
-                    float t[4], d0[4];
-                    unsigned long long fail[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float sy = __uint_as_float(grp_e[4 * k]);
-                        d0[k] = base[0] - upv[0] * sy;                        // dir[0], bit for bit
-                        const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                        t[k] = fabsf(d0[k]) * __builtin_amdgcn_rsqf(sqa);
-                        const bool clear = fabsf(__builtin_amdgcn_fractf(t[k]) - 0.5f) > fmaf(t[k], 0x1p-18f, 0x1p-18f);
-                        fail[k] = __builtin_amdgcn_ballot_w64(!clear);
-                    }
-                    if (__builtin_expect(((fail[0] | fail[1]) | (fail[2] | fail[3])) == 0ull, 1)) {
-                        const uint32_t xo = NT_LANE_OFF();
-                        put_quick(NT_GROUP_PTR(0) + xo, t[0], d0[0]);
-                        put_quick(NT_GROUP_PTR(1) + xo, t[1], d0[1]);
-                        put_quick(NT_GROUP_PTR(2) + xo, t[2], d0[2]);
-                        put_quick(NT_GROUP_PTR(3) + xo, t[3], d0[3]);
-                    } else {
-                        // (rare) the rows with a lane too close to a rounding boundary go on to the ray-by-ray loop
-                        todo |= ((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (fail[k] == 0ull) {
-                                uint32_t xo = xoff;
-                                asm volatile("" : "+v"(xo));
-                                put_quick(NT_GROUP_PTR(k) + xo, t[k], d0[k]);
-                            }
-                        }
-                    }
-                }
-                uint32_t quick_stored = 0u;
-                for (uint32_t rest = quick; rest != 0u;) {
-                    const int rr = __builtin_ctz(rest);
-                    NT_CLEAR_BIT(rest, rr);
-                    NT_ROW_LOAD(rr);
-                    const float d0 = base[0] - upv[0] * sy;                   // dir[0], bit for bit
-                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                    const float t = fabsf(d0) * __builtin_amdgcn_rsqf(sqa);          // (sqa is |dir|^2 / maxval^2)
-                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f);
-                    // (a row with a lane too close to a rounding boundary stores nothing and is not marked: the clear row is the
-                    // straight path, one branch taken a row where an if / else was laid out with three)
-                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!clear) == 0ull, 1)) {
-                        put_quick(NT_ROW_PTR() + NT_LANE_OFF(), t, d0);
-                        NT_SET_BIT(quick_stored, rr);
-                    }
-                }
-                todo |= quick & ~quick_stored;
-            } else {
-                // (the one-row loop as it was)
-                while (quick != 0u) {
-                    const int rr = __builtin_ctz(quick);
-                    NT_CLEAR_BIT(quick, rr);
-                    NT_ROW_LOAD(rr);
-                    const float d0 = base[0] - upv[0] * sy;                   // dir[0], bit for bit
-                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                    const float t = fabsf(d0) * __builtin_amdgcn_rsqf(sqa);          // (sqa is |dir|^2 / maxval^2)
-                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f);
-                    if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
-                        todo |= 1u << rr;                                             // a lane too close to a rounding boundary
-                        continue;
-                    }
-                    const nt_gptr out = NT_ROW_PTR() + NT_LANE_OFF();
-                    if (SEL8) {
-                        // 8-bit fields: t + 2^23 has round(t) in its low mantissa byte (t < 255.5; the guard keeps t off the
-                        // half-way points, so nearest-even is the reference's rounding), which is the byte v_perm_b32 picks
-                        const uint32_t q = __float_as_uint(t + 8388608.0f);
-                        // (the red byte is zero where dir[0] is not positive: a select on every row.  Until the end of round 3 the
-                        // select sat behind a wave-uniform branch -- its sign rarely changes within a stretch -- but the branch and
-                        // the jump around it are scalar instructions, and the scalar unit is the busier one in this loop: 1.4 % of
-                        // the headline call)
-                        const uint32_t w = __builtin_amdgcn_perm(d0 > 0.0f ? q : 0u, q, tg.plain_sel);
-                        NT_EXP_STORE_IF NT_G32(out) = w;
-                        continue;
-                    }
-                    uint32_t q = (uint32_t)(t + 0.5f);
-                    q = q < tg.plain_maxval ? q : tg.plain_maxval;
-                    const uint32_t w = (d0 > 0.0f ? q : 0u) * tg.plain_mul[0] + q * (tg.plain_mul[1] + tg.plain_mul[2]);      // (emit_plain)
-                    NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
+                    lean_group(g, culled_row, put_quick);
                 }
             }
+            // ---- 2. the remaining culled rows, one by one
+            uint32_t quick_stored = 0u;
+            for (uint32_t rest = quick; rest != 0u;) {
+                const int rr = __builtin_ctz(rest);
+                NT_CLEAR_BIT(rest, rr);
+                NT_ROW_LOAD(rr);
+                float t, d0;
+                // (a row with a lane too close to a rounding boundary stores nothing and is not marked: the clear row is the
+                // straight path, one branch taken a row where an if / else was laid out with three)
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(!culled_row(sy, t, d0)) == 0ull, 1)) {
+                    put_quick(NT_ROW_PTR() + NT_LANE_OFF(), t, d0);
+                    NT_SET_BIT(quick_stored, rr);
+                }
+            }
+            todo |= quick & ~quick_stored;
             // (the one-face rows of a wave mostly share their face: its component of `base` is picked once)
             uint32_t K0 = 0u;
             float bK0 = base[0], uK0 = upv[0];
             if (inner != 0u) {
                 K0 = ((uint32_t)(rowcodes >> (4 * __builtin_ctz(inner))) & 15u) - 1u;
-#pragma unroll
-                for (int j = 1; j < N; ++j) {
-                    bK0 = K0 == (uint32_t)j ? base[j] : bK0;
-                    uK0 = K0 == (uint32_t)j ? upv[j] : uK0;
-                }
+                pick_component<N>(K0, base, upv, bK0, uK0);
             }
+            // ---- 3. aligned groups of four rows that are face K0 throughout (the four nibbles of their codes are K0 + 1)
             if (GROUPS) {
-                // ... and of four rows that are face K0 throughout (the four nibbles of their codes are K0 + 1)
                 uint32_t full = full_groups(inner);
                 const uint32_t same = (K0 + 1u) * 0x1111u;
                 while (full != 0u) {
                     const int g = __builtin_ctz(full);
                     NT_CLEAR_BIT(full, g);
                     if (((uint32_t)(rowcodes >> (4 * g)) & 0xffffu) != same) continue;
-                    const nt_u32x16 grp_e = *(nt_rowtab4)(tab + g);
                     inner &= ~(15u << g);
-                    float t[4], th[4];
-                    unsigned long long fail[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float sy = __uint_as_float(grp_e[4 * k]);
-                        const float dK = bK0 - uK0 * sy;                      // dir[K0], bit for bit
-                        const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                        t[k] = fabsf(dK) * __builtin_amdgcn_rsqf(sqa);
-                        th[k] = t[k] * 0.5f;
-                        const bool clear = fabsf(__builtin_amdgcn_fractf(t[k]) - 0.5f) > fmaf(t[k], 0x1p-18f, 0x1p-18f) &&
-                                           fabsf(__builtin_amdgcn_fractf(th[k]) - 0.5f) > fmaf(th[k], 0x1p-18f, 0x1p-18f);
-                        fail[k] = __builtin_amdgcn_ballot_w64(!clear);
-                    }
-                    if (__builtin_expect(((fail[0] | fail[1]) | (fail[2] | fail[3])) == 0ull, 1)) {
-                        const uint32_t xo = NT_LANE_OFF();
-                        put_face(NT_GROUP_PTR(0) + xo, t[0], th[0]);
-                        put_face(NT_GROUP_PTR(1) + xo, t[1], th[1]);
-                        put_face(NT_GROUP_PTR(2) + xo, t[2], th[2]);
-                        put_face(NT_GROUP_PTR(3) + xo, t[3], th[3]);
-                    } else {
-                        todo |= ((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (fail[k] == 0ull) {
-                                uint32_t xo = xoff;
-                                asm volatile("" : "+v"(xo));
-                                put_face(NT_GROUP_PTR(k) + xo, t[k], th[k]);
-                            }
-                        }
-                    }
-                }
-                uint32_t inner_stored = 0u;
-                for (uint32_t rest = inner; rest != 0u;) {
-                    const int rr = __builtin_ctz(rest);
-                    NT_CLEAR_BIT(rest, rr);
-                    const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
-                    NT_ROW_LOAD(rr);
-                    float bK = bK0, uK = uK0;
-                    if (K != K0) {
-                        bK = base[0];
-                        uK = upv[0];
-    #pragma unroll
-                        for (int j = 1; j < N; ++j) {
-                            bK = K == (uint32_t)j ? base[j] : bK;
-                            uK = K == (uint32_t)j ? upv[j] : uK;
-                        }
-                    }
-                    const float dK = bK - uK * sy;                            // dir[K], bit for bit
-                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                    const float t = fabsf(dK) * __builtin_amdgcn_rsqf(sqa), th = t * 0.5f;
-                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f) &&
-                                       fabsf(__builtin_amdgcn_fractf(th) - 0.5f) > fmaf(th, 0x1p-18f, 0x1p-18f);
-                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!clear) == 0ull, 1)) {
-                        put_face(NT_ROW_PTR() + NT_LANE_OFF(), t, th);
-                        NT_SET_BIT(inner_stored, rr);
-                    }
-                }
-                todo |= inner & ~inner_stored;
-            } else {
-                while (inner != 0u) {
-                    const int rr = __builtin_ctz(inner);
-                    NT_CLEAR_BIT(inner, rr);
-                    const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
-                    NT_ROW_LOAD(rr);
-                    float bK = bK0, uK = uK0;
-                    if (K != K0) {
-                        bK = base[0];
-                        uK = upv[0];
-    #pragma unroll
-                        for (int j = 1; j < N; ++j) {
-                            bK = K == (uint32_t)j ? base[j] : bK;
-                            uK = K == (uint32_t)j ? upv[j] : uK;
-                        }
-                    }
-                    const float dK = bK - uK * sy;                            // dir[K], bit for bit
-                    const float sqa = fmaf(sy, fmaf(sy, uu, m2bu), bb);
-                    const float t = fabsf(dK) * __builtin_amdgcn_rsqf(sqa), th = t * 0.5f;
-                    const bool clear = fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f) &&
-                                       fabsf(__builtin_amdgcn_fractf(th) - 0.5f) > fmaf(th, 0x1p-18f, 0x1p-18f);
-                    if (__builtin_amdgcn_ballot_w64(!clear) != 0ull) {
-                        todo |= 1u << rr;
-                        continue;
-                    }
-                    const nt_gptr out = NT_ROW_PTR() + NT_LANE_OFF();
-                    if (SEL8) {
-                        NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(__float_as_uint(t + 8388608.0f), __float_as_uint(th + 8388608.0f), tg.plain_sel);
-                        continue;
-                    }
-                    uint32_t qr = (uint32_t)(t + 0.5f), qgb = (uint32_t)(th + 0.5f);
-                    qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
-                    qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
-                    const uint32_t w = qr * tg.plain_mul[0] + qgb * (tg.plain_mul[1] + tg.plain_mul[2]);
-                    NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
+                    lean_group(g, [&](float sy, float &t, float &th) { return face_row(bK0, uK0, sy, t, th); }, put_face);
                 }
             }
+            // ---- 4. the remaining one-face rows, one by one
+            uint32_t inner_stored = 0u;
+            for (uint32_t rest = inner; rest != 0u;) {
+                const int rr = __builtin_ctz(rest);
+                NT_CLEAR_BIT(rest, rr);
+                const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
+                NT_ROW_LOAD(rr);
+                float bK = bK0, uK = uK0;
+                if (K != K0) pick_component<N>(K, base, upv, bK, uK);
+                float t, th;
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(!face_row(bK, uK, sy, t, th)) == 0ull, 1)) {
+                    put_face(NT_ROW_PTR() + NT_LANE_OFF(), t, th);
+                    NT_SET_BIT(inner_stored, rr);
+                }
+            }
+            todo |= inner & ~inner_stored;
             };
             if (tg.plain_sel != 0u) lean_rows(std::true_type{});
             else lean_rows(std::false_type{});
@@ -1458,11 +1337,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 const int rr = __builtin_ctz(quick);
                 quick &= quick - 1u;
                 NT_ROW_LOAD(rr);
-#pragma unroll
-                for (int j = 0; j < N; ++j) dir[j] = base[j] - upv[j] * sy;
-                float sq = dir[0] * dir[0];
-#pragma unroll
-                for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
+                const float sq = row_dir<N>(base, upv, sy, dir);
                 const float in = dir[0] / sqrt_wave(sq);
                 float r, gb, b_;
                 box_background(in, r, gb, b_);
@@ -1472,11 +1347,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             float bK0 = base[0], uK0 = upv[0];
             if (inner != 0u) {
                 K0 = ((uint32_t)(rowcodes >> (4 * __builtin_ctz(inner))) & 15u) - 1u;
-#pragma unroll
-                for (int j = 1; j < N; ++j) {
-                    bK0 = K0 == (uint32_t)j ? base[j] : bK0;
-                    uK0 = K0 == (uint32_t)j ? upv[j] : uK0;
-                }
+                pick_component<N>(K0, base, upv, bK0, uK0);
             }
             while (inner != 0u) {
                 // one face K throughout: sine = d_K * (-sign d_K) <= 0, shade = -sine (tracer.hpp:105-107)
@@ -1484,21 +1355,9 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 inner &= inner - 1u;
                 const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
                 NT_ROW_LOAD(rr);
-#pragma unroll
-                for (int j = 0; j < N; ++j) dir[j] = base[j] - upv[j] * sy;
-                float sq = dir[0] * dir[0];
-#pragma unroll
-                for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
+                const float sq = row_dir<N>(base, upv, sy, dir);
                 float bK = bK0, uK = uK0;
-                if (K != K0) {
-                    bK = base[0];
-                    uK = upv[0];
-#pragma unroll
-                    for (int j = 1; j < N; ++j) {
-                        bK = K == (uint32_t)j ? base[j] : bK;
-                        uK = K == (uint32_t)j ? upv[j] : uK;
-                    }
-                }
+                if (K != K0) pick_component<N>(K, base, upv, bK, uK);
                 const float xk = bK - uK * sy;                            // dir[K], bit for bit (the same two operations)
                 const float shade = fabsf(xk / sqrt_wave(sq));
                 emit_f32x3_at(tg, NT_ROW_PTR() + NT_LANE_OFF(), shade * 1.0f, shade * 0.5f);
@@ -1515,11 +1374,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             pr.offset = NT_ROW_OFF() + (long long)xoff;
             pr.hit_index = 0;
             pr.valid = true;
-#pragma unroll
-            for (int j = 0; j < N; ++j) dir[j] = base[j] - upv[j] * sy;
-            float sq = dir[0] * dir[0];
-#pragma unroll
-            for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
+            const float sq = row_dir<N>(base, upv, sy, dir);
             // (a row with a face code is here because its cheap quantisation failed: the face is known)
             const int rcode = (int)((uint32_t)(rowcodes >> (4 * rr)) & 15u);
             if (ALLIN) {

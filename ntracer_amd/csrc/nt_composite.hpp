@@ -1651,12 +1651,9 @@ __global__ __launch_bounds__(256) void composite_persistent(NtCompositeDev sc, N
                         const int x = tx * 8 + (within & 7);
                         const int row = ty * 8 + (within >> 3);
                         bool valid = x < tg.width && row < tg.row_count;
-                        int y = tg.row_begin + row;
-                        const int orow = y;
-                        if (valid && tg.band_world > 1) {
-                            const int band = orow / tg.band_rows;
-                            y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-                        }
+                        const int orow = tg.row_begin + row;
+                        int y = orow;
+                        if (valid) y = nt_image_row(tg, orow);
                         valid = valid && y < tg.height;
                         if (valid) {
                             out_off = (long long)frame * tg.frame_stride + (long long)(tg.compact ? orow : y) * tg.pitch + (long long)x * tg.bpp;
@@ -1913,11 +1910,7 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
     const int row = ty * 8 + (lane >> 3);
     bool valid = x < tg.width && row < tg.row_count;
     const int orow = tg.row_begin + row;
-    int y = orow;
-    if (tg.band_world > 1) {
-        const int band = orow / tg.band_rows;
-        y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-    }
+    const int y = nt_image_row(tg, orow);
     valid = valid && y < tg.height;
     const long long out_off = (long long)frame * tg.frame_stride + (long long)(tg.compact ? orow : y) * tg.pitch + (long long)x * tg.bpp;
 

@@ -205,6 +205,16 @@ struct PixelRef {
     bool valid;
 };
 
+// owned row -> image row through the bands (NtTarget, nt_device.hpp): the one place the device works it out
+__device__ __forceinline__ int nt_image_row(const NtTarget &tg, int orow) {
+    int y = orow;
+    if (tg.band_world > 1) {
+        const int band = orow / tg.band_rows;
+        y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
+    }
+    return y;
+}
+
 // px,py: position inside the BW x BH tile of block (bx, by) of frame bz
 template <int BW, int BH>
 __device__ __forceinline__ PixelRef locate_pixel_at(const NtTarget &tg, int bx, int by, int bz, int px, int py, int tid) {
@@ -228,11 +238,7 @@ __device__ __forceinline__ PixelRef locate_pixel_at(const NtTarget &tg, int bx, 
     const int row = by * BH + py;                    // relative to row_begin
     if (x >= tg.width || row >= tg.row_count) return r;
     const int orow = tg.row_begin + row;             // owned-row index
-    int y = orow;
-    if (tg.band_world > 1) {
-        const int band = orow / tg.band_rows;
-        y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-    }
+    const int y = nt_image_row(tg, orow);
     if (y >= tg.height) return r;
     r.x = x;
     r.y = y;

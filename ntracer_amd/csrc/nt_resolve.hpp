@@ -35,11 +35,7 @@ __global__ __launch_bounds__(64) void resolve_kernel(NtResolveSrc src, NtTarget 
     const int lane = (int)threadIdx.x;
     const int row = (int)blockIdx.y;                     // relative to row_begin
     const int orow = tg.row_begin + row;
-    int y = orow;
-    if (tg.band_world > 1) {
-        const int band = orow / tg.band_rows;
-        y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-    }
+    const int y = nt_image_row(tg, orow);
     if (row >= tg.row_count || y >= tg.height) return;   // (the same for the whole block)
     const int x0 = (int)blockIdx.x * 64;
     const int x = x0 + lane;

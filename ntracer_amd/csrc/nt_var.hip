@@ -226,11 +226,7 @@ __global__ __launch_bounds__(256) void box_rows_kernel_var(NtCamera cam, NtTarge
         const int trow = tile_row0 + lane;
         if (lane < 4 * R && trow < tg.row_count) {
             const int orow = tg.row_begin + trow;
-            int y = orow;
-            if (tg.band_world > 1) {
-                const int band = orow / tg.band_rows;
-                y = (band * tg.band_world + tg.band_rank) * tg.band_rows + (orow - band * tg.band_rows);
-            }
+            const int y = nt_image_row(tg, orow);
             if (y < tg.height) code = box_stretch_code_var(n, camrow, tg, y, (int)blockIdx.x);
         }
         uint32_t packed = code << (4 * (lane & 7));
@@ -245,11 +241,7 @@ __global__ __launch_bounds__(256) void box_rows_kernel_var(NtCamera cam, NtTarge
     const uint32_t rowcodes = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[wv]);
     // row bookkeeping: one row per lane, read back with v_readlane (see box_tile_kernel)
     const int lorow = tg.row_begin + row0 + lane;
-    int ly = lorow;
-    if (tg.band_world > 1) {
-        const int band = lorow / tg.band_rows;
-        ly = (band * tg.band_world + tg.band_rank) * tg.band_rows + (lorow - band * tg.band_rows);
-    }
+    const int ly = nt_image_row(tg, lorow);
     const uint32_t valid = (uint32_t)__builtin_amdgcn_ballot_w64(lane < R && row0 + lane < tg.row_count && ly < tg.height);
     const float v_sy = tg.fovI * ((float)ly - tg.half_h);
     const long long v_off = (long long)blockIdx.z * tg.frame_stride + (long long)(tg.compact ? lorow : ly) * tg.pitch;

@@ -8,13 +8,16 @@ A 630 x 200 image: the last column strip has lanes past the right edge, and 200 
 groups of a wave cut.  Three launches for the three kinds of block shape (pinned below without a GPU) -- 24 frames (8 rows a
 wave, four waves a block), 240 frames (16 rows a wave) and 240 frames of a caller with overlapped calls (64 rows a wave, one
 wave a block: the bench's kernel) -- and rank 3 of 8's bands of a 630 x 1080 image, whose rows are not evenly spaced.
-N = 3..8 and 10 (the route with a second kernel); RGBX8 and a 10-10-10-2 format, whose fields are not bytes (the general copy
-of the loops; tests/fixtures.py has no such format, so it is spelled out here).
+N = 3..8 and 10 (the route with a second kernel), and N = 22, which takes no groups (NT_BOX_LEAN_GROUPS_MAX_N = 20): every row
+of its waves goes through the one-row loops, the same loops that take what the groups leave at the other dimensions.  RGBX8 and
+a 10-10-10-2 format, whose fields are not bytes (the general copy of the loops; tests/fixtures.py has no such format, so it is
+spelled out here).
 
 The cameras are those of tests/test_box_classify_sets.py, for N = 6 with eight of the bench's.  That they reach every branch is
 asserted before anything is rendered, and by a test of its own that needs no GPU: tools/box_sets_census.py's stretch_codes
 restates the codes wave, and the slot-to-row map is the 64 x 1 launch's (a column strip's four waves deal the rows out: slot s
-of wave w is row w + 4 s)."""
+of wave w is row w + 4 s).  For N = 22 it is asserted instead that waves of the bands' launch hold culled, one-face and ray-by-ray
+rows side by side in one half, and that every 630 x 200 launch has culled rows whose guard must fail."""
 import ctypes as C
 import os
 import shutil
@@ -42,7 +45,8 @@ BAND = (3, 8, 8)            # rank, world, band_rows: 136 owned rows of 1080
 BAND_FRAMES = 24
 RGB10X2 = [(10, 1, 0, 0), (10, 0, 1, 0), (10, 0, 0, 1), (2, 0, 0, 0)]
 FORMATS = (("rgbx8", fx.RGBX8), ("rgb10x2", RGB10X2))
-DIMS = (3, 4, 5, 6, 7, 8, 10)
+DIMS = (3, 4, 5, 6, 7, 8, 10)           # dimensions whose lean loops take groups of four
+NO_GROUPS = (22, )                      # ... and one beyond NT_BOX_LEAN_GROUPS_MAX_N: the one-row loops alone
 # (label, frames, nt_render_opts::overlapped, block shape: rows a wave x waves a block)
 LAUNCHES = (("24 frames", 24, 0, (8, 4)), ("240 frames", 240, 0, (16, 3)), ("240 frames, overlapped", 240, 1, (64, 1)))
 IL = (H + 63) // 64         # the 64 x 1 launch: waves of a column strip = the stride between a wave's rows
@@ -156,14 +160,54 @@ def group_census(n):
     return out
 
 
+def wave_rows(rows_a_wave, waves_a_block, count):
+    """[wave][slot] -> row of a launch of `count` rows with that block shape: the waves of a column strip deal the rows out
+    (nt_api.cpp: the stride is tiles * waves a block); rows >= count do not exist"""
+    il = (count + rows_a_wave * waves_a_block - 1) // (rows_a_wave * waves_a_block) * waves_a_block
+    return np.arange(il)[:, None] + il * np.arange(rows_a_wave)[None, :]
+
+
+def one_row_census(n):
+    """a dimension without groups, per launch of the GPU test: the 16-row halves of a wave (8 rows a wave: its eight) that hold
+    culled, one-face and ray-by-ray (code 15) rows together and, in the 630 x 200 launches, the culled rows whose guard must fail,
+    over the cameras of dimension n"""
+    band = ntd.owned_rows(TALL, *BAND)
+    launches = [(label, shape, None) for label, _, _, shape in LAUNCHES] + [("bands", (8, 4), band)]
+    out = {label: {"halves-with-all-three": 0, "culled-with-failing-guard": 0} for label, *_ in launches}
+    for _, o, a in cameras(n):
+        lean = lean_ok(o, a)
+        fails = guard_fails(o, a)
+        codes = {False: census.stretch_codes(o, a, W, H)[0], True: census.stretch_codes(o, a, W, TALL, rows=band)[0]}
+        for label, (rows_a_wave, waves_a_block), owned in launches:
+            code = codes[owned is not None]
+            count = len(code)
+            for rows in wave_rows(rows_a_wave, waves_a_block, count):
+                valid = rows < count
+                for col in np.nonzero(lean)[0]:
+                    c = np.where(valid, code[np.minimum(rows, count - 1), col], 99).astype(np.int64)
+                    if owned is None:
+                        out[label]["culled-with-failing-guard"] += int(((c == 0) & fails[np.minimum(rows, H - 1), col]).sum())
+                    for h0 in range(0, rows_a_wave, 16):
+                        ch = c[h0:h0 + 16]
+                        if (ch == 0).any() and ((ch >= 1) & (ch <= 13)).any() and (ch == 15).any():
+                            out[label]["halves-with-all-three"] += 1
+    return out
+
+
 def check_census(n):
+    if n in NO_GROUPS:
+        # (a 630 x 200 frame is too flat for one column strip to show all three kinds of row: the bands of the tall image do)
+        c = one_row_census(n)
+        assert c["bands"]["halves-with-all-three"] >= 10, (n, c)
+        assert all(c[label]["culled-with-failing-guard"] >= 1 for label, *_ in LAUNCHES), (n, c)
+        return
     c = group_census(n)
     for kind in ("culled", "one-face", "two-faces", "mixed", "cut"):
         assert c[kind] >= 10, (n, kind, c)
     assert c["culled-with-failing-guard"] >= 20 and min(c["failing-position"]) >= 1, (n, c)
 
 
-@pytest.mark.parametrize("n", DIMS)
+@pytest.mark.parametrize("n", DIMS + NO_GROUPS)
 def test_cameras_reach_every_branch_of_the_group_loops(n):
     """(no GPU) what the GPU test below relies on"""
     check_census(n)
@@ -208,7 +252,7 @@ def _render(sc, fmt, fo, fa, frames, rows, opts):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", DIMS)
+@pytest.mark.parametrize("n", DIMS + NO_GROUPS)
 def test_rows_rendered_in_groups_equal_the_oracle(n):
     import torch
     check_census(n)
