@@ -263,6 +263,58 @@ int nt_calculate_color(nt_scene_t *s, int x, int y, int width, int height, float
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys,
                  float *rgb, int device);
 
+/* ---- ray queries ---------------------------------------------------------------------------------------
+   KDNode.intersects / KDNode.occludes of the reference (src/ntracer_body.hpp:1412-1496) on the scene's root, for `count`
+   arbitrary rays in one call: a ray in, one record out.  A ray's answer is that of the reference's walk for that ray alone
+   (closest hit: kd_node_intersection, src/tracer.hpp:1179-1243, starting from o_hit.dist = max; occlusion: _occludes,
+   :1258-1307, its far-child rule included); the caller's t_near / t_far go to the root call and (skip_item, skip_lane) is the
+   intersection_target the ray leaves from.  There is no scene-box test in front: the methods have none.
+   CompositeScene only (the reference's BoxScene has no tree): a BoxScene handle is NT_E_INVALID.  An empty scene answers
+   "no hit / not blocked".  The closest-hit walk skips cells beyond the current hit unless strict_reference is set
+   (nt_render_opts, or NTRACER_STRICT_REFERENCE=1), and o_hit.normal is the reference's unless NTRACER_CLEAN_NORMALS=1, both
+   exactly as for a render. */
+#define NT_TH_MAX 24             /* transparent hits kept per ray */
+
+typedef struct {                 /* 16 bytes: one dwordx4 store a ray */
+    float dist;                  /* nearest opaque hit, in units of |direction|; FLT_MAX when none */
+    int32_t item;                /* (index << 2) | NT_KIND_*, the leaf-item code; -1: no opaque hit */
+    int32_t lane;                /* simplex inside the batch; -1 otherwise */
+    int32_t n_transparent;       /* transparent hits left in the reference's list when the walk ends */
+} nt_ray_hit;
+
+typedef struct {
+    int32_t count;
+    const float *origins, *directions;      /* [count][n]; directions are used as given, not normalised */
+    const float *t_near, *t_far;            /* NULL (= -FLT_MAX / FLT_MAX, the reference's defaults) or [count] */
+    const float *distance;                  /* occlusion only: NULL (= FLT_MAX) or [count] */
+    const int32_t *skip_item, *skip_lane;   /* NULL (= none) or [count]: the reference's `source` / `batch_index` */
+} nt_ray_batch;
+
+typedef struct {
+    nt_ray_hit *hits;                       /* [count]; occlusion: item = -1, dist = blocked ? 1 : 0, n_transparent filled */
+    float *normal_origin, *normal_dir;      /* NULL or [count][n]: o_hit.normal; rows of rays without an opaque hit are left alone */
+    nt_ray_hit *transparent;                /* NULL or [count][max_transparent]: the list itself, in the walk's order (unused
+                                               slots: item = -1) */
+    int32_t max_transparent;                /* 0..24 (NT_TH_MAX) */
+} nt_ray_results;
+
+/* Host memory in, host memory out; returns when the results are in place.  Holds the scene like nt_colors_at (NT_E_BUSY
+   while a render runs) and stages through the scene's probe scratch on the library's own stream.  NT_E_INVALID, before any
+   device is touched: NULL rays / out / hits / origins / directions, count < 0, max_transparent outside 0..NT_TH_MAX, a
+   `transparent` pointer with max_transparent == 0.  count == 0: NT_OK without a device. */
+int nt_intersect_rays(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, int device);
+int nt_occludes_rays(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, int device);
+/* Every pointer of `rays` and `out` is DEVICE memory on opts->device; the launch is only enqueued on `hip_stream`, with the
+   stream and lifetime rules of nt_render_device.  Of `opts` (may be NULL) device, strict_reference and abort_device are
+   read -- blocks that start after the abort word is raised leave without writing -- and every other field must be 0, else
+   NT_E_INVALID.  After a warm-up call with the same count nothing is allocated.  (The one buffer a query may allocate, the
+   per-lane `checked` scratch of scenes with transparent materials or Solids, is shared with the scene's renders on that device
+   and only grows: a render in between that needs a larger one reallocates it, which synchronises the device once.) */
+int nt_intersect_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out,
+                             const nt_render_opts *opts, void *hip_stream);
+int nt_occludes_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out,
+                            const nt_render_opts *opts, void *hip_stream);
+
 /* statistics of the last render on this scene that had collect_stats set */
 int nt_scene_last_stats(const nt_scene_t *s, nt_stats *out);
 

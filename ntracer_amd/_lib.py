@@ -78,6 +78,23 @@ class NtStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+NT_TH_MAX = 24
+
+
+class NtRayHit(C.Structure):                 # nt_ray_hit: 16 bytes
+    _fields_ = [("dist", C.c_float), ("item", C.c_int32), ("lane", C.c_int32), ("n_transparent", C.c_int32)]
+
+
+class NtRayBatch(C.Structure):
+    _fields_ = [("count", C.c_int32), ("origins", C.c_void_p), ("directions", C.c_void_p), ("t_near", C.c_void_p),
+                ("t_far", C.c_void_p), ("distance", C.c_void_p), ("skip_item", C.c_void_p), ("skip_lane", C.c_void_p)]
+
+
+class NtRayResults(C.Structure):
+    _fields_ = [("hits", C.c_void_p), ("normal_origin", C.c_void_p), ("normal_dir", C.c_void_p),
+                ("transparent", C.c_void_p), ("max_transparent", C.c_int32)]
+
+
 class NtKdTreeParams(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("split_threshold", C.c_int32), ("traversal_cost", C.c_float),
                 ("intersection_cost", C.c_float)]
@@ -125,6 +142,12 @@ SYMBOLS = [
                                          C.POINTER(NtImageFormat), C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_calculate_color", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
     ("nt_colors_at", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, i32p, i32p, f32p, C.c_int]),
+    ("nt_intersect_rays", C.c_int, [C.c_void_p, C.POINTER(NtRayBatch), C.POINTER(NtRayResults), C.c_int]),
+    ("nt_occludes_rays", C.c_int, [C.c_void_p, C.POINTER(NtRayBatch), C.POINTER(NtRayResults), C.c_int]),
+    ("nt_intersect_rays_device", C.c_int, [C.c_void_p, C.POINTER(NtRayBatch), C.POINTER(NtRayResults), C.POINTER(NtRenderOpts),
+                                           C.c_void_p]),
+    ("nt_occludes_rays_device", C.c_int, [C.c_void_p, C.POINTER(NtRayBatch), C.POINTER(NtRayResults), C.POINTER(NtRenderOpts),
+                                          C.c_void_p]),
     ("nt_scene_last_stats", C.c_int, [C.c_void_p, C.POINTER(NtStats)]),
     ("nt_kdtree_build", C.c_int, [C.c_int, C.c_int, f32p, f32p, i32p, f32p, C.POINTER(NtKdTreeParams), C.POINTER(NtKdTree)]),
     ("nt_kdtree_free", None, [C.POINTER(NtKdTree)]),

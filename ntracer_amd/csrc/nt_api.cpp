@@ -616,6 +616,23 @@ RenderSwitches read_switches() {
     return sw;
 }
 
+// The scratch of the walks that keep the reference's exact `checked` list (renders and ray queries alike): a column of `words`
+// dwords per resident lane, so the GRID is what the scratch has columns for and the blocks stride over the work.  `blocks` comes
+// in as what the work could use and is halved, down to `min_blocks`, until the columns -- with `extra_words` more dwords a lane
+// of other per-lane scratch the caller keeps beside them -- fit `cap_bytes`.  DevBuf::ensure only grows: after a call with the
+// same shape nothing is allocated.
+int checked_scratch(const nt_scene *s, DeviceState *ds, NtCompositeDev &c, long long lanes_per_block, long long &blocks, long long min_blocks,
+                    long long extra_words, long long cap_bytes, bool clean_normals) {
+    const long long words = ((long long)s->n_batches + s->n_triangles + s->n_solids + 31) / 32;
+    while (blocks > min_blocks && blocks * lanes_per_block * (words + extra_words) * 4 > cap_bytes) blocks /= 2;
+    if (int e = ds->checked.ensure((size_t)(blocks * lanes_per_block * words * 4))) return e;
+    c.checked = (uint32_t *)ds->checked.p;
+    c.checked_words = (int)words;
+    c.checked_lanes = (int)(blocks * lanes_per_block);
+    c.alias_normals = clean_normals ? 0 : 1;
+    return NT_OK;
+}
+
 // enqueue's CompositeScene half: the device scene, the `checked` and frame scratch of the faithful kernels, and the packet
 // kernel's counter, cameras, numerators, hit scratch and tile order
 int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, const NtTarget &tg,
@@ -642,17 +659,11 @@ int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, cons
         const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
         const long long lpb = var_t ? 64 : 256;           // lanes per block
         const long long tw = var_t ? 8 : 16;              // tile edge
-        const long long words = ((long long)s->n_batches + s->n_triangles + s->n_solids + 31) / 32;
         const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
         long long tiles = job.colors_out ? (job.probe_count + lpb - 1) / lpb
                                          : (long long)((tg.width + tw - 1) / tw) * ((tg.row_count + tw - 1) / tw) * job.nframes;
         long long blocks = std::min<long long>(std::max<long long>(tiles, 1), var_t ? 8192 : 4096);
-        while (blocks > 64 && blocks * lpb * (words + fwords) * 4 > ((long long)512 << 20)) blocks /= 2;
-        if (int e = ds->checked.ensure((size_t)(blocks * lpb * words * 4))) return e;
-        c.checked = (uint32_t *)ds->checked.p;
-        c.checked_words = (int)words;
-        c.checked_lanes = (int)(blocks * lpb);
-        c.alias_normals = sw.clean_normals ? 0 : 1;
+        if (int e = checked_scratch(s, ds, c, lpb, blocks, 64, fwords, (long long)512 << 20, sw.clean_normals)) return e;
         if (var_t) {
             if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
             c.tframes = (float *)ds->tframes.p;
@@ -1014,6 +1025,150 @@ int tree_depth(const nt_scene_desc *d, int &depth_out) {
 void pad_records(const float *src, long count, int rec_len, int stride, std::vector<float> &out) {
     out.assign((size_t)count * stride, 0.0f);
     for (long i = 0; i < count; ++i) std::memcpy(out.data() + (size_t)i * stride, src + (size_t)i * rec_len, sizeof(float) * rec_len);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ray queries: KDNode.intersects / KDNode.occludes batched (src/ntracer_body.hpp:1412-1496; kernels in nt_query.hpp)
+// ---------------------------------------------------------------------------------------------
+
+// what can be refused without a device
+int query_validate(const nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *out) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!rays || !out || !out->hits || !rays->origins || !rays->directions) return fail(NT_E_INVALID, "NULL argument");
+    if (rays->count < 0) return fail(NT_E_INVALID, "invalid ray count");
+    if (out->max_transparent < 0 || out->max_transparent > NT_TH_MAX)
+        return fail(NT_E_INVALID, "max_transparent must lie in 0..%d", NT_TH_MAX);
+    if (out->transparent && out->max_transparent == 0) return fail(NT_E_INVALID, "a transparent list with max_transparent == 0");
+    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    return NT_OK;
+}
+
+// the launch of one query: `q` holds device pointers.  The `checked` scratch of the walks with transparent hits is sized by the
+// grid: a column per resident lane, at most 256 MB of it, the blocks striding over the rays.
+int query_enqueue(nt_scene *s, DeviceState *ds, NtQuery &q, bool strict, hipStream_t stream) {
+    const RenderSwitches sw = read_switches();
+    NtCompositeDev c;
+    fill_composite(s, ds, c, false);
+    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
+    if (c.root < 0) c.root = -1;
+    const bool var = s->n > NT_MAX_FIXED_DIM || sw.force_var;
+    // closest hits of scenes with transparent materials or Solids: the walk that keeps the transparent hits and the
+    // reference's o_hit.normal, on the exact `checked` list (see plan_composite); occlusion walks keep no such list
+    const bool faithful = !q.occlusion && (!s->all_opaque || (s->n_solids > 0 && !sw.clean_normals));
+    if (faithful) {
+        // (a query keeps no ray_color frames: a quarter of the renderer's blocks are more than are resident, and half its bytes)
+        const long long lpb = var ? 64 : 256;
+        long long blocks = std::min<long long>(((long long)q.count + lpb - 1) / lpb, var ? 4096 : 1024);
+        if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, 0, (long long)256 << 20, sw.clean_normals)) return e;
+    }
+    NtLaunchInfo li{};
+    li.n = s->n;
+    li.nframes = 1;
+    li.stream = stream;
+    li.cu_count = ds->cu_count;
+    li.force_var = sw.force_var;
+    const int r = nt_launch_query(li, c, q);
+    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    return NT_OK;
+}
+
+int query_host(nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *out, int device, bool occlusion) {
+    if (int r = query_validate(s, rays, out)) return r;
+    if (rays->count == 0) return NT_OK;
+    if (int r = check_renderable(s)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    int dev;
+    if (int r = pick_device(nullptr, device, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = own_stream(ds)) return r;
+    if (int r = use_stream(ds, ds->stream)) return r;
+    // one slab of the probe scratch: rays | per-ray parameters | normals | records | lists, each 16-byte aligned
+    const size_t count = (size_t)rays->count, n = (size_t)s->n;
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t vlen = count * n * sizeof(float), flen = count * sizeof(float);
+    const size_t rbytes = count * sizeof(nt_ray_hit);
+    const size_t lbytes = out->transparent ? rbytes * (size_t)out->max_transparent : 0;
+    const float *distance = occlusion ? rays->distance : nullptr;
+    float *normal_origin = occlusion ? nullptr : out->normal_origin, *normal_dir = occlusion ? nullptr : out->normal_dir;
+    size_t total = 2 * al(vlen) + rbytes + lbytes;
+    for (const void *p : {(const void *)rays->t_near, (const void *)rays->t_far, (const void *)distance, (const void *)rays->skip_item,
+                          (const void *)rays->skip_lane})
+        if (p) total += al(flen);
+    if (normal_origin) total += al(vlen);
+    if (normal_dir) total += al(vlen);
+    if (int r = ds->probes.ensure(total)) return r;
+    char *at = (char *)ds->probes.p;
+    hipStream_t st = ds->stream;
+    // an array of the caller's, copied to the next free piece of the slab (nullptr stays nullptr)
+    auto up = [&](const void *src, size_t bytes, void *&dst) -> hipError_t {
+        dst = nullptr;
+        if (!src) return hipSuccess;
+        dst = at;
+        at += al(bytes);
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    NtQuery q{};
+    q.count = rays->count;
+    q.occlusion = occlusion ? 1 : 0;
+    void *d;
+    HIP_TRY(up(rays->origins, vlen, d)); q.origins = (const float *)d;
+    HIP_TRY(up(rays->directions, vlen, d)); q.directions = (const float *)d;
+    HIP_TRY(up(rays->t_near, flen, d)); q.t_near = (const float *)d;
+    HIP_TRY(up(rays->t_far, flen, d)); q.t_far = (const float *)d;
+    HIP_TRY(up(distance, flen, d)); q.distance = (const float *)d;
+    HIP_TRY(up(rays->skip_item, flen, d)); q.skip_item = (const int *)d;
+    HIP_TRY(up(rays->skip_lane, flen, d)); q.skip_lane = (const int *)d;
+    // (the kernels do not write the normal rows of rays without an opaque hit: the caller's rows travel through)
+    HIP_TRY(up(normal_origin, vlen, d)); q.normal_origin = (float *)d;
+    HIP_TRY(up(normal_dir, vlen, d)); q.normal_dir = (float *)d;
+    q.hits = at;
+    at += rbytes;
+    q.transparent = out->transparent ? at : nullptr;
+    q.max_transparent = out->max_transparent;
+    if (int r = query_enqueue(s, ds, q, false, st)) { (void)hipStreamSynchronize(st); return r; }
+    HIP_TRY(hipMemcpyAsync(out->hits, q.hits, rbytes, hipMemcpyDeviceToHost, st));
+    if (q.normal_origin) HIP_TRY(hipMemcpyAsync(normal_origin, q.normal_origin, vlen, hipMemcpyDeviceToHost, st));
+    if (q.normal_dir) HIP_TRY(hipMemcpyAsync(normal_dir, q.normal_dir, vlen, hipMemcpyDeviceToHost, st));
+    if (q.transparent) HIP_TRY(hipMemcpyAsync(out->transparent, q.transparent, lbytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return NT_OK;
+}
+
+int query_device(nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *out, const nt_render_opts *opts, void *hip_stream,
+                 bool occlusion) {
+    if (int r = query_validate(s, rays, out)) return r;
+    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
+        return fail(NT_E_INVALID, "a ray query reads device, strict_reference and abort_device of its options: every other field must be 0");
+    if (rays->count == 0) return NT_OK;
+    if (int r = check_renderable(s)) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    NtQuery q{};
+    q.count = rays->count;
+    q.occlusion = occlusion ? 1 : 0;
+    q.origins = rays->origins;
+    q.directions = rays->directions;
+    q.t_near = rays->t_near;
+    q.t_far = rays->t_far;
+    q.distance = occlusion ? rays->distance : nullptr;
+    q.skip_item = rays->skip_item;
+    q.skip_lane = rays->skip_lane;
+    q.hits = out->hits;
+    q.normal_origin = occlusion ? nullptr : out->normal_origin;
+    q.normal_dir = occlusion ? nullptr : out->normal_dir;
+    q.transparent = out->transparent;
+    q.max_transparent = out->max_transparent;
+    q.abort_word = opts ? (const int *)opts->abort_device : nullptr;
+    return query_enqueue(s, ds, q, opts && opts->strict_reference, (hipStream_t)hip_stream);
 }
 
 }  // namespace
@@ -1521,6 +1676,22 @@ int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t 
 int nt_calculate_color(nt_scene_t *s, int x, int y, int width, int height, float rgb[3]) {
     const int32_t xs = x, ys = y;
     return nt_colors_at(s, width, height, 1, &xs, &ys, rgb, -1);
+}
+
+int nt_intersect_rays(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, int device) {
+    return query_host(s, rays, out, device, false);
+}
+
+int nt_occludes_rays(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, int device) {
+    return query_host(s, rays, out, device, true);
+}
+
+int nt_intersect_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, const nt_render_opts *opts, void *hip_stream) {
+    return query_device(s, rays, out, opts, hip_stream, false);
+}
+
+int nt_occludes_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, const nt_render_opts *opts, void *hip_stream) {
+    return query_device(s, rays, out, opts, hip_stream, true);
 }
 
 int nt_scene_last_stats(const nt_scene_t *cs, nt_stats *out) {

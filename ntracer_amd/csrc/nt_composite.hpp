@@ -340,6 +340,19 @@ __device__ __forceinline__ float branch_t(const WaveLds &w, int lane, const NtNo
     return (nd.split - oi.x) * oi.y;
 }
 
+// The interval the root call of a walk starts from.  The render kernels' rays start at the scene box: their walks take
+// RootWhole, an empty type that costs the call nothing.  A ray query (nt_query.hpp) hands the caller's t_near / t_far to the
+// root call, as KDNode.intersects / occludes do (ntracer_body.hpp:1412-1496): RootWindow.
+struct RootWhole {
+    __device__ __forceinline__ float t_near() const { return 0.0f; }
+    __device__ __forceinline__ float t_far() const { return FLT_MAX; }
+};
+struct RootWindow {
+    float tn, tf;
+    __device__ __forceinline__ float t_near() const { return tn; }
+    __device__ __forceinline__ float t_far() const { return tf; }
+};
+
 template <int N, bool FEAT, bool STATS, bool SCALP = FEAT>
 __device__ __noinline__ bool trace_closest(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
                                               float t_near, float t_far_root, int skip_item, int skip_lane, Hit &hit, Stats &st) {
@@ -466,16 +479,16 @@ __device__ __forceinline__ bool leaf_occludes(const NtCompositeDev &sc, int star
 // (the ray travels BY VALUE: up to four dimensions that is registers -- the calling convention passes an aggregate of at most 16
 // dwords directly -- where two references to the caller's arrays were two round trips through scratch memory per component)
 template <int N> struct RayArg { float o[N], d[N]; };
-template <int N, bool STATS, bool SCALP = true>
+template <int N, bool STATS, bool SCALP = true, typename ROOT = RootWhole>
 __device__ NT_OCCL_ATTR bool trace_occluded(const NtCompositeDev &sc, const WaveLds &w, int lane, const RayArg<N> ray,
-                                            float ldistance, int skip_item, int skip_lane, Stats &st) {
+                                            float ldistance, int skip_item, int skip_lane, Stats &st, const ROOT root = ROOT()) {
     const float (&o)[N] = ray.o;
     const float (&d)[N] = ray.d;
     setup_ray_table<N>(w, lane, o, d);
     int node = sc.root;
     int sp = 0;
-    float t_near = 0.0f;
-    float t_far = FLT_MAX;
+    float t_near = root.t_near();
+    float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     if (STATS) st.shadow_rays += 1;
     for (;;) {
@@ -524,7 +537,7 @@ __device__ NT_OCCL_ATTR bool trace_occluded(const NtCompositeDev &sc, const Wave
             if (t < ldistance || far < 0) continue;             // frame returns false
             node = far;
             t_near = t;
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             if (sp > 0) {
                 const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
                 bool g2;
@@ -1102,10 +1115,10 @@ __device__ __noinline__ bool leaf_closest_t(const NtCompositeDev &sc, const Wave
 // kd_node_intersection::operator() with the transparent-list trims (tracer.hpp:1211-1231).  Stack entries:
 // branch index | list size at the push << 24; NT_STK_MARK marks "far side of this branch is being walked
 // after a near hit: trim the list when it returns with a closer hit".
-template <int N, bool ALIAS>
+template <int N, bool ALIAS, typename ROOT = RootWhole>
 __device__ __noinline__ bool trace_closest_t(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
                                              float t_near, int skip_item, int skip_lane, Hit &hit, TList &th, const Checked &ck,
-                                             float (&hn_o)[N], float (&hn_d)[N]) {
+                                             float (&hn_o)[N], float (&hn_d)[N], const ROOT root = ROOT()) {
     hit.dist = FLT_MAX;
     hit.item = -1;
     hit.lane = -1;
@@ -1114,7 +1127,7 @@ __device__ __noinline__ bool trace_closest_t(const NtCompositeDev &sc, const Wav
     int node = sc.root;
     int sp = 0;
     int dirty = 0;
-    float t_far = FLT_MAX;
+    float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     for (;;) {
         while (node >= 0) {
@@ -1173,7 +1186,7 @@ __device__ __noinline__ bool trace_closest_t(const NtCompositeDev &sc, const Wav
             node = far;
             t_near = t;
             // t_far of this frame: the split of the nearest pending (non-marker) branch below
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             for (int k = (improved ? sp - 2 : sp - 1); k >= 0; --k) {
                 const unsigned ek = (unsigned)w.stack[k * 64 + lane];
                 if (!(ek & NT_STK_MARK)) {
@@ -1192,15 +1205,15 @@ __device__ __noinline__ bool trace_closest_t(const NtCompositeDev &sc, const Wav
 }
 
 // _occludes + kd_leaf::occludes with transparent hits collected (tracer.hpp:1088-1124, 1258-1307)
-template <int N>
+template <int N, typename ROOT = RootWhole>
 __device__ __noinline__ bool trace_occluded_t(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
-                                              float ldistance, int skip_item, int skip_lane, TList &sh) {
+                                              float ldistance, int skip_item, int skip_lane, TList &sh, const ROOT root = ROOT()) {
     setup_ray_table<N>(w, lane, o, d);
     sh.n = 0;
     int node = sc.root;
     int sp = 0;
-    float t_near = 0.0f;
-    float t_far = FLT_MAX;
+    float t_near = root.t_near();
+    float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     for (;;) {
         while (node >= 0) {
@@ -1252,7 +1265,7 @@ __device__ __noinline__ bool trace_occluded_t(const NtCompositeDev &sc, const Wa
             if (t < ldistance || far < 0) continue;
             node = far;
             t_near = t;
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             if (sp > 0) {
                 const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
                 bool g2;

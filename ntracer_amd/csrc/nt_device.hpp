@@ -205,12 +205,32 @@ static inline NtBoxTileGeom nt_box_tile_geom(int width, int row_count, int nfram
     return g;
 }
 
+// One batched ray query (nt_query.hpp, nt_var.hip): `count` rays from device memory, one 16-byte record a ray out.
+// Every pointer is device memory; the optional ones are nullptr when the caller left them out.
+struct NtQuery {
+    int count;
+    int occlusion;            // 0: closest hit (KDNode.intersects), 1: KDNode.occludes
+    const float *origins;     // [count][n]
+    const float *directions;  // [count][n], used as given
+    const float *t_near, *t_far;          // nullptr (-FLT_MAX / FLT_MAX) or [count]
+    const float *distance;                // occlusion: nullptr (FLT_MAX) or [count]
+    const int *skip_item, *skip_lane;     // nullptr (none) or [count]
+    void *hits;               // [count] records {float dist; int item, lane, n_transparent} (nt_ray_hit)
+    float *normal_origin, *normal_dir;    // nullptr or [count][n]; rows of rays without an opaque hit are not written
+    void *transparent;        // nullptr or [count][max_transparent] records: the transparent hits in the walk's order
+    int max_transparent;
+    const int *abort_word;    // as NtTarget::abort_word
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
 // of `nframes` frames -- 12-byte fp32 x 3 pixels as the render kernels write them, s * tg.row_count rows of `pitch_bytes` a frame
 // -- averaged and packed into tg.dest
 int nt_launch_resolve(int s, void *stream, const void *samples, long long frame_stride_bytes, long long pitch_bytes, int nframes, const NtTarget &tg);
+// the query kernels; sc.checked (with checked_lanes = blocks of the launch * lanes a block) selects the walks with transparent
+// hits and the reference's o_hit.normal handling, as for a render
+int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

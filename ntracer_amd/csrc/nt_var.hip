@@ -2,12 +2,14 @@
 // [k][lane]) and the dispatch over the dimension: nt_launch_box / nt_launch_composite.
 #include "nt_box.hpp"
 #include "nt_composite.hpp"
+#include "nt_query.hpp"
 #include "nt_resolve.hpp"
 
 // compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
 #define NT_DECLARE_FIXED(N)                                                                              \
     int nt_box_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);               \
-    int nt_composite_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
+    int nt_composite_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg); \
+    int nt_query_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q);
 NT_DECLARE_FIXED(3) NT_DECLARE_FIXED(4) NT_DECLARE_FIXED(5) NT_DECLARE_FIXED(6)
 NT_DECLARE_FIXED(7) NT_DECLARE_FIXED(8) NT_DECLARE_FIXED(9) NT_DECLARE_FIXED(10)
 // (BoxScene alone: 11..24)
@@ -570,7 +572,8 @@ __device__ __forceinline__ bool leaf_closest_var(const VarCtx &cx, int start, in
 }
 
 // kd_node_intersection::operator() (tracer.hpp:1179-1243): the continuation stack of trace_closest (nt_composite.hpp)
-__device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit) {
+template <typename ROOT = RootWhole>
+__device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
     const int lane = cx.lane;
@@ -579,7 +582,7 @@ __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, i
     hit.lane = -1;
     mbox_reset(w, lane);
     int node = sc.root, sp = 0, dirty = 0;
-    float t_far = FLT_MAX;
+    float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     for (;;) {
         while (node >= 0) {
@@ -624,7 +627,7 @@ __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, i
             if ((near_hit && hit.dist <= t) || far < 0) continue;
             node = far;
             t_near = t;
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             if (sp > 0) {
                 const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
                 bool g2;
@@ -663,12 +666,13 @@ __device__ __forceinline__ bool leaf_occludes_var(const VarCtx &cx, int start, i
 }
 
 // _occludes (tracer.hpp:1258-1307) for the current ray, `if(t < ldistance) return false;` (:1298) included
-__device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistance, int skip_item, int skip_lane) {
+template <typename ROOT = RootWhole>
+__device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
     const int lane = cx.lane;
     int node = sc.root, sp = 0;
-    float t_near = 0.0f, t_far = FLT_MAX;
+    float t_near = root.t_near(), t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     for (;;) {
         while (node >= 0) {
@@ -711,7 +715,7 @@ __device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistanc
             if (t < ldistance || far < 0) continue;
             node = far;
             t_near = t;
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             if (sp > 0) {
                 const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
                 bool g2;
@@ -1094,9 +1098,9 @@ __device__ __noinline__ bool leaf_closest_var_t(const VarCtx &cx, int start, int
 }
 
 // trace_closest_t (nt_composite.hpp) for the current ray
-template <bool ALIAS>
+template <bool ALIAS, typename ROOT = RootWhole>
 __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit, TList &th,
-                                                 const Checked &ck, float *hn_o, float *hn_d, float *nn_o, float *nn_d) {
+                                                 const Checked &ck, float *hn_o, float *hn_d, float *nn_o, float *nn_d, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
     const int lane = cx.lane;
@@ -1106,7 +1110,7 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
     th.n = 0;
     checked_reset(ck);
     int node = sc.root, sp = 0, dirty = 0;
-    float t_far = FLT_MAX;
+    float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     for (;;) {
         while (node >= 0) {
@@ -1163,7 +1167,7 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
             }
             node = far;
             t_near = t;
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             for (int k = (improved ? sp - 2 : sp - 1); k >= 0; --k) {
                 const unsigned ek = (unsigned)w.stack[k * 64 + lane];
                 if (!(ek & NT_STK_MARK)) {
@@ -1182,13 +1186,14 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
 }
 
 // trace_occluded_t (nt_composite.hpp) for the current ray: transparent hits are collected, an opaque one blocks
-__device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, TList &sh) {
+template <typename ROOT = RootWhole>
+__device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, TList &sh, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
     const int lane = cx.lane;
     sh.n = 0;
     int node = sc.root, sp = 0;
-    float t_near = 0.0f, t_far = FLT_MAX;
+    float t_near = root.t_near(), t_far = root.t_far();
     const int max_sp = sc.stack_depth;
     for (;;) {
         while (node >= 0) {
@@ -1240,7 +1245,7 @@ __device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldista
             if (t < ldistance || far < 0) continue;
             node = far;
             t_near = t;
-            t_far = FLT_MAX;
+            t_far = root.t_far();
             if (sp > 0) {
                 const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
                 bool g2;
@@ -1559,6 +1564,145 @@ __global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompo
     emit_pixel(tg, pr, col.r, col.g, col.b);
 }
 
+// --------------------------------------------------------------------------------------
+// Ray queries at run-time n (n = 11..64, and every n under NTRACER_FORCE_VAR=1): the kernels of nt_query.hpp on the walks
+// above.  One lane per ray and one wave a block, as the run-time-n render kernels have it -- their n-vectors in LDS make
+// four waves' worth too much at the upper dimensions -- so lane l of block b takes ray 64 b + l, and the blocks stride on.
+// --------------------------------------------------------------------------------------
+__device__ __forceinline__ void query_var_lds(char *p, int n, int depth, VarLds &L, WaveLds &w) {
+    L.ray = reinterpret_cast<float2 *>(p);
+    L.dv = reinterpret_cast<float *>(p + (size_t)64 * n * 8);
+    L.ps = L.dv + (size_t)64 * n;
+    L.stack = reinterpret_cast<int *>(L.ps + (size_t)64 * n);
+    L.mbox = L.stack + (size_t)64 * depth;
+    w.ray = L.ray;
+    w.stack = L.stack;
+    w.mbox = L.mbox;
+}
+
+__device__ __forceinline__ void query_store_normal_var(const NtQuery &q, long long r, int n, const float *no, const float *nd) {
+    if (q.normal_origin) for (int k = 0; k < n; ++k) q.normal_origin[r * n + k] = no[k];
+    if (q.normal_dir) for (int k = 0; k < n; ++k) q.normal_dir[r * n + k] = nd[k];
+}
+
+__global__ __launch_bounds__(64) void query_closest_var(NtCompositeDev sc, NtQuery q, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
+        if (query_aborted(q)) return;
+        const long long r = base + lane;
+        if (r >= q.count) continue;
+        var_set_ray(cx, q.origins + r * n, q.directions + r * n);
+        const QueryRay p = query_ray(q, r);
+        RootWindow root;
+        root.tn = p.t_near;
+        root.tf = p.t_far;
+        Hit hit;
+        trace_closest_var<RootWindow>(cx, p.t_near, p.skip_item, p.skip_lane, hit, root);
+        query_store(q.hits, r, hit.dist, hit.item, hit.lane, 0);
+        if (hit.item >= 0 && (q.normal_origin || q.normal_dir)) {
+            float no[NT_DEV_MAX_DIM], nd[NT_DEV_MAX_DIM];
+            hit_normal_var(cx, hit, no, nd);
+            query_store_normal_var(q, r, n, no, nd);
+        }
+        if (q.transparent) {
+            TList none;
+            none.n = 0;
+            query_store_list(q, r, none);
+        }
+    }
+}
+
+template <bool ALIAS>
+__global__ __launch_bounds__(64) void query_closest_var_t(NtCompositeDev sc, NtQuery q, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    Checked ck;
+    ck.bits = sc.checked + ((long long)blockIdx.x * 64 + lane);
+    ck.stride = sc.checked_lanes;
+    ck.words = sc.checked_words;
+    ck.n_batches = sc.n_batches;
+    ck.n_triangles = sc.n_triangles;
+    for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
+        if (query_aborted(q)) return;
+        const long long r = base + lane;
+        if (r >= q.count) continue;
+        var_set_ray(cx, q.origins + r * n, q.directions + r * n);
+        const QueryRay p = query_ray(q, r);
+        RootWindow root;
+        root.tn = p.t_near;
+        root.tf = p.t_far;
+        Hit hit;
+        TList th;
+        float hn_o[NT_DEV_MAX_DIM], hn_d[NT_DEV_MAX_DIM], nn_o[NT_DEV_MAX_DIM], nn_d[NT_DEV_MAX_DIM];
+        for (int k = 0; k < n; ++k) { hn_o[k] = 0.0f; hn_d[k] = 0.0f; }       // ray_intersection starts out zeroed
+        trace_closest_var_t<ALIAS, RootWindow>(cx, p.t_near, p.skip_item, p.skip_lane, hit, th, ck, hn_o, hn_d, nn_o, nn_d, root);
+        query_store(q.hits, r, hit.dist, hit.item, hit.lane, th.n);
+        if (hit.item >= 0 && (q.normal_origin || q.normal_dir)) {
+            if (!ALIAS) hit_normal_var(cx, hit, hn_o, hn_d);
+            query_store_normal_var(q, r, n, hn_o, hn_d);
+        }
+        query_store_list(q, r, th);
+    }
+}
+
+__global__ __launch_bounds__(64) void query_occluded_var(NtCompositeDev sc, NtQuery q, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
+        if (query_aborted(q)) return;
+        const long long r = base + lane;
+        if (r >= q.count) continue;
+        var_set_ray(cx, q.origins + r * n, q.directions + r * n);
+        const QueryRay p = query_ray(q, r);
+        RootWindow root;
+        root.tn = p.t_near;
+        root.tf = p.t_far;
+        const bool blocked = trace_occluded_var<RootWindow>(cx, p.distance, p.skip_item, p.skip_lane, root);
+        query_store(q.hits, r, blocked ? 1.0f : 0.0f, -1, -1, 0);
+        if (q.transparent) {
+            TList none;
+            none.n = 0;
+            query_store_list(q, r, none);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void query_occluded_var_t(NtCompositeDev sc, NtQuery q, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
+        if (query_aborted(q)) return;
+        const long long r = base + lane;
+        if (r >= q.count) continue;
+        var_set_ray(cx, q.origins + r * n, q.directions + r * n);
+        const QueryRay p = query_ray(q, r);
+        RootWindow root;
+        root.tn = p.t_near;
+        root.tf = p.t_far;
+        TList sh;
+        const bool blocked = trace_occluded_var_t<RootWindow>(cx, p.distance, p.skip_item, p.skip_lane, sh, root);
+        query_store(q.hits, r, blocked ? 1.0f : 0.0f, -1, -1, sh.n);
+        query_store_list(q, r, sh);
+    }
+}
+
 #undef VO
 #undef VD
 
@@ -1693,4 +1837,55 @@ int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCom
     }
     if (r) return r;
     return finish_launch("composite kernel launch");
+}
+
+// Ray queries (nt_query.hpp): the fixed-n launcher of the scene's dimension, or the run-time-n kernels above.  Kept apart from
+// nt_launch_composite: these are no render routes.
+int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q) {
+    int r;
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_query_fixed_3(li, sc, q); break;
+        case 4: r = nt_query_fixed_4(li, sc, q); break;
+        case 5: r = nt_query_fixed_5(li, sc, q); break;
+        case 6: r = nt_query_fixed_6(li, sc, q); break;
+        case 7: r = nt_query_fixed_7(li, sc, q); break;
+        case 8: r = nt_query_fixed_8(li, sc, q); break;
+        case 9: r = nt_query_fixed_9(li, sc, q); break;
+        case 10: r = nt_query_fixed_10(li, sc, q); break;
+        default: {
+            if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
+                return -2;
+            }
+            const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc.stack_depth * 4 + (size_t)NT_MBOX * 4);
+            if (lds > 160 * 1024) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc.stack_depth);
+                return -1;
+            }
+            hipStream_t s = (hipStream_t)li.stream;
+            const dim3 grid((unsigned)(((long long)q.count + 63) / 64));
+            const void *kernel;
+            if (q.occlusion) kernel = sc.all_opaque ? reinterpret_cast<const void *>(query_occluded_var) : reinterpret_cast<const void *>(query_occluded_var_t);
+            else if (!sc.checked) kernel = reinterpret_cast<const void *>(query_closest_var);
+            else kernel = sc.alias_normals ? reinterpret_cast<const void *>(query_closest_var_t<true>) : reinterpret_cast<const void *>(query_closest_var_t<false>);
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (q.occlusion) {
+                if (sc.all_opaque) hipLaunchKernelGGL(query_occluded_var, grid, dim3(64), lds, s, sc, q, li.n);
+                else hipLaunchKernelGGL(query_occluded_var_t, grid, dim3(64), lds, s, sc, q, li.n);
+            } else if (sc.checked) {
+                // as many blocks as the `checked` scratch has lane columns for, striding over the rays
+                const dim3 tgrid((unsigned)(sc.checked_lanes / 64));
+                if (sc.alias_normals) hipLaunchKernelGGL(query_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, q, li.n);
+                else hipLaunchKernelGGL(query_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, q, li.n);
+            } else if (!sc.all_opaque) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: transparent scene without the checked-list scratch");
+                return -1;
+            } else {
+                hipLaunchKernelGGL(query_closest_var, grid, dim3(64), lds, s, sc, q, li.n);
+            }
+            r = 0;
+        }
+    }
+    if (r) return r;
+    return finish_launch("query kernel launch");
 }

@@ -8,6 +8,7 @@ Scene construction (Triangle.from_points/to_points, prototypes, build_kdtree, bu
 """
 import ctypes as C
 import math
+import weakref
 
 import numpy as np
 
@@ -16,6 +17,7 @@ from . import render as _render
 from .render import Color, Material, Scene
 
 BATCH_SIZE = _lib.NT_BATCH_SIZE     # tracer.hpp:34-38 (SSE reference build)
+_ROUNDING_FUZZ = 1.1920928955078125e-07 * 10.0     # tracer.hpp:25
 CUBE, SPHERE = 1, 2                  # wrapper.CUBE / wrapper.SPHERE (tracer.hpp:225)
 
 f32 = np.float32
@@ -516,8 +518,89 @@ class Solid(Primitive):
         return _render._solid_unpickle, (self.dimension, data, self.material)
 
 
+class RayIntersection(object):
+    """tracern.RayIntersection(dist,origin,normal,primitive,batch_index=-1) -- what KDNode.intersects / occludes answer
+    with (ntracer_body.hpp:362-377, 1759-1810): the distance along the ray in units of |direction|, the normal ray of the
+    surface (`origin`: the hit point, `normal`: its direction) and what was hit."""
+    __slots__ = ("_dist", "_origin", "_normal", "_primitive", "_batch_index")
+
+    def __init__(self, dist, origin, normal, primitive, batch_index=-1):
+        batch_index = int(batch_index)
+        if isinstance(primitive, Primitive):
+            if batch_index != -1:
+                raise ValueError('"batch_index" cannot be anything other than -1 unless "primitive" is an instance of PrimitiveBatch')
+        elif isinstance(primitive, PrimitiveBatch):
+            if batch_index < 0:
+                raise ValueError('"batch_index" cannot be less than zero if "primitive" is an instance of PrimitiveBatch')
+        else:
+            raise TypeError('"primitive" must either be an instance of Primitive or PrimitiveBatch')
+        origin = origin if isinstance(origin, Vector) else Vector(len(origin), origin)
+        normal = normal if isinstance(normal, Vector) else Vector(len(normal), normal)
+        if origin.dimension != normal.dimension:
+            raise TypeError('"origin" and "normal" must have the same dimension')
+        self._dist, self._origin, self._normal = float(dist), origin, normal
+        self._primitive, self._batch_index = primitive, batch_index
+
+    dist = property(lambda s: s._dist)
+    origin = property(lambda s: s._origin)
+    normal = property(lambda s: s._normal)
+    primitive = property(lambda s: s._primitive)
+    batch_index = property(lambda s: s._batch_index)
+
+    def __repr__(self):
+        return "RayIntersection(%r,%r,%r,%r,%r)" % (self._dist, self._origin, self._normal, self._primitive, self._batch_index)
+
+
 class KDNode(object):
-    pass
+    """tracern.KDNode: base of KDLeaf / KDBranch.  The two ray queries of the reference (ntracer_body.hpp:1412-1496) run
+    on the device, one ray a call here -- CompositeScene.intersect_rays / occludes_rays are the batched forms underneath."""
+    _owner = None           # weak reference to the CompositeScene this node is the root of
+    _private = None         # ... or a scene of its own, made on first use (its boundary is never consulted by a query)
+
+    def _query_scene(self):
+        sc = self._owner() if self._owner is not None else None
+        if sc is None:
+            if self._private is None:
+                n = self.dimension
+                self._private = CompositeScene._for_node(AABB(n, [-1.0] * n, [1.0] * n), self)
+            sc = self._private
+        return sc
+
+    def _ray_args(self, origin, direction, source, batch_index):
+        o = origin if isinstance(origin, Vector) else Vector(len(origin), origin)
+        d = direction if isinstance(direction, Vector) else Vector(len(direction), direction)
+        if o.dimension != d.dimension:
+            raise TypeError('"origin" and "direction" must have the same dimension')
+        if o.dimension != self.dimension:
+            raise TypeError("the ray and the node must have the same dimension")
+        if source is not None and not isinstance(source, (Primitive, PrimitiveBatch)):
+            raise TypeError('"source" must be an instance of Primitive or PrimitiveBatch')
+        sc = self._query_scene()
+        item = sc._item_of(source) if source is not None else -1
+        lane = int(batch_index) if isinstance(source, PrimitiveBatch) else -1
+        return sc, o._v[None], d._v[None], np.asarray([item], np.int32), np.asarray([lane], np.int32)
+
+    def intersects(self, origin, direction, t_near=None, t_far=None, source=None, batch_index=-1):
+        """KDNode.intersects(origin,direction,t_near,t_far,source,batch_index): the transparent hits, then the opaque hit
+        if there is one, as RayIntersection objects."""
+        sc, o, d, si, sl = self._ray_args(origin, direction, source, batch_index)
+        r = sc.intersect_rays(o, d, None if t_near is None else [t_near], None if t_far is None else [t_far], si, sl,
+                              normals=True, max_transparent=_lib.NT_TH_MAX)
+        hits = sc._transparent_hits(o[0], d[0], r["transparent"][0], int(r["n_transparent"][0]))
+        if r["kind"][0] >= 0:
+            hits.append(RayIntersection(float(r["dist"][0]), Vector._wrap(r["normal_origin"][0].copy()), Vector._wrap(r["normal"][0].copy()),
+                                        sc._object_of(int(r["kind"][0]), int(r["index"][0])), int(r["lane"][0])))
+        return hits
+
+    def occludes(self, origin, direction, distance=None, t_near=None, t_far=None, source=None, batch_index=-1):
+        """KDNode.occludes(origin,direction,distance,t_near,t_far,source,batch_index): (occluded, hits) -- the transparent
+        hits met on the way when nothing opaque lies nearer than `distance`, else None."""
+        sc, o, d, si, sl = self._ray_args(origin, direction, source, batch_index)
+        r = sc.occludes_rays(o, d, None if distance is None else [distance], None if t_near is None else [t_near],
+                             None if t_far is None else [t_far], si, sl, max_transparent=_lib.NT_TH_MAX)
+        if r["blocked"][0]:
+            return True, None
+        return False, sc._transparent_hits(o[0], d[0], r["transparent"][0], int(r["n_transparent"][0]))
 
 
 class KDLeaf(KDNode):
@@ -668,6 +751,15 @@ class CompositeScene(_SceneBase):
             raise TypeError("boundary and data must have the same dimension")
         self._create(self._flatten(boundary, data))
         self._root_obj = data
+        data._owner = weakref.ref(self)
+
+    @classmethod
+    def _for_node(cls, boundary, node):
+        """the private scene of a node that is no scene's root (KDNode._query_scene)"""
+        self = object.__new__(cls)
+        self._create(cls._flatten(boundary, node))
+        self._root_obj = node
+        return self
 
     @classmethod
     def from_flat(cls, dimension, flat):
@@ -684,6 +776,7 @@ class CompositeScene(_SceneBase):
         nodes, items = [], []
         batch_ids, tri_ids, solid_ids, mat_ids = {}, {}, {}, {}
         batch_recs, batch_mats, tri_recs, tri_mats, solid_recs, solid_types, solid_mats, mats = [], [], [], [], [], [], [], []
+        objects = ([], [], [])            # item -> the caller's object, per kind (RayIntersection.primitive)
 
         def mat(m):
             k = m._key()
@@ -696,17 +789,20 @@ class CompositeScene(_SceneBase):
             if isinstance(p, TriangleBatch):
                 if id(p) not in batch_ids:
                     batch_ids[id(p)] = len(batch_recs)
+                    objects[_lib.KIND_BATCH].append(p)
                     batch_recs.append([t._record() for t in p._tris])
                     batch_mats.append([mat(t.material) for t in p._tris])
                 return (batch_ids[id(p)] << 2) | _lib.KIND_BATCH
             if isinstance(p, Triangle):
                 if id(p) not in tri_ids:
                     tri_ids[id(p)] = len(tri_recs)
+                    objects[_lib.KIND_TRIANGLE].append(p)
                     tri_recs.append(p._record())
                     tri_mats.append(mat(p.material))
                 return (tri_ids[id(p)] << 2) | _lib.KIND_TRIANGLE
             if id(p) not in solid_ids:
                 solid_ids[id(p)] = len(solid_recs)
+                objects[_lib.KIND_SOLID].append(p)
                 solid_recs.append(np.concatenate([p.orientation._m.ravel(), p.inv_orientation._m.ravel(), p.position._v]))
                 solid_types.append(p.type)
                 solid_mats.append(mat(p.material))
@@ -733,7 +829,7 @@ class CompositeScene(_SceneBase):
         root_idx = add(root)
         nd = np.asarray(nodes, np.float64).reshape(-1, 4)
         rl = n * n + n + 1
-        return dict(dimension=n, root=root_idx,
+        return dict(dimension=n, root=root_idx, _objects=objects,
                     node_axis=nd[:, 0].astype(np.int32), node_split=nd[:, 1].astype(f32),
                     node_left=nd[:, 2].astype(np.int32), node_right=nd[:, 3].astype(np.int32),
                     items=np.asarray(items, np.int32),
@@ -827,7 +923,10 @@ class CompositeScene(_SceneBase):
         srecs = np.asarray(f["solid_recs"], f32).reshape(-1, 2 * n * n + n)
         solids = [Solid(int(f["solid_types"][k]), srecs[k, 2 * n * n:], Matrix._wrap(srecs[k, :n * n].reshape(n, n)), mats[int(f["solid_mats"][k])])
                   for k in range(len(srecs))]
+        for k, sol in enumerate(solids):       # the inverse the scene was made with, not a recomputed one
+            sol.inv_orientation = Matrix._wrap(srecs[k, n * n:2 * n * n].reshape(n, n))
         tables = (batches, tris, solids)
+        self._objects = tables
         axis, split, left, right, items = f["node_axis"], f["node_split"], f["node_left"], f["node_right"], f["items"]
         made = {}
         order, stack = [], [int(f["root"])] if int(f["root"]) >= 0 else []
@@ -842,6 +941,8 @@ class CompositeScene(_SceneBase):
             else:
                 made[k] = KDBranch(int(axis[k]), float(split[k]), made.get(int(left[k])), made.get(int(right[k])))
         self._root_obj = made.get(int(f["root"]))
+        if self._root_obj is not None:
+            self._root_obj._owner = weakref.ref(self)      # its queries run on this scene's handle
         return self._root_obj
 
     def _flat_description(self):
@@ -850,6 +951,8 @@ class CompositeScene(_SceneBase):
 
     def _create(self, d):
         self._flat = {k: np.array(d[k]) for k in _FLAT_KEYS}
+        self._objects = d.get("_objects")          # item -> object tables; scenes from flat arrays make them with `root`
+        self._item_ids = None
         n = int(d["dimension"])
         rl = n * n + n + 1
         keep = {}
@@ -924,6 +1027,168 @@ class CompositeScene(_SceneBase):
                        ambient=Color(0, 0, 0), bg1=Color(1, 1, 1), bg2=Color(0, 0, 0), bg3=Color(0, 1, 1))
         self._point_lights = []
         self._global_lights = []
+
+    # ---- ray queries (nt_intersect_rays / nt_occludes_rays, include/ntracer_hip.h) ----
+    def _object_of(self, kind, index):
+        """the Triangle / TriangleBatch / Solid object behind a leaf item"""
+        if self._objects is None:
+            self.root                              # (materialises the tables of a scene made from flat arrays)
+        return self._objects[kind][index]
+
+    def _item_of(self, obj):
+        """the leaf-item code of one of the scene's objects; -1 for anything else (it then matches nothing)"""
+        if self._objects is None:
+            self.root
+        if self._item_ids is None:
+            self._item_ids = {id(p): (i << 2) | kind for kind, tab in enumerate(self._objects) for i, p in enumerate(tab)}
+        return self._item_ids.get(id(obj), -1)
+
+    def _transparent_hits(self, o, d, recs, count):
+        """RayIntersection objects for the first `count` records (dist, item, lane, -) of a ray's transparent list.  The
+        kernels hand out what was hit and where along the ray; the normal ray a test would have written (triangle::intersects,
+        tracer.hpp:431-437; solid::intersects, :251-276 with hypercube_intersects / hypersphere_intersects, :126-173) is
+        worked out here, in fp32 with the reference's operations in the reference's order."""
+        n = self._n
+        o, d = np.asarray(o, f32), np.asarray(d, f32)
+
+        def dot(a, b):                         # summed left to right, every step rounded to fp32
+            acc = f32(a[0] * b[0])
+            for k in range(1, len(a)):
+                acc = f32(acc + f32(a[k] * b[k]))
+            return acc
+
+        out = []
+        for rec in recs[:min(count, len(recs))]:
+            dist = rec[0:1].view(f32)[0]
+            item, lane = int(rec[1]), int(rec[2])
+            kind, index = item & 3, item >> 2
+            prim = self._object_of(kind, index)
+            if kind == _lib.KIND_SOLID:
+                orient, inv, pos = (np.asarray(a, f32) for a in (prim.orientation._m, prim.inv_orientation._m, prim.position._v))
+                lo = np.asarray([f32(dot(inv[i], o) - pos[i]) for i in range(n)], f32)
+                ld = np.asarray([dot(inv[i], d) for i in range(n)], f32)
+                if prim.type == CUBE:
+                    ln_o, ln_d = np.zeros(n, f32), np.zeros(n, f32)
+                    for i in range(n):         # the first axis whose face the local ray passes through
+                        if ld[i] == 0:
+                            continue
+                        s = f32(1.0 if ld[i] < 0 else -1.0)
+                        t = f32(f32(s - lo[i]) / ld[i])
+                        if not t > 0:
+                            continue
+                        p = (ld * t + lo).astype(f32)
+                        if all(j == i or not abs(p[j]) > f32(1.0) + f32(_ROUNDING_FUZZ) for j in range(n)):
+                            ln_o = p.copy()
+                            ln_o[i] = s
+                            ln_d[i] = s
+                            break
+                else:
+                    ln_o = (lo + (ld * dist).astype(f32)).astype(f32)
+                    ln_d = ln_o.copy()
+                tmp = (ln_o + pos).astype(f32)
+                origin = np.asarray([dot(orient[i], tmp) for i in range(n)], f32)
+                normal = np.asarray([dot(orient[i], ln_d) for i in range(n)], f32)
+            else:
+                tri = prim[lane] if kind == _lib.KIND_BATCH else prim
+                fn = np.asarray(tri.face_normal._v, f32)
+                origin = (o + (d * dist).astype(f32)).astype(f32)
+                normal = (fn / f32(np.sqrt(dot(fn, fn)))).astype(f32)
+                if dot(fn, d) > 0:
+                    normal = -normal
+            out.append(RayIntersection(float(dist), Vector._wrap(origin), Vector._wrap(normal), prim, lane))
+        return out
+
+    def _ray_query(self, occlusion, origins, directions, t_near, t_far, distance, skip_item, skip_lane, normals, max_transparent, device):
+        n = self._n
+        max_transparent = int(max_transparent)
+        on_device = type(origins).__module__.split(".")[0] == "torch" and getattr(origins, "is_cuda", False)
+        if on_device:
+            import torch
+            dev = origins.device
+            count = int(origins.shape[0])
+
+            def vec(a, dt, shape):
+                if a is None:
+                    return None
+                if a.device != dev or a.dtype != dt or not a.is_contiguous() or tuple(a.shape) != shape:
+                    raise ValueError("device arrays of a ray query must be contiguous %s tensors of shape %r on %s" % (dt, shape, dev))
+                return a
+
+            def new(shape, dt):                # (zeroed on the stream: the rows a query leaves alone read as zeros)
+                return torch.zeros(shape, dtype=dt, device=dev)
+            ptr = lambda a: None if a is None else a.data_ptr()
+            f4, i4 = torch.float32, torch.int32
+        else:
+            origins = np.ascontiguousarray(origins, f32)
+            count = int(origins.shape[0]) if origins.ndim == 2 else -1
+
+            def vec(a, dt, shape):
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(a, dt)
+                if a.shape != shape:
+                    raise ValueError("expected an array of shape %r, got %r" % (shape, a.shape))
+                return a
+
+            def new(shape, dt):
+                return np.zeros(shape, dt)
+            ptr = lambda a: None if a is None else a.ctypes.data
+            f4, i4 = f32, np.int32
+        if count < 0 or tuple(origins.shape) != (count, n):
+            raise ValueError("origins must have shape (count, %d)" % n)
+        rays = _lib.NtRayBatch()
+        keep = [vec(origins, f4, (count, n)), vec(directions, f4, (count, n)), vec(t_near, f4, (count,)), vec(t_far, f4, (count,)),
+                vec(distance, f4, (count,)), vec(skip_item, i4, (count,)), vec(skip_lane, i4, (count,))]
+        if keep[1] is None:
+            raise ValueError("directions are required")
+        rays.count = count
+        (rays.origins, rays.directions, rays.t_near, rays.t_far, rays.distance, rays.skip_item, rays.skip_lane) = [ptr(a) for a in keep]
+        res = _lib.NtRayResults()
+        hits = new((count, 4), i4)
+        no = new((count, n), f4) if normals and not occlusion else None
+        nd = new((count, n), f4) if normals and not occlusion else None
+        tl = new((count, max_transparent, 4), i4) if max_transparent > 0 else None
+        res.hits, res.normal_origin, res.normal_dir, res.transparent = ptr(hits), ptr(no), ptr(nd), ptr(tl)
+        res.max_transparent = max_transparent
+        L = _lib.lib()
+        if on_device:
+            opts = _lib.NtRenderOpts()
+            opts.device = dev.index if dev.index is not None else -1
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            fn = L.nt_occludes_rays_device if occlusion else L.nt_intersect_rays_device
+            _lib.check(fn(self._handle, C.byref(rays), C.byref(res), C.byref(opts), stream))
+        else:
+            fn = L.nt_occludes_rays if occlusion else L.nt_intersect_rays
+            _lib.check(fn(self._handle, C.byref(rays), C.byref(res), int(device)))
+        dist = hits[:, 0].view(f4)
+        out = {"n_transparent": hits[:, 3]}
+        if occlusion:
+            out["blocked"] = dist != 0
+        else:
+            item = hits[:, 1]
+            miss = (item < 0).to(i4) if on_device else (item < 0).astype(i4)
+            out.update(dist=dist, lane=hits[:, 2], kind=(item & 3) - 4 * miss, index=(item >> 2) * (1 - miss) - miss)
+            if normals:
+                out["normal_origin"], out["normal"] = no, nd
+        if tl is not None:
+            out["transparent"] = tl
+        return out
+
+    def intersect_rays(self, origins, directions, t_near=None, t_far=None, skip_item=None, skip_lane=None, normals=False,
+                       max_transparent=0, device=-1):
+        """KDNode.intersects on the scene's root for `count` rays at once (nt_intersect_rays).  origins / directions
+        [count][n] fp32 (directions as given, not normalised), the optional per-ray arrays [count].  numpy arrays in: a dict
+        of numpy arrays out -- dist (FLT_MAX: none), kind (-1: none), index, lane, n_transparent, with `normals` also
+        normal_origin / normal (rows of rays without an opaque hit stay zero), with max_transparent > 0 also transparent
+        [count][max_transparent][4] int32 records (dist's bits, item, lane, 0).  torch tensors on a HIP device in: the
+        same as torch tensors, enqueued on the current stream without a copy or a synchronisation."""
+        return self._ray_query(False, origins, directions, t_near, t_far, None, skip_item, skip_lane, normals, max_transparent, device)
+
+    def occludes_rays(self, origins, directions, distance=None, t_near=None, t_far=None, skip_item=None, skip_lane=None,
+                      max_transparent=0, device=-1):
+        """KDNode.occludes for `count` rays at once (nt_occludes_rays): `blocked`, n_transparent and, with
+        max_transparent > 0, the transparent hits met on the way."""
+        return self._ray_query(True, origins, directions, t_near, t_far, distance, skip_item, skip_lane, False, max_transparent, device)
 
     # ---- attribute surface of ntracer_body.hpp:833-933 ----
     shadows = property(lambda s: s._p["shadows"])
