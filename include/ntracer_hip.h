@@ -315,6 +315,41 @@ int nt_intersect_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_r
 int nt_occludes_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out,
                             const nt_render_opts *opts, void *hip_stream);
 
+/* ---- primary-hit buffers ----------------------------------------------------------------------------------
+   What is under each pixel of a view: composite_scene::ray_color at depth 0 up to the point where shading starts
+   (src/tracer.hpp:1856-1868).  For pixel (x, y) of a width x height view with the scene's camera and fov: d = the primary
+   ray's unit direction (integer pixel coordinates), t0 = aabb_distance(origin, d); t0 < 0: no hit; otherwise the record of
+   kd_node_intersection on the root with t_near = t0, t_far = FLT_MAX and no source.  The record is nt_ray_hit: a pixel
+   without an opaque hit gets FLT_MAX, -1, -1, n_transparent (0 when the ray misses the scene box); d is a unit vector, so
+   dist is the Euclidean depth.  Every pixel's record is written.  One ray a pixel: the supersampling factor is ignored, as
+   by nt_colors_at.  The walk obeys strict_reference and the NTRACER_* switches exactly as a render of the scene does (opaque
+   scenes up to 10 dimensions take the render's packet walk).  CompositeScene only: a BoxScene handle is NT_E_INVALID.  An
+   empty scene answers "no hit" for every pixel. */
+typedef struct {
+    nt_ray_hit *hits;                       /* [frame][height][width]; a pixel's record index is
+                                               frame * frame_stride_records + y * width + x */
+    float *normal_origin, *normal_dir;      /* NULL or [record index][n]: o_hit.normal; the rows of pixels without an opaque
+                                               hit are left alone */
+} nt_hit_buffers;
+
+/* Host memory out, the scene's current camera, one frame; returns when the records are in place.  Holds the scene like
+   nt_colors_at.  NT_E_INVALID, before any device is touched: NULL scene / out / hits, width or height < 1, a BoxScene,
+   width * height beyond 2^31 - 1 records. */
+int nt_primary_hits(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, int device);
+/* Every pointer of `out` is DEVICE memory on opts->device; the launch is only enqueued on `hip_stream`, with the stream and
+   lifetime rules of nt_render_device.  Of `opts` (may be NULL) device, strict_reference and abort_device are read -- blocks
+   that start after the abort word is raised leave without writing -- and every other field must be 0, else NT_E_INVALID. */
+int nt_primary_hits_device(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, const nt_render_opts *opts,
+                           void *hip_stream);
+/* ... frames [first, first + count) of a camera table in one launch, as nt_render_table_device renders them:
+   frame_stride_records >= width * height records lie between the frames (the records and normal rows in between are not
+   touched).  NT_E_INVALID also for a table of another dimension or device, a bad first / count, a stride smaller than a
+   frame, and count * frame_stride_records beyond 2^31 - 1.  After a warm-up call of the same shape nothing is allocated
+   (the `checked` scratch is shared with renders and queries as described above). */
+int nt_primary_hits_table_device(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, size_t frame_stride_records,
+                                 const nt_camera_table_t *table, int first, int count, const nt_render_opts *opts,
+                                 void *hip_stream);
+
 /* statistics of the last render on this scene that had collect_stats set */
 int nt_scene_last_stats(const nt_scene_t *s, nt_stats *out);
 

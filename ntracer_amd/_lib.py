@@ -95,6 +95,10 @@ class NtRayResults(C.Structure):
                 ("transparent", C.c_void_p), ("max_transparent", C.c_int32)]
 
 
+class NtHitBuffers(C.Structure):             # nt_hit_buffers
+    _fields_ = [("hits", C.c_void_p), ("normal_origin", C.c_void_p), ("normal_dir", C.c_void_p)]
+
+
 class NtKdTreeParams(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("split_threshold", C.c_int32), ("traversal_cost", C.c_float),
                 ("intersection_cost", C.c_float)]
@@ -148,6 +152,10 @@ SYMBOLS = [
                                            C.c_void_p]),
     ("nt_occludes_rays_device", C.c_int, [C.c_void_p, C.POINTER(NtRayBatch), C.POINTER(NtRayResults), C.POINTER(NtRenderOpts),
                                           C.c_void_p]),
+    ("nt_primary_hits", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.c_int]),
+    ("nt_primary_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_primary_hits_table_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                               C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_last_stats", C.c_int, [C.c_void_p, C.POINTER(NtStats)]),
     ("nt_kdtree_build", C.c_int, [C.c_int, C.c_int, f32p, f32p, i32p, f32p, C.POINTER(NtKdTreeParams), C.POINTER(NtKdTree)]),
     ("nt_kdtree_free", None, [C.POINTER(NtKdTree)]),

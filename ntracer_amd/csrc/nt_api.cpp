@@ -633,6 +633,40 @@ int checked_scratch(const nt_scene *s, DeviceState *ds, NtCompositeDev &c, long 
     return NT_OK;
 }
 
+// Dispatch order of the packet walk's quads (2x2 tiles of 8x8 pixels) for an image of `width` x `rows`: the waves that walk the
+// middle of the scene run longest, so the quad rows nearest the centre go first; row-major within a row keeps neighbouring
+// blocks on neighbouring rays.  A table per geometry, kept on the device.
+int tile_order_for(DeviceState *ds, int width, int rows, const int *&dev_ptr) {
+    const int tx = ((width + 7) / 8 + 1) / 2, ty = ((rows + 7) / 8 + 1) / 2;
+    DeviceState::TileOrder *to = nullptr;
+    for (auto &e : ds->tile_orders)
+        if (e->tx == tx && e->ty == ty) to = e.get();
+    if (!to) {
+        std::vector<int> order((size_t)tx * ty);
+        for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+        auto key = [&](int t) {
+            const long long dy = 2 * (t / tx) - (ty - 1);
+            return dy < 0 ? -dy : dy;
+        };
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
+        if (ds->tile_orders.size() >= 16) {
+            // tables may still be read by launches queued on other streams
+            HIP_TRY(hipDeviceSynchronize());
+            for (auto &e : ds->tile_orders) e->buf.release();
+            ds->tile_orders.clear();
+        }
+        std::unique_ptr<DeviceState::TileOrder> e(new DeviceState::TileOrder);
+        if (int err = e->buf.ensure(order.size() * sizeof(int))) return err;
+        HIP_TRY(hipMemcpy(e->buf.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+        e->tx = tx;
+        e->ty = ty;
+        to = e.get();
+        ds->tile_orders.push_back(std::move(e));
+    }
+    dev_ptr = (const int *)to->buf.p;
+    return NT_OK;
+}
+
 // enqueue's CompositeScene half: the device scene, the `checked` and frame scratch of the faithful kernels, and the packet
 // kernel's counter, cameras, numerators, hit scratch and tile order
 int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, const NtTarget &tg,
@@ -704,36 +738,7 @@ int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, cons
         li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
     }
     if (li.persist_cams && !tg.colors_out && sw.tile_order) {
-        // dispatch order of the packet kernel's quads (2x2 tiles of 8x8 pixels): the waves that walk the middle
-        // of the scene run longest, so the quad rows nearest the centre go first; row-major within a row keeps
-        // neighbouring blocks on neighbouring rays
-        const int tx = ((tg.width + 7) / 8 + 1) / 2, ty = ((tg.row_count + 7) / 8 + 1) / 2;
-        DeviceState::TileOrder *to = nullptr;
-        for (auto &e : ds->tile_orders)
-            if (e->tx == tx && e->ty == ty) to = e.get();
-        if (!to) {
-            std::vector<int> order((size_t)tx * ty);
-            for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-            auto key = [&](int t) {
-                const long long dy = 2 * (t / tx) - (ty - 1);
-                return dy < 0 ? -dy : dy;
-            };
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
-            if (ds->tile_orders.size() >= 16) {
-                // tables may still be read by launches queued on other streams
-                HIP_TRY(hipDeviceSynchronize());
-                for (auto &e : ds->tile_orders) e->buf.release();
-                ds->tile_orders.clear();
-            }
-            std::unique_ptr<DeviceState::TileOrder> e(new DeviceState::TileOrder);
-            if (int err = e->buf.ensure(order.size() * sizeof(int))) return err;
-            HIP_TRY(hipMemcpy(e->buf.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
-            e->tx = tx;
-            e->ty = ty;
-            to = e.get();
-            ds->tile_orders.push_back(std::move(e));
-        }
-        li.tile_order = (const int *)to->buf.p;
+        if (int e = tile_order_for(ds, tg.width, tg.row_count, li.tile_order)) return e;
     }
     return NT_OK;
 }
@@ -1169,6 +1174,154 @@ int query_device(nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *ou
     q.max_transparent = out->max_transparent;
     q.abort_word = opts ? (const int *)opts->abort_device : nullptr;
     return query_enqueue(s, ds, q, opts && opts->strict_reference, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// primary-hit buffers: ray_color at depth 0 up to where shading starts, for every pixel (kernels in nt_hits.hpp)
+// ---------------------------------------------------------------------------------------------
+
+// what can be refused without a device
+int hits_validate(const nt_scene *s, int width, int height, const nt_hit_buffers *out, long long frame_stride, long long nframes) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!out || !out->hits) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 records", width, height);
+    if (frame_stride < (long long)width * height) return fail(NT_E_INVALID, "frame_stride_records is smaller than one frame");
+    if (frame_stride > INT_MAX || nframes * frame_stride > INT_MAX)
+        return fail(NT_E_INVALID, "%lld frames of %lld records are beyond 2^31 - 1 records", nframes, frame_stride);
+    return NT_OK;
+}
+
+int hits_check_opts(const nt_render_opts *opts) {
+    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
+        return fail(NT_E_INVALID, "a primary-hit pass reads device, strict_reference and abort_device of its options: every other field must be 0");
+    return NT_OK;
+}
+
+// The launch of one pass: `out` holds device pointers, `cam_buf` the frames' cameras in device memory (nullptr: the scene's
+// current camera, one frame).  The scene goes the way a render of it would go (plan_composite): the walks with the exact
+// `checked` list for transparent materials and the reference's o_hit.normal, the packet walk -- with its numerators and its
+// quad order -- for the opaque scenes the fixed-n kernels draw.
+int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_hit_buffers *out, long long frame_stride, const float *cam_buf,
+                 int nframes, bool strict, const int *abort_word, hipStream_t stream) {
+    const RenderSwitches sw = read_switches();
+    NtCompositeDev c;
+    fill_composite(s, ds, c, false);
+    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
+    if (c.root < 0) c.root = -1;
+    NtTarget tg;
+    std::memset(&tg, 0, sizeof(tg));
+    fill_view(tg, s, width, height);
+    tg.row_count = height;
+    tg.band_world = 1;
+    tg.band_rows = NT_RENDER_CHUNK_SIZE;
+    tg.frame_stride = frame_stride * (long long)sizeof(nt_ray_hit);
+    tg.abort_word = abort_word;
+    NtLaunchInfo li{};
+    li.n = s->n;
+    li.nframes = nframes;
+    li.stream = stream;
+    li.cu_count = ds->cu_count;
+    li.kernel_choice = sw.composite_kernel;
+    li.frame_major = sw.frame_major;
+    li.force_var = sw.force_var;
+    const bool var = s->n > NT_MAX_FIXED_DIM || sw.force_var;
+    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
+    if (faithful) {
+        // (no ray_color frames are kept: the grid of a ray query, see query_enqueue)
+        const long long lpb = var ? 64 : 256, tw = var ? 8 : 16;
+        const long long tiles = ((width + tw - 1) / tw) * ((height + tw - 1) / tw) * nframes;
+        long long blocks = std::min<long long>(tiles, var ? 4096 : 1024);
+        if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, 0, (long long)256 << 20, sw.clean_normals)) return e;
+    }
+    NtHits h{};
+    h.nframes = nframes;
+    h.frame_stride = frame_stride;
+    h.hits = out->hits;
+    h.normal_origin = out->normal_origin;
+    h.normal_dir = out->normal_dir;
+    if (cam_buf) {
+        h.cams = cam_buf;
+    } else {
+        float inl[4 * NT_MAX_DIM];
+        pack_camera(s->n, s->origin.data(), s->axes.data(), inl);
+        if (int e = ds->cams.ensure(sizeof(float) * 4 * s->n)) return e;
+        HIP_TRY(hipMemcpyAsync(ds->cams.p, inl, sizeof(float) * 4 * s->n, hipMemcpyHostToDevice, stream));
+        h.cams = (const float *)ds->cams.p;
+    }
+    if (!faithful && !var && li.kernel_choice == 0 && c.stack_depth <= 32) {
+        // the packet walk's plane numerators (as many frames as fit in 256 MB, at least one) and quad order
+        if (s->n_batches > 0 && sw.numerators) {
+            const size_t per_frame = (size_t)s->n_batches * NT_BATCH_SIZE * sizeof(float);
+            const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)256 << 20) / per_frame));
+            if (int e = ds->numer.ensure(frames * per_frame)) return e;
+            li.numer_buf = (float *)ds->numer.p;
+            li.numer_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+        }
+        if (sw.tile_order) {
+            if (int e = tile_order_for(ds, width, height, li.tile_order)) return e;
+        }
+    }
+    const int r = nt_launch_hits(li, c, tg, h);
+    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    return NT_OK;
+}
+
+int hits_host(nt_scene *s, int width, int height, const nt_hit_buffers *out, int device) {
+    if (int r = hits_validate(s, width, height, out, (long long)width * height, 1)) return r;
+    if (int r = check_renderable(s)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    int dev;
+    if (int r = pick_device(nullptr, device, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = own_stream(ds)) return r;
+    if (int r = use_stream(ds, ds->stream)) return r;
+    // one slab of the probe scratch: records | normal origins | normal directions (16-byte aligned each)
+    const size_t count = (size_t)width * height;
+    const size_t rbytes = count * sizeof(nt_ray_hit), vlen = (count * s->n * sizeof(float) + 15) & ~(size_t)15;
+    if (int r = ds->probes.ensure(rbytes + (out->normal_origin ? vlen : 0) + (out->normal_dir ? vlen : 0))) return r;
+    hipStream_t st = ds->stream;
+    char *at = (char *)ds->probes.p;
+    nt_hit_buffers d{};
+    d.hits = (nt_ray_hit *)at;
+    at += rbytes;
+    // (the kernels do not write the normal rows of pixels without an opaque hit: the caller's rows travel through)
+    if (out->normal_origin) {
+        d.normal_origin = (float *)at;
+        at += vlen;
+        HIP_TRY(hipMemcpyAsync(d.normal_origin, out->normal_origin, count * s->n * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    if (out->normal_dir) {
+        d.normal_dir = (float *)at;
+        HIP_TRY(hipMemcpyAsync(d.normal_dir, out->normal_dir, count * s->n * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    if (int r = hits_enqueue(s, ds, width, height, &d, (long long)count, nullptr, 1, false, nullptr, st)) { (void)hipStreamSynchronize(st); return r; }
+    HIP_TRY(hipMemcpyAsync(out->hits, d.hits, rbytes, hipMemcpyDeviceToHost, st));
+    if (d.normal_origin) HIP_TRY(hipMemcpyAsync(out->normal_origin, d.normal_origin, count * s->n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (d.normal_dir) HIP_TRY(hipMemcpyAsync(out->normal_dir, d.normal_dir, count * s->n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return NT_OK;
+}
+
+// `cams`: the cameras of the `count` frames in memory of device `cams_device`, or nullptr for the scene's current camera
+int hits_device(nt_scene *s, int width, int height, const nt_hit_buffers *out, long long frame_stride, const float *cams, int cams_device,
+                int count, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = check_renderable(s)) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    if (cams && dev != cams_device) return fail(NT_E_INVALID, "the camera table lives on device %d, the pass is for device %d", cams_device, dev);
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    return hits_enqueue(s, ds, width, height, out, frame_stride, cams, count, opts && opts->strict_reference,
+                        opts ? (const int *)opts->abort_device : nullptr, (hipStream_t)hip_stream);
 }
 
 }  // namespace
@@ -1692,6 +1845,27 @@ int nt_intersect_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_r
 
 int nt_occludes_rays_device(nt_scene_t *s, const nt_ray_batch *rays, const nt_ray_results *out, const nt_render_opts *opts, void *hip_stream) {
     return query_device(s, rays, out, opts, hip_stream, true);
+}
+
+int nt_primary_hits(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, int device) {
+    return hits_host(s, width, height, out, device);
+}
+
+int nt_primary_hits_device(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = hits_validate(s, width, height, out, (long long)width * height, 1)) return r;
+    if (int r = hits_check_opts(opts)) return r;
+    return hits_device(s, width, height, out, (long long)width * height, nullptr, -1, 1, opts, hip_stream);
+}
+
+int nt_primary_hits_table_device(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, size_t frame_stride_records,
+                                 const nt_camera_table_t *table, int first, int count, const nt_render_opts *opts, void *hip_stream) {
+    if (!s || !table) return fail(NT_E_INVALID, "NULL argument");
+    if (table->n != s->n) return fail(NT_E_INVALID, "the camera table is for %d dimensions, the scene has %d", table->n, s->n);
+    if (first < 0 || count < 1 || first > table->nframes - count) return fail(NT_E_INVALID, "frames %d..%d are not in a table of %d", first, first + count - 1, table->nframes);
+    if (frame_stride_records > (size_t)INT_MAX) return fail(NT_E_INVALID, "frame_stride_records is beyond 2^31 - 1 records");
+    if (int r = hits_validate(s, width, height, out, (long long)frame_stride_records, count)) return r;
+    if (int r = hits_check_opts(opts)) return r;
+    return hits_device(s, width, height, out, (long long)frame_stride_records, table->dev + (size_t)first * 4 * table->n, table->device, count, opts, hip_stream);
 }
 
 int nt_scene_last_stats(const nt_scene_t *cs, nt_stats *out) {

@@ -1892,7 +1892,10 @@ __device__ __forceinline__ bool wm_claim(int *wm, int lane, int item, bool activ
 #ifndef NT_PACKET_ATTR
 #define NT_PACKET_ATTR
 #endif
-template <int N, int DEPTH, bool FEAT, bool SCAL>
+// HITS (nt_hits.hpp launches these instantiations, never a render): the 16-byte record of every pixel out through pa.hits_out,
+// tg.frame_stride bytes between frames; nothing is shaded and tg.dest is never touched.  A trailing parameter with a default, so
+// that the render instantiations are spelled, and compiled, as before.
+template <int N, int DEPTH, bool FEAT, bool SCAL, bool HITS = false>
 __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVES4 : (N <= 7 ? 5 : 4))) NT_PACKET_ATTR void composite_packet(NtCompositeDev sc, NtTarget tg, PacketArgs pa) {
     extern __shared__ float2 lds_raw[];
     if (nt_aborted(tg)) return;                           // (four independent waves: no barrier in this kernel)
@@ -2155,6 +2158,14 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
         tr[3] = __builtin_amdgcn_ballot_w64(hit.item >= 0);
     }
 #endif
+    if (HITS) {
+        // a pixel whose ray misses the scene box, or hits nothing opaque in it: FLT_MAX, -1, -1; the last dword is the number
+        // of transparent hits, and this walk is for opaque scenes
+        if (valid) *reinterpret_cast<float4 *>(reinterpret_cast<char *>(pa.hits_out) + (long long)frame * tg.frame_stride +
+                                              ((long long)row * tg.width + x) * 16) =
+            make_float4(hit.dist, __int_as_float(hit.item), __int_as_float(hit.lane), 0.0f);
+        return;
+    }
     bool shade_here = valid;
     if (!FEAT && pa.hits_out) {
         // first pass of a lit scene: the shading pass (composite_kernel<N,true,false>) picks the hits up; rays

@@ -222,6 +222,17 @@ struct NtQuery {
     const int *abort_word;    // as NtTarget::abort_word
 };
 
+// One primary-hit pass (nt_hits.hpp, nt_var.hip): the record of every pixel of `nframes` views of tg.width x tg.height, the view
+// and the abort word in the NtTarget that travels with it.  Every pointer is device memory.  A pixel's record index is
+// frame * frame_stride + y * width + x, and its normal rows lie at that index too.
+struct NtHits {
+    const float *cams;        // [nframes][4][n] camera rows: origin, right, up, forward (NtCamera::buf)
+    int nframes;
+    long long frame_stride;   // records between frames, >= width * height
+    void *hits;               // records {float dist; int item, lane, n_transparent} (nt_ray_hit)
+    float *normal_origin, *normal_dir;    // nullptr or [record][n]; rows of pixels without an opaque hit are not written
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
@@ -231,6 +242,9 @@ int nt_launch_resolve(int s, void *stream, const void *samples, long long frame_
 // the query kernels; sc.checked (with checked_lanes = blocks of the launch * lanes a block) selects the walks with transparent
 // hits and the reference's o_hit.normal handling, as for a render
 int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q);
+// the primary-hit kernels; li carries what the packet walk wants (kernel_choice, tile_order, numer_buf, frame_major), sc.checked
+// selects the walks with transparent hits as for nt_launch_query, and tg.frame_stride is h.frame_stride in bytes
+int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

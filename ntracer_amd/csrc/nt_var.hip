@@ -3,13 +3,15 @@
 #include "nt_box.hpp"
 #include "nt_composite.hpp"
 #include "nt_query.hpp"
+#include "nt_hits.hpp"
 #include "nt_resolve.hpp"
 
 // compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
 #define NT_DECLARE_FIXED(N)                                                                              \
     int nt_box_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);               \
     int nt_composite_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg); \
-    int nt_query_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q);
+    int nt_query_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q);                        \
+    int nt_hits_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h);
 NT_DECLARE_FIXED(3) NT_DECLARE_FIXED(4) NT_DECLARE_FIXED(5) NT_DECLARE_FIXED(6)
 NT_DECLARE_FIXED(7) NT_DECLARE_FIXED(8) NT_DECLARE_FIXED(9) NT_DECLARE_FIXED(10)
 // (BoxScene alone: 11..24)
@@ -1703,6 +1705,97 @@ __global__ __launch_bounds__(64) void query_occluded_var_t(NtCompositeDev sc, Nt
     }
 }
 
+// --------------------------------------------------------------------------------------
+// Primary-hit buffers at run-time n: the kernels of nt_hits.hpp on the walks above, one wave a block and an 8x8 tile a wave
+// as composite_kernel_var has it, the blocks striding over [frame][tile row][tile column].
+// --------------------------------------------------------------------------------------
+// the pixel's primary ray (tracer.hpp:60-76) becomes the current ray: composite_kernel_var's operations, in its order
+__device__ __forceinline__ void hits_set_ray_var(const VarCtx &cx, const NtTarget &tg, const NtHits &h, const HitsPixel &p) {
+    const int n = cx.n, lane = cx.lane;
+    const float *c = h.cams + (size_t)p.frame * 4 * n;
+    const float sx = tg.fovI * ((float)p.x - tg.half_w);
+    const float sy = tg.fovI * ((float)p.y - tg.half_h);
+    float sq = 0.0f;
+    for (int k = 0; k < n; ++k) {
+        const float v = (c[3 * n + k] + c[n + k] * sx) - c[2 * n + k] * sy;
+        cx.L.dv[k * 64 + lane] = v;
+        sq = k == 0 ? v * v : sq + v * v;
+    }
+    const float len = sqrtf(sq);
+    for (int k = 0; k < n; ++k) {
+        const float dk = cx.L.dv[k * 64 + lane] / len;
+        cx.L.dv[k * 64 + lane] = dk;
+        cx.L.ray[k * 64 + lane] = make_float2(c[k], dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
+    }
+}
+
+__device__ __forceinline__ void hits_store_normal_var(const NtHits &h, long long r, int n, const float *no, const float *nd) {
+    if (h.normal_origin) for (int k = 0; k < n; ++k) h.normal_origin[r * n + k] = no[k];
+    if (h.normal_dir) for (int k = 0; k < n; ++k) h.normal_dir[r * n + k] = nd[k];
+}
+
+__global__ __launch_bounds__(64) void hits_closest_var(NtCompositeDev sc, NtTarget tg, NtHits h, int n, int tiles_x, int tiles_y) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    const long long total = (long long)tiles_x * tiles_y * h.nframes;
+    for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
+        if (nt_aborted(tg)) return;                       // (one wave a block)
+        const HitsPixel p = hits_pixel<8, 8>(tg, h, tile, tiles_x, tiles_y, lane & 7, lane >> 3);
+        if (!p.valid) continue;
+        hits_set_ray_var(cx, tg, h, p);
+        Hit hit;
+        hit.dist = FLT_MAX; hit.item = -1; hit.lane = -1;
+        const float dist0 = aabb_distance_var(cx);
+        if (dist0 >= 0.0f) trace_closest_var(cx, dist0, -1, -1, hit);
+        query_store(h.hits, p.rec, hit.dist, hit.item, hit.lane, 0);
+        if (hit.item >= 0 && (h.normal_origin || h.normal_dir)) {
+            float no[NT_DEV_MAX_DIM], nd[NT_DEV_MAX_DIM];
+            hit_normal_var(cx, hit, no, nd);
+            hits_store_normal_var(h, p.rec, n, no, nd);
+        }
+    }
+}
+
+template <bool ALIAS>
+__global__ __launch_bounds__(64) void hits_closest_var_t(NtCompositeDev sc, NtTarget tg, NtHits h, int n, int tiles_x, int tiles_y) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    Checked ck;
+    ck.bits = sc.checked + ((long long)blockIdx.x * 64 + lane);
+    ck.stride = sc.checked_lanes;
+    ck.words = sc.checked_words;
+    ck.n_batches = sc.n_batches;
+    ck.n_triangles = sc.n_triangles;
+    const long long total = (long long)tiles_x * tiles_y * h.nframes;
+    for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
+        if (nt_aborted(tg)) return;
+        const HitsPixel p = hits_pixel<8, 8>(tg, h, tile, tiles_x, tiles_y, lane & 7, lane >> 3);
+        if (!p.valid) continue;
+        hits_set_ray_var(cx, tg, h, p);
+        Hit hit;
+        hit.dist = FLT_MAX; hit.item = -1; hit.lane = -1;
+        TList th;
+        th.n = 0;
+        float hn_o[NT_DEV_MAX_DIM], hn_d[NT_DEV_MAX_DIM], nn_o[NT_DEV_MAX_DIM], nn_d[NT_DEV_MAX_DIM];
+        for (int k = 0; k < n; ++k) { hn_o[k] = 0.0f; hn_d[k] = 0.0f; }       // ray_intersection starts out zeroed
+        const float dist0 = aabb_distance_var(cx);
+        if (dist0 >= 0.0f) trace_closest_var_t<ALIAS>(cx, dist0, -1, -1, hit, th, ck, hn_o, hn_d, nn_o, nn_d);
+        query_store(h.hits, p.rec, hit.dist, hit.item, hit.lane, th.n);
+        if (hit.item >= 0 && (h.normal_origin || h.normal_dir)) {
+            if (!ALIAS) hit_normal_var(cx, hit, hn_o, hn_d);
+            hits_store_normal_var(h, p.rec, n, hn_o, hn_d);
+        }
+    }
+}
+
 #undef VO
 #undef VD
 
@@ -1888,4 +1981,55 @@ int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQu
     }
     if (r) return r;
     return finish_launch("query kernel launch");
+}
+
+// Primary-hit buffers (nt_hits.hpp): the fixed-n launcher of the scene's dimension, or the run-time-n kernels above.  Kept apart
+// from nt_launch_composite and nt_launch_query: these are neither render routes nor query routes.
+int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h) {
+    int r;
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_hits_fixed_3(li, sc, tg, h); break;
+        case 4: r = nt_hits_fixed_4(li, sc, tg, h); break;
+        case 5: r = nt_hits_fixed_5(li, sc, tg, h); break;
+        case 6: r = nt_hits_fixed_6(li, sc, tg, h); break;
+        case 7: r = nt_hits_fixed_7(li, sc, tg, h); break;
+        case 8: r = nt_hits_fixed_8(li, sc, tg, h); break;
+        case 9: r = nt_hits_fixed_9(li, sc, tg, h); break;
+        case 10: r = nt_hits_fixed_10(li, sc, tg, h); break;
+        default: {
+            if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
+                return -2;
+            }
+            const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc.stack_depth * 4 + (size_t)NT_MBOX * 4);
+            if (lds > 160 * 1024) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc.stack_depth);
+                return -1;
+            }
+            hipStream_t s = (hipStream_t)li.stream;
+            const int tiles_x = (tg.width + 7) / 8, tiles_y = (tg.height + 7) / 8;
+            const long long tiles = (long long)tiles_x * tiles_y * h.nframes;
+            const void *kernel;
+            if (!sc.checked) kernel = reinterpret_cast<const void *>(hits_closest_var);
+            else kernel = sc.alias_normals ? reinterpret_cast<const void *>(hits_closest_var_t<true>) : reinterpret_cast<const void *>(hits_closest_var_t<false>);
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (sc.checked) {
+                // as many blocks as the `checked` scratch has lane columns for, striding over the tiles
+                long long blocks = sc.checked_lanes / 64;
+                if (blocks > tiles) blocks = tiles;
+                const dim3 tgrid((unsigned)blocks);
+                if (sc.alias_normals) hipLaunchKernelGGL(hits_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+                else hipLaunchKernelGGL(hits_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+            } else if (!sc.all_opaque) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: transparent scene without the checked-list scratch");
+                return -1;
+            } else {
+                const dim3 grid((unsigned)(tiles < (1 << 22) ? tiles : (1 << 22)));
+                hipLaunchKernelGGL(hits_closest_var, grid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+            }
+            r = 0;
+        }
+    }
+    if (r) return r;
+    return finish_launch("primary-hit kernel launch");
 }

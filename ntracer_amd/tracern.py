@@ -8,6 +8,7 @@ Scene construction (Triangle.from_points/to_points, prototypes, build_kdtree, bu
 """
 import ctypes as C
 import math
+import os
 import weakref
 
 import numpy as np
@@ -549,6 +550,66 @@ class RayIntersection(object):
 
     def __repr__(self):
         return "RayIntersection(%r,%r,%r,%r,%r)" % (self._dist, self._origin, self._normal, self._primitive, self._batch_index)
+
+
+class PrimaryHits(object):
+    """What CompositeScene.primary_hits answers with: the primary-hit record of every pixel of a view, as numpy arrays or as
+    torch tensors on the device, views of the buffers the library wrote -- dist, item, kind, index, lane, n_transparent
+    [height][width] (with a camera table [count][height][width]) and, when asked for, normal_origin / normal_dir
+    [...][n].  A pixel without an opaque hit has dist = FLT_MAX and item = kind = index = lane = -1."""
+
+    def __init__(self, scene, width, height, frames, stride, hits, normal_origin, normal_dir):
+        self._scene = scene
+        self.width, self.height, self.frames = width, height, frames
+        self.hits = hits                                  # the raw records: [frames * stride][4] int32 (dist's bits, item, lane, n_transparent)
+
+        def shaped(a):                                    # [frames * stride][k] -> [frames][height][width][k], or [height][width][k]
+            if a is None:
+                return None
+            k = a.shape[-1]
+            a = a.reshape(frames or 1, stride, k)[:, :width * height].reshape(frames or 1, height, width, k)
+            return a if frames is not None else a[0]
+        h = shaped(hits)
+        self.dist = _as_f32(h[..., 0])
+        self.item, self.lane, self.n_transparent = h[..., 1], h[..., 2], h[..., 3]
+        self.normal_origin, self.normal_dir = shaped(normal_origin), shaped(normal_dir)
+
+    @property
+    def kind(self):
+        return (self.item & 3) - 4 * _as_i32(self.item < 0)
+
+    @property
+    def index(self):
+        miss = _as_i32(self.item < 0)
+        return (self.item >> 2) * (1 - miss) - miss
+
+    def intersection(self, x, y, frame=0):
+        """the RayIntersection under pixel (x, y), its `primitive` the scene's own object, or None where the ray hits nothing
+        opaque; needs the normals (primary_hits(..., normals=True))"""
+        at = (int(y), int(x)) if self.frames is None else (int(frame), int(y), int(x))
+        item = int(self.item[at])
+        if item < 0:
+            return None
+        if self.normal_origin is None:
+            raise ValueError("intersection() needs the normal rays: ask for them with primary_hits(..., normals=True)")
+        host = lambda a: np.asarray(a.cpu() if hasattr(a, "cpu") else a, f32).copy()
+        return RayIntersection(float(self.dist[at]), Vector._wrap(host(self.normal_origin[at])), Vector._wrap(host(self.normal_dir[at])),
+                               self._scene._object_of(item & 3, item >> 2), int(self.lane[at]))
+
+
+def _as_f32(a):
+    """the same 32 bits as fp32: numpy or torch"""
+    if hasattr(a, "is_cuda"):
+        import torch
+        return a.view(torch.float32)
+    return a.view(f32)
+
+
+def _as_i32(a):
+    if hasattr(a, "is_cuda"):
+        import torch
+        return a.to(torch.int32)
+    return a.astype(np.int32)
 
 
 class KDNode(object):
@@ -1189,6 +1250,76 @@ class CompositeScene(_SceneBase):
         """KDNode.occludes for `count` rays at once (nt_occludes_rays): `blocked`, n_transparent and, with
         max_transparent > 0, the transparent hits met on the way."""
         return self._ray_query(True, origins, directions, t_near, t_far, distance, skip_item, skip_lane, False, max_transparent, device)
+
+    def primary_hits(self, width, height, normals=False, device=-1, out=None, table=None, first=0, count=None, frame_stride=None,
+                     strict_reference=None):
+        """What is under each pixel of a width x height view (nt_primary_hits): the closest opaque hit of every primary ray,
+        found the way a render finds it and before anything is shaded.  Returns a PrimaryHits: dist (FLT_MAX: none), item
+        (-1: none), kind, index, lane, n_transparent, each [height][width], and with `normals` normal_origin / normal_dir
+        [height][width][n] (rows of pixels without an opaque hit stay as they were: zero in arrays made here).
+
+        `device` an int: numpy arrays through host memory, the scene's current camera.  `device` a torch device (or `out`
+        given): torch tensors that stay on the device, enqueued on torch's current stream without a synchronisation.  `out`:
+        a dict of the caller's own contiguous torch tensors -- "hits" int32 [frames * frame_stride][4], and with `normals`
+        "normal_origin" / "normal_dir" float32 [frames * frame_stride][n].  `table` (a render.CameraTable): frames
+        [first, first + count) of it in one launch, every array [count][height][width]..., `frame_stride` >= width * height
+        records between the frames (torch only: the table lives on a device)."""
+        n = self._n
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the view must be at least 1 x 1")
+        per_frame = width * height
+        torch_device = device if type(device).__module__.split(".")[0] == "torch" or isinstance(device, str) else None
+        on_device = torch_device is not None or out is not None or table is not None
+        L = _lib.lib()
+        res = _lib.NtHitBuffers()
+        if not on_device:
+            hits = np.zeros((per_frame, 4), np.int32)
+            no = np.zeros((per_frame, n), f32) if normals else None
+            nd = np.zeros((per_frame, n), f32) if normals else None
+            ptr = lambda a: None if a is None else a.ctypes.data
+            res.hits, res.normal_origin, res.normal_dir = ptr(hits), ptr(no), ptr(nd)
+            _lib.check(L.nt_primary_hits(self._handle, width, height, C.byref(res), int(device)))
+            return PrimaryHits(self, width, height, None, per_frame, hits, no, nd)
+        import torch
+        frames = 1
+        if table is not None:
+            first = int(first)
+            frames = table.frames - first if count is None else int(count)
+        stride = per_frame if frame_stride is None else int(frame_stride)
+        if stride < per_frame or (table is None and stride != per_frame):
+            raise ValueError("frame_stride must be at least width * height (and is only taken with a camera table)")
+        if out is not None:
+            dev = out["hits"].device
+        elif torch_device is not None:
+            dev = torch.device(torch_device)
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device() if int(device) < 0 else int(device))
+
+        def buf(key, shape, dt):
+            if out is None:
+                return torch.zeros(shape, dtype=dt, device=dev)          # (zeroed on the stream)
+            a = out[key]
+            if a.device != dev or a.dtype != dt or not a.is_contiguous() or tuple(a.shape) != shape:
+                raise ValueError("%r must be a contiguous %s tensor of shape %r on %s" % (key, dt, shape, dev))
+            return a
+        hits = buf("hits", (frames * stride, 4), torch.int32)
+        no = buf("normal_origin", (frames * stride, n), torch.float32) if normals else None
+        nd = buf("normal_dir", (frames * stride, n), torch.float32) if normals else None
+        ptr = lambda a: None if a is None else a.data_ptr()
+        res.hits, res.normal_origin, res.normal_dir = ptr(hits), ptr(no), ptr(nd)
+        opts = _lib.NtRenderOpts()
+        opts.device = dev.index if dev.index is not None else -1
+        if strict_reference is None:
+            strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+        opts.strict_reference = 1 if strict_reference else 0
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if table is None:
+            _lib.check(L.nt_primary_hits_device(self._handle, width, height, C.byref(res), C.byref(opts), stream))
+        else:
+            _lib.check(L.nt_primary_hits_table_device(self._handle, width, height, C.byref(res), stride, table._h, first, frames,
+                                                      C.byref(opts), stream))
+        return PrimaryHits(self, width, height, None if table is None else frames, stride, hits, no, nd)
 
     # ---- attribute surface of ntracer_body.hpp:833-933 ----
     shadows = property(lambda s: s._p["shadows"])
