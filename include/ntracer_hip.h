@@ -350,6 +350,47 @@ int nt_primary_hits_table_device(nt_scene_t *s, int width, int height, const nt_
                                  const nt_camera_table_t *table, int first, int count, const nt_render_opts *opts,
                                  void *hip_stream);
 
+/* ---- colours of the caller's rays -----------------------------------------------------------------------------
+   The shaded result for rays the camera did not make.  For ray r with origin o and direction v: the direction is normalised
+   exactly as the ray source normalises a primary ray (src/tracer.hpp:71-75) -- |v|^2 summed left to right, sqrtf, one IEEE
+   division per component -- and d is that unit direction.  CompositeScene: the colour is ray_color(o, d, depth 0, no source)
+   (src/tracer.hpp:1856-1883), i.e. what composite_scene::calculate_color does after the ray source, scene-box test included.
+   BoxScene: box_scene::calculate_color's colour for that ray (:101-114).  The walk obeys strict_reference,
+   NTRACER_CLEAN_NORMALS and NTRACER_FORCE_VAR exactly as a render of the scene does; the scene's camera, fov and supersampling
+   factor are ignored.  An empty composite scene gives the background.  Every dimension a render supports is supported
+   (compile-time kernels for n = 3..10, BoxScene to 24; run-time n to 64).  The rays of a batch need not be coherent: the
+   packet walk and BoxScene's stretch shortcuts are not used, so a camera's own rays cost more here than a render of them.
+   A ray with a non-finite component or an all-zero direction: the host forms refuse the batch; the device forms cannot look
+   at the rays, and such a ray's colour is unspecified (every loop of the walks is bounded by the tree and the reflection
+   depth whatever the bits are, so the call still ends and the other rays are not affected). */
+typedef struct {
+    int32_t count;
+    const float *origins;        /* [count][n]; or [n], one origin for every ray, when shared_origin != 0 */
+    const float *directions;     /* [count][n], any non-zero finite length */
+    int32_t shared_origin;
+} nt_rays;
+
+/* Host memory in, host memory out: rgb[count][3], the unpacked fp32 colours as nt_colors_at gives them.  Holds the scene like
+   nt_colors_at (NT_E_BUSY while a render runs), stages through the scene's probe scratch on the library's own stream and
+   returns when the result is in place.  NT_E_INVALID, before any device is touched: NULL scene / rays / rgb / origins /
+   directions, count < 0, a ray with a non-finite component or an all-zero direction (the message names the first such
+   ray).  count == 0: NT_OK without a device. */
+int nt_ray_colors(nt_scene_t *s, const nt_rays *rays, float *rgb, int device);
+/* Every pointer is DEVICE memory on opts->device; the launch is only enqueued on `hip_stream`, with the stream and lifetime
+   rules of nt_render_device.  Of `opts` (may be NULL) device, strict_reference and abort_device are read -- blocks that start
+   after the abort word is raised leave without writing -- and every other field must be 0, else NT_E_INVALID.  After a
+   warm-up call of the same count nothing is allocated (the `checked` and frame scratch of scenes with transparent materials
+   or Solids is shared with the scene's renders and queries on that device, as described for the ray queries). */
+int nt_ray_colors_device(nt_scene_t *s, const nt_rays *rays, float *rgb, const nt_render_opts *opts, void *hip_stream);
+/* The same colours as an image in any format: ray y * width + x is pixel (x, y), packed as nt_render packs it (whole image,
+   no bands, one ray a pixel); count must equal fmt->width * fmt->height.  `dest` is HOST memory, staged through the scene's
+   framebuffer scratch; pitch padding keeps the caller's bytes.  NT_E_INVALID as for nt_ray_colors, and for NULL dest, an
+   invalid format (the checks and messages of nt_render), a count that does not match it, dest_len too small. */
+int nt_render_rays(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format *fmt, const nt_rays *rays, int device);
+/* ... dest_dev and the rays in DEVICE memory, enqueued on `hip_stream`; `opts` as for nt_ray_colors_device. */
+int nt_render_rays_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_image_format *fmt, const nt_rays *rays,
+                          const nt_render_opts *opts, void *hip_stream);
+
 /* statistics of the last render on this scene that had collect_stats set */
 int nt_scene_last_stats(const nt_scene_t *s, nt_stats *out);
 

@@ -99,6 +99,10 @@ class NtHitBuffers(C.Structure):             # nt_hit_buffers
     _fields_ = [("hits", C.c_void_p), ("normal_origin", C.c_void_p), ("normal_dir", C.c_void_p)]
 
 
+class NtRays(C.Structure):                   # nt_rays
+    _fields_ = [("count", C.c_int32), ("origins", C.c_void_p), ("directions", C.c_void_p), ("shared_origin", C.c_int32)]
+
+
 class NtKdTreeParams(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("split_threshold", C.c_int32), ("traversal_cost", C.c_float),
                 ("intersection_cost", C.c_float)]
@@ -156,6 +160,11 @@ SYMBOLS = [
     ("nt_primary_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_primary_hits_table_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.c_size_t, C.c_void_p, C.c_int, C.c_int,
                                                C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_ray_colors", C.c_int, [C.c_void_p, C.POINTER(NtRays), C.c_void_p, C.c_int]),
+    ("nt_ray_colors_device", C.c_int, [C.c_void_p, C.POINTER(NtRays), C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_render_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NtImageFormat), C.POINTER(NtRays), C.c_int]),
+    ("nt_render_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NtImageFormat), C.POINTER(NtRays),
+                                        C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_last_stats", C.c_int, [C.c_void_p, C.POINTER(NtStats)]),
     ("nt_kdtree_build", C.c_int, [C.c_int, C.c_int, f32p, f32p, i32p, f32p, C.POINTER(NtKdTreeParams), C.POINTER(NtKdTree)]),
     ("nt_kdtree_free", None, [C.POINTER(NtKdTree)]),

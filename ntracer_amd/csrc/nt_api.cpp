@@ -1324,6 +1324,189 @@ int hits_device(nt_scene *s, int width, int height, const nt_hit_buffers *out, l
                         opts ? (const int *)opts->abort_device : nullptr, (hipStream_t)hip_stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// colours of the caller's rays: ray_color / box_scene::calculate_color for rays from memory (kernels in nt_rays.hpp)
+// ---------------------------------------------------------------------------------------------
+
+// what can be refused without a device; `host`: the rays can be looked at
+int rays_validate(const nt_scene *s, const nt_rays *rays, const void *out, bool host) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!rays || !out || !rays->origins || !rays->directions) return fail(NT_E_INVALID, "NULL argument");
+    if (rays->count < 0) return fail(NT_E_INVALID, "invalid ray count");
+    if (!host) return NT_OK;
+    const size_t n = (size_t)s->n;
+    for (size_t r = 0; r < (size_t)rays->count; ++r) {
+        const float *d = rays->directions + r * n;
+        const float *o = rays->shared_origin ? (r == 0 ? rays->origins : nullptr) : rays->origins + r * n;
+        bool finite = true, zero = true;
+        for (size_t k = 0; k < n; ++k) {
+            finite = finite && std::isfinite(d[k]) && (!o || std::isfinite(o[k]));
+            zero = zero && d[k] == 0.0f;
+        }
+        if (!finite) return fail(NT_E_INVALID, "ray %zu has a non-finite component", r);
+        if (zero) return fail(NT_E_INVALID, "ray %zu has an all-zero direction", r);
+    }
+    return NT_OK;
+}
+
+int rays_check_opts(const nt_render_opts *opts) {
+    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
+        return fail(NT_E_INVALID, "a ray-colour call reads device, strict_reference and abort_device of its options: every other field must be 0");
+    return NT_OK;
+}
+
+// the format and the buffer of the image forms, as nt_render checks them, and the count against the format
+int rays_image_validate(const nt_image_format *fmt, const nt_rays *rays, size_t dest_len, Format &f) {
+    if (int r = parse_format(fmt, f)) return r;
+    if ((long long)rays->count != (long long)f.width * f.height)
+        return fail(NT_E_INVALID, "%d rays do not fill an image of %d x %d pixels", rays->count, f.width, f.height);
+    if (dest_len < required_len(f, Bands())) return fail(NT_E_INVALID, "the buffer is too small for an image with the given dimensions");
+    return NT_OK;
+}
+
+// The launch of one batch: `job` holds device pointers; the colours go to `rgb` ([count][3], device), or with rgb == nullptr
+// into the image `fmt` describes at `dest_dev`.  The scene goes the way a render of it would go (plan_composite), minus the
+// packet walk: the `checked` list and, at run-time n or beyond the fixed kernels' frame stack, the ray_color frames in
+// global scratch for transparent materials and the reference's o_hit.normal, a column per resident lane -- at most 1024
+// blocks of 256 lanes, 4096 of 64 -- the blocks striding over the rays.
+int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, const Format *fmt, void *dest_dev, bool strict,
+                 const int *abort_word, hipStream_t stream) {
+    const RenderSwitches sw = read_switches();
+    NtTarget tg;
+    if (rgb) {
+        std::memset(&tg, 0, sizeof(tg));
+        tg.colors_out = rgb;
+        tg.probe_count = job.count;
+        tg.band_world = 1;
+        tg.band_rows = NT_RENDER_CHUNK_SIZE;
+        tg.abort_word = abort_word;
+    } else {
+        FrameJob fj{};
+        fj.fmt = fmt;
+        fj.dest_dev = dest_dev;
+        fj.frame_stride = 0;
+        fj.nframes = 1;
+        fj.stream = stream;
+        fj.abort_word = abort_word;
+        fj.row_begin = 0;
+        fj.row_count = fmt->height;
+        if (int r = fill_target(s, ds, fj, tg)) return r;
+        if (tg.bpp == 0) return NT_OK;                                 // nothing to draw
+        // consecutive lanes hold consecutive rays, not the aligned groups of one row that emit_pixel's shared dword stores
+        // of 3- and 6-byte pixels count on: those formats go out pixel by pixel
+        if (tg.bpp == 3 || tg.bpp == 6) tg.aligned4 = 0;
+    }
+    NtLaunchInfo li{};
+    li.n = s->n;
+    li.nframes = 1;
+    li.stream = stream;
+    li.cu_count = ds->cu_count;
+    li.force_var = sw.force_var;
+    int r;
+    if (s->composite) {
+        NtCompositeDev c;
+        fill_composite(s, ds, c, false);
+        c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
+        if (c.root < 0) c.root = -1;
+        const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
+        if (faithful) {
+            const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
+            const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
+            const long long lpb = var_t ? 64 : 256;
+            const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
+            long long blocks = std::min<long long>(((long long)job.count + lpb - 1) / lpb, var_t ? 4096 : 1024);
+            if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, fwords, (long long)512 << 20, sw.clean_normals)) return e;
+            if (var_t) {
+                if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
+                c.tframes = (float *)ds->tframes.p;
+                c.tframe_count = nframes_stack;
+            }
+        }
+        r = nt_launch_rays(li, &c, job, tg);
+    } else {
+        r = nt_launch_rays(li, nullptr, job, tg);
+    }
+    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    return NT_OK;
+}
+
+// the host forms: rays (and the image's bytes, for its padding) up, colours or image down, on the library's own stream
+int rays_host(nt_scene *s, const nt_rays *rays, float *rgb, void *dest, size_t dest_len, const nt_image_format *fmt, int device) {
+    if (int r = rays_validate(s, rays, rgb ? (const void *)rgb : (const void *)dest, false)) return r;
+    Format f;
+    if (!rgb) {
+        if (int r = rays_image_validate(fmt, rays, dest_len, f)) return r;
+    }
+    if (int r = rays_validate(s, rays, rgb ? (const void *)rgb : (const void *)dest, true)) return r;
+    if (rays->count == 0) return NT_OK;
+    if (int r = check_renderable(s)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    int dev;
+    if (int r = pick_device(nullptr, device, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = own_stream(ds)) return r;
+    if (int r = use_stream(ds, ds->stream)) return r;
+    // one slab of the probe scratch: directions | origins | colours, each 16-byte aligned
+    const size_t count = (size_t)rays->count, n = (size_t)s->n;
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t dlen = count * n * sizeof(float), olen = (rays->shared_origin ? 1 : count) * n * sizeof(float);
+    const size_t cbytes = rgb ? count * 3 * sizeof(float) : 0;
+    const size_t need = rgb ? 0 : required_len(f, Bands());
+    if (!rgb && need == 0) return NT_OK;                               // a format without channels: nothing to draw
+    if (int r = ds->probes.ensure(al(dlen) + al(olen) + cbytes)) return r;
+    hipStream_t st = ds->stream;
+    char *at = (char *)ds->probes.p;
+    NtRayJob job{};
+    job.count = rays->count;
+    job.shared_origin = rays->shared_origin ? 1 : 0;
+    job.directions = (const float *)at;
+    job.origins = (const float *)(at + al(dlen));
+    float *rgb_dev = rgb ? (float *)(at + al(dlen) + al(olen)) : nullptr;
+    HIP_TRY(hipMemcpyAsync(at, rays->directions, dlen, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(at + al(dlen), rays->origins, olen, hipMemcpyHostToDevice, st));
+    if (!rgb) {
+        if (int r = ds->framebuffer.ensure(std::max<size_t>(need, 16))) return r;
+        // pitch padding bytes are not written by the kernels: carry the caller's bytes through
+        if (f.pitch != f.width * f.bpp) HIP_TRY(hipMemcpyAsync(ds->framebuffer.p, dest, need, hipMemcpyHostToDevice, st));
+    }
+    if (int r = rays_enqueue(s, ds, job, rgb_dev, &f, ds->framebuffer.p, false, nullptr, st)) { (void)hipStreamSynchronize(st); return r; }
+    if (rgb) HIP_TRY(hipMemcpyAsync(rgb, rgb_dev, cbytes, hipMemcpyDeviceToHost, st));
+    else HIP_TRY(hipMemcpyAsync(dest, ds->framebuffer.p, need, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return NT_OK;
+}
+
+// the device forms: every pointer is device memory; enqueue only
+int rays_device(nt_scene *s, const nt_rays *rays, float *rgb, void *dest_dev, size_t dest_len, const nt_image_format *fmt,
+                const nt_render_opts *opts, void *hip_stream) {
+    if (int r = rays_validate(s, rays, rgb ? (const void *)rgb : (const void *)dest_dev, false)) return r;
+    Format f;
+    if (!rgb) {
+        if (int r = rays_image_validate(fmt, rays, dest_len, f)) return r;
+    }
+    if (int r = rays_check_opts(opts)) return r;
+    if (rays->count == 0) return NT_OK;
+    if (int r = check_renderable(s)) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    NtRayJob job{};
+    job.count = rays->count;
+    job.shared_origin = rays->shared_origin ? 1 : 0;
+    job.origins = rays->origins;
+    job.directions = rays->directions;
+    return rays_enqueue(s, ds, job, rgb, &f, dest_dev, opts && opts->strict_reference, opts ? (const int *)opts->abort_device : nullptr,
+                        (hipStream_t)hip_stream);
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1866,6 +2049,27 @@ int nt_primary_hits_table_device(nt_scene_t *s, int width, int height, const nt_
     if (int r = hits_validate(s, width, height, out, (long long)frame_stride_records, count)) return r;
     if (int r = hits_check_opts(opts)) return r;
     return hits_device(s, width, height, out, (long long)frame_stride_records, table->dev + (size_t)first * 4 * table->n, table->device, count, opts, hip_stream);
+}
+
+int nt_ray_colors(nt_scene_t *s, const nt_rays *rays, float *rgb, int device) {
+    if (!rgb) return fail(NT_E_INVALID, "NULL argument");
+    return rays_host(s, rays, rgb, nullptr, 0, nullptr, device);
+}
+
+int nt_ray_colors_device(nt_scene_t *s, const nt_rays *rays, float *rgb, const nt_render_opts *opts, void *hip_stream) {
+    if (!rgb) return fail(NT_E_INVALID, "NULL argument");
+    return rays_device(s, rays, rgb, nullptr, 0, nullptr, opts, hip_stream);
+}
+
+int nt_render_rays(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format *fmt, const nt_rays *rays, int device) {
+    if (!dest) return fail(NT_E_INVALID, "NULL argument");
+    return rays_host(s, rays, nullptr, dest, dest_len, fmt, device);
+}
+
+int nt_render_rays_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_image_format *fmt, const nt_rays *rays,
+                          const nt_render_opts *opts, void *hip_stream) {
+    if (!dest_dev) return fail(NT_E_INVALID, "NULL argument");
+    return rays_device(s, rays, nullptr, dest_dev, dest_len, fmt, opts, hip_stream);
 }
 
 int nt_scene_last_stats(const nt_scene_t *cs, nt_stats *out) {

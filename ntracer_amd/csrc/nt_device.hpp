@@ -233,6 +233,15 @@ struct NtHits {
     float *normal_origin, *normal_dir;    // nullptr or [record][n]; rows of pixels without an opaque hit are not written
 };
 
+// One batch of the caller's rays to colour (nt_rays.hpp, nt_var.hip): `count` rays from device memory.  Where the colours go is
+// in the NtTarget that travels with it: colors_out = rgb [count][3], or an image whose pixel (x, y) is ray y * width + x.
+struct NtRayJob {
+    int count;
+    int shared_origin;        // 1: `origins` is one origin [n] for every ray
+    const float *origins;     // [count][n], or [n]
+    const float *directions;  // [count][n], any non-zero finite length: normalised as primary_dir does it
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
@@ -245,6 +254,9 @@ int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQu
 // the primary-hit kernels; li carries what the packet walk wants (kernel_choice, tile_order, numer_buf, frame_major), sc.checked
 // selects the walks with transparent hits as for nt_launch_query, and tg.frame_stride is h.frame_stride in bytes
 int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h);
+// the colours of the caller's rays; sc == nullptr: BoxScene.  sc->checked / sc->tframes select the walks with transparent hits
+// as for a render, their grid what that scratch has lane columns for; tg.abort_word is honoured when a block or a stride step starts
+int nt_launch_rays(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRayJob &job, const NtTarget &tg);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

@@ -4,6 +4,7 @@
 #include "nt_composite.hpp"
 #include "nt_query.hpp"
 #include "nt_hits.hpp"
+#include "nt_rays.hpp"
 #include "nt_resolve.hpp"
 
 // compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
@@ -14,6 +15,14 @@
     int nt_hits_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h);
 NT_DECLARE_FIXED(3) NT_DECLARE_FIXED(4) NT_DECLARE_FIXED(5) NT_DECLARE_FIXED(6)
 NT_DECLARE_FIXED(7) NT_DECLARE_FIXED(8) NT_DECLARE_FIXED(9) NT_DECLARE_FIXED(10)
+// the ray-colour launchers (nt_inst_rays.hip): CompositeScene 3..10, BoxScene 3..24
+#define NT_DECLARE_RAYS(N) int nt_rays_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtRayJob &job, const NtTarget &tg);
+#define NT_DECLARE_RAYS_BOX(N) int nt_rays_box_fixed_##N(const NtLaunchInfo &li, const NtRayJob &job, const NtTarget &tg);
+NT_DECLARE_RAYS(3) NT_DECLARE_RAYS(4) NT_DECLARE_RAYS(5) NT_DECLARE_RAYS(6) NT_DECLARE_RAYS(7) NT_DECLARE_RAYS(8) NT_DECLARE_RAYS(9) NT_DECLARE_RAYS(10)
+NT_DECLARE_RAYS_BOX(3) NT_DECLARE_RAYS_BOX(4) NT_DECLARE_RAYS_BOX(5) NT_DECLARE_RAYS_BOX(6) NT_DECLARE_RAYS_BOX(7) NT_DECLARE_RAYS_BOX(8)
+NT_DECLARE_RAYS_BOX(9) NT_DECLARE_RAYS_BOX(10) NT_DECLARE_RAYS_BOX(11) NT_DECLARE_RAYS_BOX(12) NT_DECLARE_RAYS_BOX(13) NT_DECLARE_RAYS_BOX(14)
+NT_DECLARE_RAYS_BOX(15) NT_DECLARE_RAYS_BOX(16) NT_DECLARE_RAYS_BOX(17) NT_DECLARE_RAYS_BOX(18) NT_DECLARE_RAYS_BOX(19) NT_DECLARE_RAYS_BOX(20)
+NT_DECLARE_RAYS_BOX(21) NT_DECLARE_RAYS_BOX(22) NT_DECLARE_RAYS_BOX(23) NT_DECLARE_RAYS_BOX(24)
 // (BoxScene alone: 11..24)
 int nt_box_fixed_14(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_box_fixed_15(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
@@ -1796,6 +1805,151 @@ __global__ __launch_bounds__(64) void hits_closest_var_t(NtCompositeDev sc, NtTa
     }
 }
 
+// --------------------------------------------------------------------------------------
+// The colours of the caller's rays at run-time n (n = 11..64 -- BoxScene: 25..64 -- and every n under NTRACER_FORCE_VAR=1): the
+// kernels of nt_rays.hpp on composite_color_var / composite_color_var_t above.  One lane per ray and one wave a block, as the
+// run-time-n render kernels have it, so lane l of block b takes ray 64 b + l, and the blocks stride on.
+// --------------------------------------------------------------------------------------
+// ray r becomes the current ray: the origin as given, the direction normalised as composite_kernel_var normalises its primary ray
+__device__ __forceinline__ void rays_set_ray_var(const VarCtx &cx, const NtRayJob &job, long long r) {
+    const int n = cx.n, lane = cx.lane;
+    const float *pd = job.directions + r * n;
+    const float *po = job.shared_origin ? job.origins : job.origins + r * n;
+    float sq = 0.0f;
+    for (int k = 0; k < n; ++k) {
+        const float v = pd[k];
+        cx.L.dv[k * 64 + lane] = v;
+        sq = k == 0 ? v * v : sq + v * v;
+    }
+    const float len = sqrtf(sq);
+    for (int k = 0; k < n; ++k) {
+        const float dk = cx.L.dv[k * 64 + lane] / len;
+        cx.L.dv[k * 64 + lane] = dk;
+        cx.L.ray[k * 64 + lane] = make_float2(po[k], dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
+    }
+}
+
+__global__ __launch_bounds__(64) void rays_color_var(NtCompositeDev sc, NtRayJob job, NtTarget tg, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    for (long long base = (long long)blockIdx.x * 64; base < job.count; base += (long long)gridDim.x * 64) {
+        if (nt_aborted(tg)) return;                       // (one wave a block)
+        const long long r = base + lane;
+        if (r >= job.count) continue;
+        rays_set_ray_var(cx, job, r);
+        const Color3 col = composite_color_var(cx);
+        emit_pixel(tg, rays_pixel(tg, r), col.r, col.g, col.b);
+    }
+}
+
+// ... with transparent materials or the reference's o_hit.normal handling: the `checked` column and the frame stack of the
+// lane's slot, so the grid is what that scratch has columns for
+template <bool ALIAS>
+__global__ __launch_bounds__(64) void rays_color_var_t(NtCompositeDev sc, NtRayJob job, NtTarget tg, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    const long long slot = (long long)blockIdx.x * 64 + lane;
+    Checked ck;
+    ck.bits = sc.checked + slot;
+    ck.stride = sc.checked_lanes;
+    ck.words = sc.checked_words;
+    ck.n_batches = sc.n_batches;
+    ck.n_triangles = sc.n_triangles;
+    VarFrames fr;
+    fr.base = sc.tframes + slot;
+    fr.stride = sc.checked_lanes;
+    fr.fw = var_frame_words(n);
+    for (long long base = (long long)blockIdx.x * 64; base < job.count; base += (long long)gridDim.x * 64) {
+        if (nt_aborted(tg)) return;
+        const long long r = base + lane;
+        if (r >= job.count) continue;
+        rays_set_ray_var(cx, job, r);
+        const Color3 col = composite_color_var_t<ALIAS>(cx, fr, ck, sc.tframe_count);
+        emit_pixel(tg, rays_pixel(tg, r), col.r, col.g, col.b);
+    }
+}
+
+// BoxScene at run-time n: box_kernel_var's evaluation -- the reference's arithmetic on the faces in a near-tie with the candidate
+// reached last, see box_color -- for every ray, origin and direction as per-lane n-vectors in LDS, [k][lane]
+__global__ __launch_bounds__(64) void rays_box_var(NtRayJob job, NtTarget tg, int n) {
+    extern __shared__ float lds_vec[];    // [n][64] direction, [n][64] origin
+    const int lane = (int)threadIdx.x;
+    float *dir = lds_vec + lane;          // dir[j] at dir[j * 64]
+    float *org = lds_vec + (size_t)n * 64 + lane;
+    for (long long base = (long long)blockIdx.x * 64; base < job.count; base += (long long)gridDim.x * 64) {
+        if (nt_aborted(tg)) return;
+        const long long r = base + lane;
+        if (r >= job.count) continue;
+        const float *pd = job.directions + r * n;
+        const float *po = job.shared_origin ? job.origins : job.origins + r * n;
+        float sq = 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const float v = pd[j];
+            dir[j * 64] = v;
+            org[j * 64] = po[j];
+            sq = j == 0 ? v * v : sq + v * v;
+        }
+        const float len = sqrtf(sq);
+        for (int j = 0; j < n; ++j) dir[j * 64] = dir[j * 64] / len;
+        bool done = false;
+        float shade = 0.0f;
+        float aK = 0.0f, bK = 1.0f, oK = 0.0f;
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            const float di = dir[i * 64];
+            const float oi = org[i * 64];
+            const float num = (di < 0.0f ? 1.0f : -1.0f) - oi;
+            const bool pre = (num > 0.0f && di > 0.0f) || (num < 0.0f && di < 0.0f);
+            const float a = fabsf(num), bb = fabsf(di);
+            if (pre && (!any || a * bK > aK * bb)) { aK = a; bK = bb; oK = oi; any = true; }
+        }
+        const float mu = 1e-4f * (1.0f + fabsf(oK));
+        const float aKm = (aK - mu) * (1.0f - 1e-6f);
+        for (int i = 0; i < n; ++i) {
+            const float di = dir[i * 64];
+            const float oi = org[i * 64];
+            const float s = di < 0.0f ? 1.0f : -1.0f;
+            const float num = s - oi;
+            const bool pre = (num > 0.0f && di > 0.0f) || (num < 0.0f && di < 0.0f);
+            const bool tie = pre && !done && !(fabsf(num) * bK < fabsf(di) * aKm);
+            if (!tie) continue;
+            const float dist = num / di;
+            bool ok = dist > 0.0f;
+            for (int j = 0; j < n; ++j) {
+                if (j != i) {
+                    const float p = dir[j * 64] * dist + org[j * 64];
+                    ok = ok && !(fabsf(p) > (1.0f + NT_FUZZ));
+                }
+            }
+            if (ok) {
+                done = true;
+                if (dist >= FLT_MAX) shade = -1.0f;
+                else {
+                    const float sine = di * s;
+                    shade = sine <= 0.0f ? -sine : 0.0f;
+                }
+            }
+        }
+        float cr, cg, cb;
+        if (done && shade >= 0.0f) {
+            cr = shade * 1.0f;
+            cg = shade * 0.5f;
+            cb = shade * 0.5f;
+        } else {
+            box_background(dir[0], cr, cg, cb);
+        }
+        emit_pixel(tg, rays_pixel(tg, r), cr, cg, cb);
+    }
+}
+
 #undef VO
 #undef VD
 
@@ -2032,4 +2186,99 @@ int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTar
     }
     if (r) return r;
     return finish_launch("primary-hit kernel launch");
+}
+
+// The colours of the caller's rays (nt_rays.hpp): the fixed-n launcher of the scene's dimension, or the run-time-n kernels above.
+// Kept apart from nt_launch_box and nt_launch_composite: these are no render routes.  sc == nullptr: BoxScene.
+int nt_launch_rays(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRayJob &job, const NtTarget &tg) {
+    hipStream_t s = (hipStream_t)li.stream;
+    if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
+        return -2;
+    }
+    long long blocks = ((long long)job.count + 63) / 64;              // of the one-wave kernels
+    int r = 0;
+    if (!sc) {
+        switch (li.force_var ? 0 : li.n) {
+            case 3: r = nt_rays_box_fixed_3(li, job, tg); break;
+            case 4: r = nt_rays_box_fixed_4(li, job, tg); break;
+            case 5: r = nt_rays_box_fixed_5(li, job, tg); break;
+            case 6: r = nt_rays_box_fixed_6(li, job, tg); break;
+            case 7: r = nt_rays_box_fixed_7(li, job, tg); break;
+            case 8: r = nt_rays_box_fixed_8(li, job, tg); break;
+            case 9: r = nt_rays_box_fixed_9(li, job, tg); break;
+            case 10: r = nt_rays_box_fixed_10(li, job, tg); break;
+            case 11: r = nt_rays_box_fixed_11(li, job, tg); break;
+            case 12: r = nt_rays_box_fixed_12(li, job, tg); break;
+            case 13: r = nt_rays_box_fixed_13(li, job, tg); break;
+            case 14: r = nt_rays_box_fixed_14(li, job, tg); break;
+            case 15: r = nt_rays_box_fixed_15(li, job, tg); break;
+            case 16: r = nt_rays_box_fixed_16(li, job, tg); break;
+            case 17: r = nt_rays_box_fixed_17(li, job, tg); break;
+            case 18: r = nt_rays_box_fixed_18(li, job, tg); break;
+            case 19: r = nt_rays_box_fixed_19(li, job, tg); break;
+            case 20: r = nt_rays_box_fixed_20(li, job, tg); break;
+            case 21: r = nt_rays_box_fixed_21(li, job, tg); break;
+            case 22: r = nt_rays_box_fixed_22(li, job, tg); break;
+            case 23: r = nt_rays_box_fixed_23(li, job, tg); break;
+            case 24: r = nt_rays_box_fixed_24(li, job, tg); break;
+            default: {
+                if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+                const size_t lds = (size_t)2 * li.n * 64 * sizeof(float);
+                hipLaunchKernelGGL(rays_box_var, dim3((unsigned)blocks), dim3(64), lds, s, job, tg, li.n);
+            }
+        }
+        if (r) return r;
+        return finish_launch("ray-colour kernel launch");
+    }
+    const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc->stack_depth * 4 + (size_t)NT_MBOX * 4);
+    if (sc->tframes) {
+        // transparent materials / the reference's normal handling at run-time n (or beyond the fixed kernels' frame stack)
+        if (!sc->checked || sc->checked_lanes < 64) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "run-time-n transparency kernel: bad launch (n %d)", li.n);
+            return -2;
+        }
+        if (lds > 160 * 1024) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
+            return -1;
+        }
+        // as many blocks as the scratch has lane columns for, striding over the rays
+        if (blocks > sc->checked_lanes / 64) blocks = sc->checked_lanes / 64;
+        if (sc->alias_normals) {
+            if (lds > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(rays_color_var_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(rays_color_var_t<true>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
+        } else {
+            if (lds > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(rays_color_var_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(rays_color_var_t<false>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
+        }
+        return finish_launch("ray-colour kernel launch");
+    }
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_rays_fixed_3(li, *sc, job, tg); break;
+        case 4: r = nt_rays_fixed_4(li, *sc, job, tg); break;
+        case 5: r = nt_rays_fixed_5(li, *sc, job, tg); break;
+        case 6: r = nt_rays_fixed_6(li, *sc, job, tg); break;
+        case 7: r = nt_rays_fixed_7(li, *sc, job, tg); break;
+        case 8: r = nt_rays_fixed_8(li, *sc, job, tg); break;
+        case 9: r = nt_rays_fixed_9(li, *sc, job, tg); break;
+        case 10: r = nt_rays_fixed_10(li, *sc, job, tg); break;
+        default: {
+            if (!sc->all_opaque || sc->checked) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the run-time-n kernel without frame scratch does not shade transparent materials");
+                return -1;
+            }
+            if (lds > 160 * 1024) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
+                return -1;
+            }
+            if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+            if (lds > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(rays_color_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(rays_color_var, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
+        }
+    }
+    if (r) return r;
+    return finish_launch("ray-colour kernel launch");
 }

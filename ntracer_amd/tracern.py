@@ -778,6 +778,93 @@ class _SceneBase(Scene):
                                            ys.ctypes.data_as(_lib.i32p), out.ctypes.data_as(_lib.f32p), int(device)))
         return out
 
+    def _rays_arg(self, origins, directions):
+        """(nt_rays, count, torch device or None, arrays to keep alive) for ray_colors / render_rays"""
+        n = self._n
+        on_device = type(directions).__module__.split(".")[0] == "torch" and getattr(directions, "is_cuda", False)
+        if on_device:
+            import torch
+            dev = directions.device
+            for a in (origins, directions):
+                if (type(a).__module__.split(".")[0] != "torch" or a.device != dev or a.dtype != torch.float32 or not a.is_contiguous()):
+                    raise ValueError("device arrays of a ray batch must be contiguous %s tensors on %s" % (torch.float32, dev))
+            ptr = lambda a: a.data_ptr()
+        else:
+            dev = None
+            origins = np.ascontiguousarray(origins, f32)
+            directions = np.ascontiguousarray(directions, f32)
+            ptr = lambda a: a.ctypes.data
+        if len(directions.shape) != 2 or int(directions.shape[1]) != n:
+            raise ValueError("directions must have shape (count, %d)" % n)
+        count = int(directions.shape[0])
+        shared = tuple(origins.shape) == (n,)
+        if not shared and tuple(origins.shape) != (count, n):
+            raise ValueError("origins must have shape (count, %d) or (%d,)" % (n, n))
+        rays = _lib.NtRays()
+        rays.count, rays.origins, rays.directions, rays.shared_origin = count, ptr(origins), ptr(directions), 1 if shared else 0
+        return rays, count, dev, (origins, directions)
+
+    @staticmethod
+    def _rays_opts(dev, strict_reference):
+        opts = _lib.NtRenderOpts()
+        opts.device = dev.index if dev.index is not None else -1
+        if strict_reference is None:
+            strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+        opts.strict_reference = 1 if strict_reference else 0
+        return opts
+
+    def ray_colors(self, origins, directions, device=-1, out=None, strict_reference=None):
+        """fp32 colours of the caller's own rays (nt_ray_colors): ray_color at depth 0 -- BoxScene: calculate_color -- for each
+        (origin, direction), the direction normalised as the camera's ray source normalises its own; the scene's camera, fov
+        and supersampling factor play no part.  origins [count][n], or [n] for one origin shared by every ray; directions
+        [count][n], any non-zero finite length.  numpy arrays in: a numpy [count][3] float32 array out, through host memory.
+        Contiguous float32 torch tensors on a HIP device in: a torch tensor on that device (or `out`, the caller's own
+        [count][3]), enqueued on torch's current stream without a copy or a synchronisation."""
+        rays, count, dev, keep = self._rays_arg(origins, directions)
+        L = _lib.lib()
+        if dev is None:
+            if out is None:
+                out = np.zeros((count, 3), f32)
+            elif not (isinstance(out, np.ndarray) and out.dtype == f32 and out.shape == (count, 3) and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError("out must be a writable contiguous float32 array of shape (%d, 3)" % count)
+            _lib.check(L.nt_ray_colors(self._handle, C.byref(rays), out.ctypes.data, int(device)))
+            return out
+        import torch
+        if out is None:
+            out = torch.zeros((count, 3), dtype=torch.float32, device=dev)
+        elif (type(out).__module__.split(".")[0] != "torch" or out.device != dev or out.dtype != torch.float32 or not out.is_contiguous()
+              or tuple(out.shape) != (count, 3)):
+            raise ValueError("out must be a contiguous %s tensor of shape %r on %s" % (torch.float32, (count, 3), dev))
+        if count == 0:
+            return out                          # (an empty tensor has no address to hand over)
+        opts = self._rays_opts(dev, strict_reference)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_ray_colors_device(self._handle, C.byref(rays), out.data_ptr(), C.byref(opts), stream))
+        return out
+
+    def render_rays(self, dest, format, origins, directions, device=-1, strict_reference=None):
+        """The image whose pixel (x, y) is the colour of ray y * width + x (nt_render_rays), packed in `format` as
+        BlockingRenderer.render packs a frame.  `dest`: a writable buffer, with numpy rays -- or a torch uint8 tensor on the
+        device, with device rays, enqueued on torch's current stream."""
+        if not isinstance(format, _render.ImageFormat):
+            raise TypeError("format must be an ImageFormat")
+        rays, count, dev, keep = self._rays_arg(origins, directions)
+        fmt = format._as_struct()
+        L = _lib.lib()
+        target = _render._device_pointer(dest)
+        if (target is None) != (dev is None):
+            raise ValueError("the destination and the rays must both be in host memory or both on the device")
+        if dev is None:
+            arr, nbytes = _render._host_buffer(dest)
+            _lib.check(L.nt_render_rays(self._handle, arr, nbytes, C.byref(fmt), C.byref(rays), int(device)))
+            return True
+        ptr, nbytes, index, stream = target
+        if index != dev.index:
+            raise ValueError("the destination and the rays must be on the same device")
+        opts = self._rays_opts(dev, strict_reference)
+        _lib.check(L.nt_render_rays_device(self._handle, C.c_void_p(ptr), nbytes, C.byref(fmt), C.byref(rays), C.byref(opts), C.c_void_p(stream)))
+        return True
+
     def last_stats(self):
         st = _lib.NtStats()
         _lib.check(_lib.lib().nt_scene_last_stats(self._handle, C.byref(st)))
