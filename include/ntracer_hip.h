@@ -391,6 +391,40 @@ int nt_render_rays(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_fo
 int nt_render_rays_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_image_format *fmt, const nt_rays *rays,
                           const nt_render_opts *opts, void *hip_stream);
 
+/* ---- lenses: fisheye, panoramic and other projections that keep the eye in one point ---------------------------
+   A lens is a table of width x height x 3 fp32 coefficients (sx, sy, sz), row-major [y][x].  Set on a scene it replaces the
+   pinhole ray source of the render entry points: pixel (x, y)'s ray leaves the camera's origin along
+       v[j] = (forward[j] * sz + right[j] * sx) - up[j] * sy,      d = v / |v|
+   with d formed as the pinhole's is (|v|^2 summed left to right, sqrtf, one IEEE division a component, no contraction).  The
+   pinhole itself is sz = 1, sx = fovI * (x - width / 2), sy = fovI * (y - height / 2), fovI = tan(fov / 2) / (width / 2); with
+   sz = 1.0f the direction is the pinhole's bit for bit.  The table does not depend on the camera: it is uploaded to a device
+   on first use there and serves every frame.  An entry whose three coefficients are all zero, or that holds a NaN, is a
+   masked pixel: no ray is cast and the pixel gets colour (0, 0, 0) through the format.  While a lens is set the scene's fov
+   is ignored; strict_reference and the NTRACER_* render switches act as on any render.
+   Honoured by nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device, which return NT_E_INVALID --
+   before any device is touched -- when the lens is not of the format's width x height, and NT_E_UNSUPPORTED, drawing nothing,
+   for what a lens does not do yet: a supersampling factor above 1, row bands (band_world > 1), collect_stats.  With a lens
+   set nt_colors_at / nt_calculate_color and nt_primary_hits* are refused with NT_E_UNSUPPORTED as well (never answered with
+   the pinhole).  nt_ray_colors*, nt_render_rays* and the ray queries take their rays from the caller and ignore the lens.
+   Opaque CompositeScenes up to 10 dimensions keep the packet walk under a lens (two passes: the walk leaves 16-byte hit
+   records, a shading pass picks them up); every other scene is rendered by the ray-colour kernels from directions expanded
+   on the device, in bands of whole rows of at most 1 GiB. */
+typedef struct nt_lens nt_lens_t;
+/* `coeffs`: width * height * 3 floats in host memory, copied.  NULL (NT_E_INVALID) for a size < 1 or NULL coeffs. */
+nt_lens_t *nt_lens_create(int width, int height, const float *coeffs);
+/* the pinhole of a width x height view with the given fov, filled with the very expressions the pinhole ray source uses */
+nt_lens_t *nt_lens_create_pinhole(int width, int height, float fov);
+void nt_lens_destroy(nt_lens_t *lens);
+int nt_lens_width(const nt_lens_t *lens);
+int nt_lens_height(const nt_lens_t *lens);
+/* copies the table (width * height * 3 floats) to `out` */
+int nt_lens_coeffs(const nt_lens_t *lens, float *out);
+/* NULL takes the lens off.  The scene shares ownership of the table: the handle may be destroyed while the scene uses it.
+   NT_E_LOCKED while a render holds the scene, as nt_scene_set_camera. */
+int nt_scene_set_lens(nt_scene_t *s, const nt_lens_t *lens);
+/* a new handle on the scene's lens (to be destroyed by the caller), or NULL when none is set */
+nt_lens_t *nt_scene_get_lens(const nt_scene_t *s);
+
 /* statistics of the last render on this scene that had collect_stats set */
 int nt_scene_last_stats(const nt_scene_t *s, nt_stats *out);
 

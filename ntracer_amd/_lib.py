@@ -165,6 +165,14 @@ SYMBOLS = [
     ("nt_render_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NtImageFormat), C.POINTER(NtRays), C.c_int]),
     ("nt_render_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NtImageFormat), C.POINTER(NtRays),
                                         C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_lens_create", C.c_void_p, [C.c_int, C.c_int, f32p]),
+    ("nt_lens_create_pinhole", C.c_void_p, [C.c_int, C.c_int, C.c_float]),
+    ("nt_lens_destroy", None, [C.c_void_p]),
+    ("nt_lens_width", C.c_int, [C.c_void_p]),
+    ("nt_lens_height", C.c_int, [C.c_void_p]),
+    ("nt_lens_coeffs", C.c_int, [C.c_void_p, f32p]),
+    ("nt_scene_set_lens", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("nt_scene_get_lens", C.c_void_p, [C.c_void_p]),
     ("nt_scene_last_stats", C.c_int, [C.c_void_p, C.POINTER(NtStats)]),
     ("nt_kdtree_build", C.c_int, [C.c_int, C.c_int, f32p, f32p, i32p, f32p, C.POINTER(NtKdTreeParams), C.POINTER(NtKdTree)]),
     ("nt_kdtree_free", None, [C.POINTER(NtKdTree)]),

@@ -110,6 +110,7 @@ struct DeviceState {
     DevBuf checked;                      // reference-faithful normals: the exact `checked` bitmap, one column per resident lane
     DevBuf ties;                         // BoxScene: tie sets of the marked stretches (fused path)
     DevBuf tframes;                      // run-time-n transparency kernel: the ray_color frame stacks, one column per resident lane
+    DevBuf lens_dirs;                    // renders through a lens on the ray route: the directions of a band of rows
     // camera tables travel through pinned host memory (a pageable source makes hipMemcpyAsync wait for the copy on the
     // host, which stalls the launch pipeline of back-to-back calls): a ring of slots, each guarded by an event
     struct Stage { void *host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool in_flight = false; };
@@ -135,6 +136,27 @@ struct Format {                          // validated image_format (render.cpp:1
 
 }  // namespace
 
+// A lens (ntracer_hip.h): the coefficient table, and its copy on every device that has rendered through it.  Shared by the
+// handles (nt_lens) and the scenes it is set on; the last owner frees the device copies.
+struct NtLensData {
+    int width = 0, height = 0;
+    long long masked = 0;                // entries that cast no ray
+    std::vector<float> coeffs;           // [height][width][3]
+    std::mutex mu;
+    std::map<int, void *> dev;           // device -> the table there
+    ~NtLensData() {
+        for (auto &kv : dev) {
+            if (hipSetDevice(kv.first) != hipSuccess) continue;
+            (void)hipDeviceSynchronize();          // launches that read the table may still be queued
+            (void)hipFree(kv.second);
+        }
+    }
+};
+
+struct nt_lens {
+    std::shared_ptr<NtLensData> d;
+};
+
 struct nt_scene {
     bool composite = false;
     int n = 0;
@@ -145,6 +167,7 @@ struct nt_scene {
     int supersampling = 1;               // s x s samples a pixel (nt_scene_set_supersampling; the reference has none)
     int ss_scratch_mb = 1024;            // ... and the cap of their scratch buffer, MiB per device (nt_scene_set_supersampling_scratch_mb)
     std::vector<float> origin, axes;     // camera<Store>: origin[n], t_orientation[n][n] (camera.hpp:7-15)
+    std::shared_ptr<NtLensData> lens;    // not null: the renders' ray source (nt_scene_set_lens); fov is then ignored
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -900,9 +923,136 @@ int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
     return NT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// renders through a lens (nt_scene_set_lens; kernels in nt_lens.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+// What a lens render refuses, checked by the entry points before a device is touched (and by enqueue_lens again, for every
+// way in): the lens is of the image's size, and nothing is asked that the lens routes do not do yet
+int lens_check(const nt_scene *s, int width, int height, const Bands &b, bool stats, bool probes) {
+    if (!s->lens) return NT_OK;
+    if (probes) return fail(NT_E_UNSUPPORTED, "nt_colors_at / nt_calculate_color are not available while a lens is set (nt_ray_colors takes any ray)");
+    if (s->lens->width != width || s->lens->height != height)
+        return fail(NT_E_INVALID, "the lens is for %d x %d pixels, the render is of %d x %d", s->lens->width, s->lens->height, width, height);
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "supersampling %d is not available while a lens is set", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "row bands (band_world %d) are not available while a lens is set", b.world);
+    if (stats) return fail(NT_E_UNSUPPORTED, "collect_stats is not available while a lens is set");
+    return NT_OK;
+}
+
+// the lens's table on the device of `ds`: uploaded on first use there and kept
+int lens_table(NtLensData *ld, DeviceState *ds, const float *&dev_ptr) {
+    std::lock_guard<std::mutex> g(ld->mu);
+    auto it = ld->dev.find(ds->device);
+    if (it == ld->dev.end()) {
+        void *p = nullptr;
+        const size_t bytes = ld->coeffs.size() * sizeof(float);
+        HIP_TRY(hipMalloc(&p, bytes));
+        if (hipMemcpy(p, ld->coeffs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(p);
+            return fail(NT_E_DEVICE, "lens table upload failed");
+        }
+        it = ld->dev.emplace(ds->device, p).first;
+    }
+    dev_ptr = (const float *)it->second;
+    return NT_OK;
+}
+
+int rays_image_target(const nt_scene *s, DeviceState *ds, const Format *fmt, void *dest_dev, const int *abort_word, hipStream_t stream, NtTarget &tg);
+int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, const Format *fmt, void *dest_dev, bool strict,
+                 const int *abort_word, hipStream_t stream);
+
+// the cap of the ray route's direction scratch, a device: the default of the supersampling scratch
+const long long kLensDirsCap = (long long)1024 << 20;
+
+// A render job with a lens set.  Opaque composite scenes that launch_composite_fixed would give the packet walk keep it
+// (nt_launch_lens: the LENS instantiation of the walk into hit records, then lens_shade); every other scene -- transparent
+// materials, the reference's normals for Solids, run-time n, NTRACER_COMPOSITE_KERNEL set, a tree deeper than the packet
+// stack, BoxScene -- is rendered frame by frame by the ray-colour kernels (rays_enqueue) from directions that lens_expand
+// writes for a band of whole rows at a time, and lens_mask_fill paints the masked pixels afterwards.  Enqueue only.
+int enqueue_lens(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw) {
+    NtLensData *ld = s->lens.get();
+    if (int r = lens_check(s, job.colors_out ? job.view_w : job.fmt->width, job.colors_out ? job.view_h : job.fmt->height, job.bands, job.stats,
+                           job.colors_out != nullptr)) return r;
+    const Format &f = *job.fmt;
+    if (job.row_begin != 0 || job.row_count != f.height) return fail(NT_E_UNSUPPORTED, "a row range is not available while a lens is set");
+    if (f.bpp == 0) return NT_OK;                                       // nothing to draw
+    const float *table = nullptr;
+    if (int r = lens_table(ld, ds, table)) return r;
+    const int n = s->n;
+    // the cameras in device memory: the caller's table, or the scene's own camera
+    const float *cams = job.cam_buf;
+    if (!cams) {
+        float packed[4 * NT_DEV_MAX_DIM];
+        pack_camera(n, s->origin.data(), s->axes.data(), packed);
+        if (int e = ds->cams.ensure(sizeof(float) * 4 * n)) return e;
+        HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
+        cams = (const float *)ds->cams.p;
+    }
+    NtLaunchInfo li{};
+    li.n = n;
+    li.nframes = job.nframes;
+    li.stream = job.stream;
+    li.cu_count = ds->cu_count;
+    li.kernel_choice = sw.composite_kernel;
+    li.frame_major = sw.frame_major;
+    li.force_var = sw.force_var;
+    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
+    if (s->composite && !faithful && n <= NT_MAX_FIXED_DIM && !sw.force_var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32) {
+        FrameJob pj = job;
+        pj.cam_buf = cams;
+        NtTarget tg;
+        if (int r = fill_target(s, ds, pj, tg)) return r;
+        NtCamera cam{};
+        cam.buf = cams;
+        cam.n = n;
+        NtCompositeDev c;
+        if (int e = plan_composite(s, ds, pj, sw, tg, cam, li, c)) return e;      // (the counter, numerators, tile order)
+        // the records between the walk and the shading pass: as many frames as fit in 512 MB, at least one (the two-pass
+        // route's own scratch and rule)
+        const size_t per_frame = (size_t)16 * f.width * f.height;
+        const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / per_frame));
+        if (int e = ds->hits.ensure(frames * per_frame)) return e;
+        li.hit_buf = ds->hits.p;
+        li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+        NtLens ln{};
+        ln.table = table;
+        ln.cams = cams;
+        const int r = nt_launch_lens(li, c, tg, ln);
+        if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        return NT_OK;
+    }
+    // the ray route: bands of whole rows whose directions fit the cap
+    const long long row_bytes = (long long)f.width * n * sizeof(float);
+    const int band = (int)std::max<long long>(1, std::min<long long>(f.height, kLensDirsCap / row_bytes));
+    if (int e = ds->lens_dirs.ensure((size_t)band * row_bytes)) return e;
+    for (int fr = 0; fr < job.nframes; ++fr) {
+        const float *cam = cams + (size_t)fr * 4 * n;
+        for (int r0 = 0; r0 < f.height; r0 += band) {
+            const int rows = std::min(band, f.height - r0);
+            const long long first = (long long)r0 * f.width, count = (long long)rows * f.width;
+            void *dest = (char *)job.dest_dev + (size_t)fr * job.frame_stride + (size_t)r0 * f.pitch;
+            if (nt_launch_lens_expand(li, table, cam, first, count, (float *)ds->lens_dirs.p)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            NtRayJob rj{};
+            rj.count = (int)count;
+            rj.shared_origin = 1;
+            rj.origins = cam;                                           // (the camera's first row)
+            rj.directions = (const float *)ds->lens_dirs.p;
+            if (int e = rays_enqueue(s, ds, rj, nullptr, &f, dest, job.strict, job.abort_word, job.stream)) return e;
+            if (ld->masked) {
+                NtTarget tg;
+                if (int e = rays_image_target(s, ds, &f, dest, job.abort_word, job.stream, tg)) return e;
+                if (nt_launch_lens_mask(li, table, first, count, tg)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            }
+        }
+    }
+    return NT_OK;
+}
+
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
+    if (s->lens) return enqueue_lens(s, ds, job, sw);
     if (s->supersampling > 1 && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_supersampled(s, ds, job);
     if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
         // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
@@ -1186,6 +1336,7 @@ int hits_validate(const nt_scene *s, int width, int height, const nt_hit_buffers
     if (!out || !out->hits) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
     if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "primary-hit buffers are not available while a lens is set");
     if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 records", width, height);
     if (frame_stride < (long long)width * height) return fail(NT_E_INVALID, "frame_stride_records is smaller than one frame");
     if (frame_stride > INT_MAX || nframes * frame_stride > INT_MAX)
@@ -1369,6 +1520,24 @@ int rays_image_validate(const nt_image_format *fmt, const nt_rays *rays, size_t 
 // packet walk: the `checked` list and, at run-time n or beyond the fixed kernels' frame stack, the ray_color frames in
 // global scratch for transparent materials and the reference's o_hit.normal, a column per resident lane -- at most 1024
 // blocks of 256 lanes, 4096 of 64 -- the blocks striding over the rays.
+// the image of the image forms as a launch target: ray y * width + x is pixel (x, y) of the whole image at dest_dev
+int rays_image_target(const nt_scene *s, DeviceState *ds, const Format *fmt, void *dest_dev, const int *abort_word, hipStream_t stream, NtTarget &tg) {
+    FrameJob fj{};
+    fj.fmt = fmt;
+    fj.dest_dev = dest_dev;
+    fj.frame_stride = 0;
+    fj.nframes = 1;
+    fj.stream = stream;
+    fj.abort_word = abort_word;
+    fj.row_begin = 0;
+    fj.row_count = fmt->height;
+    if (int r = fill_target(s, ds, fj, tg)) return r;
+    // consecutive lanes hold consecutive rays, not the aligned groups of one row that emit_pixel's shared dword stores
+    // of 3- and 6-byte pixels count on: those formats go out pixel by pixel
+    if (tg.bpp == 3 || tg.bpp == 6) tg.aligned4 = 0;
+    return NT_OK;
+}
+
 int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, const Format *fmt, void *dest_dev, bool strict,
                  const int *abort_word, hipStream_t stream) {
     const RenderSwitches sw = read_switches();
@@ -1381,20 +1550,8 @@ int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, 
         tg.band_rows = NT_RENDER_CHUNK_SIZE;
         tg.abort_word = abort_word;
     } else {
-        FrameJob fj{};
-        fj.fmt = fmt;
-        fj.dest_dev = dest_dev;
-        fj.frame_stride = 0;
-        fj.nframes = 1;
-        fj.stream = stream;
-        fj.abort_word = abort_word;
-        fj.row_begin = 0;
-        fj.row_count = fmt->height;
-        if (int r = fill_target(s, ds, fj, tg)) return r;
+        if (int r = rays_image_target(s, ds, fmt, dest_dev, abort_word, stream, tg)) return r;
         if (tg.bpp == 0) return NT_OK;                                 // nothing to draw
-        // consecutive lanes hold consecutive rays, not the aligned groups of one row that emit_pixel's shared dword stores
-        // of 3- and 6-byte pixels count on: those formats go out pixel by pixel
-        if (tg.bpp == 3 || tg.bpp == 6) tg.aligned4 = 0;
     }
     NtLaunchInfo li{};
     li.n = s->n;
@@ -1599,7 +1756,7 @@ void nt_scene_destroy(nt_scene_t *s) {
         (void)hipDeviceSynchronize();
         for (DevBuf *b : {&ds->nodes, &ds->items, &ds->batch_recs, &ds->batch_mats, &ds->tri_recs, &ds->tri_mats, &ds->solid_recs,
                           &ds->solid_types, &ds->solid_mats, &ds->materials, &ds->aabb, &ds->lights, &ds->framebuffer, &ds->cams, &ds->counter,
-                          &ds->probes, &ds->stats, &ds->hits, &ds->stats_frame, &ds->samples, &ds->numer, &ds->cull, &ds->checked, &ds->tframes, &ds->ties})
+                          &ds->probes, &ds->stats, &ds->hits, &ds->stats_frame, &ds->samples, &ds->numer, &ds->cull, &ds->checked, &ds->tframes, &ds->ties, &ds->lens_dirs})
             b->release();
         for (auto &t : ds->chan_tables) if (t->dev) (void)hipFree(t->dev);
         for (auto &t : ds->row_tables) if (t->dev) (void)hipFree(t->dev);
@@ -1634,6 +1791,88 @@ int nt_scene_get_camera(const nt_scene_t *s, float *origin, float *axes) {
     std::memcpy(origin, s->origin.data(), sizeof(float) * s->n);
     std::memcpy(axes, s->axes.data(), sizeof(float) * s->n * s->n);
     return NT_OK;
+}
+
+namespace {
+nt_lens_t *lens_new(int width, int height) {
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 3) {
+        fail(NT_E_INVALID, "invalid lens size %d x %d", width, height);
+        return nullptr;
+    }
+    nt_lens *l = new (std::nothrow) nt_lens();
+    if (!l) { fail(NT_E_NOMEM, "out of memory"); return nullptr; }
+    l->d = std::make_shared<NtLensData>();
+    l->d->width = width;
+    l->d->height = height;
+    l->d->coeffs.resize((size_t)width * height * 3);
+    return l;
+}
+void lens_count_masked(NtLensData *d) {
+    d->masked = 0;
+    for (size_t i = 0; i < d->coeffs.size(); i += 3) {
+        const float a = d->coeffs[i], b = d->coeffs[i + 1], c = d->coeffs[i + 2];
+        if (!(a == a && b == b && c == c) || (a == 0.0f && b == 0.0f && c == 0.0f)) ++d->masked;
+    }
+}
+}  // namespace
+
+nt_lens_t *nt_lens_create(int width, int height, const float *coeffs) {
+    if (!coeffs) { fail(NT_E_INVALID, "NULL argument"); return nullptr; }
+    nt_lens *l = lens_new(width, height);
+    if (!l) return nullptr;
+    std::memcpy(l->d->coeffs.data(), coeffs, l->d->coeffs.size() * sizeof(float));
+    lens_count_masked(l->d.get());
+    return l;
+}
+
+nt_lens_t *nt_lens_create_pinhole(int width, int height, float fov) {
+    nt_lens *l = lens_new(width, height);
+    if (!l) return nullptr;
+    // fill_view's constants and primary_dir's coefficients, expression for expression
+    const float half_w = float(width) / float(2), half_h = float(height) / float(2);
+    const float fovI = std::tan(fov / 2) / half_w;
+    float *c = l->d->coeffs.data();
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x, c += 3) {
+            c[0] = fovI * ((float)x - half_w);
+            c[1] = fovI * ((float)y - half_h);
+            c[2] = 1.0f;
+        }
+    lens_count_masked(l->d.get());
+    return l;
+}
+
+void nt_lens_destroy(nt_lens_t *lens) { delete lens; }
+int nt_lens_width(const nt_lens_t *lens) { return lens ? lens->d->width : fail(NT_E_INVALID, "lens is NULL"); }
+int nt_lens_height(const nt_lens_t *lens) { return lens ? lens->d->height : fail(NT_E_INVALID, "lens is NULL"); }
+
+int nt_lens_coeffs(const nt_lens_t *lens, float *out) {
+    if (!lens || !out) return fail(NT_E_INVALID, "NULL argument");
+    std::memcpy(out, lens->d->coeffs.data(), lens->d->coeffs.size() * sizeof(float));
+    return NT_OK;
+}
+
+int nt_scene_set_lens(nt_scene_t *s, const nt_lens_t *lens) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    std::shared_ptr<NtLensData> old;               // (released outside the lock: the last owner waits for the device)
+    {
+        std::lock_guard<std::mutex> g(s->mu);
+        if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+        old = std::move(s->lens);
+        s->lens = lens ? lens->d : nullptr;
+    }
+    return NT_OK;
+}
+
+nt_lens_t *nt_scene_get_lens(const nt_scene_t *cs) {
+    nt_scene *s = const_cast<nt_scene *>(cs);
+    if (!s) { fail(NT_E_INVALID, "scene is NULL"); return nullptr; }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (!s->lens) return nullptr;
+    nt_lens *l = new (std::nothrow) nt_lens();
+    if (!l) { fail(NT_E_NOMEM, "out of memory"); return nullptr; }
+    l->d = s->lens;
+    return l;
 }
 
 int nt_scene_set_fov(nt_scene_t *s, float fov) {
@@ -1725,6 +1964,7 @@ int nt_render(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format 
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
+    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (abort_flag && *abort_flag) return NT_ABORTED;           // (before anything touches `dest` or the device)
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
@@ -1805,6 +2045,7 @@ int nt_render_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_im
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
@@ -1841,6 +2082,7 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
@@ -1946,6 +2188,7 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     if (dev != table->device) return fail(NT_E_INVALID, "the camera table lives on device %d, the render is for device %d", table->device, dev);
@@ -1981,6 +2224,7 @@ int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t 
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);   // Scene.calculate_color locks the scene for the call (render.cpp:599-603)
     if (int r = guard.acquire()) return r;
+    if (int r = lens_check(s, width, height, Bands(), false, true)) return r;
     int dev;
     if (int r = pick_device(nullptr, device, dev)) return r;
     DeviceState *ds;

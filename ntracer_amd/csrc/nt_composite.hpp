@@ -1819,6 +1819,7 @@ struct PacketArgs {
     float4 *hits_out;         // not null: write the primary hits ([frame][row][x]) instead of shading
     const float *numer;       // not null: [frame][batch][4] plane numerators -(N.o + d) (packet_numerators)
     int n_batches;
+    const float *lens;        // LENS instantiations only: [height][width][3] coefficients (nt_lens.hpp); nobody else reads or sets it
 };
 
 // The per-lane part of the frame stack is ONE register: bit k of `bothbits` says that the lane entered both
@@ -1895,7 +1896,9 @@ __device__ __forceinline__ bool wm_claim(int *wm, int lane, int item, bool activ
 // HITS (nt_hits.hpp launches these instantiations, never a render): the 16-byte record of every pixel out through pa.hits_out,
 // tg.frame_stride bytes between frames; nothing is shaded and tg.dest is never touched.  A trailing parameter with a default, so
 // that the render instantiations are spelled, and compiled, as before.
-template <int N, int DEPTH, bool FEAT, bool SCAL, bool HITS = false>
+// LENS (nt_lens.hpp launches these instantiations): the lane's direction from its entry of pa.lens (lens_dir) instead of from
+// tg.fovI; the lane of a masked entry is simply never active.  The walk needs the shared origin, not the flat image plane.
+template <int N, int DEPTH, bool FEAT, bool SCAL, bool HITS = false, bool LENS = false>
 __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVES4 : (N <= 7 ? 5 : 4))) NT_PACKET_ATTR void composite_packet(NtCompositeDev sc, NtTarget tg, PacketArgs pa) {
     extern __shared__ float2 lds_raw[];
     if (nt_aborted(tg)) return;                           // (four independent waves: no barrier in this kernel)
@@ -1931,12 +1934,23 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
     const long long out_off = (long long)frame * tg.frame_stride + (long long)(tg.compact ? orow : y) * tg.pitch + (long long)x * tg.bpp;
 
     float o[N], d[N], invd[N];
+    bool lens_live = true;
     {
         const float *c = pa.cams + (size_t)frame * 4 * N;
         float right[N], up[N], fwd[N];
 #pragma unroll
         for (int k = 0; k < N; ++k) { o[k] = c[k]; right[k] = c[N + k]; up[k] = c[2 * N + k]; fwd[k] = c[3 * N + k]; }
-        primary_dir<N>(tg, right, up, fwd, x, y, d);
+        if (LENS) {
+            float sx = 0.0f, sy = 0.0f, sz = 0.0f;                  // (a lane outside the image: masked)
+            if (valid) {
+                const float *e = pa.lens + ((long long)y * tg.width + x) * 3;
+                sx = e[0]; sy = e[1]; sz = e[2];
+            }
+            lens_live = !lens_masked(sx, sy, sz);
+            lens_dir<N>(right, up, fwd, sx, sy, sz, d);
+        } else {
+            primary_dir<N>(tg, right, up, fwd, x, y, d);
+        }
         // invdir = 1/direction (tracer.hpp:1174); NaN marks direction == 0 (see setup_ray_table)
 #pragma unroll
         for (int k = 0; k < N; ++k) invd[k] = d[k] != 0.0f ? 1.0f / d[k] : __int_as_float(0x7fc00000);
@@ -1945,6 +1959,7 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
     hit.dist = FLT_MAX; hit.item = -1; hit.lane = -1;
     const float dist0 = aabb_distance<N>(sc, o, d);
     bool active = valid && dist0 >= 0.0f;
+    if (LENS) active = active && lens_live;
     float t_near = dist0, t_far = FLT_MAX;
     int dirty = 0;
     unsigned int bothbits = 0u;   // bit k: this lane entered BOTH sides of the branch pushed at stack level k

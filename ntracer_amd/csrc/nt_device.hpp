@@ -242,6 +242,14 @@ struct NtRayJob {
     const float *directions;  // [count][n], any non-zero finite length: normalised as primary_dir does it
 };
 
+// A lens (nt_lens.hpp): per-pixel coefficients (sx, sy, sz) of the primary ray in the camera's frame, in place of the pinhole's
+// fovI * (x - half_w), fovI * (y - half_h), 1.  Every pointer is device memory.
+struct NtLens {
+    const float *table;       // [height][width][3], the size of the view
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    const void *hits;         // packet route: the 16-byte records between the walk and the shading pass (the launcher's own)
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
@@ -257,6 +265,14 @@ int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTar
 // the colours of the caller's rays; sc == nullptr: BoxScene.  sc->checked / sc->tframes select the walks with transparent hits
 // as for a render, their grid what that scratch has lane columns for; tg.abort_word is honoured when a block or a stride step starts
 int nt_launch_rays(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRayJob &job, const NtTarget &tg);
+// A render through a lens on the packet walk (opaque scenes, n <= 10, stack depth <= 32): li as for nt_launch_composite, with
+// li.hit_buf holding li.hit_frames frames of tg.width * tg.height records; tg is the whole image (no bands)
+int nt_launch_lens(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln);
+// ... and for every other scene, around nt_launch_rays: the unnormalised directions of pixels [first, first + count) of the
+// view under the camera `cam` ([4][n], device) into out[count][n], zero for a masked pixel; and (0, 0, 0) into the masked ones
+// among those pixels of the image at tg.dest, whose first pixel is pixel `first`
+int nt_launch_lens_expand(const NtLaunchInfo &li, const float *table, const float *cam, long long first, long long count, float *out);
+int nt_launch_lens_mask(const NtLaunchInfo &li, const float *table, long long first, long long count, const NtTarget &tg);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

@@ -366,6 +366,25 @@ __device__ __forceinline__ void primary_dir(const NtTarget &tg, const float (&ri
     for (int j = 0; j < N; ++j) dir[j] = dir[j] / len;
 }
 
+// The same ray through a lens (nt_lens.hpp): the pixel's coefficients (sx, sy, sz) come from a table instead of fovI, and the
+// forward row is scaled as well.  With sz = 1.0f this is primary_dir bit for bit (fwd * 1.0f is fwd).
+template <int N>
+__device__ __forceinline__ void lens_dir(const float (&right)[N], const float (&up)[N], const float (&fwd)[N], float sx, float sy, float sz,
+                                         float (&dir)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) dir[j] = (fwd[j] * sz + right[j] * sx) - up[j] * sy;
+    float sq = dir[0] * dir[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
+    const float len = sqrtf(sq);
+#pragma unroll
+    for (int j = 0; j < N; ++j) dir[j] = dir[j] / len;
+}
+// a masked pixel: all three coefficients zero, or a NaN among them -- no ray, colour (0, 0, 0)
+__device__ __forceinline__ bool lens_masked(float sx, float sy, float sz) {
+    return !(sx == sx && sy == sy && sz == sz) || (sx == 0.0f && sy == 0.0f && sz == 0.0f);
+}
+
 // --------------------------------------------------------------------------------------
 // launch helpers
 // --------------------------------------------------------------------------------------

@@ -23,6 +23,9 @@ NT_DECLARE_RAYS_BOX(3) NT_DECLARE_RAYS_BOX(4) NT_DECLARE_RAYS_BOX(5) NT_DECLARE_
 NT_DECLARE_RAYS_BOX(9) NT_DECLARE_RAYS_BOX(10) NT_DECLARE_RAYS_BOX(11) NT_DECLARE_RAYS_BOX(12) NT_DECLARE_RAYS_BOX(13) NT_DECLARE_RAYS_BOX(14)
 NT_DECLARE_RAYS_BOX(15) NT_DECLARE_RAYS_BOX(16) NT_DECLARE_RAYS_BOX(17) NT_DECLARE_RAYS_BOX(18) NT_DECLARE_RAYS_BOX(19) NT_DECLARE_RAYS_BOX(20)
 NT_DECLARE_RAYS_BOX(21) NT_DECLARE_RAYS_BOX(22) NT_DECLARE_RAYS_BOX(23) NT_DECLARE_RAYS_BOX(24)
+// the packet route of a render through a lens (nt_inst_lens.hip)
+#define NT_DECLARE_LENS(N) int nt_lens_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln);
+NT_DECLARE_LENS(3) NT_DECLARE_LENS(4) NT_DECLARE_LENS(5) NT_DECLARE_LENS(6) NT_DECLARE_LENS(7) NT_DECLARE_LENS(8) NT_DECLARE_LENS(9) NT_DECLARE_LENS(10)
 // (BoxScene alone: 11..24)
 int nt_box_fixed_14(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_box_fixed_15(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
@@ -1950,6 +1953,34 @@ __global__ __launch_bounds__(64) void rays_box_var(NtRayJob job, NtTarget tg, in
     }
 }
 
+// --------------------------------------------------------------------------------------
+// A render through a lens (nt_lens.hpp) on the ray-colour kernels above: every scene the packet walk does not take.  The table
+// and the frame's camera are expanded into the unnormalised directions v[j] = (fwd[j] * sz + right[j] * sx) - up[j] * sy of a
+// band of whole rows -- run-time n, one lane a pixel, the blocks striding -- which the rays_* kernels then take with the camera's
+// origin shared; a masked pixel gets a zero direction there, whose colour is unspecified, and (0, 0, 0) from lens_mask_fill
+// afterwards.  The ray entry points themselves pay nothing for it.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lens_expand(const float *table, const float *cam, int n, long long first, long long count, float *out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const float *e = table + (first + i) * 3;
+        const float sx = e[0], sy = e[1], sz = e[2];
+        float *v = out + i * n;
+        if (lens_masked(sx, sy, sz)) {
+            for (int j = 0; j < n; ++j) v[j] = 0.0f;
+        } else {
+            for (int j = 0; j < n; ++j) v[j] = (cam[3 * n + j] * sz + cam[n + j] * sx) - cam[2 * n + j] * sy;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void lens_mask_fill(const float *table, long long first, long long count, NtTarget tg) {
+    if (nt_aborted(tg)) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const float *e = table + (first + i) * 3;
+        if (lens_masked(e[0], e[1], e[2])) emit_pixel(tg, rays_pixel(tg, i), 0.0f, 0.0f, 0.0f);
+    }
+}
+
 #undef VO
 #undef VD
 
@@ -2281,4 +2312,42 @@ int nt_launch_rays(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRay
     }
     if (r) return r;
     return finish_launch("ray-colour kernel launch");
+}
+
+// A render through a lens.  The packet route (nt_lens.hpp): the fixed-n launcher of the scene's dimension; there is no
+// run-time-n packet walk, and the host sends those scenes through the ray route below.
+int nt_launch_lens(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln) {
+    int r = 0;
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_lens_fixed_3(li, sc, tg, ln); break;
+        case 4: r = nt_lens_fixed_4(li, sc, tg, ln); break;
+        case 5: r = nt_lens_fixed_5(li, sc, tg, ln); break;
+        case 6: r = nt_lens_fixed_6(li, sc, tg, ln); break;
+        case 7: r = nt_lens_fixed_7(li, sc, tg, ln); break;
+        case 8: r = nt_lens_fixed_8(li, sc, tg, ln); break;
+        case 9: r = nt_lens_fixed_9(li, sc, tg, ln); break;
+        case 10: r = nt_lens_fixed_10(li, sc, tg, ln); break;
+        default:
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no packet walk for a lens at run-time n (n %d)", li.n);
+            return -1;
+    }
+    if (r) return r;
+    return finish_launch("lens kernel launch");
+}
+
+// The ray route's two helpers around nt_launch_rays: pixels [first, first + count) of the table
+int nt_launch_lens_expand(const NtLaunchInfo &li, const float *table, const float *cam, long long first, long long count, float *out) {
+    long long blocks = (count + 255) / 256;
+    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    if (blocks < 1) return 0;
+    hipLaunchKernelGGL(lens_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, table, cam, li.n, first, count, out);
+    return finish_launch("lens expansion kernel launch");
+}
+
+int nt_launch_lens_mask(const NtLaunchInfo &li, const float *table, long long first, long long count, const NtTarget &tg) {
+    long long blocks = (count + 255) / 256;
+    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    if (blocks < 1) return 0;
+    hipLaunchKernelGGL(lens_mask_fill, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, table, first, count, tg);
+    return finish_launch("lens mask kernel launch");
 }

@@ -709,6 +709,126 @@ class KDBranch(KDNode):
     dimension = property(lambda s: (s.left if s.left is not None else s.right).dimension)
 
 
+class Lens(object):
+    """Lens(width, height, coeffs) -- a projection that keeps the eye in one point, as a table of [height][width][3] float32
+    coefficients (sx, sy, sz): pixel (x, y)'s ray leaves the camera along (forward * sz + right * sx) - up * sy, normalised
+    as the pinhole's ray is (include/ntracer_hip.h).  An entry that is all zero, or holds a NaN, is a masked pixel: no ray,
+    colour (0, 0, 0).  Set on a scene (Scene.set_lens) it replaces the pinhole of every render; the table does not depend on
+    the camera and is uploaded once a device.  The constructors compute in float64 and round once, with u = x - width / 2 and
+    v = y - height / 2 -- the pinhole's own pixel coordinates."""
+
+    def __init__(self, width, height, coeffs):
+        for v in (width, height):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("the size of a lens must be two integers")
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a lens must be positive")
+        c = np.ascontiguousarray(coeffs, f32)
+        if c.shape != (height, width, 3):
+            raise ValueError("coeffs must have shape (%d, %d, 3)" % (height, width))
+        self._handle = None
+        h = _lib.lib().nt_lens_create(width, height, c.ctypes.data_as(_lib.f32p))
+        if not h:
+            raise ValueError(_lib.last_error())
+        self._handle = h
+
+    @classmethod
+    def _adopt(cls, handle):
+        if not handle:
+            raise ValueError(_lib.last_error())
+        self = cls.__new__(cls)
+        self._handle = handle
+        return self
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                _lib.lib().nt_lens_destroy(h)
+            except Exception:
+                pass
+
+    width = property(lambda s: int(_lib.lib().nt_lens_width(s._handle)))
+    height = property(lambda s: int(_lib.lib().nt_lens_height(s._handle)))
+
+    @property
+    def coeffs(self):
+        """the float32 table, [height][width][3] (a copy)"""
+        out = np.zeros((self.height, self.width, 3), f32)
+        _lib.check(_lib.lib().nt_lens_coeffs(self._handle, out.ctypes.data_as(_lib.f32p)))
+        return out
+
+    @property
+    def masked(self):
+        """[height][width] bool: the pixels that cast no ray"""
+        c = self.coeffs
+        return np.isnan(c).any(axis=2) | (c == 0).all(axis=2)
+
+    @staticmethod
+    def _grid(width, height):
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a lens must be positive")
+        u = np.arange(width, dtype=np.float64)[None, :] - width / 2.0
+        v = np.arange(height, dtype=np.float64)[:, None] - height / 2.0
+        return width, height, np.broadcast_to(u, (height, width)), np.broadcast_to(v, (height, width))
+
+    @classmethod
+    def pinhole(cls, width, height, fov):
+        """the flat pinhole of a scene with this fov, built by the library from the ray source's own expressions: a render
+        through it is the plain render, bit for bit"""
+        return cls._adopt(_lib.lib().nt_lens_create_pinhole(int(width), int(height), float(fov)))
+
+    @classmethod
+    def fisheye(cls, width, height, fov):
+        """equidistant fisheye: the angle from the axis grows linearly with the distance from the centre, fov / 2 at the
+        distance width / 2; fov up to 2 pi; pixels beyond the angle pi are masked"""
+        fov = float(fov)
+        if not (0.0 < fov <= 2.0 * math.pi):
+            raise ValueError("the fov of a fisheye must be in (0, 2 pi]")
+        width, height, u, v = cls._grid(width, height)
+        r = np.hypot(u, v)
+        theta = r * (fov / 2.0) / (width / 2.0)
+        rs = np.where(r == 0.0, 1.0, r)
+        c = np.stack([np.sin(theta) * u / rs, np.sin(theta) * v / rs, np.cos(theta)], axis=2)
+        c[r == 0.0] = (0.0, 0.0, 1.0)
+        c[theta > math.pi] = 0.0
+        return cls(width, height, c.astype(f32))
+
+    @classmethod
+    def equirectangular(cls, width, height, hfov=2.0 * math.pi, vfov=math.pi):
+        """longitude across, latitude down: the full sphere by default"""
+        width, height, u, v = cls._grid(width, height)
+        lam = u * float(hfov) / width
+        phi = v * float(vfov) / height
+        c = np.stack([np.sin(lam) * np.cos(phi), np.sin(phi), np.cos(lam) * np.cos(phi)], axis=2)
+        return cls(width, height, c.astype(f32))
+
+    @classmethod
+    def cylindrical(cls, width, height, hfov):
+        """longitude across, a flat projection down (the scale of the axis' pixel)"""
+        width, height, u, v = cls._grid(width, height)
+        lam = u * float(hfov) / width
+        c = np.stack([np.sin(lam), v * float(hfov) / width, np.cos(lam)], axis=2)
+        return cls(width, height, c.astype(f32))
+
+    def directions(self, camera):
+        """The unnormalised direction of every pixel's ray for `camera`, float32 [height * width][n], computed in float32 in
+        the device's operation order; zero rows for masked pixels.  With them Scene.render_rays / ray_colors /
+        intersect_rays reproduce what a render through the lens casts."""
+        if not isinstance(camera, Camera):
+            raise TypeError("camera must be a Camera")
+        c = self.coeffs.reshape(-1, 3)
+        ax = np.ascontiguousarray(camera._axes, f32)
+        right, up, fwd = ax[0][None, :], ax[1][None, :], ax[2][None, :]
+        sx, sy, sz = c[:, 0:1], c[:, 1:2], c[:, 2:3]
+        with np.errstate(invalid="ignore"):
+            v = (fwd * sz + right * sx) - up * sy
+        v[self.masked.reshape(-1)] = 0
+        return np.ascontiguousarray(v, f32)
+
+
 class _SceneBase(Scene):
     """Camera / fov handling shared by BoxScene and CompositeScene (ntracer_body.hpp:676-715)."""
 
@@ -748,6 +868,17 @@ class _SceneBase(Scene):
         if isinstance(mib, bool) or not isinstance(mib, (int, np.integer)):
             raise ValueError("the supersampling scratch cap must be an integer number of MiB")
         _lib.check(_lib.lib().nt_scene_set_supersampling_scratch_mb(self._handle, int(mib)))
+
+    def set_lens(self, lens):
+        """Render through `lens` (a Lens of the image's size) instead of the pinhole; None takes it off.  fov is ignored
+        while a lens is set.  Supersampling, row bands, statistics, calculate_color / colors_at and primary_hits are refused
+        under a lens; ray_colors, render_rays and the ray queries ignore it.  A view setting like fov: not pickled."""
+        if lens is not None and not isinstance(lens, Lens):
+            raise TypeError("lens must be a Lens or None")
+        _lib.check(_lib.lib().nt_scene_set_lens(self._handle, lens._handle if lens is not None else None))
+        self._lens = lens
+
+    lens = property(lambda s: getattr(s, "_lens", None))
 
     def set_camera(self, camera):
         if not isinstance(camera, Camera) or camera.dimension != self._n:
