@@ -425,6 +425,33 @@ int nt_scene_set_lens(nt_scene_t *s, const nt_lens_t *lens);
 /* a new handle on the scene's lens (to be destroyed by the caller), or NULL when none is set */
 nt_lens_t *nt_scene_get_lens(const nt_scene_t *s);
 
+/* ---- the parallel (orthographic) projection ----------------------------------------------------------------------
+   With half_width > 0 set on a scene, the scene's camera unchanged, pixel (x, y) of a width x height render casts the ray
+       k  = half_width / half_w
+       sx = k * ((float)x - half_w)
+       sy = k * ((float)y - half_h)
+       o'[j] = (origin[j] + right[j] * sx) - up[j] * sy
+       v = forward,      d = v / |v|
+   with half_w = float(width) / 2 and half_h = float(height) / 2, d formed as the pinhole's is (|v|^2 summed left to right,
+   sqrtf, one IEEE division a component, no contraction) and k computed once on the host in fp32, as the pinhole's fovI is.
+   The image spans 2 * half_width scene units horizontally, with square pixels: half_width plays the part tan(fov / 2) plays
+   for the pinhole, and the scene's fov is ignored while the projection is set.  Everything behind the ray source is a
+   render's own: the scene-box test, the walk, shading, packing, strict_reference and the NTRACER_* render switches.
+   Honoured by nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device, which return
+   NT_E_UNSUPPORTED -- before any device is touched, drawing nothing -- for what the projection does not do yet: a
+   supersampling factor above 1, row bands (band_world > 1), collect_stats.  While it is set nt_colors_at /
+   nt_calculate_color and nt_primary_hits* are refused with NT_E_UNSUPPORTED as well (never answered with the pinhole).
+   nt_ray_colors*, nt_render_rays* and the ray queries take their rays from the caller and ignore the setting.
+   Opaque CompositeScenes up to 10 dimensions are rendered by a packet walk for rays that share their direction (two
+   passes: the walk leaves 16-byte hit records, a shading pass picks them up); every other scene by the ray-colour kernels
+   from origins expanded on the device, in bands of whole rows of at most 1 GiB.
+   half_width 0 takes the projection off; negative, NaN or infinite: NT_E_INVALID.  NT_E_LOCKED while a render holds the
+   scene, as nt_scene_set_camera.  A lens and the parallel projection exclude each other: setting either while the other
+   is set is NT_E_INVALID and changes nothing. */
+int nt_scene_set_parallel(nt_scene_t *s, float half_width);
+/* the half_width set, 0 when the projection is off */
+float nt_scene_get_parallel(const nt_scene_t *s);
+
 /* statistics of the last render on this scene that had collect_stats set */
 int nt_scene_last_stats(const nt_scene_t *s, nt_stats *out);
 

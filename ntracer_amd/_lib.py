@@ -173,6 +173,8 @@ SYMBOLS = [
     ("nt_lens_coeffs", C.c_int, [C.c_void_p, f32p]),
     ("nt_scene_set_lens", C.c_int, [C.c_void_p, C.c_void_p]),
     ("nt_scene_get_lens", C.c_void_p, [C.c_void_p]),
+    ("nt_scene_set_parallel", C.c_int, [C.c_void_p, C.c_float]),
+    ("nt_scene_get_parallel", C.c_float, [C.c_void_p]),
     ("nt_scene_last_stats", C.c_int, [C.c_void_p, C.POINTER(NtStats)]),
     ("nt_kdtree_build", C.c_int, [C.c_int, C.c_int, f32p, f32p, i32p, f32p, C.POINTER(NtKdTreeParams), C.POINTER(NtKdTree)]),
     ("nt_kdtree_free", None, [C.POINTER(NtKdTree)]),

@@ -110,7 +110,8 @@ struct DeviceState {
     DevBuf checked;                      // reference-faithful normals: the exact `checked` bitmap, one column per resident lane
     DevBuf ties;                         // BoxScene: tie sets of the marked stretches (fused path)
     DevBuf tframes;                      // run-time-n transparency kernel: the ray_color frame stacks, one column per resident lane
-    DevBuf lens_dirs;                    // renders through a lens on the ray route: the directions of a band of rows
+    DevBuf lens_dirs;                    // renders through a lens on the ray route: the directions of a band of rows; under the
+                                         // parallel projection the band's origins and directions
     // camera tables travel through pinned host memory (a pageable source makes hipMemcpyAsync wait for the copy on the
     // host, which stalls the launch pipeline of back-to-back calls): a ring of slots, each guarded by an event
     struct Stage { void *host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool in_flight = false; };
@@ -168,6 +169,7 @@ struct nt_scene {
     int ss_scratch_mb = 1024;            // ... and the cap of their scratch buffer, MiB per device (nt_scene_set_supersampling_scratch_mb)
     std::vector<float> origin, axes;     // camera<Store>: origin[n], t_orientation[n][n] (camera.hpp:7-15)
     std::shared_ptr<NtLensData> lens;    // not null: the renders' ray source (nt_scene_set_lens); fov is then ignored
+    float parallel = 0.0f;               // > 0: the parallel projection's half_width (nt_scene_set_parallel); excludes a lens
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -1049,10 +1051,104 @@ int enqueue_lens(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
     return NT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// renders under the parallel projection (nt_scene_set_parallel; kernels in nt_parallel.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+// What a parallel render refuses, checked by the entry points before a device is touched (and by enqueue_parallel again, for
+// every way in), as lens_check does it
+int parallel_check(const nt_scene *s, const Bands &b, bool stats, bool probes) {
+    if (!(s->parallel > 0.0f)) return NT_OK;
+    if (probes) return fail(NT_E_UNSUPPORTED, "nt_colors_at / nt_calculate_color are not available while the parallel projection is set (nt_ray_colors takes any ray)");
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "supersampling %d is not available while the parallel projection is set", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "row bands (band_world %d) are not available while the parallel projection is set", b.world);
+    if (stats) return fail(NT_E_UNSUPPORTED, "collect_stats is not available while the parallel projection is set");
+    return NT_OK;
+}
+
+// A render job with the parallel projection set: enqueue_lens's two routes.  Opaque composite scenes that
+// launch_composite_fixed would give the packet walk get the shared-direction walk (nt_launch_parallel: parallel_packet into hit
+// records, then parallel_shade); every other scene is rendered frame by frame by the ray-colour kernels (rays_enqueue, one
+// origin a ray) from what parallel_expand writes for a band of whole rows at a time.  Enqueue only.
+int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw) {
+    if (int r = parallel_check(s, job.bands, job.stats, job.colors_out != nullptr)) return r;
+    const Format &f = *job.fmt;
+    if (job.row_begin != 0 || job.row_count != f.height) return fail(NT_E_UNSUPPORTED, "a row range is not available while the parallel projection is set");
+    if (f.bpp == 0) return NT_OK;                                       // nothing to draw
+    const int n = s->n;
+    // the cameras in device memory: the caller's table, or the scene's own camera
+    const float *cams = job.cam_buf;
+    if (!cams) {
+        float packed[4 * NT_DEV_MAX_DIM];
+        pack_camera(n, s->origin.data(), s->axes.data(), packed);
+        if (int e = ds->cams.ensure(sizeof(float) * 4 * n)) return e;
+        HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
+        cams = (const float *)ds->cams.p;
+    }
+    NtLaunchInfo li{};
+    li.n = n;
+    li.nframes = job.nframes;
+    li.stream = job.stream;
+    li.cu_count = ds->cu_count;
+    li.kernel_choice = sw.composite_kernel;
+    li.frame_major = sw.frame_major;
+    li.force_var = sw.force_var;
+    const float half_w = float(f.width) / float(2), half_h = float(f.height) / float(2);
+    const float k = s->parallel / half_w;                               // (once, in fp32, as fill_view forms fovI)
+    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
+    if (s->composite && !faithful && n <= NT_MAX_FIXED_DIM && !sw.force_var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32) {
+        FrameJob pj = job;
+        pj.cam_buf = cams;
+        NtTarget tg;
+        if (int r = fill_target(s, ds, pj, tg)) return r;
+        tg.fovI = k;
+        NtCamera cam{};
+        cam.buf = cams;
+        cam.n = n;
+        NtCompositeDev c;
+        // (the counter and the tile order; plan_composite also ensures the numerator scratch, which this walk never reads)
+        if (int e = plan_composite(s, ds, pj, sw, tg, cam, li, c)) return e;
+        // the records between the walk and the shading pass: as many frames as fit in 512 MB, at least one (the two-pass
+        // route's own scratch and rule)
+        const size_t per_frame = (size_t)16 * f.width * f.height;
+        const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / per_frame));
+        if (int e = ds->hits.ensure(frames * per_frame)) return e;
+        li.hit_buf = ds->hits.p;
+        li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+        NtParallel pl{};
+        pl.cams = cams;
+        const int r = nt_launch_parallel(li, c, tg, pl);
+        if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        return NT_OK;
+    }
+    // the ray route: bands of whole rows whose origins and directions fit the cap
+    const long long row_bytes = (long long)f.width * n * sizeof(float) * 2;
+    const int band = (int)std::max<long long>(1, std::min<long long>(f.height, kLensDirsCap / row_bytes));
+    if (int e = ds->lens_dirs.ensure((size_t)band * row_bytes)) return e;
+    for (int fr = 0; fr < job.nframes; ++fr) {
+        const float *cam = cams + (size_t)fr * 4 * n;
+        for (int r0 = 0; r0 < f.height; r0 += band) {
+            const int rows = std::min(band, f.height - r0);
+            const long long first = (long long)r0 * f.width, count = (long long)rows * f.width;
+            void *dest = (char *)job.dest_dev + (size_t)fr * job.frame_stride + (size_t)r0 * f.pitch;
+            float *scratch = (float *)ds->lens_dirs.p;
+            if (nt_launch_parallel_expand(li, cam, f.width, k, half_w, half_h, first, count, scratch)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            NtRayJob rj{};
+            rj.count = (int)count;
+            rj.shared_origin = 0;
+            rj.origins = scratch;
+            rj.directions = scratch + (size_t)count * n;
+            if (int e = rays_enqueue(s, ds, rj, nullptr, &f, dest, job.strict, job.abort_word, job.stream)) return e;
+        }
+    }
+    return NT_OK;
+}
+
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
     if (s->lens) return enqueue_lens(s, ds, job, sw);
+    if (s->parallel > 0.0f) return enqueue_parallel(s, ds, job, sw);
     if (s->supersampling > 1 && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_supersampled(s, ds, job);
     if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
         // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
@@ -1337,6 +1433,7 @@ int hits_validate(const nt_scene *s, int width, int height, const nt_hit_buffers
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
     if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
     if (s->lens) return fail(NT_E_UNSUPPORTED, "primary-hit buffers are not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "primary-hit buffers are not available while the parallel projection is set");
     if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 records", width, height);
     if (frame_stride < (long long)width * height) return fail(NT_E_INVALID, "frame_stride_records is smaller than one frame");
     if (frame_stride > INT_MAX || nframes * frame_stride > INT_MAX)
@@ -1858,6 +1955,7 @@ int nt_scene_set_lens(nt_scene_t *s, const nt_lens_t *lens) {
     {
         std::lock_guard<std::mutex> g(s->mu);
         if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+        if (lens && s->parallel > 0.0f) return fail(NT_E_INVALID, "a lens and the parallel projection exclude each other: take the parallel projection off first");
         old = std::move(s->lens);
         s->lens = lens ? lens->d : nullptr;
     }
@@ -1873,6 +1971,23 @@ nt_lens_t *nt_scene_get_lens(const nt_scene_t *cs) {
     if (!l) { fail(NT_E_NOMEM, "out of memory"); return nullptr; }
     l->d = s->lens;
     return l;
+}
+
+int nt_scene_set_parallel(nt_scene_t *s, float half_width) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!(half_width >= 0.0f) || std::isinf(half_width)) return fail(NT_E_INVALID, "half_width must be a finite number >= 0");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    if (half_width > 0.0f && s->lens) return fail(NT_E_INVALID, "the parallel projection and a lens exclude each other: take the lens off first");
+    s->parallel = half_width > 0.0f ? half_width : 0.0f;
+    return NT_OK;
+}
+
+float nt_scene_get_parallel(const nt_scene_t *cs) {
+    nt_scene *s = const_cast<nt_scene *>(cs);
+    if (!s) { fail(NT_E_INVALID, "scene is NULL"); return 0.0f; }
+    std::lock_guard<std::mutex> g(s->mu);
+    return s->parallel;
 }
 
 int nt_scene_set_fov(nt_scene_t *s, float fov) {
@@ -1965,6 +2080,7 @@ int nt_render(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format 
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
+    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     if (abort_flag && *abort_flag) return NT_ABORTED;           // (before anything touches `dest` or the device)
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
@@ -2046,6 +2162,7 @@ int nt_render_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_im
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
+    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
@@ -2083,6 +2200,7 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
+    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
@@ -2189,6 +2307,7 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
+    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     if (dev != table->device) return fail(NT_E_INVALID, "the camera table lives on device %d, the render is for device %d", table->device, dev);
@@ -2225,6 +2344,7 @@ int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t 
     RenderGuard guard(s);   // Scene.calculate_color locks the scene for the call (render.cpp:599-603)
     if (int r = guard.acquire()) return r;
     if (int r = lens_check(s, width, height, Bands(), false, true)) return r;
+    if (int r = parallel_check(s, Bands(), false, true)) return r;
     int dev;
     if (int r = pick_device(nullptr, device, dev)) return r;
     DeviceState *ds;

@@ -250,6 +250,12 @@ struct NtLens {
     const void *hits;         // packet route: the 16-byte records between the walk and the shading pass (the launcher's own)
 };
 
+// The parallel projection (nt_parallel.hpp): its scale k = half_width / half_w travels in NtTarget::fovI.  Device memory.
+struct NtParallel {
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    const void *hits;         // packet route: the 16-byte records between the walk and the shading pass (the launcher's own)
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
@@ -273,6 +279,14 @@ int nt_launch_lens(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTar
 // among those pixels of the image at tg.dest, whose first pixel is pixel `first`
 int nt_launch_lens_expand(const NtLaunchInfo &li, const float *table, const float *cam, long long first, long long count, float *out);
 int nt_launch_lens_mask(const NtLaunchInfo &li, const float *table, long long first, long long count, const NtTarget &tg);
+// A render under the parallel projection on the packet walk (opaque scenes, n <= 10, stack depth <= 32): as nt_launch_lens,
+// with tg.fovI = half_width / half_w
+int nt_launch_parallel(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl);
+// ... and for every other scene, in front of nt_launch_rays: the origins o' of pixels [first, first + count) of a view `width`
+// pixels wide under the camera `cam` ([4][n], device) into out[count][n], and the unnormalised forward row into the `count`
+// rows behind them; k, half_w and half_h as NtTarget has them
+int nt_launch_parallel_expand(const NtLaunchInfo &li, const float *cam, int width, float k, float half_w, float half_h, long long first,
+                              long long count, float *out);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

@@ -385,6 +385,27 @@ __device__ __forceinline__ bool lens_masked(float sx, float sy, float sz) {
     return !(sx == sx && sy == sy && sz == sz) || (sx == 0.0f && sy == 0.0f && sz == 0.0f);
 }
 
+// The parallel projection (nt_parallel.hpp): pixel (x, y)'s ray starts at o' = (origin + right * sx) - up * sy with
+// sx = k * (x - half_w), sy = k * (y - half_h), k = half_width / half_w from the host in tg.fovI's place; every ray runs along
+// the forward row, normalised as primary_dir normalises (parallel_dir)
+template <int N>
+__device__ __forceinline__ void parallel_origin(const NtTarget &tg, const float (&org)[N], const float (&right)[N], const float (&up)[N],
+                                                int x, int y, float (&o)[N]) {
+    const float sx = tg.fovI * ((float)x - tg.half_w);
+    const float sy = tg.fovI * ((float)y - tg.half_h);
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[j] = (org[j] + right[j] * sx) - up[j] * sy;
+}
+template <int N>
+__device__ __forceinline__ void parallel_dir(const float (&fwd)[N], float (&dir)[N]) {
+    float sq = fwd[0] * fwd[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) sq = sq + fwd[j] * fwd[j];
+    const float len = sqrtf(sq);
+#pragma unroll
+    for (int j = 0; j < N; ++j) dir[j] = fwd[j] / len;
+}
+
 // --------------------------------------------------------------------------------------
 // launch helpers
 // --------------------------------------------------------------------------------------

@@ -26,6 +26,9 @@ NT_DECLARE_RAYS_BOX(21) NT_DECLARE_RAYS_BOX(22) NT_DECLARE_RAYS_BOX(23) NT_DECLA
 // the packet route of a render through a lens (nt_inst_lens.hip)
 #define NT_DECLARE_LENS(N) int nt_lens_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln);
 NT_DECLARE_LENS(3) NT_DECLARE_LENS(4) NT_DECLARE_LENS(5) NT_DECLARE_LENS(6) NT_DECLARE_LENS(7) NT_DECLARE_LENS(8) NT_DECLARE_LENS(9) NT_DECLARE_LENS(10)
+// the packet route of a render under the parallel projection (nt_inst_parallel.hip)
+#define NT_DECLARE_PARALLEL(N) int nt_parallel_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl);
+NT_DECLARE_PARALLEL(3) NT_DECLARE_PARALLEL(4) NT_DECLARE_PARALLEL(5) NT_DECLARE_PARALLEL(6) NT_DECLARE_PARALLEL(7) NT_DECLARE_PARALLEL(8) NT_DECLARE_PARALLEL(9) NT_DECLARE_PARALLEL(10)
 // (BoxScene alone: 11..24)
 int nt_box_fixed_14(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_box_fixed_15(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
@@ -1981,6 +1984,27 @@ __global__ __launch_bounds__(256) void lens_mask_fill(const float *table, long l
     }
 }
 
+// --------------------------------------------------------------------------------------
+// A render under the parallel projection (nt_parallel.hpp) on the ray-colour kernels above: every scene the packet walk does
+// not take.  Pixels [first, first + count) of a view `width` wide -- a band of whole rows -- get their origin
+// o'[j] = (origin[j] + right[j] * sx) - up[j] * sy into out[i][n] and the unnormalised forward row into out[count + i][n]:
+// run-time n, one lane a pixel, the blocks striding.  The rays_* kernels then take one origin a ray.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void parallel_expand(const float *cam, int n, int width, float k, float half_w, float half_h, long long first,
+                                                       long long count, float *out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const long long p = first + i;
+        const int y = (int)(p / width), x = (int)(p - (long long)y * width);
+        const float sx = k * ((float)x - half_w);
+        const float sy = k * ((float)y - half_h);
+        float *o = out + i * n, *v = out + (count + i) * n;
+        for (int j = 0; j < n; ++j) {
+            o[j] = (cam[j] + cam[n + j] * sx) - cam[2 * n + j] * sy;
+            v[j] = cam[3 * n + j];
+        }
+    }
+}
+
 #undef VO
 #undef VD
 
@@ -2350,4 +2374,35 @@ int nt_launch_lens_mask(const NtLaunchInfo &li, const float *table, long long fi
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(lens_mask_fill, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, table, first, count, tg);
     return finish_launch("lens mask kernel launch");
+}
+
+// A render under the parallel projection.  The packet route (nt_parallel.hpp): the fixed-n launcher of the scene's dimension;
+// there is no run-time-n packet walk, and the host sends those scenes through the ray route below.
+int nt_launch_parallel(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl) {
+    int r = 0;
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_parallel_fixed_3(li, sc, tg, pl); break;
+        case 4: r = nt_parallel_fixed_4(li, sc, tg, pl); break;
+        case 5: r = nt_parallel_fixed_5(li, sc, tg, pl); break;
+        case 6: r = nt_parallel_fixed_6(li, sc, tg, pl); break;
+        case 7: r = nt_parallel_fixed_7(li, sc, tg, pl); break;
+        case 8: r = nt_parallel_fixed_8(li, sc, tg, pl); break;
+        case 9: r = nt_parallel_fixed_9(li, sc, tg, pl); break;
+        case 10: r = nt_parallel_fixed_10(li, sc, tg, pl); break;
+        default:
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no packet walk for the parallel projection at run-time n (n %d)", li.n);
+            return -1;
+    }
+    if (r) return r;
+    return finish_launch("parallel projection kernel launch");
+}
+
+// The ray route's helper in front of nt_launch_rays: pixels [first, first + count) of the view
+int nt_launch_parallel_expand(const NtLaunchInfo &li, const float *cam, int width, float k, float half_w, float half_h, long long first,
+                              long long count, float *out) {
+    long long blocks = (count + 255) / 256;
+    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    if (blocks < 1) return 0;
+    hipLaunchKernelGGL(parallel_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, cam, li.n, width, k, half_w, half_h, first, count, out);
+    return finish_launch("parallel projection expansion kernel launch");
 }

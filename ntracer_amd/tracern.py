@@ -880,6 +880,48 @@ class _SceneBase(Scene):
 
     lens = property(lambda s: getattr(s, "_lens", None))
 
+    def set_parallel_projection(self, half_width):
+        """Render under the parallel (orthographic) projection: every pixel's ray runs along the camera's forward row and
+        starts in the camera's image plane, which spans 2 * half_width scene units across with square pixels
+        (include/ntracer_hip.h); None or 0 takes it off.  fov is ignored while it is set; a lens and the projection exclude
+        each other (ValueError).  Supersampling, row bands, statistics, calculate_color / colors_at and primary_hits are
+        refused under it; ray_colors, render_rays and the ray queries ignore it.  A view setting like fov: not pickled."""
+        if half_width is None:
+            half_width = 0.0
+        if isinstance(half_width, bool) or not isinstance(half_width, (int, float, np.integer, np.floating)):
+            raise ValueError("half_width must be a number or None")
+        _lib.check(_lib.lib().nt_scene_set_parallel(self._handle, float(half_width)))
+
+    @property
+    def parallel_projection(self):
+        """None, or the half_width of the parallel projection"""
+        v = float(_lib.lib().nt_scene_get_parallel(self._handle))
+        return v if v > 0.0 else None
+
+    def parallel_rays(self, width, height, camera=None):
+        """(origins float32 [height * width][n], direction float32 [n]): the rays a width x height render casts under the
+        parallel projection that is set, for `camera` or the scene's own -- the origins computed in float32 in the device's
+        operation order, the direction the unnormalised forward row.  With the direction repeated for every origin
+        (np.broadcast_to(direction, origins.shape)) Scene.render_rays / ray_colors reproduce what the render casts."""
+        hw = self.parallel_projection
+        if hw is None:
+            raise ValueError("no parallel projection is set")
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        if camera is None:
+            camera = self.get_camera()
+        elif not isinstance(camera, Camera) or camera.dimension != self._n:
+            raise TypeError("the scene and camera must have the same dimension")
+        org = np.ascontiguousarray(camera._origin, f32)
+        ax = np.ascontiguousarray(camera._axes, f32)
+        half_w, half_h = f32(width) / f32(2), f32(height) / f32(2)
+        k = f32(hw) / half_w
+        sx = (k * (np.arange(width, dtype=f32) - half_w)).astype(f32)
+        sy = (k * (np.arange(height, dtype=f32) - half_h)).astype(f32)
+        o = (org[None, None, :] + ax[0][None, None, :] * sx[None, :, None]) - ax[1][None, None, :] * sy[:, None, None]
+        return np.ascontiguousarray(o.reshape(height * width, self._n), f32), ax[2].copy()
+
     def set_camera(self, camera):
         if not isinstance(camera, Camera) or camera.dimension != self._n:
             raise TypeError("the scene and camera must have the same dimension")
