@@ -205,6 +205,33 @@ int nt_scene_set_supersampling(nt_scene_t *s, int factor);
 int nt_scene_get_supersampling(const nt_scene_t *s);
 int nt_scene_set_supersampling_scratch_mb(nt_scene_t *s, int mib);
 int nt_scene_get_supersampling_scratch_mb(const nt_scene_t *s);
+/* Adaptive supersampling: one more view setting beside the factor, off by default.  enabled != 0 with a finite float `threshold`
+   t switches it on.  With it on and a factor s > 1, a W x H render is defined as follows.  Let P be the plain single-sample frame
+   of the same scene, camera and fov, each component clamped to [0, 1] as a sample is clamped.  The contrast of pixel (x, y) is the
+   largest |P[x,y][c] - P[x',y'][c]| over c in {r, g, b} and over those of its four neighbours (x +- 1, y), (x, y +- 1) that lie
+   inside the image; a pixel without a neighbour inside the image has contrast 0.  The pixel is flagged iff contrast > t, in fp32.
+   A flagged pixel gets exactly the supersampled pixel defined above (its s*s samples clamped, summed in fp32 in row-major order,
+   divided by (float)(s*s)); an unflagged pixel gets P's colour; either goes through the format's conversion and packing as always.
+   So t < 0 flags every pixel and the frame is the supersampled frame, t >= 1 flags none and the frame is the plain frame, and with
+   s = 1 the setting changes nothing.  What the scheme cannot see: a feature thinner than a pixel that every pixel-centre ray
+   misses leaves no contrast in P and is not refined.  All of it runs on the device (a base frame and a list of flagged pixels, 16
+   bytes a pixel a frame, under the cap of nt_scene_set_supersampling_scratch_mb; larger jobs are cut into chunks of whole frames,
+   and a single frame that does not fit fails with NT_E_UNSUPPORTED before anything is launched).  Refused with NT_E_UNSUPPORTED
+   ("adaptive ...") before a device is touched, drawing nothing: row bands (band_world > 1) and collect_stats -- a pixel's
+   neighbours across a band are not there, and the refining kernels keep no counters.  A lens and the parallel projection refuse
+   any factor above 1 as before.  nt_calculate_color / nt_colors_at, nt_primary_hits*, nt_ray_colors*, nt_render_rays* and the ray
+   queries ignore the setting, as they ignore the factor.  Not part of a pickled scene.  NT_E_INVALID for a NaN or infinite
+   threshold (the setting stays as it was), NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it;
+   the getter writes 0 / 1 and the threshold (0 when off) through whichever pointers are not NULL. */
+int nt_scene_set_adaptive_supersampling(nt_scene_t *s, int enabled, float threshold);
+int nt_scene_get_adaptive_supersampling(const nt_scene_t *s, int *enabled, float *threshold);
+/* The flags of a width x height render of the scene's own camera under the threshold that is set, whatever the factor:
+   mask[y * width + x] = 1 for a flagged pixel, 0 otherwise.  The host form also returns their number through `flagged` (may be
+   NULL); it reads device, strict_reference of `opts`.  The device form writes width * height bytes of device memory at mask_dev
+   and is only enqueued on hip_stream; it also reads abort_device and overlapped.  NT_E_INVALID when the threshold is off;
+   NT_E_UNSUPPORTED for bands or collect_stats in `opts`, and while a lens or the parallel projection is set. */
+int nt_adaptive_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *flagged, const nt_render_opts *opts);
+int nt_adaptive_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream);
 /* CompositeScene.set_shadows/set_camera_light/set_max_reflect_depth/set_ambient_color/
    set_background/add_light rolled into one call */
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p);

@@ -132,6 +132,10 @@ SYMBOLS = [
     ("nt_scene_get_supersampling", C.c_int, [C.c_void_p]),
     ("nt_scene_set_supersampling_scratch_mb", C.c_int, [C.c_void_p, C.c_int]),
     ("nt_scene_get_supersampling_scratch_mb", C.c_int, [C.c_void_p]),
+    ("nt_scene_set_adaptive_supersampling", C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    ("nt_scene_get_adaptive_supersampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    ("nt_adaptive_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
+    ("nt_adaptive_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_set_params", C.c_int, [C.c_void_p, C.POINTER(NtSceneParams)]),
     ("nt_scene_lock", C.c_int, [C.c_void_p]),
     ("nt_scene_unlock", C.c_int, [C.c_void_p]),

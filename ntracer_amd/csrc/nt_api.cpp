@@ -103,7 +103,9 @@ struct DeviceState {
     DevBuf framebuffer, cams, probes, stats, counter;
     DevBuf hits;                         // primary-hit records between the two passes of a lit render
     DevBuf stats_frame;                  // where the statistics launch of a "faithful" scene draws (discarded)
-    DevBuf samples;                      // supersampling: the fp32 x 3 samples between the render and the resolve kernel
+    DevBuf samples;                      // supersampling: the fp32 x 3 samples between the render and the resolve kernel; adaptive
+                                         // supersampling: the base frame, the list of flagged pixels and the host forms' mask
+    DevBuf refine_count;                 // adaptive supersampling: the length of that list
     DevBuf numer;                        // packet kernel: -(N.o + d) per (frame, simplex)
     DevBuf cull;                         // BoxScene: row culling bits
     bool cull_clean = false;             // `cull` is all zero (what the fused BoxScene path needs and leaves behind)
@@ -167,6 +169,8 @@ struct nt_scene {
     float fov = 0.8f;                    // tracer.hpp:91,1731
     int supersampling = 1;               // s x s samples a pixel (nt_scene_set_supersampling; the reference has none)
     int ss_scratch_mb = 1024;            // ... and the cap of their scratch buffer, MiB per device (nt_scene_set_supersampling_scratch_mb)
+    bool adaptive = false;               // with supersampling > 1: only pixels whose contrast exceeds adaptive_t get the s x s samples
+    float adaptive_t = 0.0f;             // (nt_scene_set_adaptive_supersampling)
     std::vector<float> origin, axes;     // camera<Store>: origin[n], t_orientation[n][n] (camera.hpp:7-15)
     std::shared_ptr<NtLensData> lens;    // not null: the renders' ray source (nt_scene_set_lens); fov is then ignored
     float parallel = 0.0f;               // > 0: the parallel projection's half_width (nt_scene_set_parallel); excludes a lens
@@ -926,6 +930,140 @@ int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// adaptive supersampling (nt_scene_set_adaptive_supersampling; kernels in nt_adaptive.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+int rays_scene(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, bool strict, long long count, long long lpb_fixed, long long max_fixed,
+               NtCompositeDev &c);
+
+// What an adaptive render refuses, checked by the entry points before a device is touched (and by enqueue_adaptive again, for
+// every way in): the contrast of a pixel needs its neighbours, which another rank's band holds, and the refine kernels keep no
+// counters
+int adaptive_check(const nt_scene *s, const Bands &b, bool stats) {
+    if (!s->adaptive || s->supersampling <= 1) return NT_OK;
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "row bands (band_world %d) are not available with adaptive supersampling: a pixel's contrast needs its neighbours", b.world);
+    if (stats) return fail(NT_E_UNSUPPORTED, "collect_stats is not available with adaptive supersampling");
+    return NT_OK;
+}
+
+// An adaptive render, in three stages per chunk of whole frames (nt_adaptive.hpp): the job once more in the plain fp32 x 3 format
+// into scratch -- every route of a plain render comes with it --, adaptive_flag, which draws the unflagged pixels and lists the
+// others, and the refine kernels over that list.  `mask_dev` (nt_adaptive_mask*): the [nframes][H][W] flag bytes go there, and
+// with job.fmt == nullptr nothing is drawn: the view is then job.view_w x job.view_h and stage 3 is left out.  The scratch -- 12 + 4
+// bytes a pixel a frame, and one more for `mask_scratch`, the host form's mask -- sits under the supersampling cap.  Enqueue only.
+int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, uint8_t *mask_dev, bool mask_scratch,
+                     uint8_t **mask_out) {
+    const bool draw = job.fmt != nullptr;
+    const int ss = s->supersampling;
+    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
+    if (job.bands.world > 1) return fail(NT_E_UNSUPPORTED, "row bands (band_world %d) are not available with adaptive supersampling: a pixel's contrast needs its neighbours", job.bands.world);
+    if (job.stats) return fail(NT_E_UNSUPPORTED, "collect_stats is not available with adaptive supersampling");
+    if (draw && (job.row_begin != 0 || job.row_count != H)) return fail(NT_E_UNSUPPORTED, "a row range is not available with adaptive supersampling");
+    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const long long px = (long long)W * H;
+    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const long long per_frame = px * (mask_scratch ? 17 : 16);
+    if (px > INT_MAX / 4) return fail(NT_E_UNSUPPORTED, "adaptive supersampling of a %d x %d image: more pixels than the list of flagged pixels addresses", W, H);
+    if (per_frame > cap)
+        return fail(NT_E_UNSUPPORTED, "adaptive supersampling of a %d x %d image: the base frame and the list of one frame (%lld bytes) do not fit "
+                    "the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    if (draw && ((long long)ss * W > INT_MAX / 12 || (long long)ss * H > INT_MAX))
+        return fail(NT_E_UNSUPPORTED, "supersampling %d of a %d x %d image: beyond the views the kernels address", ss, W, H);
+    const int chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame), (INT_MAX / 4) / px));
+    if (int e = ds->samples.ensure((size_t)chunk_frames * per_frame)) return e;
+    if (int e = ds->refine_count.ensure(64)) return e;
+    char *scratch = (char *)ds->samples.p;
+    uint32_t *list = (uint32_t *)(scratch + (size_t)chunk_frames * px * 12);
+    if (mask_scratch) mask_dev = (uint8_t *)(scratch + (size_t)chunk_frames * px * 16);
+    if (mask_out) *mask_out = mask_dev;
+    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
+    const nt_image_format base_desc = {(int32_t)W, (int32_t)H, 0, 3, plain, 0};
+    Format bf;
+    if (int r = parse_format(&base_desc, bf)) return r;
+    const int n = s->n;
+    NtTarget tg;
+    if (draw) {
+        if (int r = fill_target(s, ds, job, tg)) return r;
+    } else {
+        std::memset(&tg, 0, sizeof(tg));
+        fill_view(tg, s, W, H);
+        tg.band_world = 1;
+        tg.band_rows = NT_RENDER_CHUNK_SIZE;
+        tg.row_count = H;
+        tg.abort_word = job.abort_word;
+    }
+    const float *cams = job.cam_buf;
+    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
+        const int nf = std::min(chunk_frames, job.nframes - f0);
+        FrameJob bj = job;
+        bj.samples_pass = true;
+        bj.fmt = &bf;
+        bj.bands = Bands();
+        bj.bands.owned_rows = H;
+        bj.row_begin = 0;
+        bj.row_count = H;
+        bj.nframes = nf;
+        bj.frame_stride = (size_t)px * 12;
+        bj.dest_dev = scratch;
+        bj.stats = false;
+        if (job.cam_buf) {
+            bj.cam_buf = job.cam_buf + (size_t)f0 * 4 * n;
+            bj.cam_dots = job.cam_dots + (size_t)f0 * 4;
+        }
+        if (int e = enqueue(s, ds, bj)) return e;
+        NtAdaptive ad{};
+        ad.base = (const uint32_t *)scratch;
+        ad.nframes = nf;
+        ad.threshold = s->adaptive_t;
+        ad.list = list;
+        ad.count = (int *)ds->refine_count.p;
+        ad.mask = mask_dev ? mask_dev + (size_t)f0 * px : nullptr;
+        ad.draw = draw ? 1 : 0;
+        NtTarget ft = tg;
+        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        if (nt_launch_adaptive_flag(job.stream, ad, ft)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+        if (!draw || ss <= 1) continue;
+        if (!cams) {
+            // the scene's own camera in device memory, packed as enqueue_lens packs it (after the base frame, whose packet walk
+            // puts the same rows there)
+            float packed[4 * NT_DEV_MAX_DIM];
+            pack_camera(n, s->origin.data(), s->axes.data(), packed);
+            if (int e = ds->cams.ensure(sizeof(float) * 4 * n)) return e;
+            HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
+        }
+        NtRefine rf{};
+        rf.list = list;
+        rf.count = ad.count;
+        rf.max_count = (long long)nf * px;
+        rf.cams = cams ? cams + (size_t)f0 * 4 * n : (const float *)ds->cams.p;
+        rf.s = ss;
+        NtTarget hv;
+        fill_view(hv, s, ss * W, ss * H);                               // (the view of 4.3's first stage)
+        rf.half_w = hv.half_w;
+        rf.half_h = hv.half_h;
+        rf.fovI = hv.fovI;
+        // consecutive lanes hold the list's pixels, not the aligned groups of one row that emit_pixel's shared dword stores of
+        // 3- and 6-byte pixels count on: those formats go out pixel by pixel (as rays_image_target has it)
+        if (ft.bpp == 3 || ft.bpp == 6) ft.aligned4 = 0;
+        NtLaunchInfo li{};
+        li.n = n;
+        li.nframes = nf;
+        li.stream = job.stream;
+        li.cu_count = ds->cu_count;
+        li.force_var = sw.force_var;
+        int r;
+        if (s->composite) {
+            NtCompositeDev c;
+            if (int e = rays_scene(s, ds, sw, job.strict, rf.max_count, 64, 4096, c)) return e;
+            r = nt_launch_refine(li, &c, rf, ft);
+        } else {
+            r = nt_launch_refine(li, nullptr, rf, ft);
+        }
+        if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    }
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // renders through a lens (nt_scene_set_lens; kernels in nt_lens.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1149,6 +1287,8 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     FrameJob job = job_in;
     if (s->lens) return enqueue_lens(s, ds, job, sw);
     if (s->parallel > 0.0f) return enqueue_parallel(s, ds, job, sw);
+    if (s->supersampling > 1 && s->adaptive && !job.colors_out && !job.samples_pass && !job.counters_pass)
+        return enqueue_adaptive(s, ds, job, sw, nullptr, false, nullptr);
     if (s->supersampling > 1 && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_supersampled(s, ds, job);
     if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
         // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
@@ -1635,6 +1775,30 @@ int rays_image_target(const nt_scene *s, DeviceState *ds, const Format *fmt, voi
     return NT_OK;
 }
 
+// the scene of a ray-colour launch over `count` rays, and its per-lane scratch: `lpb_fixed` lanes a block of the compile-time-N
+// kernels (the run-time-n ones have 64), at most `max_fixed` blocks of them
+int rays_scene(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, bool strict, long long count, long long lpb_fixed, long long max_fixed,
+               NtCompositeDev &c) {
+    fill_composite(s, ds, c, false);
+    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
+    if (c.root < 0) c.root = -1;
+    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
+    if (faithful) {
+        const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
+        const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
+        const long long lpb = var_t ? 64 : lpb_fixed;
+        const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
+        long long blocks = std::min<long long>((count + lpb - 1) / lpb, var_t ? 4096 : max_fixed);
+        if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, fwords, (long long)512 << 20, sw.clean_normals)) return e;
+        if (var_t) {
+            if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
+            c.tframes = (float *)ds->tframes.p;
+            c.tframe_count = nframes_stack;
+        }
+    }
+    return NT_OK;
+}
+
 int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, const Format *fmt, void *dest_dev, bool strict,
                  const int *abort_word, hipStream_t stream) {
     const RenderSwitches sw = read_switches();
@@ -1659,23 +1823,7 @@ int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, 
     int r;
     if (s->composite) {
         NtCompositeDev c;
-        fill_composite(s, ds, c, false);
-        c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
-        if (c.root < 0) c.root = -1;
-        const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
-        if (faithful) {
-            const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
-            const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
-            const long long lpb = var_t ? 64 : 256;
-            const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
-            long long blocks = std::min<long long>(((long long)job.count + lpb - 1) / lpb, var_t ? 4096 : 1024);
-            if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, fwords, (long long)512 << 20, sw.clean_normals)) return e;
-            if (var_t) {
-                if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
-                c.tframes = (float *)ds->tframes.p;
-                c.tframe_count = nframes_stack;
-            }
-        }
+        if (int e = rays_scene(s, ds, sw, strict, job.count, 256, 1024, c)) return e;
         r = nt_launch_rays(li, &c, job, tg);
     } else {
         r = nt_launch_rays(li, nullptr, job, tg);
@@ -2022,6 +2170,23 @@ int nt_scene_set_supersampling_scratch_mb(nt_scene_t *s, int mib) {
 
 int nt_scene_get_supersampling_scratch_mb(const nt_scene_t *s) { return s ? s->ss_scratch_mb : fail(NT_E_INVALID, "scene is NULL"); }
 
+int nt_scene_set_adaptive_supersampling(nt_scene_t *s, int enabled, float threshold) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (enabled && !std::isfinite(threshold)) return fail(NT_E_INVALID, "the adaptive threshold must be a finite number");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->adaptive = enabled != 0;
+    s->adaptive_t = enabled ? threshold : 0.0f;
+    return NT_OK;
+}
+
+int nt_scene_get_adaptive_supersampling(const nt_scene_t *s, int *enabled, float *threshold) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (enabled) *enabled = s->adaptive ? 1 : 0;
+    if (threshold) *threshold = s->adaptive_t;
+    return NT_OK;
+}
+
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");
     if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no lighting parameters");
@@ -2081,6 +2246,7 @@ int nt_render(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format 
     if (int r = guard.acquire()) return r;
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
+    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
     if (abort_flag && *abort_flag) return NT_ABORTED;           // (before anything touches `dest` or the device)
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
@@ -2163,6 +2329,7 @@ int nt_render_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_im
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
+    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
@@ -2201,6 +2368,7 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
+    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
@@ -2308,6 +2476,7 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
+    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
     int dev;
     if (int r = pick_device(opts, -1, dev)) return r;
     if (dev != table->device) return fail(NT_E_INVALID, "the camera table lives on device %d, the render is for device %d", table->device, dev);
@@ -2334,6 +2503,72 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     job.row_begin = 0;
     job.row_count = b.owned_rows;
     return enqueue(s, ds, job);
+}
+
+namespace {
+// what both forms of nt_adaptive_mask check before a device is touched
+int mask_validate(const nt_scene *s, int width, int height, const void *mask, const nt_render_opts *opts) {
+    if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (!s->adaptive) return fail(NT_E_INVALID, "the adaptive threshold is off (nt_scene_set_adaptive_supersampling)");
+    if (opts && opts->band_world > 1)
+        return fail(NT_E_UNSUPPORTED, "the adaptive mask is of the whole image: row bands (band_world %d) are not available", opts->band_world);
+    if (opts && opts->collect_stats) return fail(NT_E_UNSUPPORTED, "the adaptive mask keeps no counters: collect_stats is not available");
+    if (s->lens || s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "the adaptive mask is not available while a lens or the parallel projection is set");
+    return check_renderable(s);
+}
+}  // namespace
+
+int nt_adaptive_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *flagged, const nt_render_opts *opts) {
+    if (int r = mask_validate(s, width, height, mask, opts)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = own_stream(ds)) return r;
+    if (int r = use_stream(ds, ds->stream)) return r;
+    FrameJob job{};
+    job.nframes = 1;
+    job.stream = ds->stream;
+    job.strict = opts && opts->strict_reference;
+    job.view_w = width;
+    job.view_h = height;
+    job.row_count = height;
+    job.bands.owned_rows = height;
+    uint8_t *mask_dev = nullptr;
+    if (int r = enqueue_adaptive(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    int count = 0;
+    HIP_TRY(hipMemcpyAsync(mask, mask_dev, (size_t)width * height, hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipMemcpyAsync(&count, ds->refine_count.p, sizeof(int), hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipStreamSynchronize(ds->stream));
+    if (flagged) *flagged = count;
+    return NT_OK;
+}
+
+int nt_adaptive_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = mask_validate(s, width, height, mask_dev, opts)) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    FrameJob job{};
+    job.nframes = 1;
+    job.stream = (hipStream_t)hip_stream;
+    job.strict = opts && opts->strict_reference;
+    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
+    job.overlapped = opts ? opts->overlapped : 0;
+    job.view_w = width;
+    job.view_h = height;
+    job.row_count = height;
+    job.bands.owned_rows = height;
+    return enqueue_adaptive(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
 }
 
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {

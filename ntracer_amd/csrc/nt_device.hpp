@@ -256,6 +256,26 @@ struct NtParallel {
     const void *hits;         // packet route: the 16-byte records between the walk and the shading pass (the launcher's own)
 };
 
+// Adaptive supersampling (nt_adaptive.hpp, nt_var.hip): what lies between the base frame and the caller's image.  Every pointer
+// is device memory.  A flagged pixel's list entry is frame * height * width + y * width + x, frames counted within the launch.
+struct NtAdaptive {
+    const uint32_t *base;     // the base frame: [nframes][height][width] pixels of three big-endian floats, clamped to [0, 1]
+    int nframes;
+    float threshold;          // contrast > threshold flags the pixel
+    uint32_t *list;           // the flagged pixels; room for every pixel of the launch
+    int *count;               // their number: zeroed in stream order in front of the flag kernel (adaptive_reset)
+    uint8_t *mask;            // nullptr, or [nframes][height][width] bytes: 1 flagged, 0 not
+    int draw;                 // 1: unflagged pixels go into tg.dest; 0: the mask alone is wanted
+};
+struct NtRefine {
+    const uint32_t *list;     // NtAdaptive::list
+    const int *count;         // NtAdaptive::count
+    long long max_count;      // pixels of the launch: what the list could hold (the grid is sized by it)
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    int s;                    // s x s samples a pixel
+    float half_w, half_h, fovI;   // the s * width x s * height view (fill_view)
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
@@ -287,6 +307,11 @@ int nt_launch_parallel(const NtLaunchInfo &li, const NtCompositeDev &sc, const N
 // rows behind them; k, half_w and half_h as NtTarget has them
 int nt_launch_parallel_expand(const NtLaunchInfo &li, const float *cam, int width, float k, float half_w, float half_h, long long first,
                               long long count, float *out);
+// adaptive_flag: tg is the whole image of ad.nframes frames (no bands); see NtAdaptive
+int nt_launch_adaptive_flag(void *stream, const NtAdaptive &ad, const NtTarget &tg);
+// the refine kernels: the scene as for nt_launch_rays (sc == nullptr: BoxScene; sc->checked / sc->tframes with lane columns for
+// blocks of 64 lanes); tg is the whole image the list's pixels belong to
+int nt_launch_refine(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRefine &rf, const NtTarget &tg);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

@@ -6,6 +6,7 @@
 #include "nt_hits.hpp"
 #include "nt_rays.hpp"
 #include "nt_resolve.hpp"
+#include "nt_adaptive.hpp"
 
 // compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
 #define NT_DECLARE_FIXED(N)                                                                              \
@@ -24,6 +25,14 @@ NT_DECLARE_RAYS_BOX(9) NT_DECLARE_RAYS_BOX(10) NT_DECLARE_RAYS_BOX(11) NT_DECLAR
 NT_DECLARE_RAYS_BOX(15) NT_DECLARE_RAYS_BOX(16) NT_DECLARE_RAYS_BOX(17) NT_DECLARE_RAYS_BOX(18) NT_DECLARE_RAYS_BOX(19) NT_DECLARE_RAYS_BOX(20)
 NT_DECLARE_RAYS_BOX(21) NT_DECLARE_RAYS_BOX(22) NT_DECLARE_RAYS_BOX(23) NT_DECLARE_RAYS_BOX(24)
 // the packet route of a render through a lens (nt_inst_lens.hip)
+#define NT_DECLARE_REFINE(N) int nt_refine_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtRefine &rf, const NtTarget &tg);
+#define NT_DECLARE_REFINE_BOX(N) int nt_refine_box_fixed_##N(const NtLaunchInfo &li, const NtRefine &rf, const NtTarget &tg);
+NT_DECLARE_REFINE(3) NT_DECLARE_REFINE(4) NT_DECLARE_REFINE(5) NT_DECLARE_REFINE(6) NT_DECLARE_REFINE(7) NT_DECLARE_REFINE(8) NT_DECLARE_REFINE(9) NT_DECLARE_REFINE(10)
+NT_DECLARE_REFINE_BOX(3) NT_DECLARE_REFINE_BOX(4) NT_DECLARE_REFINE_BOX(5) NT_DECLARE_REFINE_BOX(6) NT_DECLARE_REFINE_BOX(7) NT_DECLARE_REFINE_BOX(8)
+NT_DECLARE_REFINE_BOX(9) NT_DECLARE_REFINE_BOX(10) NT_DECLARE_REFINE_BOX(11) NT_DECLARE_REFINE_BOX(12) NT_DECLARE_REFINE_BOX(13) NT_DECLARE_REFINE_BOX(14)
+NT_DECLARE_REFINE_BOX(15) NT_DECLARE_REFINE_BOX(16) NT_DECLARE_REFINE_BOX(17) NT_DECLARE_REFINE_BOX(18) NT_DECLARE_REFINE_BOX(19) NT_DECLARE_REFINE_BOX(20)
+NT_DECLARE_REFINE_BOX(21) NT_DECLARE_REFINE_BOX(22) NT_DECLARE_REFINE_BOX(23) NT_DECLARE_REFINE_BOX(24)
+
 #define NT_DECLARE_LENS(N) int nt_lens_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln);
 NT_DECLARE_LENS(3) NT_DECLARE_LENS(4) NT_DECLARE_LENS(5) NT_DECLARE_LENS(6) NT_DECLARE_LENS(7) NT_DECLARE_LENS(8) NT_DECLARE_LENS(9) NT_DECLARE_LENS(10)
 // the packet route of a render under the parallel projection (nt_inst_parallel.hip)
@@ -2005,6 +2014,174 @@ __global__ __launch_bounds__(256) void parallel_expand(const float *cam, int n, 
     }
 }
 
+// --------------------------------------------------------------------------------------
+// Adaptive supersampling at run-time n (n = 11..64 -- BoxScene: 25..64 -- and every n under NTRACER_FORCE_VAR=1): the refine
+// kernels of nt_adaptive.hpp on composite_color_var / composite_color_var_t and on rays_box_var's evaluation.  One lane a
+// flagged pixel, one wave a block, the blocks striding over the list.
+// --------------------------------------------------------------------------------------
+// sample k = j * s + i of the pixel becomes the current ray: hits_set_ray_var's operations on the s W x s H view
+__device__ __forceinline__ void refine_set_ray_var(const VarCtx &cx, const NtRefine &rf, const RefinePixel &p, int k) {
+    const int n = cx.n, lane = cx.lane;
+    const int j = k / rf.s, i = k - j * rf.s;
+    const float *c = rf.cams + (size_t)p.frame * 4 * n;
+    const float sx = rf.fovI * ((float)(rf.s * p.x + i) - rf.half_w);
+    const float sy = rf.fovI * ((float)(rf.s * p.y + j) - rf.half_h);
+    float sq = 0.0f;
+    for (int q = 0; q < n; ++q) {
+        const float v = (c[3 * n + q] + c[n + q] * sx) - c[2 * n + q] * sy;
+        cx.L.dv[q * 64 + lane] = v;
+        sq = q == 0 ? v * v : sq + v * v;
+    }
+    const float len = sqrtf(sq);
+    for (int q = 0; q < n; ++q) {
+        const float dk = cx.L.dv[q * 64 + lane] / len;
+        cx.L.dv[q * 64 + lane] = dk;
+        cx.L.ray[q * 64 + lane] = make_float2(c[q], dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
+    }
+}
+
+__global__ __launch_bounds__(64) void refine_color_var(NtCompositeDev sc, NtRefine rf, NtTarget tg, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    const long long count = (long long)*rf.count;
+    const int ss = rf.s * rf.s;
+    for (long long base = (long long)blockIdx.x * 64; base < count; base += (long long)gridDim.x * 64) {
+        if (nt_aborted(tg)) return;
+        if (base + lane >= count) continue;
+        const RefinePixel p = refine_pixel(tg, rf, base + lane);
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < ss; ++k) {
+            refine_set_ray_var(cx, rf, p, k);
+            const Color3 col = composite_color_var(cx);
+            refine_add(acc, k, col.r, col.g, col.b);
+        }
+        refine_emit(tg, rf, p, acc);
+    }
+}
+
+template <bool ALIAS>
+__global__ __launch_bounds__(64) void refine_color_var_t(NtCompositeDev sc, NtRefine rf, NtTarget tg, int n) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const VarCtx cx = {sc, L, w, n, lane};
+    const long long slot = (long long)blockIdx.x * 64 + lane;
+    Checked ck;
+    ck.bits = sc.checked + slot;
+    ck.stride = sc.checked_lanes;
+    ck.words = sc.checked_words;
+    ck.n_batches = sc.n_batches;
+    ck.n_triangles = sc.n_triangles;
+    VarFrames fr;
+    fr.base = sc.tframes + slot;
+    fr.stride = sc.checked_lanes;
+    fr.fw = var_frame_words(n);
+    const long long count = (long long)*rf.count;
+    const int ss = rf.s * rf.s;
+    for (long long base = (long long)blockIdx.x * 64; base < count; base += (long long)gridDim.x * 64) {
+        if (nt_aborted(tg)) return;
+        if (base + lane >= count) continue;
+        const RefinePixel p = refine_pixel(tg, rf, base + lane);
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < ss; ++k) {
+            refine_set_ray_var(cx, rf, p, k);
+            const Color3 col = composite_color_var_t<ALIAS>(cx, fr, ck, sc.tframe_count);
+            refine_add(acc, k, col.r, col.g, col.b);
+        }
+        refine_emit(tg, rf, p, acc);
+    }
+}
+
+// BoxScene: rays_box_var's evaluation of the ray whose direction and origin lie in LDS as dir[j * 64], org[j * 64]
+__device__ __forceinline__ void refine_box_color_var(const float *dir, const float *org, int n, float &cr, float &cg, float &cb) {
+    bool done = false;
+    float shade = 0.0f;
+    float aK = 0.0f, bK = 1.0f, oK = 0.0f;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const float di = dir[i * 64];
+        const float oi = org[i * 64];
+        const float num = (di < 0.0f ? 1.0f : -1.0f) - oi;
+        const bool pre = (num > 0.0f && di > 0.0f) || (num < 0.0f && di < 0.0f);
+        const float a = fabsf(num), bb = fabsf(di);
+        if (pre && (!any || a * bK > aK * bb)) { aK = a; bK = bb; oK = oi; any = true; }
+    }
+    const float mu = 1e-4f * (1.0f + fabsf(oK));
+    const float aKm = (aK - mu) * (1.0f - 1e-6f);
+    for (int i = 0; i < n; ++i) {
+        const float di = dir[i * 64];
+        const float oi = org[i * 64];
+        const float s = di < 0.0f ? 1.0f : -1.0f;
+        const float num = s - oi;
+        const bool pre = (num > 0.0f && di > 0.0f) || (num < 0.0f && di < 0.0f);
+        const bool tie = pre && !done && !(fabsf(num) * bK < fabsf(di) * aKm);
+        if (!tie) continue;
+        const float dist = num / di;
+        bool ok = dist > 0.0f;
+        for (int j = 0; j < n; ++j) {
+            if (j != i) {
+                const float p = dir[j * 64] * dist + org[j * 64];
+                ok = ok && !(fabsf(p) > (1.0f + NT_FUZZ));
+            }
+        }
+        if (ok) {
+            done = true;
+            if (dist >= FLT_MAX) shade = -1.0f;
+            else {
+                const float sine = di * s;
+                shade = sine <= 0.0f ? -sine : 0.0f;
+            }
+        }
+    }
+    if (done && shade >= 0.0f) {
+        cr = shade * 1.0f;
+        cg = shade * 0.5f;
+        cb = shade * 0.5f;
+    } else {
+        box_background(dir[0], cr, cg, cb);
+    }
+}
+
+__global__ __launch_bounds__(64) void refine_box_var(NtRefine rf, NtTarget tg, int n) {
+    extern __shared__ float lds_vec[];    // [n][64] direction, [n][64] origin
+    const int lane = (int)threadIdx.x;
+    float *dir = lds_vec + lane;          // dir[j] at dir[j * 64]
+    float *org = lds_vec + (size_t)n * 64 + lane;
+    const long long count = (long long)*rf.count;
+    const int ss = rf.s * rf.s;
+    for (long long base = (long long)blockIdx.x * 64; base < count; base += (long long)gridDim.x * 64) {
+        if (nt_aborted(tg)) return;
+        if (base + lane >= count) continue;
+        const RefinePixel p = refine_pixel(tg, rf, base + lane);
+        const float *c = rf.cams + (size_t)p.frame * 4 * n;
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < ss; ++k) {
+            const int sj = k / rf.s, si = k - sj * rf.s;
+            const float sx = rf.fovI * ((float)(rf.s * p.x + si) - rf.half_w);
+            const float sy = rf.fovI * ((float)(rf.s * p.y + sj) - rf.half_h);
+            float sq = 0.0f;
+            for (int j = 0; j < n; ++j) {
+                const float v = (c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy;
+                dir[j * 64] = v;
+                org[j * 64] = c[j];
+                sq = j == 0 ? v * v : sq + v * v;
+            }
+            const float len = sqrtf(sq);
+            for (int j = 0; j < n; ++j) dir[j * 64] = dir[j * 64] / len;
+            float cr, cg, cb;
+            refine_box_color_var(dir, org, n, cr, cg, cb);
+            refine_add(acc, k, cr, cg, cb);
+        }
+        refine_emit(tg, rf, p, acc);
+    }
+}
+
 #undef VO
 #undef VD
 
@@ -2336,6 +2513,101 @@ int nt_launch_rays(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRay
     }
     if (r) return r;
     return finish_launch("ray-colour kernel launch");
+}
+
+// Adaptive supersampling (nt_adaptive.hpp): the flag kernel, and the refine kernels chosen as nt_launch_rays chooses the rays_* ones
+int nt_launch_adaptive_flag(void *stream, const NtAdaptive &ad, const NtTarget &tg) {
+    launch_adaptive_flag((hipStream_t)stream, ad, tg);
+    return finish_launch("adaptive flag kernel launch");
+}
+
+int nt_launch_refine(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRefine &rf, const NtTarget &tg) {
+    hipStream_t s = (hipStream_t)li.stream;
+    if (li.n < 3 || li.n > NT_DEV_MAX_DIM || rf.s < 2 || rf.s > 8) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "refine kernels: unsupported dimension %d or factor %d", li.n, rf.s);
+        return -2;
+    }
+    long long blocks = refine_blocks(rf);
+    int r = 0;
+    if (!sc) {
+        switch (li.force_var ? 0 : li.n) {
+            case 3: r = nt_refine_box_fixed_3(li, rf, tg); break;
+            case 4: r = nt_refine_box_fixed_4(li, rf, tg); break;
+            case 5: r = nt_refine_box_fixed_5(li, rf, tg); break;
+            case 6: r = nt_refine_box_fixed_6(li, rf, tg); break;
+            case 7: r = nt_refine_box_fixed_7(li, rf, tg); break;
+            case 8: r = nt_refine_box_fixed_8(li, rf, tg); break;
+            case 9: r = nt_refine_box_fixed_9(li, rf, tg); break;
+            case 10: r = nt_refine_box_fixed_10(li, rf, tg); break;
+            case 11: r = nt_refine_box_fixed_11(li, rf, tg); break;
+            case 12: r = nt_refine_box_fixed_12(li, rf, tg); break;
+            case 13: r = nt_refine_box_fixed_13(li, rf, tg); break;
+            case 14: r = nt_refine_box_fixed_14(li, rf, tg); break;
+            case 15: r = nt_refine_box_fixed_15(li, rf, tg); break;
+            case 16: r = nt_refine_box_fixed_16(li, rf, tg); break;
+            case 17: r = nt_refine_box_fixed_17(li, rf, tg); break;
+            case 18: r = nt_refine_box_fixed_18(li, rf, tg); break;
+            case 19: r = nt_refine_box_fixed_19(li, rf, tg); break;
+            case 20: r = nt_refine_box_fixed_20(li, rf, tg); break;
+            case 21: r = nt_refine_box_fixed_21(li, rf, tg); break;
+            case 22: r = nt_refine_box_fixed_22(li, rf, tg); break;
+            case 23: r = nt_refine_box_fixed_23(li, rf, tg); break;
+            case 24: r = nt_refine_box_fixed_24(li, rf, tg); break;
+            default: {
+                const size_t lds = (size_t)2 * li.n * 64 * sizeof(float);
+                hipLaunchKernelGGL(refine_box_var, dim3((unsigned)blocks), dim3(64), lds, s, rf, tg, li.n);
+            }
+        }
+        if (r) return r;
+        return finish_launch("refine kernel launch");
+    }
+    const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc->stack_depth * 4 + (size_t)NT_MBOX * 4);
+    if (sc->tframes) {
+        if (!sc->checked || sc->checked_lanes < 64) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "run-time-n transparency kernel: bad launch (n %d)", li.n);
+            return -2;
+        }
+        if (lds > 160 * 1024) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
+            return -1;
+        }
+        if (blocks > sc->checked_lanes / 64) blocks = sc->checked_lanes / 64;
+        if (sc->alias_normals) {
+            if (lds > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(refine_color_var_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(refine_color_var_t<true>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
+        } else {
+            if (lds > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(refine_color_var_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(refine_color_var_t<false>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
+        }
+        return finish_launch("refine kernel launch");
+    }
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_refine_fixed_3(li, *sc, rf, tg); break;
+        case 4: r = nt_refine_fixed_4(li, *sc, rf, tg); break;
+        case 5: r = nt_refine_fixed_5(li, *sc, rf, tg); break;
+        case 6: r = nt_refine_fixed_6(li, *sc, rf, tg); break;
+        case 7: r = nt_refine_fixed_7(li, *sc, rf, tg); break;
+        case 8: r = nt_refine_fixed_8(li, *sc, rf, tg); break;
+        case 9: r = nt_refine_fixed_9(li, *sc, rf, tg); break;
+        case 10: r = nt_refine_fixed_10(li, *sc, rf, tg); break;
+        default: {
+            if (!sc->all_opaque || sc->checked) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the run-time-n kernel without frame scratch does not shade transparent materials");
+                return -1;
+            }
+            if (lds > 160 * 1024) {
+                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
+                return -1;
+            }
+            if (lds > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(refine_color_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(refine_color_var, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
+        }
+    }
+    if (r) return r;
+    return finish_launch("refine kernel launch");
 }
 
 // A render through a lens.  The packet route (nt_lens.hpp): the fixed-n launcher of the scene's dimension; there is no

@@ -869,6 +869,57 @@ class _SceneBase(Scene):
             raise ValueError("the supersampling scratch cap must be an integer number of MiB")
         _lib.check(_lib.lib().nt_scene_set_supersampling_scratch_mb(self._handle, int(mib)))
 
+    @property
+    def adaptive_supersampling(self):
+        """None, or the contrast threshold above which a pixel gets the s x s samples (set_adaptive_supersampling)"""
+        on, t = C.c_int(0), C.c_float(0.0)
+        _lib.check(_lib.lib().nt_scene_get_adaptive_supersampling(self._handle, C.byref(on), C.byref(t)))
+        return float(t.value) if on.value else None
+
+    def set_adaptive_supersampling(self, threshold):
+        """With a supersampling factor above 1, refine only the pixels that show contrast: a pixel whose plain single-sample
+        colour (clamped to [0, 1]) differs from that of one of its four neighbours by more than `threshold` in some component
+        gets the factor's s x s samples, every other pixel keeps the plain colour.  None takes it off; a
+        negative threshold refines every pixel, 1 or more refines none.  A feature thinner than a pixel that every pixel-centre
+        ray misses is not seen.  Row bands and statistics are refused with it.  A view setting like fov: not pickled."""
+        if threshold is None:
+            _lib.check(_lib.lib().nt_scene_set_adaptive_supersampling(self._handle, 0, 0.0))
+            return
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+            raise ValueError("the adaptive threshold must be a finite number or None")
+        _lib.check(_lib.lib().nt_scene_set_adaptive_supersampling(self._handle, 1, float(threshold)))
+
+    def refinement_mask(self, width, height, device=None, strict_reference=None):
+        """The pixels a width x height render of the scene's camera would refine under the adaptive threshold that is set
+        (nt_adaptive_mask), whatever the factor: a numpy bool array [height][width] -- or, with `device` a torch device, a
+        torch bool tensor there, enqueued on torch's current stream."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        L = _lib.lib()
+        if device is None:
+            opts = _lib.NtRenderOpts()
+            opts.device = -1
+            if strict_reference is None:
+                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+            opts.strict_reference = 1 if strict_reference else 0
+            mask = np.zeros((height, width), np.uint8)
+            _lib.check(L.nt_adaptive_mask(self._handle, width, height, mask.ctypes.data, None, C.byref(opts)))
+            return mask.view(np.bool_)
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self.adaptive_supersampling is None:
+            raise ValueError("the adaptive threshold is off (set_adaptive_supersampling)")
+        mask = torch.zeros((height, width), dtype=torch.uint8, device=dev)
+        opts = self._rays_opts(dev, strict_reference)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_adaptive_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return mask.view(torch.bool)
+
     def set_lens(self, lens):
         """Render through `lens` (a Lens of the image's size) instead of the pinhole; None takes it off.  fov is ignored
         while a lens is set.  Supersampling, row bands, statistics, calculate_color / colors_at and primary_hits are refused
@@ -1211,6 +1262,7 @@ class CompositeScene(_SceneBase):
         other.set_fov(self.fov)
         other.set_supersampling(self.supersampling)
         other.set_supersampling_scratch_mb(self.supersampling_scratch_mb)
+        other.set_adaptive_supersampling(self.adaptive_supersampling)
         other._push(_pl=list(self._point_lights), _gl=list(self._global_lights), **dict(self._p))
         cam = self.get_camera()
         other._set_camera_arrays(cam._origin, cam._axes)

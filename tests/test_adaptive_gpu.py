@@ -1,0 +1,418 @@
+"""Adaptive supersampling (scene.set_adaptive_supersampling(t) with a factor s > 1) on the GPU against the oracle.
+
+The expected image never comes from the library: tests/adaptive_cases.py builds it from the oracle's plain frame, the
+supersampled image of tests/ss_expected.py and the mask as defined.  BoxScene must match byte for byte, mask included;
+CompositeScene to the project's tolerances against the oracle (1e-5 a component in fp32, one level a channel in packed bytes)
+on the decided pixels, either variant on the undecided ones."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import adaptive_cases as ac
+import fixtures as fx
+import ntracer_amd
+import oracle_binding as ob
+import ss_expected as sx
+from ntracer_amd import _lib, tracern
+from ntracer_amd.render import CameraTable
+
+pytestmark = pytest.mark.gpu
+
+W, H, T = ac.W, ac.H, ac.T
+TOL_ORACLE = 1e-5
+RGB24 = [(8, 1, 0, 0), (8, 0, 1, 0), (8, 0, 0, 1)]
+RGB565 = [(5, 1, 0, 0), (6, 0, 1, 0), (5, 0, 0, 1)]
+# (name, channels, reversed)
+PACKED = [("rgbx8", fx.RGBX8, False), ("rgb24", RGB24, False), ("rgb565", RGB565, False), ("rgb16", fx.RGB16, False),
+          ("rgb24-reversed", RGB24, True), ("rgbx8-reversed", fx.RGBX8, True)]
+
+
+def fmt_of(w, h, chans, pitch=0, rev=False):
+    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
+
+
+def render_host(scene, fmt, **kw):
+    buf = bytearray(fmt.pitch * fmt.height)
+    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene, **kw)
+    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
+
+
+def box_scene(n, camera, s, t):
+    o, a = ac.box_cameras(n)[camera]
+    sc = tracern.BoxScene(n)
+    sc._set_camera_arrays(o, a)
+    sc.set_supersampling(s)
+    sc.set_adaptive_supersampling(t)
+    return sc
+
+
+def composite_scene(case, mp):
+    name, env = case[0], case[1]
+    for k in ac.SWITCHES:
+        mp.delenv(k, raising=False)
+    for k, v in env.items():
+        mp.setenv(k, v)
+    n, flat, params, o, a, _ = ac.case_oracle(case)
+    sc = tracern.CompositeScene.from_flat(n, flat)
+    sc.set_params_flat(params)
+    sc._set_camera_arrays(o, a)
+    return sc
+
+
+# ------------------------------------------------------------------ 1. BoxScene, byte-exact
+@pytest.mark.parametrize("n,s", ac.BOX_CASES)
+def test_box_scene_equals_the_expected_image_and_mask_exactly(n, s):
+    """n: the fixed kernels (3, 4, 6, 10, 16), run-time n (27); the cameras of adaptive_cases.BOX_CAMERAS, each in fp32 x 3 and
+    two packed formats; the returned mask and count are the oracle's"""
+    for j, k in enumerate(ac.BOX_CAMERAS):
+        e = ac.box_expected(n, s, k)
+        sc = box_scene(n, k, s, T)
+        pick = [("rgbf32", fx.RGBF32, False), PACKED[(2 * j + s) % len(PACKED)], PACKED[(2 * j + s + 1) % len(PACKED)]]
+        for name, chans, rev in pick:
+            img = render_host(sc, fmt_of(W, H, chans, rev=rev))
+            want = e.image(chans, rev)
+            assert np.array_equal(img, want), (n, s, k, name, int((img != want).sum()))
+        mask = sc.refinement_mask(W, H)
+        assert mask.dtype == np.bool_ and mask.shape == (H, W)
+        assert np.array_equal(mask, e.mask), (n, s, k, int((mask != e.mask).sum()))
+        count = C.c_longlong(-1)
+        raw = np.zeros((H, W), np.uint8)
+        _lib.check(_lib.lib().nt_adaptive_mask(sc._handle, W, H, raw.ctypes.data, C.byref(count), None))
+        assert count.value == int(e.mask.sum()) and set(np.unique(raw)) <= {0, 1}
+
+
+# ------------------------------------------------------------------ 2. CompositeScene
+def assert_decided_close(img, e, chans, what):
+    """decided pixels: the project's tolerances against the expected image; undecided ones: against either variant"""
+    want, other = e.image(chans), e.other_image(chans)
+    if chans is fx.RGBF32:
+        got = img.view(">f4").astype(np.float32).reshape(H, W, 3)
+        d = np.abs(got - want.view(">f4").astype(np.float32).reshape(H, W, 3)).max(axis=2)
+        d2 = np.abs(got - other.view(">f4").astype(np.float32).reshape(H, W, 3)).max(axis=2)
+        tol = TOL_ORACLE
+    else:
+        got = img.astype(np.int32).reshape(H, W, 4)
+        d = np.abs(got - want.astype(np.int32).reshape(H, W, 4)).max(axis=2)
+        d2 = np.abs(got - other.astype(np.int32).reshape(H, W, 4)).max(axis=2)
+        tol = 1
+    print(what, "decided: max delta %.3g; undecided pixels %d" % (float(d[~e.undecided].max()), int(e.undecided.sum())))
+    assert d[~e.undecided].max() <= tol, (what, float(d[~e.undecided].max()), int((d[~e.undecided] > tol).sum()))
+    assert (np.minimum(d, d2)[e.undecided] <= tol).all(), what
+
+
+COMPOSITE = [(c, s) for c in ac.CASES for s in c[3]]
+
+
+@pytest.mark.parametrize("case,s", COMPOSITE, ids=["%s-s%d" % (ac.case_id(c), s) for c, s in COMPOSITE])
+def test_composite_scene_within_the_projects_tolerances_of_the_expected_image(case, s, monkeypatch):
+    sc = composite_scene(case, monkeypatch)
+    sc.set_supersampling(s)
+    sc.set_adaptive_supersampling(T)
+    e = ac.case_expected(case, s)
+    for chans in (fx.RGBF32, fx.RGBX8):
+        img = render_host(sc, fmt_of(W, H, chans))
+        assert_decided_close(img, e, chans, "%s s=%d" % (ac.case_id(case), s))
+    mask = sc.refinement_mask(W, H)
+    assert np.array_equal(mask[~e.undecided], e.mask[~e.undecided]), int((mask != e.mask)[~e.undecided].sum())
+
+
+# ------------------------------------------------------------------ 3. the extremes of the threshold
+def test_threshold_extremes_box_scene():
+    """t = -1: the supersampled render, byte for byte; t = 2, and any t with s = 1: the plain render, byte for byte"""
+    n, k = 6, 7
+    o, a = ac.box_cameras(n)[k]
+    plain = tracern.BoxScene(n)
+    plain._set_camera_arrays(o, a)
+    full = tracern.BoxScene(n)
+    full._set_camera_arrays(o, a)
+    for s in (2, 3):
+        full.set_supersampling(s)
+        for name, chans, rev in [("rgbf32", fx.RGBF32, False)] + PACKED[:3]:
+            fmt = fmt_of(W, H, chans, rev=rev)
+            sc = box_scene(n, k, s, -1.0)
+            assert np.array_equal(render_host(sc, fmt), render_host(full, fmt)), (s, name)
+            assert np.array_equal(render_host(sc, fmt), sx.expected(ob.OracleScene(n, o, a), W, H, s, chans, rev)), (s, name)
+            assert sc.refinement_mask(W, H).all()
+            sc.set_adaptive_supersampling(2.0)
+            assert np.array_equal(render_host(sc, fmt), render_host(plain, fmt)), (s, name)
+            assert not sc.refinement_mask(W, H).any()
+            sc.set_adaptive_supersampling(T)
+            sc.set_supersampling(1)
+            assert np.array_equal(render_host(sc, fmt), render_host(plain, fmt)), (s, name)
+            assert np.array_equal(sc.refinement_mask(W, H), ac.box_expected(n, 2, k).mask)        # the mask does not ask for the factor
+
+
+@pytest.mark.parametrize("name", ["cell600_n4", "feature5_n5", "lit12_n12"])
+def test_threshold_extremes_composite_scene(name, monkeypatch):
+    case = [c for c in ac.CASES if c[0] == name and not c[1] and not c[2]][0]
+    s = 2
+    sc = composite_scene(case, monkeypatch)
+    plain = {chans is fx.RGBF32: render_host(sc, fmt_of(W, H, chans)) for chans in (fx.RGBF32, fx.RGBX8)}
+    sc.set_supersampling(s)
+    full = render_host(sc, fmt_of(W, H, fx.RGBF32))
+    sc.set_adaptive_supersampling(-1.0)
+    img = render_host(sc, fmt_of(W, H, fx.RGBF32))
+    d = np.abs(img.view(">f4").astype(np.float32) - full.view(">f4").astype(np.float32)).max()
+    print(name, "t = -1 against the supersampled render: max |delta| %.3g" % float(d))
+    assert d <= TOL_ORACLE
+    e = ac.case_expected(case, s)
+    d = np.abs(img.view(">f4").astype(np.float32).reshape(H, W, 3) - e.M).max()
+    assert d <= TOL_ORACLE
+    sc.set_adaptive_supersampling(2.0)
+    for chans in (fx.RGBF32, fx.RGBX8):
+        assert np.array_equal(render_host(sc, fmt_of(W, H, chans)), plain[chans is fx.RGBF32])
+    sc.set_adaptive_supersampling(T)
+    sc.set_supersampling(1)
+    for chans in (fx.RGBF32, fx.RGBX8):
+        assert np.array_equal(render_host(sc, fmt_of(W, H, chans)), plain[chans is fx.RGBF32])
+
+
+# ------------------------------------------------------------------ 4. shapes
+SHAPES = [(1, 1), (1, 7), (7, 1), (8, 8), (9, 17), (64, 48), (256, 37)]
+
+
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_shapes_formats_pitches_and_an_unaligned_destination(w, h):
+    """where the flag kernel can go wrong: images smaller than a wave's stretch and a block's four rows, one row, one column,
+    an exact stretch, a width of four stretches; every packed format, a padded pitch whose padding stays as it was, and RGB24
+    into a device buffer at an odd address.  t = 0.02 so that the small images have flagged pixels too."""
+    import torch
+    n, k, s, t = 6, 7, 2, 0.02
+    e = ac.box_expected(n, s, k, t, w, h)
+    print("%d x %d: flagged %d of %d" % (w, h, int(e.mask.sum()), w * h))
+    if w * h >= 64 * 48:
+        assert e.mask.sum() >= ac.MIN_PIXELS and (~e.mask).sum() >= ac.MIN_PIXELS
+    if (w, h) == (1, 1):
+        assert not e.mask.any()                              # no neighbour inside the image: contrast 0
+    sc = box_scene(n, k, s, t)
+    assert np.array_equal(sc.refinement_mask(w, h), e.mask)
+    for name, chans, rev in [("rgbf32", fx.RGBF32, False)] + PACKED:
+        bpp = len(e.image(chans, rev)[0]) // w
+        img = render_host(sc, fmt_of(w, h, chans, rev=rev))
+        assert np.array_equal(img, e.image(chans, rev)), (name, int((img != e.image(chans, rev)).sum()))
+        fmt = fmt_of(w, h, chans, pitch=w * bpp + 7, rev=rev)
+        buf = bytearray(b"\xb3" * (fmt.pitch * h))
+        assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
+        got = np.frombuffer(bytes(buf), np.uint8).reshape(h, fmt.pitch)
+        assert np.array_equal(got[:, :w * bpp], e.image(chans, rev)), name
+        assert (got[:, w * bpp:] == 0xb3).all(), name
+    for rev in (False, True):
+        fmt = fmt_of(w, h, RGB24, pitch=3 * w + 5, rev=rev)
+        buf = torch.full((fmt.pitch * h + 16,), 0x5C, dtype=torch.uint8, device="cuda")
+        dest = buf[1:1 + fmt.pitch * h]
+        fst = fmt._as_struct()
+        _lib.check(_lib.lib().nt_render_device(sc._handle, C.c_void_p(dest.data_ptr()), fmt.pitch * h, C.byref(fst), None,
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        got = buf.cpu().numpy()
+        rows = got[1:1 + fmt.pitch * h].reshape(h, fmt.pitch)
+        assert np.array_equal(rows[:, :3 * w], e.image(RGB24, rev)), rev
+        assert (rows[:, 3 * w:] == 0x5C).all() and got[0] == 0x5C and (got[1 + fmt.pitch * h:] == 0x5C).all()
+
+
+# ------------------------------------------------------------------ 5. frames and chunking
+@pytest.mark.parametrize("which", ["box6", "feature5_n5"])
+def test_three_frames_equal_single_renders_whatever_the_chunking(which, monkeypatch):
+    """a frame of 203 x 117 takes 16 * 23 751 = 380 016 bytes of scratch: three fit the default cap and make one chunk, a cap of
+    1 MiB holds two, so the call is cut into chunks of two frames and one"""
+    import torch
+    s, nf = 2, 3
+    if which == "box6":
+        n, chans = 6, fx.RGBX8
+        cams = [ac.box_cameras(n)[k] for k in ac.BOX_CAMERAS]
+        sc = tracern.BoxScene(n)
+    else:
+        case = [c for c in ac.CASES if c[0] == which and not c[1]][0]
+        sc = composite_scene(case, monkeypatch)
+        n, chans = 5, fx.RGBF32
+        g = fx.load(which)
+        cams = [(g["origins"][f], g["axes"][f]) for f in (0, 1, 2)]
+    sc.set_supersampling(s)
+    sc.set_adaptive_supersampling(T)
+    fmt = fmt_of(W, H, chans)
+    singles = []
+    for o, a in cams:
+        sc._set_camera_arrays(o, a)
+        singles.append(render_host(sc, fmt))
+    if which == "box6":
+        for j, k in enumerate(ac.BOX_CAMERAS):
+            assert np.array_equal(singles[j], ac.box_expected(n, s, k).image(chans))
+    singles = np.stack(singles)
+    origins = np.ascontiguousarray(np.stack([c[0] for c in cams]), np.float32)
+    axes = np.ascontiguousarray(np.stack([c[1] for c in cams]), np.float32)
+    frame_bytes = fmt.pitch * H + 64
+    fst = fmt._as_struct()
+    stream = torch.cuda.current_stream().cuda_stream
+    table = CameraTable(n, origins, axes)
+    assert 2 * 16 * W * H <= 1 << 20 < 3 * 16 * W * H
+    for mib in (1024, 1):
+        sc.set_supersampling_scratch_mb(mib)
+        buf = torch.full((nf * frame_bytes,), 0x3D, dtype=torch.uint8, device="cuda")
+        assert table.render(sc, buf, fmt, frame_bytes=frame_bytes, first=0, count=nf)
+        torch.cuda.synchronize()
+        got = buf.cpu().numpy().reshape(nf, frame_bytes)
+        assert np.array_equal(got[:, :fmt.pitch * H].reshape(nf, H, fmt.pitch), singles), mib
+        assert (got[:, fmt.pitch * H:] == 0x3D).all()
+        buf.fill_(0x3D)
+        _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(buf.data_ptr()), frame_bytes, nf, origins.ctypes.data_as(_lib.f32p),
+                                                      axes.ctypes.data_as(_lib.f32p), C.byref(fst), None, C.c_void_p(stream)))
+        torch.cuda.synchronize()
+        got = buf.cpu().numpy().reshape(nf, frame_bytes)
+        assert np.array_equal(got[:, :fmt.pitch * H].reshape(nf, H, fmt.pitch), singles), mib
+        assert (got[:, fmt.pitch * H:] == 0x3D).all()
+        sc._set_camera_arrays(*cams[1])
+        assert np.array_equal(render_host(sc, fmt), singles[1])
+
+
+def test_a_frame_that_does_not_fit_the_scratch_cap_is_refused_before_anything_is_launched():
+    """300 x 300 pixels take 1 440 000 bytes: refused under a cap of 1 MiB with the destination untouched, drawn under the default"""
+    n, k, s, w, h = 6, 7, 2, 300, 300
+    sc = box_scene(n, k, s, T)
+    sc.set_supersampling_scratch_mb(1)
+    L = _lib.lib()
+    fmt = fmt_of(w, h, fx.RGBX8)
+    fst = fmt._as_struct()
+    dest = (C.c_char * (fmt.pitch * h))(*([0x4E] * (fmt.pitch * h)))
+    assert L.nt_render(sc._handle, dest, fmt.pitch * h, C.byref(fst), None, None) == _lib.NT_E_UNSUPPORTED
+    assert "adaptive" in _lib.last_error() and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error() and "1 MiB" in _lib.last_error()
+    assert bytes(dest) == b"\x4e" * (fmt.pitch * h)
+    with pytest.raises(NotImplementedError):
+        render_host(sc, fmt)
+    sc.set_supersampling_scratch_mb(1024)
+    e = ac.box_expected(n, s, k, T, w, h)
+    img = render_host(sc, fmt)
+    assert np.array_equal(img, e.image(fx.RGBX8)), int((img != e.image(fx.RGBX8)).sum())
+
+
+# ------------------------------------------------------------------ 6. the device path
+def test_a_torch_destination_and_a_device_mask_on_the_current_stream():
+    import torch
+    n, k, s = 6, 7, 2
+    sc = box_scene(n, k, s, T)
+    e = ac.box_expected(n, s, k)
+    fmt = fmt_of(W, H, fx.RGBX8)
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        buf = torch.zeros(fmt.pitch * H, dtype=torch.uint8, device="cuda")
+        assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
+        mask = sc.refinement_mask(W, H, device="cuda")
+    st.synchronize()
+    assert np.array_equal(buf.cpu().numpy().reshape(H, fmt.pitch), e.image(fx.RGBX8))
+    assert mask.dtype == torch.bool and tuple(mask.shape) == (H, W) and mask.is_cuda
+    assert np.array_equal(mask.cpu().numpy(), e.mask)
+
+
+def test_an_adaptive_table_call_is_still_capturable():
+    """after a warm-up call of the same shape nt_render_table_device only enqueues -- no read-back, no allocation -- also with
+    the threshold on and the call cut into two chunks: captured into a HIP graph on one stream and replayed, it gives the
+    direct call's bytes"""
+    import torch
+    n, s, nf = 6, 2, 3
+    st = torch.cuda.Stream()
+    cams = [ac.box_cameras(n)[k] for k in ac.BOX_CAMERAS]
+    origins = np.ascontiguousarray(np.stack([c[0] for c in cams]), np.float32)
+    axes = np.ascontiguousarray(np.stack([c[1] for c in cams]), np.float32)
+    fmt = fmt_of(W, H, fx.RGBX8)
+    fst = fmt._as_struct()
+    sc = tracern.BoxScene(n)
+    sc.set_supersampling(s)
+    sc.set_adaptive_supersampling(T)
+    sc.set_supersampling_scratch_mb(1)
+    tab = CameraTable(n, origins, axes)
+    ref = torch.zeros((nf, H * fmt.pitch), dtype=torch.uint8, device="cuda")
+    fb = torch.zeros_like(ref)
+
+    def call(buf):
+        return _lib.lib().nt_render_table_device(sc._handle, C.c_void_p(buf.data_ptr()), H * fmt.pitch, tab._h, 0, nf, C.byref(fst), None,
+                                                 C.c_void_p(st.cuda_stream))
+    with torch.cuda.stream(st):
+        _lib.check(call(ref))
+    st.synchronize()
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr, stream=st):
+        _lib.check(call(fb))
+    for rep in range(2):
+        fb.zero_()
+        torch.cuda.synchronize()
+        gr.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(fb, ref), rep
+    del gr
+    for j, k in enumerate(ac.BOX_CAMERAS):
+        assert np.array_equal(ref[j].cpu().numpy().reshape(H, fmt.pitch), ac.box_expected(n, s, k).image(fx.RGBX8)), k
+
+
+def test_an_abort_word_raised_before_the_call_and_the_refusals_draw_nothing(monkeypatch):
+    import torch
+    L = _lib.lib()
+    case = ac.CASES[0]
+    sc = composite_scene(case, monkeypatch)
+    sc.set_supersampling(2)
+    sc.set_adaptive_supersampling(T)
+    fmt = fmt_of(W, H, fx.RGBX8)
+    fst = fmt._as_struct()
+    size = fmt.pitch * H
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    # the host flag is already up: NT_ABORTED, nothing drawn
+    dest = (C.c_char * size)(*([0x6A] * size))
+    flag = C.c_int(1)
+    assert L.nt_render(sc._handle, dest, size, C.byref(fst), None, C.byref(flag)) == _lib.NT_ABORTED
+    assert bytes(dest) == b"\x6a" * size
+    # an abort word that is set before the call: the blocks of all three stages leave when they start
+    word = torch.ones(1, dtype=torch.int32, device="cuda")
+    buf = torch.full((size,), 0x6A, dtype=torch.uint8, device="cuda")
+    mask = torch.full((W * H,), 0x6A, dtype=torch.uint8, device="cuda")
+    opts = _lib.NtRenderOpts()
+    opts.device = -1
+    opts.abort_device = word.data_ptr()
+    torch.cuda.synchronize()
+    _lib.check(L.nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), C.byref(opts), stream))
+    _lib.check(L.nt_adaptive_mask_device(sc._handle, W, H, C.c_void_p(mask.data_ptr()), C.byref(opts), stream))
+    torch.cuda.synchronize()
+    assert bool((buf == 0x6A).all()) and bool((mask == 0x6A).all())
+    word.zero_()
+    torch.cuda.synchronize()
+    _lib.check(L.nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), C.byref(opts), stream))
+    torch.cuda.synchronize()
+    assert np.array_equal(buf.cpu().numpy().reshape(H, fmt.pitch), render_host(sc, fmt))
+    # what the setting refuses leaves the destination as it was
+    buf.fill_(0x6A)
+    for field in ("band_world", "collect_stats"):
+        opts = _lib.NtRenderOpts()
+        opts.device = -1
+        setattr(opts, field, 2 if field == "band_world" else 1)
+        assert L.nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), C.byref(opts), stream) == _lib.NT_E_UNSUPPORTED
+        assert "adaptive" in _lib.last_error()
+        assert L.nt_render(sc._handle, dest, size, C.byref(fst), C.byref(opts), None) == _lib.NT_E_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((buf == 0x6A).all()) and bytes(dest) == b"\x6a" * size
+    with pytest.raises(NotImplementedError, match="adaptive"):
+        render_host(sc, fmt, band_rank=0, band_world=2)
+    with pytest.raises(NotImplementedError, match="adaptive"):
+        render_host(sc, fmt, collect_stats=True)
+    # the probes, the primary hits and the caller's rays ignore the setting, as they ignore the factor: a scene with both set
+    # answers as one with neither
+    n, flat, params, o, a, osc = ac.case_oracle(case)
+    rng = np.random.default_rng(3)
+    xs, ys = rng.integers(0, W, 100), rng.integers(0, H, 100)
+    plain = composite_scene(case, monkeypatch)
+    assert sc.adaptive_supersampling == float(np.float32(T)) and sc.supersampling == 2 and plain.adaptive_supersampling is None
+    assert np.array_equal(sc.colors_at(xs, ys, W, H).view(np.uint32), plain.colors_at(xs, ys, W, H).view(np.uint32))
+    assert np.abs(sc.colors_at(xs, ys, W, H) - osc.colors_at(xs, ys, W, H)).max() <= TOL_ORACLE
+    assert tuple(sc.calculate_color(int(xs[0]), int(ys[0]), W, H)) == tuple(plain.calculate_color(int(xs[0]), int(ys[0]), W, H))
+    got, want = sc.primary_hits(W, H, normals=True), plain.primary_hits(W, H, normals=True)
+    assert np.array_equal(got.hits, want.hits) and (got.item >= 0).sum() > 1000
+    assert np.array_equal(got.normal_dir.view(np.uint32), want.normal_dir.view(np.uint32))
+    import ray_color_cases as rc
+    dirs = rc.camera_rays(a, xs, ys, W, H)
+    assert np.array_equal(sc.ray_colors(o, dirs).view(np.uint32), plain.ray_colors(o, dirs).view(np.uint32))
+    assert np.abs(sc.ray_colors(o, dirs) - osc.colors_at(xs, ys, W, H)).max() <= TOL_ORACLE
+    small = fmt_of(10, 10, fx.RGBX8)
+    images = []
+    for scene in (sc, plain):
+        img = bytearray(small.pitch * 10)
+        assert scene.render_rays(img, small, o, dirs)
+        images.append(bytes(img))
+    assert images[0] == images[1] and len(set(images[0])) > 4
