@@ -232,6 +232,39 @@ int nt_scene_get_adaptive_supersampling(const nt_scene_t *s, int *enabled, float
    NT_E_UNSUPPORTED for bands or collect_stats in `opts`, and while a lens or the parallel projection is set. */
 int nt_adaptive_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *flagged, const nt_render_opts *opts);
 int nt_adaptive_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream);
+/* Ambient occlusion: a view setting of a CompositeScene, off by default, that darkens a pixel by how enclosed its primary hit is.
+   count = K (1..256) samples, `directions` a [K][n] table (every component finite, no row all zero, rows used as given, not
+   normalised), radius > 0, bias >= 0, strength in [0, 1]; count = 0 takes it off.  Everything below is fp32 without contraction,
+   dot products summed left to right.
+   The blocked count of pixel (x, y) of a W x H view rests on the record nt_primary_hits defines for that pixel, normal_origin = no
+   and normal_dir = nd included.  Without an opaque hit blocked = -1.  Otherwise, with d the primary ray's unit direction,
+   side = -dot(d, nd), b = side < 0 ? -bias : bias, o'[j] = no[j] + nd[j] * b; for k = 0..K-1, s = dot(nd, t_k) and
+   v = ((s < 0) != (side < 0)) ? -t_k : t_k; sample k is blocked iff the closest-hit walk nt_intersect_rays defines -- origin o',
+   direction v, t_near = 0, t_far = radius, (skip_item, skip_lane) the primary hit's (item, lane), strict_reference and the
+   NTRACER_* switches as for a query on this scene -- answers item >= 0 && dist <= radius.  The radius is thus in units of |t_k|;
+   transparent surfaces do not block; blocked is the number of blocked samples.
+   A render with the setting on: P the plain single-sample frame with each component clamped to [0, 1], a = (float)blocked / (float)K
+   (0 for blocked = -1), f = 1.0f - strength * a, and the pixel is (P.r * f, P.g * f, P.b * f) through the format's conversion
+   and packing as always: with strength = 0, or where nothing blocks, the plain frame byte for byte.  nt_render, nt_render_device,
+   nt_render_frames_device and nt_render_table_device honour the setting and refuse with NT_E_UNSUPPORTED ("ambient occlusion
+   ...") before a device is touched, drawing nothing: a supersampling factor above 1, row bands (band_world > 1),
+   collect_stats, a lens, the parallel projection (and a row range, which only a caller inside the library can ask for).  nt_colors_at / nt_calculate_color, nt_primary_hits*, nt_ray_colors*,
+   nt_render_rays* and the ray queries ignore it.  All of it runs on the device under the cap of
+   nt_scene_set_supersampling_scratch_mb: 32 + 8 n bytes a pixel a frame, and for scenes with transparent materials, Solids with the
+   reference's normals, n > 10 or NTRACER_FORCE_VAR=1 also 8 n + 32 bytes a ray of a chunk of whole pixel rows; larger jobs are cut
+   into chunks of whole frames, and a single frame (with one row of rays) that does not fit fails with NT_E_UNSUPPORTED before
+   anything is launched.  Not part of a pickled scene.  NT_E_INVALID for a BoxScene, a count outside 0..256, NULL directions with
+   count > 0, a non-finite or all-zero row, a radius that is not positive and finite, a negative or non-finite bias, a strength
+   outside [0, 1] (the setting stays as it was); NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it;
+   the getter writes through whichever pointers are not NULL, the table ([count][n] floats) included. */
+int nt_scene_set_ambient_occlusion(nt_scene_t *s, int count, const float *directions, float radius, float bias, float strength);
+int nt_scene_get_ambient_occlusion(const nt_scene_t *s, int *count, float *directions, float *radius, float *bias, float *strength);
+/* The blocked counts of a width x height view of the scene's current camera, blocked[y * width + x].  The host form holds the
+   scene like nt_colors_at and reads device and strict_reference of `opts`.  The device form writes exactly width * height dwords of
+   device memory at blocked_dev and is only enqueued on hip_stream; it also reads abort_device, and every other field of `opts`
+   must be 0.  NT_E_INVALID when the setting is off; NT_E_UNSUPPORTED while a lens or the parallel projection is set. */
+int nt_ambient_occlusion(nt_scene_t *s, int width, int height, int32_t *blocked, const nt_render_opts *opts);
+int nt_ambient_occlusion_device(nt_scene_t *s, int width, int height, void *blocked_dev, const nt_render_opts *opts, void *hip_stream);
 /* CompositeScene.set_shadows/set_camera_light/set_max_reflect_depth/set_ambient_color/
    set_background/add_light rolled into one call */
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p);

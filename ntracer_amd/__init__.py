@@ -7,8 +7,8 @@ libntracer_hip.so (include/ntracer_hip.h); there is no CPU fallback.
 """
 from .render import (BlockingRenderer, CallbackRenderer, Channel, Color, ImageFormat, LockedError, Material,  # noqa: F401
                      Scene)
-from .tracern import CUBE, SPHERE, Lens  # noqa: F401
+from .tracern import CUBE, SPHERE, Lens, sphere_directions  # noqa: F401
 from .wrapper import NTracer  # noqa: F401
 
 __all__ = ["NTracer", "Material", "ImageFormat", "Channel", "BlockingRenderer", "CallbackRenderer", "Color",
-           "LockedError", "Scene", "CUBE", "SPHERE", "Lens"]
+           "LockedError", "Scene", "CUBE", "SPHERE", "Lens", "sphere_directions"]

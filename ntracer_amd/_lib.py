@@ -136,6 +136,10 @@ SYMBOLS = [
     ("nt_scene_get_adaptive_supersampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     ("nt_adaptive_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
     ("nt_adaptive_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_scene_set_ambient_occlusion", C.c_int, [C.c_void_p, C.c_int, f32p, C.c_float, C.c_float, C.c_float]),
+    ("nt_scene_get_ambient_occlusion", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p, f32p, f32p]),
+    ("nt_ambient_occlusion", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),
+    ("nt_ambient_occlusion_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_set_params", C.c_int, [C.c_void_p, C.POINTER(NtSceneParams)]),
     ("nt_scene_lock", C.c_int, [C.c_void_p]),
     ("nt_scene_unlock", C.c_int, [C.c_void_p]),

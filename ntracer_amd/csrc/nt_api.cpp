@@ -104,8 +104,12 @@ struct DeviceState {
     DevBuf hits;                         // primary-hit records between the two passes of a lit render
     DevBuf stats_frame;                  // where the statistics launch of a "faithful" scene draws (discarded)
     DevBuf samples;                      // supersampling: the fp32 x 3 samples between the render and the resolve kernel; adaptive
-                                         // supersampling: the base frame, the list of flagged pixels and the host forms' mask
+                                         // supersampling: the base frame, the list of flagged pixels and the host forms' mask;
+                                         // ambient occlusion: the hit records, both normal rows, the base frame and the counts
+                                         // of a chunk of frames, and on the ray route the ray arrays and answers of a chunk of rows
     DevBuf refine_count;                 // adaptive supersampling: the length of that list
+    DevBuf ao_dirs;                      // ambient occlusion: the table of directions
+    unsigned long long ao_version = 0;
     DevBuf numer;                        // packet kernel: -(N.o + d) per (frame, simplex)
     DevBuf cull;                         // BoxScene: row culling bits
     bool cull_clean = false;             // `cull` is all zero (what the fused BoxScene path needs and leaves behind)
@@ -174,6 +178,10 @@ struct nt_scene {
     std::vector<float> origin, axes;     // camera<Store>: origin[n], t_orientation[n][n] (camera.hpp:7-15)
     std::shared_ptr<NtLensData> lens;    // not null: the renders' ray source (nt_scene_set_lens); fov is then ignored
     float parallel = 0.0f;               // > 0: the parallel projection's half_width (nt_scene_set_parallel); excludes a lens
+    int ao_count = 0;                    // > 0: ambient occlusion with that many samples a pixel (nt_scene_set_ambient_occlusion)
+    std::vector<float> ao_dirs;          // ... their directions [ao_count][n], used as given
+    float ao_radius = 0.0f, ao_bias = 0.0f, ao_strength = 0.0f;
+    unsigned long long ao_version = 1;   // counts the changes of ao_dirs
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -411,6 +419,14 @@ int upload_scene(nt_scene *s, DeviceState *ds) {
         if (ds->lights.p) { (void)hipDeviceSynchronize(); ds->lights.release(); }
         ds->lights = fresh;
         ds->lights_version = s->lights_version;
+    }
+    if (s->ao_count > 0 && ds->ao_version != s->ao_version) {
+        // (a fresh allocation, as for the lights)
+        DevBuf fresh;
+        if (int r = upload(fresh, s->ao_dirs)) return r;
+        if (ds->ao_dirs.p) { (void)hipDeviceSynchronize(); ds->ao_dirs.release(); }
+        ds->ao_dirs = fresh;
+        ds->ao_version = s->ao_version;
     }
     return NT_OK;
 }
@@ -1064,6 +1080,178 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 }
 
 // ---------------------------------------------------------------------------------------------
+// ambient occlusion (nt_scene_set_ambient_occlusion; kernels in nt_ao.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_hit_buffers *out, long long frame_stride, const float *cam_buf,
+                 int nframes, bool strict, const int *abort_word, hipStream_t stream);
+int query_enqueue(nt_scene *s, DeviceState *ds, NtQuery &q, bool strict, hipStream_t stream);
+
+// What a render with the setting on refuses, checked by the entry points before a device is touched (and by enqueue_ao again, for
+// every way in): the counts come from a primary-hit pass of the whole pinhole view, one sample a pixel, and no kernel of it
+// keeps counters.  The entry points hand over whole images: without bands their owned rows are all of them, so the row-range
+// answer cannot be reached through the ABI; it guards enqueue_ao against callers within this file that split a job into rows
+int ao_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
+    if (s->ao_count <= 0) return NT_OK;
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available with a supersampling factor above 1 (%d)", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available with row bands (band_world %d)", b.world);
+    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available for a row range");
+    if (stats) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available with collect_stats");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available while the parallel projection is set");
+    return NT_OK;
+}
+
+// The blocked counts of every pixel of the job's frames and, with job.fmt, the render that uses them, per chunk of whole frames:
+// the plain fp32 x 3 base frame into scratch (a render only), a primary-hit pass with normals into scratch (hits_enqueue: every
+// route of it), the counts -- ao_kernel for the opaque scenes the fixed-n kernels draw, else ao_expand, the closest-hit query
+// launch and ao_reduce over chunks of whole pixel rows --, and ao_apply into the caller's image.  Without job.fmt the view is
+// job.view_w x job.view_h, one frame, and the counts go to `blocked_dev`, or with that nullptr stay in scratch: *blocked_out.
+// The scratch -- per pixel and frame 16 bytes of record, 8 n of normal rows, 12 of base frame and 4 of count; on the ray route
+// 8 n + 32 bytes a ray of a chunk behind them -- sits under the supersampling cap.  Enqueue only.
+int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, int *blocked_dev, int **blocked_out) {
+    const bool draw = job.fmt != nullptr;
+    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
+    if (int r = ao_check(s, job.bands, job.stats, draw ? job.row_begin : 0, draw ? job.row_count : H, H)) return r;
+    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const int n = s->n, K = s->ao_count;
+    const long long px = (long long)W * H;
+    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const long long per_frame = px * (16 + 8 * n + 12 + 4);
+    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
+    if (per_frame > cap)
+        return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d x %d image: the base frame, the hit records, the normal rows and the counts of one "
+                    "frame (%lld bytes) do not fit the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    const bool var = n > NT_MAX_FIXED_DIM || sw.force_var;
+    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);        // (hits_enqueue's terms)
+    const bool fast = !faithful && !var;
+    long long chunk_frames = std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame), INT_MAX / px));
+    // the ray route: the rays of whole pixel rows behind the frames, 16-byte aligned
+    const long long row_bytes = (long long)W * K * (8 * n + 32);
+    long long chunk_rows = 0;
+    if (!fast) {
+        chunk_frames = std::min(chunk_frames, (cap - 16 - row_bytes) / per_frame);
+        if (chunk_frames < 1)
+            return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d x %d image with %d samples: one frame (%lld bytes) and the rays of one pixel row "
+                        "(%lld bytes) do not fit the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, K, per_frame, row_bytes, cap >> 20);
+        chunk_rows = std::min<long long>(std::min<long long>((cap - 16 - chunk_frames * per_frame) / row_bytes, chunk_frames * H), INT_MAX / ((long long)W * K));
+        if (chunk_rows < 1) return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d pixel wide image with %d samples: beyond 2^31 - 1 rays a pixel row", W, K);
+    }
+    if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame + (fast ? 0 : 16 + chunk_rows * row_bytes)))) return e;
+    const size_t fpx = (size_t)chunk_frames * px;
+    char *at = (char *)ds->samples.p;
+    void *recs = at; at += fpx * 16;
+    float *no = (float *)at; at += fpx * n * 4;
+    float *nd = (float *)at; at += fpx * n * 4;
+    char *base = at; at += fpx * 12;
+    int *counts = (int *)at; at += fpx * 4;
+    char *rays = (char *)(((uintptr_t)at + 15) & ~(uintptr_t)15);
+    if (!draw && blocked_dev) counts = blocked_dev;
+    if (blocked_out) *blocked_out = counts;
+    NtTarget tg;
+    if (draw) {
+        if (int r = fill_target(s, ds, job, tg)) return r;
+    } else {
+        std::memset(&tg, 0, sizeof(tg));
+        fill_view(tg, s, W, H);
+        tg.band_world = 1;
+        tg.band_rows = NT_RENDER_CHUNK_SIZE;
+        tg.row_count = H;
+        tg.abort_word = job.abort_word;
+    }
+    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
+    const nt_image_format base_desc = {(int32_t)W, (int32_t)H, 0, 3, plain, 0};
+    Format bf;
+    if (int r = parse_format(&base_desc, bf)) return r;
+    for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
+        const int nf = std::min((int)chunk_frames, job.nframes - f0);
+        const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
+        if (draw) {
+            FrameJob bj = job;
+            bj.samples_pass = true;
+            bj.fmt = &bf;
+            bj.bands = Bands();
+            bj.bands.owned_rows = H;
+            bj.row_begin = 0;
+            bj.row_count = H;
+            bj.nframes = nf;
+            bj.frame_stride = (size_t)px * 12;
+            bj.dest_dev = base;
+            bj.stats = false;
+            if (job.cam_buf) {
+                bj.cam_buf = cams;
+                bj.cam_dots = job.cam_dots + (size_t)f0 * 4;
+            }
+            if (int e = enqueue(s, ds, bj)) return e;
+        }
+        nt_hit_buffers hb{};
+        hb.hits = (nt_ray_hit *)recs;
+        hb.normal_origin = no;
+        hb.normal_dir = nd;
+        if (int e = hits_enqueue(s, ds, W, H, &hb, px, cams, nf, job.strict, job.abort_word, job.stream)) return e;
+        NtAo ao{};
+        ao.cams = cams ? cams : (const float *)ds->cams.p;              // (hits_enqueue has put the scene's own camera there)
+        ao.nframes = nf;
+        ao.recs = recs;
+        ao.normal_origin = no;
+        ao.normal_dir = nd;
+        ao.dirs = (const float *)ds->ao_dirs.p;
+        ao.count = K;
+        ao.radius = s->ao_radius;
+        ao.bias = s->ao_bias;
+        ao.blocked = counts;
+        NtLaunchInfo li{};
+        li.n = n;
+        li.nframes = nf;
+        li.stream = job.stream;
+        li.cu_count = ds->cu_count;
+        li.force_var = sw.force_var;
+        if (fast) {
+            NtCompositeDev c;
+            fill_composite(s, ds, c, false);
+            c.prune = (job.strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as query_enqueue has it)
+            if (c.root < 0) c.root = -1;
+            const int r = nt_launch_ao(li, c, tg, ao);
+            if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        } else {
+            const long long rows = (long long)nf * H;
+            for (long long r0 = 0; r0 < rows; r0 += chunk_rows) {
+                NtAoRays ar{};
+                ar.first = r0 * W;
+                ar.pixels = std::min(chunk_rows, rows - r0) * W;
+                const size_t nr = (size_t)ar.pixels * K;
+                char *q0 = rays;
+                ar.results = q0; q0 += nr * 16;
+                ar.origins = (float *)q0; q0 += nr * n * 4;
+                ar.directions = (float *)q0; q0 += nr * n * 4;
+                ar.t_near = (float *)q0; q0 += nr * 4;
+                ar.t_far = (float *)q0; q0 += nr * 4;
+                ar.skip_item = (int *)q0; q0 += nr * 4;
+                ar.skip_lane = (int *)q0;
+                if (nt_launch_ao_expand(li, tg, ao, ar)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+                NtQuery q{};
+                q.count = (int)nr;
+                q.origins = ar.origins;
+                q.directions = ar.directions;
+                q.t_near = ar.t_near;
+                q.t_far = ar.t_far;
+                q.skip_item = ar.skip_item;
+                q.skip_lane = ar.skip_lane;
+                q.hits = (void *)ar.results;
+                q.abort_word = job.abort_word;
+                if (int e = query_enqueue(s, ds, q, job.strict, job.stream)) return e;
+                if (nt_launch_ao_reduce(li, tg, ao, ar)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            }
+        }
+        if (draw) {
+            NtTarget ft = tg;
+            ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+            if (nt_launch_ao_apply(job.stream, (const uint32_t *)base, counts, K, s->ao_strength, nf, ft)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+        }
+    }
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // renders through a lens (nt_scene_set_lens; kernels in nt_lens.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1285,6 +1473,8 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
+    if (s->ao_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
+        return enqueue_ao(s, ds, job, sw, nullptr, nullptr);
     if (s->lens) return enqueue_lens(s, ds, job, sw);
     if (s->parallel > 0.0f) return enqueue_parallel(s, ds, job, sw);
     if (s->supersampling > 1 && s->adaptive && !job.colors_out && !job.samples_pass && !job.counters_pass)
@@ -2187,6 +2377,47 @@ int nt_scene_get_adaptive_supersampling(const nt_scene_t *s, int *enabled, float
     return NT_OK;
 }
 
+int nt_scene_set_ambient_occlusion(nt_scene_t *s, int count, const float *directions, float radius, float bias, float strength) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no ambient occlusion");
+    if (count < 0 || count > 256) return fail(NT_E_INVALID, "the number of ambient occlusion samples must be between 0 and 256");
+    if (count > 0) {
+        if (!directions) return fail(NT_E_INVALID, "the ambient occlusion directions are NULL");
+        for (int k = 0; k < count; ++k) {
+            bool zero = true;
+            for (int j = 0; j < s->n; ++j) {
+                const float v = directions[(size_t)k * s->n + j];
+                if (!std::isfinite(v)) return fail(NT_E_INVALID, "ambient occlusion direction %d has a component that is not finite", k);
+                zero = zero && v == 0.0f;
+            }
+            if (zero) return fail(NT_E_INVALID, "ambient occlusion direction %d is all zero", k);
+        }
+        if (!(radius > 0.0f) || !std::isfinite(radius)) return fail(NT_E_INVALID, "the ambient occlusion radius must be positive and finite");
+        if (!(bias >= 0.0f) || !std::isfinite(bias)) return fail(NT_E_INVALID, "the ambient occlusion bias must be finite and not negative");
+        if (!(strength >= 0.0f && strength <= 1.0f)) return fail(NT_E_INVALID, "the ambient occlusion strength must lie in [0, 1]");
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->ao_count = count;
+    if (count > 0) s->ao_dirs.assign(directions, directions + (size_t)count * s->n);
+    else s->ao_dirs.clear();
+    s->ao_radius = count > 0 ? radius : 0.0f;
+    s->ao_bias = count > 0 ? bias : 0.0f;
+    s->ao_strength = count > 0 ? strength : 0.0f;
+    ++s->ao_version;
+    return NT_OK;
+}
+
+int nt_scene_get_ambient_occlusion(const nt_scene_t *s, int *count, float *directions, float *radius, float *bias, float *strength) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (count) *count = s->ao_count;
+    if (directions && s->ao_count > 0) std::memcpy(directions, s->ao_dirs.data(), s->ao_dirs.size() * sizeof(float));
+    if (radius) *radius = s->ao_radius;
+    if (bias) *bias = s->ao_bias;
+    if (strength) *strength = s->ao_strength;
+    return NT_OK;
+}
+
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");
     if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no lighting parameters");
@@ -2244,6 +2475,7 @@ int nt_render(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format 
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
+    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
@@ -2327,6 +2559,7 @@ int nt_render_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_im
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
@@ -2366,6 +2599,7 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
@@ -2474,6 +2708,7 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
     if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
     if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
@@ -2569,6 +2804,69 @@ int nt_adaptive_mask_device(nt_scene_t *s, int width, int height, void *mask_dev
     job.row_count = height;
     job.bands.owned_rows = height;
     return enqueue_adaptive(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
+}
+
+namespace {
+// what both forms of nt_ambient_occlusion check before a device is touched
+int ao_validate(const nt_scene *s, int width, int height, const void *blocked) {
+    if (!s || !blocked) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (s->ao_count <= 0) return fail(NT_E_INVALID, "ambient occlusion is off (nt_scene_set_ambient_occlusion)");
+    if (s->lens || s->parallel > 0.0f)
+        return fail(NT_E_UNSUPPORTED, "the ambient occlusion counts are not available while a lens or the parallel projection is set");
+    return check_renderable(s);
+}
+}  // namespace
+
+int nt_ambient_occlusion(nt_scene_t *s, int width, int height, int32_t *blocked, const nt_render_opts *opts) {
+    if (int r = ao_validate(s, width, height, blocked)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = own_stream(ds)) return r;
+    if (int r = use_stream(ds, ds->stream)) return r;
+    FrameJob job{};
+    job.nframes = 1;
+    job.stream = ds->stream;
+    job.strict = opts && opts->strict_reference;
+    job.view_w = width;
+    job.view_h = height;
+    job.row_count = height;
+    job.bands.owned_rows = height;
+    int *counts = nullptr;
+    if (int r = enqueue_ao(s, ds, job, read_switches(), nullptr, &counts)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    HIP_TRY(hipMemcpyAsync(blocked, counts, (size_t)width * height * sizeof(int32_t), hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipStreamSynchronize(ds->stream));
+    return NT_OK;
+}
+
+int nt_ambient_occlusion_device(nt_scene_t *s, int width, int height, void *blocked_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = ao_validate(s, width, height, blocked_dev)) return r;
+    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
+        return fail(NT_E_INVALID, "the ambient occlusion counts read device, strict_reference and abort_device of their options: every other field must be 0");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    int dev;
+    if (int r = pick_device(opts, -1, dev)) return r;
+    DeviceState *ds;
+    if (int r = device_state(s, dev, ds)) return r;
+    if (int r = upload_scene(s, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    FrameJob job{};
+    job.nframes = 1;
+    job.stream = (hipStream_t)hip_stream;
+    job.strict = opts && opts->strict_reference;
+    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
+    job.view_w = width;
+    job.view_h = height;
+    job.row_count = height;
+    job.bands.owned_rows = height;
+    return enqueue_ao(s, ds, job, read_switches(), (int *)blocked_dev, nullptr);
 }
 
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {

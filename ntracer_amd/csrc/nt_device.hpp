@@ -276,6 +276,28 @@ struct NtRefine {
     float half_w, half_h, fovI;   // the s * width x s * height view (fill_view)
 };
 
+// Ambient occlusion (nt_ao.hpp, nt_var.hip): K short rays from the primary hit of every pixel, counted.  Every
+// pointer is device memory; a pixel's index is frame * height * width + y * width + x, frames counted within the launch, and its
+// hit record and normal rows (a primary-hit pass with normals, NtHits) lie at that index.
+struct NtAo {
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    int nframes;
+    const void *recs;         // the pixels' 16-byte hit records
+    const float *normal_origin, *normal_dir;   // [pixel][n]; rows of pixels without an opaque hit are never read
+    const float *dirs;        // the setting's table, [count][n], used as given
+    int count;                // K
+    float radius, bias;
+    int *blocked;             // [pixel]: -1 without an opaque hit, else the number of blocked samples
+};
+// the ray route's arrays for pixels [first, first + pixels): pixels * K rays, ray k of pixel i at i * K + k
+struct NtAoRays {
+    long long first, pixels;
+    float *origins, *directions;          // [pixels * K][n]
+    float *t_near, *t_far;                // [pixels * K]
+    int *skip_item, *skip_lane;           // [pixels * K]
+    const void *results;                  // [pixels * K] 16-byte records, what the closest-hit query wrote
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
@@ -312,6 +334,15 @@ int nt_launch_adaptive_flag(void *stream, const NtAdaptive &ad, const NtTarget &
 // the refine kernels: the scene as for nt_launch_rays (sc == nullptr: BoxScene; sc->checked / sc->tframes with lane columns for
 // blocks of 64 lanes); tg is the whole image the list's pixels belong to
 int nt_launch_refine(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRefine &rf, const NtTarget &tg);
+// ambient occlusion, fast route: ao_kernel<N, SCALP> of the scene's dimension (opaque scenes the fixed-n kernels draw); tg is
+// the view and the abort word
+int nt_launch_ao(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao);
+// ... and the ray route's two kernels around nt_launch_query (run-time n): the rays of a chunk of pixels, and their counts
+int nt_launch_ao_expand(const NtLaunchInfo &li, const NtTarget &tg, const NtAo &ao, const NtAoRays &ar);
+int nt_launch_ao_reduce(const NtLaunchInfo &li, const NtTarget &tg, const NtAo &ao, const NtAoRays &ar);
+// ao_apply: the base frame (NtAdaptive::base's layout) times 1 - strength * blocked / K into tg.dest, the whole image of
+// `nframes` frames (no bands)
+int nt_launch_ao_apply(void *stream, const uint32_t *base, const int *blocked, int count, float strength, int nframes, const NtTarget &tg);
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count);
 int nt_var_frame_words(int n);   // floats per ray_color frame of composite_kernel_var_t
 const char *nt_launch_error();

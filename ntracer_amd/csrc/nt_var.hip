@@ -38,6 +38,9 @@ NT_DECLARE_LENS(3) NT_DECLARE_LENS(4) NT_DECLARE_LENS(5) NT_DECLARE_LENS(6) NT_D
 // the packet route of a render under the parallel projection (nt_inst_parallel.hip)
 #define NT_DECLARE_PARALLEL(N) int nt_parallel_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl);
 NT_DECLARE_PARALLEL(3) NT_DECLARE_PARALLEL(4) NT_DECLARE_PARALLEL(5) NT_DECLARE_PARALLEL(6) NT_DECLARE_PARALLEL(7) NT_DECLARE_PARALLEL(8) NT_DECLARE_PARALLEL(9) NT_DECLARE_PARALLEL(10)
+// the ambient occlusion kernel (nt_inst_ao.hip)
+#define NT_DECLARE_AO(N) int nt_ao_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao);
+NT_DECLARE_AO(3) NT_DECLARE_AO(4) NT_DECLARE_AO(5) NT_DECLARE_AO(6) NT_DECLARE_AO(7) NT_DECLARE_AO(8) NT_DECLARE_AO(9) NT_DECLARE_AO(10)
 // (BoxScene alone: 11..24)
 int nt_box_fixed_14(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_box_fixed_15(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
@@ -2015,6 +2018,105 @@ __global__ __launch_bounds__(256) void parallel_expand(const float *cam, int n, 
 }
 
 // --------------------------------------------------------------------------------------
+// Ambient occlusion (nt_ao.hpp) on the closest-hit query kernels above: every scene ao_kernel does not take.
+// ao_expand writes the K rays of pixels [first, first + pixels) of the launch -- one lane a ray, ray k of pixel i at i * K + k,
+// run-time n, the blocks striding -- from the pixel's record and normal rows: origin o' = no + nd * b, direction +-t_k, the window
+// [0, radius] and the primary hit as the skip target, by ao_kernel's operations in ao_kernel's order (d is primary_dir's, formed
+// on the fly: the same operands give the same bits twice).  A pixel without an opaque hit gets rays with an inverted window,
+// which end in the first leaf they reach and whose answers nobody reads.  The query launch then answers all of them, and
+// ao_reduce, one lane a pixel, counts item >= 0 && dist <= radius over each K records.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ao_expand(NtTarget tg, NtAo ao, NtAoRays ar, int n) {
+    const long long rays = ar.pixels * ao.count;
+    const long long per_frame = (long long)tg.width * tg.height;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rays; i += (long long)gridDim.x * 256) {
+        const long long pl = i / ao.count;
+        const int k = (int)(i - pl * ao.count);
+        const long long pix = ar.first + pl;
+        const int4 rec = reinterpret_cast<const int4 *>(ao.recs)[pix];
+        const float *t = ao.dirs + (size_t)k * n;
+        float *o = ar.origins + i * n, *v = ar.directions + i * n;
+        ar.t_near[i] = 0.0f;
+        if (rec.y < 0) {
+            for (int j = 0; j < n; ++j) { o[j] = 0.0f; v[j] = t[j]; }
+            ar.t_far[i] = -1.0f;
+            ar.skip_item[i] = -1;
+            ar.skip_lane[i] = -1;
+            continue;
+        }
+        const int frame = (int)(pix / per_frame);
+        const int rem = (int)(pix - (long long)frame * per_frame);
+        const int y = rem / tg.width, x = rem - y * tg.width;
+        const float *c = ao.cams + (size_t)frame * 4 * n;
+        const float sx = tg.fovI * ((float)x - tg.half_w);
+        const float sy = tg.fovI * ((float)y - tg.half_h);
+        float sq = 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const float u = (c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy;
+            sq = j == 0 ? u * u : sq + u * u;
+        }
+        const float len = sqrtf(sq);
+        const float *no = ao.normal_origin + pix * n, *nd = ao.normal_dir + pix * n;
+        float dn = 0.0f, s = 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const float dj = ((c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy) / len;
+            dn = j == 0 ? dj * nd[j] : dn + dj * nd[j];
+            s = j == 0 ? nd[j] * t[j] : s + nd[j] * t[j];
+        }
+        const float side = -dn;
+        const float b = side < 0.0f ? -ao.bias : ao.bias;
+        const bool flip = (s < 0.0f) != (side < 0.0f);
+        for (int j = 0; j < n; ++j) {
+            o[j] = no[j] + nd[j] * b;
+            v[j] = flip ? -t[j] : t[j];
+        }
+        ar.t_far[i] = ao.radius;
+        ar.skip_item[i] = rec.y;
+        ar.skip_lane[i] = rec.z;
+    }
+}
+
+__global__ __launch_bounds__(256) void ao_reduce(NtTarget tg, NtAo ao, NtAoRays ar) {
+    if (nt_aborted(tg)) return;
+    for (long long pl = (long long)blockIdx.x * 256 + threadIdx.x; pl < ar.pixels; pl += (long long)gridDim.x * 256) {
+        const long long pix = ar.first + pl;
+        int blocked = -1;
+        if (reinterpret_cast<const int4 *>(ao.recs)[pix].y >= 0) {
+            const int4 *r = reinterpret_cast<const int4 *>(ar.results) + pl * ao.count;
+            blocked = 0;
+            for (int k = 0; k < ao.count; ++k) {
+                const int4 e = r[k];
+                if (e.y >= 0 && __int_as_float(e.x) <= ao.radius) ++blocked;
+            }
+        }
+        ao.blocked[pix] = blocked;
+    }
+}
+
+// Drawing: pixel = P * (1 - strength * blocked / K) through emit_pixel, P the base frame (three big-endian floats a pixel, clamped
+// to [0, 1] by the packer that wrote them), blocked = -1 counting as 0.  adaptive_flag's geometry: a block is 64 pixels of four
+// rows, one wave a row, so the shared dword stores of 3- and 6-byte pixels find their aligned groups; the grid's z is the frame.
+__global__ __launch_bounds__(256) void ao_apply(const uint32_t *base, const int *blocked, int count, float strength, NtTarget tg) {
+    if (nt_aborted(tg)) return;
+    const int tid = (int)threadIdx.x;
+    const int x = (int)blockIdx.x * 64 + (tid & 63);
+    const int y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (y >= tg.height || x >= tg.width) return;
+    const long long pix = ((long long)blockIdx.z * tg.height + y) * tg.width + x;
+    const uint32_t *p = base + pix * 3;
+    const int bl = blocked[pix];
+    const float a = bl < 0 ? 0.0f : (float)bl / (float)count;
+    const float f = 1.0f - strength * a;
+    PixelRef pr;
+    pr.valid = true;
+    pr.hit_index = 0;
+    pr.x = x;
+    pr.y = y;
+    pr.offset = (long long)blockIdx.z * tg.frame_stride + (long long)y * tg.pitch + (long long)x * tg.bpp;
+    emit_pixel(tg, pr, __uint_as_float(bswap32(p[0])) * f, __uint_as_float(bswap32(p[1])) * f, __uint_as_float(bswap32(p[2])) * f);
+}
+
+// --------------------------------------------------------------------------------------
 // Adaptive supersampling at run-time n (n = 11..64 -- BoxScene: 25..64 -- and every n under NTRACER_FORCE_VAR=1): the refine
 // kernels of nt_adaptive.hpp on composite_color_var / composite_color_var_t and on rays_box_var's evaluation.  One lane a
 // flagged pixel, one wave a block, the blocks striding over the list.
@@ -2677,4 +2779,48 @@ int nt_launch_parallel_expand(const NtLaunchInfo &li, const float *cam, int widt
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(parallel_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, cam, li.n, width, k, half_w, half_h, first, count, out);
     return finish_launch("parallel projection expansion kernel launch");
+}
+
+// Ambient occlusion.  The fast route (nt_ao.hpp): the fixed-n launcher of the scene's dimension; the host sends every other
+// scene through the ray route below.
+int nt_launch_ao(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao) {
+    int r = 0;
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_ao_fixed_3(li, sc, tg, ao); break;
+        case 4: r = nt_ao_fixed_4(li, sc, tg, ao); break;
+        case 5: r = nt_ao_fixed_5(li, sc, tg, ao); break;
+        case 6: r = nt_ao_fixed_6(li, sc, tg, ao); break;
+        case 7: r = nt_ao_fixed_7(li, sc, tg, ao); break;
+        case 8: r = nt_ao_fixed_8(li, sc, tg, ao); break;
+        case 9: r = nt_ao_fixed_9(li, sc, tg, ao); break;
+        case 10: r = nt_ao_fixed_10(li, sc, tg, ao); break;
+        default:
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no ambient occlusion kernel at run-time n (n %d)", li.n);
+            return -1;
+    }
+    if (r) return r;
+    return finish_launch("ambient occlusion kernel launch");
+}
+
+// The ray route's two kernels around nt_launch_query: pixels [ar.first, ar.first + ar.pixels) of the launch
+int nt_launch_ao_expand(const NtLaunchInfo &li, const NtTarget &tg, const NtAo &ao, const NtAoRays &ar) {
+    long long blocks = (ar.pixels * ao.count + 255) / 256;
+    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    if (blocks < 1) return 0;
+    hipLaunchKernelGGL(ao_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, tg, ao, ar, li.n);
+    return finish_launch("ambient occlusion expansion kernel launch");
+}
+
+int nt_launch_ao_reduce(const NtLaunchInfo &li, const NtTarget &tg, const NtAo &ao, const NtAoRays &ar) {
+    long long blocks = (ar.pixels + 255) / 256;
+    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    if (blocks < 1) return 0;
+    hipLaunchKernelGGL(ao_reduce, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, tg, ao, ar);
+    return finish_launch("ambient occlusion count kernel launch");
+}
+
+int nt_launch_ao_apply(void *stream, const uint32_t *base, const int *blocked, int count, float strength, int nframes, const NtTarget &tg) {
+    const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)nframes);
+    hipLaunchKernelGGL(ao_apply, grid, dim3(256), 0, (hipStream_t)stream, base, blocked, count, strength, tg);
+    return finish_launch("ambient occlusion drawing kernel launch");
 }

@@ -829,6 +829,16 @@ class Lens(object):
         return np.ascontiguousarray(v, f32)
 
 
+def sphere_directions(n, count, seed=0):
+    """`count` directions uniform on the unit sphere of n dimensions, float32 [count][n]: normal deviates of
+    numpy.random.default_rng(seed), normalised in float64 -- the table set_ambient_occlusion makes of a plain sample count"""
+    n, count = int(n), int(count)
+    if n < 1 or count < 0:
+        raise ValueError("sphere_directions wants a positive dimension and a count that is not negative")
+    v = np.random.default_rng(seed).standard_normal((count, n))
+    return np.ascontiguousarray(v / np.sqrt((v * v).sum(axis=1))[:, None], f32)
+
+
 class _SceneBase(Scene):
     """Camera / fov handling shared by BoxScene and CompositeScene (ntracer_body.hpp:676-715)."""
 
@@ -919,6 +929,83 @@ class _SceneBase(Scene):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(L.nt_adaptive_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
         return mask.view(torch.bool)
+
+    def set_ambient_occlusion(self, samples, radius=None, bias=None, strength=1.0):
+        """Darken every pixel of a render by how enclosed its primary hit is (include/ntracer_hip.h): of K short
+        rays cast from the hit point into the hemisphere of the side the primary ray came from, `blocked` find an opaque
+        surface within `radius`, and the pixel's plain colour is multiplied by 1 - strength * blocked / K.  `samples`: an int K
+        (1..256), meaning sphere_directions(n, K); or a [K][n] array of directions, used as given (the radius is in units of
+        their length); or None / 0 for off, which needs no radius.  `bias` lifts the rays' origin off the surface along its normal (None:
+        1e-3 * radius).  CompositeScene only.  Supersampling, row bands, statistics, a lens and the parallel projection are
+        refused with it; calculate_color / colors_at, primary_hits, ray_colors, render_rays and the ray queries ignore it.  A
+        view setting like fov: not pickled."""
+        L = _lib.lib()
+        if samples is None or (isinstance(samples, (int, np.integer)) and not isinstance(samples, bool) and int(samples) == 0):
+            _lib.check(L.nt_scene_set_ambient_occlusion(self._handle, 0, None, 0.0, 0.0, 0.0))
+            return
+        if isinstance(samples, bool):
+            raise ValueError("samples must be a count, an array of directions or None")
+        if radius is None:
+            raise ValueError("ambient occlusion wants a radius")
+        for v in (radius, strength) + (() if bias is None else (bias,)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("radius, bias and strength must be numbers")
+        if isinstance(samples, (int, np.integer)):
+            if int(samples) < 0:
+                raise ValueError("the number of ambient occlusion samples must be between 0 and 256")
+            table = sphere_directions(self._n, int(samples))
+        else:
+            table = np.ascontiguousarray(samples, f32)
+            if table.ndim != 2 or table.shape[1] != self._n:
+                raise ValueError("the directions must be a [K][%d] array" % self._n)
+        if bias is None:
+            bias = 1e-3 * float(radius)
+        _lib.check(L.nt_scene_set_ambient_occlusion(self._handle, len(table), table.ctypes.data_as(_lib.f32p), float(radius), float(bias),
+                                                    float(strength)))
+
+    @property
+    def ambient_occlusion(self):
+        """None, or a dict of the setting: count, directions (float32 [count][n]), radius, bias, strength"""
+        L = _lib.lib()
+        count, radius, bias, strength = C.c_int(0), C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        _lib.check(L.nt_scene_get_ambient_occlusion(self._handle, C.byref(count), None, C.byref(radius), C.byref(bias), C.byref(strength)))
+        if count.value <= 0:
+            return None
+        table = np.zeros((count.value, self._n), f32)
+        _lib.check(L.nt_scene_get_ambient_occlusion(self._handle, None, table.ctypes.data_as(_lib.f32p), None, None, None))
+        return dict(count=int(count.value), directions=table, radius=float(radius.value), bias=float(bias.value), strength=float(strength.value))
+
+    def occlusion_counts(self, width, height, device=None, strict_reference=None):
+        """The blocked counts of a width x height view of the scene's camera under the ambient occlusion that is set
+        (nt_ambient_occlusion): int32 [height][width], -1 where the primary ray finds nothing opaque, else how many of the K
+        samples are blocked -- a numpy array, or with `device` a torch device a torch tensor there, enqueued on torch's
+        current stream."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        L = _lib.lib()
+        if device is None:
+            opts = _lib.NtRenderOpts()
+            opts.device = -1
+            if strict_reference is None:
+                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+            opts.strict_reference = 1 if strict_reference else 0
+            counts = np.zeros((height, width), np.int32)
+            _lib.check(L.nt_ambient_occlusion(self._handle, width, height, counts.ctypes.data, C.byref(opts)))
+            return counts
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self.ambient_occlusion is None:
+            raise ValueError("ambient occlusion is off (set_ambient_occlusion)")
+        counts = torch.empty((height, width), dtype=torch.int32, device=dev)
+        opts = self._rays_opts(dev, strict_reference)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_ambient_occlusion_device(self._handle, width, height, C.c_void_p(counts.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return counts
 
     def set_lens(self, lens):
         """Render through `lens` (a Lens of the image's size) instead of the pinhole; None takes it off.  fov is ignored
