@@ -431,6 +431,33 @@ int upload_scene(nt_scene *s, DeviceState *ds) {
     return NT_OK;
 }
 
+// The first device calls of every entry point: the device -- of the options, else `explicit_dev`, else the current one --, the
+// scene's state on it (ds->device says which it is) and the scene in its memory.  `table_device` >= 0: the call's camera table
+// lives there, and any other device is refused before it is touched; `table_user` is what the message says the device is for.
+int scene_on_device(nt_scene *s, const nt_render_opts *opts, int explicit_dev, DeviceState *&ds, int table_device = -1,
+                    const char *table_user = nullptr) {
+    int dev;
+    if (int r = pick_device(opts, explicit_dev, dev)) return r;
+    if (table_device >= 0 && dev != table_device)
+        return fail(NT_E_INVALID, "the camera table lives on device %d, the %s is for device %d", table_device, table_user, dev);
+    if (int r = device_state(s, dev, ds)) return r;
+    return upload_scene(s, ds);
+}
+
+// ... and of the host forms, which bring no stream: the scene's own
+int use_own_stream(DeviceState *ds) {
+    if (int r = own_stream(ds)) return r;
+    return use_stream(ds, ds->stream);
+}
+
+// The device forms outside the renders take three fields of their options.  `reader` is the subject and verb of the refusal, and
+// `whose` its pronoun.
+int only_device_strict_abort(const nt_render_opts *opts, const char *reader, const char *whose = "its") {
+    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
+        return fail(NT_E_INVALID, "%s device, strict_reference and abort_device of %s options: every other field must be 0", reader, whose);
+    return NT_OK;
+}
+
 int chan_table(DeviceState *ds, const Format &f, const NtChanDev *&dev_ptr) {
     for (auto &t : ds->chan_tables) {
         if (t->host.size() == f.chans.size() &&
@@ -529,6 +556,14 @@ void pack_camera(int n, const float *origin, const float *axes, float *out) {
     std::memcpy(out + n, axes, sizeof(float) * n);            // right  = t_orientation[0]
     std::memcpy(out + 2 * n, axes + n, sizeof(float) * n);    // up     = t_orientation[1]
     std::memcpy(out + 3 * n, axes + 2 * n, sizeof(float) * n);// forward= t_orientation[2]
+}
+
+// a camera table (NtCamera::buf): the rows of all `nframes` cameras, then their dot products, (4 n + 4) * nframes floats
+void pack_cameras(int n, int nframes, const float *origins, const float *axes, float *out) {
+    for (int f = 0; f < nframes; ++f) {
+        pack_camera(n, origins + (size_t)f * n, axes + (size_t)f * n * n, out + (size_t)f * 4 * n);
+        camera_dots(n, origins + (size_t)f * n, axes + (size_t)f * n * n, out + (size_t)nframes * 4 * n + (size_t)f * 4);
+    }
 }
 
 void fill_view(NtTarget &tg, const nt_scene *s, int w, int h) {
@@ -661,20 +696,159 @@ RenderSwitches read_switches() {
     return sw;
 }
 
+// Which kernels a composite scene goes to.  The launchers (nt_var.hip, nt_composite.hpp, nt_hits.hpp ...) decide the same way from
+// what the host hands them, and the host allocates the scratch the chosen kernel reads -- the `checked` columns, the frame
+// stacks -- so the rule is written here once and every enqueue takes its answers from it; what a site adds (no `checked` list
+// for an occlusion query or a counters pass) it adds on top.
+struct CompositeRoute {
+    // Scenes with transparent materials or Solids are rendered with the reference's own handling of o_hit.normal (its
+    // first leaf loop lets every primitive test write to the current hit's normal ray, tracer.hpp:1001,1020 -- see
+    // composite_kernel_t<N, true>), which needs the reference's exact `checked` list: a bitmap column per resident
+    // lane.  NTRACER_CLEAN_NORMALS=1 selects the intended semantics instead (a hit keeps the normal of what was hit).
+    // (transparent materials need the exact list in either mode: the reference trims its transparent hits with the
+    // distance of the LAST test, so a repeated test is not harmless there)
+    bool faithful;
+    bool var;            // the run-time-n kernels
+    int frame_stack;     // ray_color frames a lane of a faithful walk keeps
+    // The compile-time-N kernel keeps NT_TFRAMES ray_color frames in registers/scratch; above NT_MAX_FIXED_DIM, and
+    // for reflection deeper than that among transparent things, the run-time-n kernel with its frames in global
+    // scratch takes over (one wave per block there).
+    bool var_t;
+    // what launch_composite_fixed gives the packet walk, for a composite scene (the walk has a stack of 32 nodes)
+    bool packet_walk;
+};
+
+CompositeRoute composite_route(const nt_scene *s, const RenderSwitches &sw) {
+    CompositeRoute r;
+    r.faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
+    r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;
+    r.frame_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
+    r.var_t = r.var || r.frame_stack > 6;
+    r.packet_walk = !r.faithful && !r.var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32;
+    return r;
+}
+
+// the scene as the kernels of a launch see it
+void scene_dev(const nt_scene *s, const DeviceState *ds, const RenderSwitches &sw, bool strict, bool stats, NtCompositeDev &c) {
+    fill_composite(s, ds, c, stats);
+    // closest-hit walks drop subtrees beyond the current hit unless the caller (or NTRACER_STRICT_REFERENCE=1)
+    // asks for the reference's exact walk; the pixels are the same (nt_beyond_hit in nt_composite.hpp)
+    // ... and never for scenes with Solids: trees from the reference's own builder leave solids out of some cells
+    // they reach (its goldens show it), i.e. they break the invariant the shortcut relies on
+    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;
+    if (c.root < 0) c.root = -1;
+}
+
+// what every launcher is told; the buffers of a route (counter, cameras, numerators, hit records, tile order, cull bits) are its
+// enqueue's to add
+NtLaunchInfo launch_info(const nt_scene *s, const DeviceState *ds, const RenderSwitches &sw, int nframes, hipStream_t stream) {
+    NtLaunchInfo li{};
+    li.n = s->n;
+    li.nframes = nframes;
+    li.stream = stream;
+    li.cu_count = ds->cu_count;
+    li.kernel_choice = sw.composite_kernel;
+    li.frame_major = sw.frame_major;
+    li.force_var = sw.force_var;
+    li.box_var_rows = sw.box_var_rows;
+    return li;
+}
+
+// a launcher's non-zero status: -2 is a launch the kernels refuse, anything else the device's own error
+int launch_failed(int r) { return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error()); }
+
+// the cameras of a launch in device memory: the caller's table, or the scene's own camera, copied there in stream order
+int device_camera(const nt_scene *s, DeviceState *ds, const float *cam_buf, hipStream_t stream, const float *&cams) {
+    cams = cam_buf;
+    if (cams) return NT_OK;
+    float packed[4 * NT_DEV_MAX_DIM];
+    pack_camera(s->n, s->origin.data(), s->axes.data(), packed);
+    if (int e = ds->cams.ensure(sizeof(float) * 4 * s->n)) return e;
+    HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * s->n, hipMemcpyHostToDevice, stream));
+    cams = (const float *)ds->cams.p;
+    return NT_OK;
+}
+
+// the plain fp32 x 3 format, 12-byte pixels without padding: what a stage draws in when another kernel reads its pixels
+int plain_f32_format(int w, int h, Format &out) {
+    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
+    const nt_image_format desc = {(int32_t)w, (int32_t)h, 0, 3, plain, 0};
+    return parse_format(&desc, out);
+}
+
+// the target of the kernels that draw nothing: the whole pinhole view of w x h, and the abort word
+void view_target(const nt_scene *s, int w, int h, const int *abort_word, NtTarget &tg) {
+    std::memset(&tg, 0, sizeof(tg));
+    fill_view(tg, s, w, h);
+    tg.band_world = 1;
+    tg.band_rows = NT_RENDER_CHUNK_SIZE;
+    tg.row_count = h;
+    tg.abort_word = abort_word;
+}
+
+// The sub-job of a render that works on a base frame (adaptive supersampling, ambient occlusion): frames [f0, f0 + nf) of `job`,
+// whole and without bands, in the plain format `bf` into scratch at `dest`, `frame_bytes` apart -- every route of a plain render
+// comes with it.  No counters: such a render has refused them.
+FrameJob base_frame_job(const nt_scene *s, const FrameJob &job, const Format &bf, int f0, int nf, void *dest, size_t frame_bytes) {
+    FrameJob bj = job;
+    bj.samples_pass = true;
+    bj.fmt = &bf;
+    bj.bands = Bands();
+    bj.bands.owned_rows = bf.height;
+    bj.row_begin = 0;
+    bj.row_count = bf.height;
+    bj.nframes = nf;
+    bj.frame_stride = frame_bytes;
+    bj.dest_dev = dest;
+    bj.stats = false;
+    if (job.cam_buf) {
+        bj.cam_buf = job.cam_buf + (size_t)f0 * 4 * s->n;
+        bj.cam_dots = job.cam_dots + (size_t)f0 * 4;
+    }
+    return bj;
+}
+
 // The scratch of the walks that keep the reference's exact `checked` list (renders and ray queries alike): a column of `words`
 // dwords per resident lane, so the GRID is what the scratch has columns for and the blocks stride over the work.  `blocks` comes
-// in as what the work could use and is halved, down to `min_blocks`, until the columns -- with `extra_words` more dwords a lane
-// of other per-lane scratch the caller keeps beside them -- fit `cap_bytes`.  DevBuf::ensure only grows: after a call with the
-// same shape nothing is allocated.
-int checked_scratch(const nt_scene *s, DeviceState *ds, NtCompositeDev &c, long long lanes_per_block, long long &blocks, long long min_blocks,
-                    long long extra_words, long long cap_bytes, bool clean_normals) {
+// in as what the work could use and is halved, down to `min_blocks`, until the columns fit `cap_bytes` -- together with the
+// ray_color frames a lane (`frame_stack` > 0: CompositeRoute::var_t), which get their columns in DeviceState::tframes here as
+// well.  DevBuf::ensure only grows: after a call with the same shape nothing is allocated.
+int checked_scratch(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, NtCompositeDev &c, long long lanes_per_block, long long &blocks,
+                    long long min_blocks, int frame_stack, long long cap_bytes) {
     const long long words = ((long long)s->n_batches + s->n_triangles + s->n_solids + 31) / 32;
-    while (blocks > min_blocks && blocks * lanes_per_block * (words + extra_words) * 4 > cap_bytes) blocks /= 2;
+    const long long fwords = (long long)nt_var_frame_words(s->n) * frame_stack;
+    while (blocks > min_blocks && blocks * lanes_per_block * (words + fwords) * 4 > cap_bytes) blocks /= 2;
     if (int e = ds->checked.ensure((size_t)(blocks * lanes_per_block * words * 4))) return e;
     c.checked = (uint32_t *)ds->checked.p;
     c.checked_words = (int)words;
     c.checked_lanes = (int)(blocks * lanes_per_block);
-    c.alias_normals = clean_normals ? 0 : 1;
+    c.alias_normals = sw.clean_normals ? 0 : 1;
+    if (frame_stack > 0) {
+        if (int e = ds->tframes.ensure((size_t)(blocks * lanes_per_block * fwords * 4))) return e;
+        c.tframes = (float *)ds->tframes.p;
+        c.tframe_count = frame_stack;
+    }
+    return NT_OK;
+}
+
+// the packet walk's plane numerators: as many frames as fit in 256 MB, at least one
+int numerator_scratch(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, int nframes, NtLaunchInfo &li) {
+    if (s->n_batches <= 0 || !sw.numerators) return NT_OK;
+    const size_t per_frame = (size_t)s->n_batches * NT_BATCH_SIZE * sizeof(float);
+    const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)256 << 20) / per_frame));
+    if (int e = ds->numer.ensure(frames * per_frame)) return e;
+    li.numer_buf = (float *)ds->numer.p;
+    li.numer_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+    return NT_OK;
+}
+
+// the primary hits between the two passes of a packet-walk render, `per_frame` bytes of records a frame: as many frames as fit in
+// 512 MB, at least one
+int hit_record_scratch(DeviceState *ds, const RenderSwitches &sw, size_t per_frame, int nframes, NtLaunchInfo &li) {
+    const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)512 << 20) / std::max<size_t>(per_frame, 1)));
+    if (int e = ds->hits.ensure(frames * per_frame)) return e;
+    li.hit_buf = ds->hits.p;
+    li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
     return NT_OK;
 }
 
@@ -716,42 +890,22 @@ int tile_order_for(DeviceState *ds, int width, int rows, const int *&dev_ptr) {
 // kernel's counter, cameras, numerators, hit scratch and tile order
 int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, const NtTarget &tg,
                    const NtCamera &cam, NtLaunchInfo &li, NtCompositeDev &c) {
-    fill_composite(s, ds, c, job.stats);
-    // closest-hit walks drop subtrees beyond the current hit unless the caller (or NTRACER_STRICT_REFERENCE=1)
-    // asks for the reference's exact walk; the pixels are the same (nt_beyond_hit in nt_composite.hpp)
-    // ... and never for scenes with Solids: trees from the reference's own builder leave solids out of some cells
-    // they reach (its goldens show it), i.e. they break the invariant the shortcut relies on
-    c.prune = (job.strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;
-    if (c.root < 0) c.root = -1;
-    // Scenes with transparent materials or Solids are rendered with the reference's own handling of o_hit.normal (its
-    // first leaf loop lets every primitive test write to the current hit's normal ray, tracer.hpp:1001,1020 -- see
-    // composite_kernel_t<N, true>), which needs the reference's exact `checked` list: a bitmap column per resident
-    // lane.  NTRACER_CLEAN_NORMALS=1 selects the intended semantics instead (a hit keeps the normal of what was hit).
-    const bool faithful = !job.counters_pass && (!s->all_opaque || (s->n_solids > 0 && !sw.clean_normals));
+    scene_dev(s, ds, sw, job.strict, job.stats, c);
+    const CompositeRoute rt = composite_route(s, sw);
+    // (the statistics launch of a scene with Solids is the counting kernel, which keeps no `checked` list: see enqueue)
+    const bool faithful = !job.counters_pass && rt.faithful;
     if (faithful) {
-        // (transparent materials need the exact list in either mode: the reference trims its transparent hits with the
-        // distance of the LAST test, so a repeated test is not harmless there)
-        // The compile-time-N kernel keeps NT_TFRAMES ray_color frames in registers/scratch; above NT_MAX_FIXED_DIM, and
-        // for reflection deeper than that among transparent things, the run-time-n kernel with its frames in global
-        // scratch takes over (one wave per block there).
-        const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
-        const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
-        const long long lpb = var_t ? 64 : 256;           // lanes per block
-        const long long tw = var_t ? 8 : 16;              // tile edge
-        const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
+        const long long lpb = rt.var_t ? 64 : 256;        // lanes per block
+        const long long tw = rt.var_t ? 8 : 16;           // tile edge
         long long tiles = job.colors_out ? (job.probe_count + lpb - 1) / lpb
                                          : (long long)((tg.width + tw - 1) / tw) * ((tg.row_count + tw - 1) / tw) * job.nframes;
-        long long blocks = std::min<long long>(std::max<long long>(tiles, 1), var_t ? 8192 : 4096);
-        if (int e = checked_scratch(s, ds, c, lpb, blocks, 64, fwords, (long long)512 << 20, sw.clean_normals)) return e;
-        if (var_t) {
-            if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
-            c.tframes = (float *)ds->tframes.p;
-            c.tframe_count = nframes_stack;
-        }
+        long long blocks = std::min<long long>(std::max<long long>(tiles, 1), rt.var_t ? 8192 : 4096);
+        if (int e = checked_scratch(s, ds, sw, c, lpb, blocks, 64, rt.var_t ? rt.frame_stack : 0, (long long)512 << 20)) return e;
     }
     // image renders of opaque scenes made of batches go through the packet kernel (primary rays share the
     // camera origin): it needs the camera table in device memory (and, for the persistent variant, a counter)
-    const bool packetable = c.all_opaque != 0 && !faithful;
+    // (what is not faithful has opaque materials alone, a counters pass too: enqueue refuses it to any other scene)
+    const bool packetable = !faithful;
     if (packetable && !job.stats && !job.colors_out && s->n <= NT_MAX_FIXED_DIM && li.kernel_choice != 2) {
         // persistent kernel: a zeroed work counter and the camera table in device memory (stream ordered)
         if (int e = ds->counter.ensure(8)) return e;
@@ -765,24 +919,14 @@ int plan_composite(const nt_scene *s, DeviceState *ds, const FrameJob &job, cons
             li.persist_cams = (const float *)ds->cams.p;
         }
     }
-    if (li.persist_cams && !tg.colors_out && s->n_batches > 0 && sw.numerators) {
-        // plane numerators of the packet kernel: as many frames as fit in 256 MB, at least one
-        const size_t per_frame = (size_t)s->n_batches * NT_BATCH_SIZE * sizeof(float);
-        const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)256 << 20) / per_frame));
-        if (int e = ds->numer.ensure(frames * per_frame)) return e;
-        li.numer_buf = (float *)ds->numer.p;
-        li.numer_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
-    }
+    if (!li.persist_cams || tg.colors_out) return NT_OK;
+    // ... and its numerators, the hit records of a two-pass render, and the order of its quads
+    if (int e = numerator_scratch(s, ds, sw, job.nframes, li)) return e;
     const bool lit = !s->pl_color.empty() || !s->gl_color.empty() || c.any_reflective || c.has_scalar_prims;
-    if (li.persist_cams && !tg.colors_out && lit && sw.two_pass) {
-        // scratch for the primary hits of a two-pass render: as many frames as fit in 512 MB, at least one
-        const size_t per_frame = (size_t)16 * tg.width * tg.row_count;
-        size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / std::max<size_t>(per_frame, 1)));
-        if (int e = ds->hits.ensure(frames * per_frame)) return e;
-        li.hit_buf = ds->hits.p;
-        li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+    if (lit && sw.two_pass) {
+        if (int e = hit_record_scratch(ds, sw, (size_t)16 * tg.width * tg.row_count, job.nframes, li)) return e;
     }
-    if (li.persist_cams && !tg.colors_out && sw.tile_order) {
+    if (sw.tile_order) {
         if (int e = tile_order_for(ds, tg.width, tg.row_count, li.tile_order)) return e;
     }
     return NT_OK;
@@ -902,10 +1046,8 @@ int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
     if (row_bytes > cap)
         return fail(NT_E_UNSUPPORTED, "supersampling %d of a %d pixel wide image: the samples of one row (%lld bytes) do not fit the scratch "
                     "buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", ss, f.width, row_bytes, cap >> 20);
-    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
-    const nt_image_format hi_desc = {(int32_t)hi_w, (int32_t)hi_h, 0, 3, plain, 0};
     Format hf;
-    if (int r = parse_format(&hi_desc, hf)) return r;
+    if (int r = plain_f32_format((int)hi_w, (int)hi_h, hf)) return r;
     // (16384 rows at most: the grids of the two stages count rows in their y)
     const long long rows_fit = std::min<long long>(cap / row_bytes, 16384);
     const int chunk_rows = (int)std::min<long long>(rows_fit, job.row_count);
@@ -938,8 +1080,7 @@ int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
             rt.dest = tg.dest + (long long)f0 * tg.frame_stride;
             rt.row_begin = job.row_begin + r0;
             rt.row_count = rc;
-            const int r = nt_launch_resolve(ss, job.stream, ds->samples.p, (long long)hj.frame_stride, hi_pitch, nf, rt);
-            if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+            if (int r = nt_launch_resolve(ss, job.stream, ds->samples.p, (long long)hj.frame_stride, hi_pitch, nf, rt)) return launch_failed(r);
         }
     }
     return NT_OK;
@@ -991,40 +1132,17 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
     uint32_t *list = (uint32_t *)(scratch + (size_t)chunk_frames * px * 12);
     if (mask_scratch) mask_dev = (uint8_t *)(scratch + (size_t)chunk_frames * px * 16);
     if (mask_out) *mask_out = mask_dev;
-    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
-    const nt_image_format base_desc = {(int32_t)W, (int32_t)H, 0, 3, plain, 0};
     Format bf;
-    if (int r = parse_format(&base_desc, bf)) return r;
-    const int n = s->n;
+    if (int r = plain_f32_format(W, H, bf)) return r;
     NtTarget tg;
     if (draw) {
         if (int r = fill_target(s, ds, job, tg)) return r;
     } else {
-        std::memset(&tg, 0, sizeof(tg));
-        fill_view(tg, s, W, H);
-        tg.band_world = 1;
-        tg.band_rows = NT_RENDER_CHUNK_SIZE;
-        tg.row_count = H;
-        tg.abort_word = job.abort_word;
+        view_target(s, W, H, job.abort_word, tg);
     }
-    const float *cams = job.cam_buf;
     for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
         const int nf = std::min(chunk_frames, job.nframes - f0);
-        FrameJob bj = job;
-        bj.samples_pass = true;
-        bj.fmt = &bf;
-        bj.bands = Bands();
-        bj.bands.owned_rows = H;
-        bj.row_begin = 0;
-        bj.row_count = H;
-        bj.nframes = nf;
-        bj.frame_stride = (size_t)px * 12;
-        bj.dest_dev = scratch;
-        bj.stats = false;
-        if (job.cam_buf) {
-            bj.cam_buf = job.cam_buf + (size_t)f0 * 4 * n;
-            bj.cam_dots = job.cam_dots + (size_t)f0 * 4;
-        }
+        const FrameJob bj = base_frame_job(s, job, bf, f0, nf, scratch, (size_t)px * 12);
         if (int e = enqueue(s, ds, bj)) return e;
         NtAdaptive ad{};
         ad.base = (const uint32_t *)scratch;
@@ -1036,21 +1154,15 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
         ad.draw = draw ? 1 : 0;
         NtTarget ft = tg;
         if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
-        if (nt_launch_adaptive_flag(job.stream, ad, ft)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+        if (int r = nt_launch_adaptive_flag(job.stream, ad, ft)) return launch_failed(r);
         if (!draw || ss <= 1) continue;
-        if (!cams) {
-            // the scene's own camera in device memory, packed as enqueue_lens packs it (after the base frame, whose packet walk
-            // puts the same rows there)
-            float packed[4 * NT_DEV_MAX_DIM];
-            pack_camera(n, s->origin.data(), s->axes.data(), packed);
-            if (int e = ds->cams.ensure(sizeof(float) * 4 * n)) return e;
-            HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
-        }
         NtRefine rf{};
         rf.list = list;
         rf.count = ad.count;
         rf.max_count = (long long)nf * px;
-        rf.cams = cams ? cams + (size_t)f0 * 4 * n : (const float *)ds->cams.p;
+        // the chunk's cameras; the scene's own goes to device memory here, after the base frame, whose packet walk puts the same
+        // rows there
+        if (int e = device_camera(s, ds, bj.cam_buf, job.stream, rf.cams)) return e;
         rf.s = ss;
         NtTarget hv;
         fill_view(hv, s, ss * W, ss * H);                               // (the view of 4.3's first stage)
@@ -1060,21 +1172,12 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
         // consecutive lanes hold the list's pixels, not the aligned groups of one row that emit_pixel's shared dword stores of
         // 3- and 6-byte pixels count on: those formats go out pixel by pixel (as rays_image_target has it)
         if (ft.bpp == 3 || ft.bpp == 6) ft.aligned4 = 0;
-        NtLaunchInfo li{};
-        li.n = n;
-        li.nframes = nf;
-        li.stream = job.stream;
-        li.cu_count = ds->cu_count;
-        li.force_var = sw.force_var;
-        int r;
+        const NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
+        NtCompositeDev c;
         if (s->composite) {
-            NtCompositeDev c;
             if (int e = rays_scene(s, ds, sw, job.strict, rf.max_count, 64, 4096, c)) return e;
-            r = nt_launch_refine(li, &c, rf, ft);
-        } else {
-            r = nt_launch_refine(li, nullptr, rf, ft);
         }
-        if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        if (int r = nt_launch_refine(li, s->composite ? &c : nullptr, rf, ft)) return launch_failed(r);
     }
     return NT_OK;
 }
@@ -1121,9 +1224,9 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
     if (per_frame > cap)
         return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d x %d image: the base frame, the hit records, the normal rows and the counts of one "
                     "frame (%lld bytes) do not fit the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
-    const bool var = n > NT_MAX_FIXED_DIM || sw.force_var;
-    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);        // (hits_enqueue's terms)
-    const bool fast = !faithful && !var;
+    // the opaque scenes the fixed-n kernels draw have a counting kernel of their own; every other scene takes the ray route
+    const CompositeRoute rt = composite_route(s, sw);
+    const bool fast = !rt.faithful && !rt.var;
     long long chunk_frames = std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame), INT_MAX / px));
     // the ray route: the rays of whole pixel rows behind the frames, 16-byte aligned
     const long long row_bytes = (long long)W * K * (8 * n + 32);
@@ -1151,37 +1254,15 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
     if (draw) {
         if (int r = fill_target(s, ds, job, tg)) return r;
     } else {
-        std::memset(&tg, 0, sizeof(tg));
-        fill_view(tg, s, W, H);
-        tg.band_world = 1;
-        tg.band_rows = NT_RENDER_CHUNK_SIZE;
-        tg.row_count = H;
-        tg.abort_word = job.abort_word;
+        view_target(s, W, H, job.abort_word, tg);
     }
-    static const nt_channel plain[3] = {{1.0f, 0.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 1.0f, 0.0f, 0.0f, 32, 1, {0, 0}}, {0.0f, 0.0f, 1.0f, 0.0f, 32, 1, {0, 0}}};
-    const nt_image_format base_desc = {(int32_t)W, (int32_t)H, 0, 3, plain, 0};
     Format bf;
-    if (int r = parse_format(&base_desc, bf)) return r;
+    if (int r = plain_f32_format(W, H, bf)) return r;
     for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
         const int nf = std::min((int)chunk_frames, job.nframes - f0);
         const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
         if (draw) {
-            FrameJob bj = job;
-            bj.samples_pass = true;
-            bj.fmt = &bf;
-            bj.bands = Bands();
-            bj.bands.owned_rows = H;
-            bj.row_begin = 0;
-            bj.row_count = H;
-            bj.nframes = nf;
-            bj.frame_stride = (size_t)px * 12;
-            bj.dest_dev = base;
-            bj.stats = false;
-            if (job.cam_buf) {
-                bj.cam_buf = cams;
-                bj.cam_dots = job.cam_dots + (size_t)f0 * 4;
-            }
-            if (int e = enqueue(s, ds, bj)) return e;
+            if (int e = enqueue(s, ds, base_frame_job(s, job, bf, f0, nf, base, (size_t)px * 12))) return e;
         }
         nt_hit_buffers hb{};
         hb.hits = (nt_ray_hit *)recs;
@@ -1199,19 +1280,11 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
         ao.radius = s->ao_radius;
         ao.bias = s->ao_bias;
         ao.blocked = counts;
-        NtLaunchInfo li{};
-        li.n = n;
-        li.nframes = nf;
-        li.stream = job.stream;
-        li.cu_count = ds->cu_count;
-        li.force_var = sw.force_var;
+        const NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
         if (fast) {
             NtCompositeDev c;
-            fill_composite(s, ds, c, false);
-            c.prune = (job.strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as query_enqueue has it)
-            if (c.root < 0) c.root = -1;
-            const int r = nt_launch_ao(li, c, tg, ao);
-            if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+            scene_dev(s, ds, sw, job.strict, false, c);
+            if (int r = nt_launch_ao(li, c, tg, ao)) return launch_failed(r);
         } else {
             const long long rows = (long long)nf * H;
             for (long long r0 = 0; r0 < rows; r0 += chunk_rows) {
@@ -1227,7 +1300,7 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
                 ar.t_far = (float *)q0; q0 += nr * 4;
                 ar.skip_item = (int *)q0; q0 += nr * 4;
                 ar.skip_lane = (int *)q0;
-                if (nt_launch_ao_expand(li, tg, ao, ar)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+                if (int r = nt_launch_ao_expand(li, tg, ao, ar)) return launch_failed(r);
                 NtQuery q{};
                 q.count = (int)nr;
                 q.origins = ar.origins;
@@ -1239,13 +1312,13 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
                 q.hits = (void *)ar.results;
                 q.abort_word = job.abort_word;
                 if (int e = query_enqueue(s, ds, q, job.strict, job.stream)) return e;
-                if (nt_launch_ao_reduce(li, tg, ao, ar)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+                if (int r = nt_launch_ao_reduce(li, tg, ao, ar)) return launch_failed(r);
             }
         }
         if (draw) {
             NtTarget ft = tg;
             ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
-            if (nt_launch_ao_apply(job.stream, (const uint32_t *)base, counts, K, s->ao_strength, nf, ft)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            if (int r = nt_launch_ao_apply(job.stream, (const uint32_t *)base, counts, K, s->ao_strength, nf, ft)) return launch_failed(r);
         }
     }
     return NT_OK;
@@ -1308,25 +1381,10 @@ int enqueue_lens(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
     const float *table = nullptr;
     if (int r = lens_table(ld, ds, table)) return r;
     const int n = s->n;
-    // the cameras in device memory: the caller's table, or the scene's own camera
-    const float *cams = job.cam_buf;
-    if (!cams) {
-        float packed[4 * NT_DEV_MAX_DIM];
-        pack_camera(n, s->origin.data(), s->axes.data(), packed);
-        if (int e = ds->cams.ensure(sizeof(float) * 4 * n)) return e;
-        HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
-        cams = (const float *)ds->cams.p;
-    }
-    NtLaunchInfo li{};
-    li.n = n;
-    li.nframes = job.nframes;
-    li.stream = job.stream;
-    li.cu_count = ds->cu_count;
-    li.kernel_choice = sw.composite_kernel;
-    li.frame_major = sw.frame_major;
-    li.force_var = sw.force_var;
-    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
-    if (s->composite && !faithful && n <= NT_MAX_FIXED_DIM && !sw.force_var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32) {
+    const float *cams;
+    if (int e = device_camera(s, ds, job.cam_buf, job.stream, cams)) return e;
+    NtLaunchInfo li = launch_info(s, ds, sw, job.nframes, job.stream);
+    if (s->composite && composite_route(s, sw).packet_walk) {
         FrameJob pj = job;
         pj.cam_buf = cams;
         NtTarget tg;
@@ -1336,18 +1394,12 @@ int enqueue_lens(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
         cam.n = n;
         NtCompositeDev c;
         if (int e = plan_composite(s, ds, pj, sw, tg, cam, li, c)) return e;      // (the counter, numerators, tile order)
-        // the records between the walk and the shading pass: as many frames as fit in 512 MB, at least one (the two-pass
-        // route's own scratch and rule)
-        const size_t per_frame = (size_t)16 * f.width * f.height;
-        const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / per_frame));
-        if (int e = ds->hits.ensure(frames * per_frame)) return e;
-        li.hit_buf = ds->hits.p;
-        li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+        // the records between the walk and the shading pass, for every scene: the two-pass route's own scratch and rule
+        if (int e = hit_record_scratch(ds, sw, (size_t)16 * f.width * f.height, job.nframes, li)) return e;
         NtLens ln{};
         ln.table = table;
         ln.cams = cams;
-        const int r = nt_launch_lens(li, c, tg, ln);
-        if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        if (int r = nt_launch_lens(li, c, tg, ln)) return launch_failed(r);
         return NT_OK;
     }
     // the ray route: bands of whole rows whose directions fit the cap
@@ -1360,7 +1412,7 @@ int enqueue_lens(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
             const int rows = std::min(band, f.height - r0);
             const long long first = (long long)r0 * f.width, count = (long long)rows * f.width;
             void *dest = (char *)job.dest_dev + (size_t)fr * job.frame_stride + (size_t)r0 * f.pitch;
-            if (nt_launch_lens_expand(li, table, cam, first, count, (float *)ds->lens_dirs.p)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            if (int r = nt_launch_lens_expand(li, table, cam, first, count, (float *)ds->lens_dirs.p)) return launch_failed(r);
             NtRayJob rj{};
             rj.count = (int)count;
             rj.shared_origin = 1;
@@ -1370,7 +1422,7 @@ int enqueue_lens(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
             if (ld->masked) {
                 NtTarget tg;
                 if (int e = rays_image_target(s, ds, &f, dest, job.abort_word, job.stream, tg)) return e;
-                if (nt_launch_lens_mask(li, table, first, count, tg)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+                if (int r = nt_launch_lens_mask(li, table, first, count, tg)) return launch_failed(r);
             }
         }
     }
@@ -1402,27 +1454,12 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
     if (job.row_begin != 0 || job.row_count != f.height) return fail(NT_E_UNSUPPORTED, "a row range is not available while the parallel projection is set");
     if (f.bpp == 0) return NT_OK;                                       // nothing to draw
     const int n = s->n;
-    // the cameras in device memory: the caller's table, or the scene's own camera
-    const float *cams = job.cam_buf;
-    if (!cams) {
-        float packed[4 * NT_DEV_MAX_DIM];
-        pack_camera(n, s->origin.data(), s->axes.data(), packed);
-        if (int e = ds->cams.ensure(sizeof(float) * 4 * n)) return e;
-        HIP_TRY(hipMemcpyAsync(ds->cams.p, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
-        cams = (const float *)ds->cams.p;
-    }
-    NtLaunchInfo li{};
-    li.n = n;
-    li.nframes = job.nframes;
-    li.stream = job.stream;
-    li.cu_count = ds->cu_count;
-    li.kernel_choice = sw.composite_kernel;
-    li.frame_major = sw.frame_major;
-    li.force_var = sw.force_var;
+    const float *cams;
+    if (int e = device_camera(s, ds, job.cam_buf, job.stream, cams)) return e;
+    NtLaunchInfo li = launch_info(s, ds, sw, job.nframes, job.stream);
     const float half_w = float(f.width) / float(2), half_h = float(f.height) / float(2);
     const float k = s->parallel / half_w;                               // (once, in fp32, as fill_view forms fovI)
-    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
-    if (s->composite && !faithful && n <= NT_MAX_FIXED_DIM && !sw.force_var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32) {
+    if (s->composite && composite_route(s, sw).packet_walk) {
         FrameJob pj = job;
         pj.cam_buf = cams;
         NtTarget tg;
@@ -1434,17 +1471,11 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
         NtCompositeDev c;
         // (the counter and the tile order; plan_composite also ensures the numerator scratch, which this walk never reads)
         if (int e = plan_composite(s, ds, pj, sw, tg, cam, li, c)) return e;
-        // the records between the walk and the shading pass: as many frames as fit in 512 MB, at least one (the two-pass
-        // route's own scratch and rule)
-        const size_t per_frame = (size_t)16 * f.width * f.height;
-        const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)job.nframes, ((size_t)512 << 20) / per_frame));
-        if (int e = ds->hits.ensure(frames * per_frame)) return e;
-        li.hit_buf = ds->hits.p;
-        li.hit_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
+        // the records between the walk and the shading pass, for every scene: the two-pass route's own scratch and rule
+        if (int e = hit_record_scratch(ds, sw, (size_t)16 * f.width * f.height, job.nframes, li)) return e;
         NtParallel pl{};
         pl.cams = cams;
-        const int r = nt_launch_parallel(li, c, tg, pl);
-        if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+        if (int r = nt_launch_parallel(li, c, tg, pl)) return launch_failed(r);
         return NT_OK;
     }
     // the ray route: bands of whole rows whose origins and directions fit the cap
@@ -1458,7 +1489,7 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
             const long long first = (long long)r0 * f.width, count = (long long)rows * f.width;
             void *dest = (char *)job.dest_dev + (size_t)fr * job.frame_stride + (size_t)r0 * f.pitch;
             float *scratch = (float *)ds->lens_dirs.p;
-            if (nt_launch_parallel_expand(li, cam, f.width, k, half_w, half_h, first, count, scratch)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+            if (int r = nt_launch_parallel_expand(li, cam, f.width, k, half_w, half_h, first, count, scratch)) return launch_failed(r);
             NtRayJob rj{};
             rj.count = (int)count;
             rj.shared_origin = 0;
@@ -1510,15 +1541,7 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     cam.n = s->n;
     if (!job.cam_buf) pack_camera(s->n, s->origin.data(), s->axes.data(), cam.inl);
     camera_dots(s->n, s->origin.data(), s->axes.data(), cam.odots);
-    NtLaunchInfo li{};
-    li.n = s->n;
-    li.nframes = job.nframes;
-    li.stream = job.stream;
-    li.cu_count = ds->cu_count;
-    li.kernel_choice = sw.composite_kernel;
-    li.frame_major = sw.frame_major;
-    li.force_var = sw.force_var;
-    li.box_var_rows = sw.box_var_rows;
+    NtLaunchInfo li = launch_info(s, ds, sw, job.nframes, job.stream);
     int r;
     if (s->composite) {
         NtCompositeDev c;
@@ -1528,7 +1551,7 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
         if (int e = plan_box(s, ds, job, sw, tg, li)) return e;
         r = nt_launch_box(li, cam, tg);
     }
-    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    if (r) return launch_failed(r);
     return NT_OK;
 }
 
@@ -1537,6 +1560,53 @@ int prepare_stats(DeviceState *ds, hipStream_t st, bool on) {
     if (int r = ds->stats.ensure(8 * sizeof(unsigned long long))) return r;
     HIP_TRY(hipMemsetAsync(ds->stats.p, 0, 8 * sizeof(unsigned long long), st));
     return NT_OK;
+}
+
+// what the scene's settings refuse of a render, in the order the render entry points say it, before they touch a device
+int render_checks(const nt_scene *s, const Format &f, const Bands &b, bool stats) {
+    if (int r = ao_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
+    if (int r = lens_check(s, f.width, f.height, b, stats, false)) return r;
+    if (int r = parallel_check(s, b, stats, false)) return r;
+    return adaptive_check(s, b, stats);
+}
+
+// What a job takes from the caller's options.  abort_device and overlapped are the device forms' (`device_form`): a host form
+// has its own abort word or none, and waits for its launch.
+void job_options(FrameJob &job, const nt_render_opts *opts, bool device_form) {
+    job.strict = opts && opts->strict_reference;
+    if (!device_form) return;
+    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
+    job.overlapped = opts ? opts->overlapped : 0;
+}
+
+// the job of a render entry point: the owned rows of `nframes` whole images at `dest_dev`, `frame_stride` bytes apart
+FrameJob render_job(const Format &f, const Bands &b, void *dest_dev, size_t frame_stride, int nframes, hipStream_t stream, bool stats,
+                    const nt_render_opts *opts, bool device_form) {
+    FrameJob job{};
+    job.fmt = &f;
+    job.bands = b;
+    job.dest_dev = dest_dev;
+    job.frame_stride = frame_stride;
+    job.nframes = nframes;
+    job.stream = stream;
+    job.stats = stats;
+    job_options(job, opts, device_form);
+    job.row_begin = 0;
+    job.row_count = b.owned_rows;
+    return job;
+}
+
+// ... and of the entry points that draw nothing (nt_adaptive_mask, nt_ambient_occlusion): one whole view of w x h
+FrameJob view_job(int w, int h, hipStream_t stream, const nt_render_opts *opts, bool device_form) {
+    FrameJob job{};
+    job.nframes = 1;
+    job.stream = stream;
+    job_options(job, opts, device_form);
+    job.view_w = w;
+    job.view_h = h;
+    job.row_count = h;
+    job.bands.owned_rows = h;
+    return job;
 }
 
 int validate_desc(const nt_scene_desc *d) {
@@ -1629,27 +1699,18 @@ int query_validate(const nt_scene *s, const nt_ray_batch *rays, const nt_ray_res
 int query_enqueue(nt_scene *s, DeviceState *ds, NtQuery &q, bool strict, hipStream_t stream) {
     const RenderSwitches sw = read_switches();
     NtCompositeDev c;
-    fill_composite(s, ds, c, false);
-    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
-    if (c.root < 0) c.root = -1;
-    const bool var = s->n > NT_MAX_FIXED_DIM || sw.force_var;
+    scene_dev(s, ds, sw, strict, false, c);
+    const CompositeRoute rt = composite_route(s, sw);
     // closest hits of scenes with transparent materials or Solids: the walk that keeps the transparent hits and the
-    // reference's o_hit.normal, on the exact `checked` list (see plan_composite); occlusion walks keep no such list
-    const bool faithful = !q.occlusion && (!s->all_opaque || (s->n_solids > 0 && !sw.clean_normals));
+    // reference's o_hit.normal, on the exact `checked` list (see CompositeRoute); occlusion walks keep no such list
+    const bool faithful = !q.occlusion && rt.faithful;
     if (faithful) {
         // (a query keeps no ray_color frames: a quarter of the renderer's blocks are more than are resident, and half its bytes)
-        const long long lpb = var ? 64 : 256;
-        long long blocks = std::min<long long>(((long long)q.count + lpb - 1) / lpb, var ? 4096 : 1024);
-        if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, 0, (long long)256 << 20, sw.clean_normals)) return e;
+        const long long lpb = rt.var ? 64 : 256;
+        long long blocks = std::min<long long>(((long long)q.count + lpb - 1) / lpb, rt.var ? 4096 : 1024);
+        if (int e = checked_scratch(s, ds, sw, c, lpb, blocks, 1, 0, (long long)256 << 20)) return e;
     }
-    NtLaunchInfo li{};
-    li.n = s->n;
-    li.nframes = 1;
-    li.stream = stream;
-    li.cu_count = ds->cu_count;
-    li.force_var = sw.force_var;
-    const int r = nt_launch_query(li, c, q);
-    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    if (int r = nt_launch_query(launch_info(s, ds, sw, 1, stream), c, q)) return launch_failed(r);
     return NT_OK;
 }
 
@@ -1659,13 +1720,9 @@ int query_host(nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *out,
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
-    int dev;
-    if (int r = pick_device(nullptr, device, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
+    if (int r = scene_on_device(s, nullptr, device, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
     // one slab of the probe scratch: rays | per-ray parameters | normals | records | lists, each 16-byte aligned
     const size_t count = (size_t)rays->count, n = (size_t)s->n;
     auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
@@ -1721,17 +1778,13 @@ int query_host(nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *out,
 int query_device(nt_scene *s, const nt_ray_batch *rays, const nt_ray_results *out, const nt_render_opts *opts, void *hip_stream,
                  bool occlusion) {
     if (int r = query_validate(s, rays, out)) return r;
-    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
-        return fail(NT_E_INVALID, "a ray query reads device, strict_reference and abort_device of its options: every other field must be 0");
+    if (int r = only_device_strict_abort(opts, "a ray query reads")) return r;
     if (rays->count == 0) return NT_OK;
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     NtQuery q{};
     q.count = rays->count;
@@ -1771,12 +1824,6 @@ int hits_validate(const nt_scene *s, int width, int height, const nt_hit_buffers
     return NT_OK;
 }
 
-int hits_check_opts(const nt_render_opts *opts) {
-    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
-        return fail(NT_E_INVALID, "a primary-hit pass reads device, strict_reference and abort_device of its options: every other field must be 0");
-    return NT_OK;
-}
-
 // The launch of one pass: `out` holds device pointers, `cam_buf` the frames' cameras in device memory (nullptr: the scene's
 // current camera, one frame).  The scene goes the way a render of it would go (plan_composite): the walks with the exact
 // `checked` list for transparent materials and the reference's o_hit.normal, the packet walk -- with its numerators and its
@@ -1785,33 +1832,18 @@ int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_h
                  int nframes, bool strict, const int *abort_word, hipStream_t stream) {
     const RenderSwitches sw = read_switches();
     NtCompositeDev c;
-    fill_composite(s, ds, c, false);
-    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
-    if (c.root < 0) c.root = -1;
+    scene_dev(s, ds, sw, strict, false, c);
     NtTarget tg;
-    std::memset(&tg, 0, sizeof(tg));
-    fill_view(tg, s, width, height);
-    tg.row_count = height;
-    tg.band_world = 1;
-    tg.band_rows = NT_RENDER_CHUNK_SIZE;
+    view_target(s, width, height, abort_word, tg);
     tg.frame_stride = frame_stride * (long long)sizeof(nt_ray_hit);
-    tg.abort_word = abort_word;
-    NtLaunchInfo li{};
-    li.n = s->n;
-    li.nframes = nframes;
-    li.stream = stream;
-    li.cu_count = ds->cu_count;
-    li.kernel_choice = sw.composite_kernel;
-    li.frame_major = sw.frame_major;
-    li.force_var = sw.force_var;
-    const bool var = s->n > NT_MAX_FIXED_DIM || sw.force_var;
-    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
-    if (faithful) {
+    NtLaunchInfo li = launch_info(s, ds, sw, nframes, stream);
+    const CompositeRoute rt = composite_route(s, sw);
+    if (rt.faithful) {
         // (no ray_color frames are kept: the grid of a ray query, see query_enqueue)
-        const long long lpb = var ? 64 : 256, tw = var ? 8 : 16;
+        const long long lpb = rt.var ? 64 : 256, tw = rt.var ? 8 : 16;
         const long long tiles = ((width + tw - 1) / tw) * ((height + tw - 1) / tw) * nframes;
-        long long blocks = std::min<long long>(tiles, var ? 4096 : 1024);
-        if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, 0, (long long)256 << 20, sw.clean_normals)) return e;
+        long long blocks = std::min<long long>(tiles, rt.var ? 4096 : 1024);
+        if (int e = checked_scratch(s, ds, sw, c, lpb, blocks, 1, 0, (long long)256 << 20)) return e;
     }
     NtHits h{};
     h.nframes = nframes;
@@ -1819,30 +1851,15 @@ int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_h
     h.hits = out->hits;
     h.normal_origin = out->normal_origin;
     h.normal_dir = out->normal_dir;
-    if (cam_buf) {
-        h.cams = cam_buf;
-    } else {
-        float inl[4 * NT_MAX_DIM];
-        pack_camera(s->n, s->origin.data(), s->axes.data(), inl);
-        if (int e = ds->cams.ensure(sizeof(float) * 4 * s->n)) return e;
-        HIP_TRY(hipMemcpyAsync(ds->cams.p, inl, sizeof(float) * 4 * s->n, hipMemcpyHostToDevice, stream));
-        h.cams = (const float *)ds->cams.p;
-    }
-    if (!faithful && !var && li.kernel_choice == 0 && c.stack_depth <= 32) {
-        // the packet walk's plane numerators (as many frames as fit in 256 MB, at least one) and quad order
-        if (s->n_batches > 0 && sw.numerators) {
-            const size_t per_frame = (size_t)s->n_batches * NT_BATCH_SIZE * sizeof(float);
-            const size_t frames = std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)256 << 20) / per_frame));
-            if (int e = ds->numer.ensure(frames * per_frame)) return e;
-            li.numer_buf = (float *)ds->numer.p;
-            li.numer_frames = std::max(1, std::min((int)frames, sw.chunk_frames));
-        }
+    if (int e = device_camera(s, ds, cam_buf, stream, h.cams)) return e;
+    if (rt.packet_walk) {                                               // (of a composite scene: no other comes here)
+        // the packet walk's plane numerators and quad order
+        if (int e = numerator_scratch(s, ds, sw, nframes, li)) return e;
         if (sw.tile_order) {
             if (int e = tile_order_for(ds, width, height, li.tile_order)) return e;
         }
     }
-    const int r = nt_launch_hits(li, c, tg, h);
-    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    if (int r = nt_launch_hits(li, c, tg, h)) return launch_failed(r);
     return NT_OK;
 }
 
@@ -1851,13 +1868,9 @@ int hits_host(nt_scene *s, int width, int height, const nt_hit_buffers *out, int
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
-    int dev;
-    if (int r = pick_device(nullptr, device, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
+    if (int r = scene_on_device(s, nullptr, device, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
     // one slab of the probe scratch: records | normal origins | normal directions (16-byte aligned each)
     const size_t count = (size_t)width * height;
     const size_t rbytes = count * sizeof(nt_ray_hit), vlen = (count * s->n * sizeof(float) + 15) & ~(size_t)15;
@@ -1891,12 +1904,8 @@ int hits_device(nt_scene *s, int width, int height, const nt_hit_buffers *out, l
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
-    if (cams && dev != cams_device) return fail(NT_E_INVALID, "the camera table lives on device %d, the pass is for device %d", cams_device, dev);
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
+    if (int r = scene_on_device(s, opts, -1, ds, cams ? cams_device : -1, "pass")) return r;
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     return hits_enqueue(s, ds, width, height, out, frame_stride, cams, count, opts && opts->strict_reference,
                         opts ? (const int *)opts->abort_device : nullptr, (hipStream_t)hip_stream);
@@ -1924,12 +1933,6 @@ int rays_validate(const nt_scene *s, const nt_rays *rays, const void *out, bool 
         if (!finite) return fail(NT_E_INVALID, "ray %zu has a non-finite component", r);
         if (zero) return fail(NT_E_INVALID, "ray %zu has an all-zero direction", r);
     }
-    return NT_OK;
-}
-
-int rays_check_opts(const nt_render_opts *opts) {
-    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
-        return fail(NT_E_INVALID, "a ray-colour call reads device, strict_reference and abort_device of its options: every other field must be 0");
     return NT_OK;
 }
 
@@ -1969,22 +1972,12 @@ int rays_image_target(const nt_scene *s, DeviceState *ds, const Format *fmt, voi
 // kernels (the run-time-n ones have 64), at most `max_fixed` blocks of them
 int rays_scene(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, bool strict, long long count, long long lpb_fixed, long long max_fixed,
                NtCompositeDev &c) {
-    fill_composite(s, ds, c, false);
-    c.prune = (strict || sw.strict_reference || s->n_solids > 0) ? 0 : 1;     // (as plan_composite has it)
-    if (c.root < 0) c.root = -1;
-    const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);
-    if (faithful) {
-        const int nframes_stack = s->any_reflective ? s->max_reflect_depth + 1 : 1;
-        const bool var_t = s->n > NT_MAX_FIXED_DIM || sw.force_var || nframes_stack > 6;
-        const long long lpb = var_t ? 64 : lpb_fixed;
-        const long long fwords = var_t ? (long long)nt_var_frame_words(s->n) * nframes_stack : 0;
-        long long blocks = std::min<long long>((count + lpb - 1) / lpb, var_t ? 4096 : max_fixed);
-        if (int e = checked_scratch(s, ds, c, lpb, blocks, 1, fwords, (long long)512 << 20, sw.clean_normals)) return e;
-        if (var_t) {
-            if (int e = ds->tframes.ensure((size_t)(blocks * lpb * fwords * 4))) return e;
-            c.tframes = (float *)ds->tframes.p;
-            c.tframe_count = nframes_stack;
-        }
+    scene_dev(s, ds, sw, strict, false, c);
+    const CompositeRoute rt = composite_route(s, sw);
+    if (rt.faithful) {
+        const long long lpb = rt.var_t ? 64 : lpb_fixed;
+        long long blocks = std::min<long long>((count + lpb - 1) / lpb, rt.var_t ? 4096 : max_fixed);
+        if (int e = checked_scratch(s, ds, sw, c, lpb, blocks, 1, rt.var_t ? rt.frame_stack : 0, (long long)512 << 20)) return e;
     }
     return NT_OK;
 }
@@ -2004,21 +1997,11 @@ int rays_enqueue(nt_scene *s, DeviceState *ds, const NtRayJob &job, float *rgb, 
         if (int r = rays_image_target(s, ds, fmt, dest_dev, abort_word, stream, tg)) return r;
         if (tg.bpp == 0) return NT_OK;                                 // nothing to draw
     }
-    NtLaunchInfo li{};
-    li.n = s->n;
-    li.nframes = 1;
-    li.stream = stream;
-    li.cu_count = ds->cu_count;
-    li.force_var = sw.force_var;
-    int r;
+    NtCompositeDev c;
     if (s->composite) {
-        NtCompositeDev c;
         if (int e = rays_scene(s, ds, sw, strict, job.count, 256, 1024, c)) return e;
-        r = nt_launch_rays(li, &c, job, tg);
-    } else {
-        r = nt_launch_rays(li, nullptr, job, tg);
     }
-    if (r) return fail(r == -2 ? NT_E_UNSUPPORTED : NT_E_DEVICE, "%s", nt_launch_error());
+    if (int r = nt_launch_rays(launch_info(s, ds, sw, 1, stream), s->composite ? &c : nullptr, job, tg)) return launch_failed(r);
     return NT_OK;
 }
 
@@ -2034,13 +2017,9 @@ int rays_host(nt_scene *s, const nt_rays *rays, float *rgb, void *dest, size_t d
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
-    int dev;
-    if (int r = pick_device(nullptr, device, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
+    if (int r = scene_on_device(s, nullptr, device, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
     // one slab of the probe scratch: directions | origins | colours, each 16-byte aligned
     const size_t count = (size_t)rays->count, n = (size_t)s->n;
     auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
@@ -2079,16 +2058,13 @@ int rays_device(nt_scene *s, const nt_rays *rays, float *rgb, void *dest_dev, si
     if (!rgb) {
         if (int r = rays_image_validate(fmt, rays, dest_len, f)) return r;
     }
-    if (int r = rays_check_opts(opts)) return r;
+    if (int r = only_device_strict_abort(opts, "a ray-colour call reads")) return r;
     if (rays->count == 0) return NT_OK;
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     NtRayJob job{};
     job.count = rays->count;
@@ -2475,34 +2451,18 @@ int nt_render(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format 
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
-    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
-    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
-    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
-    if (abort_flag && *abort_flag) return NT_ABORTED;           // (before anything touches `dest` or the device)
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
-    DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
-    if (int r = ds->framebuffer.ensure(std::max<size_t>(need, 16))) return r;
     const bool stats = opts && opts->collect_stats;
+    if (int r = render_checks(s, f, b, stats)) return r;
+    if (abort_flag && *abort_flag) return NT_ABORTED;           // (before anything touches `dest` or the device)
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    if (int r = ds->framebuffer.ensure(std::max<size_t>(need, 16))) return r;
     if (int r = prepare_stats(ds, ds->stream, stats)) return r;
     // pitch padding bytes are not written by the kernels: carry the caller's bytes through
     if (f.pitch != f.width * f.bpp || (b.world > 1 && !b.compact)) HIP_TRY(hipMemcpyAsync(ds->framebuffer.p, dest, need, hipMemcpyHostToDevice, ds->stream));
 
-    FrameJob job{};
-    job.fmt = &f;
-    job.bands = b;
-    job.dest_dev = ds->framebuffer.p;
-    job.frame_stride = 0;
-    job.nframes = 1;
-    job.cam_buf = nullptr;
-    job.stream = ds->stream;
-    job.stats = stats;
-    job.strict = opts && opts->strict_reference;
+    FrameJob job = render_job(f, b, ds->framebuffer.p, 0, 1, ds->stream, stats, opts, false);
     // Abort (the reference's workers poll renderer::CANCEL per pixel, render.cpp:412): ONE launch for the frame -- cutting it
     // into slabs cost a 120-cell frame a kernel tail per slab (9.3 ms instead of 1.2) -- whose blocks read a dword in device
     // memory when they start, and the packet kernel's waves every few dozen nodes (NtTarget::abort_word).  The host waits for the
@@ -2522,8 +2482,6 @@ int nt_render(nt_scene_t *s, void *dest, size_t dest_len, const nt_image_format 
         HIP_TRY(hipMemsetAsync(ds->abort_word.p, 0, 4, ds->stream));
         job.abort_word = (const int *)ds->abort_word.p;
     }
-    job.row_begin = 0;
-    job.row_count = b.owned_rows;
     if (int r = enqueue(s, ds, job)) { (void)hipStreamSynchronize(ds->stream); return r; }
     bool aborted = false;
     if (abort_flag) {
@@ -2559,32 +2517,14 @@ int nt_render_device(nt_scene_t *s, void *dest_dev, size_t dest_len, const nt_im
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
-    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
-    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
-    DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     const bool stats = opts && opts->collect_stats;
+    if (int r = render_checks(s, f, b, stats)) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     if (int r = prepare_stats(ds, (hipStream_t)hip_stream, stats)) return r;
-    if (stats) { s->have_stats = false; s->stats_device = dev; }
-    FrameJob job{};
-    job.fmt = &f;
-    job.bands = b;
-    job.dest_dev = dest_dev;
-    job.nframes = 1;
-    job.stream = (hipStream_t)hip_stream;
-    job.stats = stats;
-    job.strict = opts && opts->strict_reference;
-    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
-    job.overlapped = opts ? opts->overlapped : 0;
-    job.row_begin = 0;
-    job.row_count = b.owned_rows;
-    return enqueue(s, ds, job);
+    if (stats) { s->have_stats = false; s->stats_device = ds->device; }
+    return enqueue(s, ds, render_job(f, b, dest_dev, 0, 1, (hipStream_t)hip_stream, stats, opts, true));
 }
 
 int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, int nframes, const float *origins, const float *axes,
@@ -2599,15 +2539,10 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
-    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
-    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
+    const bool stats = opts && opts->collect_stats;
+    if (int r = render_checks(s, f, b, stats)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
     {
         // This entry point stages the caller's host arrays in a pinned slot that later calls reuse: a graph would replay the
         // launch, not the staging.  Refused while `hip_stream` is being captured -- a camera table (nt_render_table_device), whose
@@ -2622,36 +2557,20 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     DeviceState::Stage *st = nullptr;
     if (int r = stage_slot(ds, cam_floats * sizeof(float), st)) return r;
     float *packed = (float *)st->host;
-    for (int fidx = 0; fidx < nframes; ++fidx) {
-        pack_camera(n, origins + (size_t)fidx * n, axes + (size_t)fidx * n * n, packed + (size_t)fidx * 4 * n);
-        camera_dots(n, origins + (size_t)fidx * n, axes + (size_t)fidx * n * n, packed + (size_t)nframes * 4 * n + (size_t)fidx * 4);
-    }
+    pack_cameras(n, nframes, origins, axes, packed);
     // a camera table that earlier launches may still read must not be overwritten: grow-only buffer,
     // refilled only after the stream that used it has drained (same-stream ordering)
     if (int r = ds->cams.ensure(cam_floats * sizeof(float))) return r;
     // a copy kernel on the launch stream reads the pinned slot in place; the event keeps the slot from reuse until it has
     // (removed: NTRACER_CAM_UPLOAD=memcpy, and NTRACER_STAGE_EVENT=0, which skipped the event: unsafe beyond 8 calls in flight)
-    if (nt_launch_upload(hip_stream, packed, (float *)ds->cams.p, (int)cam_floats)) return fail(NT_E_DEVICE, "%s", nt_launch_error());
+    if (int r = nt_launch_upload(hip_stream, packed, (float *)ds->cams.p, (int)cam_floats)) return launch_failed(r);
     HIP_TRY(hipEventRecord(st->done, (hipStream_t)hip_stream));
     st->in_flight = true;
-    const bool stats = opts && opts->collect_stats;
     if (int r = prepare_stats(ds, (hipStream_t)hip_stream, stats)) return r;
-    if (stats) { s->have_stats = false; s->stats_device = dev; }
-    FrameJob job{};
-    job.fmt = &f;
-    job.bands = b;
-    job.dest_dev = dest_dev;
-    job.frame_stride = frame_stride;
-    job.nframes = nframes;
+    if (stats) { s->have_stats = false; s->stats_device = ds->device; }
+    FrameJob job = render_job(f, b, dest_dev, frame_stride, nframes, (hipStream_t)hip_stream, stats, opts, true);
     job.cam_buf = (const float *)ds->cams.p;
     job.cam_dots = job.cam_buf + (size_t)nframes * 4 * s->n;
-    job.stream = (hipStream_t)hip_stream;
-    job.stats = stats;
-    job.strict = opts && opts->strict_reference;
-    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
-    job.overlapped = opts ? opts->overlapped : 0;
-    job.row_begin = 0;
-    job.row_count = b.owned_rows;
     return enqueue(s, ds, job);
 }
 
@@ -2670,10 +2589,7 @@ nt_camera_table_t *nt_camera_table_create(int dimension, int nframes, const floa
     const int n = dimension;
     const size_t cam_floats = (size_t)nframes * 4 * n + (size_t)nframes * 4;
     std::vector<float> packed(cam_floats);
-    for (int f = 0; f < nframes; ++f) {
-        pack_camera(n, origins + (size_t)f * n, axes + (size_t)f * n * n, packed.data() + (size_t)f * 4 * n);
-        camera_dots(n, origins + (size_t)f * n, axes + (size_t)f * n * n, packed.data() + (size_t)nframes * 4 * n + (size_t)f * 4);
-    }
+    pack_cameras(n, nframes, origins, axes, packed.data());
     void *p = nullptr;
     if (hipMalloc(&p, cam_floats * sizeof(float)) != hipSuccess) { fail(NT_E_NOMEM, "hipMalloc failed for the camera table"); return nullptr; }
     if (hipMemcpy(p, packed.data(), cam_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
@@ -2708,35 +2624,16 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     if (int r = check_renderable(s)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    if (int r = ao_check(s, b, opts && opts->collect_stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = lens_check(s, f.width, f.height, b, opts && opts->collect_stats, false)) return r;
-    if (int r = parallel_check(s, b, opts && opts->collect_stats, false)) return r;
-    if (int r = adaptive_check(s, b, opts && opts->collect_stats)) return r;
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
-    if (dev != table->device) return fail(NT_E_INVALID, "the camera table lives on device %d, the render is for device %d", table->device, dev);
-    DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     const bool stats = opts && opts->collect_stats;
+    if (int r = render_checks(s, f, b, stats)) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds, table->device, "render")) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     if (int r = prepare_stats(ds, (hipStream_t)hip_stream, stats)) return r;
-    if (stats) { s->have_stats = false; s->stats_device = dev; }
-    FrameJob job{};
-    job.fmt = &f;
-    job.bands = b;
-    job.dest_dev = dest_dev;
-    job.frame_stride = frame_stride;
-    job.nframes = count;
+    if (stats) { s->have_stats = false; s->stats_device = ds->device; }
+    FrameJob job = render_job(f, b, dest_dev, frame_stride, count, (hipStream_t)hip_stream, stats, opts, true);
     job.cam_buf = table->dev + (size_t)first * 4 * table->n;                                  // (the table: all cameras, then all dot products)
     job.cam_dots = table->dev + (size_t)table->nframes * 4 * table->n + (size_t)first * 4;
-    job.stream = (hipStream_t)hip_stream;
-    job.stats = stats;
-    job.strict = opts && opts->strict_reference;
-    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
-    job.overlapped = opts ? opts->overlapped : 0;
-    job.row_begin = 0;
-    job.row_count = b.owned_rows;
     return enqueue(s, ds, job);
 }
 
@@ -2758,21 +2655,10 @@ int nt_adaptive_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long l
     if (int r = mask_validate(s, width, height, mask, opts)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
-    FrameJob job{};
-    job.nframes = 1;
-    job.stream = ds->stream;
-    job.strict = opts && opts->strict_reference;
-    job.view_w = width;
-    job.view_h = height;
-    job.row_count = height;
-    job.bands.owned_rows = height;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const FrameJob job = view_job(width, height, ds->stream, opts, false);
     uint8_t *mask_dev = nullptr;
     if (int r = enqueue_adaptive(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
     int count = 0;
@@ -2787,22 +2673,10 @@ int nt_adaptive_mask_device(nt_scene_t *s, int width, int height, void *mask_dev
     if (int r = mask_validate(s, width, height, mask_dev, opts)) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    FrameJob job{};
-    job.nframes = 1;
-    job.stream = (hipStream_t)hip_stream;
-    job.strict = opts && opts->strict_reference;
-    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
-    job.overlapped = opts ? opts->overlapped : 0;
-    job.view_w = width;
-    job.view_h = height;
-    job.row_count = height;
-    job.bands.owned_rows = height;
+    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);
     return enqueue_adaptive(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
 }
 
@@ -2823,21 +2697,10 @@ int nt_ambient_occlusion(nt_scene_t *s, int width, int height, int32_t *blocked,
     if (int r = ao_validate(s, width, height, blocked)) return r;
     RenderGuard guard(s);
     if (int r = guard.acquire()) return r;
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
-    FrameJob job{};
-    job.nframes = 1;
-    job.stream = ds->stream;
-    job.strict = opts && opts->strict_reference;
-    job.view_w = width;
-    job.view_h = height;
-    job.row_count = height;
-    job.bands.owned_rows = height;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const FrameJob job = view_job(width, height, ds->stream, opts, false);
     int *counts = nullptr;
     if (int r = enqueue_ao(s, ds, job, read_switches(), nullptr, &counts)) { (void)hipStreamSynchronize(ds->stream); return r; }
     HIP_TRY(hipMemcpyAsync(blocked, counts, (size_t)width * height * sizeof(int32_t), hipMemcpyDeviceToHost, ds->stream));
@@ -2847,25 +2710,13 @@ int nt_ambient_occlusion(nt_scene_t *s, int width, int height, int32_t *blocked,
 
 int nt_ambient_occlusion_device(nt_scene_t *s, int width, int height, void *blocked_dev, const nt_render_opts *opts, void *hip_stream) {
     if (int r = ao_validate(s, width, height, blocked_dev)) return r;
-    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->collect_stats || opts->overlapped))
-        return fail(NT_E_INVALID, "the ambient occlusion counts read device, strict_reference and abort_device of their options: every other field must be 0");
+    if (int r = only_device_strict_abort(opts, "the ambient occlusion counts read", "their")) return r;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    int dev;
-    if (int r = pick_device(opts, -1, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    FrameJob job{};
-    job.nframes = 1;
-    job.stream = (hipStream_t)hip_stream;
-    job.strict = opts && opts->strict_reference;
-    job.abort_word = opts ? (const int *)opts->abort_device : nullptr;
-    job.view_w = width;
-    job.view_h = height;
-    job.row_count = height;
-    job.bands.owned_rows = height;
+    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
     return enqueue_ao(s, ds, job, read_switches(), (int *)blocked_dev, nullptr);
 }
 
@@ -2878,13 +2729,9 @@ int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t 
     if (int r = guard.acquire()) return r;
     if (int r = lens_check(s, width, height, Bands(), false, true)) return r;
     if (int r = parallel_check(s, Bands(), false, true)) return r;
-    int dev;
-    if (int r = pick_device(nullptr, device, dev)) return r;
     DeviceState *ds;
-    if (int r = device_state(s, dev, ds)) return r;
-    if (int r = upload_scene(s, ds)) return r;
-    if (int r = own_stream(ds)) return r;
-    if (int r = use_stream(ds, ds->stream)) return r;
+    if (int r = scene_on_device(s, nullptr, device, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
     const size_t ibytes = (size_t)count * sizeof(int32_t);
     const size_t cbytes = (size_t)count * 3 * sizeof(float);
     if (int r = ds->probes.ensure(2 * ibytes + cbytes)) return r;
@@ -2933,7 +2780,7 @@ int nt_primary_hits(nt_scene_t *s, int width, int height, const nt_hit_buffers *
 
 int nt_primary_hits_device(nt_scene_t *s, int width, int height, const nt_hit_buffers *out, const nt_render_opts *opts, void *hip_stream) {
     if (int r = hits_validate(s, width, height, out, (long long)width * height, 1)) return r;
-    if (int r = hits_check_opts(opts)) return r;
+    if (int r = only_device_strict_abort(opts, "a primary-hit pass reads")) return r;
     return hits_device(s, width, height, out, (long long)width * height, nullptr, -1, 1, opts, hip_stream);
 }
 
@@ -2944,7 +2791,7 @@ int nt_primary_hits_table_device(nt_scene_t *s, int width, int height, const nt_
     if (first < 0 || count < 1 || first > table->nframes - count) return fail(NT_E_INVALID, "frames %d..%d are not in a table of %d", first, first + count - 1, table->nframes);
     if (frame_stride_records > (size_t)INT_MAX) return fail(NT_E_INVALID, "frame_stride_records is beyond 2^31 - 1 records");
     if (int r = hits_validate(s, width, height, out, (long long)frame_stride_records, count)) return r;
-    if (int r = hits_check_opts(opts)) return r;
+    if (int r = only_device_strict_abort(opts, "a primary-hit pass reads")) return r;
     return hits_device(s, width, height, out, (long long)frame_stride_records, table->dev + (size_t)first * 4 * table->n, table->device, count, opts, hip_stream);
 }
 

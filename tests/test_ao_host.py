@@ -82,11 +82,12 @@ def test_every_ao_launch_has_a_row_and_every_row_a_gpu_case():
     # every case lands on rows of the table, and both routes have cases
     for name, env in ao.CASES:
         assert _routes(name, env) <= set(rows), (name, env)
-    # the rule above is enqueue_ao's own
-    api = _body(_read("nt_api.cpp"), "int enqueue_ao(")
-    assert "const bool var = n > NT_MAX_FIXED_DIM || sw.force_var;" in api
-    assert "const bool faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);" in api
-    assert "const bool fast = !faithful && !var;" in api
+    # the rule above is enqueue_ao's own: the terms are composite_route's, which it asks, keeping none of its own
+    rule, api = _body(_read("nt_api.cpp"), "CompositeRoute composite_route("), _body(_read("nt_api.cpp"), "int enqueue_ao(")
+    assert "r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;" in rule
+    assert "r.faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);" in rule
+    assert "const CompositeRoute rt = composite_route(s, sw);" in api and "all_opaque" not in api
+    assert "const bool fast = !rt.faithful && !rt.var;" in api
     # the new launches stay out of the render, query and hits launchers, whose every launch wants a row of their own matrices
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("),
                       ("nt_query.hpp", "int launch_query_fixed("), ("nt_var.hip", "int nt_launch_query("),

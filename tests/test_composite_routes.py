@@ -83,6 +83,18 @@ def test_the_reader_reads_exactly_the_render_switches_and_nothing_else_calls_get
         assert calls == want, (name, calls)
 
 
+def test_every_enqueue_takes_its_route_from_composite_route():
+    """the host allocates the scratch the chosen kernel reads, so it must choose as the launchers do: the rule is written once, in
+    composite_route, and the enqueues that size `checked` columns, frame stacks or the packet walk's scratch ask it and keep no
+    terms of their own (enqueue_lens, enqueue_parallel and enqueue_ao: test_lens_host, test_parallel_host, test_ao_host)"""
+    api = _read("nt_api.cpp")
+    for head in ("int plan_composite(", "int hits_enqueue(", "int query_enqueue(", "int rays_scene("):
+        start = api.rindex(head)                                      # (the definition: some are declared further up)
+        body = _body(api[start:], head)
+        assert body.count("\n") > 5 and "composite_route(" in body, head
+        assert "all_opaque" not in body, head
+
+
 def test_the_thresholds_the_deep_rows_are_built_around():
     fixed = _fixed()
     # the packet kernel takes trees of stack_depth <= 32 only: its uniform stack has 32 entries and a 32-bit `bothbits`

@@ -86,9 +86,12 @@ def test_every_lens_launch_is_reached_by_a_case():
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("), ("nt_var.hip", "int nt_launch_box(")):
         assert not any("lens" in k or k.endswith(",true,true>") and k.startswith("composite_packet") for k in _launches(_body(_read(src), head)))
     assert "getenv" not in hpp
-    # what enqueue_lens sends to the packet walk is what launch_composite_fixed would: pinned text of the two conditions
-    api = _body(_read("nt_api.cpp"), "int enqueue_lens(")
-    assert "sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32" in api and "n <= NT_MAX_FIXED_DIM && !sw.force_var" in api
+    # what enqueue_lens sends to the packet walk is what launch_composite_fixed would: pinned text of the conditions, which are
+    # composite_route's -- enqueue_lens asks it and keeps no terms of its own
+    rule, api = _body(_read("nt_api.cpp"), "CompositeRoute composite_route("), _body(_read("nt_api.cpp"), "int enqueue_lens(")
+    assert "r.packet_walk = !r.faithful && !r.var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32;" in rule
+    assert "r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;" in rule
+    assert "s->composite && composite_route(s, sw).packet_walk" in api and "all_opaque" not in api
 
 
 def test_the_pinhole_table_is_the_ray_sources_own_arithmetic():

@@ -77,9 +77,12 @@ def test_every_parallel_launch_is_reached_by_a_case():
                       ("nt_var.hip", "int nt_launch_composite("), ("nt_var.hip", "int nt_launch_box("), ("nt_var.hip", "int nt_launch_rays(")):
         assert not any("parallel" in k for k in _launches(_body(_read(src), head)))
     assert "getenv" not in hpp
-    # what enqueue_parallel sends to the packet walk is what enqueue_lens sends to its own: pinned text of the conditions
-    api = _body(_read("nt_api.cpp"), "int enqueue_parallel(")
-    assert "sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32" in api and "n <= NT_MAX_FIXED_DIM && !sw.force_var" in api
+    # what enqueue_parallel sends to the packet walk is what enqueue_lens sends to its own: pinned text of the conditions, which
+    # are composite_route's -- enqueue_parallel asks it and keeps no terms of its own
+    rule, api = _body(_read("nt_api.cpp"), "CompositeRoute composite_route("), _body(_read("nt_api.cpp"), "int enqueue_parallel(")
+    assert "r.packet_walk = !r.faithful && !r.var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32;" in rule
+    assert "r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;" in rule
+    assert "s->composite && composite_route(s, sw).packet_walk" in api and "all_opaque" not in api
     assert "rj.shared_origin = 0;" in api
 
 
