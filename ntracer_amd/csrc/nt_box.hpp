@@ -900,8 +900,9 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
 //
 //   box_tile_kernel<N, F32, ROWS, WAVES>   a block = 64 columns x WAVES*ROWS rows (at most 64: one row per lane of the wave
 //                                   that works out the stretch codes, box_stretch_code, and leaves them in LDS); after the
-//                                   barrier every wave renders its ROWS rows from them with the lean loops, sixteen rows (a
-//                                   qword of codes) at a time.  Per-row parameters come from the host's row table through
+//                                   barrier every wave renders its ROWS rows from them with the lean loops, all of them in
+//                                   one pass (one wave a block, 64 rows: no LDS, no barrier -- the codes stay in the lanes
+//                                   that worked them out).  Per-row parameters come from the host's row table through
 //                                   scalar loads (NtTarget::rowtab).  Packed RGB at N > 8: a row it cannot settle (code 14,
 //                                   or a lane that needs the reference's face-by-face arithmetic) gets its bit set in the
 //                                   redo bitmap, [frame][row][word of 32 stretches], with an atomic OR.
@@ -964,16 +965,44 @@ __device__ __forceinline__ float row_dir(const float (&base)[N], const float (&u
     for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
     return sq;
 }
+// Rows a pass of the row phase covers in the 64 x 1 shape: all 64 (masks of 64 row bits in scalar register pairs), or 16 -- the
+// sixteen-row passes the kernel had while its codes went through a qword of LDS, four a wave, each with its own header: the build
+// to measure against.  The 16- and 8-row shapes take their rows in one pass either way.
+#ifndef NT_BOX_PASS_ROWS
+#define NT_BOX_PASS_ROWS 64
+#endif
+// masks of row bits, 32 or 64 of them: the lowest set bit, and mask &= ~(1 << bit) / mask |= 1 << bit as ONE scalar instruction
+// (the compiler writes mask & (mask - 1) as an add and an and): the lean loops run about as many scalar instructions a row as
+// vector ones
+__device__ __forceinline__ int nt_low_bit(uint32_t m) { return __builtin_ctz(m); }
+__device__ __forceinline__ int nt_low_bit(unsigned long long m) { return __builtin_ctzll(m); }
+__device__ __forceinline__ int nt_count_bits(uint32_t m) { return __builtin_popcount(m); }
+__device__ __forceinline__ int nt_count_bits(unsigned long long m) { return __builtin_popcountll(m); }
+__device__ __forceinline__ void nt_clear_bit(uint32_t &m, int bit) { asm("s_bitset0_b32 %0, %1" : "+s"(m) : "s"(bit)); }
+__device__ __forceinline__ void nt_clear_bit(unsigned long long &m, int bit) { asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(bit)); }
+__device__ __forceinline__ void nt_set_bit(uint32_t &m, int bit) { asm("s_bitset1_b32 %0, %1" : "+s"(m) : "s"(bit)); }
+__device__ __forceinline__ void nt_set_bit(unsigned long long &m, int bit) { asm("s_bitset1_b64 %0, %1" : "+s"(m) : "s"(bit)); }
+// ... and without its lowest set bit (`bit`), as the loops outside the lean ones always stepped: 32 bits, the compiler's add and
+// and; 64 bits, where that is an add, an add with carry and an and, the one instruction
+__device__ __forceinline__ void nt_drop_low_bit(uint32_t &m, int) { m &= m - 1u; }
+__device__ __forceinline__ void nt_drop_low_bit(unsigned long long &m, int bit) { nt_clear_bit(m, bit); }
 template <int N, bool F32, int ROWS, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCameraFixed cam, NtTarget tg) {
-    static_assert(ROWS == 8 || ROWS == 16 || ROWS == 32 || ROWS == 64, "sixteen row codes to a qword, one to four qwords a wave");
+    static_assert(ROWS == 8 || ROWS == 16 || ROWS == 64, "a wave's rows: a qword of sixteen codes in LDS or fewer, or one row a lane");
     static_assert(WAVES >= 1 && WAVES <= 4 && WAVES * ROWS <= 64, "the codes of a tile are the work of one wave, a row per lane");
+    static_assert(WAVES == 1 ? ROWS == 64 : ROWS <= 16, "one wave a block renders the 64 rows whose codes it worked out itself");
     constexpr int R = ROWS;
-    __shared__ uint32_t s_code[64];
+    // One wave a block: the wave that works out the codes is the one that renders their rows.  Code and tie sets of slot s stay in
+    // lane s, in one register (sets: bits 0..19 and 31 as box_stretch_code2 leaves them; code: bits 20..23), and the row phase
+    // fetches them with v_readlane_b32 on the slot's scalar index: no LDS, no barrier.  More waves a block: another wave's codes
+    // come through LDS.
+    constexpr bool REG = WAVES == 1;
+    constexpr int LDS_N = REG ? 1 : 64;
+    __shared__ uint32_t s_code[LDS_N];
     // ... and the same as one bit per tile row and class (culled / one face / ray by ray / near-tie): the row loops are driven by
-    // 32-bit masks of row bits -- two scalar instructions to step, one to index the row table (masks of nibble positions in a
+    // masks of row bits -- two scalar instructions to step, one to index the row table (masks of nibble positions in a
     // qword cost five and two; the scalar unit is as busy as the vector units in these loops)
-    __shared__ unsigned long long s_rows[4];
+    __shared__ unsigned long long s_rows[REG ? 1 : 4];
     // F32: this kernel is bound by its stores (12 bytes a pixel), not by vector instructions, and renders the near-tie and
     // unclear stretches itself -- no second kernel; the tie sets of its rows stay in LDS
     // ... and so does the packed format up to eight dimensions, where the codes wave's tie sets (LDS) give the near-tie
@@ -982,8 +1011,9 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
     // 6-12 % slower without box_redo_kernel, BoxScene(16) 15 %.
     constexpr bool ALLIN = F32 || N <= NT_BOX_INLINE_MAX_N;
     constexpr bool SETS_LDS = ALLIN && N <= NT_BOX_SETS_MAX_N;
-    __shared__ uint32_t s_sets[SETS_LDS ? 64 : 1];
+    __shared__ uint32_t s_sets[SETS_LDS ? LDS_N : 1];
     __shared__ int s_abort;                  // the codes wave's reading of NtTarget::abort_word: one answer for the whole block
+    uint32_t lane_cs = 0u;                   // REG: code and tie sets of the slot that is this lane
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1022,11 +1052,11 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
     const int tile_row0 = (int)blockIdx.y * WAVES * R;
     // ---- phase 1: the tile's stretch codes, one row per lane of one wave -- a different one from block to block, so that
     // the extra work does not always land on the same SIMD of a CU
-    if (wv == (int)((blockIdx.x + blockIdx.y + frame) % (unsigned)WAVES)) {
+    if (REG || wv == (int)((blockIdx.x + blockIdx.y + frame) % (unsigned)WAVES)) {
         if (tg.abort_word != nullptr) {
             const bool ab = nt_aborted(tg);
-            if (WAVES == 1) { if (ab) return; }
-            else if (lane == 0) s_abort = ab ? 1 : 0;
+            if constexpr (REG) { if (ab) return; }
+            else { if (lane == 0) s_abort = ab ? 1 : 0; }
         }
         uint32_t code = 0u;
         uint32_t row_sets = 0u;
@@ -1043,37 +1073,46 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 row_sets = (uint32_t)(cs >> 32);
             }
         }
-        if (SETS_LDS) s_sets[lane] = row_sets;
-        {
-            const unsigned long long m0 = __builtin_amdgcn_ballot_w64(code == 0u), m1 = __builtin_amdgcn_ballot_w64(code >= 1u && code <= 13u),
-                                     m2 = __builtin_amdgcn_ballot_w64(code == 15u), m3 = __builtin_amdgcn_ballot_w64(code == 14u);
-            if (lane == 0) {
-                s_rows[0] = m0;
-                s_rows[1] = m1;
-                s_rows[2] = m2;
-                s_rows[3] = m3;
+        if constexpr (REG) {
+            lane_cs = (SETS_LDS ? row_sets & 0x800fffffu : 0u) | (code << 20);
+        } else {
+            if (SETS_LDS) s_sets[lane] = row_sets;
+            {
+                const unsigned long long m0 = __builtin_amdgcn_ballot_w64(code == 0u), m1 = __builtin_amdgcn_ballot_w64(code >= 1u && code <= 13u),
+                                         m2 = __builtin_amdgcn_ballot_w64(code == 15u), m3 = __builtin_amdgcn_ballot_w64(code == 14u);
+                if (lane == 0) {
+                    s_rows[0] = m0;
+                    s_rows[1] = m1;
+                    s_rows[2] = m2;
+                    s_rows[3] = m3;
+                }
+            }
+            // rows of wave w in nibbles of s_code[2w] (rows 0..7) and s_code[2w + 1] (rows 8..15)
+            uint32_t packed = code << (4 * (lane & 7));
+            packed |= (uint32_t)__shfl_xor((int)packed, 1, 64);
+            packed |= (uint32_t)__shfl_xor((int)packed, 2, 64);
+            packed |= (uint32_t)__shfl_xor((int)packed, 4, 64);
+            if ((lane & 7) == 0) {
+                const int grp = lane >> 3;                                   // eight rows each
+                const int slot = R == 8 ? 2 * grp : grp;                     // R == 8: wave w's rows are group w
+                s_code[slot] = packed;
+                if (R == 8) s_code[slot + 1] = 0u;
             }
         }
-        // rows of wave w in nibbles of s_code[2w] (rows 0..7) and s_code[2w + 1] (rows 8..15); R == 32: s_code[4w .. 4w + 3]
-        uint32_t packed = code << (4 * (lane & 7));
-        packed |= (uint32_t)__shfl_xor((int)packed, 1, 64);
-        packed |= (uint32_t)__shfl_xor((int)packed, 2, 64);
-        packed |= (uint32_t)__shfl_xor((int)packed, 4, 64);
-        if ((lane & 7) == 0) {
-            const int grp = lane >> 3;                                   // eight rows each
-            const int slot = R == 8 ? 2 * grp : grp;                     // R == 8: wave w's rows are group w
-            s_code[slot] = packed;
-            if (R == 8) s_code[slot + 1] = 0u;
-        }
     }
-    __syncthreads();
-    if (WAVES > 1 && tg.abort_word != nullptr && s_abort != 0) return;
+    if constexpr (!REG) {
+        __syncthreads();
+        if (tg.abort_word != nullptr && s_abort != 0) return;
+    }
 #ifdef NT_EXP_TRACE
     trace_t1 = wall_clock64();
 #endif
-    // Sixteen rows at a time (their codes fill a qword), once or -- R == 32 -- twice per wave: what depends on the column
-    // alone (forward + right*sx, the quadratic for |dir|^2) is set up once for all the wave's rows.
-    constexpr int HALVES = R >= 32 ? R / 16 : 1;
+    // The row phase takes PASS rows a pass: all the wave's rows at once, driven by masks of one bit a row (64 bits in the 64 x 1
+    // shape) -- or, -DNT_BOX_PASS_ROWS=16, that shape's rows sixteen at a time, the same driver run four times.  What depends on
+    // the column alone (forward + right*sx, the quadratic for |dir|^2) is set up once for all the wave's rows.
+    constexpr int PASS = R == 64 ? NT_BOX_PASS_ROWS : R;
+    static_assert(PASS == R || (R == 64 && PASS == 16), "NT_BOX_PASS_ROWS: 64 or 16");
+    typedef typename std::conditional<PASS == 64, unsigned long long, uint32_t>::type mask_t;
     const int wrow0 = tile_row0 + wv * R;                     // the wave's first slot (its first row when rows are not interleaved)
     const int il = tg.row_il;                                 // (scalar) 0, or the stride between a wave's rows
     const int wfirst = il > 0 ? (int)blockIdx.y * WAVES + wv : wrow0;
@@ -1100,10 +1139,9 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         // (instruction selection works block by block and only recognises base + zero-extended 32-bit offset when it sees the
         // extension: the empty asm keeps it from being hoisted out of the row loops)
 #define NT_LANE_OFF() ({ asm volatile("" : "+v"(xoff)); xoff; })
-        // mask &= ~(1 << bit) as ONE scalar instruction (the compiler writes mask & (mask - 1) as an add and an and): the lean loops
-        // run about as many scalar instructions a row as vector ones
-#define NT_CLEAR_BIT(mask, bit) asm("s_bitset0_b32 %0, %1" : "+s"(mask) : "s"(bit))
-#define NT_SET_BIT(mask, bit) asm("s_bitset1_b32 %0, %1" : "+s"(mask) : "s"(bit))
+        // (one scalar instruction each, on 32 or 64 row bits: nt_clear_bit)
+#define NT_CLEAR_BIT(mask, bit) nt_clear_bit(mask, bit)
+#define NT_SET_BIT(mask, bit) nt_set_bit(mask, bit)
         int x = (int)blockIdx.x * 64 + lane;
         x = x < tg.width ? x : tg.width - 1;
         uint32_t xoff = (uint32_t)x * (uint32_t)tg.bpp;
@@ -1145,39 +1183,72 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         bb = bb * inv_maxv2;
         uu = uu * inv_maxv2;
         // the classes of the wave's rows, a bit per row
-        auto rows_of = [&](int k) {
-            const unsigned long long m = s_rows[k];
-            return (((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32) |
-                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m)) >> (wv * R);
-        };
-        const unsigned long long rows_culled = rows_of(0), rows_face = rows_of(1), rows_rays = rows_of(2), rows_tie = rows_of(3);
-        // Which of the wave's rows exist: one slot per lane (lane l <-> slot wrow0 + l), once for all the wave's halves -- the
-        // band arithmetic and the launch parameters it reads stay out of the per-half loop, whose scalar registers are short.
+        const uint32_t lane_code = (lane_cs >> 20) & 15u;       // (REG)
+        unsigned long long rows_culled, rows_face, rows_rays, rows_tie;
+        if constexpr (REG) {
+            // one wave a block: the ballots themselves
+            rows_culled = __builtin_amdgcn_ballot_w64(lane_code == 0u);
+            rows_face = __builtin_amdgcn_ballot_w64(lane_code >= 1u && lane_code <= 13u);
+            rows_rays = __builtin_amdgcn_ballot_w64(lane_code == 15u);
+            rows_tie = __builtin_amdgcn_ballot_w64(lane_code == 14u);
+        } else {
+            auto rows_of = [&](int k) {
+                const unsigned long long m = s_rows[k];
+                return (((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m)) >> (wv * R);
+            };
+            rows_culled = rows_of(0);
+            rows_face = rows_of(1);
+            rows_rays = rows_of(2);
+            rows_tie = rows_of(3);
+        }
+        // Which of the wave's rows exist: one slot per lane (lane l <-> slot wrow0 + l), once for all the wave's rows -- the
+        // band arithmetic and the launch parameters it reads stay out of the row loops, whose scalar registers are short.
         // Every lane stays active in the row loops -- lanes past the right edge redo the last pixel (same bytes, same value)
         // instead of leaving
         const int lrow = il > 0 ? wfirst + il * lane : wrow0 + lane;
         const int ly = nt_image_row(tg, tg.row_begin + lrow);
         const unsigned long long rows_valid = __builtin_amdgcn_ballot_w64(lane < R && lrow < tg.row_count && ly < tg.height);
 #pragma unroll 1
-        for (int half = 0; half < HALVES; ++half) {
-        const int row0 = wrow0 + 16 * half;                   // slot of the half's first row
-        const int hfirst = il > 0 ? wfirst + il * 16 * half : row0;        // ... and that row
+        for (int pass = 0; pass < R / PASS; ++pass) {
+        const int slot0 = PASS * pass;                        // the pass's first slot among the wave's
+        const int row0 = wrow0 + slot0;                       // ... among the launch's
+        const int hfirst = il > 0 ? wfirst + il * slot0 : row0;            // ... and that row
         if (hfirst >= tg.row_count) break;
-        uint32_t redo_bits = 0u;                              // rows (bit rr) left to box_redo_kernel
-        const int cw = (R >= 32 ? (R / 8) * wv + 2 * half : 2 * wv);
-        unsigned long long rowcodes = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[cw + 1]) << 32) |
-                                      (uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[cw]);
-        const uint32_t valid = HALVES > 1 ? (uint32_t)(rows_valid >> (16 * half)) & 0xffffu : (uint32_t)rows_valid;
+        mask_t redo_bits = 0u;                                // rows (bit rr) left to box_redo_kernel
+        // Code and tie sets of slot rr of the pass.  REG: one v_readlane_b32 from the lane that worked them out; otherwise the
+        // codes wave's qword of sixteen nibbles and its dword of sets, from LDS.
+        unsigned long long rowcodes = 0ull;
+        if constexpr (!REG) {
+            rowcodes = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[2 * wv + 1]) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)s_code[2 * wv]);
+        }
+        auto slot_word = [&](int rr) { return (uint32_t)__builtin_amdgcn_readlane((int)lane_cs, slot0 + rr); };
+        auto code_of = [&](int rr) {
+            if constexpr (REG) return (slot_word(rr) >> 20) & 15u;
+            else return (uint32_t)(rowcodes >> (4 * rr)) & 15u;
+        };
+        auto sets_of = [&](int rr) {
+            if constexpr (!SETS_LDS) return 0u;
+            else if constexpr (REG) return slot_word(rr) & 0x800fffffu;
+            else return (uint32_t)__builtin_amdgcn_readfirstlane((int)s_sets[wv * R + rr]);
+        };
+        // the rows of the pass whose code is c (a face's): one vector compare -- of the lane's own code, or of its nibble of the qword
+        auto rows_with_code = [&](uint32_t c) {
+            if constexpr (REG) return (mask_t)(__builtin_amdgcn_ballot_w64(lane_code == c) >> slot0);
+            else return (mask_t)__builtin_amdgcn_ballot_w64(lane < PASS && ((uint32_t)(rowcodes >> (4 * (lane & 15))) & 15u) == c);
+        };
+        const mask_t valid = R > PASS ? (mask_t)(rows_valid >> slot0) & (mask_t)((1ull << (PASS & 63)) - 1ull) : (mask_t)rows_valid;
         // (interleaved rows: the table is in slot order and belongs to this launch's row range)
         const nt_rowtab tab = (nt_rowtab)tg.rowtab + (il > 0 ? row0 : tg.row_begin + row0);
         // (bit rr <-> row row0 + rr; code 14 -- a near-tie stretch -- is not looked at here unless this kernel is all there is)
-        uint32_t quick = (uint32_t)(rows_culled >> (16 * half)) & valid, inner = (uint32_t)(rows_face >> (16 * half)) & valid;
-        uint32_t todo = (uint32_t)((ALLIN ? rows_rays | rows_tie : rows_rays) >> (16 * half)) & valid;
-        if (!ALLIN) redo_bits = (uint32_t)(rows_tie >> (16 * half)) & valid;
+        mask_t quick = (mask_t)(rows_culled >> slot0) & valid, inner = (mask_t)(rows_face >> slot0) & valid;
+        mask_t todo = (mask_t)((ALLIN ? rows_rays | rows_tie : rows_rays) >> slot0) & valid;
+        if (!ALLIN) redo_bits = (mask_t)(rows_tie >> slot0) & valid;
 #ifdef NT_EXP_TRACE
-        trace_rows += (unsigned)__builtin_popcount(quick) | ((unsigned)__builtin_popcount(inner) << 8) |
-                      ((unsigned)__builtin_popcount((uint32_t)(rows_rays >> (16 * half)) & valid) << 16) |
-                      ((unsigned)__builtin_popcount((uint32_t)(rows_tie >> (16 * half)) & valid) << 24);
+        trace_rows += (unsigned)nt_count_bits(quick) | ((unsigned)nt_count_bits(inner) << 8) |
+                      ((unsigned)nt_count_bits((mask_t)(rows_rays >> slot0) & valid) << 16) |
+                      ((unsigned)nt_count_bits((mask_t)(rows_tie >> slot0) & valid) << 24);
 #endif
         if (!F32) {
             // ---- packed RGB: guarded rsq quantisation.  round(|dir[K]|/len * maxval) (and its half for a hit), as in box_pixel,
@@ -1193,6 +1264,14 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             auto lean_rows = [&](auto sel8) {
             constexpr bool SEL8 = decltype(sel8)::value;
             // the packed pixel of a culled row (t: the guarded quotient, d0: dir[0]) and of a one-face row (t and its half)
+            // (-DNT_EXP_RED_BY_SHIFT, measured and not taken, DESIGN.md 4.1: culled_row hands over -dir[0], and the red byte is
+            // q AND the sign of that spread over the dword -- a shift and an AND, both full rate, for the compare and the select.
+            // The same bytes: dir[0] = +-0 has t = 0 either way, and a NaN fails the guard before any store.)
+#ifdef NT_EXP_RED_BY_SHIFT
+#define NT_RED_OF(q, d0) ((q) & (uint32_t)((int32_t)__float_as_uint(d0) >> 31))
+#else
+#define NT_RED_OF(q, d0) ((d0) > 0.0f ? (q) : 0u)
+#endif
             auto put_quick = [&](nt_gptr out, float t, float d0) {
                 if (SEL8) {
                     // 8-bit fields: t + 2^23 has round(t) in its low mantissa byte (t < 255.5; the guard keeps t off the
@@ -1202,12 +1281,12 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                     // select sat behind a wave-uniform branch -- its sign rarely changes within a stretch -- but the branch and
                     // the jump around it are scalar instructions, and the scalar unit is the busier one in this loop: 1.4 % of
                     // the headline call)
-                    NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(d0 > 0.0f ? q : 0u, q, tg.plain_sel);
+                    NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(NT_RED_OF(q, d0), q, tg.plain_sel);
                     return;
                 }
                 uint32_t q = (uint32_t)(t + 0.5f);
                 q = q < tg.plain_maxval ? q : tg.plain_maxval;
-                const uint32_t w = (d0 > 0.0f ? q : 0u) * tg.plain_mul[0] + q * (tg.plain_mul[1] + tg.plain_mul[2]);      // (emit_plain)
+                const uint32_t w = NT_RED_OF(q, d0) * tg.plain_mul[0] + q * (tg.plain_mul[1] + tg.plain_mul[2]);      // (emit_plain)
                 NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
             };
             auto put_face = [&](nt_gptr out, float t, float th) {
@@ -1222,7 +1301,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
             };
             // bit 4k of the result: bits 4k .. 4k + 3 of the mask are all set
-            auto full_groups = [](uint32_t mask) { return mask & (mask >> 1) & (mask >> 2) & (mask >> 3) & 0x1111u; };
+            auto full_groups = [](mask_t mask) { return mask & (mask >> 1) & (mask >> 2) & (mask >> 3) & (mask_t)(PASS == 64 ? 0x1111111111111111ull : 0x1111ull); };
             // The aligned group of four slots g .. g + 3.  row(sy, a, b): one row's arithmetic and its own guard as in the one-row
             // loops below (a, b: what `put` stores; returns "clear"), nothing shared between rows; the four guards' outcomes stay
             // scalar lane masks, and one branch decides for the four stores.  Otherwise the clear rows are stored one by one and the
@@ -1242,7 +1321,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                     put(NT_GROUP_PTR(3) + xo, a[3], b[3]);
                 } else {
                     // (rare) the rows with a lane too close to a rounding boundary go on to the ray-by-ray loop
-                    todo |= ((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
+                    todo |= (mask_t)((fail[0] != 0ull ? 1u : 0u) | (fail[1] != 0ull ? 2u : 0u) | (fail[2] != 0ull ? 4u : 0u) | (fail[3] != 0ull ? 8u : 0u)) << g;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         if (fail[k] == 0ull) {
@@ -1255,7 +1334,11 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             };
             // a culled row: t and dir[0]
             auto culled_row = [&](float sy, float &t, float &d0) {
+#ifdef NT_EXP_RED_BY_SHIFT
+                d0 = upv[0] * sy - base[0];                               // -dir[0], exactly (the same product, the operands swapped)
+#else
                 d0 = base[0] - upv[0] * sy;                               // dir[0], bit for bit
+#endif
                 t = lean_quotient(d0, sy, uu, m2bu, bb);
                 return guard_clear(t);
             };
@@ -1268,18 +1351,18 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             };
             // ---- 1. aligned groups of four culled rows (groups that are mixed or cut by `valid` are left to 2.)
             if (GROUPS) {
-                uint32_t full = full_groups(quick);
+                mask_t full = full_groups(quick);
                 quick &= ~(full * 15u);
                 while (full != 0u) {
-                    const int g = __builtin_ctz(full);
+                    const int g = nt_low_bit(full);
                     NT_CLEAR_BIT(full, g);
                     lean_group(g, culled_row, put_quick);
                 }
             }
             // ---- 2. the remaining culled rows, one by one
-            uint32_t quick_stored = 0u;
-            for (uint32_t rest = quick; rest != 0u;) {
-                const int rr = __builtin_ctz(rest);
+            mask_t quick_stored = 0u;
+            for (mask_t rest = quick; rest != 0u;) {
+                const int rr = nt_low_bit(rest);
                 NT_CLEAR_BIT(rest, rr);
                 NT_ROW_LOAD(rr);
                 float t, d0;
@@ -1291,41 +1374,38 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 }
             }
             todo |= quick & ~quick_stored;
-            // (the one-face rows of a wave mostly share their face: its component of `base` is picked once)
-            uint32_t K0 = 0u;
-            float bK0 = base[0], uK0 = upv[0];
-            if (inner != 0u) {
-                K0 = ((uint32_t)(rowcodes >> (4 * __builtin_ctz(inner))) & 15u) - 1u;
-                pick_component<N>(K0, base, upv, bK0, uK0);
-            }
-            // ---- 3. aligned groups of four rows that are face K0 throughout (the four nibbles of their codes are K0 + 1)
-            if (GROUPS) {
-                uint32_t full = full_groups(inner);
-                const uint32_t same = (K0 + 1u) * 0x1111u;
-                while (full != 0u) {
-                    const int g = __builtin_ctz(full);
-                    NT_CLEAR_BIT(full, g);
-                    if (((uint32_t)(rowcodes >> (4 * g)) & 0xffffu) != same) continue;
-                    inner &= ~(15u << g);
-                    lean_group(g, [&](float sy, float &t, float &th) { return face_row(bK0, uK0, sy, t, th); }, put_face);
+            // The one-face rows, face by face (a wave has one to three): K0 is the face of the first row left, its components of
+            // `base` and `up` are picked once, and one vector compare finds the rows that share it.
+            while (inner != 0u) {
+                const uint32_t code0 = code_of(nt_low_bit(inner));
+                float bK0, uK0;
+                pick_component<N>(code0 - 1u, base, upv, bK0, uK0);
+                mask_t same = inner & rows_with_code(code0);
+                inner &= ~same;
+                // ---- 3. its aligned groups of four
+                if (GROUPS) {
+                    mask_t full = full_groups(same);
+                    same &= ~(full * 15u);
+                    while (full != 0u) {
+                        const int g = nt_low_bit(full);
+                        NT_CLEAR_BIT(full, g);
+                        lean_group(g, [&](float sy, float &t, float &th) { return face_row(bK0, uK0, sy, t, th); }, put_face);
+                    }
                 }
-            }
-            // ---- 4. the remaining one-face rows, one by one
-            uint32_t inner_stored = 0u;
-            for (uint32_t rest = inner; rest != 0u;) {
-                const int rr = __builtin_ctz(rest);
-                NT_CLEAR_BIT(rest, rr);
-                const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
-                NT_ROW_LOAD(rr);
-                float bK = bK0, uK = uK0;
-                if (K != K0) pick_component<N>(K, base, upv, bK, uK);
-                float t, th;
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(!face_row(bK, uK, sy, t, th)) == 0ull, 1)) {
-                    put_face(NT_ROW_PTR() + NT_LANE_OFF(), t, th);
-                    NT_SET_BIT(inner_stored, rr);
+                // ---- 4. its remaining rows, one by one
+                mask_t same_stored = 0u;
+                for (mask_t rest = same; rest != 0u;) {
+                    const int rr = nt_low_bit(rest);
+                    NT_CLEAR_BIT(rest, rr);
+                    NT_ROW_LOAD(rr);
+                    float t, th;
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!face_row(bK0, uK0, sy, t, th)) == 0ull, 1)) {
+                        put_face(NT_ROW_PTR() + NT_LANE_OFF(), t, th);
+                        NT_SET_BIT(same_stored, rr);
+                    }
                 }
+                todo |= same & ~same_stored;
             }
-            todo |= inner & ~inner_stored;
             };
             if (tg.plain_sel != 0u) lean_rows(std::true_type{});
             else lean_rows(std::false_type{});
@@ -1334,8 +1414,8 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             // done as they stand -- but on rows whose code says which x it is, nothing else is
             while (quick != 0u) {
                 // background rows: i = dir[0]; i > 0 ? (i,i,i) : (0,-i,-i) (tracer.hpp:109-113), clamped as channel_value does
-                const int rr = __builtin_ctz(quick);
-                quick &= quick - 1u;
+                const int rr = nt_low_bit(quick);
+                nt_drop_low_bit(quick, rr);
                 NT_ROW_LOAD(rr);
                 const float sq = row_dir<N>(base, upv, sy, dir);
                 const float in = dir[0] / sqrt_wave(sq);
@@ -1343,30 +1423,31 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 box_background(in, r, gb, b_);
                 emit_f32x3_at(tg, NT_ROW_PTR() + NT_LANE_OFF(), r, gb);
             }
-            uint32_t K0 = 0u;
-            float bK0 = base[0], uK0 = upv[0];
-            if (inner != 0u) {
-                K0 = ((uint32_t)(rowcodes >> (4 * __builtin_ctz(inner))) & 15u) - 1u;
-                pick_component<N>(K0, base, upv, bK0, uK0);
-            }
+            // (face by face, as the packed formats' rows)
             while (inner != 0u) {
-                // one face K throughout: sine = d_K * (-sign d_K) <= 0, shade = -sine (tracer.hpp:105-107)
-                const int rr = __builtin_ctz(inner);
-                inner &= inner - 1u;
-                const uint32_t K = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) - 1u;
-                NT_ROW_LOAD(rr);
-                const float sq = row_dir<N>(base, upv, sy, dir);
-                float bK = bK0, uK = uK0;
-                if (K != K0) pick_component<N>(K, base, upv, bK, uK);
-                const float xk = bK - uK * sy;                            // dir[K], bit for bit (the same two operations)
-                const float shade = fabsf(xk / sqrt_wave(sq));
-                emit_f32x3_at(tg, NT_ROW_PTR() + NT_LANE_OFF(), shade * 1.0f, shade * 0.5f);
+                const uint32_t code0 = code_of(nt_low_bit(inner));
+                float bK0, uK0;
+                pick_component<N>(code0 - 1u, base, upv, bK0, uK0);
+                mask_t same = inner & rows_with_code(code0);
+                inner &= ~same;
+                while (same != 0u) {
+                    // one face K throughout: sine = d_K * (-sign d_K) <= 0, shade = -sine (tracer.hpp:105-107)
+                    const int rr = nt_low_bit(same);
+                    nt_drop_low_bit(same, rr);
+                    NT_ROW_LOAD(rr);
+                    const float sq = row_dir<N>(base, upv, sy, dir);
+                    const float xk = bK0 - uK0 * sy;                          // dir[K], bit for bit (the same two operations)
+                    const float shade = fabsf(xk / sqrt_wave(sq));
+                    emit_f32x3_at(tg, NT_ROW_PTR() + NT_LANE_OFF(), shade * 1.0f, shade * 0.5f);
+                }
             }
         }
         while (todo != 0u) {
-            const int rr = __builtin_ctz(todo);
-            todo &= todo - 1u;
-            const bool rowhit = ((uint32_t)(rowcodes >> (4 * rr)) & 15u) != 0u;
+            const int rr = nt_low_bit(todo);
+            nt_drop_low_bit(todo, rr);
+            // (a row with a face code is here because its cheap quantisation failed: the face is known)
+            const int rcode = (int)code_of(rr);
+            const bool rowhit = rcode != 0;
             NT_ROW_LOAD(rr);
             PixelRef pr;
             pr.x = x;
@@ -1375,29 +1456,25 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             pr.hit_index = 0;
             pr.valid = true;
             const float sq = row_dir<N>(base, upv, sy, dir);
-            // (a row with a face code is here because its cheap quantisation failed: the face is known)
-            const int rcode = (int)((uint32_t)(rowcodes >> (4 * rr)) & 15u);
             if (ALLIN) {
                 // everything here: classification, the reference's arithmetic on the faces in question (on the stretch's tie sets
                 // for a near-tie stretch), box_color for rays that start on or in the cube
-                uint32_t sets = 0u;
-                if (SETS_LDS) sets = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_sets[wv * R + 16 * half + rr]);
-                box_pixel<N, !F32, false, false, F32>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit, rcode >= 1 && rcode <= 13 ? rcode - 1 : -1, sets,
-                                                       rcode == 14);
+                box_pixel<N, !F32, false, false, F32>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit, rcode >= 1 && rcode <= 13 ? rcode - 1 : -1,
+                                                       sets_of(rr), rcode == 14);
             } else if (!box_pixel<N, true, true, false, false>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit, rcode >= 1 && rcode <= 13 ? rcode - 1 : -1)) {
-                redo_bits |= 1u << rr;
+                redo_bits |= (mask_t)1u << rr;
             }
         }
         // mark the rows left over in the redo bitmap (clean on entry: box_redo_kernel zeroes what it has read)
         if (!ALLIN && lane == 0) {
             while (redo_bits != 0u) {
-                const int rr = __builtin_ctz(redo_bits);
-                redo_bits &= redo_bits - 1u;
-                const int mrow = il > 0 ? hfirst + il * rr : row0 + rr;
+                const int rr = nt_low_bit(redo_bits);
+                nt_drop_low_bit(redo_bits, rr);
+                const int mrow = il > 0 ? hfirst + il * rr : row0 + rr;     // (hfirst, row0: of slot PASS * pass)
                 atomicOr(tg.redo + ((size_t)frame * tg.row_count + mrow) * tg.redo_words + (blockIdx.x >> 5), 1u << (blockIdx.x & 31));
             }
         }
-        }           // (sixteen rows)
+        }           // (a pass)
     }
 #ifdef NT_EXP_TRACE
     if (lane == 0) {       // the records lie behind the last frame: [frame][tile row][column][wave] x 4 qwords
@@ -1416,6 +1493,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
 #undef NT_LANE_OFF
 #undef NT_CLEAR_BIT
 #undef NT_SET_BIT
+#undef NT_RED_OF
 }
 
 template <int N>

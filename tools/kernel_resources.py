@@ -16,7 +16,7 @@ for o in sorted(glob.glob(os.path.join(ROOT, "ntracer_amd", "build", "*.o"))):
     with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, "dev.co")
         fat = os.path.join(td, "fat.bin")
-        r = subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, o], capture_output=True)
+        r = subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, o, os.path.join(td, "copy.o")], capture_output=True)
         if r.returncode or not os.path.exists(fat):
             continue
         r = subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
