@@ -265,6 +265,50 @@ int nt_scene_get_ambient_occlusion(const nt_scene_t *s, int *count, float *direc
    must be 0.  NT_E_INVALID when the setting is off; NT_E_UNSUPPORTED while a lens or the parallel projection is set. */
 int nt_ambient_occlusion(nt_scene_t *s, int width, int height, int32_t *blocked, const nt_render_opts *opts);
 int nt_ambient_occlusion_device(nt_scene_t *s, int width, int height, void *blocked_dev, const nt_render_opts *opts, void *hip_stream);
+/* Outlines (the reference has none): a line along the silhouette, along every edge where two facets meet at an angle and along
+   every jump in depth, drawn on the device from the primary hits of the render itself.  CompositeScene only.  enabled = 0 takes
+   the setting off; else crease_cos in [0, 1], depth_gap >= 0 (0: no depth lines), every color component and strength in [0, 1],
+   all finite.  Everything below is fp32 without contraction, dot products summed left to right.
+   For a W x H view let R(p) = (dist, item, lane) and nd(p) = normal_dir be what nt_primary_hits defines for pixel p, with the
+   strict_reference and NTRACER_* switches of a render of the scene.  The mask byte of p is 0 when item(p) < 0.  Otherwise it is
+   the OR, over those of the four neighbours q = (x +- 1, y), (x, y +- 1) that lie inside the image, of
+     NT_OUTLINE_SILHOUETTE  if item(q) < 0;
+     nothing                if item(q) == item(p) and lane(q) == lane(p);
+     nothing                if dist(p) > dist(q): the nearer pixel carries the line, so lines are one pixel wide;
+     otherwise, with c = dot(nd(p), nd(q)), la = dot(nd(p), nd(p)), lb = dot(nd(q), nd(q)) and cc = crease_cos * crease_cos
+     computed once,
+       NT_OUTLINE_CREASE    if c * c < cc * (la * lb),
+       NT_OUTLINE_DEPTH     if depth_gap > 0 and (dist(q) - dist(p)) > depth_gap * dist(p).
+   Neighbours outside the image do not count (a 1 x 1 view has no lines) and never cross a frame boundary.  The normals are used
+   as given: they are not all of unit length (hence la * lb) and are compared up to sign, because neighbouring simplices of one
+   facet may be oriented either way.  Transparent surfaces carry no lines: the records are those of opaque hits.
+   A render with the setting on: P the plain single-sample frame with each component clamped to [0, 1]; a pixel with mask != 0
+   becomes (P.c * (1.0f - strength)) + (color.c * strength) for each component c, every other pixel is P, and either goes through
+   the format's conversion and packing as always: with strength = 0 the plain frame byte for byte.  nt_render, nt_render_device,
+   nt_render_frames_device and nt_render_table_device honour the setting and refuse with NT_E_UNSUPPORTED ("outlines ...")
+   before a device is touched, drawing nothing: a supersampling factor above 1 (adaptive or not), row bands (band_world > 1),
+   collect_stats, a lens, the parallel projection, ambient occlusion being on (and a row range, which only a caller inside the
+   library can ask for).  nt_colors_at / nt_calculate_color, nt_primary_hits*, nt_ray_colors*, nt_render_rays*, the ray queries,
+   nt_adaptive_mask* and nt_ambient_occlusion* ignore it.  Opaque scenes up to 10 dimensions on the renders' packet walk are drawn
+   from one walk: 16 bytes of record a pixel a frame.  Every other scene (transparent materials, Solids with the reference's
+   normals, n > 10, NTRACER_FORCE_VAR=1, NTRACER_COMPOSITE_KERNEL set) takes 29 + 4 n bytes a pixel a frame -- base frame, record,
+   normal row, mask; 17 + 4 n for nt_outline_mask*, which draw no base frame -- under the cap of nt_scene_set_supersampling_scratch_mb, and so does the packet walk's record scratch here:
+   larger jobs are cut into chunks of whole frames, and a single frame that does not fit fails with NT_E_UNSUPPORTED before
+   anything is launched.  Not part of a pickled scene.  NT_E_INVALID for a BoxScene and for a value outside its range (the
+   setting stays as it was); NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it; the getter writes
+   through whichever pointers are not NULL. */
+#define NT_OUTLINE_SILHOUETTE 1
+#define NT_OUTLINE_CREASE 2
+#define NT_OUTLINE_DEPTH 4
+int nt_scene_set_outlines(nt_scene_t *s, int enabled, float crease_cos, float depth_gap, const float color[3], float strength);
+int nt_scene_get_outlines(const nt_scene_t *s, int *enabled, float *crease_cos, float *depth_gap, float color[3], float *strength);
+/* The mask bytes of a width x height view of the scene's current camera, mask[y * width + x].  The host form also returns the
+   number of non-zero bytes through `marked` (may be NULL); it holds the scene like nt_colors_at and reads device and
+   strict_reference of `opts`.  The device form writes exactly width * height bytes of device memory at mask_dev and is only
+   enqueued on hip_stream; it also reads abort_device, and every other field of `opts` must be 0.  NT_E_INVALID when the setting
+   is off; NT_E_UNSUPPORTED while a lens or the parallel projection is set. */
+int nt_outline_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts);
+int nt_outline_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream);
 /* CompositeScene.set_shadows/set_camera_light/set_max_reflect_depth/set_ambient_color/
    set_background/add_light rolled into one call */
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p);

@@ -79,6 +79,9 @@ class NtStats(C.Structure):
 
 
 NT_TH_MAX = 24
+NT_OUTLINE_SILHOUETTE = 1        # the bits of an outline mask byte (nt_outline_mask)
+NT_OUTLINE_CREASE = 2
+NT_OUTLINE_DEPTH = 4
 
 
 class NtRayHit(C.Structure):                 # nt_ray_hit: 16 bytes
@@ -140,6 +143,10 @@ SYMBOLS = [
     ("nt_scene_get_ambient_occlusion", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p, f32p, f32p]),
     ("nt_ambient_occlusion", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),
     ("nt_ambient_occlusion_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_scene_set_outlines", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, f32p, C.c_float]),
+    ("nt_scene_get_outlines", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p, f32p, f32p]),
+    ("nt_outline_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
+    ("nt_outline_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_set_params", C.c_int, [C.c_void_p, C.POINTER(NtSceneParams)]),
     ("nt_scene_lock", C.c_int, [C.c_void_p]),
     ("nt_scene_unlock", C.c_int, [C.c_void_p]),

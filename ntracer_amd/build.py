@@ -2,7 +2,7 @@
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The kernels are templates over the dimension; every
 dimension is its own translation unit (csrc/nt_inst_box.hip with -DNT_INST_N=3..24, csrc/nt_inst_composite.hip,
-csrc/nt_inst_query.hip, csrc/nt_inst_hits.hip, csrc/nt_inst_lens.hip, csrc/nt_inst_parallel.hip and csrc/nt_inst_ao.hip with 3..10, csrc/nt_inst_rays.hip and
+csrc/nt_inst_query.hip, csrc/nt_inst_hits.hip, csrc/nt_inst_lens.hip, csrc/nt_inst_parallel.hip, csrc/nt_inst_ao.hip and csrc/nt_inst_outline.hip with 3..10, csrc/nt_inst_rays.hip and
 csrc/nt_inst_adaptive.hip with 3..24),
 compiled in parallel into build/*.o and linked with the host side.  -ffp-contract=off is part of the arithmetic
 contract with the oracle (see csrc/nt_pixel.hpp); -fno-slp-vectorize because packing pairs of independent fp32
@@ -20,7 +20,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libntracer_hip.so")
 DIMS = range(3, 11)
 BOX_ONLY_DIMS = range(11, 25)         # BoxScene kernels alone are also compiled for N = 11..24
-HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp")] + \
+HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp")] + \
       [os.path.join(HERE, "..", "include", "ntracer_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function"]
@@ -41,6 +41,7 @@ def units():
         u.append(("nt_lens_%d" % n, "nt_inst_lens.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_parallel_%d" % n, "nt_inst_parallel.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_ao_%d" % n, "nt_inst_ao.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_outline_%d" % n, "nt_inst_outline.hip", ["-DNT_INST_N=%d" % n]))
     for n in BOX_ONLY_DIMS:
         u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))      # (BoxScene's kernel alone)
@@ -108,7 +109,7 @@ def build(force=False, verbose=False, out=None):
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
         # the composite units are the long ones (~40 s each): start them first
-        long_units = ("nt_inst_composite.hip", "nt_inst_rays.hip", "nt_inst_adaptive.hip", "nt_inst_lens.hip", "nt_inst_parallel.hip")
+        long_units = ("nt_inst_composite.hip", "nt_inst_rays.hip", "nt_inst_adaptive.hip", "nt_inst_lens.hip", "nt_inst_parallel.hip", "nt_inst_outline.hip")
         jobs.sort(key=lambda c: 0 if c[-3].endswith(long_units) else (1 if "nt_inst_query.hip" in c[-3] or "nt_inst_hits.hip" in c[-3] or "nt_inst_ao.hip" in c[-3] else 2))
         with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
             list(ex.map(run, jobs))

@@ -106,7 +106,9 @@ struct DeviceState {
     DevBuf samples;                      // supersampling: the fp32 x 3 samples between the render and the resolve kernel; adaptive
                                          // supersampling: the base frame, the list of flagged pixels and the host forms' mask;
                                          // ambient occlusion: the hit records, both normal rows, the base frame and the counts
-                                         // of a chunk of frames, and on the ray route the ray arrays and answers of a chunk of rows
+                                         // of a chunk of frames, and on the ray route the ray arrays and answers of a chunk of rows;
+                                         // outlines: the hit records of a chunk of frames and, off the packet walk, their normal
+                                         // rows, base frame and mask bytes
     DevBuf refine_count;                 // adaptive supersampling: the length of that list
     DevBuf ao_dirs;                      // ambient occlusion: the table of directions
     unsigned long long ao_version = 0;
@@ -182,6 +184,8 @@ struct nt_scene {
     std::vector<float> ao_dirs;          // ... their directions [ao_count][n], used as given
     float ao_radius = 0.0f, ao_bias = 0.0f, ao_strength = 0.0f;
     unsigned long long ao_version = 1;   // counts the changes of ao_dirs
+    bool outlines = false;               // silhouette, crease and depth lines on the renders (nt_scene_set_outlines)
+    float ol_crease_cos = 0.0f, ol_depth_gap = 0.0f, ol_color[3] = {0, 0, 0}, ol_strength = 0.0f;
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -1325,6 +1329,122 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
 }
 
 // ---------------------------------------------------------------------------------------------
+// outlines (nt_scene_set_outlines; kernels in nt_outline.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+static_assert(NT_OUTLINE_SILHOUETTE == NT_DEV_OUTLINE_SILHOUETTE && NT_OUTLINE_CREASE == NT_DEV_OUTLINE_CREASE &&
+              NT_OUTLINE_DEPTH == NT_DEV_OUTLINE_DEPTH, "the mask bits of the ABI are the kernels'");
+
+// What a render with the setting on refuses, checked by the entry points before a device is touched (and by enqueue_outlines
+// again, for every way in): the lines come from the records of the whole pinhole view, one sample a pixel, a pixel's mask needs
+// its neighbours, and no kernel of it keeps counters.  In front of ao_check: a scene with both settings on is refused here, not
+// drawn with one of them missing.  (The row-range answer guards against callers within this file, as ao_check's does.)
+int outline_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
+    if (!s->outlines) return NT_OK;
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "outlines are not available with a supersampling factor above 1 (%d)", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "outlines are not available with row bands (band_world %d): a pixel's mask needs its neighbours", b.world);
+    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "outlines are not available for a row range");
+    if (stats) return fail(NT_E_UNSUPPORTED, "outlines are not available with collect_stats");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "outlines are not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "outlines are not available while the parallel projection is set");
+    if (s->ao_count > 0) return fail(NT_E_UNSUPPORTED, "outlines are not available while ambient occlusion is on");
+    return NT_OK;
+}
+
+// The mask bytes of every pixel of the job's frames and, with job.fmt, the render that draws them, per chunk of whole frames.
+// Opaque scenes that launch_composite_fixed would give the packet walk take one walk into hit records and outline_shade -- or
+// outline_mark_fixed for the mask alone -- (nt_launch_outline*); every other scene the plain fp32 x 3 base frame into scratch (a
+// render only), a primary-hit pass with normal_dir into scratch (hits_enqueue: every route of it), outline_mark and
+// outline_apply into the caller's image.  Without job.fmt the view is job.view_w x job.view_h, one frame, and the bytes go to
+// `mask_dev`, or with `mask_scratch` stay in scratch: *mask_out.  The scratch -- per pixel and frame 16 bytes of record on the
+// packet route, 29 + 4 n elsewhere: record, normal row, base frame, mask byte (17 + 4 n for the mask alone, which has no base
+// frame) -- sits under the supersampling cap.  Enqueue only.
+int enqueue_outlines(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, uint8_t *mask_dev, bool mask_scratch,
+                     uint8_t **mask_out) {
+    const bool draw = job.fmt != nullptr;
+    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
+    if (int r = outline_check(s, job.bands, job.stats, draw ? job.row_begin : 0, draw ? job.row_count : H, H)) return r;
+    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const int n = s->n;
+    const long long px = (long long)W * H;
+    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const bool fast = composite_route(s, sw).packet_walk;
+    const long long per_frame = fast ? px * (16 + (mask_scratch ? 1 : 0)) : px * (16 + 4 * n + (draw ? 12 : 0) + 1);
+    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "outlines of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
+    if (per_frame > cap)
+        return fail(NT_E_UNSUPPORTED, "outlines of a %d x %d image: the scratch of one frame (%lld bytes) does not fit the scratch buffer of "
+                    "%lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    const int chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame),
+                                                                              std::min<long long>(INT_MAX / px, std::max(sw.chunk_frames, 1))));
+    if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame))) return e;
+    const size_t fpx = (size_t)chunk_frames * px;
+    char *at = (char *)ds->samples.p;
+    void *recs = at; at += fpx * 16;
+    float *nd = nullptr;
+    char *base = nullptr;
+    if (!fast) {
+        nd = (float *)at; at += fpx * n * 4;
+        if (draw) { base = at; at += fpx * 12; }
+    }
+    if (!fast || mask_scratch) mask_dev = mask_dev ? mask_dev : (uint8_t *)at;
+    if (mask_out) *mask_out = mask_dev;
+    NtTarget tg;
+    if (draw) {
+        if (int r = fill_target(s, ds, job, tg)) return r;
+    } else {
+        view_target(s, W, H, job.abort_word, tg);
+    }
+    NtOutline ol{};
+    ol.cc = s->ol_crease_cos * s->ol_crease_cos;
+    ol.depth_gap = s->ol_depth_gap;
+    for (int k = 0; k < 3; ++k) ol.color[k] = s->ol_color[k];
+    ol.strength = s->ol_strength;
+    ol.recs = recs;
+    ol.normal_dir = nd;
+    ol.mask = mask_dev;
+    Format bf;
+    if (int r = plain_f32_format(W, H, bf)) return r;
+    const float *all_cams = nullptr;
+    NtCompositeDev c;
+    if (fast) {
+        if (int e = device_camera(s, ds, job.cam_buf, job.stream, all_cams)) return e;
+        scene_dev(s, ds, sw, job.strict, false, c);
+    }
+    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
+        const int nf = std::min(chunk_frames, job.nframes - f0);
+        NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
+        NtTarget ft = tg;
+        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        ol.nframes = nf;
+        if (fast) {
+            // the packet walk's plane numerators and quad order, as hits_enqueue hands them over, and the records' place
+            if (int e = numerator_scratch(s, ds, sw, nf, li)) return e;
+            if (sw.tile_order) {
+                if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
+            }
+            li.hit_buf = recs;
+            li.hit_frames = nf;
+            ol.cams = all_cams + (size_t)f0 * 4 * n;
+            if (int r = draw ? nt_launch_outline(li, c, ft, ol) : nt_launch_outline_mask(li, c, ft, ol)) return launch_failed(r);
+            continue;
+        }
+        const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
+        if (draw) {
+            if (int e = enqueue(s, ds, base_frame_job(s, job, bf, f0, nf, base, (size_t)px * 12))) return e;
+        }
+        nt_hit_buffers hb{};
+        hb.hits = (nt_ray_hit *)recs;
+        hb.normal_dir = nd;
+        if (int e = hits_enqueue(s, ds, W, H, &hb, px, cams, nf, job.strict, job.abort_word, job.stream)) return e;
+        if (int r = nt_launch_outline_mark(li, ft, ol)) return launch_failed(r);
+        if (draw) {
+            if (int r = nt_launch_outline_apply(job.stream, (const uint32_t *)base, ol, ft)) return launch_failed(r);
+        }
+    }
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // renders through a lens (nt_scene_set_lens; kernels in nt_lens.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1504,6 +1624,8 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
+    if (s->outlines && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
+        return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->ao_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
         return enqueue_ao(s, ds, job, sw, nullptr, nullptr);
     if (s->lens) return enqueue_lens(s, ds, job, sw);
@@ -1564,6 +1686,7 @@ int prepare_stats(DeviceState *ds, hipStream_t st, bool on) {
 
 // what the scene's settings refuse of a render, in the order the render entry points say it, before they touch a device
 int render_checks(const nt_scene *s, const Format &f, const Bands &b, bool stats) {
+    if (int r = outline_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = ao_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, stats, false)) return r;
     if (int r = parallel_check(s, b, stats, false)) return r;
@@ -1596,7 +1719,7 @@ FrameJob render_job(const Format &f, const Bands &b, void *dest_dev, size_t fram
     return job;
 }
 
-// ... and of the entry points that draw nothing (nt_adaptive_mask, nt_ambient_occlusion): one whole view of w x h
+// ... and of the entry points that draw nothing (nt_adaptive_mask, nt_ambient_occlusion, nt_outline_mask): one whole view of w x h
 FrameJob view_job(int w, int h, hipStream_t stream, const nt_render_opts *opts, bool device_form) {
     FrameJob job{};
     job.nframes = 1;
@@ -2394,6 +2517,37 @@ int nt_scene_get_ambient_occlusion(const nt_scene_t *s, int *count, float *direc
     return NT_OK;
 }
 
+int nt_scene_set_outlines(nt_scene_t *s, int enabled, float crease_cos, float depth_gap, const float color[3], float strength) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no outlines");
+    if (enabled) {
+        if (!color) return fail(NT_E_INVALID, "the outline colour is NULL");
+        if (!(crease_cos >= 0.0f && crease_cos <= 1.0f)) return fail(NT_E_INVALID, "the outlines' crease_cos must lie in [0, 1]");
+        if (!(depth_gap >= 0.0f) || !std::isfinite(depth_gap)) return fail(NT_E_INVALID, "the outlines' depth_gap must be finite and not negative");
+        for (int k = 0; k < 3; ++k)
+            if (!(color[k] >= 0.0f && color[k] <= 1.0f)) return fail(NT_E_INVALID, "the outline colour's components must lie in [0, 1]");
+        if (!(strength >= 0.0f && strength <= 1.0f)) return fail(NT_E_INVALID, "the outlines' strength must lie in [0, 1]");
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->outlines = enabled != 0;
+    s->ol_crease_cos = enabled ? crease_cos : 0.0f;
+    s->ol_depth_gap = enabled ? depth_gap : 0.0f;
+    for (int k = 0; k < 3; ++k) s->ol_color[k] = enabled ? color[k] : 0.0f;
+    s->ol_strength = enabled ? strength : 0.0f;
+    return NT_OK;
+}
+
+int nt_scene_get_outlines(const nt_scene_t *s, int *enabled, float *crease_cos, float *depth_gap, float color[3], float *strength) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (enabled) *enabled = s->outlines ? 1 : 0;
+    if (crease_cos) *crease_cos = s->ol_crease_cos;
+    if (depth_gap) *depth_gap = s->ol_depth_gap;
+    if (color) for (int k = 0; k < 3; ++k) color[k] = s->ol_color[k];
+    if (strength) *strength = s->ol_strength;
+    return NT_OK;
+}
+
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");
     if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no lighting parameters");
@@ -2718,6 +2872,48 @@ int nt_ambient_occlusion_device(nt_scene_t *s, int width, int height, void *bloc
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
     return enqueue_ao(s, ds, job, read_switches(), (int *)blocked_dev, nullptr);
+}
+
+namespace {
+// what both forms of nt_outline_mask check before a device is touched
+int outline_validate(const nt_scene *s, int width, int height, const void *mask) {
+    if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (!s->outlines) return fail(NT_E_INVALID, "outlines are off (nt_scene_set_outlines)");
+    if (s->lens || s->parallel > 0.0f)
+        return fail(NT_E_UNSUPPORTED, "the outline mask is not available while a lens or the parallel projection is set");
+    return check_renderable(s);
+}
+}  // namespace
+
+int nt_outline_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts) {
+    if (int r = outline_validate(s, width, height, mask)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const FrameJob job = view_job(width, height, ds->stream, opts, false);
+    uint8_t *mask_dev = nullptr;
+    if (int r = enqueue_outlines(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    const size_t count = (size_t)width * height;
+    HIP_TRY(hipMemcpyAsync(mask, mask_dev, count, hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipStreamSynchronize(ds->stream));
+    if (marked) *marked = (long long)(count - (size_t)std::count(mask, mask + count, (uint8_t)0));
+    return NT_OK;
+}
+
+int nt_outline_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = outline_validate(s, width, height, mask_dev)) return r;
+    if (int r = only_device_strict_abort(opts, "the outline mask reads")) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
+    return enqueue_outlines(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
 }
 
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {

@@ -298,7 +298,34 @@ struct NtAoRays {
     const void *results;                  // [pixels * K] 16-byte records, what the closest-hit query wrote
 };
 
+// Outlines (nt_outline.hpp, nt_var.hip): the mask bytes of every pixel from its hit record and those of its four
+// neighbours.  Every pointer is device memory; a pixel's index is frame * height * width + y * width + x, frames counted within
+// the launch, and its hit record, normal row and mask byte lie at that index.
+#define NT_DEV_OUTLINE_SILHOUETTE 1   // the mask bits (NT_OUTLINE_* of ntracer_hip.h)
+#define NT_DEV_OUTLINE_CREASE 2
+#define NT_DEV_OUTLINE_DEPTH 4
+struct NtOutline {
+    const float *cams;        // fast route: [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    int nframes;
+    const void *recs;         // the pixels' 16-byte hit records (fast route: the launcher's own, li.hit_buf)
+    const float *normal_dir;  // general route: [pixel][n]; rows of pixels without an opaque hit are never read
+    float cc;                 // crease_cos * crease_cos, formed once by the host in fp32
+    float depth_gap;
+    float color[3], strength;
+    uint8_t *mask;            // [pixel] (the mask-only launches and the general route)
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
+// Outlines, fast route (opaque scenes, n <= 10, stack depth <= 32): the packet walk into li.hit_buf (li.hit_frames frames of
+// tg.width * tg.height records), then outline_shade into tg, the whole image of every frame (no bands) ...
+int nt_launch_outline(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol);
+// ... or outline_mark_fixed into ol.mask (tg: the view and the abort word)
+int nt_launch_outline_mask(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol);
+// general route: ol.recs and ol.normal_dir (a primary-hit pass, NtHits) into ol.mask at run-time n ...
+int nt_launch_outline_mark(const NtLaunchInfo &li, const NtTarget &tg, const NtOutline &ol);
+// ... and the base frame (NtAdaptive::base's layout) blended with the colour where the mask is set, into tg.dest, the whole image
+// of ol.nframes frames (no bands)
+int nt_launch_outline_apply(void *stream, const uint32_t *base, const NtOutline &ol, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
 // of `nframes` frames -- 12-byte fp32 x 3 pixels as the render kernels write them, s * tg.row_count rows of `pitch_bytes` a frame

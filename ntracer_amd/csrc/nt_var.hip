@@ -7,6 +7,7 @@
 #include "nt_rays.hpp"
 #include "nt_resolve.hpp"
 #include "nt_adaptive.hpp"
+#include "nt_outline.hpp"
 
 // compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
 #define NT_DECLARE_FIXED(N)                                                                              \
@@ -41,6 +42,9 @@ NT_DECLARE_PARALLEL(3) NT_DECLARE_PARALLEL(4) NT_DECLARE_PARALLEL(5) NT_DECLARE_
 // the ambient occlusion kernel (nt_inst_ao.hip)
 #define NT_DECLARE_AO(N) int nt_ao_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao);
 NT_DECLARE_AO(3) NT_DECLARE_AO(4) NT_DECLARE_AO(5) NT_DECLARE_AO(6) NT_DECLARE_AO(7) NT_DECLARE_AO(8) NT_DECLARE_AO(9) NT_DECLARE_AO(10)
+
+#define NT_DECLARE_OUTLINE(N) int nt_outline_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw);
+NT_DECLARE_OUTLINE(3) NT_DECLARE_OUTLINE(4) NT_DECLARE_OUTLINE(5) NT_DECLARE_OUTLINE(6) NT_DECLARE_OUTLINE(7) NT_DECLARE_OUTLINE(8) NT_DECLARE_OUTLINE(9) NT_DECLARE_OUTLINE(10)
 // (BoxScene alone: 11..24)
 int nt_box_fixed_14(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 int nt_box_fixed_15(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
@@ -2117,6 +2121,69 @@ __global__ __launch_bounds__(256) void ao_apply(const uint32_t *base, const int 
 }
 
 // --------------------------------------------------------------------------------------
+// Outlines (nt_outline.hpp) behind a primary-hit pass with normal rows: every scene the packet route does not
+// take.  outline_mark, one lane a pixel at run-time n in ao_apply's geometry (64 pixels of four rows a block, the grid's z the
+// frame: no division finds a pixel, and the abort word is read once a block), applies outline_pair to the
+// pixel's record and those of its four neighbours within its own frame; the dot products read the two normal rows as stored.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void outline_mark(NtTarget tg, NtOutline ol, int n) {
+    if (nt_aborted(tg)) return;
+    const int tid = (int)threadIdx.x;
+    const int x = (int)blockIdx.x * 64 + (tid & 63);
+    const int y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (y >= tg.height || x >= tg.width) return;
+    const long long pix = ((long long)blockIdx.z * tg.height + y) * tg.width + x;
+    const int4 *recs = reinterpret_cast<const int4 *>(ol.recs);
+    const int4 rec = recs[pix];
+    int m = 0;
+    if (rec.y >= 0) {
+        const float *a = ol.normal_dir + pix * n;
+        for (int k = 0; k < 4; ++k) {
+            const int qx = x + (k == 0 ? -1 : (k == 1 ? 1 : 0));
+            const int qy = y + (k == 2 ? -1 : (k == 3 ? 1 : 0));
+            if (qx < 0 || qy < 0 || qx >= tg.width || qy >= tg.height) continue;
+            const long long qi = pix + (long long)(qy - y) * tg.width + (qx - x);
+            const float *b = ol.normal_dir + qi * n;
+            m |= outline_pair(rec, recs[qi], ol.cc, ol.depth_gap, [&](float &c, float &la, float &lb) {
+                c = a[0] * b[0];
+                la = a[0] * a[0];
+                lb = b[0] * b[0];
+                for (int j = 1; j < n; ++j) {
+                    c = c + a[j] * b[j];
+                    la = la + a[j] * a[j];
+                    lb = lb + b[j] * b[j];
+                }
+            });
+        }
+    }
+    ol.mask[pix] = (uint8_t)m;
+}
+
+// Drawing: a pixel whose mask byte is set becomes (P * (1 - strength)) + (color * strength) through emit_pixel, every other pixel
+// P, the base frame (three big-endian floats a pixel, clamped to [0, 1] by the packer that wrote them).  ao_apply's geometry.
+__global__ __launch_bounds__(256) void outline_apply(const uint32_t *base, NtOutline ol, NtTarget tg) {
+    if (nt_aborted(tg)) return;
+    const int tid = (int)threadIdx.x;
+    const int x = (int)blockIdx.x * 64 + (tid & 63);
+    const int y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (y >= tg.height || x >= tg.width) return;
+    const long long pix = ((long long)blockIdx.z * tg.height + y) * tg.width + x;
+    const uint32_t *p = base + pix * 3;
+    float c[3] = {__uint_as_float(bswap32(p[0])), __uint_as_float(bswap32(p[1])), __uint_as_float(bswap32(p[2]))};
+    if (ol.mask[pix] != 0) {
+        const float keep = 1.0f - ol.strength;
+        for (int k = 0; k < 3; ++k) c[k] = (c[k] * keep) + (ol.color[k] * ol.strength);
+    }
+    PixelRef pr;
+    pr.valid = true;
+    pr.hit_index = 0;
+    pr.x = x;
+    pr.y = y;
+    pr.offset = (long long)blockIdx.z * tg.frame_stride + (long long)y * tg.pitch + (long long)x * tg.bpp;
+    emit_pixel(tg, pr, c[0], c[1], c[2]);
+}
+
+// --------------------------------------------------------------------------------------
 // Adaptive supersampling at run-time n (n = 11..64 -- BoxScene: 25..64 -- and every n under NTRACER_FORCE_VAR=1): the refine
 // kernels of nt_adaptive.hpp on composite_color_var / composite_color_var_t and on rays_box_var's evaluation.  One lane a
 // flagged pixel, one wave a block, the blocks striding over the list.
@@ -2823,4 +2890,47 @@ int nt_launch_ao_apply(void *stream, const uint32_t *base, const int *blocked, i
     const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)nframes);
     hipLaunchKernelGGL(ao_apply, grid, dim3(256), 0, (hipStream_t)stream, base, blocked, count, strength, tg);
     return finish_launch("ambient occlusion drawing kernel launch");
+}
+
+// Outlines.  The fast route (nt_outline.hpp): the fixed-n launcher of the scene's dimension -- the packet walk, then outline_shade
+// (`draw`) or outline_mark_fixed; there is no run-time-n packet walk, and the host sends those scenes through the general route
+// below.
+static int nt_launch_outline_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw) {
+    int r = 0;
+    switch (li.force_var ? 0 : li.n) {
+        case 3: r = nt_outline_fixed_3(li, sc, tg, ol, draw); break;
+        case 4: r = nt_outline_fixed_4(li, sc, tg, ol, draw); break;
+        case 5: r = nt_outline_fixed_5(li, sc, tg, ol, draw); break;
+        case 6: r = nt_outline_fixed_6(li, sc, tg, ol, draw); break;
+        case 7: r = nt_outline_fixed_7(li, sc, tg, ol, draw); break;
+        case 8: r = nt_outline_fixed_8(li, sc, tg, ol, draw); break;
+        case 9: r = nt_outline_fixed_9(li, sc, tg, ol, draw); break;
+        case 10: r = nt_outline_fixed_10(li, sc, tg, ol, draw); break;
+        default:
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no packet walk for outlines at run-time n (n %d)", li.n);
+            return -1;
+    }
+    if (r) return r;
+    return finish_launch("outline kernel launch");
+}
+
+int nt_launch_outline(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol) {
+    return nt_launch_outline_fixed(li, sc, tg, ol, true);
+}
+
+int nt_launch_outline_mask(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol) {
+    return nt_launch_outline_fixed(li, sc, tg, ol, false);
+}
+
+// The general route's two kernels behind nt_launch_hits: every pixel of the launch's frames
+int nt_launch_outline_mark(const NtLaunchInfo &li, const NtTarget &tg, const NtOutline &ol) {
+    const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)ol.nframes);
+    hipLaunchKernelGGL(outline_mark, grid, dim3(256), 0, (hipStream_t)li.stream, tg, ol, li.n);
+    return finish_launch("outline mask kernel launch");
+}
+
+int nt_launch_outline_apply(void *stream, const uint32_t *base, const NtOutline &ol, const NtTarget &tg) {
+    const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)ol.nframes);
+    hipLaunchKernelGGL(outline_apply, grid, dim3(256), 0, (hipStream_t)stream, base, ol, tg);
+    return finish_launch("outline drawing kernel launch");
 }

@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib, builder
 from . import render as _render
 from .render import Color, Material, Scene
+from ._lib import NT_OUTLINE_SILHOUETTE, NT_OUTLINE_CREASE, NT_OUTLINE_DEPTH  # noqa: F401
 
 BATCH_SIZE = _lib.NT_BATCH_SIZE     # tracer.hpp:34-38 (SSE reference build)
 _ROUNDING_FUZZ = 1.1920928955078125e-07 * 10.0     # tracer.hpp:25
@@ -1006,6 +1007,72 @@ class _SceneBase(Scene):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(L.nt_ambient_occlusion_device(self._handle, width, height, C.c_void_p(counts.data_ptr()), C.byref(opts), C.c_void_p(stream)))
         return counts
+
+    def set_outlines(self, crease_angle=0.1, depth_gap=0.02, color=(0, 0, 0), strength=1.0):
+        """Draw a line along the silhouette, along every edge where two facets meet and along every jump in depth (DESIGN.md
+        4.11, include/ntracer_hip.h), from the primary hits of the render itself.  A pixel with an opaque hit is marked when one
+        of its four neighbours hits nothing, or hits another simplex no nearer than the pixel's own whose normal makes more than
+        `crease_angle` (radians, up to sign; crease_cos = float32(cos(angle))) with the pixel's, or which lies farther by more
+        than `depth_gap` times the pixel's distance (0: no depth lines); a marked pixel's plain colour P becomes
+        P * (1 - strength) + color * strength.  set_outlines(None) takes the setting off.  CompositeScene only.  Supersampling,
+        row bands, statistics, a lens, the parallel projection and ambient occlusion are refused with it; calculate_color /
+        colors_at, primary_hits, ray_colors, render_rays, the ray queries, refinement_mask and occlusion_counts ignore it.  A
+        view setting like fov: not pickled."""
+        L = _lib.lib()
+        if crease_angle is None:
+            _lib.check(L.nt_scene_set_outlines(self._handle, 0, 0.0, 0.0, None, 0.0))
+            return
+        for v in (crease_angle, depth_gap, strength):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("crease_angle, depth_gap and strength must be numbers")
+        col = np.ascontiguousarray([float(c) for c in color], f32)
+        if col.shape != (3,):
+            raise ValueError("color must have three components")
+        if not 0.0 <= float(crease_angle) <= math.pi / 2:
+            raise ValueError("crease_angle must lie between 0 and pi / 2 radians")
+        crease_cos = f32(math.cos(float(crease_angle)))
+        _lib.check(L.nt_scene_set_outlines(self._handle, 1, float(crease_cos), float(depth_gap), col.ctypes.data_as(_lib.f32p), float(strength)))
+
+    @property
+    def outlines(self):
+        """None, or a dict of the setting: crease_cos, depth_gap, color (three floats), strength"""
+        on, cc, gap, st = C.c_int(0), C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        col = np.zeros(3, f32)
+        _lib.check(_lib.lib().nt_scene_get_outlines(self._handle, C.byref(on), C.byref(cc), C.byref(gap), col.ctypes.data_as(_lib.f32p), C.byref(st)))
+        if not on.value:
+            return None
+        return dict(crease_cos=float(cc.value), depth_gap=float(gap.value), color=tuple(float(c) for c in col), strength=float(st.value))
+
+    def outline_mask(self, width, height, device=None, strict_reference=None):
+        """The outline mask of a width x height view of the scene's camera under the setting that is on (nt_outline_mask): uint8
+        [height][width], 0 or an OR of NT_OUTLINE_SILHOUETTE, NT_OUTLINE_CREASE and NT_OUTLINE_DEPTH -- a numpy array, or with
+        `device` a torch device a torch tensor there, enqueued on torch's current stream."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        L = _lib.lib()
+        if device is None:
+            opts = _lib.NtRenderOpts()
+            opts.device = -1
+            if strict_reference is None:
+                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+            opts.strict_reference = 1 if strict_reference else 0
+            mask = np.zeros((height, width), np.uint8)
+            _lib.check(L.nt_outline_mask(self._handle, width, height, mask.ctypes.data, None, C.byref(opts)))
+            return mask
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self.outlines is None:
+            raise ValueError("outlines are off (set_outlines)")
+        mask = torch.empty((height, width), dtype=torch.uint8, device=dev)
+        opts = self._rays_opts(dev, strict_reference)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_outline_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return mask
 
     def set_lens(self, lens):
         """Render through `lens` (a Lens of the image's size) instead of the pinhole; None takes it off.  fov is ignored
