@@ -1,9 +1,11 @@
 """Build libntracer_hip.so in-tree:  python -m ntracer_amd.build
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The kernels are templates over the dimension; every
-dimension is its own translation unit (csrc/nt_inst_box.hip with -DNT_INST_N=3..24, csrc/nt_inst_composite.hip,
-csrc/nt_inst_query.hip, csrc/nt_inst_hits.hip, csrc/nt_inst_lens.hip, csrc/nt_inst_parallel.hip, csrc/nt_inst_ao.hip and csrc/nt_inst_outline.hip with 3..10, csrc/nt_inst_rays.hip and
-csrc/nt_inst_adaptive.hip with 3..24),
+dimension is its own translation unit: csrc/nt_inst_X.hip with -DNT_INST_N=N defines the one launcher nt_X_fixed<N> that
+csrc/nt_dispatch.hpp declares and csrc/nt_var.hip dispatches to (and does not compile without the macro).  N = 3..24 for
+nt_inst_box.hip, nt_inst_rays.hip and nt_inst_adaptive.hip (BoxScene's kernels; CompositeScene's up to 10), 3..10 for
+nt_inst_composite.hip, nt_inst_query.hip, nt_inst_hits.hip, nt_inst_lens.hip, nt_inst_parallel.hip, nt_inst_ao.hip and
+nt_inst_outline.hip.  units() is the list, and tests/test_dispatch.py holds the library's exports to it.  They are
 compiled in parallel into build/*.o and linked with the host side.  -ffp-contract=off is part of the arithmetic
 contract with the oracle (see csrc/nt_pixel.hpp); -fno-slp-vectorize because packing pairs of independent fp32
 operations into v_pk_* costs more register shuffling than it saves here (measured: 2-4 %)."""
@@ -20,7 +22,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libntracer_hip.so")
 DIMS = range(3, 11)
 BOX_ONLY_DIMS = range(11, 25)         # BoxScene kernels alone are also compiled for N = 11..24
-HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp")] + \
+HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp", "nt_dispatch.hpp")] + \
       [os.path.join(HERE, "..", "include", "ntracer_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function"]

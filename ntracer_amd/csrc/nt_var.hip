@@ -1,5 +1,7 @@
 // nt_var.hip -- the run-time-n kernels (the reference's generic `tracern` / var_geometry.hpp path: n-vectors in LDS as
-// [k][lane]) and the dispatch over the dimension: nt_launch_box / nt_launch_composite.
+// [k][lane]), the small kernels around them (camera upload, lens / parallel / ambient occlusion expansion, outline marks), and
+// every nt_launch_* of nt_device.hpp: the dispatch over the dimension (nt_dispatch.hpp) to the compile-time-N launchers of the
+// nt_inst_*.hip units, or to the run-time-n kernels here.
 #include "nt_box.hpp"
 #include "nt_composite.hpp"
 #include "nt_query.hpp"
@@ -8,58 +10,8 @@
 #include "nt_resolve.hpp"
 #include "nt_adaptive.hpp"
 #include "nt_outline.hpp"
-
-// compile-time-N launchers, one translation unit per N (nt_inst_box.hip / nt_inst_composite.hip)
-#define NT_DECLARE_FIXED(N)                                                                              \
-    int nt_box_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);               \
-    int nt_composite_fixed_##N(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg); \
-    int nt_query_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q);                        \
-    int nt_hits_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h);
-NT_DECLARE_FIXED(3) NT_DECLARE_FIXED(4) NT_DECLARE_FIXED(5) NT_DECLARE_FIXED(6)
-NT_DECLARE_FIXED(7) NT_DECLARE_FIXED(8) NT_DECLARE_FIXED(9) NT_DECLARE_FIXED(10)
-// the ray-colour launchers (nt_inst_rays.hip): CompositeScene 3..10, BoxScene 3..24
-#define NT_DECLARE_RAYS(N) int nt_rays_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtRayJob &job, const NtTarget &tg);
-#define NT_DECLARE_RAYS_BOX(N) int nt_rays_box_fixed_##N(const NtLaunchInfo &li, const NtRayJob &job, const NtTarget &tg);
-NT_DECLARE_RAYS(3) NT_DECLARE_RAYS(4) NT_DECLARE_RAYS(5) NT_DECLARE_RAYS(6) NT_DECLARE_RAYS(7) NT_DECLARE_RAYS(8) NT_DECLARE_RAYS(9) NT_DECLARE_RAYS(10)
-NT_DECLARE_RAYS_BOX(3) NT_DECLARE_RAYS_BOX(4) NT_DECLARE_RAYS_BOX(5) NT_DECLARE_RAYS_BOX(6) NT_DECLARE_RAYS_BOX(7) NT_DECLARE_RAYS_BOX(8)
-NT_DECLARE_RAYS_BOX(9) NT_DECLARE_RAYS_BOX(10) NT_DECLARE_RAYS_BOX(11) NT_DECLARE_RAYS_BOX(12) NT_DECLARE_RAYS_BOX(13) NT_DECLARE_RAYS_BOX(14)
-NT_DECLARE_RAYS_BOX(15) NT_DECLARE_RAYS_BOX(16) NT_DECLARE_RAYS_BOX(17) NT_DECLARE_RAYS_BOX(18) NT_DECLARE_RAYS_BOX(19) NT_DECLARE_RAYS_BOX(20)
-NT_DECLARE_RAYS_BOX(21) NT_DECLARE_RAYS_BOX(22) NT_DECLARE_RAYS_BOX(23) NT_DECLARE_RAYS_BOX(24)
-// the packet route of a render through a lens (nt_inst_lens.hip)
-#define NT_DECLARE_REFINE(N) int nt_refine_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtRefine &rf, const NtTarget &tg);
-#define NT_DECLARE_REFINE_BOX(N) int nt_refine_box_fixed_##N(const NtLaunchInfo &li, const NtRefine &rf, const NtTarget &tg);
-NT_DECLARE_REFINE(3) NT_DECLARE_REFINE(4) NT_DECLARE_REFINE(5) NT_DECLARE_REFINE(6) NT_DECLARE_REFINE(7) NT_DECLARE_REFINE(8) NT_DECLARE_REFINE(9) NT_DECLARE_REFINE(10)
-NT_DECLARE_REFINE_BOX(3) NT_DECLARE_REFINE_BOX(4) NT_DECLARE_REFINE_BOX(5) NT_DECLARE_REFINE_BOX(6) NT_DECLARE_REFINE_BOX(7) NT_DECLARE_REFINE_BOX(8)
-NT_DECLARE_REFINE_BOX(9) NT_DECLARE_REFINE_BOX(10) NT_DECLARE_REFINE_BOX(11) NT_DECLARE_REFINE_BOX(12) NT_DECLARE_REFINE_BOX(13) NT_DECLARE_REFINE_BOX(14)
-NT_DECLARE_REFINE_BOX(15) NT_DECLARE_REFINE_BOX(16) NT_DECLARE_REFINE_BOX(17) NT_DECLARE_REFINE_BOX(18) NT_DECLARE_REFINE_BOX(19) NT_DECLARE_REFINE_BOX(20)
-NT_DECLARE_REFINE_BOX(21) NT_DECLARE_REFINE_BOX(22) NT_DECLARE_REFINE_BOX(23) NT_DECLARE_REFINE_BOX(24)
-
-#define NT_DECLARE_LENS(N) int nt_lens_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln);
-NT_DECLARE_LENS(3) NT_DECLARE_LENS(4) NT_DECLARE_LENS(5) NT_DECLARE_LENS(6) NT_DECLARE_LENS(7) NT_DECLARE_LENS(8) NT_DECLARE_LENS(9) NT_DECLARE_LENS(10)
-// the packet route of a render under the parallel projection (nt_inst_parallel.hip)
-#define NT_DECLARE_PARALLEL(N) int nt_parallel_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl);
-NT_DECLARE_PARALLEL(3) NT_DECLARE_PARALLEL(4) NT_DECLARE_PARALLEL(5) NT_DECLARE_PARALLEL(6) NT_DECLARE_PARALLEL(7) NT_DECLARE_PARALLEL(8) NT_DECLARE_PARALLEL(9) NT_DECLARE_PARALLEL(10)
-// the ambient occlusion kernel (nt_inst_ao.hip)
-#define NT_DECLARE_AO(N) int nt_ao_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao);
-NT_DECLARE_AO(3) NT_DECLARE_AO(4) NT_DECLARE_AO(5) NT_DECLARE_AO(6) NT_DECLARE_AO(7) NT_DECLARE_AO(8) NT_DECLARE_AO(9) NT_DECLARE_AO(10)
-
-#define NT_DECLARE_OUTLINE(N) int nt_outline_fixed_##N(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw);
-NT_DECLARE_OUTLINE(3) NT_DECLARE_OUTLINE(4) NT_DECLARE_OUTLINE(5) NT_DECLARE_OUTLINE(6) NT_DECLARE_OUTLINE(7) NT_DECLARE_OUTLINE(8) NT_DECLARE_OUTLINE(9) NT_DECLARE_OUTLINE(10)
-// (BoxScene alone: 11..24)
-int nt_box_fixed_14(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_15(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_16(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_11(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_12(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_13(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_17(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_18(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_19(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_20(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_21(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_22(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_23(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
-int nt_box_fixed_24(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
+#include "nt_dispatch.hpp"
+#include <climits>
 
 namespace {
 
@@ -423,8 +375,20 @@ struct VarLds {
     int *mbox;       // [NT_MBOX][64]
 };
 
-__device__ __forceinline__ size_t var_lds_bytes(int depth, int n) {
+// The dynamic LDS of every walk kernel below, one wave a block: what var_lds_carve lays out, so the host sizes a launch by the
+// expression the kernels carve by -- ray 8 n, dv 4 n, ps 4 n, stack 4 depth and mbox 4 NT_MBOX bytes a lane
+__host__ __device__ __forceinline__ size_t var_lds_bytes(int depth, int n) {
     return (size_t)64 * ((size_t)n * 16 + (size_t)depth * 4 + (size_t)NT_MBOX * 4);
+}
+__device__ __forceinline__ void var_lds_carve(char *p, int n, int depth, VarLds &L, WaveLds &w) {
+    L.ray = reinterpret_cast<float2 *>(p);
+    L.dv = reinterpret_cast<float *>(p + (size_t)64 * n * 8);
+    L.ps = L.dv + (size_t)64 * n;
+    L.stack = reinterpret_cast<int *>(L.ps + (size_t)64 * n);
+    L.mbox = L.stack + (size_t)64 * depth;
+    w.ray = L.ray;
+    w.stack = L.stack;
+    w.mbox = L.mbox;
 }
 
 struct VarCtx {
@@ -939,6 +903,13 @@ struct VarFrames {
 enum { VF_DEPTH = 0, VF_SKIP_ITEM, VF_SKIP_LANE, VF_NSURF, VF_J, VF_R, VF_SPEC = VF_R + 3, VF_R0 = VF_SPEC + 3, VF_C = VF_R0 + 3,
        VF_SPEC_A = VF_C + 3, VF_REFL, VF_SURF, VF_WORDS = VF_SURF + 3 * (NT_TH_MAX + 1) };
 __host__ __device__ __forceinline__ int var_frame_words(int n) { return 4 * n + VF_WORDS; }
+
+// the frame stack of lane slot `slot` of the launch's scratch (filled in place: returned by value, the kernels' code changes)
+__device__ __forceinline__ void var_frames(VarFrames &fr, const NtCompositeDev &sc, long long slot, int n) {
+    fr.base = sc.tframes + slot;
+    fr.stride = sc.checked_lanes;
+    fr.fw = var_frame_words(n);
+}
 
 #define FRW(f, w) (fr.base[((long long)(f) * fr.fw + (w)) * fr.stride])
 #define FRI(f, w) (reinterpret_cast<int *>(fr.base)[((long long)(f) * fr.fw + (w)) * fr.stride])
@@ -1493,6 +1464,7 @@ __global__ __launch_bounds__(64) void composite_kernel_var_t(NtCamera cam, NtCom
     const int lane = (int)threadIdx.x;
     VarLds L;
     {
+        // var_lds_carve's layout, written out: through the function this kernel alone compiles to other code
         char *p = reinterpret_cast<char *>(lds_raw);
         L.ray = reinterpret_cast<float2 *>(p);
         L.dv = reinterpret_cast<float *>(p + (size_t)64 * n * 8);
@@ -1512,9 +1484,7 @@ __global__ __launch_bounds__(64) void composite_kernel_var_t(NtCamera cam, NtCom
     ck.n_batches = sc.n_batches;
     ck.n_triangles = sc.n_triangles;
     VarFrames fr;
-    fr.base = sc.tframes + slot;
-    fr.stride = sc.checked_lanes;
-    fr.fw = var_frame_words(n);
+    var_frames(fr, sc, slot, n);
     const VarCtx cx = {sc, L, w, n, lane};
     const long long total = (long long)tiles_x * tiles_y * frames;
     for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
@@ -1555,20 +1525,9 @@ __global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompo
     extern __shared__ float2 lds_raw[];
     if (nt_aborted(tg)) return;
     const int lane = (int)threadIdx.x;
-    const int depth = sc.stack_depth;
     VarLds L;
-    {
-        char *p = reinterpret_cast<char *>(lds_raw);
-        L.ray = reinterpret_cast<float2 *>(p);
-        L.dv = reinterpret_cast<float *>(p + (size_t)64 * n * 8);
-        L.ps = L.dv + (size_t)64 * n;
-        L.stack = reinterpret_cast<int *>(L.ps + (size_t)64 * n);
-        L.mbox = L.stack + (size_t)64 * depth;
-    }
     WaveLds w;
-    w.ray = L.ray;
-    w.stack = L.stack;
-    w.mbox = L.mbox;
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const PixelRef pr = tg.colors_out ? locate_pixel<8, 8>(tg, 0, 0, lane) : locate_pixel<8, 8>(tg, lane & 7, lane >> 3, lane);
     if (!pr.valid) return;
     const float *c = cam.buf ? cam.buf + (size_t)blockIdx.z * 4 * n : nullptr;
@@ -1602,17 +1561,6 @@ __global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompo
 // above.  One lane per ray and one wave a block, as the run-time-n render kernels have it -- their n-vectors in LDS make
 // four waves' worth too much at the upper dimensions -- so lane l of block b takes ray 64 b + l, and the blocks stride on.
 // --------------------------------------------------------------------------------------
-__device__ __forceinline__ void query_var_lds(char *p, int n, int depth, VarLds &L, WaveLds &w) {
-    L.ray = reinterpret_cast<float2 *>(p);
-    L.dv = reinterpret_cast<float *>(p + (size_t)64 * n * 8);
-    L.ps = L.dv + (size_t)64 * n;
-    L.stack = reinterpret_cast<int *>(L.ps + (size_t)64 * n);
-    L.mbox = L.stack + (size_t)64 * depth;
-    w.ray = L.ray;
-    w.stack = L.stack;
-    w.mbox = L.mbox;
-}
-
 __device__ __forceinline__ void query_store_normal_var(const NtQuery &q, long long r, int n, const float *no, const float *nd) {
     if (q.normal_origin) for (int k = 0; k < n; ++k) q.normal_origin[r * n + k] = no[k];
     if (q.normal_dir) for (int k = 0; k < n; ++k) q.normal_dir[r * n + k] = nd[k];
@@ -1623,7 +1571,7 @@ __global__ __launch_bounds__(64) void query_closest_var(NtCompositeDev sc, NtQue
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
         if (query_aborted(q)) return;
@@ -1656,7 +1604,7 @@ __global__ __launch_bounds__(64) void query_closest_var_t(NtCompositeDev sc, NtQ
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     Checked ck;
     ck.bits = sc.checked + ((long long)blockIdx.x * 64 + lane);
@@ -1692,7 +1640,7 @@ __global__ __launch_bounds__(64) void query_occluded_var(NtCompositeDev sc, NtQu
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
         if (query_aborted(q)) return;
@@ -1718,7 +1666,7 @@ __global__ __launch_bounds__(64) void query_occluded_var_t(NtCompositeDev sc, Nt
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     for (long long base = (long long)blockIdx.x * 64; base < q.count; base += (long long)gridDim.x * 64) {
         if (query_aborted(q)) return;
@@ -1770,7 +1718,7 @@ __global__ __launch_bounds__(64) void hits_closest_var(NtCompositeDev sc, NtTarg
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     const long long total = (long long)tiles_x * tiles_y * h.nframes;
     for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
@@ -1797,7 +1745,7 @@ __global__ __launch_bounds__(64) void hits_closest_var_t(NtCompositeDev sc, NtTa
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     Checked ck;
     ck.bits = sc.checked + ((long long)blockIdx.x * 64 + lane);
@@ -1856,7 +1804,7 @@ __global__ __launch_bounds__(64) void rays_color_var(NtCompositeDev sc, NtRayJob
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     for (long long base = (long long)blockIdx.x * 64; base < job.count; base += (long long)gridDim.x * 64) {
         if (nt_aborted(tg)) return;                       // (one wave a block)
@@ -1876,7 +1824,7 @@ __global__ __launch_bounds__(64) void rays_color_var_t(NtCompositeDev sc, NtRayJ
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     const long long slot = (long long)blockIdx.x * 64 + lane;
     Checked ck;
@@ -1886,9 +1834,7 @@ __global__ __launch_bounds__(64) void rays_color_var_t(NtCompositeDev sc, NtRayJ
     ck.n_batches = sc.n_batches;
     ck.n_triangles = sc.n_triangles;
     VarFrames fr;
-    fr.base = sc.tframes + slot;
-    fr.stride = sc.checked_lanes;
-    fr.fw = var_frame_words(n);
+    var_frames(fr, sc, slot, n);
     for (long long base = (long long)blockIdx.x * 64; base < job.count; base += (long long)gridDim.x * 64) {
         if (nt_aborted(tg)) return;
         const long long r = base + lane;
@@ -2214,7 +2160,7 @@ __global__ __launch_bounds__(64) void refine_color_var(NtCompositeDev sc, NtRefi
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     const long long count = (long long)*rf.count;
     const int ss = rf.s * rf.s;
@@ -2238,7 +2184,7 @@ __global__ __launch_bounds__(64) void refine_color_var_t(NtCompositeDev sc, NtRe
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
-    query_var_lds(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
     const VarCtx cx = {sc, L, w, n, lane};
     const long long slot = (long long)blockIdx.x * 64 + lane;
     Checked ck;
@@ -2248,9 +2194,7 @@ __global__ __launch_bounds__(64) void refine_color_var_t(NtCompositeDev sc, NtRe
     ck.n_batches = sc.n_batches;
     ck.n_triangles = sc.n_triangles;
     VarFrames fr;
-    fr.base = sc.tframes + slot;
-    fr.stride = sc.checked_lanes;
-    fr.fw = var_frame_words(n);
+    var_frames(fr, sc, slot, n);
     const long long count = (long long)*rf.count;
     const int ss = rf.s * rf.s;
     for (long long base = (long long)blockIdx.x * 64; base < count; base += (long long)gridDim.x * 64) {
@@ -2363,6 +2307,73 @@ __global__ __launch_bounds__(256) void upload_kernel(const float *__restrict__ s
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (i < count) dst[i] = src[i];
 }
+
+// --------------------------------------------------------------------------------------
+// What the nt_launch_* below share.  The guards of a run-time-n launch, each with its message and its code in one place ...
+// --------------------------------------------------------------------------------------
+int var_dim_check(int n) {
+    if (n >= 3 && n <= NT_DEV_MAX_DIM) return 0;
+    snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", n);
+    return -2;
+}
+
+// A walk kernel is about to be launched: the dimension check, the LDS the kernel carves (var_lds_bytes), refused beyond the
+// 160 KiB of a CU, and beyond the 64 KiB a kernel gets unasked the attribute that admits it.  0 and `lds`; -2 (dimension) or
+// -1 (too deep) and the launch error.
+int var_walk_ready(int n, const NtCompositeDev &sc, const void *kernel, size_t &lds) {
+    if (const int r = var_dim_check(n)) return r;
+    lds = var_lds_bytes(sc.stack_depth, n);
+    if (lds > 160 * 1024) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", n, sc.stack_depth);
+        return -1;
+    }
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return 0;
+}
+
+// the kernels that shade through sc.tframes: the `checked` columns must be there, a block's worth at least
+int var_frames_check(int n, const NtCompositeDev &sc) {
+    if (n >= 3 && n <= NT_DEV_MAX_DIM && sc.checked && sc.checked_lanes >= 64) return 0;
+    snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "run-time-n transparency kernel: bad launch (n %d)", n);
+    return -2;
+}
+
+int no_checked_scratch() {
+    snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: transparent scene without the checked-list scratch");
+    return -1;
+}
+
+// ... the kernel of a <true> / <false> pair that sc.alias_normals picks ...
+template <typename K>
+const void *alias_kernel(const NtCompositeDev &sc, K *aliased, K *clean) {
+    return reinterpret_cast<const void *>(sc.alias_normals ? aliased : clean);
+}
+
+// ... and the grids: as many one-wave blocks as the `checked` scratch has lane columns for, `want` at the most; the blocks of
+// 256 lanes of a kernel that strides over `count` items (none: there is nothing to launch)
+long long checked_blocks(const NtCompositeDev &sc, long long want = LLONG_MAX) {
+    const long long have = sc.checked_lanes / 64;
+    return want < have ? want : have;
+}
+
+long long stride_blocks(long long count) {
+    const long long blocks = (count + 255) / 256;
+    return blocks > NT_RAYS_MAX_BLOCKS ? NT_RAYS_MAX_BLOCKS : blocks;
+}
+
+// The routes that have compile-time-N kernels alone (a lens, the parallel projection, ambient occlusion, outlines): f is
+// `[&](auto N) { return nt_X_fixed<N>(...); }`.  Any other n, and every n under force_var: "internal: <none> at run-time n" --
+// the host sends those scenes another way.
+template <typename F>
+int launch_fixed_only(const NtLaunchInfo &li, const char *none, const char *what, F &&f) {
+    int r = 0;
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, f)) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: %s at run-time n (n %d)", none, li.n);
+        return -1;
+    }
+    if (r) return r;
+    return finish_launch(what);
+}
 }  // namespace
 
 int nt_launch_upload(void *stream, const float *src_pinned, float *dst, int count) {
@@ -2376,40 +2387,17 @@ int nt_launch_resolve(int s, void *stream, const void *samples, long long frame_
 }
 
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg) {
-    switch (li.force_var ? 0 : li.n) {
-        case 3: nt_box_fixed_3(li, cam, tg); break;
-        case 4: nt_box_fixed_4(li, cam, tg); break;
-        case 5: nt_box_fixed_5(li, cam, tg); break;
-        case 6: nt_box_fixed_6(li, cam, tg); break;
-        case 7: nt_box_fixed_7(li, cam, tg); break;
-        case 8: nt_box_fixed_8(li, cam, tg); break;
-        case 9: nt_box_fixed_9(li, cam, tg); break;
-        case 10: nt_box_fixed_10(li, cam, tg); break;
-        case 11: nt_box_fixed_11(li, cam, tg); break;
-        case 12: nt_box_fixed_12(li, cam, tg); break;
-        case 13: nt_box_fixed_13(li, cam, tg); break;
-        case 14: nt_box_fixed_14(li, cam, tg); break;
-        case 15: nt_box_fixed_15(li, cam, tg); break;
-        case 16: nt_box_fixed_16(li, cam, tg); break;
-        case 17: nt_box_fixed_17(li, cam, tg); break;
-        case 18: nt_box_fixed_18(li, cam, tg); break;
-        case 19: nt_box_fixed_19(li, cam, tg); break;
-        case 20: nt_box_fixed_20(li, cam, tg); break;
-        case 21: nt_box_fixed_21(li, cam, tg); break;
-        case 22: nt_box_fixed_22(li, cam, tg); break;
-        case 23: nt_box_fixed_23(li, cam, tg); break;
-        case 24: nt_box_fixed_24(li, cam, tg); break;
-        default: {
-            // packed plain RGB of <= 10 bits in one aligned dword: the rows kernel (codes + lean loops), if its n-vectors fit LDS
-            const size_t lds_rows = ((size_t)li.n * 256 + (size_t)4 * li.n + 4) * sizeof(float);
-            if (!tg.colors_out && tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4 && tg.aligned4 && lds_rows <= 160 * 1024 &&
-                li.box_var_rows) {
-                const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.row_count + 31) / 32), (unsigned)li.nframes);
-                if (lds_rows > 64 * 1024)
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(box_rows_kernel_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows);
-                hipLaunchKernelGGL(box_rows_kernel_var, grid, dim3(256), lds_rows, (hipStream_t)li.stream, cam, tg);
-                break;
-            }
+    int r;          // (launch_box_fixed returns 0 and nothing else)
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_box_fixed<decltype(N)::value>(li, cam, tg); })) {
+        // packed plain RGB of <= 10 bits in one aligned dword: the rows kernel (codes + lean loops), if its n-vectors fit LDS
+        const size_t lds_rows = ((size_t)li.n * 256 + (size_t)4 * li.n + 4) * sizeof(float);
+        if (!tg.colors_out && tg.plain_bits != 0u && tg.plain_bits <= 10u && tg.bpp == 4 && tg.aligned4 && lds_rows <= 160 * 1024 &&
+            li.box_var_rows) {
+            const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.row_count + 31) / 32), (unsigned)li.nframes);
+            if (lds_rows > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(box_rows_kernel_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows);
+            hipLaunchKernelGGL(box_rows_kernel_var, grid, dim3(256), lds_rows, (hipStream_t)li.stream, cam, tg);
+        } else {
             dim3 grid;
             grid_for(tg, 64, 4, li.nframes, grid);
             const size_t lds = ((size_t)li.n * 256 + (size_t)4 * li.n) * sizeof(float);
@@ -2424,64 +2412,32 @@ int nt_var_frame_words(int n) { return var_frame_words(n); }
 
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg) {
     int r;
+    size_t lds;
+    dim3 grid;
     if (sc.tframes) {
         // transparent materials / the reference's normal handling at run-time n (or beyond the fixed kernels' frame stack)
-        if (li.n < 3 || li.n > NT_DEV_MAX_DIM || !sc.checked || sc.checked_lanes < 64) {
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "run-time-n transparency kernel: bad launch (n %d)", li.n);
-            return -2;
-        }
-        const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc.stack_depth * 4 + (size_t)NT_MBOX * 4);
-        if (lds > 160 * 1024) {
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc.stack_depth);
-            return -1;
-        }
-        dim3 grid;
+        if ((r = var_frames_check(li.n, sc))) return r;
+        if ((r = var_walk_ready(li.n, sc, alias_kernel(sc, composite_kernel_var_t<true>, composite_kernel_var_t<false>), lds))) return r;
         grid_for(tg, 8, 8, li.nframes, grid);
-        const unsigned blocks = (unsigned)(sc.checked_lanes / 64);
-        if (sc.alias_normals) {
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(composite_kernel_var_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(composite_kernel_var_t<true>, dim3(blocks), dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, (int)grid.x,
-                               (int)grid.y, (int)grid.z);
-        } else {
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(composite_kernel_var_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(composite_kernel_var_t<false>, dim3(blocks), dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, (int)grid.x,
-                               (int)grid.y, (int)grid.z);
-        }
+        const dim3 blocks((unsigned)checked_blocks(sc));
+        if (sc.alias_normals)
+            hipLaunchKernelGGL(composite_kernel_var_t<true>, blocks, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, (int)grid.x, (int)grid.y,
+                               (int)grid.z);
+        else
+            hipLaunchKernelGGL(composite_kernel_var_t<false>, blocks, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, (int)grid.x, (int)grid.y,
+                               (int)grid.z);
         return finish_launch("composite kernel launch");
     }
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_composite_fixed_3(li, cam, sc, tg); break;
-        case 4: r = nt_composite_fixed_4(li, cam, sc, tg); break;
-        case 5: r = nt_composite_fixed_5(li, cam, sc, tg); break;
-        case 6: r = nt_composite_fixed_6(li, cam, sc, tg); break;
-        case 7: r = nt_composite_fixed_7(li, cam, sc, tg); break;
-        case 8: r = nt_composite_fixed_8(li, cam, sc, tg); break;
-        case 9: r = nt_composite_fixed_9(li, cam, sc, tg); break;
-        case 10: r = nt_composite_fixed_10(li, cam, sc, tg); break;
-        default: {
-            if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
-                return -2;
-            }
-            if (!sc.all_opaque) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "the run-time-n kernel does not render transparent materials");
-                return -2;
-            }
-            // run-time-n kernel: one wave per 8x8 tile (probe mode: 64 probes per block)
-            dim3 grid;
-            grid_for(tg, 8, 8, li.nframes, grid);
-            const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc.stack_depth * 4 + (size_t)NT_MBOX * 4);
-            if (lds > 160 * 1024) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc.stack_depth);
-                return -1;
-            }
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(composite_kernel_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(composite_kernel_var, grid, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n);
-            r = 0;
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_composite_fixed<decltype(N)::value>(li, cam, sc, tg); })) {
+        if ((r = var_dim_check(li.n))) return r;
+        if (!sc.all_opaque) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "the run-time-n kernel does not render transparent materials");
+            return -2;
         }
+        if ((r = var_walk_ready(li.n, sc, reinterpret_cast<const void *>(composite_kernel_var), lds))) return r;
+        // run-time-n kernel: one wave per 8x8 tile (probe mode: 64 probes per block)
+        grid_for(tg, 8, 8, li.nframes, grid);
+        hipLaunchKernelGGL(composite_kernel_var, grid, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n);
     }
     if (r) return r;
     return finish_launch("composite kernel launch");
@@ -2491,47 +2447,27 @@ int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCom
 // nt_launch_composite: these are no render routes.
 int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q) {
     int r;
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_query_fixed_3(li, sc, q); break;
-        case 4: r = nt_query_fixed_4(li, sc, q); break;
-        case 5: r = nt_query_fixed_5(li, sc, q); break;
-        case 6: r = nt_query_fixed_6(li, sc, q); break;
-        case 7: r = nt_query_fixed_7(li, sc, q); break;
-        case 8: r = nt_query_fixed_8(li, sc, q); break;
-        case 9: r = nt_query_fixed_9(li, sc, q); break;
-        case 10: r = nt_query_fixed_10(li, sc, q); break;
-        default: {
-            if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
-                return -2;
-            }
-            const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc.stack_depth * 4 + (size_t)NT_MBOX * 4);
-            if (lds > 160 * 1024) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc.stack_depth);
-                return -1;
-            }
-            hipStream_t s = (hipStream_t)li.stream;
-            const dim3 grid((unsigned)(((long long)q.count + 63) / 64));
-            const void *kernel;
-            if (q.occlusion) kernel = sc.all_opaque ? reinterpret_cast<const void *>(query_occluded_var) : reinterpret_cast<const void *>(query_occluded_var_t);
-            else if (!sc.checked) kernel = reinterpret_cast<const void *>(query_closest_var);
-            else kernel = sc.alias_normals ? reinterpret_cast<const void *>(query_closest_var_t<true>) : reinterpret_cast<const void *>(query_closest_var_t<false>);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (q.occlusion) {
-                if (sc.all_opaque) hipLaunchKernelGGL(query_occluded_var, grid, dim3(64), lds, s, sc, q, li.n);
-                else hipLaunchKernelGGL(query_occluded_var_t, grid, dim3(64), lds, s, sc, q, li.n);
-            } else if (sc.checked) {
-                // as many blocks as the `checked` scratch has lane columns for, striding over the rays
-                const dim3 tgrid((unsigned)(sc.checked_lanes / 64));
-                if (sc.alias_normals) hipLaunchKernelGGL(query_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, q, li.n);
-                else hipLaunchKernelGGL(query_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, q, li.n);
-            } else if (!sc.all_opaque) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: transparent scene without the checked-list scratch");
-                return -1;
-            } else {
-                hipLaunchKernelGGL(query_closest_var, grid, dim3(64), lds, s, sc, q, li.n);
-            }
-            r = 0;
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_query_fixed<decltype(N)::value>(li, sc, q); })) {
+        const void *kernel;
+        if (q.occlusion) kernel = sc.all_opaque ? reinterpret_cast<const void *>(query_occluded_var) : reinterpret_cast<const void *>(query_occluded_var_t);
+        else if (!sc.checked) kernel = reinterpret_cast<const void *>(query_closest_var);
+        else kernel = alias_kernel(sc, query_closest_var_t<true>, query_closest_var_t<false>);
+        size_t lds;
+        if ((r = var_walk_ready(li.n, sc, kernel, lds))) return r;
+        hipStream_t s = (hipStream_t)li.stream;
+        const dim3 grid((unsigned)(((long long)q.count + 63) / 64));
+        if (q.occlusion) {
+            if (sc.all_opaque) hipLaunchKernelGGL(query_occluded_var, grid, dim3(64), lds, s, sc, q, li.n);
+            else hipLaunchKernelGGL(query_occluded_var_t, grid, dim3(64), lds, s, sc, q, li.n);
+        } else if (sc.checked) {
+            // as many blocks as the `checked` scratch has lane columns for, striding over the rays
+            const dim3 tgrid((unsigned)checked_blocks(sc));
+            if (sc.alias_normals) hipLaunchKernelGGL(query_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, q, li.n);
+            else hipLaunchKernelGGL(query_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, q, li.n);
+        } else if (!sc.all_opaque) {
+            return no_checked_scratch();
+        } else {
+            hipLaunchKernelGGL(query_closest_var, grid, dim3(64), lds, s, sc, q, li.n);
         }
     }
     if (r) return r;
@@ -2542,47 +2478,25 @@ int nt_launch_query(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQu
 // from nt_launch_composite and nt_launch_query: these are neither render routes nor query routes.
 int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtHits &h) {
     int r;
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_hits_fixed_3(li, sc, tg, h); break;
-        case 4: r = nt_hits_fixed_4(li, sc, tg, h); break;
-        case 5: r = nt_hits_fixed_5(li, sc, tg, h); break;
-        case 6: r = nt_hits_fixed_6(li, sc, tg, h); break;
-        case 7: r = nt_hits_fixed_7(li, sc, tg, h); break;
-        case 8: r = nt_hits_fixed_8(li, sc, tg, h); break;
-        case 9: r = nt_hits_fixed_9(li, sc, tg, h); break;
-        case 10: r = nt_hits_fixed_10(li, sc, tg, h); break;
-        default: {
-            if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
-                return -2;
-            }
-            const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc.stack_depth * 4 + (size_t)NT_MBOX * 4);
-            if (lds > 160 * 1024) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc.stack_depth);
-                return -1;
-            }
-            hipStream_t s = (hipStream_t)li.stream;
-            const int tiles_x = (tg.width + 7) / 8, tiles_y = (tg.height + 7) / 8;
-            const long long tiles = (long long)tiles_x * tiles_y * h.nframes;
-            const void *kernel;
-            if (!sc.checked) kernel = reinterpret_cast<const void *>(hits_closest_var);
-            else kernel = sc.alias_normals ? reinterpret_cast<const void *>(hits_closest_var_t<true>) : reinterpret_cast<const void *>(hits_closest_var_t<false>);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (sc.checked) {
-                // as many blocks as the `checked` scratch has lane columns for, striding over the tiles
-                long long blocks = sc.checked_lanes / 64;
-                if (blocks > tiles) blocks = tiles;
-                const dim3 tgrid((unsigned)blocks);
-                if (sc.alias_normals) hipLaunchKernelGGL(hits_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
-                else hipLaunchKernelGGL(hits_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
-            } else if (!sc.all_opaque) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: transparent scene without the checked-list scratch");
-                return -1;
-            } else {
-                const dim3 grid((unsigned)(tiles < (1 << 22) ? tiles : (1 << 22)));
-                hipLaunchKernelGGL(hits_closest_var, grid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
-            }
-            r = 0;
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_hits_fixed<decltype(N)::value>(li, sc, tg, h); })) {
+        const void *kernel;
+        if (!sc.checked) kernel = reinterpret_cast<const void *>(hits_closest_var);
+        else kernel = alias_kernel(sc, hits_closest_var_t<true>, hits_closest_var_t<false>);
+        size_t lds;
+        if ((r = var_walk_ready(li.n, sc, kernel, lds))) return r;
+        hipStream_t s = (hipStream_t)li.stream;
+        const int tiles_x = (tg.width + 7) / 8, tiles_y = (tg.height + 7) / 8;
+        const long long tiles = (long long)tiles_x * tiles_y * h.nframes;
+        if (sc.checked) {
+            // as many blocks as the `checked` scratch has lane columns for, striding over the tiles
+            const dim3 tgrid((unsigned)checked_blocks(sc, tiles));
+            if (sc.alias_normals) hipLaunchKernelGGL(hits_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+            else hipLaunchKernelGGL(hits_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+        } else if (!sc.all_opaque) {
+            return no_checked_scratch();
+        } else {
+            const dim3 grid((unsigned)(tiles < (1 << 22) ? tiles : (1 << 22)));
+            hipLaunchKernelGGL(hits_closest_var, grid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
         }
     }
     if (r) return r;
@@ -2593,92 +2507,37 @@ int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTar
 // Kept apart from nt_launch_box and nt_launch_composite: these are no render routes.  sc == nullptr: BoxScene.
 int nt_launch_rays(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtRayJob &job, const NtTarget &tg) {
     hipStream_t s = (hipStream_t)li.stream;
-    if (li.n < 3 || li.n > NT_DEV_MAX_DIM) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "unsupported dimension %d", li.n);
-        return -2;
-    }
+    int r = var_dim_check(li.n);
+    if (r) return r;
     long long blocks = ((long long)job.count + 63) / 64;              // of the one-wave kernels
-    int r = 0;
+    size_t lds;
     if (!sc) {
-        switch (li.force_var ? 0 : li.n) {
-            case 3: r = nt_rays_box_fixed_3(li, job, tg); break;
-            case 4: r = nt_rays_box_fixed_4(li, job, tg); break;
-            case 5: r = nt_rays_box_fixed_5(li, job, tg); break;
-            case 6: r = nt_rays_box_fixed_6(li, job, tg); break;
-            case 7: r = nt_rays_box_fixed_7(li, job, tg); break;
-            case 8: r = nt_rays_box_fixed_8(li, job, tg); break;
-            case 9: r = nt_rays_box_fixed_9(li, job, tg); break;
-            case 10: r = nt_rays_box_fixed_10(li, job, tg); break;
-            case 11: r = nt_rays_box_fixed_11(li, job, tg); break;
-            case 12: r = nt_rays_box_fixed_12(li, job, tg); break;
-            case 13: r = nt_rays_box_fixed_13(li, job, tg); break;
-            case 14: r = nt_rays_box_fixed_14(li, job, tg); break;
-            case 15: r = nt_rays_box_fixed_15(li, job, tg); break;
-            case 16: r = nt_rays_box_fixed_16(li, job, tg); break;
-            case 17: r = nt_rays_box_fixed_17(li, job, tg); break;
-            case 18: r = nt_rays_box_fixed_18(li, job, tg); break;
-            case 19: r = nt_rays_box_fixed_19(li, job, tg); break;
-            case 20: r = nt_rays_box_fixed_20(li, job, tg); break;
-            case 21: r = nt_rays_box_fixed_21(li, job, tg); break;
-            case 22: r = nt_rays_box_fixed_22(li, job, tg); break;
-            case 23: r = nt_rays_box_fixed_23(li, job, tg); break;
-            case 24: r = nt_rays_box_fixed_24(li, job, tg); break;
-            default: {
-                if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
-                const size_t lds = (size_t)2 * li.n * 64 * sizeof(float);
-                hipLaunchKernelGGL(rays_box_var, dim3((unsigned)blocks), dim3(64), lds, s, job, tg, li.n);
-            }
+        if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_rays_box_fixed<decltype(N)::value>(li, job, tg); })) {
+            if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+            lds = (size_t)2 * li.n * 64 * sizeof(float);
+            hipLaunchKernelGGL(rays_box_var, dim3((unsigned)blocks), dim3(64), lds, s, job, tg, li.n);
         }
         if (r) return r;
         return finish_launch("ray-colour kernel launch");
     }
-    const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc->stack_depth * 4 + (size_t)NT_MBOX * 4);
     if (sc->tframes) {
         // transparent materials / the reference's normal handling at run-time n (or beyond the fixed kernels' frame stack)
-        if (!sc->checked || sc->checked_lanes < 64) {
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "run-time-n transparency kernel: bad launch (n %d)", li.n);
-            return -2;
-        }
-        if (lds > 160 * 1024) {
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
-            return -1;
-        }
+        if ((r = var_frames_check(li.n, *sc))) return r;
+        if ((r = var_walk_ready(li.n, *sc, alias_kernel(*sc, rays_color_var_t<true>, rays_color_var_t<false>), lds))) return r;
         // as many blocks as the scratch has lane columns for, striding over the rays
-        if (blocks > sc->checked_lanes / 64) blocks = sc->checked_lanes / 64;
-        if (sc->alias_normals) {
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(rays_color_var_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(rays_color_var_t<true>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
-        } else {
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(rays_color_var_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(rays_color_var_t<false>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
-        }
+        blocks = checked_blocks(*sc, blocks);
+        if (sc->alias_normals) hipLaunchKernelGGL(rays_color_var_t<true>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
+        else hipLaunchKernelGGL(rays_color_var_t<false>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
         return finish_launch("ray-colour kernel launch");
     }
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_rays_fixed_3(li, *sc, job, tg); break;
-        case 4: r = nt_rays_fixed_4(li, *sc, job, tg); break;
-        case 5: r = nt_rays_fixed_5(li, *sc, job, tg); break;
-        case 6: r = nt_rays_fixed_6(li, *sc, job, tg); break;
-        case 7: r = nt_rays_fixed_7(li, *sc, job, tg); break;
-        case 8: r = nt_rays_fixed_8(li, *sc, job, tg); break;
-        case 9: r = nt_rays_fixed_9(li, *sc, job, tg); break;
-        case 10: r = nt_rays_fixed_10(li, *sc, job, tg); break;
-        default: {
-            if (!sc->all_opaque || sc->checked) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the run-time-n kernel without frame scratch does not shade transparent materials");
-                return -1;
-            }
-            if (lds > 160 * 1024) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
-                return -1;
-            }
-            if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(rays_color_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(rays_color_var, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_rays_fixed<decltype(N)::value>(li, *sc, job, tg); })) {
+        if (!sc->all_opaque || sc->checked) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the run-time-n kernel without frame scratch does not shade transparent materials");
+            return -1;
         }
+        if ((r = var_walk_ready(li.n, *sc, reinterpret_cast<const void *>(rays_color_var), lds))) return r;
+        if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+        hipLaunchKernelGGL(rays_color_var, dim3((unsigned)blocks), dim3(64), lds, s, *sc, job, tg, li.n);
     }
     if (r) return r;
     return finish_launch("ray-colour kernel launch");
@@ -2698,82 +2557,30 @@ int nt_launch_refine(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtR
     }
     long long blocks = refine_blocks(rf);
     int r = 0;
+    size_t lds;
     if (!sc) {
-        switch (li.force_var ? 0 : li.n) {
-            case 3: r = nt_refine_box_fixed_3(li, rf, tg); break;
-            case 4: r = nt_refine_box_fixed_4(li, rf, tg); break;
-            case 5: r = nt_refine_box_fixed_5(li, rf, tg); break;
-            case 6: r = nt_refine_box_fixed_6(li, rf, tg); break;
-            case 7: r = nt_refine_box_fixed_7(li, rf, tg); break;
-            case 8: r = nt_refine_box_fixed_8(li, rf, tg); break;
-            case 9: r = nt_refine_box_fixed_9(li, rf, tg); break;
-            case 10: r = nt_refine_box_fixed_10(li, rf, tg); break;
-            case 11: r = nt_refine_box_fixed_11(li, rf, tg); break;
-            case 12: r = nt_refine_box_fixed_12(li, rf, tg); break;
-            case 13: r = nt_refine_box_fixed_13(li, rf, tg); break;
-            case 14: r = nt_refine_box_fixed_14(li, rf, tg); break;
-            case 15: r = nt_refine_box_fixed_15(li, rf, tg); break;
-            case 16: r = nt_refine_box_fixed_16(li, rf, tg); break;
-            case 17: r = nt_refine_box_fixed_17(li, rf, tg); break;
-            case 18: r = nt_refine_box_fixed_18(li, rf, tg); break;
-            case 19: r = nt_refine_box_fixed_19(li, rf, tg); break;
-            case 20: r = nt_refine_box_fixed_20(li, rf, tg); break;
-            case 21: r = nt_refine_box_fixed_21(li, rf, tg); break;
-            case 22: r = nt_refine_box_fixed_22(li, rf, tg); break;
-            case 23: r = nt_refine_box_fixed_23(li, rf, tg); break;
-            case 24: r = nt_refine_box_fixed_24(li, rf, tg); break;
-            default: {
-                const size_t lds = (size_t)2 * li.n * 64 * sizeof(float);
-                hipLaunchKernelGGL(refine_box_var, dim3((unsigned)blocks), dim3(64), lds, s, rf, tg, li.n);
-            }
+        if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_refine_box_fixed<decltype(N)::value>(li, rf, tg); })) {
+            lds = (size_t)2 * li.n * 64 * sizeof(float);
+            hipLaunchKernelGGL(refine_box_var, dim3((unsigned)blocks), dim3(64), lds, s, rf, tg, li.n);
         }
         if (r) return r;
         return finish_launch("refine kernel launch");
     }
-    const size_t lds = (size_t)64 * ((size_t)li.n * 16 + (size_t)sc->stack_depth * 4 + (size_t)NT_MBOX * 4);
     if (sc->tframes) {
-        if (!sc->checked || sc->checked_lanes < 64) {
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "run-time-n transparency kernel: bad launch (n %d)", li.n);
-            return -2;
-        }
-        if (lds > 160 * 1024) {
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
-            return -1;
-        }
-        if (blocks > sc->checked_lanes / 64) blocks = sc->checked_lanes / 64;
-        if (sc->alias_normals) {
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(refine_color_var_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(refine_color_var_t<true>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
-        } else {
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(refine_color_var_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(refine_color_var_t<false>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
-        }
+        if ((r = var_frames_check(li.n, *sc))) return r;
+        if ((r = var_walk_ready(li.n, *sc, alias_kernel(*sc, refine_color_var_t<true>, refine_color_var_t<false>), lds))) return r;
+        blocks = checked_blocks(*sc, blocks);
+        if (sc->alias_normals) hipLaunchKernelGGL(refine_color_var_t<true>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
+        else hipLaunchKernelGGL(refine_color_var_t<false>, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
         return finish_launch("refine kernel launch");
     }
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_refine_fixed_3(li, *sc, rf, tg); break;
-        case 4: r = nt_refine_fixed_4(li, *sc, rf, tg); break;
-        case 5: r = nt_refine_fixed_5(li, *sc, rf, tg); break;
-        case 6: r = nt_refine_fixed_6(li, *sc, rf, tg); break;
-        case 7: r = nt_refine_fixed_7(li, *sc, rf, tg); break;
-        case 8: r = nt_refine_fixed_8(li, *sc, rf, tg); break;
-        case 9: r = nt_refine_fixed_9(li, *sc, rf, tg); break;
-        case 10: r = nt_refine_fixed_10(li, *sc, rf, tg); break;
-        default: {
-            if (!sc->all_opaque || sc->checked) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the run-time-n kernel without frame scratch does not shade transparent materials");
-                return -1;
-            }
-            if (lds > 160 * 1024) {
-                snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "scene too deep for the LDS budget (n %d, depth %d)", li.n, sc->stack_depth);
-                return -1;
-            }
-            if (lds > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(refine_color_var), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(refine_color_var, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_refine_fixed<decltype(N)::value>(li, *sc, rf, tg); })) {
+        if (!sc->all_opaque || sc->checked) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the run-time-n kernel without frame scratch does not shade transparent materials");
+            return -1;
         }
+        if ((r = var_walk_ready(li.n, *sc, reinterpret_cast<const void *>(refine_color_var), lds))) return r;
+        hipLaunchKernelGGL(refine_color_var, dim3((unsigned)blocks), dim3(64), lds, s, *sc, rf, tg, li.n);
     }
     if (r) return r;
     return finish_launch("refine kernel launch");
@@ -2782,36 +2589,20 @@ int nt_launch_refine(const NtLaunchInfo &li, const NtCompositeDev *sc, const NtR
 // A render through a lens.  The packet route (nt_lens.hpp): the fixed-n launcher of the scene's dimension; there is no
 // run-time-n packet walk, and the host sends those scenes through the ray route below.
 int nt_launch_lens(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln) {
-    int r = 0;
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_lens_fixed_3(li, sc, tg, ln); break;
-        case 4: r = nt_lens_fixed_4(li, sc, tg, ln); break;
-        case 5: r = nt_lens_fixed_5(li, sc, tg, ln); break;
-        case 6: r = nt_lens_fixed_6(li, sc, tg, ln); break;
-        case 7: r = nt_lens_fixed_7(li, sc, tg, ln); break;
-        case 8: r = nt_lens_fixed_8(li, sc, tg, ln); break;
-        case 9: r = nt_lens_fixed_9(li, sc, tg, ln); break;
-        case 10: r = nt_lens_fixed_10(li, sc, tg, ln); break;
-        default:
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no packet walk for a lens at run-time n (n %d)", li.n);
-            return -1;
-    }
-    if (r) return r;
-    return finish_launch("lens kernel launch");
+    return launch_fixed_only(li, "no packet walk for a lens", "lens kernel launch",
+                             [&](auto N) { return nt_lens_fixed<decltype(N)::value>(li, sc, tg, ln); });
 }
 
 // The ray route's two helpers around nt_launch_rays: pixels [first, first + count) of the table
 int nt_launch_lens_expand(const NtLaunchInfo &li, const float *table, const float *cam, long long first, long long count, float *out) {
-    long long blocks = (count + 255) / 256;
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    const long long blocks = stride_blocks(count);
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(lens_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, table, cam, li.n, first, count, out);
     return finish_launch("lens expansion kernel launch");
 }
 
 int nt_launch_lens_mask(const NtLaunchInfo &li, const float *table, long long first, long long count, const NtTarget &tg) {
-    long long blocks = (count + 255) / 256;
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    const long long blocks = stride_blocks(count);
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(lens_mask_fill, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, table, first, count, tg);
     return finish_launch("lens mask kernel launch");
@@ -2820,29 +2611,14 @@ int nt_launch_lens_mask(const NtLaunchInfo &li, const float *table, long long fi
 // A render under the parallel projection.  The packet route (nt_parallel.hpp): the fixed-n launcher of the scene's dimension;
 // there is no run-time-n packet walk, and the host sends those scenes through the ray route below.
 int nt_launch_parallel(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl) {
-    int r = 0;
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_parallel_fixed_3(li, sc, tg, pl); break;
-        case 4: r = nt_parallel_fixed_4(li, sc, tg, pl); break;
-        case 5: r = nt_parallel_fixed_5(li, sc, tg, pl); break;
-        case 6: r = nt_parallel_fixed_6(li, sc, tg, pl); break;
-        case 7: r = nt_parallel_fixed_7(li, sc, tg, pl); break;
-        case 8: r = nt_parallel_fixed_8(li, sc, tg, pl); break;
-        case 9: r = nt_parallel_fixed_9(li, sc, tg, pl); break;
-        case 10: r = nt_parallel_fixed_10(li, sc, tg, pl); break;
-        default:
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no packet walk for the parallel projection at run-time n (n %d)", li.n);
-            return -1;
-    }
-    if (r) return r;
-    return finish_launch("parallel projection kernel launch");
+    return launch_fixed_only(li, "no packet walk for the parallel projection", "parallel projection kernel launch",
+                             [&](auto N) { return nt_parallel_fixed<decltype(N)::value>(li, sc, tg, pl); });
 }
 
 // The ray route's helper in front of nt_launch_rays: pixels [first, first + count) of the view
 int nt_launch_parallel_expand(const NtLaunchInfo &li, const float *cam, int width, float k, float half_w, float half_h, long long first,
                               long long count, float *out) {
-    long long blocks = (count + 255) / 256;
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    const long long blocks = stride_blocks(count);
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(parallel_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, cam, li.n, width, k, half_w, half_h, first, count, out);
     return finish_launch("parallel projection expansion kernel launch");
@@ -2851,36 +2627,20 @@ int nt_launch_parallel_expand(const NtLaunchInfo &li, const float *cam, int widt
 // Ambient occlusion.  The fast route (nt_ao.hpp): the fixed-n launcher of the scene's dimension; the host sends every other
 // scene through the ray route below.
 int nt_launch_ao(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao) {
-    int r = 0;
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_ao_fixed_3(li, sc, tg, ao); break;
-        case 4: r = nt_ao_fixed_4(li, sc, tg, ao); break;
-        case 5: r = nt_ao_fixed_5(li, sc, tg, ao); break;
-        case 6: r = nt_ao_fixed_6(li, sc, tg, ao); break;
-        case 7: r = nt_ao_fixed_7(li, sc, tg, ao); break;
-        case 8: r = nt_ao_fixed_8(li, sc, tg, ao); break;
-        case 9: r = nt_ao_fixed_9(li, sc, tg, ao); break;
-        case 10: r = nt_ao_fixed_10(li, sc, tg, ao); break;
-        default:
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no ambient occlusion kernel at run-time n (n %d)", li.n);
-            return -1;
-    }
-    if (r) return r;
-    return finish_launch("ambient occlusion kernel launch");
+    return launch_fixed_only(li, "no ambient occlusion kernel", "ambient occlusion kernel launch",
+                             [&](auto N) { return nt_ao_fixed<decltype(N)::value>(li, sc, tg, ao); });
 }
 
 // The ray route's two kernels around nt_launch_query: pixels [ar.first, ar.first + ar.pixels) of the launch
 int nt_launch_ao_expand(const NtLaunchInfo &li, const NtTarget &tg, const NtAo &ao, const NtAoRays &ar) {
-    long long blocks = (ar.pixels * ao.count + 255) / 256;
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    const long long blocks = stride_blocks(ar.pixels * ao.count);
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(ao_expand, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, tg, ao, ar, li.n);
     return finish_launch("ambient occlusion expansion kernel launch");
 }
 
 int nt_launch_ao_reduce(const NtLaunchInfo &li, const NtTarget &tg, const NtAo &ao, const NtAoRays &ar) {
-    long long blocks = (ar.pixels + 255) / 256;
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    const long long blocks = stride_blocks(ar.pixels);
     if (blocks < 1) return 0;
     hipLaunchKernelGGL(ao_reduce, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)li.stream, tg, ao, ar);
     return finish_launch("ambient occlusion count kernel launch");
@@ -2896,22 +2656,8 @@ int nt_launch_ao_apply(void *stream, const uint32_t *base, const int *blocked, i
 // (`draw`) or outline_mark_fixed; there is no run-time-n packet walk, and the host sends those scenes through the general route
 // below.
 static int nt_launch_outline_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw) {
-    int r = 0;
-    switch (li.force_var ? 0 : li.n) {
-        case 3: r = nt_outline_fixed_3(li, sc, tg, ol, draw); break;
-        case 4: r = nt_outline_fixed_4(li, sc, tg, ol, draw); break;
-        case 5: r = nt_outline_fixed_5(li, sc, tg, ol, draw); break;
-        case 6: r = nt_outline_fixed_6(li, sc, tg, ol, draw); break;
-        case 7: r = nt_outline_fixed_7(li, sc, tg, ol, draw); break;
-        case 8: r = nt_outline_fixed_8(li, sc, tg, ol, draw); break;
-        case 9: r = nt_outline_fixed_9(li, sc, tg, ol, draw); break;
-        case 10: r = nt_outline_fixed_10(li, sc, tg, ol, draw); break;
-        default:
-            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: no packet walk for outlines at run-time n (n %d)", li.n);
-            return -1;
-    }
-    if (r) return r;
-    return finish_launch("outline kernel launch");
+    return launch_fixed_only(li, "no packet walk for outlines", "outline kernel launch",
+                             [&](auto N) { return nt_outline_fixed<decltype(N)::value>(li, sc, tg, ol, draw); });
 }
 
 int nt_launch_outline(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol) {
