@@ -309,6 +309,56 @@ int nt_scene_get_outlines(const nt_scene_t *s, int *enabled, float *crease_cos, 
    is off; NT_E_UNSUPPORTED while a lens or the parallel projection is set. */
 int nt_outline_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts);
 int nt_outline_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream);
+/* Depth cues (the reference has none): a surface fades towards a fog colour with its distance from the eye, and is tinted by
+   where its visible point lies along a direction of n-space ("colour by w"), on the device from the primary hits of the render
+   itself.  CompositeScene only.  Everything below is fp32 without contraction, sums left to right,
+   clamp01(v) = max(0, min(1, v)).  The host forms two reciprocals once, in fp32: inv_fog = 1.0f / (fog_far - fog_near) and,
+   with a tint, inv_tint = 1.0f / (tint_hi - tint_lo).
+   For a W x H view let R(p) = (dist, item, lane, n_transparent) be what nt_primary_hits defines for pixel p, with the
+   strict_reference and NTRACER_* switches of a render of the scene, o the camera's origin and d the primary ray's unit direction
+   as the render forms it.  The pixel's two factors (f, g):
+     item >= 0:  t = dist, f = clamp01((t - fog_near) * inv_fog);
+                 with a tint x_k = (d_k * t) + o_k, s = tint_axis_0 * x_0, then s = s + (tint_axis_k * x_k) for k = 1 .. n - 1,
+                 and g = clamp01((s - tint_lo) * inv_tint); without a tint g = -1;
+     item < 0, fog_background set and n_transparent == 0:  f = 1, g = -1;
+     otherwise f = -1, g = -1: the pixel is left alone.  Transparent surfaces carry no cue, as they carry no lines.
+   A render with the setting on: P the plain single-sample frame with each component clamped to [0, 1], Q = P;
+     if g >= 0:  Q.c = P.c * ((tint_color_lo.c * (1.0f - g)) + (tint_color_hi.c * g));
+     if f >= 0:  w = f * fog_strength and Q.c = (Q.c * (1.0f - w)) + (fog_color.c * w);
+   and Q goes through the format's conversion and packing as always: with fog_strength = 0 and no tint the plain frame byte for
+   byte.  nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device honour the setting and refuse with
+   NT_E_UNSUPPORTED ("depth cue ...") before a device is touched, drawing nothing: a supersampling factor above 1 (adaptive or
+   not), row bands (band_world > 1), collect_stats, a lens, the parallel projection, ambient occlusion, outlines (and a row
+   range, which only a caller inside the library can ask for).  nt_colors_at / nt_calculate_color, nt_primary_hits*,
+   nt_ray_colors*, nt_render_rays*, the ray queries, nt_adaptive_mask*, nt_ambient_occlusion* and nt_outline_mask* ignore it.
+   Opaque scenes up to 10 dimensions on the renders' packet walk are drawn from one walk: 16 bytes of record a pixel a frame.
+   Every other scene (transparent materials, Solids with the reference's normals, n > 10, NTRACER_FORCE_VAR=1,
+   NTRACER_COMPOSITE_KERNEL set) takes 28 bytes a pixel a frame -- base frame and record; 16 for nt_depth_cue_factors*, which
+   draw no base frame -- under the cap of nt_scene_set_supersampling_scratch_mb, and so does the packet walk's record scratch
+   here: larger jobs are cut into chunks of whole frames, and a single frame that does not fit fails with NT_E_UNSUPPORTED
+   before anything is launched.  Not part of a pickled scene. */
+typedef struct nt_depth_cue {
+    float fog_near, fog_far;           /* 0 <= fog_near < fog_far, 1 / (fog_far - fog_near) finite */
+    float fog_color[3];                /* every colour component and fog_strength in [0, 1] */
+    float fog_strength;
+    int32_t fog_background;            /* not 0: pixels that hit nothing at all take the fog in full */
+    float tint_lo, tint_hi;            /* read with a tint_axis only: tint_lo < tint_hi, 1 / (tint_hi - tint_lo) finite */
+    float tint_color_lo[3], tint_color_hi[3];
+} nt_depth_cue;
+/* cue == NULL takes the setting off; tint_axis == NULL means no tint, else `dimension` floats, finite and not all zero.
+   NT_E_INVALID for a BoxScene and for a value that is not finite or outside its range (the setting stays as it was);
+   NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it; the getter writes through whichever
+   pointers are not NULL: *enabled 0 or 1, *cue (zeroes while off, tint fields zero without a tint), *has_tint 0 or 1,
+   tint_axis `dimension` floats (zeroes without a tint). */
+int nt_scene_set_depth_cue(nt_scene_t *s, const nt_depth_cue *cue, const float *tint_axis);
+int nt_scene_get_depth_cue(const nt_scene_t *s, int *enabled, nt_depth_cue *cue, int *has_tint, float *tint_axis);
+/* The factors (f, g) of a width x height view of the scene's current camera, factors[(y * width + x) * 2 + {0, 1}].  The host
+   form holds the scene like nt_colors_at and reads device and strict_reference of `opts`.  The device form writes exactly
+   width * height * 8 bytes of device memory at factors_dev and is only enqueued on hip_stream; it also reads abort_device, and
+   every other field of `opts` must be 0.  NT_E_INVALID when the setting is off; NT_E_UNSUPPORTED while a lens or the parallel
+   projection is set. */
+int nt_depth_cue_factors(nt_scene_t *s, int width, int height, float *factors, const nt_render_opts *opts);
+int nt_depth_cue_factors_device(nt_scene_t *s, int width, int height, void *factors_dev, const nt_render_opts *opts, void *hip_stream);
 /* CompositeScene.set_shadows/set_camera_light/set_max_reflect_depth/set_ambient_color/
    set_background/add_light rolled into one call */
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p);

@@ -84,6 +84,12 @@ NT_OUTLINE_CREASE = 2
 NT_OUTLINE_DEPTH = 4
 
 
+class NtDepthCue(C.Structure):               # nt_depth_cue: 60 bytes
+    _fields_ = [("fog_near", C.c_float), ("fog_far", C.c_float), ("fog_color", C.c_float * 3), ("fog_strength", C.c_float),
+                ("fog_background", C.c_int32), ("tint_lo", C.c_float), ("tint_hi", C.c_float), ("tint_color_lo", C.c_float * 3),
+                ("tint_color_hi", C.c_float * 3)]
+
+
 class NtRayHit(C.Structure):                 # nt_ray_hit: 16 bytes
     _fields_ = [("dist", C.c_float), ("item", C.c_int32), ("lane", C.c_int32), ("n_transparent", C.c_int32)]
 
@@ -147,6 +153,10 @@ SYMBOLS = [
     ("nt_scene_get_outlines", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p, f32p, f32p]),
     ("nt_outline_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
     ("nt_outline_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_scene_set_depth_cue", C.c_int, [C.c_void_p, C.POINTER(NtDepthCue), f32p]),
+    ("nt_scene_get_depth_cue", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(NtDepthCue), C.POINTER(C.c_int), f32p]),
+    ("nt_depth_cue_factors", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),
+    ("nt_depth_cue_factors_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_set_params", C.c_int, [C.c_void_p, C.POINTER(NtSceneParams)]),
     ("nt_scene_lock", C.c_int, [C.c_void_p]),
     ("nt_scene_unlock", C.c_int, [C.c_void_p]),

@@ -108,7 +108,8 @@ struct DeviceState {
                                          // ambient occlusion: the hit records, both normal rows, the base frame and the counts
                                          // of a chunk of frames, and on the ray route the ray arrays and answers of a chunk of rows;
                                          // outlines: the hit records of a chunk of frames and, off the packet walk, their normal
-                                         // rows, base frame and mask bytes
+                                         // rows, base frame and mask bytes; depth cues: the hit records of a chunk of frames and,
+                                         // off the packet walk, their base frame, and the host form's factors
     DevBuf refine_count;                 // adaptive supersampling: the length of that list
     DevBuf ao_dirs;                      // ambient occlusion: the table of directions
     unsigned long long ao_version = 0;
@@ -186,6 +187,10 @@ struct nt_scene {
     unsigned long long ao_version = 1;   // counts the changes of ao_dirs
     bool outlines = false;               // silhouette, crease and depth lines on the renders (nt_scene_set_outlines)
     float ol_crease_cos = 0.0f, ol_depth_gap = 0.0f, ol_color[3] = {0, 0, 0}, ol_strength = 0.0f;
+    bool cue = false, cue_tint = false;  // distance fog and a coordinate tint on the renders (nt_scene_set_depth_cue)
+    nt_depth_cue cue_set{};              // ... as the caller gave it, the tint's fields zero without a tint,
+    std::vector<float> cue_axis;         // ... the tint axis [n], empty without a tint,
+    float cue_inv_fog = 0.0f, cue_inv_tint = 0.0f;   // ... and the two reciprocals of the rule, formed once
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -1445,6 +1450,120 @@ int enqueue_outlines(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 }
 
 // ---------------------------------------------------------------------------------------------
+// depth cues (nt_scene_set_depth_cue; kernels in nt_cue.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+// What a render with the setting on refuses, checked by the entry points before a device is touched, in front of every other
+// setting's check (and by enqueue_cue again, for every way in): the factors come from the records of the whole pinhole view, one
+// sample a pixel, no kernel of it keeps counters, and a scene with another such setting on is refused here, not drawn with one
+// of them missing.  (The row-range answer guards against callers within this file, as ao_check's does.)
+int cue_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
+    if (!s->cue) return NT_OK;
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "depth cues are not available with a supersampling factor above 1 (%d)", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "depth cues are not available with row bands (band_world %d)", b.world);
+    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "depth cues are not available for a row range");
+    if (stats) return fail(NT_E_UNSUPPORTED, "depth cues are not available with collect_stats");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "depth cues are not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "depth cues are not available while the parallel projection is set");
+    if (s->ao_count > 0) return fail(NT_E_UNSUPPORTED, "depth cues are not available while ambient occlusion is on");
+    if (s->outlines) return fail(NT_E_UNSUPPORTED, "depth cues are not available while outlines are on");
+    return NT_OK;
+}
+
+// The factors (f, g) of every pixel of the job's frames or, with job.fmt, the render they shape, per chunk of whole frames.
+// Opaque scenes that launch_composite_fixed would give the packet walk take one walk into hit records and cue_shade -- or
+// cue_factors_fixed for the factors alone -- (nt_launch_cue*); every other scene the plain fp32 x 3 base frame into scratch (a
+// render only), a primary-hit pass without normal rows into scratch (hits_enqueue: every route of it) and cue_apply into the
+// caller's image, or cue_factors.  Without job.fmt the view is job.view_w x job.view_h, one frame, and the floats go to
+// `factors_dev`, or with `factors_scratch` stay in scratch: *factors_out.  The scratch -- per pixel and frame 16 bytes of record,
+// 12 of base frame off the packet walk, 8 of factors for the host form -- sits under the supersampling cap.  Enqueue only.
+int enqueue_cue(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, float *factors_dev, bool factors_scratch,
+                float **factors_out) {
+    const bool draw = job.fmt != nullptr;
+    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
+    if (int r = cue_check(s, job.bands, job.stats, draw ? job.row_begin : 0, draw ? job.row_count : H, H)) return r;
+    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const int n = s->n;
+    const long long px = (long long)W * H;
+    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const bool fast = composite_route(s, sw).packet_walk;
+    const long long per_frame = px * (16 + (!fast && draw ? 12 : 0) + (factors_scratch ? 8 : 0));
+    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "depth cue of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
+    if (per_frame > cap)
+        return fail(NT_E_UNSUPPORTED, "depth cue of a %d x %d image: the scratch of one frame (%lld bytes) does not fit the scratch buffer of "
+                    "%lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    const int chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame),
+                                                                              std::min<long long>(INT_MAX / px, std::max(sw.chunk_frames, 1))));
+    if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame))) return e;
+    const size_t fpx = (size_t)chunk_frames * px;
+    char *at = (char *)ds->samples.p;
+    void *recs = at; at += fpx * 16;
+    char *base = nullptr;
+    if (!fast && draw) { base = at; at += fpx * 12; }
+    if (factors_scratch) factors_dev = (float *)at;
+    if (factors_out) *factors_out = factors_dev;
+    NtTarget tg;
+    if (draw) {
+        if (int r = fill_target(s, ds, job, tg)) return r;
+    } else {
+        view_target(s, W, H, job.abort_word, tg);
+    }
+    NtCue cu{};
+    cu.recs = recs;
+    cu.fog_near = s->cue_set.fog_near;
+    cu.inv_fog = s->cue_inv_fog;
+    cu.fog_strength = s->cue_set.fog_strength;
+    cu.fog_background = s->cue_set.fog_background != 0;
+    cu.tint = s->cue_tint ? 1 : 0;
+    cu.tint_lo = s->cue_set.tint_lo;
+    cu.inv_tint = s->cue_inv_tint;
+    for (int k = 0; k < 3; ++k) {
+        cu.fog_color[k] = s->cue_set.fog_color[k];
+        cu.tint_color_lo[k] = s->cue_set.tint_color_lo[k];
+        cu.tint_color_hi[k] = s->cue_set.tint_color_hi[k];
+    }
+    for (int k = 0; k < n && s->cue_tint; ++k) cu.tint_axis[k] = s->cue_axis[k];
+    cu.factors = factors_dev;
+    Format bf;
+    if (int r = plain_f32_format(W, H, bf)) return r;
+    const float *all_cams = nullptr;
+    NtCompositeDev c;
+    if (fast) {
+        if (int e = device_camera(s, ds, job.cam_buf, job.stream, all_cams)) return e;
+        scene_dev(s, ds, sw, job.strict, false, c);
+    }
+    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
+        const int nf = std::min(chunk_frames, job.nframes - f0);
+        NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
+        NtTarget ft = tg;
+        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        cu.nframes = nf;
+        if (fast) {
+            // the packet walk's plane numerators and quad order, as hits_enqueue hands them over, and the records' place
+            if (int e = numerator_scratch(s, ds, sw, nf, li)) return e;
+            if (sw.tile_order) {
+                if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
+            }
+            li.hit_buf = recs;
+            li.hit_frames = nf;
+            cu.cams = all_cams + (size_t)f0 * 4 * n;
+            if (int r = draw ? nt_launch_cue(li, c, ft, cu) : nt_launch_cue_factors_fixed(li, c, ft, cu)) return launch_failed(r);
+            continue;
+        }
+        const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
+        if (draw) {
+            if (int e = enqueue(s, ds, base_frame_job(s, job, bf, f0, nf, base, (size_t)px * 12))) return e;
+        }
+        nt_hit_buffers hb{};
+        hb.hits = (nt_ray_hit *)recs;
+        if (int e = hits_enqueue(s, ds, W, H, &hb, px, cams, nf, job.strict, job.abort_word, job.stream)) return e;
+        cu.cams = cams ? cams : (const float *)ds->cams.p;              // (hits_enqueue has put the scene's own camera there)
+        if (int r = draw ? nt_launch_cue_apply(li, (const uint32_t *)base, cu, ft) : nt_launch_cue_factors(li, ft, cu)) return launch_failed(r);
+    }
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // renders through a lens (nt_scene_set_lens; kernels in nt_lens.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1624,6 +1743,8 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
+    if (s->cue && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
+        return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
     if (s->outlines && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
         return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->ao_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
@@ -1686,6 +1807,7 @@ int prepare_stats(DeviceState *ds, hipStream_t st, bool on) {
 
 // what the scene's settings refuse of a render, in the order the render entry points say it, before they touch a device
 int render_checks(const nt_scene *s, const Format &f, const Bands &b, bool stats) {
+    if (int r = cue_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = outline_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = ao_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, stats, false)) return r;
@@ -1719,7 +1841,8 @@ FrameJob render_job(const Format &f, const Bands &b, void *dest_dev, size_t fram
     return job;
 }
 
-// ... and of the entry points that draw nothing (nt_adaptive_mask, nt_ambient_occlusion, nt_outline_mask): one whole view of w x h
+// ... and of the entry points that draw nothing (nt_adaptive_mask, nt_ambient_occlusion, nt_outline_mask,
+// nt_depth_cue_factors): one whole view of w x h
 FrameJob view_job(int w, int h, hipStream_t stream, const nt_render_opts *opts, bool device_form) {
     FrameJob job{};
     job.nframes = 1;
@@ -2548,6 +2671,66 @@ int nt_scene_get_outlines(const nt_scene_t *s, int *enabled, float *crease_cos, 
     return NT_OK;
 }
 
+namespace {
+bool cue_unit(float v) { return v >= 0.0f && v <= 1.0f; }          // (false for a NaN)
+}  // namespace
+
+int nt_scene_set_depth_cue(nt_scene_t *s, const nt_depth_cue *cue, const float *tint_axis) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no depth cue");
+    nt_depth_cue set{};
+    std::vector<float> axis;
+    float inv_fog = 0.0f, inv_tint = 0.0f;
+    if (cue) {
+        set = *cue;
+        set.fog_background = cue->fog_background != 0;
+        if (!std::isfinite(set.fog_near) || !std::isfinite(set.fog_far) || !(set.fog_near >= 0.0f) || !(set.fog_far > set.fog_near))
+            return fail(NT_E_INVALID, "the depth cue's fog range must be finite with 0 <= fog_near < fog_far");
+        inv_fog = 1.0f / (set.fog_far - set.fog_near);
+        if (!std::isfinite(inv_fog)) return fail(NT_E_INVALID, "the depth cue's fog range is too narrow: 1 / (fog_far - fog_near) is not finite");
+        for (int k = 0; k < 3; ++k)
+            if (!cue_unit(set.fog_color[k])) return fail(NT_E_INVALID, "the depth cue's fog colour components must lie in [0, 1]");
+        if (!cue_unit(set.fog_strength)) return fail(NT_E_INVALID, "the depth cue's fog_strength must lie in [0, 1]");
+        if (tint_axis) {
+            if (!std::isfinite(set.tint_lo) || !std::isfinite(set.tint_hi) || !(set.tint_hi > set.tint_lo))
+                return fail(NT_E_INVALID, "the depth cue's tint range must be finite with tint_lo < tint_hi");
+            inv_tint = 1.0f / (set.tint_hi - set.tint_lo);
+            if (!std::isfinite(inv_tint)) return fail(NT_E_INVALID, "the depth cue's tint range is too narrow: 1 / (tint_hi - tint_lo) is not finite");
+            for (int k = 0; k < 3; ++k)
+                if (!cue_unit(set.tint_color_lo[k]) || !cue_unit(set.tint_color_hi[k]))
+                    return fail(NT_E_INVALID, "the depth cue's tint colour components must lie in [0, 1]");
+            axis.assign(tint_axis, tint_axis + s->n);
+            bool any = false;
+            for (float v : axis) {
+                if (!std::isfinite(v)) return fail(NT_E_INVALID, "the depth cue's tint_axis must be finite");
+                any = any || v != 0.0f;
+            }
+            if (!any) return fail(NT_E_INVALID, "the depth cue's tint_axis must not be all zero");
+        } else {
+            set.tint_lo = set.tint_hi = 0.0f;
+            for (int k = 0; k < 3; ++k) set.tint_color_lo[k] = set.tint_color_hi[k] = 0.0f;
+        }
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->cue = cue != nullptr;
+    s->cue_tint = cue && tint_axis;
+    s->cue_set = set;
+    s->cue_axis = std::move(axis);
+    s->cue_inv_fog = inv_fog;
+    s->cue_inv_tint = inv_tint;
+    return NT_OK;
+}
+
+int nt_scene_get_depth_cue(const nt_scene_t *s, int *enabled, nt_depth_cue *cue, int *has_tint, float *tint_axis) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (enabled) *enabled = s->cue ? 1 : 0;
+    if (cue) *cue = s->cue_set;
+    if (has_tint) *has_tint = s->cue_tint ? 1 : 0;
+    if (tint_axis) for (int k = 0; k < s->n; ++k) tint_axis[k] = s->cue_tint ? s->cue_axis[k] : 0.0f;
+    return NT_OK;
+}
+
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");
     if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no lighting parameters");
@@ -2914,6 +3097,46 @@ int nt_outline_mask_device(nt_scene_t *s, int width, int height, void *mask_dev,
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
     return enqueue_outlines(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
+}
+
+namespace {
+// what both forms of nt_depth_cue_factors check before a device is touched
+int cue_validate(const nt_scene *s, int width, int height, const void *factors) {
+    if (!s || !factors) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (!s->cue) return fail(NT_E_INVALID, "the depth cue is off (nt_scene_set_depth_cue)");
+    if (s->lens || s->parallel > 0.0f)
+        return fail(NT_E_UNSUPPORTED, "the depth cue factors are not available while a lens or the parallel projection is set");
+    return check_renderable(s);
+}
+}  // namespace
+
+int nt_depth_cue_factors(nt_scene_t *s, int width, int height, float *factors, const nt_render_opts *opts) {
+    if (int r = cue_validate(s, width, height, factors)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const FrameJob job = view_job(width, height, ds->stream, opts, false);
+    float *factors_dev = nullptr;
+    if (int r = enqueue_cue(s, ds, job, read_switches(), nullptr, true, &factors_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    HIP_TRY(hipMemcpyAsync(factors, factors_dev, (size_t)width * height * 8, hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipStreamSynchronize(ds->stream));
+    return NT_OK;
+}
+
+int nt_depth_cue_factors_device(nt_scene_t *s, int width, int height, void *factors_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = cue_validate(s, width, height, factors_dev)) return r;
+    if (int r = only_device_strict_abort(opts, "the depth cue factors read", "their")) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
+    return enqueue_cue(s, ds, job, read_switches(), (float *)factors_dev, false, nullptr);
 }
 
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {

@@ -315,6 +315,23 @@ struct NtOutline {
     uint8_t *mask;            // [pixel] (the mask-only launches and the general route)
 };
 
+// Depth cues (nt_cue.hpp, nt_var.hip; the rule in full: ntracer_hip.h): the factors (f, g) of a pixel from its
+// own hit record, its primary ray and the camera's origin.  Every pointer is device memory; a pixel's index is
+// frame * height * width + y * width + x, frames counted within the launch.  The tint axis travels in the kernel arguments.
+struct NtCue {
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    int nframes;
+    const void *recs;         // the pixels' 16-byte hit records {dist, item, lane, n_transparent}
+    float fog_near, inv_fog;  // inv_fog = 1.0f / (fog_far - fog_near), formed once by the host in fp32
+    float fog_color[3], fog_strength;
+    int fog_background;
+    int tint;                 // 0: no tint, g = -1 everywhere
+    float tint_lo, inv_tint;  // inv_tint = 1.0f / (tint_hi - tint_lo), likewise
+    float tint_color_lo[3], tint_color_hi[3];
+    float tint_axis[NT_DEV_MAX_DIM];
+    float *factors;           // [pixel][2] (the factor launches)
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 // Outlines, fast route (opaque scenes, n <= 10, stack depth <= 32): the packet walk into li.hit_buf (li.hit_frames frames of
 // tg.width * tg.height records), then outline_shade into tg, the whole image of every frame (no bands) ...
@@ -326,6 +343,16 @@ int nt_launch_outline_mark(const NtLaunchInfo &li, const NtTarget &tg, const NtO
 // ... and the base frame (NtAdaptive::base's layout) blended with the colour where the mask is set, into tg.dest, the whole image
 // of ol.nframes frames (no bands)
 int nt_launch_outline_apply(void *stream, const uint32_t *base, const NtOutline &ol, const NtTarget &tg);
+// Depth cues, fast route (opaque scenes, n <= 10, stack depth <= 32): the packet walk into li.hit_buf (li.hit_frames frames of
+// tg.width * tg.height records), then cue_shade into tg, the whole image of every frame (no bands) ...
+int nt_launch_cue(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu);
+// ... or cue_factors_fixed into cu.factors (tg: the view and the abort word)
+int nt_launch_cue_factors_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu);
+// general route, at run-time n behind a primary-hit pass (cu.recs): the factors of every pixel of cu.nframes frames into
+// cu.factors ...
+int nt_launch_cue_factors(const NtLaunchInfo &li, const NtTarget &tg, const NtCue &cu);
+// ... or the base frame (NtAdaptive::base's layout) blended by them into tg.dest, the whole image of cu.nframes frames (no bands)
+int nt_launch_cue_apply(const NtLaunchInfo &li, const uint32_t *base, const NtCue &cu, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
 // of `nframes` frames -- 12-byte fp32 x 3 pixels as the render kernels write them, s * tg.row_count rows of `pitch_bytes` a frame

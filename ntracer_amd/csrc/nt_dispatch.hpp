@@ -16,6 +16,7 @@ struct NtLens;
 struct NtParallel;
 struct NtAo;
 struct NtOutline;
+struct NtCue;
 
 // The compile-time-N launchers, one family a primary template.  Nothing defines the primary: every dimension is the explicit
 // specialisation `template <> int nt_X_fixed<NT_INST_N>(...)` of its own translation unit (nt_inst_*.hip, compiled once per
@@ -32,6 +33,8 @@ template <int N> int nt_lens_fixed(const NtLaunchInfo &li, const NtCompositeDev 
 template <int N> int nt_parallel_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtParallel &pl);
 template <int N> int nt_ao_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao);
 template <int N> int nt_outline_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw);
+// (depth cues, nt_inst_cue.hip: N = 3..NT_DEV_MAX_FIXED like the others; the family is named for the walk it launches)
+template <int N> int nt_cue_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu, bool draw);
 
 template <int LO, typename F, int... I>
 inline bool nt_dispatch_dim_seq(int n, int &r, F &f, std::integer_sequence<int, I...>) {

@@ -1,7 +1,7 @@
 // nt_var.hip -- the run-time-n kernels (the reference's generic `tracern` / var_geometry.hpp path: n-vectors in LDS as
-// [k][lane]), the small kernels around them (camera upload, lens / parallel / ambient occlusion expansion, outline marks), and
-// every nt_launch_* of nt_device.hpp: the dispatch over the dimension (nt_dispatch.hpp) to the compile-time-N launchers of the
-// nt_inst_*.hip units, or to the run-time-n kernels here.
+// [k][lane]), the small kernels around them (camera upload, lens / parallel / ambient occlusion expansion, outline marks, depth
+// cues), and every nt_launch_* of nt_device.hpp: the dispatch over the dimension (nt_dispatch.hpp) to the compile-time-N launchers
+// of the nt_inst_*.hip units, or to the run-time-n kernels here.
 #include "nt_box.hpp"
 #include "nt_composite.hpp"
 #include "nt_query.hpp"
@@ -10,6 +10,7 @@
 #include "nt_resolve.hpp"
 #include "nt_adaptive.hpp"
 #include "nt_outline.hpp"
+#include "nt_cue.hpp"
 #include "nt_dispatch.hpp"
 #include <climits>
 
@@ -2130,6 +2131,64 @@ __global__ __launch_bounds__(256) void outline_apply(const uint32_t *base, NtOut
 }
 
 // --------------------------------------------------------------------------------------
+// Depth cues (nt_cue.hpp) behind a primary-hit pass: every scene the packet route does not take.  One lane a
+// pixel at run-time n in ao_apply's geometry (64 pixels of four rows a block, the grid's z the frame); cue_pixel and cue_blend are
+// nt_cue.hpp's.  The pixel's direction is primary_dir's, formed on the fly as ao_expand forms it: the same operands give the same
+// bits twice.
+// --------------------------------------------------------------------------------------
+__device__ __forceinline__ void cue_pixel_var(const NtTarget &tg, const NtCue &cu, int n, int x, int y, long long pix, float &f, float &g) {
+    const int4 rec = reinterpret_cast<const int4 *>(cu.recs)[pix];
+    const float *c = cu.cams + (size_t)blockIdx.z * 4 * n;
+    const float sx = tg.fovI * ((float)x - tg.half_w);
+    const float sy = tg.fovI * ((float)y - tg.half_h);
+    float len = 1.0f;
+    if (rec.y >= 0 && cu.tint) {
+        float sq = 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const float u = (c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy;
+            sq = j == 0 ? u * u : sq + u * u;
+        }
+        len = sqrtf(sq);
+    }
+    cue_pixel(cu, rec, n, [&](int k) { return ((c[3 * n + k] + c[n + k] * sx) - c[2 * n + k] * sy) / len; }, [&](int k) { return c[k]; }, f, g);
+}
+
+__global__ __launch_bounds__(256) void cue_factors(NtTarget tg, NtCue cu, int n) {
+    if (nt_aborted(tg)) return;
+    const int tid = (int)threadIdx.x;
+    const int x = (int)blockIdx.x * 64 + (tid & 63);
+    const int y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (y >= tg.height || x >= tg.width) return;
+    const long long pix = ((long long)blockIdx.z * tg.height + y) * tg.width + x;
+    float f, g;
+    cue_pixel_var(tg, cu, n, x, y, pix, f, g);
+    reinterpret_cast<float2 *>(cu.factors)[pix] = make_float2(f, g);
+}
+
+// Drawing: the base frame's pixel P (three big-endian floats, clamped to [0, 1] by the packer that wrote them) through cue_blend
+// and emit_pixel.
+__global__ __launch_bounds__(256) void cue_apply(const uint32_t *base, NtCue cu, NtTarget tg, int n) {
+    if (nt_aborted(tg)) return;
+    const int tid = (int)threadIdx.x;
+    const int x = (int)blockIdx.x * 64 + (tid & 63);
+    const int y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (y >= tg.height || x >= tg.width) return;
+    const long long pix = ((long long)blockIdx.z * tg.height + y) * tg.width + x;
+    float f, g;
+    cue_pixel_var(tg, cu, n, x, y, pix, f, g);
+    const uint32_t *p = base + pix * 3;
+    float c[3] = {__uint_as_float(bswap32(p[0])), __uint_as_float(bswap32(p[1])), __uint_as_float(bswap32(p[2]))};
+    cue_blend(cu, f, g, c);
+    PixelRef pr;
+    pr.valid = true;
+    pr.hit_index = 0;
+    pr.x = x;
+    pr.y = y;
+    pr.offset = (long long)blockIdx.z * tg.frame_stride + (long long)y * tg.pitch + (long long)x * tg.bpp;
+    emit_pixel(tg, pr, c[0], c[1], c[2]);
+}
+
+// --------------------------------------------------------------------------------------
 // Adaptive supersampling at run-time n (n = 11..64 -- BoxScene: 25..64 -- and every n under NTRACER_FORCE_VAR=1): the refine
 // kernels of nt_adaptive.hpp on composite_color_var / composite_color_var_t and on rays_box_var's evaluation.  One lane a
 // flagged pixel, one wave a block, the blocks striding over the list.
@@ -2679,4 +2738,33 @@ int nt_launch_outline_apply(void *stream, const uint32_t *base, const NtOutline 
     const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)ol.nframes);
     hipLaunchKernelGGL(outline_apply, grid, dim3(256), 0, (hipStream_t)stream, base, ol, tg);
     return finish_launch("outline drawing kernel launch");
+}
+
+// Depth cues.  The fast route (nt_cue.hpp): the fixed-n launcher of the scene's dimension -- the packet walk, then cue_shade
+// (`draw`) or cue_factors_fixed; there is no run-time-n packet walk, and the host sends those scenes through the general route
+// below.
+static int nt_launch_cue_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu, bool draw) {
+    return launch_fixed_only(li, "no packet walk for depth cues", "depth cue kernel launch",
+                             [&](auto N) { return nt_cue_packet<decltype(N)::value>(li, sc, tg, cu, draw); });
+}
+
+int nt_launch_cue(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu) {
+    return nt_launch_cue_packet(li, sc, tg, cu, true);
+}
+
+int nt_launch_cue_factors_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu) {
+    return nt_launch_cue_packet(li, sc, tg, cu, false);
+}
+
+// The general route's two kernels behind nt_launch_hits: every pixel of the launch's frames
+int nt_launch_cue_factors(const NtLaunchInfo &li, const NtTarget &tg, const NtCue &cu) {
+    const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)cu.nframes);
+    hipLaunchKernelGGL(cue_factors, grid, dim3(256), 0, (hipStream_t)li.stream, tg, cu, li.n);
+    return finish_launch("depth cue factor kernel launch");
+}
+
+int nt_launch_cue_apply(const NtLaunchInfo &li, const uint32_t *base, const NtCue &cu, const NtTarget &tg) {
+    const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)cu.nframes);
+    hipLaunchKernelGGL(cue_apply, grid, dim3(256), 0, (hipStream_t)li.stream, base, cu, tg, li.n);
+    return finish_launch("depth cue drawing kernel launch");
 }

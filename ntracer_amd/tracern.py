@@ -1074,6 +1074,99 @@ class _SceneBase(Scene):
         _lib.check(L.nt_outline_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
         return mask
 
+    def set_depth_cue(self, near=0.0, far=1.0, color=(0, 0, 0), strength=1.0, background=False, tint_axis=None, tint_range=None,
+                      tint_colors=None):
+        """Depth cues on the renders (include/ntracer_hip.h), from the primary hits of the render itself.  Fog: a
+        pixel with an opaque hit at distance t fades towards `color` by strength * clamp01((t - near) / (far - near)), and with
+        `background` so do the pixels that hit nothing at all, in full.  Tint ("colour by w"): with `tint_axis`, a Vector or n
+        numbers, the pixel's plain colour is first multiplied by the colour between tint_colors = (colour_lo, colour_hi) at
+        g = clamp01((axis . x - lo) / (hi - lo)), x the visible point and tint_range = (lo, hi); both are required exactly when
+        tint_axis is given.  set_depth_cue(None) takes the setting off.  CompositeScene only.  Supersampling, row bands,
+        statistics, a lens, the parallel projection, ambient occlusion and outlines are refused with it; calculate_color /
+        colors_at, primary_hits, ray_colors, render_rays, the ray queries, refinement_mask, occlusion_counts and outline_mask
+        ignore it.  A view setting like fov: not pickled."""
+        L = _lib.lib()
+        if near is None:
+            _lib.check(L.nt_scene_set_depth_cue(self._handle, None, None))
+            return
+        for v in (near, far, strength):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("near, far and strength must be numbers")
+
+        def colour(c, what):
+            col = [float(v) for v in c]
+            if len(col) != 3:
+                raise ValueError("%s must have three components" % what)
+            return col
+
+        cue = _lib.NtDepthCue()
+        cue.fog_near, cue.fog_far, cue.fog_strength = float(near), float(far), float(strength)
+        cue.fog_color[:] = colour(color, "color")
+        cue.fog_background = 1 if background else 0
+        axis = None
+        if tint_axis is None:
+            if tint_range is not None or tint_colors is not None:
+                raise ValueError("tint_range and tint_colors need a tint_axis")
+        else:
+            if tint_range is None or tint_colors is None:
+                raise ValueError("a tint_axis needs tint_range and tint_colors")
+            axis = np.ascontiguousarray([float(v) for v in tint_axis], f32)
+            if axis.shape != (self.dimension,):
+                raise ValueError("tint_axis must have %d components" % self.dimension)
+            lo, hi = tint_range
+            cue.tint_lo, cue.tint_hi = float(lo), float(hi)
+            c_lo, c_hi = tint_colors
+            cue.tint_color_lo[:] = colour(c_lo, "tint_colors[0]")
+            cue.tint_color_hi[:] = colour(c_hi, "tint_colors[1]")
+        _lib.check(L.nt_scene_set_depth_cue(self._handle, C.byref(cue), None if axis is None else axis.ctypes.data_as(_lib.f32p)))
+
+    @property
+    def depth_cue(self):
+        """None, or a dict of the setting: near, far, color, strength, background, and tint_axis, tint_range, tint_colors (None
+        without a tint)"""
+        on, tint, cue = C.c_int(0), C.c_int(0), _lib.NtDepthCue()
+        axis = np.zeros(self.dimension, f32)
+        _lib.check(_lib.lib().nt_scene_get_depth_cue(self._handle, C.byref(on), C.byref(cue), C.byref(tint), axis.ctypes.data_as(_lib.f32p)))
+        if not on.value:
+            return None
+        d = dict(near=float(cue.fog_near), far=float(cue.fog_far), color=tuple(float(c) for c in cue.fog_color),
+                 strength=float(cue.fog_strength), background=bool(cue.fog_background), tint_axis=None, tint_range=None, tint_colors=None)
+        if tint.value:
+            d.update(tint_axis=tuple(float(v) for v in axis), tint_range=(float(cue.tint_lo), float(cue.tint_hi)),
+                     tint_colors=(tuple(float(c) for c in cue.tint_color_lo), tuple(float(c) for c in cue.tint_color_hi)))
+        return d
+
+    def depth_cue_factors(self, width, height, device=None, strict_reference=None):
+        """The two factors (f, g) of every pixel of a width x height view of the scene's camera under the setting that is on
+        (nt_depth_cue_factors): float32 [height][width][2], f the fog factor and g the tint factor, -1 where the pixel carries
+        none -- a numpy array, or with `device` a torch device a torch tensor there, enqueued on torch's current stream."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        L = _lib.lib()
+        if device is None:
+            opts = _lib.NtRenderOpts()
+            opts.device = -1
+            if strict_reference is None:
+                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+            opts.strict_reference = 1 if strict_reference else 0
+            factors = np.zeros((height, width, 2), f32)
+            _lib.check(L.nt_depth_cue_factors(self._handle, width, height, factors.ctypes.data, C.byref(opts)))
+            return factors
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self.depth_cue is None:
+            raise ValueError("the depth cue is off (set_depth_cue)")
+        factors = torch.empty((height, width, 2), dtype=torch.float32, device=dev)
+        opts = self._rays_opts(dev, strict_reference)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_depth_cue_factors_device(self._handle, width, height, C.c_void_p(factors.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return factors
+
     def set_lens(self, lens):
         """Render through `lens` (a Lens of the image's size) instead of the pinhole; None takes it off.  fov is ignored
         while a lens is set.  Supersampling, row bands, statistics, calculate_color / colors_at and primary_hits are refused
