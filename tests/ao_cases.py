@@ -57,16 +57,11 @@ def dot_lr(a, b):
     return s
 
 
-@functools.lru_cache(maxsize=None)
-def _expected(name, clean, prune, width, height, tkey, radius, bias):
-    g, n, flat = rq.scene(name)
-    T = np.frombuffer(tkey, f32).reshape(-1, n)
+def blocked_of(n, flat, clean, prune, e, d, T, radius, bias):
+    """the rule on the primary-hit records e (dist / item / lane / normal_origin / normal [H][W]...) and the primary directions
+    d [H][W][n] of any flat scene: what _expected returns"""
+    height, width = e["item"].shape
     count = len(T)
-    env = dict([("NTRACER_CLEAN_NORMALS", "1")] if clean else [])
-    if not prune:
-        env["NTRACER_STRICT_REFERENCE"] = "1"               # (primary_hit_cases.expected: no pruning, whatever the scene)
-    e = ph.expected((name, env), width, height)
-    d, _ = ph.rays(name, width, height, 0)
     hit = np.nonzero(e["item"].ravel() >= 0)[0]
     blocked = np.full(width * height, -1, np.int32)
     dist = np.full((width * height, count), rq.FLT_MAX, f32)
@@ -97,6 +92,18 @@ def _expected(name, clean, prune, width, height, tkey, radius, bias):
     for v in out.values():
         v.setflags(write=False)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(name, clean, prune, width, height, tkey, radius, bias):
+    g, n, flat = rq.scene(name)
+    T = np.frombuffer(tkey, f32).reshape(-1, n)
+    env = dict([("NTRACER_CLEAN_NORMALS", "1")] if clean else [])
+    if not prune:
+        env["NTRACER_STRICT_REFERENCE"] = "1"               # (primary_hit_cases.expected: no pruning, whatever the scene)
+    e = ph.expected((name, env), width, height)
+    d, _ = ph.rays(name, width, height, 0)
+    return blocked_of(n, flat, clean, prune, e, d, T, radius, bias)
 
 
 def expected(case, width, height, T=None, radius=RADIUS, bias=BIAS):
