@@ -652,6 +652,79 @@ void nt_kdtree_free(nt_kdtree *t);
 int nt_polytope_clip_box(int dimension, int n_verts, const float *verts, const uint64_t *tight, int shared_for_edge, int first_free_bit,
                          const float *lo, const float *hi, float *out_lo, float *out_hi);
 
+/* ---- BoxScene hit buffers and face lines ---------------------------------------------------------------------------
+   Which face of the cube [-1, 1]^n a pixel sees, and how far away it is: hypercube_intersects (src/tracer.hpp:115-152) taken
+   one step further than the colour needs it.  For pixel (x, y) of a width x height view with the scene's camera and fov let o
+   be the camera's origin and d the primary ray's unit direction exactly as the BoxScene renders form it (integer pixel
+   coordinates): sx = fovI * (x - half_w), sy = fovI * (y - half_h), v = (forward + right * sx) - up * sy, |v|^2 summed left to
+   right, sqrtf, one IEEE division a component.  Then, in fp32 without contraction:
+     for i = 0 .. n - 1 in ascending order, skipping d_i == 0:
+       s = d_i < 0 ? 1.0f : -1.0f;  dist = (s - o_i) / d_i;
+       if dist > 0 and for every j != i:  !(fabsf((d_j * dist) + o_j) > 1.0f + ROUNDING_FUZZ), ROUNDING_FUZZ = FLT_EPSILON * 10:
+         dist >= FLT_MAX: no hit (tracer.hpp:142 with the default cutoff); else: the hit is face (i, s) at dist.  Stop.
+     no face passes: no hit.
+   The record is nt_ray_hit: dist, the Euclidean depth (d is a unit vector); item = i, the axis the face is perpendicular to;
+   lane = 1 for the face at +1 and 0 for the face at -1; n_transparent = 0.  A pixel without a hit gets FLT_MAX, -1, -1, 0.
+   Every pixel's record is written.  The outward normal is s * e_i and is not stored.  An origin inside the cube sees nothing,
+   as in the reference.  One ray a pixel: the supersampling factor is ignored, as by nt_colors_at, and so is the face-line
+   setting below.  BoxScene only: a CompositeScene handle is NT_E_INVALID ("not a box scene"); nt_primary_hits* is its
+   counterpart there.  NT_E_UNSUPPORTED while a lens or the parallel projection is set.  Up to 24 dimensions the kernel is
+   compiled for the dimension; above, and at every dimension under NTRACER_FORCE_VAR=1, the run-time-n kernel answers. */
+
+/* Host memory out ([height][width] records), the scene's current camera, one frame; returns when the records are in place.
+   Holds the scene like nt_colors_at.  NT_E_INVALID, before any device is touched: NULL scene / hits, width or height < 1, a
+   CompositeScene, width * height beyond 2^31 - 1 records. */
+int nt_box_hits(nt_scene_t *s, int width, int height, nt_ray_hit *hits, int device);
+/* `hits_dev` is DEVICE memory on opts->device; the launch is only enqueued on `hip_stream`, with the stream and lifetime rules
+   of nt_render_device.  Of `opts` (may be NULL) device and abort_device are read -- blocks that start after the abort word is
+   raised leave without writing -- and every other field must be 0, else NT_E_INVALID. */
+int nt_box_hits_device(nt_scene_t *s, int width, int height, void *hits_dev, const nt_render_opts *opts, void *hip_stream);
+/* ... frames [first, first + count) of a camera table in one launch: a pixel's record index is
+   frame * frame_stride_records + y * width + x, and the records between the frames are not touched.  NT_E_INVALID also for a
+   table of another dimension or device, a bad first / count, a stride smaller than a frame, and count * frame_stride_records
+   beyond 2^31 - 1.  Nothing is allocated. */
+int nt_box_hits_table_device(nt_scene_t *s, int width, int height, void *hits_dev, size_t frame_stride_records,
+                             const nt_camera_table_t *table, int first, int count, const nt_render_opts *opts, void *hip_stream);
+
+/* Face lines: a line along the cube's silhouette and along every edge where two of its faces meet, drawn inside the render.
+   `kinds` = 0 takes the setting off; otherwise it is an OR of NT_OUTLINE_SILHOUETTE and NT_OUTLINE_CREASE (a convex body has no
+   depth lines: NT_OUTLINE_DEPTH is refused), every colour component and `strength` finite and in [0, 1].  NT_E_INVALID for a
+   CompositeScene (nt_scene_set_outlines is its counterpart) and for a value out of range -- the setting stays as it was;
+   NT_E_LOCKED while a render holds the scene.  No device is needed.  The setting is not part of a pickled scene.
+
+   With R(p) = (dist, item, lane) the record above, the mask byte of pixel p of a W x H view is 0 when item(p) < 0, and
+   otherwise the OR, over those of the four neighbours q = (x +- 1, y), (x, y +- 1) that lie inside the image (and the frame:
+   lines never cross a frame boundary), of
+     NT_OUTLINE_SILHOUETTE  if item(q) < 0;
+     nothing                if item(q) == item(p) and lane(q) == lane(p);
+     nothing                if dist(p) > dist(q): the nearer pixel carries the line, so lines are one pixel wide (both carry it
+                            on an exact tie);
+     NT_OUTLINE_CREASE      otherwise,
+   ANDed with `kinds`.  This is the outline rule with the crease test always true: two different faces of a cube are
+   perpendicular or opposite.
+
+   A render with the setting on: P = the plain single-sample colour with each component clamped to [0, 1]; a pixel with a
+   non-zero mask becomes (P.c * (1.0f - strength)) + (color.c * strength), every other pixel is P, and either goes through the
+   format's conversion and packing as always.  With strength = 0 the frame is the plain frame byte for byte, in every format.
+   nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device honour the setting, and refuse with
+   NT_E_UNSUPPORTED ("face lines ...") before a device is touched, drawing nothing, for a supersampling factor above 1 (adaptive
+   or not), row bands, collect_stats, a lens, the parallel projection (and a row range, which only a caller inside the library
+   can ask for).  nt_colors_at / nt_calculate_color, nt_ray_colors*, nt_render_rays*, nt_adaptive_mask* and nt_box_hits* ignore
+   it.  Up to 24 dimensions one kernel computes the records of a 64 x 32 tile and its one-pixel halo into LDS, marks and draws:
+   no record crosses device memory and nothing is allocated.  Above (and under NTRACER_FORCE_VAR=1) the records of whole frames
+   go through a scratch of 16 bytes a pixel and frame under the cap of nt_scene_set_supersampling_scratch_mb, larger jobs in
+   chunks of whole frames; a single frame that does not fit is NT_E_UNSUPPORTED before anything is launched. */
+int nt_scene_set_box_lines(nt_scene_t *s, int kinds, const float color[3], float strength);
+/* any out pointer may be NULL */
+int nt_scene_get_box_lines(const nt_scene_t *s, int *kinds, float color[3], float *strength);
+/* The mask bytes alone, [height][width], one sample a pixel of the scene's current camera.  Host memory out, `marked` (may be
+   NULL) the number of non-zero bytes; of `opts` (may be NULL) device is read.  NT_E_INVALID when the setting is off, as
+   nt_outline_mask; NT_E_UNSUPPORTED under a lens or the parallel projection. */
+int nt_box_line_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts);
+/* `mask_dev` is DEVICE memory on opts->device; only enqueued on `hip_stream`.  Of `opts` device and abort_device are read and
+   every other field must be 0. */
+int nt_box_line_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

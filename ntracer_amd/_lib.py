@@ -185,6 +185,14 @@ SYMBOLS = [
     ("nt_primary_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_primary_hits_table_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(NtHitBuffers), C.c_size_t, C.c_void_p, C.c_int, C.c_int,
                                                C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_box_hits", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("nt_box_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_box_hits_table_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                           C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_scene_set_box_lines", C.c_int, [C.c_void_p, C.c_int, f32p, C.c_float]),
+    ("nt_scene_get_box_lines", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p]),
+    ("nt_box_line_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
+    ("nt_box_line_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_ray_colors", C.c_int, [C.c_void_p, C.POINTER(NtRays), C.c_void_p, C.c_int]),
     ("nt_ray_colors_device", C.c_int, [C.c_void_p, C.POINTER(NtRays), C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_render_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NtImageFormat), C.POINTER(NtRays), C.c_int]),

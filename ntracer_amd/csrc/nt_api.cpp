@@ -191,6 +191,8 @@ struct nt_scene {
     nt_depth_cue cue_set{};              // ... as the caller gave it, the tint's fields zero without a tint,
     std::vector<float> cue_axis;         // ... the tint axis [n], empty without a tint,
     float cue_inv_fog = 0.0f, cue_inv_tint = 0.0f;   // ... and the two reciprocals of the rule, formed once
+    int box_lines = 0;                   // BoxScene: != 0, the kinds of face lines on the renders (nt_scene_set_box_lines)
+    float bl_color[3] = {0, 0, 0}, bl_strength = 0.0f;
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -1450,6 +1452,92 @@ int enqueue_outlines(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 }
 
 // ---------------------------------------------------------------------------------------------
+// BoxScene face lines (nt_scene_set_box_lines; kernels in nt_boxhits.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+// What a render with the setting on refuses, checked by the entry points before a device is touched (and by enqueue_box_lines
+// again, for every way in): a pixel's mask needs the records of its neighbours in the whole pinhole view, one sample a pixel, and
+// no kernel of it keeps counters.
+int box_lines_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
+    if (!s->box_lines || s->composite) return NT_OK;
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "face lines are not available with a supersampling factor above 1 (%d)", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "face lines are not available with row bands (band_world %d): a pixel's mask needs its neighbours", b.world);
+    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "face lines are not available for a row range");
+    if (stats) return fail(NT_E_UNSUPPORTED, "face lines are not available with collect_stats");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "face lines are not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "face lines are not available while the parallel projection is set");
+    return NT_OK;
+}
+
+// the camera of frames [f0, ...) of a job as the BoxScene kernels take it
+void box_camera(const nt_scene *s, const float *cam_buf, const float *cam_dots, int f0, NtCamera &cam) {
+    cam.buf = cam_buf ? cam_buf + (size_t)f0 * 4 * s->n : nullptr;
+    cam.dots = cam_buf ? cam_dots + (size_t)f0 * 4 : nullptr;
+    cam.n = s->n;
+    if (!cam_buf) pack_camera(s->n, s->origin.data(), s->axes.data(), cam.inl);
+    camera_dots(s->n, s->origin.data(), s->axes.data(), cam.odots);
+}
+
+// The mask bytes of every pixel of the job's frames or, with job.fmt, the render that draws the lines.  Up to NT_MAX_FIXED_BOX_DIM
+// dimensions one kernel does either, its records in LDS, and needs no scratch (but the mask bytes of a host form: `mask_scratch`,
+// *mask_out).  At run-time n (and under NTRACER_FORCE_VAR=1) box_hits_var writes 16 bytes a pixel and frame into scratch under
+// the supersampling cap and box_lines_var reads them: per chunk of whole frames.  Without job.fmt the view is job.view_w x
+// job.view_h, one frame.  Enqueue only.
+int enqueue_box_lines(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, uint8_t *mask_dev, bool mask_scratch,
+                      uint8_t **mask_out) {
+    const bool draw = job.fmt != nullptr;
+    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
+    // (the mask is one sample a pixel of the whole view whatever the supersampling factor says, as nt_box_hits is)
+    if (draw) {
+        if (int r = box_lines_check(s, job.bands, job.stats, job.row_begin, job.row_count, H)) return r;
+    }
+    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const long long px = (long long)W * H;
+    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "face lines of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
+    const bool var = s->n > NT_MAX_FIXED_BOX_DIM || sw.force_var;
+    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const long long per_frame = px * ((var ? 16 : 0) + (mask_scratch ? 1 : 0));
+    if (per_frame > cap)
+        return fail(NT_E_UNSUPPORTED, "face lines of a %d x %d image: the scratch of one frame (%lld bytes) does not fit the scratch buffer of "
+                    "%lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    int chunk_frames = job.nframes;
+    if (var) chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame),
+                                                                             std::min<long long>(INT_MAX / px, std::max(sw.chunk_frames, 1))));
+    void *recs = nullptr;
+    if (per_frame > 0) {
+        if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame))) return e;
+        char *at = (char *)ds->samples.p;
+        if (var) { recs = at; at += (size_t)chunk_frames * px * 16; }
+        if (mask_scratch) mask_dev = (uint8_t *)at;
+    }
+    if (mask_out) *mask_out = mask_dev;
+    NtTarget tg;
+    if (draw) {
+        if (int r = fill_target(s, ds, job, tg)) return r;
+    } else {
+        view_target(s, W, H, job.abort_word, tg);
+    }
+    NtBoxFaces bf{};
+    bf.mode = draw ? NT_BOX_FACES_DRAW : NT_BOX_FACES_MASK;
+    bf.recs = recs;
+    bf.frame_stride = px;
+    bf.mask = mask_dev;
+    bf.kinds = s->box_lines;
+    for (int k = 0; k < 3; ++k) bf.color[k] = s->bl_color[k];
+    bf.strength = s->bl_strength;
+    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
+        const int nf = std::min(chunk_frames, job.nframes - f0);
+        const NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
+        NtTarget ft = tg;
+        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        NtCamera cam;
+        box_camera(s, job.cam_buf, job.cam_dots, f0, cam);
+        if (int r = nt_launch_box_faces(li, cam, ft, bf)) return launch_failed(r);
+    }
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // depth cues (nt_scene_set_depth_cue; kernels in nt_cue.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1749,6 +1837,8 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
         return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->ao_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
         return enqueue_ao(s, ds, job, sw, nullptr, nullptr);
+    if (s->box_lines && !s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
+        return enqueue_box_lines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->lens) return enqueue_lens(s, ds, job, sw);
     if (s->parallel > 0.0f) return enqueue_parallel(s, ds, job, sw);
     if (s->supersampling > 1 && s->adaptive && !job.colors_out && !job.samples_pass && !job.counters_pass)
@@ -1810,6 +1900,7 @@ int render_checks(const nt_scene *s, const Format &f, const Bands &b, bool stats
     if (int r = cue_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = outline_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = ao_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
+    if (int r = box_lines_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = lens_check(s, f.width, f.height, b, stats, false)) return r;
     if (int r = parallel_check(s, b, stats, false)) return r;
     return adaptive_check(s, b, stats);
@@ -2155,6 +2246,83 @@ int hits_device(nt_scene *s, int width, int height, const nt_hit_buffers *out, l
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     return hits_enqueue(s, ds, width, height, out, frame_stride, cams, count, opts && opts->strict_reference,
                         opts ? (const int *)opts->abort_device : nullptr, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// BoxScene hit buffers: the face of the cube under every pixel and its distance (kernels in nt_boxhits.hpp)
+// ---------------------------------------------------------------------------------------------
+
+// what can be refused without a device
+int box_hits_validate(const nt_scene *s, int width, int height, const void *hits, long long frame_stride, long long nframes) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!hits) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (s->composite) return fail(NT_E_INVALID, "not a box scene");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "BoxScene hit buffers are not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "BoxScene hit buffers are not available while the parallel projection is set");
+    if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 records", width, height);
+    if (frame_stride < (long long)width * height) return fail(NT_E_INVALID, "frame_stride_records is smaller than one frame");
+    if (frame_stride > INT_MAX || nframes * frame_stride > INT_MAX)
+        return fail(NT_E_INVALID, "%lld frames of %lld records are beyond 2^31 - 1 records", nframes, frame_stride);
+    return NT_OK;
+}
+
+// the device forms take two fields of their options; `reader` is the subject of the refusal
+int only_device_abort(const nt_render_opts *opts, const char *reader) {
+    if (opts && (opts->band_rank || opts->band_world || opts->band_rows || opts->compact || opts->strict_reference || opts->collect_stats ||
+                 opts->overlapped))
+        return fail(NT_E_INVALID, "%s reads device and abort_device of its options: every other field must be 0", reader);
+    return NT_OK;
+}
+
+// The launch of one pass: `recs_dev` is device memory, `cam_buf` / `cam_dots` the frames' cameras and their dot products in
+// device memory (nullptr: the scene's current camera, one frame, in the kernel arguments as for a render).
+int box_hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, void *recs_dev, long long frame_stride, const float *cam_buf,
+                     const float *cam_dots, int nframes, const int *abort_word, hipStream_t stream) {
+    const RenderSwitches sw = read_switches();
+    NtTarget tg;
+    view_target(s, width, height, abort_word, tg);
+    tg.frame_stride = frame_stride * (long long)sizeof(nt_ray_hit);
+    NtCamera cam;
+    box_camera(s, cam_buf, cam_dots, 0, cam);
+    const NtLaunchInfo li = launch_info(s, ds, sw, nframes, stream);
+    NtBoxFaces bf{};
+    bf.mode = NT_BOX_FACES_RECORDS;
+    bf.recs = recs_dev;
+    bf.frame_stride = frame_stride;
+    if (int r = nt_launch_box_faces(li, cam, tg, bf)) return launch_failed(r);
+    return NT_OK;
+}
+
+int box_hits_host(nt_scene *s, int width, int height, nt_ray_hit *hits, int device) {
+    if (int r = box_hits_validate(s, width, height, hits, (long long)width * height, 1)) return r;
+    RenderGuard guard(s);   // held like nt_colors_at holds it
+    if (int r = guard.acquire()) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, nullptr, device, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const size_t rbytes = (size_t)width * height * sizeof(nt_ray_hit);
+    if (int r = ds->probes.ensure(rbytes)) return r;
+    hipStream_t st = ds->stream;
+    if (int r = box_hits_enqueue(s, ds, width, height, ds->probes.p, (long long)width * height, nullptr, nullptr, 1, nullptr, st)) {
+        (void)hipStreamSynchronize(st);
+        return r;
+    }
+    HIP_TRY(hipMemcpyAsync(hits, ds->probes.p, rbytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return NT_OK;
+}
+
+// `cams` / `dots`: the cameras of the `count` frames in memory of device `cams_device`, or nullptr for the scene's current camera
+int box_hits_device(nt_scene *s, int width, int height, void *hits_dev, long long frame_stride, const float *cams, const float *dots,
+                    int cams_device, int count, const nt_render_opts *opts, void *hip_stream) {
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds, cams ? cams_device : -1, "pass")) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    return box_hits_enqueue(s, ds, width, height, hits_dev, frame_stride, cams, dots, count, opts ? (const int *)opts->abort_device : nullptr,
+                            (hipStream_t)hip_stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2642,7 +2810,7 @@ int nt_scene_get_ambient_occlusion(const nt_scene_t *s, int *count, float *direc
 
 int nt_scene_set_outlines(nt_scene_t *s, int enabled, float crease_cos, float depth_gap, const float color[3], float strength) {
     if (!s) return fail(NT_E_INVALID, "scene is NULL");
-    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no outlines");
+    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no outlines: its lines are nt_scene_set_box_lines");
     if (enabled) {
         if (!color) return fail(NT_E_INVALID, "the outline colour is NULL");
         if (!(crease_cos >= 0.0f && crease_cos <= 1.0f)) return fail(NT_E_INVALID, "the outlines' crease_cos must lie in [0, 1]");
@@ -2668,6 +2836,34 @@ int nt_scene_get_outlines(const nt_scene_t *s, int *enabled, float *crease_cos, 
     if (depth_gap) *depth_gap = s->ol_depth_gap;
     if (color) for (int k = 0; k < 3; ++k) color[k] = s->ol_color[k];
     if (strength) *strength = s->ol_strength;
+    return NT_OK;
+}
+
+int nt_scene_set_box_lines(nt_scene_t *s, int kinds, const float color[3], float strength) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (s->composite) return fail(NT_E_INVALID, "not a box scene: CompositeScene has outlines (nt_scene_set_outlines)");
+    if (kinds) {
+        if (kinds & ~(NT_OUTLINE_SILHOUETTE | NT_OUTLINE_CREASE))
+            return fail(NT_E_INVALID, "the face lines' kinds are an OR of NT_OUTLINE_SILHOUETTE and NT_OUTLINE_CREASE (%d)", kinds);
+        if (!color) return fail(NT_E_INVALID, "the face lines' colour is NULL");
+        for (int k = 0; k < 3; ++k)
+            if (!(color[k] >= 0.0f && color[k] <= 1.0f)) return fail(NT_E_INVALID, "the face lines' colour components must lie in [0, 1]");
+        if (!(strength >= 0.0f && strength <= 1.0f)) return fail(NT_E_INVALID, "the face lines' strength must lie in [0, 1]");
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->box_lines = kinds;
+    for (int k = 0; k < 3; ++k) s->bl_color[k] = kinds ? color[k] : 0.0f;
+    s->bl_strength = kinds ? strength : 0.0f;
+    return NT_OK;
+}
+
+int nt_scene_get_box_lines(const nt_scene_t *s, int *kinds, float color[3], float *strength) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (s->composite) return fail(NT_E_INVALID, "not a box scene");
+    if (kinds) *kinds = s->box_lines;
+    if (color) for (int k = 0; k < 3; ++k) color[k] = s->bl_color[k];
+    if (strength) *strength = s->bl_strength;
     return NT_OK;
 }
 
@@ -3139,6 +3335,49 @@ int nt_depth_cue_factors_device(nt_scene_t *s, int width, int height, void *fact
     return enqueue_cue(s, ds, job, read_switches(), (float *)factors_dev, false, nullptr);
 }
 
+namespace {
+// what both forms of nt_box_line_mask check before a device is touched
+int box_lines_validate(const nt_scene *s, int width, int height, const void *mask) {
+    if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (s->composite) return fail(NT_E_INVALID, "not a box scene");
+    if (!s->box_lines) return fail(NT_E_INVALID, "face lines are off (nt_scene_set_box_lines)");
+    if (s->lens || s->parallel > 0.0f)
+        return fail(NT_E_UNSUPPORTED, "the face-line mask is not available while a lens or the parallel projection is set");
+    if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 pixels", width, height);
+    return NT_OK;
+}
+}  // namespace
+
+int nt_box_line_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts) {
+    if (int r = box_lines_validate(s, width, height, mask)) return r;
+    RenderGuard guard(s);
+    if (int r = guard.acquire()) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const FrameJob job = view_job(width, height, ds->stream, opts, false);
+    uint8_t *mask_dev = nullptr;
+    if (int r = enqueue_box_lines(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    const size_t count = (size_t)width * height;
+    HIP_TRY(hipMemcpyAsync(mask, mask_dev, count, hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipStreamSynchronize(ds->stream));
+    if (marked) *marked = (long long)(count - (size_t)std::count(mask, mask + count, (uint8_t)0));
+    return NT_OK;
+}
+
+int nt_box_line_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = box_lines_validate(s, width, height, mask_dev)) return r;
+    if (int r = only_device_abort(opts, "the face-line mask")) return r;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);
+    return enqueue_box_lines(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
+}
+
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {
     if (!s || (count > 0 && (!xs || !ys || !rgb))) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1 || count < 0) return fail(NT_E_INVALID, "invalid view size or count");
@@ -3212,6 +3451,28 @@ int nt_primary_hits_table_device(nt_scene_t *s, int width, int height, const nt_
     if (int r = hits_validate(s, width, height, out, (long long)frame_stride_records, count)) return r;
     if (int r = only_device_strict_abort(opts, "a primary-hit pass reads")) return r;
     return hits_device(s, width, height, out, (long long)frame_stride_records, table->dev + (size_t)first * 4 * table->n, table->device, count, opts, hip_stream);
+}
+
+int nt_box_hits(nt_scene_t *s, int width, int height, nt_ray_hit *hits, int device) {
+    return box_hits_host(s, width, height, hits, device);
+}
+
+int nt_box_hits_device(nt_scene_t *s, int width, int height, void *hits_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = box_hits_validate(s, width, height, hits_dev, (long long)width * height, 1)) return r;
+    if (int r = only_device_abort(opts, "a BoxScene hit pass")) return r;
+    return box_hits_device(s, width, height, hits_dev, (long long)width * height, nullptr, nullptr, -1, 1, opts, hip_stream);
+}
+
+int nt_box_hits_table_device(nt_scene_t *s, int width, int height, void *hits_dev, size_t frame_stride_records, const nt_camera_table_t *table,
+                             int first, int count, const nt_render_opts *opts, void *hip_stream) {
+    if (!s || !table) return fail(NT_E_INVALID, "NULL argument");
+    if (table->n != s->n) return fail(NT_E_INVALID, "the camera table is for %d dimensions, the scene has %d", table->n, s->n);
+    if (first < 0 || count < 1 || first > table->nframes - count) return fail(NT_E_INVALID, "frames %d..%d are not in a table of %d", first, first + count - 1, table->nframes);
+    if (frame_stride_records > (size_t)INT_MAX) return fail(NT_E_INVALID, "frame_stride_records is beyond 2^31 - 1 records");
+    if (int r = box_hits_validate(s, width, height, hits_dev, (long long)frame_stride_records, count)) return r;
+    if (int r = only_device_abort(opts, "a BoxScene hit pass")) return r;
+    return box_hits_device(s, width, height, hits_dev, (long long)frame_stride_records, table->dev + (size_t)first * 4 * table->n,
+                           table->dev + (size_t)table->nframes * 4 * table->n + (size_t)first * 4, table->device, count, opts, hip_stream);
 }
 
 int nt_ray_colors(nt_scene_t *s, const nt_rays *rays, float *rgb, int device) {

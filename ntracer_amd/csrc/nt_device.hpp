@@ -332,7 +332,28 @@ struct NtCue {
     float *factors;           // [pixel][2] (the factor launches)
 };
 
+// BoxScene hit buffers and face lines (nt_boxhits.hpp, nt_var.hip; the rules in full: ntracer_hip.h): the face
+// record of every pixel of li.nframes views of tg.width x tg.height, or what follows from the records of a pixel and its four
+// neighbours -- the mask bytes, or the frame with the lines drawn.  Every pointer is device memory; a pixel's record index is
+// frame * frame_stride + y * width + x, its mask byte lies at frame * height * width + y * width + x.
+#define NT_BOX_FACES_RECORDS 0        // the records into `recs`
+#define NT_BOX_FACES_MASK 1           // the mask bytes into `mask`
+#define NT_BOX_FACES_DRAW 2           // the plain frame with the lines drawn, into the NtTarget that travels with it
+struct NtBoxFaces {
+    int mode;                 // NT_BOX_FACES_*
+    void *recs;               // records {float dist; int item, lane, n_transparent} (nt_ray_hit): item = axis, lane = side.  MASK and
+                              // DRAW: scratch for the run-time-n kernels alone (the compile-time-N kernel keeps its records in LDS)
+    long long frame_stride;   // records between frames, >= width * height
+    uint8_t *mask;            // MASK: [frame][height][width]
+    int kinds;                // MASK, DRAW: the setting's OR of NT_DEV_OUTLINE_SILHOUETTE and NT_DEV_OUTLINE_CREASE
+    float color[3], strength; // DRAW
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
+// BoxScene hit buffers and face lines: the kernels of nt_boxhits.hpp at the scene's dimension, or box_hits_var (and, behind it,
+// box_lines_var on bf.recs).  RECORDS, MASK: tg is the view and the abort word; DRAW: the whole image of every frame (no bands).
+// The cameras travel as for nt_launch_box.
+int nt_launch_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxFaces &bf);
 // Outlines, fast route (opaque scenes, n <= 10, stack depth <= 32): the packet walk into li.hit_buf (li.hit_frames frames of
 // tg.width * tg.height records), then outline_shade into tg, the whole image of every frame (no bands) ...
 int nt_launch_outline(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol);

@@ -17,6 +17,7 @@ struct NtParallel;
 struct NtAo;
 struct NtOutline;
 struct NtCue;
+struct NtBoxFaces;
 
 // The compile-time-N launchers, one family a primary template.  Nothing defines the primary: every dimension is the explicit
 // specialisation `template <> int nt_X_fixed<NT_INST_N>(...)` of its own translation unit (nt_inst_*.hip, compiled once per
@@ -35,6 +36,8 @@ template <int N> int nt_ao_fixed(const NtLaunchInfo &li, const NtCompositeDev &s
 template <int N> int nt_outline_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw);
 // (depth cues, nt_inst_cue.hip: N = 3..NT_DEV_MAX_FIXED like the others; the family is named for the walk it launches)
 template <int N> int nt_cue_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu, bool draw);
+// (BoxScene hit buffers, nt_inst_boxhits.hip: N = 3..NT_DEV_MAX_FIXED_BOX like the other BoxScene families)
+template <int N> int nt_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxFaces &bf);
 
 template <int LO, typename F, int... I>
 inline bool nt_dispatch_dim_seq(int n, int &r, F &f, std::integer_sequence<int, I...>) {

@@ -11,6 +11,7 @@
 #include "nt_adaptive.hpp"
 #include "nt_outline.hpp"
 #include "nt_cue.hpp"
+#include "nt_boxhits.hpp"
 #include "nt_dispatch.hpp"
 #include <climits>
 
@@ -1919,6 +1920,161 @@ __global__ __launch_bounds__(64) void rays_box_var(NtRayJob job, NtTarget tg, in
     }
 }
 
+// BoxScene hit buffers at run-time n (nt_boxhits.hpp has the compile-time-N kernel and the record): rays_box_var's layout and
+// evaluation -- the direction as a per-lane n-vector in LDS, [k][lane] -- with the camera's rows behind it, staged once a block as
+// box_kernel_var stages them, keeping the face and the distance instead of the shade.  One wave a block, a lane walks a column
+// of NT_BOXROWS rows; frames in blockIdx.z.
+__global__ __launch_bounds__(64) void box_hits_var(NtCamera cam, NtTarget tg, NtBoxFaces bf) {
+    extern __shared__ float lds_vec[];    // [n][64] direction, then [4][n] camera rows (broadcast reads)
+    if (nt_aborted(tg)) return;           // (every lane reads the same word: the whole block leaves, ahead of the barrier)
+    const int lane = (int)threadIdx.x;
+    const int n = cam.n;
+    float *camrow = lds_vec + (size_t)n * 64;
+    {
+        const float *src = cam.buf ? cam.buf + (size_t)blockIdx.z * 4 * n : nullptr;
+        for (int k = lane; k < 4 * n; k += 64) camrow[k] = src ? src[k] : cam.inl[k];
+    }
+    __syncthreads();
+    const float *c = camrow;              // origin, right, up, forward
+    float *dir = lds_vec + lane;          // dir[j] at dir[j * 64]
+    float dots[4];
+    if (cam.buf) {
+        const float *dp = cam.dots + (size_t)blockIdx.z * 4;
+        dots[0] = dp[0]; dots[1] = dp[1]; dots[2] = dp[2]; dots[3] = dp[3];
+    } else {
+        dots[0] = cam.odots[0]; dots[1] = cam.odots[1]; dots[2] = cam.odots[2]; dots[3] = cam.odots[3];
+    }
+    const int x = (int)blockIdx.x * 64 + lane;
+    if (x >= tg.width) return;
+    const float sx = tg.fovI * ((float)x - tg.half_w);
+    int4 *out = reinterpret_cast<int4 *>(bf.recs) + (long long)blockIdx.z * bf.frame_stride + x;
+    for (int rr = 0; rr < NT_BOXROWS; ++rr) {
+        const int y = (int)blockIdx.y * NT_BOXROWS + rr;
+        if (y >= tg.height) return;
+        const float sy = tg.fovI * ((float)y - tg.half_h);
+        float sq = 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const float v = (c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy;
+            dir[j * 64] = v;
+            sq = j == 0 ? v * v : sq + v * v;
+        }
+        const bool maybe = box_may_hit(n, dots, sx, sy, sq);
+        int face = -1, side = -1;
+        float fdist = FLT_MAX;
+        if (__builtin_amdgcn_ballot_w64(maybe) != 0ull) {
+            const float len = sqrtf(sq);
+            for (int j = 0; j < n; ++j) dir[j * 64] = dir[j * 64] / len;
+            bool done = false;
+            float aK = 0.0f, bK = 1.0f, oK = 0.0f;
+            bool any = false;
+            for (int i = 0; i < n; ++i) {
+                const float di = dir[i * 64];
+                const float oi = c[i];
+                const float num = (di < 0.0f ? 1.0f : -1.0f) - oi;
+                const bool pre = maybe && ((num > 0.0f && di > 0.0f) || (num < 0.0f && di < 0.0f));
+                const float a = fabsf(num), bb = fabsf(di);
+                if (pre && (!any || a * bK > aK * bb)) { aK = a; bK = bb; oK = oi; any = true; }
+            }
+            const float mu = 1e-4f * (1.0f + fabsf(oK));
+            const float aKm = (aK - mu) * (1.0f - 1e-6f);
+            for (int i = 0; i < n; ++i) {
+                const float di = dir[i * 64];
+                const float oi = c[i];
+                const float num = (di < 0.0f ? 1.0f : -1.0f) - oi;
+                const bool pre = maybe && ((num > 0.0f && di > 0.0f) || (num < 0.0f && di < 0.0f));
+                const bool tie = pre && !done && !(fabsf(num) * bK < fabsf(di) * aKm);
+                if (!tie) continue;
+                const float dist = num / di;
+                bool ok = dist > 0.0f;
+                for (int j = 0; j < n; ++j) {
+                    if (j != i) {
+                        const float p = dir[j * 64] * dist + c[j];
+                        ok = ok && !(fabsf(p) > (1.0f + NT_FUZZ));
+                    }
+                }
+                if (ok) {
+                    done = true;
+                    // `if(dist >= cutoff) return 0` with cutoff = FLT_MAX (tracer.hpp:142): a miss
+                    if (!(dist >= FLT_MAX)) { face = i; side = di < 0.0f ? 1 : 0; fdist = dist; }
+                }
+            }
+        }
+        out[(long long)y * tg.width] = make_int4(__float_as_int(fdist), face, side, 0);
+    }
+}
+
+// Face lines at run-time n, behind box_hits_var: one lane a pixel reads its record and those of its four neighbours inside the
+// image from `bf.recs` ([frame][height][width]), applies the rule (ntracer_hip.h; box_line_pair of nt_boxhits.hpp) and
+// writes the mask byte -- or (DRAW) re-forms its own ray for the plain colour, |d_face| or the background from d_0, blends and
+// emits.  A block: 64 x 4 pixels of frame blockIdx.z; the camera's rows staged in LDS as box_kernel_var stages them.
+template <bool DRAW>
+__global__ __launch_bounds__(256) void box_lines_var(NtCamera cam, NtTarget tg, NtBoxFaces bf) {
+    extern __shared__ float lds_vec[];    // [4][n] camera rows (broadcast reads)
+    if (nt_aborted(tg)) return;           // (the whole block leaves, ahead of the barrier)
+    const int tid = (int)threadIdx.x;
+    const int n = cam.n;
+    if (DRAW) {
+        const float *src = cam.buf ? cam.buf + (size_t)blockIdx.z * 4 * n : nullptr;
+        for (int k = tid; k < 4 * n; k += 256) lds_vec[k] = src ? src[k] : cam.inl[k];
+        __syncthreads();
+    }
+    const int x = (int)blockIdx.x * 64 + (tid & 63), y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (x >= tg.width || y >= tg.height) return;
+    const int4 *fr = reinterpret_cast<const int4 *>(bf.recs) + (long long)blockIdx.z * bf.frame_stride;
+    const long long at = (long long)y * tg.width + x;
+    const int4 rec = fr[at];
+    int m = 0;
+    if (rec.y >= 0) {
+        const float pd = __int_as_float(rec.x);
+        for (int k = 0; k < 4; ++k) {
+            const int qx = x + (k == 0 ? -1 : (k == 1 ? 1 : 0));
+            const int qy = y + (k == 2 ? -1 : (k == 3 ? 1 : 0));
+            if (qx < 0 || qy < 0 || qx >= tg.width || qy >= tg.height) continue;
+            const int4 q = fr[(long long)qy * tg.width + qx];
+            m |= box_line_pair(pd, 2 * rec.y + rec.z, __int_as_float(q.x), q.y < 0 ? -1 : 2 * q.y + q.z);
+        }
+        m &= bf.kinds;
+    }
+    if (!DRAW) {
+        bf.mask[((long long)blockIdx.z * tg.height + y) * tg.width + x] = (uint8_t)m;
+        return;
+    }
+    const float *c = lds_vec;             // origin, right, up, forward
+    const float sx = tg.fovI * ((float)x - tg.half_w);
+    const float sy = tg.fovI * ((float)y - tg.half_h);
+    const int pick = rec.y >= 0 ? rec.y : 0;
+    float sq = 0.0f, vp = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float v = (c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy;
+        sq = j == 0 ? v * v : sq + v * v;
+        vp = j == pick ? v : vp;
+    }
+    const float xval = vp / sqrtf(sq);
+    PixelRef pr;
+    pr.x = x;
+    pr.y = y;
+    pr.offset = (long long)blockIdx.z * tg.frame_stride + (long long)y * tg.pitch + (long long)x * tg.bpp;
+    pr.hit_index = 0;
+    pr.valid = true;
+    float r, g, b;
+    if (rec.y >= 0) {
+        const float shade = fabsf(xval);
+        r = shade * 1.0f;
+        g = shade * 0.5f;
+        b = shade * 0.5f;
+    } else {
+        box_background(xval, r, g, b);
+    }
+    const float keep = 1.0f - bf.strength;
+    float p[3] = {r, g, b};
+    for (int k = 0; k < 3; ++k) {
+        float v = p[k] > 0.0f ? p[k] : 0.0f;
+        v = v < 1.0f ? v : 1.0f;
+        p[k] = m != 0 ? (v * keep) + (bf.color[k] * bf.strength) : v;
+    }
+    emit_pixel(tg, pr, p[0], p[1], p[2]);
+}
+
 // --------------------------------------------------------------------------------------
 // A render through a lens (nt_lens.hpp) on the ray-colour kernels above: every scene the packet walk does not take.  The table
 // and the frame's camera are expanded into the unnormalised directions v[j] = (fwd[j] * sz + right[j] * sx) - up[j] * sy of a
@@ -2464,6 +2620,30 @@ int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &t
         }
     }
     return finish_launch("box kernel launch");
+}
+
+// BoxScene hit buffers and face lines (nt_boxhits.hpp): the fixed-n launcher of the scene's dimension, or the run-time-n
+// kernels above -- box_hits_var into bf.recs and, for the mask or the drawing, box_lines_var behind it.  Kept apart from
+// nt_launch_box: this is no route of a plain render.
+int nt_launch_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxFaces &bf) {
+    int r = var_dim_check(li.n);
+    if (r) return r;
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_box_faces<decltype(N)::value>(li, cam, tg, bf); })) {
+        if (!bf.recs || (bf.mode == NT_BOX_FACES_MASK && !bf.mask) ||
+            (bf.mode == NT_BOX_FACES_DRAW && (tg.row_begin != 0 || tg.row_count != tg.height || tg.band_world > 1 || tg.colors_out))) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a face-line launch at run-time n without its records, or not for whole frames");
+            return -1;
+        }
+        hipStream_t st = (hipStream_t)li.stream;
+        const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + NT_BOXROWS - 1) / NT_BOXROWS), (unsigned)li.nframes);
+        hipLaunchKernelGGL(box_hits_var, grid, dim3(64), ((size_t)li.n * 64 + (size_t)4 * li.n) * sizeof(float), st, cam, tg, bf);
+        const dim3 lgrid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)li.nframes);
+        const size_t lds = (size_t)4 * li.n * sizeof(float);
+        if (bf.mode == NT_BOX_FACES_DRAW) hipLaunchKernelGGL(box_lines_var<true>, lgrid, dim3(256), lds, st, cam, tg, bf);
+        else if (bf.mode == NT_BOX_FACES_MASK) hipLaunchKernelGGL(box_lines_var<false>, lgrid, dim3(256), lds, st, cam, tg, bf);
+    }
+    if (r) return r;
+    return finish_launch("box face kernel launch");
 }
 
 // words per ray_color frame of composite_kernel_var_t (the host sizes NtCompositeDev::tframes with it)

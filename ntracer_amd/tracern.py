@@ -598,6 +598,33 @@ class PrimaryHits(object):
                                self._scene._object_of(item & 3, item >> 2), int(self.lane[at]))
 
 
+class FaceHits(object):
+    """What BoxScene.face_hits answers with: which face of the cube every pixel of a view sees and how far away it is, as numpy
+    arrays or as torch tensors on the device, views of the records the library wrote -- dist (FLT_MAX: nothing), axis (the axis
+    the face is perpendicular to, -1: nothing), side (1: the face at +1, 0: the face at -1, -1: nothing) and hit (bool), each
+    [height][width], with a camera table [count][height][width]; records is the raw buffer, [frames * stride][4] int32 (dist's
+    bits, axis, side, 0)."""
+
+    def __init__(self, dimension, width, height, frames, stride, records):
+        self.dimension = dimension
+        self.width, self.height, self.frames = width, height, frames
+        self.records = records
+        r = records.reshape(frames or 1, stride, 4)[:, :width * height].reshape(frames or 1, height, width, 4)
+        if frames is None:
+            r = r[0]
+        self.dist = _as_f32(r[..., 0])
+        self.axis, self.side = r[..., 1], r[..., 2]
+        self.hit = self.axis >= 0
+
+    def normal(self, x, y, frame=0):
+        """the outward unit normal of the face under pixel (x, y) as a Vector, or None where the ray sees nothing"""
+        at = (int(y), int(x)) if self.frames is None else (int(frame), int(y), int(x))
+        axis = int(self.axis[at])
+        if axis < 0:
+            return None
+        return Vector.axis(self.dimension, axis, 1.0 if int(self.side[at]) else -1.0)
+
+
 def _as_f32(a):
     """the same 32 bits as fp32: numpy or torch"""
     if hasattr(a, "is_cuda"):
@@ -1352,6 +1379,122 @@ class BoxScene(_SceneBase):
             raise ValueError(_lib.last_error())
         self._handle = h
         self._init_common(n)
+
+    def face_hits(self, width, height, device=-1, out=None, table=None, first=0, count=None, frame_stride=None):
+        """Which face of the cube is under each pixel of a width x height view, and how far away (nt_box_hits; the rule in full:
+        include/ntracer_hip.h).  Returns a FaceHits: dist, axis, side, hit, each [height][width], and records.
+
+        `device` an int: numpy arrays through host memory, the scene's current camera.  `device` a torch device (or `out`
+        given): torch tensors that stay on the device, enqueued on torch's current stream without a synchronisation.  `out`:
+        the caller's own contiguous int32 tensor [frames * frame_stride][4].  `table` (a render.CameraTable): frames
+        [first, first + count) of it in one launch, every array [count][height][width], `frame_stride` >= width * height
+        records between the frames, whose records in between are not touched (torch only: the table lives on a device)."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the view must be at least 1 x 1")
+        per_frame = width * height
+        torch_device = device if type(device).__module__.split(".")[0] == "torch" or isinstance(device, str) else None
+        on_device = torch_device is not None or out is not None or table is not None
+        L = _lib.lib()
+        if not on_device:
+            recs = np.zeros((per_frame, 4), np.int32)
+            _lib.check(L.nt_box_hits(self._handle, width, height, recs.ctypes.data, int(device)))
+            return FaceHits(self._n, width, height, None, per_frame, recs)
+        import torch
+        frames = 1
+        if table is not None:
+            first = int(first)
+            frames = table.frames - first if count is None else int(count)
+        stride = per_frame if frame_stride is None else int(frame_stride)
+        if stride < per_frame or (table is None and stride != per_frame):
+            raise ValueError("frame_stride must be at least width * height (and is only taken with a camera table)")
+        if out is not None:
+            dev = out.device
+        elif torch_device is not None:
+            dev = torch.device(torch_device)
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device() if int(device) < 0 else int(device))
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        shape = (frames * stride, 4)
+        if out is None:
+            recs = torch.zeros(shape, dtype=torch.int32, device=dev)          # (zeroed on the stream)
+        else:
+            recs = out
+            if recs.dtype != torch.int32 or not recs.is_contiguous() or tuple(recs.shape) != shape:
+                raise ValueError("out must be a contiguous int32 tensor of shape %r on %s" % (shape, dev))
+        opts = _lib.NtRenderOpts()
+        opts.device = dev.index
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if table is None:
+            _lib.check(L.nt_box_hits_device(self._handle, width, height, C.c_void_p(recs.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        else:
+            _lib.check(L.nt_box_hits_table_device(self._handle, width, height, C.c_void_p(recs.data_ptr()), stride, table._h, first, frames,
+                                                  C.byref(opts), C.c_void_p(stream)))
+        return FaceHits(self._n, width, height, None if table is None else frames, stride, recs)
+
+    def set_face_lines(self, color=(0, 0, 0), strength=1.0, silhouette=True, edges=True):
+        """Draw a line along the cube's silhouette and along every edge where two of its faces meet, inside the render
+        (include/ntracer_hip.h).  A pixel that sees a face is marked when one of its four neighbours sees nothing
+        (`silhouette`) or sees another face that is not nearer (`edges`); a marked pixel's plain colour P becomes
+        P * (1 - strength) + color * strength.  set_face_lines(None) takes the setting off.  Supersampling, row bands,
+        statistics, a lens and the parallel projection are refused with it; calculate_color / colors_at, face_hits, ray_colors,
+        render_rays and refinement_mask ignore it.  A view setting like fov: not pickled."""
+        L = _lib.lib()
+        if color is None:
+            _lib.check(L.nt_scene_set_box_lines(self._handle, 0, None, 0.0))
+            return
+        if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)):
+            raise ValueError("strength must be a number")
+        col = np.ascontiguousarray([float(c) for c in color], f32)
+        if col.shape != (3,):
+            raise ValueError("color must have three components")
+        kinds = (_lib.NT_OUTLINE_SILHOUETTE if silhouette else 0) | (_lib.NT_OUTLINE_CREASE if edges else 0)
+        if not kinds:
+            raise ValueError("face lines without silhouette and edges: set_face_lines(None) takes the setting off")
+        _lib.check(L.nt_scene_set_box_lines(self._handle, kinds, col.ctypes.data_as(_lib.f32p), float(strength)))
+
+    @property
+    def face_lines(self):
+        """None, or a dict of the setting: silhouette, edges, color (three floats), strength"""
+        kinds, st = C.c_int(0), C.c_float(0.0)
+        col = np.zeros(3, f32)
+        _lib.check(_lib.lib().nt_scene_get_box_lines(self._handle, C.byref(kinds), col.ctypes.data_as(_lib.f32p), C.byref(st)))
+        if not kinds.value:
+            return None
+        return dict(silhouette=bool(kinds.value & _lib.NT_OUTLINE_SILHOUETTE), edges=bool(kinds.value & _lib.NT_OUTLINE_CREASE),
+                    color=tuple(float(c) for c in col), strength=float(st.value))
+
+    def face_line_mask(self, width, height, device=None):
+        """The face-line mask of a width x height view of the scene's camera under the setting that is on (nt_box_line_mask):
+        uint8 [height][width], 0 or an OR of NT_OUTLINE_SILHOUETTE and NT_OUTLINE_CREASE -- a numpy array, or with `device` a
+        torch device a torch tensor there, enqueued on torch's current stream."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        L = _lib.lib()
+        if device is None:
+            opts = _lib.NtRenderOpts()
+            opts.device = -1
+            mask = np.zeros((height, width), np.uint8)
+            _lib.check(L.nt_box_line_mask(self._handle, width, height, mask.ctypes.data, None, C.byref(opts)))
+            return mask
+        if self.face_lines is None:
+            raise ValueError("face lines are off (set_face_lines)")
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        mask = torch.empty((height, width), dtype=torch.uint8, device=dev)
+        opts = _lib.NtRenderOpts()
+        opts.device = dev.index
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_box_line_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return mask
 
 
 _FLAT_KEYS = ("root", "node_axis", "node_split", "node_left", "node_right", "items", "batch_recs", "batch_mats",

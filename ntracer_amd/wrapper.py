@@ -78,7 +78,7 @@ class NTracer(object):
         obj.AABB = _bind_dimension(tracern.AABB, dimension)
         for n in ("CompositeScene", "KDNode", "KDLeaf", "KDBranch", "Primitive", "PrimitiveBatch", "Solid", "Triangle",
                   "TriangleBatch", "TrianglePrototype", "TriangleBatchPrototype", "SolidPrototype", "PrimitivePrototype", "PointLight",
-                  "GlobalLight", "RayIntersection",
+                  "GlobalLight", "RayIntersection", "FaceHits",
                   "dot", "cross", "build_kdtree", "build_composite_scene",
                   "screen_coord_to_ray", "BATCH_SIZE"):
             setattr(obj, n, getattr(tracern, n))
