@@ -359,6 +359,44 @@ int nt_scene_get_depth_cue(const nt_scene_t *s, int *enabled, nt_depth_cue *cue,
    projection is set. */
 int nt_depth_cue_factors(nt_scene_t *s, int width, int height, float *factors, const nt_render_opts *opts);
 int nt_depth_cue_factors_device(nt_scene_t *s, int width, int height, void *factors_dev, const nt_render_opts *opts, void *hip_stream);
+/* Clip planes (the reference has none): cutaway views.  Up to NT_CLIP_MAX planes; plane k is a normal a_k of `dimension`
+   floats, finite and not all zero (it need not be a unit vector), and a finite offset b_k.  The keep-region is the set of
+   points x with a_k . x <= b_k for every k: what lies outside it does not exist for any ray the tracer casts.  CompositeScene
+   only.  Everything below is fp32 without contraction, sums left to right.
+   The window of a ray (o, d), d exactly as the walk that casts the ray uses it:
+     t0 = 0, t1 = FLT_MAX, empty = false;
+     for k = 0 .. count - 1:  p = a_k0 * o_0, then p = p + a_kj * o_j for j = 1 .. n - 1;  s = p - b_k;
+                              r = a_k0 * d_0, then r = r + a_kj * d_j for j = 1 .. n - 1;
+         r > 0:             q = (-s) / r, and if q < t1 then t1 = q;
+         r < 0:             q = (-s) / r, and if q > t0 then t0 = q;
+         r == 0 and s > 0:  empty = true;
+     at the end empty = empty or t0 > t1.
+   A candidate hit at parameter t of any primitive test is accepted iff the rule without planes accepts it and
+   !empty && t0 <= t <= t1.  This holds for every ray: primary rays, shadow rays (beside their light-distance rule), reflection
+   rays and the continuation through transparent hits -- the geometry cut away casts no shadow and shows in no mirror.  A
+   rejected candidate leaves the walk as if the primitive had never been tested (the hit, the transparent list and which
+   subtrees count as having improved it; the walk's record of tested primitives may remember it).  A primary walk starts at
+   max(aabb entry, t0) and ends at t1; the walks of the other rays visit the cells they always visit.  Lights keep shining from
+   wherever they are.  There are no caps: a cut shell is open and its inner side is seen.
+   nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device honour the setting, and so do nt_primary_hits,
+   nt_primary_hits_device and nt_primary_hits_table_device, normal rows included: picking under a cutaway answers what is seen.
+   Refused with NT_E_UNSUPPORTED ("clip planes ...") before a device is touched, drawing nothing: a supersampling factor above 1
+   (adaptive or not), row bands (band_world > 1), collect_stats, a lens, the parallel projection, ambient occlusion, outlines,
+   depth cues, and a scene with Solids -- a Solid cut open needs a cap or an inner wall, which nothing here defines -- (and a
+   row range, which only a caller inside the library can ask for).  While the
+   setting is on nt_colors_at / nt_calculate_color, nt_ray_colors*, nt_render_rays*, nt_adaptive_mask*, nt_ambient_occlusion*,
+   nt_outline_mask* and nt_depth_cue_factors* are refused likewise.  The ray queries (nt_intersect_rays*, nt_occludes_rays*) are
+   the tree's own methods and ignore the setting.
+   Opaque scenes up to 10 dimensions on the renders' packet walk are drawn from one clipped walk into 16 bytes of record a
+   pixel and a shading pass; every other scene (transparent materials, n > 10, NTRACER_FORCE_VAR=1, NTRACER_COMPOSITE_KERNEL
+   set, trees deeper than the walk's stack) by the run-time-n kernels.  Not part of a pickled scene. */
+#define NT_CLIP_MAX 8
+/* normals: [count][dimension], offsets: [count].  count == 0 or a NULL pointer takes the setting off.  NT_E_INVALID for a
+   BoxScene, a count outside [0, NT_CLIP_MAX] and a non-finite or all-zero normal or a non-finite offset (the setting stays as
+   it was); NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it; the getter writes through
+   whichever pointers are not NULL: *count, then `count` rows of normals and `count` offsets (room for NT_CLIP_MAX suffices). */
+int nt_scene_set_clip_planes(nt_scene_t *s, int count, const float *normals, const float *offsets);
+int nt_scene_get_clip_planes(const nt_scene_t *s, int *count, float *normals, float *offsets);
 /* CompositeScene.set_shadows/set_camera_light/set_max_reflect_depth/set_ambient_color/
    set_background/add_light rolled into one call */
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p);

@@ -82,6 +82,7 @@ NT_TH_MAX = 24
 NT_OUTLINE_SILHOUETTE = 1        # the bits of an outline mask byte (nt_outline_mask)
 NT_OUTLINE_CREASE = 2
 NT_OUTLINE_DEPTH = 4
+NT_CLIP_MAX = 8
 
 
 class NtDepthCue(C.Structure):               # nt_depth_cue: 60 bytes
@@ -157,6 +158,8 @@ SYMBOLS = [
     ("nt_scene_get_depth_cue", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(NtDepthCue), C.POINTER(C.c_int), f32p]),
     ("nt_depth_cue_factors", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),
     ("nt_depth_cue_factors_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_scene_set_clip_planes", C.c_int, [C.c_void_p, C.c_int, f32p, f32p]),
+    ("nt_scene_get_clip_planes", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p]),
     ("nt_scene_set_params", C.c_int, [C.c_void_p, C.POINTER(NtSceneParams)]),
     ("nt_scene_lock", C.c_int, [C.c_void_p]),
     ("nt_scene_unlock", C.c_int, [C.c_void_p]),

@@ -6,7 +6,8 @@ csrc/nt_dispatch.hpp declares and csrc/nt_var.hip dispatches to (and does not co
 nt_inst_box.hip, nt_inst_rays.hip, nt_inst_adaptive.hip (BoxScene's kernels; CompositeScene's up to 10) and nt_inst_boxhits.hip
 (whose launcher is nt_box_faces<N>), 3..10 for
 nt_inst_composite.hip, nt_inst_query.hip, nt_inst_hits.hip, nt_inst_lens.hip, nt_inst_parallel.hip, nt_inst_ao.hip,
-nt_inst_outline.hip and nt_inst_cue.hip (whose launcher is nt_cue_packet<N>).  units() is the list, and
+nt_inst_outline.hip, nt_inst_cue.hip (whose launcher is nt_cue_packet<N>) and nt_inst_clip.hip (nt_clip_packet<N>).  units() is
+the list, and
 tests/test_dispatch.py holds the library's exports to it.  They are
 compiled in parallel into build/*.o and linked with the host side.  -ffp-contract=off is part of the arithmetic
 contract with the oracle (see csrc/nt_pixel.hpp); -fno-slp-vectorize because packing pairs of independent fp32
@@ -24,7 +25,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libntracer_hip.so")
 DIMS = range(3, 11)
 BOX_ONLY_DIMS = range(11, 25)         # BoxScene kernels alone are also compiled for N = 11..24
-HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp", "nt_cue.hpp", "nt_boxhits.hpp", "nt_dispatch.hpp")] + \
+HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp", "nt_cue.hpp", "nt_clip.hpp", "nt_boxhits.hpp", "nt_dispatch.hpp")] + \
       [os.path.join(HERE, "..", "include", "ntracer_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function"]
@@ -48,6 +49,7 @@ def units():
         u.append(("nt_outline_%d" % n, "nt_inst_outline.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_cue_%d" % n, "nt_inst_cue.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_clip_%d" % n, "nt_inst_clip.hip", ["-DNT_INST_N=%d" % n]))
     for n in BOX_ONLY_DIMS:
         u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))      # (BoxScene's kernel alone)
@@ -116,7 +118,7 @@ def build(force=False, verbose=False, out=None):
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
         # the composite units are the long ones (~40 s each): start them first
-        long_units = ("nt_inst_composite.hip", "nt_inst_rays.hip", "nt_inst_adaptive.hip", "nt_inst_lens.hip", "nt_inst_parallel.hip", "nt_inst_outline.hip", "nt_inst_cue.hip")
+        long_units = ("nt_inst_composite.hip", "nt_inst_rays.hip", "nt_inst_adaptive.hip", "nt_inst_lens.hip", "nt_inst_parallel.hip", "nt_inst_outline.hip", "nt_inst_cue.hip", "nt_inst_clip.hip")
         jobs.sort(key=lambda c: 0 if c[-3].endswith(long_units) else (1 if "nt_inst_query.hip" in c[-3] or "nt_inst_hits.hip" in c[-3] or "nt_inst_ao.hip" in c[-3] else 2))
         with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
             list(ex.map(run, jobs))

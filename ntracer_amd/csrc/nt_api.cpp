@@ -113,6 +113,8 @@ struct DeviceState {
     DevBuf refine_count;                 // adaptive supersampling: the length of that list
     DevBuf ao_dirs;                      // ambient occlusion: the table of directions
     unsigned long long ao_version = 0;
+    DevBuf clip;                         // clip planes: [count][n + 1] floats, a plane's normal and then its offset
+    unsigned long long clip_version = 0;
     DevBuf numer;                        // packet kernel: -(N.o + d) per (frame, simplex)
     DevBuf cull;                         // BoxScene: row culling bits
     bool cull_clean = false;             // `cull` is all zero (what the fused BoxScene path needs and leaves behind)
@@ -191,6 +193,9 @@ struct nt_scene {
     nt_depth_cue cue_set{};              // ... as the caller gave it, the tint's fields zero without a tint,
     std::vector<float> cue_axis;         // ... the tint axis [n], empty without a tint,
     float cue_inv_fog = 0.0f, cue_inv_tint = 0.0f;   // ... and the two reciprocals of the rule, formed once
+    int clip_count = 0;                  // clip planes that every ray of a render honours (nt_scene_set_clip_planes), 0: off
+    std::vector<float> clip_planes;      // ... [clip_count][n + 1]: a plane's normal and then its offset, as the kernels read them
+    unsigned long long clip_version = 1; // counts the changes of clip_planes
     int box_lines = 0;                   // BoxScene: != 0, the kinds of face lines on the renders (nt_scene_set_box_lines)
     float bl_color[3] = {0, 0, 0}, bl_strength = 0.0f;
 
@@ -438,6 +443,14 @@ int upload_scene(nt_scene *s, DeviceState *ds) {
         if (ds->ao_dirs.p) { (void)hipDeviceSynchronize(); ds->ao_dirs.release(); }
         ds->ao_dirs = fresh;
         ds->ao_version = s->ao_version;
+    }
+    if (s->clip_count > 0 && ds->clip_version != s->clip_version) {
+        // (a fresh allocation, as for the lights)
+        DevBuf fresh;
+        if (int r = upload(fresh, s->clip_planes)) return r;
+        if (ds->clip.p) { (void)hipDeviceSynchronize(); ds->clip.release(); }
+        ds->clip = fresh;
+        ds->clip_version = s->clip_version;
     }
     return NT_OK;
 }
@@ -1652,6 +1665,75 @@ int enqueue_cue(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderS
 }
 
 // ---------------------------------------------------------------------------------------------
+// clip planes (nt_scene_set_clip_planes; kernels in nt_clip.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+// What a render with the setting on refuses, checked by the entry points before a device is touched, in front of every other
+// setting's check (and by enqueue_clip again, for every way in): the cutaway is one sample a pixel of the whole pinhole view, no
+// kernel of it keeps counters, and a scene with another such setting on is refused here, not drawn with one of them missing.
+// A Solid cut open needs a cap or an inner wall, which nothing defines: refused, not approximated.
+int clip_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
+    if (s->clip_count <= 0) return NT_OK;
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "clip planes are not available with a supersampling factor above 1 (%d)", s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "clip planes are not available with row bands (band_world %d)", b.world);
+    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "clip planes are not available for a row range");
+    if (stats) return fail(NT_E_UNSUPPORTED, "clip planes are not available with collect_stats");
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "clip planes are not available while a lens is set");
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "clip planes are not available while the parallel projection is set");
+    if (s->ao_count > 0) return fail(NT_E_UNSUPPORTED, "clip planes are not available while ambient occlusion is on");
+    if (s->outlines) return fail(NT_E_UNSUPPORTED, "clip planes are not available while outlines are on");
+    if (s->cue) return fail(NT_E_UNSUPPORTED, "clip planes are not available while depth cues are on");
+    if (s->n_solids > 0) return fail(NT_E_UNSUPPORTED, "clip planes are not available for a scene with Solids (a Solid cut open has no cap)");
+    return NT_OK;
+}
+
+// ... and what the entry points that do not honour the setting say while it is on
+int clip_refuses(const nt_scene *s, const char *what) {
+    if (s && s->composite && s->clip_count > 0) return fail(NT_E_UNSUPPORTED, "clip planes are set: %s is not available under them", what);
+    return NT_OK;
+}
+
+// The frames of a render under the planes.  Opaque scenes that launch_composite_fixed would give the packet walk take one
+// clipped walk into hit records and clip_shade; every other scene the run-time-n kernels with the planes in the scene they
+// see, whatever its dimension -- with the `checked` columns and ray_color frames of the faithful walks.  Enqueue only.
+int enqueue_clip(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw) {
+    const int W = job.fmt->width, H = job.fmt->height;
+    if (int r = clip_check(s, job.bands, job.stats, job.row_begin, job.row_count, H)) return r;
+    if (job.fmt->bpp == 0) return NT_OK;                                // nothing to draw
+    NtTarget tg;
+    if (int r = fill_target(s, ds, job, tg)) return r;
+    NtCompositeDev c;
+    scene_dev(s, ds, sw, job.strict, false, c);
+    const CompositeRoute rt = composite_route(s, sw);
+    NtLaunchInfo li = launch_info(s, ds, sw, job.nframes, job.stream);
+    NtCamera cam;
+    cam.n = s->n;
+    cam.dots = job.cam_dots;
+    pack_camera(s->n, s->origin.data(), s->axes.data(), cam.inl);
+    camera_dots(s->n, s->origin.data(), s->axes.data(), cam.odots);
+    if (int e = device_camera(s, ds, job.cam_buf, job.stream, cam.buf)) return e;
+    NtClip cl{};
+    cl.planes = (const float *)ds->clip.p;
+    cl.count = s->clip_count;
+    cl.cams = cam.buf;
+    cl.nframes = job.nframes;
+    if (rt.packet_walk) {
+        // the packet walk's plane numerators, record scratch and quad order, as plan_composite hands them over
+        if (int e = numerator_scratch(s, ds, sw, job.nframes, li)) return e;
+        if (int e = hit_record_scratch(ds, sw, (size_t)16 * W * H, job.nframes, li)) return e;
+        if (sw.tile_order) {
+            if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
+        }
+    } else if (rt.faithful) {
+        const long long tiles = (long long)((W + 7) / 8) * ((H + 7) / 8) * job.nframes;
+        long long blocks = std::min<long long>(std::max<long long>(tiles, 1), 8192);
+        if (int e = checked_scratch(s, ds, sw, c, 64, blocks, 64, rt.frame_stack, (long long)512 << 20)) return e;
+    }
+    if (int r = nt_launch_clip(li, cam, c, tg, cl, true)) return launch_failed(r);
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // renders through a lens (nt_scene_set_lens; kernels in nt_lens.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1831,6 +1913,7 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
+    if (s->clip_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_clip(s, ds, job, sw);
     if (s->cue && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
         return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
     if (s->outlines && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
@@ -1897,6 +1980,7 @@ int prepare_stats(DeviceState *ds, hipStream_t st, bool on) {
 
 // what the scene's settings refuse of a render, in the order the render entry points say it, before they touch a device
 int render_checks(const nt_scene *s, const Format &f, const Bands &b, bool stats) {
+    if (int r = clip_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = cue_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = outline_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
     if (int r = ao_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
@@ -2154,6 +2238,8 @@ int hits_validate(const nt_scene *s, int width, int height, const nt_hit_buffers
     if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
     if (s->lens) return fail(NT_E_UNSUPPORTED, "primary-hit buffers are not available while a lens is set");
     if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "primary-hit buffers are not available while the parallel projection is set");
+    if (s->clip_count > 0 && s->n_solids > 0)
+        return fail(NT_E_UNSUPPORTED, "clip planes are not available for a scene with Solids (a Solid cut open has no cap)");
     if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 records", width, height);
     if (frame_stride < (long long)width * height) return fail(NT_E_INVALID, "frame_stride_records is smaller than one frame");
     if (frame_stride > INT_MAX || nframes * frame_stride > INT_MAX)
@@ -2175,11 +2261,13 @@ int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_h
     tg.frame_stride = frame_stride * (long long)sizeof(nt_ray_hit);
     NtLaunchInfo li = launch_info(s, ds, sw, nframes, stream);
     const CompositeRoute rt = composite_route(s, sw);
+    const bool clip = s->clip_count > 0;       // under clip planes every scene off the packet walk takes the run-time-n kernels
     if (rt.faithful) {
         // (no ray_color frames are kept: the grid of a ray query, see query_enqueue)
-        const long long lpb = rt.var ? 64 : 256, tw = rt.var ? 8 : 16;
+        const bool var = rt.var || clip;
+        const long long lpb = var ? 64 : 256, tw = var ? 8 : 16;
         const long long tiles = ((width + tw - 1) / tw) * ((height + tw - 1) / tw) * nframes;
-        long long blocks = std::min<long long>(tiles, rt.var ? 4096 : 1024);
+        long long blocks = std::min<long long>(tiles, var ? 4096 : 1024);
         if (int e = checked_scratch(s, ds, sw, c, lpb, blocks, 1, 0, (long long)256 << 20)) return e;
     }
     NtHits h{};
@@ -2195,6 +2283,23 @@ int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_h
         if (sw.tile_order) {
             if (int e = tile_order_for(ds, width, height, li.tile_order)) return e;
         }
+    }
+    if (clip) {
+        // the same walks with the planes: what is under a pixel of the cutaway (nt_launch_clip, kept apart from nt_launch_hits)
+        NtClip cl{};
+        cl.planes = (const float *)ds->clip.p;
+        cl.count = s->clip_count;
+        cl.cams = h.cams;
+        cl.nframes = nframes;
+        cl.hits = h.hits;
+        cl.frame_stride = h.frame_stride;
+        cl.normal_origin = h.normal_origin;
+        cl.normal_dir = h.normal_dir;
+        NtCamera cam{};
+        cam.n = s->n;
+        cam.buf = h.cams;
+        if (int r = nt_launch_clip(li, cam, c, tg, cl, false)) return launch_failed(r);
+        return NT_OK;
     }
     if (int r = nt_launch_hits(li, c, tg, h)) return launch_failed(r);
     return NT_OK;
@@ -2334,6 +2439,7 @@ int rays_validate(const nt_scene *s, const nt_rays *rays, const void *out, bool 
     if (!s) return fail(NT_E_INVALID, "scene is NULL");
     if (!rays || !out || !rays->origins || !rays->directions) return fail(NT_E_INVALID, "NULL argument");
     if (rays->count < 0) return fail(NT_E_INVALID, "invalid ray count");
+    if (int r = clip_refuses(s, "the colour of a caller's ray (nt_ray_colors / nt_render_rays)")) return r;
     if (!host) return NT_OK;
     const size_t n = (size_t)s->n;
     for (size_t r = 0; r < (size_t)rays->count; ++r) {
@@ -2927,6 +3033,45 @@ int nt_scene_get_depth_cue(const nt_scene_t *s, int *enabled, nt_depth_cue *cue,
     return NT_OK;
 }
 
+int nt_scene_set_clip_planes(nt_scene_t *s, int count, const float *normals, const float *offsets) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no clip planes");
+    if (count < 0 || count > NT_CLIP_MAX) return fail(NT_E_INVALID, "the number of clip planes must lie in [0, %d] (%d)", NT_CLIP_MAX, count);
+    if (!normals || !offsets) count = 0;
+    const int n = s->n;
+    std::vector<float> planes((size_t)count * (n + 1));
+    for (int k = 0; k < count; ++k) {
+        bool any = false;
+        for (int j = 0; j < n; ++j) {
+            const float v = normals[(size_t)k * n + j];
+            if (!std::isfinite(v)) return fail(NT_E_INVALID, "the normal of clip plane %d must be finite", k);
+            any = any || v != 0.0f;
+            planes[(size_t)k * (n + 1) + j] = v;
+        }
+        if (!any) return fail(NT_E_INVALID, "the normal of clip plane %d must not be all zero", k);
+        if (!std::isfinite(offsets[k])) return fail(NT_E_INVALID, "the offset of clip plane %d must be finite", k);
+        planes[(size_t)k * (n + 1) + n] = offsets[k];
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->clip_count = count;
+    s->clip_planes = std::move(planes);
+    ++s->clip_version;
+    return NT_OK;
+}
+
+int nt_scene_get_clip_planes(const nt_scene_t *s, int *count, float *normals, float *offsets) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> g(const_cast<nt_scene_t *>(s)->mu);      // (the setter swaps the vector under it)
+    if (count) *count = s->clip_count;
+    const int n = s->n;
+    for (int k = 0; k < s->clip_count; ++k) {
+        if (normals) std::memcpy(normals + (size_t)k * n, s->clip_planes.data() + (size_t)k * (n + 1), sizeof(float) * n);
+        if (offsets) offsets[k] = s->clip_planes[(size_t)k * (n + 1) + n];
+    }
+    return NT_OK;
+}
+
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");
     if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no lighting parameters");
@@ -3175,6 +3320,7 @@ namespace {
 int mask_validate(const nt_scene *s, int width, int height, const void *mask, const nt_render_opts *opts) {
     if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (int r = clip_refuses(s, "the adaptive mask")) return r;
     if (!s->adaptive) return fail(NT_E_INVALID, "the adaptive threshold is off (nt_scene_set_adaptive_supersampling)");
     if (opts && opts->band_world > 1)
         return fail(NT_E_UNSUPPORTED, "the adaptive mask is of the whole image: row bands (band_world %d) are not available", opts->band_world);
@@ -3219,6 +3365,7 @@ int ao_validate(const nt_scene *s, int width, int height, const void *blocked) {
     if (!s || !blocked) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
     if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (int r = clip_refuses(s, "the ambient occlusion count")) return r;
     if (s->ao_count <= 0) return fail(NT_E_INVALID, "ambient occlusion is off (nt_scene_set_ambient_occlusion)");
     if (s->lens || s->parallel > 0.0f)
         return fail(NT_E_UNSUPPORTED, "the ambient occlusion counts are not available while a lens or the parallel projection is set");
@@ -3259,6 +3406,7 @@ int outline_validate(const nt_scene *s, int width, int height, const void *mask)
     if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
     if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (int r = clip_refuses(s, "the outline mask")) return r;
     if (!s->outlines) return fail(NT_E_INVALID, "outlines are off (nt_scene_set_outlines)");
     if (s->lens || s->parallel > 0.0f)
         return fail(NT_E_UNSUPPORTED, "the outline mask is not available while a lens or the parallel projection is set");
@@ -3301,6 +3449,7 @@ int cue_validate(const nt_scene *s, int width, int height, const void *factors) 
     if (!s || !factors) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
     if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (int r = clip_refuses(s, "the depth cue factors")) return r;
     if (!s->cue) return fail(NT_E_INVALID, "the depth cue is off (nt_scene_set_depth_cue)");
     if (s->lens || s->parallel > 0.0f)
         return fail(NT_E_UNSUPPORTED, "the depth cue factors are not available while a lens or the parallel projection is set");
@@ -3381,6 +3530,7 @@ int nt_box_line_mask_device(nt_scene_t *s, int width, int height, void *mask_dev
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {
     if (!s || (count > 0 && (!xs || !ys || !rgb))) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1 || count < 0) return fail(NT_E_INVALID, "invalid view size or count");
+    if (int r = clip_refuses(s, "the colour of single pixels (nt_colors_at / nt_calculate_color)")) return r;
     if (count == 0) return NT_OK;
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);   // Scene.calculate_color locks the scene for the call (render.cpp:599-603)

@@ -270,14 +270,73 @@ __device__ __forceinline__ void setup_ray_table(const WaveLds &w, int lane, cons
     }
 }
 
+// Clip planes (nt_scene_set_clip_planes; the rule in full: ntracer_hip.h).  The window [t0, t1] of a ray (o, d)
+// under `count` planes at `planes` ([count][N + 1]: normal, offset; a uniform address, so scalar loads): fp32, sums left to
+// right.  An empty window comes back as t0 > t1, so that has() is false for every t.
+struct ClipWin {
+    static constexpr bool on = true;
+    float t0, t1;
+    __device__ __forceinline__ bool has(float t) const { return t >= t0 && t <= t1; }
+};
+template <int N>
+__device__ __forceinline__ ClipWin clip_window(const float *__restrict__ planes, int count, const float (&o)[N], const float (&d)[N]) {
+    float t0 = 0.0f, t1 = FLT_MAX;
+    bool empty = false;
+    for (int k = 0; k < count; ++k) {
+        const float *a = planes + (size_t)k * (N + 1);
+        float p = a[0] * o[0], r = a[0] * d[0];
+#pragma unroll
+        for (int j = 1; j < N; ++j) { p = p + a[j] * o[j]; r = r + a[j] * d[j]; }
+        const float s = p - a[N];
+        if (r > 0.0f) {
+            const float q = (-s) / r;
+            if (q < t1) t1 = q;
+        } else if (r < 0.0f) {
+            const float q = (-s) / r;
+            if (q > t0) t0 = q;
+        } else if (r == 0.0f && s > 0.0f) {
+            empty = true;
+        }
+    }
+    empty = empty || t0 > t1;
+    ClipWin w;
+    w.t0 = empty ? 1.0f : t0;
+    w.t1 = empty ? 0.0f : t1;
+    return w;
+}
+// What the per-lane walks take as their last template parameter.  ClipOff, the default, adds no argument to any call and its
+// window is an empty type: every instantiation from before the setting is spelled, and compiled, as before.  With ClipOn the
+// scene a walk is handed is an NtCompositeClip -- the planes travel behind the scene, so the walks' signatures stay as they
+// are -- and the walk forms the window of its ray once; a leaf accepts a candidate t only inside it, and a rejected candidate
+// leaves the walk's state as if the primitive had never been tested (the mailbox may remember it).  The cells walked are not
+// narrowed here: shadow and reflection rays keep the reference's walk, _occludes' far-child rule included.
+struct NtCompositeClip : NtCompositeDev {
+    const float *clip;        // [clip_count][N + 1]
+    int clip_count;
+};
+struct ClipOff {
+    // (a leaf spells its accept rule twice under `if constexpr (WIN::on)`: with one more operand in the && chain of the rule
+    // from before the setting, even a constant one, the compiler gave the old instantiations other registers)
+    struct Win { static constexpr bool on = false; __device__ __forceinline__ bool has(float) const { return true; } };
+    template <int N> static __device__ __forceinline__ Win window(const NtCompositeDev &, const float (&)[N], const float (&)[N]) { return Win(); }
+};
+struct ClipOn {
+    typedef ClipWin Win;
+    template <int N> static __device__ __forceinline__ Win window(const NtCompositeDev &sc, const float (&o)[N], const float (&d)[N]) {
+        const NtCompositeClip &c = static_cast<const NtCompositeClip &>(sc);
+        return clip_window<N>(c.clip, c.clip_count, o, d);
+    }
+};
+
 // One leaf (kd_leaf<Store,true>::intersects, tracer.hpp:977-1086) for all-opaque scenes: every
 // hit tightens the cutoff, so the two-loop structure collapses to "keep the nearest, first wins".
 // SCALP: leaves may hold unbatched triangles and solids (NtCompositeDev::has_scalar_prims).  Scenes made of batches alone --
 // every polytope of the reference's scripts -- take the instantiations without: no call to solid_intersects in the leaf
 // loops, and with it a good part of the shading kernel's registers (214 VGPRs with, two waves a SIMD).
-template <int N, bool FEAT, bool STATS, bool SCALP = FEAT>
+template <int N, bool FEAT, bool STATS, bool SCALP = FEAT, typename WIN = ClipOff::Win>
 __device__ __forceinline__ bool leaf_closest(const NtCompositeDev &sc, const WaveLds &w, int lane, int start, int count,
-                                             const float (&o)[N], const float (&d)[N], int skip_item, int skip_lane, Hit &hit, Stats &st) {
+                                             const float (&o)[N], const float (&d)[N], int skip_item, int skip_lane, Hit &hit, Stats &st,
+                                             const WIN win = WIN()) {
     bool improved = false;
     for (int i = 0; i < count; ++i) {
         const int item = sc.items[start + i];
@@ -294,7 +353,11 @@ __device__ __forceinline__ bool leaf_closest(const NtCompositeDev &sc, const Wav
                 SimplexRec<N> s;
                 s.load(base + (size_t)l * sc.rec_stride);
                 const float t = simplex_batch_form<N>(s, o, d);
-                if (l != sl && t != 0.0f && t < min_t) { min_t = t; r = l; }
+                if constexpr (WIN::on) {
+                    if (l != sl && t != 0.0f && t < min_t && win.has(t)) { min_t = t; r = l; }
+                } else {
+                    if (l != sl && t != 0.0f && t < min_t) { min_t = t; r = l; }
+                }
             }
             if (STATS) st.simplex_tests += NT_DEV_BATCH;
             if (r >= 0) { hit.dist = min_t; hit.item = item; hit.lane = r; improved = true; }
@@ -310,7 +373,11 @@ __device__ __forceinline__ bool leaf_closest(const NtCompositeDev &sc, const Wav
                 t = solid_intersects<N>(sc, idx, o, d, hit.dist, false, no, nd);
                 if (STATS) st.solid_tests += 1;
             }
-            if (t != 0.0f) { hit.dist = t; hit.item = item; hit.lane = -1; improved = true; }
+            if constexpr (WIN::on) {
+                if (t != 0.0f && win.has(t)) { hit.dist = t; hit.item = item; hit.lane = -1; improved = true; }
+            } else {
+                if (t != 0.0f) { hit.dist = t; hit.item = item; hit.lane = -1; improved = true; }
+            }
         }
     }
     return improved;
@@ -353,9 +420,10 @@ struct RootWindow {
     __device__ __forceinline__ float t_far() const { return tf; }
 };
 
-template <int N, bool FEAT, bool STATS, bool SCALP = FEAT>
+template <int N, bool FEAT, bool STATS, bool SCALP = FEAT, typename CLIP = ClipOff>
 __device__ __noinline__ bool trace_closest(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
                                               float t_near, float t_far_root, int skip_item, int skip_lane, Hit &hit, Stats &st) {
+    const typename CLIP::Win win = CLIP::template window<N>(sc, o, d);
     hit.dist = FLT_MAX;
     hit.item = -1;
     hit.lane = -1;
@@ -371,7 +439,7 @@ __device__ __noinline__ bool trace_closest(const NtCompositeDev &sc, const WaveL
             const NtNode nd = sc.nodes[node];
             if (nd.axis < 0) {
                 if (STATS) st.leaves += 1;
-                if (leaf_closest<N, FEAT, STATS, SCALP>(sc, w, lane, nd.left, nd.right, o, d, skip_item, skip_lane, hit, st)) dirty = sp;
+                if (leaf_closest<N, FEAT, STATS, SCALP, typename CLIP::Win>(sc, w, lane, nd.left, nd.right, o, d, skip_item, skip_lane, hit, st, win)) dirty = sp;
                 node = -1;
                 break;
             }
@@ -429,9 +497,9 @@ __device__ __noinline__ bool trace_closest(const NtCompositeDev &sc, const WaveL
 }
 
 // kd_leaf::occludes (tracer.hpp:1088-1124), all-opaque scenes
-template <int N, bool STATS, bool SCALP = true>
+template <int N, bool STATS, bool SCALP = true, typename WIN = ClipOff::Win>
 __device__ __forceinline__ bool leaf_occludes(const NtCompositeDev &sc, int start, int count, const float (&o)[N], const float (&d)[N],
-                                              float ldistance, int skip_item, int skip_lane, Stats &st) {
+                                              float ldistance, int skip_item, int skip_lane, Stats &st, const WIN win = WIN()) {
     // (the id of item i + 1 is fetched before item i's records: one memory round trip less on the chain id -> records -> test)
     int next_item = count > 0 ? sc.items[start] : 0;
     for (int i = 0; i < count; ++i) {
@@ -448,7 +516,8 @@ __device__ __forceinline__ bool leaf_occludes(const NtCompositeDev &sc, int star
                 SimplexRec<N> s;
                 s.load(base + (size_t)l * sc.rec_stride);
                 const float t = simplex_batch_form<N>(s, o, d);
-                any = any || (l != sl && t != 0.0f && t < ldistance);
+                if constexpr (WIN::on) any = any || (l != sl && t != 0.0f && t < ldistance && win.has(t));
+                else any = any || (l != sl && t != 0.0f && t < ldistance);
             }
             if (STATS) st.simplex_tests += NT_DEV_BATCH;
             if (any) return true;
@@ -464,7 +533,11 @@ __device__ __forceinline__ bool leaf_occludes(const NtCompositeDev &sc, int star
                 t = solid_intersects<N>(sc, idx, o, d, ldistance, false, no, nd);
                 if (STATS) st.solid_tests += 1;
             }
-            if (t != 0.0f) return true;
+            if constexpr (WIN::on) {
+                if (t != 0.0f && win.has(t)) return true;
+            } else {
+                if (t != 0.0f) return true;
+            }
         }
     }
     return false;
@@ -479,11 +552,12 @@ __device__ __forceinline__ bool leaf_occludes(const NtCompositeDev &sc, int star
 // (the ray travels BY VALUE: up to four dimensions that is registers -- the calling convention passes an aggregate of at most 16
 // dwords directly -- where two references to the caller's arrays were two round trips through scratch memory per component)
 template <int N> struct RayArg { float o[N], d[N]; };
-template <int N, bool STATS, bool SCALP = true, typename ROOT = RootWhole>
+template <int N, bool STATS, bool SCALP = true, typename ROOT = RootWhole, typename CLIP = ClipOff>
 __device__ NT_OCCL_ATTR bool trace_occluded(const NtCompositeDev &sc, const WaveLds &w, int lane, const RayArg<N> ray,
                                             float ldistance, int skip_item, int skip_lane, Stats &st, const ROOT root = ROOT()) {
     const float (&o)[N] = ray.o;
     const float (&d)[N] = ray.d;
+    const typename CLIP::Win win = CLIP::template window<N>(sc, o, d);
     setup_ray_table<N>(w, lane, o, d);
     int node = sc.root;
     int sp = 0;
@@ -496,7 +570,7 @@ __device__ NT_OCCL_ATTR bool trace_occluded(const NtCompositeDev &sc, const Wave
             const NtNode nd = sc.nodes[node];
             if (nd.axis < 0) {
                 if (STATS) st.leaves += 1;
-                if (leaf_occludes<N, STATS, SCALP>(sc, nd.left, nd.right, o, d, ldistance, skip_item, skip_lane, st)) return true;
+                if (leaf_occludes<N, STATS, SCALP, typename CLIP::Win>(sc, nd.left, nd.right, o, d, ldistance, skip_item, skip_lane, st, win)) return true;
                 node = -1;
                 break;
             }
@@ -701,7 +775,7 @@ __device__ __forceinline__ Color3 surface_color_lean(const NtCompositeDev &sc, c
 
 // `primary`: when not null, the closest hit of the depth-0 ray has already been found (by the packet walk) and
 // is taken from there instead of being traced here.
-template <int N, bool FEAT, bool STATS, bool SCALP = FEAT>
+template <int N, bool FEAT, bool STATS, bool SCALP = FEAT, typename CLIP = ClipOff>
 __device__ __forceinline__ Color3 composite_color(const NtCompositeDev &sc, const WaveLds &w, int lane, float (&o)[N], float (&d)[N], Stats &st,
                                                   const Hit *primary = nullptr) {
     Level levels[FEAT ? NT_DEV_MAX_REFLECT : 1];
@@ -725,7 +799,7 @@ __device__ __forceinline__ Color3 composite_color(const NtCompositeDev &sc, cons
             if (dist >= 0.0f) {
                 if (STATS && depth == 0) st.aabb_enter += 1;
                 setup_ray_table<N>(w, lane, o, d);
-                found = trace_closest<N, FEAT, STATS, SCALP>(sc, w, lane, o, d, dist, FLT_MAX, skip_item, skip_lane, hit, st);
+                found = trace_closest<N, FEAT, STATS, SCALP, CLIP>(sc, w, lane, o, d, dist, FLT_MAX, skip_item, skip_lane, hit, st);
             }
         }
         if (!found) {
@@ -759,7 +833,7 @@ __device__ __forceinline__ Color3 composite_color(const NtCompositeDev &sc, cons
                             RayArg<N> sray;
 #pragma unroll
                             for (int k = 0; k < N; ++k) { sray.o[k] = no[k]; sray.d[k] = lv[k]; }
-                            if (!trace_occluded<N, STATS, SCALP>(sc, w, lane, sray, ldist, hit.item, hit.lane, st)) {
+                            if (!trace_occluded<N, STATS, SCALP, RootWhole, CLIP>(sc, w, lane, sray, ldist, hit.item, hit.lane, st)) {
                                 const Color3 filtered = cscale(plc, strength);
                                 light = cadd(light, cscale(filtered, sine));
                                 if (m[8] != 0.0f) append_specular<N>(specular, spec_a, m, filtered, d, nd, lv);
@@ -782,7 +856,7 @@ __device__ __forceinline__ Color3 composite_color(const NtCompositeDev &sc, cons
                         RayArg<N> sray;
 #pragma unroll
                         for (int k = 0; k < N; ++k) { sray.o[k] = no[k]; sray.d[k] = neg[k]; }
-                        if (!trace_occluded<N, STATS, SCALP>(sc, w, lane, sray, FLT_MAX, hit.item, hit.lane, st)) {
+                        if (!trace_occluded<N, STATS, SCALP, RootWhole, CLIP>(sc, w, lane, sray, FLT_MAX, hit.item, hit.lane, st)) {
                             light = cadd(light, cscale(glc, sine));
                             if (m[8] != 0.0f) append_specular<N>(specular, spec_a, m, glc, d, nd, neg);
                         }
@@ -1820,6 +1894,8 @@ struct PacketArgs {
     const float *numer;       // not null: [frame][batch][4] plane numerators -(N.o + d) (packet_numerators)
     int n_batches;
     const float *lens;        // LENS instantiations only: [height][width][3] coefficients (nt_lens.hpp); nobody else reads or sets it
+    const float *clip;        // CLIP instantiations only: [clip_count][N + 1] planes (nt_clip.hpp); likewise
+    int clip_count;
 };
 
 // The per-lane part of the frame stack is ONE register: bit k of `bothbits` says that the lane entered both
@@ -1898,7 +1974,10 @@ __device__ __forceinline__ bool wm_claim(int *wm, int lane, int item, bool activ
 // that the render instantiations are spelled, and compiled, as before.
 // LENS (nt_lens.hpp launches these instantiations): the lane's direction from its entry of pa.lens (lens_dir) instead of from
 // tg.fovI; the lane of a masked entry is simply never active.  The walk needs the shared origin, not the flat image plane.
-template <int N, int DEPTH, bool FEAT, bool SCAL, bool HITS = false, bool LENS = false>
+// CLIP (nt_clip.hpp launches these instantiations): the lane's clip_window folded into active, t_near and t_far -- the walk
+// starts at max(aabb entry, t0) and ends at t1 -- and a candidate t is accepted only inside [t0, t1]: two more compares in the
+// stage-2 ballot and at both accept sites.  The origin is still shared; the numerators stay usable.
+template <int N, int DEPTH, bool FEAT, bool SCAL, bool HITS = false, bool LENS = false, bool CLIP = false>
 __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVES4 : (N <= 7 ? 5 : 4))) NT_PACKET_ATTR void composite_packet(NtCompositeDev sc, NtTarget tg, PacketArgs pa) {
     extern __shared__ float2 lds_raw[];
     if (nt_aborted(tg)) return;                           // (four independent waves: no barrier in this kernel)
@@ -1961,6 +2040,14 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
     bool active = valid && dist0 >= 0.0f;
     if (LENS) active = active && lens_live;
     float t_near = dist0, t_far = FLT_MAX;
+    ClipWin cw;
+    cw.t0 = 0.0f; cw.t1 = FLT_MAX;
+    if constexpr (CLIP) {
+        cw = clip_window<N>(pa.clip, pa.clip_count, o, d);
+        active = active && cw.t0 <= cw.t1;
+        t_near = cw.t0 > dist0 ? cw.t0 : dist0;
+        t_far = cw.t1;
+    }
     int dirty = 0;
     unsigned int bothbits = 0u;   // bit k: this lane entered BOTH sides of the branch pushed at stack level k
     wm_reset(wm, lane);
@@ -2005,7 +2092,12 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
                                 float no_[N], nd_[N];
                                 t = solid_intersects<N>(sc, cur >> 2, o, d, hit.dist, false, no_, nd_);
                             }
-                            if (t != 0.0f) { hit.dist = t; hit.item = cur; hit.lane = -1; improved = true; }
+                            // (the rule is spelled twice under `if constexpr`, here and below: see ClipOff::Win)
+                            if constexpr (CLIP) {
+                                if (t != 0.0f && cw.has(t)) { hit.dist = t; hit.item = cur; hit.lane = -1; improved = true; }
+                            } else {
+                                if (t != 0.0f) { hit.dist = t; hit.item = cur; hit.lane = -1; improved = true; }
+                            }
                         }
                         continue;
                     }
@@ -2040,7 +2132,11 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
                     for (int l = 0; l < NT_DEV_BATCH; ++l) {
                         // stage 2 only if some lane can still accept this simplex (same accept rule as below)
                         const float t = tl[l];
-                        if (__builtin_amdgcn_ballot_w64(cur_doit && ok1[l] && t != 0.0f && t < min_t) == 0ull) continue;
+                        if constexpr (CLIP) {
+                            if (__builtin_amdgcn_ballot_w64(cur_doit && ok1[l] && t != 0.0f && t < min_t && cw.has(t)) == 0ull) continue;
+                        } else {
+                            if (__builtin_amdgcn_ballot_w64(cur_doit && ok1[l] && t != 0.0f && t < min_t) == 0ull) continue;
+                        }
                         const float *rec = base + (size_t)l * sc.rec_stride;
                         float pside[N];
 #pragma unroll
@@ -2057,7 +2153,11 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
                             tot += area;
                         }
                         ok = ok && tot <= (1.0f + NT_FUZZ);
-                        if (ok && t != 0.0f && t < min_t) { min_t = t; r = l; }
+                        if constexpr (CLIP) {
+                            if (ok && t != 0.0f && t < min_t && cw.has(t)) { min_t = t; r = l; }
+                        } else {
+                            if (ok && t != 0.0f && t < min_t) { min_t = t; r = l; }
+                        }
                     }
                     if (cur_doit && r >= 0) { hit.dist = min_t; hit.item = cur; hit.lane = r; improved = true; }
                 }
@@ -2148,6 +2248,7 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
             // lane entered on both sides (its near subtree is where we are); none: the root's t_far
             const unsigned int below = bothbits & ((1u << sp) - 1u);
             float ef = FLT_MAX;
+            if constexpr (CLIP) ef = cw.t1;
             if (below != 0u) {
                 const int ks = 31 - __clz((int)below);
                 const float s2 = __int_as_float(ustack[ks * 8 + 3]);

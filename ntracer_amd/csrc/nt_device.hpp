@@ -332,6 +332,23 @@ struct NtCue {
     float *factors;           // [pixel][2] (the factor launches)
 };
 
+// Clip planes (nt_clip.hpp, nt_var.hip; the rule in full: ntracer_hip.h): the keep-region a . x <= b of up to
+// NT_DEV_CLIP_MAX planes, which every ray of the launch honours.  Device memory, read at uniform addresses.
+#define NT_DEV_CLIP_MAX 8
+struct NtClipPlanes {        // what the run-time-n walk kernels take as their last argument: {nullptr, 0} without the setting
+    const float *planes;      // [count][n + 1]: a plane's normal, then its offset
+    int count;                // 0: no clip
+};
+struct NtClip {
+    const float *planes;      // [count][n + 1]: a plane's normal, then its offset
+    int count;                // 0: no clip
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    int nframes;
+    void *hits;               // renders on the packet route: li.hit_buf; primary-hit passes: the caller's records (NtHits::hits)
+    long long frame_stride;   // primary-hit passes: records between frames (NtHits::frame_stride)
+    float *normal_origin, *normal_dir;    // primary-hit passes: as NtHits has them
+};
+
 // BoxScene hit buffers and face lines (nt_boxhits.hpp, nt_var.hip; the rules in full: ntracer_hip.h): the face
 // record of every pixel of li.nframes views of tg.width x tg.height, or what follows from the records of a pixel and its four
 // neighbours -- the mask bytes, or the frame with the lines drawn.  Every pointer is device memory; a pixel's record index is
@@ -375,6 +392,12 @@ int nt_launch_cue_factors(const NtLaunchInfo &li, const NtTarget &tg, const NtCu
 // ... or the base frame (NtAdaptive::base's layout) blended by them into tg.dest, the whole image of cu.nframes frames (no bands)
 int nt_launch_cue_apply(const NtLaunchInfo &li, const uint32_t *base, const NtCue &cu, const NtTarget &tg);
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg);
+// Renders and primary-hit passes under clip planes, kept apart from every launcher above.  draw: tg is the whole image of every
+// frame (no bands); otherwise tg is the view and the abort word and the records go to cl.hits (normal rows: cl.normal_*).
+// Opaque scenes the packet walk takes (n <= 10, stack depth <= 32, kernel_choice 0, no force_var): composite_packet<..., CLIP>
+// into records -- a render's in li.hit_buf, li.hit_frames frames of them -- and clip_shade, or hits_normals.  Every other
+// scene: the run-time-n kernels with cl in their arguments, sc.checked / sc.tframes as for nt_launch_composite / nt_launch_hits
+int nt_launch_clip(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg, const NtClip &cl, bool draw);
 // resolve_kernel<s> (nt_resolve.hpp): the s x s samples of every pixel of owned rows [tg.row_begin, tg.row_begin + tg.row_count)
 // of `nframes` frames -- 12-byte fp32 x 3 pixels as the render kernels write them, s * tg.row_count rows of `pitch_bytes` a frame
 // -- averaged and packed into tg.dest

@@ -18,6 +18,7 @@ struct NtAo;
 struct NtOutline;
 struct NtCue;
 struct NtBoxFaces;
+struct NtClip;
 
 // The compile-time-N launchers, one family a primary template.  Nothing defines the primary: every dimension is the explicit
 // specialisation `template <> int nt_X_fixed<NT_INST_N>(...)` of its own translation unit (nt_inst_*.hip, compiled once per
@@ -36,6 +37,8 @@ template <int N> int nt_ao_fixed(const NtLaunchInfo &li, const NtCompositeDev &s
 template <int N> int nt_outline_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtOutline &ol, bool draw);
 // (depth cues, nt_inst_cue.hip: N = 3..NT_DEV_MAX_FIXED like the others; the family is named for the walk it launches)
 template <int N> int nt_cue_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtCue &cu, bool draw);
+// (clip planes, nt_inst_clip.hip: N = 3..NT_DEV_MAX_FIXED; named for the walk it launches, as the depth cues' family is)
+template <int N> int nt_clip_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtClip &cl, bool draw);
 // (BoxScene hit buffers, nt_inst_boxhits.hip: N = 3..NT_DEV_MAX_FIXED_BOX like the other BoxScene families)
 template <int N> int nt_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxFaces &bf);
 

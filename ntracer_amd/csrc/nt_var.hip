@@ -399,6 +399,14 @@ struct VarCtx {
     WaveLds w;
     int n, lane;
 };
+// What the CLIP instantiations of the walks below are handed as their VarCtx (the four kernels nt_launch_clip launches make one):
+// the planes and this lane's window travel behind the context, so no walk's signature changes and the instantiations without
+// CLIP -- every call from before the setting -- are the parent commit's code
+struct VarCtxClip : VarCtx {
+    const float *clip;       // clip planes [clip_count][n + 1] (NtClipPlanes)
+    int clip_count;
+    float *cwin;             // this lane's {t0, t1} of the current ray (clip_window_var) and the candidates rejected of the item at hand
+};
 
 #define VO(k) (cx.L.ray[(k) * 64 + cx.lane].x)       // origin[k] of the current ray
 #define VD(k) (cx.L.dv[(k) * 64 + cx.lane])          // direction[k]
@@ -410,6 +418,64 @@ __device__ __forceinline__ void var_set_ray(const VarCtx &cx, const float *o, co
         cx.L.dv[k * 64 + cx.lane] = dk;
         cx.L.ray[k * 64 + cx.lane] = make_float2(o[k], dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
     }
+}
+
+// Clip planes at run-time n (cx.clip, cx.clip_count; the rule in full: ntracer_hip.h, and clip_window in nt_composite.hpp): the
+// window [t0, t1] of the current ray into cx.cwin, an empty one as t0 > t1.  Every walk forms it when it starts, so whatever
+// made its ray the current one need not know of the setting.
+__device__ __forceinline__ void clip_window_var(const VarCtx &cx_) {
+    const VarCtxClip &cx = static_cast<const VarCtxClip &>(cx_);
+    const int n = cx.n;
+    float t0 = 0.0f, t1 = FLT_MAX;
+    bool empty = false;
+    for (int k = 0; k < cx.clip_count; ++k) {
+        const float *a = cx.clip + (size_t)k * (n + 1);
+        float p = 0.0f, r = 0.0f;
+        for (int j = 0; j < n; ++j) {
+            const float po = a[j] * VO(j), pd = a[j] * VD(j);
+            p = j == 0 ? po : p + po;
+            r = j == 0 ? pd : r + pd;
+        }
+        const float s = p - a[n];
+        if (r > 0.0f) {
+            const float q = (-s) / r;
+            if (q < t1) t1 = q;
+        } else if (r < 0.0f) {
+            const float q = (-s) / r;
+            if (q > t0) t0 = q;
+        } else if (r == 0.0f && s > 0.0f) {
+            empty = true;
+        }
+    }
+    empty = empty || t0 > t1;
+    cx.cwin[0] = empty ? 1.0f : t0;
+    cx.cwin[1] = empty ? 0.0f : t1;
+    cx.cwin[2] = 0.0f;
+}
+
+// a candidate t of the current ray under the planes: t itself, or 0 -- "no hit", as if the primitive had not been tested --
+// outside the ray's window (cwin[2] counts the rejections; leaf_closest_var_t, its one reader, clears it before every item)
+template <bool CLIP>
+__device__ __forceinline__ float clip_keep_var(const VarCtx &cx_, float t) {
+    if constexpr (CLIP) {
+        const VarCtxClip &cx = static_cast<const VarCtxClip &>(cx_);
+        if (t != 0.0f && !(t >= cx.cwin[0] && t <= cx.cwin[1])) {
+            cx.cwin[2] += 1.0f;
+            return 0.0f;
+        }
+    }
+    return t;
+}
+
+// The root interval of a primary walk under the planes: from max(aabb entry, t0) to t1.  false: the window is empty.
+__device__ __forceinline__ bool clip_primary_var(const VarCtx &cx_, float &t_near, RootWindow &root) {
+    const VarCtxClip &cx = static_cast<const VarCtxClip &>(cx_);
+    clip_window_var(cx);
+    if (!(cx.cwin[0] <= cx.cwin[1])) return false;
+    if (cx.cwin[0] > t_near) t_near = cx.cwin[0];
+    root.tn = 0.0f;
+    root.tf = cx.cwin[1];
+    return true;
 }
 
 // triangle_batch::intersects lane / triangle::intersects with run-time n (tracer.hpp:411-440, 561-581)
@@ -544,6 +610,7 @@ __device__ __forceinline__ float aabb_distance_var(const VarCtx &cx) {
 }
 
 // kd_leaf<Store,true>::intersects for all-opaque scenes (see leaf_closest in nt_composite.hpp)
+template <bool CLIP = false>
 __device__ __forceinline__ bool leaf_closest_var(const VarCtx &cx, int start, int count, int skip_item, int skip_lane, Hit &hit) {
     const NtCompositeDev &sc = cx.sc;
     bool improved = false;
@@ -556,7 +623,7 @@ __device__ __forceinline__ bool leaf_closest_var(const VarCtx &cx, int start, in
             float min_t = hit.dist;
             int r = -1;
             for (int l = 0; l < NT_DEV_BATCH; ++l) {
-                const float t = simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, cx.n, cx.L, cx.lane, false, 0.0f);
+                const float t = clip_keep_var<CLIP>(cx, simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, cx.n, cx.L, cx.lane, false, 0.0f));
                 if (l != sl && t != 0.0f && t < min_t) { min_t = t; r = l; }
             }
             if (r >= 0) { hit.dist = min_t; hit.item = item; hit.lane = r; improved = true; }
@@ -564,6 +631,7 @@ __device__ __forceinline__ bool leaf_closest_var(const VarCtx &cx, int start, in
             float t;
             if (kind == 1) t = simplex_var(sc.tri_recs + (size_t)idx * sc.rec_stride, cx.n, cx.L, cx.lane, true, hit.dist);
             else t = solid_var(cx, idx, hit.dist, false, nullptr, nullptr);
+            t = clip_keep_var<CLIP>(cx, t);
             if (t != 0.0f) { hit.dist = t; hit.item = item; hit.lane = -1; improved = true; }
         }
     }
@@ -571,7 +639,7 @@ __device__ __forceinline__ bool leaf_closest_var(const VarCtx &cx, int start, in
 }
 
 // kd_node_intersection::operator() (tracer.hpp:1179-1243): the continuation stack of trace_closest (nt_composite.hpp)
-template <typename ROOT = RootWhole>
+template <typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
@@ -580,6 +648,7 @@ __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, i
     hit.item = -1;
     hit.lane = -1;
     mbox_reset(w, lane);
+    if constexpr (CLIP) clip_window_var(cx);
     int node = sc.root, sp = 0, dirty = 0;
     float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
@@ -588,7 +657,7 @@ __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, i
             if (sc.prune && nt_beyond_hit(hit.dist, t_near)) { node = -1; break; }
             const NtNode nd = sc.nodes[node];
             if (nd.axis < 0) {
-                if (leaf_closest_var(cx, nd.left, nd.right, skip_item, skip_lane, hit)) dirty = sp;
+                if (leaf_closest_var<CLIP>(cx, nd.left, nd.right, skip_item, skip_lane, hit)) dirty = sp;
                 node = -1;
                 break;
             }
@@ -641,6 +710,7 @@ __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, i
 }
 
 // kd_leaf::occludes (tracer.hpp:1088-1124), all-opaque scenes
+template <bool CLIP = false>
 __device__ __forceinline__ bool leaf_occludes_var(const VarCtx &cx, int start, int count, float ldistance, int skip_item, int skip_lane) {
     const NtCompositeDev &sc = cx.sc;
     for (int i = 0; i < count; ++i) {
@@ -650,7 +720,7 @@ __device__ __forceinline__ bool leaf_occludes_var(const VarCtx &cx, int start, i
             const int sl = item == skip_item ? skip_lane : -1;
             bool any = false;
             for (int l = 0; l < NT_DEV_BATCH; ++l) {
-                const float t = simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, cx.n, cx.L, cx.lane, false, 0.0f);
+                const float t = clip_keep_var<CLIP>(cx, simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, cx.n, cx.L, cx.lane, false, 0.0f));
                 any = any || (l != sl && t != 0.0f && t < ldistance);
             }
             if (any) return true;
@@ -658,18 +728,19 @@ __device__ __forceinline__ bool leaf_occludes_var(const VarCtx &cx, int start, i
             float t;
             if (kind == 1) t = simplex_var(sc.tri_recs + (size_t)idx * sc.rec_stride, cx.n, cx.L, cx.lane, true, ldistance);
             else t = solid_var(cx, idx, ldistance, false, nullptr, nullptr);
-            if (t != 0.0f) return true;
+            if (clip_keep_var<CLIP>(cx, t) != 0.0f) return true;
         }
     }
     return false;
 }
 
 // _occludes (tracer.hpp:1258-1307) for the current ray, `if(t < ldistance) return false;` (:1298) included
-template <typename ROOT = RootWhole>
+template <typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
     const int lane = cx.lane;
+    if constexpr (CLIP) clip_window_var(cx);
     int node = sc.root, sp = 0;
     float t_near = root.t_near(), t_far = root.t_far();
     const int max_sp = sc.stack_depth;
@@ -677,7 +748,7 @@ __device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistanc
         while (node >= 0) {
             const NtNode nd = sc.nodes[node];
             if (nd.axis < 0) {
-                if (leaf_occludes_var(cx, nd.left, nd.right, ldistance, skip_item, skip_lane)) return true;
+                if (leaf_occludes_var<CLIP>(cx, nd.left, nd.right, ldistance, skip_item, skip_lane)) return true;
                 node = -1;
                 break;
             }
@@ -751,6 +822,7 @@ __device__ __forceinline__ void append_specular_var(int n, Color3 &c, float &a, 
 
 // ray_color + base_color (tracer.hpp:1768-1883), the reflection recursion as a level stack (see composite_color).
 // On entry the primary ray is the current ray.
+template <bool CLIP = false>
 __device__ __noinline__ Color3 composite_color_var(const VarCtx &cx) {
     const NtCompositeDev &sc = cx.sc;
     const int n = cx.n;
@@ -766,7 +838,20 @@ __device__ __noinline__ Color3 composite_color_var(const VarCtx &cx) {
         hit.dist = FLT_MAX; hit.item = -1; hit.lane = -1;
         bool found = false;
         const float dist0 = aabb_distance_var(cx);
-        if (dist0 >= 0.0f) found = trace_closest_var(cx, dist0, skip_item, skip_lane, hit);
+        if (dist0 >= 0.0f) {
+            if constexpr (CLIP) {
+                if (depth == 0) {
+                    // the primary ray under clip planes: the walk starts at max(aabb entry, t0) and ends at t1
+                    float tn = dist0;
+                    RootWindow root;
+                    if (clip_primary_var(cx, tn, root)) found = trace_closest_var<RootWindow, true>(cx, tn, skip_item, skip_lane, hit, root);
+                } else {
+                    found = trace_closest_var<RootWhole, true>(cx, dist0, skip_item, skip_lane, hit);
+                }
+            } else {
+                found = trace_closest_var(cx, dist0, skip_item, skip_lane, hit);
+            }
+        }
         if (!found) {
             const float iv = VD(sc.bg_axis);
             result = iv >= 0.0f ? cadd(cscale(c3p(sc.bg1), iv), cscale(c3p(sc.bg2), 1.0f - iv))
@@ -811,7 +896,7 @@ __device__ __noinline__ Color3 composite_color_var(const VarCtx &cx) {
                 if (sc.shadows) {
                     if (fmaxf(plc.r, fmaxf(plc.g, plc.b)) * strength * sine > NT_LIGHT_THRESHOLD) {
                         var_set_ray(cx, no, lv);
-                        if (!trace_occluded_var(cx, ldist, hit.item, hit.lane)) {
+                        if (!trace_occluded_var<RootWhole, CLIP>(cx, ldist, hit.item, hit.lane)) {
                             const Color3 filtered = cscale(plc, strength);
                             light = cadd(light, cscale(filtered, sine));
                             if (m[8] != 0.0f) append_specular_var(n, specular, spec_a, m, filtered, dir, nd, lv);
@@ -830,7 +915,7 @@ __device__ __noinline__ Color3 composite_color_var(const VarCtx &cx) {
                 if (sc.shadows) {
                     for (int k = 0; k < n; ++k) lv[k] = -gd[k];
                     var_set_ray(cx, no, lv);
-                    if (!trace_occluded_var(cx, FLT_MAX, hit.item, hit.lane)) {
+                    if (!trace_occluded_var<RootWhole, CLIP>(cx, FLT_MAX, hit.item, hit.lane)) {
                         light = cadd(light, cscale(glc, sine));
                         if (m[8] != 0.0f) append_specular_var(n, specular, spec_a, m, glc, dir, nd, lv);
                     }
@@ -920,6 +1005,7 @@ __device__ __forceinline__ Color3 fr_get3(const VarFrames &fr, int f, int w) { r
 __device__ __forceinline__ void fr_put3(const VarFrames &fr, int f, int w, Color3 c) { FRW(f, w) = c.r; FRW(f, w + 1) = c.g; FRW(f, w + 2) = c.b; }
 
 // test_item (nt_composite.hpp) on the current ray
+template <bool CLIP = false>
 __device__ __forceinline__ float test_item_var(const VarCtx &cx, int item, float cutoff, int skip_item, int skip_lane, int &lane_out) {
     const NtCompositeDev &sc = cx.sc;
     const int kind = item & 3, idx = item >> 2;
@@ -929,14 +1015,14 @@ __device__ __forceinline__ float test_item_var(const VarCtx &cx, int item, float
         float min_t = cutoff;
         int r = -1;
         for (int l = 0; l < NT_DEV_BATCH; ++l) {
-            const float t = simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, cx.n, cx.L, cx.lane, false, 0.0f);
+            const float t = clip_keep_var<CLIP>(cx, simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, cx.n, cx.L, cx.lane, false, 0.0f));
             if (l != sl && t != 0.0f && t < min_t) { min_t = t; r = l; }
         }
         lane_out = r;
         return r >= 0 ? min_t : 0.0f;
     }
-    if (kind == 1) return simplex_var(sc.tri_recs + (size_t)idx * sc.rec_stride, cx.n, cx.L, cx.lane, true, cutoff);
-    return solid_var(cx, idx, cutoff, false, nullptr, nullptr);
+    if (kind == 1) return clip_keep_var<CLIP>(cx, simplex_var(sc.tri_recs + (size_t)idx * sc.rec_stride, cx.n, cx.L, cx.lane, true, cutoff));
+    return clip_keep_var<CLIP>(cx, solid_var(cx, idx, cutoff, false, nullptr, nullptr));
 }
 
 // the normal ray of a hit on the current ray (hit_normal in nt_composite.hpp)
@@ -1041,13 +1127,14 @@ __device__ __noinline__ float solid_marks_var(const VarCtx &cx, int idx, float c
     return dist;
 }
 
+template <bool CLIP = false>
 __device__ __forceinline__ float test_item_marks_var(const VarCtx &cx, int item, float cutoff, int skip_item, int skip_lane, int &lane_out,
                                                      float *no, float *nd) {
     if ((item & 3) == 2) {
         lane_out = -1;
         return solid_marks_var(cx, item >> 2, cutoff, no, nd);
     }
-    const float t = test_item_var(cx, item, cutoff, skip_item, skip_lane, lane_out);
+    const float t = test_item_var<CLIP>(cx, item, cutoff, skip_item, skip_lane, lane_out);
     if (t != 0.0f) {
         Hit h;
         h.dist = t;
@@ -1059,7 +1146,7 @@ __device__ __forceinline__ float test_item_marks_var(const VarCtx &cx, int item,
 }
 
 // leaf_closest_t (nt_composite.hpp): kd_leaf<Store,true>::intersects with transparent hits (tracer.hpp:977-1086)
-template <bool ALIAS>
+template <bool ALIAS, bool CLIP = false>
 __device__ __noinline__ bool leaf_closest_var_t(const VarCtx &cx, int start, int count, int skip_item, int skip_lane, Hit &hit, TList &th,
                                                 const Checked &ck, float *hn_o, float *hn_d, float *nn_o, float *nn_d) {
     const NtCompositeDev &sc = cx.sc;
@@ -1072,17 +1159,25 @@ __device__ __noinline__ bool leaf_closest_var_t(const VarCtx &cx, int start, int
         if (checked_seen(ck, item)) continue;
         int l;
         float t;
+        if constexpr (CLIP) static_cast<const VarCtxClip &>(cx).cwin[2] = 0.0f;       // the rejections of THIS item are counted below
         if (ALIAS) {
             if (!found) {
-                t = test_item_marks_var(cx, item, hit.dist, skip_item, skip_lane, l, hn_o, hn_d);
+                t = test_item_marks_var<CLIP>(cx, item, hit.dist, skip_item, skip_lane, l, hn_o, hn_d);
             } else {
-                t = test_item_marks_var(cx, item, hit.dist, skip_item, skip_lane, l, nn_o, nn_d);
+                t = test_item_marks_var<CLIP>(cx, item, hit.dist, skip_item, skip_lane, l, nn_o, nn_d);
                 if (t != 0.0f && material_of(sc, item, l)[6] >= 1.0f) {
                     for (int k = 0; k < cx.n; ++k) { hn_o[k] = nn_o[k]; hn_d[k] = nn_d[k]; }
                 }
             }
         } else {
-            t = test_item_var(cx, item, hit.dist, skip_item, skip_lane, l);
+            t = test_item_var<CLIP>(cx, item, hit.dist, skip_item, skip_lane, l);
+        }
+        if constexpr (CLIP) {
+            // An item ALL of whose primitives were cut away -- the one of a triangle, the NT_DEV_BATCH of a batch -- is as if it
+            // had not been tested: dist_last stays.  A batch that keeps a primitive has been tested, and a miss of what it keeps
+            // is today's miss.
+            const float rejected = static_cast<const VarCtxClip &>(cx).cwin[2];
+            if (t == 0.0f && rejected >= ((item & 3) == 0 ? (float)NT_DEV_BATCH : 1.0f)) continue;
         }
         dist_last = t;
         if (t != 0.0f) {
@@ -1104,7 +1199,7 @@ __device__ __noinline__ bool leaf_closest_var_t(const VarCtx &cx, int start, int
 }
 
 // trace_closest_t (nt_composite.hpp) for the current ray
-template <bool ALIAS, typename ROOT = RootWhole>
+template <bool ALIAS, typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit, TList &th,
                                                  const Checked &ck, float *hn_o, float *hn_d, float *nn_o, float *nn_d, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
@@ -1115,6 +1210,7 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
     hit.lane = -1;
     th.n = 0;
     checked_reset(ck);
+    if constexpr (CLIP) clip_window_var(cx);
     int node = sc.root, sp = 0, dirty = 0;
     float t_far = root.t_far();
     const int max_sp = sc.stack_depth;
@@ -1122,7 +1218,7 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
         while (node >= 0) {
             const NtNode nd = sc.nodes[node];
             if (nd.axis < 0) {
-                if (leaf_closest_var_t<ALIAS>(cx, nd.left, nd.right, skip_item, skip_lane, hit, th, ck, hn_o, hn_d, nn_o, nn_d)) dirty = sp;
+                if (leaf_closest_var_t<ALIAS, CLIP>(cx, nd.left, nd.right, skip_item, skip_lane, hit, th, ck, hn_o, hn_d, nn_o, nn_d)) dirty = sp;
                 node = -1;
                 break;
             }
@@ -1192,12 +1288,13 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
 }
 
 // trace_occluded_t (nt_composite.hpp) for the current ray: transparent hits are collected, an opaque one blocks
-template <typename ROOT = RootWhole>
+template <typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, TList &sh, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
     const WaveLds &w = cx.w;
     const int lane = cx.lane;
     sh.n = 0;
+    if constexpr (CLIP) clip_window_var(cx);
     int node = sc.root, sp = 0;
     float t_near = root.t_near(), t_far = root.t_far();
     const int max_sp = sc.stack_depth;
@@ -1209,7 +1306,7 @@ __device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldista
                     const int item = sc.items[nd.left + i];
                     if ((item & 3) != 0 && item == skip_item) continue;
                     int l;
-                    const float t = test_item_var(cx, item, ldistance, skip_item, skip_lane, l);
+                    const float t = test_item_var<CLIP>(cx, item, ldistance, skip_item, skip_lane, l);
                     if (t != 0.0f) {
                         if (material_of(sc, item, l)[6] >= 1.0f) return true;
                         tl_add(sh, t, item, l);
@@ -1265,9 +1362,10 @@ __device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldista
 }
 
 // light_reaches (tracer.hpp:1750-1766); the shadow ray is the current ray
+template <bool CLIP = false>
 __device__ __forceinline__ bool light_reaches_var_t(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, Color3 &filtered) {
     TList sh;
-    if (trace_occluded_var_t(cx, ldistance, skip_item, skip_lane, sh)) return false;
+    if (trace_occluded_var_t<RootWhole, CLIP>(cx, ldistance, skip_item, skip_lane, sh)) return false;
     if (sh.n) {
         tl_sort_unique(sh);
         for (int i = sh.n - 1; i >= 0; --i) filtered = cscale(filtered, 1.0f - material_of(cx.sc, sh.e[i].item, sh.e[i].lane)[6]);
@@ -1277,7 +1375,7 @@ __device__ __forceinline__ bool light_reaches_var_t(const VarCtx &cx, float ldis
 
 // composite_color_t (nt_composite.hpp): ray_color / base_color as a state machine over the frame stack.  On entry the
 // primary ray is the current ray; `nframes` frames are there (max_reflect_depth + 1 when anything reflects).
-template <bool ALIAS>
+template <bool ALIAS, bool CLIP = false>
 __device__ __noinline__ Color3 composite_color_var_t(const VarCtx &cx, const VarFrames &fr, const Checked &ck, int nframes) {
     const NtCompositeDev &sc = cx.sc;
     const int n = cx.n;
@@ -1306,8 +1404,22 @@ __device__ __noinline__ Color3 composite_color_var_t(const VarCtx &cx, const Var
             Hit hit;
             hit.item = -1; hit.lane = -1; hit.dist = FLT_MAX;
             const float dist = aabb_distance_var(cx);
-            if (dist >= 0.0f)
-                trace_closest_var_t<ALIAS>(cx, dist, FRI(fp, S + VF_SKIP_ITEM), FRI(fp, S + VF_SKIP_LANE), hit, th, ck, hn_o, hn_d, a2, a3);
+            if (dist >= 0.0f) {
+                if constexpr (CLIP) {
+                    if (fp == 0) {
+                        // the primary ray under clip planes: the walk starts at max(aabb entry, t0) and ends at t1
+                        float tn = dist;
+                        RootWindow root;
+                        if (clip_primary_var(cx, tn, root))
+                            trace_closest_var_t<ALIAS, RootWindow, true>(cx, tn, FRI(fp, S + VF_SKIP_ITEM), FRI(fp, S + VF_SKIP_LANE), hit, th, ck, hn_o, hn_d,
+                                                                         a2, a3, root);
+                    } else {
+                        trace_closest_var_t<ALIAS, RootWhole, true>(cx, dist, FRI(fp, S + VF_SKIP_ITEM), FRI(fp, S + VF_SKIP_LANE), hit, th, ck, hn_o, hn_d, a2, a3);
+                    }
+                } else {
+                    trace_closest_var_t<ALIAS>(cx, dist, FRI(fp, S + VF_SKIP_ITEM), FRI(fp, S + VF_SKIP_LANE), hit, th, ck, hn_o, hn_d, a2, a3);
+                }
+            }
             if (ALIAS) {
                 for (int k = 0; k < n; ++k) { FRW(fp, 2 * n + k) = hn_o[k]; FRW(fp, 3 * n + k) = hn_d[k]; }
             }
@@ -1381,7 +1493,7 @@ __device__ __noinline__ Color3 composite_color_var_t(const VarCtx &cx, const Var
                         if (fmaxf(plc.r, fmaxf(plc.g, plc.b)) * strength * sine > NT_LIGHT_THRESHOLD) {
                             Color3 filtered = plc;
                             var_set_ray(cx, no, lv);
-                            if (light_reaches_var_t(cx, ldist, hit.item, hit.lane, filtered)) {
+                            if (light_reaches_var_t<CLIP>(cx, ldist, hit.item, hit.lane, filtered)) {
                                 filtered = cscale(filtered, strength);
                                 light = cadd(light, cscale(filtered, sine));
                                 if (m[8] != 0.0f) append_specular_var(n, specular, spec_a, m, filtered, dir, nd, lv);
@@ -1401,7 +1513,7 @@ __device__ __noinline__ Color3 composite_color_var_t(const VarCtx &cx, const Var
                         for (int k = 0; k < n; ++k) lv[k] = -gd[k];
                         Color3 filtered = glc;
                         var_set_ray(cx, no, lv);
-                        if (light_reaches_var_t(cx, FLT_MAX, hit.item, hit.lane, filtered)) {
+                        if (light_reaches_var_t<CLIP>(cx, FLT_MAX, hit.item, hit.lane, filtered)) {
                             light = cadd(light, cscale(filtered, sine));
                             if (m[8] != 0.0f) append_specular_var(n, specular, spec_a, m, filtered, dir, nd, lv);
                         }
@@ -1461,7 +1573,7 @@ __device__ __noinline__ Color3 composite_color_var_t(const VarCtx &cx, const Var
 // the grid, not by the image), one wave per block as in composite_kernel_var.
 template <bool ALIAS>
 __global__ __launch_bounds__(64) void composite_kernel_var_t(NtCamera cam, NtCompositeDev sc, NtTarget tg, int n, int tiles_x, int tiles_y,
-                                                             int frames) {
+                                                             int frames, NtClipPlanes cp) {
     extern __shared__ float2 lds_raw[];
     const int lane = (int)threadIdx.x;
     VarLds L;
@@ -1487,7 +1599,9 @@ __global__ __launch_bounds__(64) void composite_kernel_var_t(NtCamera cam, NtCom
     ck.n_triangles = sc.n_triangles;
     VarFrames fr;
     var_frames(fr, sc, slot, n);
-    const VarCtx cx = {sc, L, w, n, lane};
+    float cwin[3];                            // (clip planes: the window of the lane's current ray)
+    const VarCtxClip cxc = {{sc, L, w, n, lane}, cp.planes, cp.count, cwin};
+    const VarCtx &cx = cxc;
     const long long total = (long long)tiles_x * tiles_y * frames;
     for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
         if (nt_aborted(tg)) return;                       // (one wave a block)
@@ -1518,12 +1632,12 @@ __global__ __launch_bounds__(64) void composite_kernel_var_t(NtCamera cam, NtCom
             const float ok_ = c ? c[k] : cam.inl[k];
             L.ray[k * 64 + lane] = make_float2(ok_, dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
         }
-        const Color3 col = composite_color_var_t<ALIAS>(cx, fr, ck, sc.tframe_count);
+        const Color3 col = cp.count ? composite_color_var_t<ALIAS, true>(cx, fr, ck, sc.tframe_count) : composite_color_var_t<ALIAS>(cx, fr, ck, sc.tframe_count);
         emit_pixel(tg, pr, col.r, col.g, col.b);
     }
 }
 
-__global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompositeDev sc, NtTarget tg, int n) {
+__global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompositeDev sc, NtTarget tg, int n, NtClipPlanes cp) {
     extern __shared__ float2 lds_raw[];
     if (nt_aborted(tg)) return;
     const int lane = (int)threadIdx.x;
@@ -1553,8 +1667,10 @@ __global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompo
         const float ok_ = c ? c[k] : cam.inl[k];
         L.ray[k * 64 + lane] = make_float2(ok_, dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
     }
-    const VarCtx cx = {sc, L, w, n, lane};
-    const Color3 col = composite_color_var(cx);
+    float cwin[3];                            // (clip planes: the window of the lane's current ray)
+    const VarCtxClip cxc = {{sc, L, w, n, lane}, cp.planes, cp.count, cwin};
+    const VarCtx &cx = cxc;
+    const Color3 col = cp.count ? composite_color_var<true>(cx) : composite_color_var(cx);
     emit_pixel(tg, pr, col.r, col.g, col.b);
 }
 
@@ -1715,13 +1831,15 @@ __device__ __forceinline__ void hits_store_normal_var(const NtHits &h, long long
     if (h.normal_dir) for (int k = 0; k < n; ++k) h.normal_dir[r * n + k] = nd[k];
 }
 
-__global__ __launch_bounds__(64) void hits_closest_var(NtCompositeDev sc, NtTarget tg, NtHits h, int n, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(64) void hits_closest_var(NtCompositeDev sc, NtTarget tg, NtHits h, int n, int tiles_x, int tiles_y, NtClipPlanes cp) {
     extern __shared__ float2 lds_raw[];
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
     var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
-    const VarCtx cx = {sc, L, w, n, lane};
+    float cwin[3];                            // (clip planes: the window of the lane's current ray)
+    const VarCtxClip cxc = {{sc, L, w, n, lane}, cp.planes, cp.count, cwin};
+    const VarCtx &cx = cxc;
     const long long total = (long long)tiles_x * tiles_y * h.nframes;
     for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
         if (nt_aborted(tg)) return;                       // (one wave a block)
@@ -1731,7 +1849,15 @@ __global__ __launch_bounds__(64) void hits_closest_var(NtCompositeDev sc, NtTarg
         Hit hit;
         hit.dist = FLT_MAX; hit.item = -1; hit.lane = -1;
         const float dist0 = aabb_distance_var(cx);
-        if (dist0 >= 0.0f) trace_closest_var(cx, dist0, -1, -1, hit);
+        if (dist0 >= 0.0f) {
+            if (cp.count) {
+                float tn = dist0;
+                RootWindow root;
+                if (clip_primary_var(cx, tn, root)) trace_closest_var<RootWindow, true>(cx, tn, -1, -1, hit, root);
+            } else {
+                trace_closest_var(cx, dist0, -1, -1, hit);
+            }
+        }
         query_store(h.hits, p.rec, hit.dist, hit.item, hit.lane, 0);
         if (hit.item >= 0 && (h.normal_origin || h.normal_dir)) {
             float no[NT_DEV_MAX_DIM], nd[NT_DEV_MAX_DIM];
@@ -1742,13 +1868,15 @@ __global__ __launch_bounds__(64) void hits_closest_var(NtCompositeDev sc, NtTarg
 }
 
 template <bool ALIAS>
-__global__ __launch_bounds__(64) void hits_closest_var_t(NtCompositeDev sc, NtTarget tg, NtHits h, int n, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(64) void hits_closest_var_t(NtCompositeDev sc, NtTarget tg, NtHits h, int n, int tiles_x, int tiles_y, NtClipPlanes cp) {
     extern __shared__ float2 lds_raw[];
     const int lane = (int)threadIdx.x;
     VarLds L;
     WaveLds w;
     var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
-    const VarCtx cx = {sc, L, w, n, lane};
+    float cwin[3];                            // (clip planes: the window of the lane's current ray)
+    const VarCtxClip cxc = {{sc, L, w, n, lane}, cp.planes, cp.count, cwin};
+    const VarCtx &cx = cxc;
     Checked ck;
     ck.bits = sc.checked + ((long long)blockIdx.x * 64 + lane);
     ck.stride = sc.checked_lanes;
@@ -1768,7 +1896,15 @@ __global__ __launch_bounds__(64) void hits_closest_var_t(NtCompositeDev sc, NtTa
         float hn_o[NT_DEV_MAX_DIM], hn_d[NT_DEV_MAX_DIM], nn_o[NT_DEV_MAX_DIM], nn_d[NT_DEV_MAX_DIM];
         for (int k = 0; k < n; ++k) { hn_o[k] = 0.0f; hn_d[k] = 0.0f; }       // ray_intersection starts out zeroed
         const float dist0 = aabb_distance_var(cx);
-        if (dist0 >= 0.0f) trace_closest_var_t<ALIAS>(cx, dist0, -1, -1, hit, th, ck, hn_o, hn_d, nn_o, nn_d);
+        if (dist0 >= 0.0f) {
+            if (cp.count) {
+                float tn = dist0;
+                RootWindow root;
+                if (clip_primary_var(cx, tn, root)) trace_closest_var_t<ALIAS, RootWindow, true>(cx, tn, -1, -1, hit, th, ck, hn_o, hn_d, nn_o, nn_d, root);
+            } else {
+                trace_closest_var_t<ALIAS>(cx, dist0, -1, -1, hit, th, ck, hn_o, hn_d, nn_o, nn_d);
+            }
+        }
         query_store(h.hits, p.rec, hit.dist, hit.item, hit.lane, th.n);
         if (hit.item >= 0 && (h.normal_origin || h.normal_dir)) {
             if (!ALIAS) hit_normal_var(cx, hit, hn_o, hn_d);
@@ -2649,6 +2785,75 @@ int nt_launch_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTar
 // words per ray_color frame of composite_kernel_var_t (the host sizes NtCompositeDev::tframes with it)
 int nt_var_frame_words(int n) { return var_frame_words(n); }
 
+namespace {
+// The general route of a render or a primary-hit pass under clip planes: the run-time-n walks at every dimension, the planes
+// their last argument.  Transparent materials need the `checked` columns, and a render of them its ray_color frames, as
+// nt_launch_composite and nt_launch_hits want them.
+int clip_var_launch(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sv, const NtTarget &tg, const NtClip &cl, bool draw) {
+    const NtClipPlanes cp = {cl.planes, cl.count};
+    int r;
+    size_t lds;
+    hipStream_t s = (hipStream_t)li.stream;
+    if ((r = var_dim_check(li.n))) return r;
+    if (!sv.all_opaque && !sv.checked) return no_checked_scratch();
+    if (draw) {
+        dim3 grid;
+        grid_for(tg, 8, 8, li.nframes, grid);
+        if (sv.checked) {
+            if (!sv.tframes) return no_checked_scratch();
+            if ((r = var_frames_check(li.n, sv))) return r;
+            if ((r = var_walk_ready(li.n, sv, alias_kernel(sv, composite_kernel_var_t<true>, composite_kernel_var_t<false>), lds))) return r;
+            const dim3 blocks((unsigned)checked_blocks(sv));
+            if (sv.alias_normals)
+                hipLaunchKernelGGL(composite_kernel_var_t<true>, blocks, dim3(64), lds, s, cam, sv, tg, li.n, (int)grid.x, (int)grid.y, (int)grid.z, cp);
+            else
+                hipLaunchKernelGGL(composite_kernel_var_t<false>, blocks, dim3(64), lds, s, cam, sv, tg, li.n, (int)grid.x, (int)grid.y, (int)grid.z, cp);
+        } else {
+            if ((r = var_walk_ready(li.n, sv, reinterpret_cast<const void *>(composite_kernel_var), lds))) return r;
+            hipLaunchKernelGGL(composite_kernel_var, grid, dim3(64), lds, s, cam, sv, tg, li.n, cp);
+        }
+        return 0;
+    }
+    NtHits h;
+    h.cams = cl.cams;
+    h.nframes = li.nframes;
+    h.frame_stride = cl.frame_stride;
+    h.hits = cl.hits;
+    h.normal_origin = cl.normal_origin;
+    h.normal_dir = cl.normal_dir;
+    const int tiles_x = (tg.width + 7) / 8, tiles_y = (tg.height + 7) / 8;
+    const long long tiles = (long long)tiles_x * tiles_y * h.nframes;
+    if (sv.checked) {
+        if ((r = var_walk_ready(li.n, sv, alias_kernel(sv, hits_closest_var_t<true>, hits_closest_var_t<false>), lds))) return r;
+        const dim3 tgrid((unsigned)checked_blocks(sv, tiles));
+        if (sv.alias_normals) hipLaunchKernelGGL(hits_closest_var_t<true>, tgrid, dim3(64), lds, s, sv, tg, h, li.n, tiles_x, tiles_y, cp);
+        else hipLaunchKernelGGL(hits_closest_var_t<false>, tgrid, dim3(64), lds, s, sv, tg, h, li.n, tiles_x, tiles_y, cp);
+    } else {
+        if ((r = var_walk_ready(li.n, sv, reinterpret_cast<const void *>(hits_closest_var), lds))) return r;
+        const dim3 grid((unsigned)(tiles < (1 << 22) ? tiles : (1 << 22)));
+        hipLaunchKernelGGL(hits_closest_var, grid, dim3(64), lds, s, sv, tg, h, li.n, tiles_x, tiles_y, cp);
+    }
+    return 0;
+}
+}  // namespace
+
+// Clip planes (nt_clip.hpp): the packet route of the scene's dimension for what launch_composite_fixed would give the packet
+// walk, the run-time-n kernels for every other scene.  Kept apart from nt_launch_composite and nt_launch_hits: with the
+// setting off nothing here is reached.
+int nt_launch_clip(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg, const NtClip &cl, bool draw) {
+    if (!cl.planes || cl.count < 1 || cl.count > NT_DEV_CLIP_MAX || !cl.cams || (!draw && !cl.hits)) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a clip launch without its planes, cameras or records");
+        return -1;
+    }
+    int r = 0;
+    const bool packet = sc.all_opaque && !sc.checked && sc.stack_depth <= 32 && li.kernel_choice == 0 && !li.force_var;
+    if (!packet || !nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.n, r, [&](auto N) { return nt_clip_packet<decltype(N)::value>(li, sc, tg, cl, draw); })) {
+        r = clip_var_launch(li, cam, sc, tg, cl, draw);
+    }
+    if (r) return r;
+    return finish_launch("clip kernel launch");
+}
+
 int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg) {
     int r;
     size_t lds;
@@ -2661,10 +2866,10 @@ int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCom
         const dim3 blocks((unsigned)checked_blocks(sc));
         if (sc.alias_normals)
             hipLaunchKernelGGL(composite_kernel_var_t<true>, blocks, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, (int)grid.x, (int)grid.y,
-                               (int)grid.z);
+                               (int)grid.z, NtClipPlanes{nullptr, 0});
         else
             hipLaunchKernelGGL(composite_kernel_var_t<false>, blocks, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, (int)grid.x, (int)grid.y,
-                               (int)grid.z);
+                               (int)grid.z, NtClipPlanes{nullptr, 0});
         return finish_launch("composite kernel launch");
     }
     if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_composite_fixed<decltype(N)::value>(li, cam, sc, tg); })) {
@@ -2676,7 +2881,7 @@ int nt_launch_composite(const NtLaunchInfo &li, const NtCamera &cam, const NtCom
         if ((r = var_walk_ready(li.n, sc, reinterpret_cast<const void *>(composite_kernel_var), lds))) return r;
         // run-time-n kernel: one wave per 8x8 tile (probe mode: 64 probes per block)
         grid_for(tg, 8, 8, li.nframes, grid);
-        hipLaunchKernelGGL(composite_kernel_var, grid, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n);
+        hipLaunchKernelGGL(composite_kernel_var, grid, dim3(64), lds, (hipStream_t)li.stream, cam, sc, tg, li.n, NtClipPlanes{nullptr, 0});
     }
     if (r) return r;
     return finish_launch("composite kernel launch");
@@ -2729,13 +2934,13 @@ int nt_launch_hits(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTar
         if (sc.checked) {
             // as many blocks as the `checked` scratch has lane columns for, striding over the tiles
             const dim3 tgrid((unsigned)checked_blocks(sc, tiles));
-            if (sc.alias_normals) hipLaunchKernelGGL(hits_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
-            else hipLaunchKernelGGL(hits_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+            if (sc.alias_normals) hipLaunchKernelGGL(hits_closest_var_t<true>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y, NtClipPlanes{nullptr, 0});
+            else hipLaunchKernelGGL(hits_closest_var_t<false>, tgrid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y, NtClipPlanes{nullptr, 0});
         } else if (!sc.all_opaque) {
             return no_checked_scratch();
         } else {
             const dim3 grid((unsigned)(tiles < (1 << 22) ? tiles : (1 << 22)));
-            hipLaunchKernelGGL(hits_closest_var, grid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y);
+            hipLaunchKernelGGL(hits_closest_var, grid, dim3(64), lds, s, sc, tg, h, li.n, tiles_x, tiles_y, NtClipPlanes{nullptr, 0});
         }
     }
     if (r) return r;

@@ -857,6 +857,17 @@ class Lens(object):
         return np.ascontiguousarray(v, f32)
 
 
+def clip_plane_through(point, normal):
+    """The (normal, offset) pair of set_clip_planes for the plane through `point` with the given normal, which keeps the side
+    the normal points away from: the normal's components as float32, the offset their float64 dot product with the point
+    rounded once to float32."""
+    a = np.asarray([float(v) for v in normal], f32)
+    p = np.asarray([float(v) for v in point], np.float64)
+    if a.shape != p.shape or a.ndim != 1:
+        raise ValueError("point and normal must have the same number of components")
+    return tuple(float(v) for v in a), float(f32(np.dot(a.astype(np.float64), p)))
+
+
 def sphere_directions(n, count, seed=0):
     """`count` directions uniform on the unit sphere of n dimensions, float32 [count][n]: normal deviates of
     numpy.random.default_rng(seed), normalised in float64 -- the table set_ambient_occlusion makes of a plain sample count"""
@@ -1193,6 +1204,48 @@ class _SceneBase(Scene):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(L.nt_depth_cue_factors_device(self._handle, width, height, C.c_void_p(factors.data_ptr()), C.byref(opts), C.c_void_p(stream)))
         return factors
+
+    def set_clip_planes(self, planes):
+        """Cutaway views (include/ntracer_hip.h): `planes` is a sequence of up to 8 (normal, offset) pairs, a
+        normal being a Vector or n numbers, finite and not all zero, and the keep-region the points x with normal . x <= offset
+        for every pair (clip_plane_through makes a pair from a point and a normal).  Every ray of a render honours it -- primary,
+        shadow and reflection rays, and the continuation through transparent hits -- so the geometry cut away casts no shadow and
+        shows in no mirror; there are no caps.  render and primary_hits honour the setting.  set_clip_planes(None) or an empty
+        sequence takes it off.  CompositeScene only.  Supersampling, row bands, statistics, a lens, the parallel projection,
+        ambient occlusion, outlines, depth cues and scenes with Solids are refused with it, and so are calculate_color /
+        colors_at, ray_colors, render_rays, refinement_mask, occlusion_counts, outline_mask and depth_cue_factors while it is on;
+        the ray queries ignore it.  A view setting like fov: not pickled."""
+        L = _lib.lib()
+        if planes is None:
+            _lib.check(L.nt_scene_set_clip_planes(self._handle, 0, None, None))
+            return
+        pairs = list(planes)
+        n = self.dimension
+        normals = np.zeros((max(len(pairs), 1), n), f32)
+        offsets = np.zeros(max(len(pairs), 1), f32)
+        for k, pair in enumerate(pairs):
+            try:
+                normal, offset = pair
+            except (TypeError, ValueError):
+                raise ValueError("a clip plane is a (normal, offset) pair")
+            row = [float(v) for v in normal]
+            if len(row) != n:
+                raise ValueError("the normal of a clip plane must have %d components" % n)
+            if isinstance(offset, bool) or not isinstance(offset, (int, float, np.integer, np.floating)):
+                raise ValueError("the offset of a clip plane must be a number")
+            normals[k] = row
+            offsets[k] = offset
+        _lib.check(L.nt_scene_set_clip_planes(self._handle, len(pairs), normals.ctypes.data_as(_lib.f32p), offsets.ctypes.data_as(_lib.f32p)))
+
+    @property
+    def clip_planes(self):
+        """the setting of set_clip_planes: a tuple of (normal, offset) pairs, normal a tuple of n floats; empty while off"""
+        count = C.c_int(0)
+        normals = np.zeros((_lib.NT_CLIP_MAX, self.dimension), f32)
+        offsets = np.zeros(_lib.NT_CLIP_MAX, f32)
+        _lib.check(_lib.lib().nt_scene_get_clip_planes(self._handle, C.byref(count), normals.ctypes.data_as(_lib.f32p),
+                                                       offsets.ctypes.data_as(_lib.f32p)))
+        return tuple((tuple(float(v) for v in normals[k]), float(offsets[k])) for k in range(count.value))
 
     def set_lens(self, lens):
         """Render through `lens` (a Lens of the image's size) instead of the pinhole; None takes it off.  fov is ignored
