@@ -187,6 +187,56 @@ __device__ __forceinline__ float nt_vmax3(float a, float b, float c) { float r; 
 __device__ __forceinline__ float nt_vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ float nt_vmed3(float a, float b, float c) { float r; asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ float nt_vmax_abs(float a, float b) { float r; asm("v_max_f32 %0, |%1|, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }   // max(|a|, b)
+__device__ __forceinline__ float nt_vmax3_abs(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }   // max(a, |b|, |c|)
+__device__ __forceinline__ float nt_vmin_abs(float a, float b) { float r; asm("v_min_f32 %0, |%1|, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }   // min(|a|, b)
+
+// The "sure hit" bit of a stretch's sets word (box_stretch_code2; bit 24: bits 20..23 hold the code where code and sets share a
+// register): every ray of the stretch is a hit for the reference, at a face of T -- which one is the business of its rounding,
+// but the packed pixel rarely depends on it (box_pixel's sure_hit_row).  Packed RGB, N = NT_BOX_TIE_SHORTCUT_MIN_N.._MAX_N, the 64 x 1
+// shape in launches of NT_BOX_TIE_SHORTCUT_MIN_WAVES waves or more;
+// -DNT_BOX_TIE_SHORTCUT=0: neither the bit nor the branch, the build to measure and to test against (and N = 7's, nt_inst_box.hip).
+//
+// The reference's ray is (o, d) with the float d = v/|v|, u = 2^-24.  Face i (entry plane s_i = -+1) has
+// dist_i = fl(fl(s_i - o_i)/d_i) = tau_i (1 + e1)(1 + e2), |e| <= u, tau_i = (s_i - o_i)/d_i exactly; it passes iff dist_i > 0
+// and |p_j| <= 1 + FUZZ = 1 + 20u for every j != i, p_j = fl(fl(d_j dist_i) + o_j).  A stretch with valid sets (T, C) has
+// (1) no face outside T passing and (2) no coordinate outside C failing for a face of T, at any tau of [t_lo, t_hi], which
+// holds every such test (box_stretch_code2).  The bit is set when, besides,
+//   * C == T;
+//   * no slab is left inside the window: (t_hi - t_lo) * max_j (|vc_j| + g_j) <= 1 (T's axes are what the argument needs);
+//   * |o_j| <= NT_BOX_TIE_SURE_MAX_ORIGIN on every axis j of T.
+// Then the face K* of T with the largest float dist passes.  A coordinate outside T = C passes by (2).  For j in T, j != K*:
+// dist_K* >= dist_j, so the exact P_j = o_j + d_j dist_K* lies on the inner side of
+//   o_j + d_j dist_j = s_j + (s_j - o_j)(e1 + e2 + e1 e2),   at most (1 + |o_j|) 2u (and u^2 of that) outside the slab:
+// it has entered, or is that far short of entering; and it has not left: both entries lie in the window, across which no
+// coordinate of T moves by more than 1 of the slab's width of 2.  So |P_j| <= 1 + (1 + |o_j|) 2u.  The product's rounding adds
+// at most |d_j dist_K*| u <= (1 + |o_j|) u (P_j is between o_j and the far plane), the sum's -- a result next to 1 -- at most u:
+//   |p_j| <= 1 + (4 + 3|o_j|) u  <=  1 + 17.5 u  <  1 + 20u     at |o_j| = 4.5    (16.5 u at the bench's 4.17; 5.33 is the break-even).
+// K* passes, faces outside T do not (1), every face of T has dist > 0 (t_lo > 1e-3) and below FLT_MAX (t_hi < 1e30): the
+// reference returns a hit at the first passing face of T.
+#ifndef NT_BOX_TIE_SHORTCUT
+#define NT_BOX_TIE_SHORTCUT 1
+#endif
+#ifndef NT_BOX_TIE_SHORTCUT_MIN_N
+#define NT_BOX_TIE_SHORTCUT_MIN_N 6
+#endif
+#ifndef NT_BOX_TIE_SHORTCUT_MAX_N
+#define NT_BOX_TIE_SHORTCUT_MAX_N 8
+#endif
+#ifndef NT_BOX_TIE_SURE_MAX_ORIGIN
+#define NT_BOX_TIE_SURE_MAX_ORIGIN 4.5f
+#endif
+// The kernel with the bit and the branch in it (box_tile_kernel<N, false, 64, 1, true>) is a launch's kernel only from this many
+// 64-row waves on: having them costs a launch a nearly fixed time whether any row takes the branch -- with a bit that is never set
+// the headline call (81 600 waves) measured 308.2 -> 312.4 us and a rank's eighth of it in the same shape (14 400 waves) 75.0 ->
+// 77.3 us -- and what the stored rows save grows with the rows: 9.2 us of the headline call, 1.0 us of the eighth.  Those figures
+// meet at about 24 000 waves.  Smaller launches, and the 16- and 8-row shapes, which are small launches by
+// construction, run the kernel without.
+#ifndef NT_BOX_TIE_SHORTCUT_MIN_WAVES
+#define NT_BOX_TIE_SHORTCUT_MIN_WAVES 32768
+#endif
+#define NT_BOX_SETS_SURE 0x01000000u
+template <int N>
+constexpr bool nt_box_tie_shortcut() { return NT_BOX_TIE_SHORTCUT != 0 && N >= NT_BOX_TIE_SHORTCUT_MIN_N && N <= NT_BOX_TIE_SHORTCUT_MAX_N && N <= NT_BOX_SETS_MAX_N; }
 
 // box_classify for a row sorted ray by ray (code 15) whose stretch has valid sets (box_stretch_code2: T in bits 0..9, C in bits
 // 10..19, wave-uniform): the same three verdicts from T's entry planes and C's coordinates alone -- |C| reciprocals, slab updates
@@ -407,7 +457,7 @@ __device__ __forceinline__ float sqrt_wave(float x) {
 // REDO (box_redo_kernel): no sorting into clear and unclear -- box_resolve is complete by itself (a clear hit is T = C =
 // {K}; a clear miss fails at a coordinate of C), and in a stretch that is here because of its unclear lanes the
 // sorting of the others saves nothing.
-template <int N, bool PLAIN, bool DEFER = false, bool REDO = false, bool F32 = false>
+template <int N, bool PLAIN, bool DEFER = false, bool REDO = false, bool F32 = false, bool TIE = false>
 __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr, const float (&org)[N], float (&dir)[N], float sq,
                                           const float (&dots)[4], float sx, float sy, float margin, bool rowhit = true, int face = -1,
                                           uint32_t sets = 0u, bool noclass = false) {
@@ -462,6 +512,43 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
             }
         }
     };
+    // A stretch whose sets carry the "sure hit" bit (NT_BOX_SETS_SURE: every ray hits a face of T): the pixel without the
+    // reference's arithmetic.  Its colour is |d_i| (1, 1/2, 1/2) for the face i of T the reference's rounding picks, and
+    // t(x) = |x| rsq(sq) maxval -- the clear path's quotient below, with its guard of 2^-20 (1 + t) -- is monotone in |x|, as is
+    // t - guard(t): when t and t/2 of the smallest and of the largest |dir_i| over T are clear of every k + 1/2 and round to the
+    // same two integers, those of every face of T lie between them, are clear, and round likewise.  Those are the bytes; a wave
+    // with a lane that is not so takes exact_on_sets as before.  (Axes picked by scalar tests on `sets`; wave-uniform result.)
+    constexpr bool SURE = TIE && nt_box_tie_shortcut<N>() && INL && PLAIN && !F32;
+    auto sure_hit_row = [&]() -> bool {
+        float lo = INFINITY, hi = 0.0f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            if (((sets >> j) & 1u) != 0u) {
+                asm volatile("" : "+v"(lo), "+v"(hi));
+                lo = nt_vmin_abs(dir[j], lo);
+                hi = nt_vmax_abs(dir[j], hi);
+            }
+        }
+        const float maxv = (float)tg.plain_maxval;
+        const float rs = __builtin_amdgcn_rsqf(sq);
+        const float t0 = (lo * rs) * maxv, t1 = (hi * rs) * maxv;
+        const float h0 = t0 * 0.5f, h1 = t1 * 0.5f;
+        auto clear = [](float t) { return fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-20f, 0x1p-20f); };
+        // t + 2^23 holds round(t) in its low mantissa bits (t <= 1023.5: plain_bits <= 10)
+        const uint32_t r0 = __float_as_uint(t0 + 8388608.0f), r1 = __float_as_uint(t1 + 8388608.0f);
+        const uint32_t g0 = __float_as_uint(h0 + 8388608.0f), g1 = __float_as_uint(h1 + 8388608.0f);
+        const bool same = clear(t0) && clear(t1) && clear(h0) && clear(h1) && r0 == r1 && g0 == g1;      // (a NaN fails)
+        if (__builtin_amdgcn_ballot_w64(!same) != 0ull) return false;
+        if (tg.plain_sel != 0u) {
+            *reinterpret_cast<uint32_t *>(tg.dest + pr.offset) = __builtin_amdgcn_perm(r1, g1, tg.plain_sel);
+            return true;
+        }
+        uint32_t qgb = (uint32_t)(h1 + 0.5f), qr = (uint32_t)(t1 + 0.5f);
+        qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
+        qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
+        emit_plain(tg, pr, qr, qgb);
+        return true;
+    };
     if constexpr (CSETS) {
         const bool have_sets = face < 0 && (sets & 0x80000000u) != 0u;
         bool on_sets = have_sets && redo;
@@ -477,6 +564,9 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
             sorted = true;
         }
         if (on_sets) {
+            if constexpr (SURE) {
+                if ((sets & NT_BOX_SETS_SURE) != 0u && redo && sure_hit_row()) return true;
+            }
             hit = false;
             exact_on_sets();
         } else if (sorted) {
@@ -487,12 +577,15 @@ __device__ __forceinline__ bool box_pixel(const NtTarget &tg, const PixelRef &pr
             box_classify<N>(org, dir, margin, maybe, hit, unclear, x, near, tn, vK);
         }
     } else {
-        // (as it was before there was a box_classify_sets: the device code of these dimensions has not changed)
+        // (as it was before there was a box_classify_sets)
         if (face >= 0) {
             hit = true;
 #pragma unroll
             for (int j = 1; j < N; ++j) x = face == j ? dir[j] : x;
         } else if ((REDO || INL) && redo && (sets & 0x80000000u) != 0u) {
+            if constexpr (SURE) {
+                if ((sets & NT_BOX_SETS_SURE) != 0u && sure_hit_row()) return true;
+            }
             exact_on_sets();
         } else if (redo) {
             box_entries<N>(org, dir, near, tn, vK);
@@ -731,7 +824,7 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
 // The code of one 64-pixel stretch (see the comment above): row y of the image, stretch `col` of the row.
 // `sets` (box_tile_kernel): for a stretch of code 14 or 15, what box_resolve works out ray by ray from entry times -- the faces T that
 // can still be the reference's answer and the coordinates C one of them could fail at -- as supersets valid for EVERY ray
-// of the stretch (bits 0..9: T, bits 10..19: C, bit 31: valid), so that box_tile_kernel goes straight to the reference's
+// of the stretch (bits 0..9: T, bits 10..19: C, bit 31: valid, bit 24: every ray hits a face of T -- NT_BOX_SETS_SURE), so that box_tile_kernel goes straight to the reference's
 // arithmetic on them in its near-tie stretches.  With [A_j, B_j] the range of slab j's entry time over the stretch's directions: every ray's last
 // entry is at or after TN = max_j A_j; M = m / (the smallest |v_j| of an axis that can be last, B_j >= TN) is at least the
 // ray's m/|v_K|; so a face within m/|v_K| of a ray's last entry has B_j >= TN - M: that is T.  The entries of T's faces,
@@ -739,7 +832,7 @@ __global__ __launch_bounds__(256) void box_redo_kernel(NtCameraFixed cam, NtTarg
 // stretch's directions, passes every test made there: the others, and T itself, are C.  (A face of T that a given ray
 // enters long before its last entry fails at that ray's last axis, which is in T, hence in C.)  No valid sets when a candidate's v_j
 // changes sign in the stretch or TN - M is not clearly positive (rays starting on or in the cube: box_color's business).
-template <int N, bool SETS = false>
+template <int N, bool SETS = false, bool SURE = false>
 __device__ __forceinline__ unsigned long long box_stretch_code2(const float (&org)[N], const float (&right)[N], const float (&up)[N],
                                                                 const float (&fwd)[N], const NtTarget &tg, int y, int col) {
     // returns the code in the low dword and, SETS, the sets in the high one
@@ -862,6 +955,22 @@ __device__ __forceinline__ unsigned long long box_stretch_code2(const float (&or
                 }
                 const bool valid = vmin > 0.0f && t_lo > 1e-3f && t_hi < 1e30f;         // (a NaN fails)
                 *sets = valid ? (0x80000000u | (C << 10) | T) : 0u;
+                if constexpr (SURE) {
+                    // the "sure hit" bit (NT_BOX_SETS_SURE, see there): C == T, no slab left inside the window, no axis of T
+                    // further out than the bound on the reference's rounding allows.  One vector instruction an axis: the
+                    // largest |v_j| is taken over all axes, not T's alone (of the bench's cameras' stretches that costs none its
+                    // bit, tools/box_sets_census.py), and which axes are too far out is the same for every stretch of a frame:
+                    // an integer compare of |o_j|'s bits -- a NaN counts as too far -- on the scalar unit.
+                    float wmax = 0.0f;
+                    uint32_t far_axes = 0u;
+#pragma unroll
+                    for (int j = 0; j < N; ++j) {
+                        wmax = nt_vmax3_abs(wmax, vc[j] - g[j], vc[j] + g[j]);            // (the larger is |vc_j| + g_j)
+                        far_axes |= (__float_as_uint(org[j]) & 0x7fffffffu) > __float_as_uint(NT_BOX_TIE_SURE_MAX_ORIGIN) ? 1u << j : 0u;
+                    }
+                    const bool sure = valid && C == T && (T & far_axes) == 0u && (t_hi - t_lo) * wmax <= 1.0f;      // (a NaN fails)
+                    *sets |= sure ? NT_BOX_SETS_SURE : 0u;
+                }
             }
         }
     }
@@ -986,14 +1095,16 @@ __device__ __forceinline__ void nt_set_bit(unsigned long long &m, int bit) { asm
 // and; 64 bits, where that is an add, an add with carry and an and, the one instruction
 __device__ __forceinline__ void nt_drop_low_bit(uint32_t &m, int) { m &= m - 1u; }
 __device__ __forceinline__ void nt_drop_low_bit(unsigned long long &m, int bit) { nt_clear_bit(m, bit); }
-template <int N, bool F32, int ROWS, int WAVES>
+// TIE: the near-tie rows' short cut (NT_BOX_SETS_SURE) is in this kernel -- launch_box_fixed says for which launches
+template <int N, bool F32, int ROWS, int WAVES, bool TIE = false>
 __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCameraFixed cam, NtTarget tg) {
+    static_assert(!TIE || (!F32 && ROWS == 64 && nt_box_tie_shortcut<N>()), "the short cut: packed RGB, 64 x 1, the dimensions it is built for");
     static_assert(ROWS == 8 || ROWS == 16 || ROWS == 64, "a wave's rows: a qword of sixteen codes in LDS or fewer, or one row a lane");
     static_assert(WAVES >= 1 && WAVES <= 4 && WAVES * ROWS <= 64, "the codes of a tile are the work of one wave, a row per lane");
     static_assert(WAVES == 1 ? ROWS == 64 : ROWS <= 16, "one wave a block renders the 64 rows whose codes it worked out itself");
     constexpr int R = ROWS;
     // One wave a block: the wave that works out the codes is the one that renders their rows.  Code and tie sets of slot s stay in
-    // lane s, in one register (sets: bits 0..19 and 31 as box_stretch_code2 leaves them; code: bits 20..23), and the row phase
+    // lane s, in one register (sets: bits 0..19, 24 and 31 as box_stretch_code2 leaves them; code: bits 20..23), and the row phase
     // fetches them with v_readlane_b32 on the slot's scalar index: no LDS, no barrier.  More waves a block: another wave's codes
     // come through LDS.
     constexpr bool REG = WAVES == 1;
@@ -1011,6 +1122,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
     // 6-12 % slower without box_redo_kernel, BoxScene(16) 15 %.
     constexpr bool ALLIN = F32 || N <= NT_BOX_INLINE_MAX_N;
     constexpr bool SETS_LDS = ALLIN && N <= NT_BOX_SETS_MAX_N;
+    constexpr uint32_t SETS_MASK = 0x800fffffu | (TIE ? NT_BOX_SETS_SURE : 0u);       // what of a sets word lane_cs keeps
     __shared__ uint32_t s_sets[SETS_LDS ? LDS_N : 1];
     __shared__ int s_abort;                  // the codes wave's reading of NtTarget::abort_word: one answer for the whole block
     uint32_t lane_cs = 0u;                   // REG: code and tie sets of the slot that is this lane
@@ -1068,13 +1180,13 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             if (y < tg.height) {
                 // (N > 8: the sets' arithmetic would raise the kernel's register allocation -- 124 VGPRs and spills at N = 10 --
                 // for every row; those dimensions go without)
-                const unsigned long long cs = box_stretch_code2<N, (N <= NT_BOX_SETS_MAX_N)>(org, right, up, fwd, tg, y, (int)blockIdx.x);
+                const unsigned long long cs = box_stretch_code2<N, (N <= NT_BOX_SETS_MAX_N), TIE>(org, right, up, fwd, tg, y, (int)blockIdx.x);
                 code = (uint32_t)cs;
                 row_sets = (uint32_t)(cs >> 32);
             }
         }
         if constexpr (REG) {
-            lane_cs = (SETS_LDS ? row_sets & 0x800fffffu : 0u) | (code << 20);
+            lane_cs = (SETS_LDS ? row_sets & SETS_MASK : 0u) | (code << 20);
         } else {
             if (SETS_LDS) s_sets[lane] = row_sets;
             {
@@ -1230,7 +1342,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         };
         auto sets_of = [&](int rr) {
             if constexpr (!SETS_LDS) return 0u;
-            else if constexpr (REG) return slot_word(rr) & 0x800fffffu;
+            else if constexpr (REG) return slot_word(rr) & SETS_MASK;
             else return (uint32_t)__builtin_amdgcn_readfirstlane((int)s_sets[wv * R + rr]);
         };
         // the rows of the pass whose code is c (a face's): one vector compare -- of the lane's own code, or of its nibble of the qword
@@ -1459,7 +1571,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
             if (ALLIN) {
                 // everything here: classification, the reference's arithmetic on the faces in question (on the stretch's tie sets
                 // for a near-tie stretch), box_color for rays that start on or in the cube
-                box_pixel<N, !F32, false, false, F32>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit, rcode >= 1 && rcode <= 13 ? rcode - 1 : -1,
+                box_pixel<N, !F32, false, false, F32, TIE>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit, rcode >= 1 && rcode <= 13 ? rcode - 1 : -1,
                                                        sets_of(rr), rcode == 14);
             } else if (!box_pixel<N, true, true, false, false>(tg, pr, org, dir, sq, dots, sx, sy, margin, rowhit, rcode >= 1 && rcode <= 13 ? rcode - 1 : -1)) {
                 redo_bits |= (mask_t)1u << rr;
@@ -1544,7 +1656,12 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
         if ((long long)li.nframes + tg.lead_frames > 65535) tg.lead_frames = 0;        // (grid z)
         tgrid.z += (unsigned)tg.lead_frames;
         if (fmt_rgb) {
-            if (r64) hipLaunchKernelGGL((box_tile_kernel<N, false, 64, 1>), tgrid, dim3(64), 0, st, cf, tg);
+            // (one 64-row wave a block; tgrid.z counts the lead slots too, hence li.nframes)
+            bool tie = false;
+            if constexpr (nt_box_tie_shortcut<N>()) tie = r64 && (unsigned long long)tgrid.x * tgrid.y * (unsigned)li.nframes >= (unsigned long long)NT_BOX_TIE_SHORTCUT_MIN_WAVES;
+            if (tie) {
+                if constexpr (nt_box_tie_shortcut<N>()) hipLaunchKernelGGL((box_tile_kernel<N, false, 64, 1, true>), tgrid, dim3(64), 0, st, cf, tg);
+            } else if (r64) hipLaunchKernelGGL((box_tile_kernel<N, false, 64, 1>), tgrid, dim3(64), 0, st, cf, tg);
             else if (r16 && wpb == 3) hipLaunchKernelGGL((box_tile_kernel<N, false, 16, 3>), tgrid, dim3(192), 0, st, cf, tg);
             else if (r16) hipLaunchKernelGGL((box_tile_kernel<N, false, 16, 4>), tgrid, dim3(256), 0, st, cf, tg);
             else hipLaunchKernelGGL((box_tile_kernel<N, false, 8, 4>), tgrid, dim3(256), 0, st, cf, tg);

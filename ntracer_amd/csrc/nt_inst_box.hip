@@ -28,6 +28,11 @@
 #define NT_TILE_OCC __attribute__((amdgpu_waves_per_eu(3, 3)))
 #endif
 #endif
+#if NT_INST_N == 7 && !defined(NT_BOX_TIE_SHORTCUT)
+// (the near-tie rows' short cut, nt_box.hpp NT_BOX_SETS_SURE: at n = 7 the bench's rotation gains 1.5-2 % and 64 random cameras
+// a call lose 2.3-2.7 %, two visits, spreads under 1 %, DESIGN.md 4.1 -- without it this unit's device code is what it was)
+#define NT_BOX_TIE_SHORTCUT 0
+#endif
 #include "nt_box.hpp"
 #include "nt_dispatch.hpp"
 

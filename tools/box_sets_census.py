@@ -48,9 +48,24 @@ def screen(w, h, fov=0.8):
     return half_w, half_h, F(fovI)
 
 
+TIE_SURE_MAX_ORIGIN = F(4.5)        # NT_BOX_TIE_SURE_MAX_ORIGIN
+
+
 def stretch_codes(origin, axes, w, h, fov=0.8, rows=None):
     """codes and sets of every 64-pixel stretch of the rows `rows` (default: all h) of a w x h frame seen from (origin, axes):
     two arrays [len(rows)][ceil(w / 64)], uint32.  sets: bits 0..9 T, bits 10..19 C, bit 31 valid (N <= 10)."""
+    return _stretch(origin, axes, w, h, fov, rows)[:2]
+
+
+def stretch_sure_hit(origin, axes, w, h, fov=0.8, rows=None, limit=TIE_SURE_MAX_ORIGIN):
+    """stretch_codes' two arrays and box_stretch_code2's "sure hit" bit (bit 24 of the device's sets word) as a third, bool: the
+    stretch has valid sets with C == T, no slab can be left inside the window of tau that holds every test made there --
+    (t_hi - t_lo) * max over all axes of (|vc_j| + g_j) <= 1 -- and |o_j| <= limit on every axis of T.  Every ray of such a stretch is a
+    hit, at a face of T, for the reference (nt_box.hpp, NT_BOX_TIE_SURE_MAX_ORIGIN)."""
+    return _stretch(origin, axes, w, h, fov, rows, limit)
+
+
+def _stretch(origin, axes, w, h, fov=0.8, rows=None, limit=TIE_SURE_MAX_ORIGIN):
     org = np.asarray(origin, F)
     right, up, fwd = (np.asarray(axes, F)[k] for k in range(3))
     n = len(org)
@@ -106,6 +121,7 @@ def stretch_codes(origin, axes, w, h, fov=0.8, rows=None):
         tie = (code == 15) & ~(((tn - tn2).astype(F) * np.abs(vK)).astype(F) > m)
         code = np.where(tie, 14, code).astype(np.uint32)
         sets = np.zeros(S, np.uint32)
+        sure = np.zeros(S, bool)
         if n <= 10:
             rA, rB, rV = [], [], []
             TN, TH = np.full(S, -INF, F), np.full(S, -INF, F)
@@ -140,7 +156,15 @@ def stretch_codes(origin, axes, w, h, fov=0.8, rows=None):
                 Cs |= np.where(inC, np.uint32(1 << j), np.uint32(0))
             valid = (vmin > 0) & (s_lo > F(1e-3)) & (s_hi < F(1e30))
             sets = np.where(valid & (code >= 14), np.uint32(0x80000000) | (Cs << np.uint32(10)) | T, np.uint32(0)).astype(np.uint32)
-    return code.reshape(len(ys), ncols), sets.reshape(len(ys), ncols)
+            # the "sure hit" bit
+            wmax, omax_T = np.zeros(S, F), np.zeros(S, F)
+            for j in range(n):
+                inT = ((T >> np.uint32(j)) & 1).astype(bool)
+                wmax = np.fmax(wmax, np.fmax(np.abs((vc[j] - g[j]).astype(F)), np.abs((vc[j] + g[j]).astype(F))))
+                omax_T = np.where(inT, np.fmax(omax_T, np.abs(org[j])), omax_T)
+            with np.errstate(invalid="ignore"):
+                sure = (sets != 0) & (Cs == T) & (((s_hi - s_lo).astype(F) * wmax).astype(F) <= F(1.0)) & (omax_T <= F(limit))
+    return code.reshape(len(ys), ncols), sets.reshape(len(ys), ncols), sure.reshape(len(ys), ncols)
 
 
 def popcount(x):

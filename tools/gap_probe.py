@@ -15,7 +15,7 @@ ks = [(short(r["Kernel_Name"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"
 groups = {}
 last_tile_end = None
 for i, (name, s, e) in enumerate(ks):
-    if name.startswith("box_tile_kernel<6, false, 64, 1>"):
+    if name.startswith("box_tile_kernel<6, false, 64, 1"):
         before = ks[i - 1][0][:24] if i else "-"
         if last_tile_end is not None:
             groups.setdefault(before, []).append(((s - last_tile_end) / 1e3, (e - s) / 1e3))
