@@ -26,6 +26,7 @@
 
 #include "../../include/ntracer_hip.h"
 #include "nt_device.hpp"
+#include "nt_box_span.hpp"
 
 namespace {
 
@@ -679,6 +680,7 @@ struct FrameJob {
     int nframes;
     const float *cam_buf;     // device [nframes][4][n] or nullptr
     const float *cam_dots = nullptr;   // with cam_buf: device [nframes][4], the cameras' dot products (camera_dots)
+    const float *cam_span = nullptr;   // with cam_buf, from a camera table only: device [nframes][2], the cameras' spans (NtCamera::span)
     hipStream_t stream;
     bool stats;
     bool strict = false;      // nt_render_opts.strict_reference
@@ -828,6 +830,7 @@ FrameJob base_frame_job(const nt_scene *s, const FrameJob &job, const Format &bf
     if (job.cam_buf) {
         bj.cam_buf = job.cam_buf + (size_t)f0 * 4 * s->n;
         bj.cam_dots = job.cam_dots + (size_t)f0 * 4;
+        if (job.cam_span) bj.cam_span = job.cam_span + (size_t)f0 * 2;
     }
     return bj;
 }
@@ -1098,6 +1101,7 @@ int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
             if (job.cam_buf) {
                 hj.cam_buf = job.cam_buf + (size_t)f0 * 4 * s->n;
                 hj.cam_dots = job.cam_dots + (size_t)f0 * 4;
+                if (job.cam_span) hj.cam_span = job.cam_span + (size_t)f0 * 2;
             }
             if (int e = enqueue(s, ds, hj)) return e;
             NtTarget rt = tg;
@@ -1954,6 +1958,7 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     NtCamera cam;
     cam.buf = job.cam_buf;
     cam.dots = job.cam_dots;
+    cam.span = job.cam_buf ? job.cam_span : nullptr;
     cam.n = s->n;
     if (!job.cam_buf) pack_camera(s->n, s->origin.data(), s->axes.data(), cam.inl);
     camera_dots(s->n, s->origin.data(), s->axes.data(), cam.odots);
@@ -3254,7 +3259,8 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
 
 struct nt_camera_table {
     int n = 0, nframes = 0, device = -1;
-    float *dev = nullptr;                // [nframes][4][n] camera rows, then [nframes][4] dot products (NtCamera::buf)
+    float *dev = nullptr;                // [nframes][4][n] camera rows, then [nframes][4] dot products (NtCamera::buf), then
+                                         // [nframes][2] spans (NtCamera::span)
 };
 
 nt_camera_table_t *nt_camera_table_create(int dimension, int nframes, const float *origins, const float *axes, int device) {
@@ -3265,9 +3271,18 @@ nt_camera_table_t *nt_camera_table_create(int dimension, int nframes, const floa
     int dev;
     if (pick_device(nullptr, device, dev)) return nullptr;
     const int n = dimension;
-    const size_t cam_floats = (size_t)nframes * 4 * n + (size_t)nframes * 4;
+    const size_t span_at = (size_t)nframes * 4 * n + (size_t)nframes * 4;
+    const size_t cam_floats = span_at + (size_t)nframes * 2;
     std::vector<float> packed(cam_floats);
     pack_cameras(n, nframes, origins, axes, packed.data());
+    // the span of every camera (nt_box_span.hpp): once here, a few microseconds each, for the 510 waves of every frame that would
+    // each work it out again in their stretch codes.  (The table does not know its scene: only BoxScene's tile kernel reads them.)
+    for (int f = 0; f < nframes; ++f) {
+        const float *o = origins + (size_t)f * n, *ax = axes + (size_t)f * n * n;
+        const NtBoxSpan sp = nt_box_strip_span(n, o, ax, ax + n, ax + 2 * n);
+        packed[span_at + 2 * (size_t)f] = sp.lo;
+        packed[span_at + 2 * (size_t)f + 1] = sp.hi;
+    }
     void *p = nullptr;
     if (hipMalloc(&p, cam_floats * sizeof(float)) != hipSuccess) { fail(NT_E_NOMEM, "hipMalloc failed for the camera table"); return nullptr; }
     if (hipMemcpy(p, packed.data(), cam_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
@@ -3312,6 +3327,7 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     FrameJob job = render_job(f, b, dest_dev, frame_stride, count, (hipStream_t)hip_stream, stats, opts, true);
     job.cam_buf = table->dev + (size_t)first * 4 * table->n;                                  // (the table: all cameras, then all dot products)
     job.cam_dots = table->dev + (size_t)table->nframes * 4 * table->n + (size_t)first * 4;
+    job.cam_span = table->dev + (size_t)table->nframes * (4 * table->n + 4) + (size_t)first * 2;
     return enqueue(s, ds, job);
 }
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <type_traits>
 #include "nt_pixel.hpp"
+#include "nt_box_span.hpp"
 
 namespace {
 
@@ -119,9 +120,7 @@ __device__ __forceinline__ void box_color(const float (&o)[N], const float (&dir
 #ifndef NT_BOX_SETS_MAX_N
 #define NT_BOX_SETS_MAX_N NT_BOX_INLINE_MAX_N
 #endif
-#ifndef NT_BOX_MARGIN
-#define NT_BOX_MARGIN 1e-5f
-#endif
+// (NT_BOX_MARGIN itself: nt_box_span.hpp, which the host's span of a camera shares it with; -DNT_BOX_MARGIN=... reaches both)
 // Which rays need the exact evaluation at all?  Everything below works on the UNNORMALISED direction v
 // (p_j(tau) = o_j + v_j*tau; the reference's dist is tau*|v|), with reciprocals from v_rcp_f32, and sorts a lane
 // that may hit into one of three classes.  m = NT_BOX_MARGIN*(1 + max|o_j|) dominates the sum of ROUNDING_FUZZ and
@@ -235,6 +234,25 @@ __device__ __forceinline__ float nt_vmin_abs(float a, float b) { float r; asm("v
 #define NT_BOX_TIE_SHORTCUT_MIN_WAVES 32768
 #endif
 #define NT_BOX_SETS_SURE 0x01000000u
+// The span of a frame (NtCamera::span, nt_box_span.hpp: a camera table's frames have one): no ray with sx outside [lo, hi] can
+// come within h of the cube at a tau > 0, whatever its row.  A wave whose column strip lies outside it -- the strip's sx runs
+// from its first pixel's to its last one's, the row phase's own fp32 expressions, which are monotonic in x -- goes around
+// box_stretch_code2 with code 0 and no sets for every lane: about 155 vector instructions, two v_rcp_f32 an axis among them,
+// that more than half of the headline call's waves spent on finding out what the camera alone decides.
+// The bytes cannot change.  A skipped strip's rows are culled rows: culled_row / put_quick behind their guard, with the
+// reference's arithmetic (box_pixel) where the guard fails -- the path of every code-0 row.  Code 0 itself only ever meant "no
+// ray of the stretch can be a hit for the reference", and that is what the span states of the whole strip, from the premise
+// box_stretch_code2 works from (with the same m and h), in double and with a slack of a sixth of a pixel.  A stretch that the
+// looser per-stretch cull used to keep and the span clears was classified ray by ray or went through box_pixel, and every ray
+// came out a miss: background, the same bytes as the culled path's (which is what the guard is for).
+// -DNT_BOX_STRIP_SPAN=0: without the test, the device code as it was: the build to measure and to test against.
+#ifndef NT_BOX_STRIP_SPAN
+#define NT_BOX_STRIP_SPAN 1
+#endif
+// (Measured with it and not taken: a counted loop of sixteen groups of four, the next group's table entries loaded ahead, for
+// waves all of whose 64 slots are culled rows.  Rotating the sixteen scalar registers of the entries costs nine s_mov_b64 a
+// group -- two sets that swap roles do not fit the scalar registers -- and the kernel ran 4 % MORE scalar instructions, at the
+// same time or 0.2 % slower: DESIGN.md 4.1.)
 template <int N>
 constexpr bool nt_box_tie_shortcut() { return NT_BOX_TIE_SHORTCUT != 0 && N >= NT_BOX_TIE_SHORTCUT_MIN_N && N <= NT_BOX_TIE_SHORTCUT_MAX_N && N <= NT_BOX_SETS_MAX_N; }
 
@@ -1162,6 +1180,21 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         dots[0] = cam.odots[0]; dots[1] = cam.odots[1]; dots[2] = cam.odots[2]; dots[3] = cam.odots[3];
     }
     const int tile_row0 = (int)blockIdx.y * WAVES * R;
+    // the strip against the frame's span (NT_BOX_STRIP_SPAN, see there): wave-uniform, two scalar loads; +-inf and NaN compare
+    // as they should (no statement: never outside; the empty interval: always)
+    // (dimensions beyond NT_BOX_SPAN_MAX_N never get a statement: their kernels go without the test)
+    bool strip_out = false;
+    if constexpr (NT_BOX_STRIP_SPAN != 0 && N <= NT_BOX_SPAN_MAX_N) {
+      if (cam.span != nullptr) {
+        const float *sp = cam.span + (size_t)frame * 2;
+        const float span_lo = sp[0], span_hi = sp[1];
+        const int x_first = (int)blockIdx.x * 64;
+        const int x_last = x_first + 63 < tg.width ? x_first + 63 : tg.width - 1;
+        // (the smaller and the larger of the two: a negative fovI turns the strip round)
+        const float sx_a = tg.fovI * ((float)x_first - tg.half_w), sx_b = tg.fovI * ((float)x_last - tg.half_w);
+        strip_out = fmaxf(sx_a, sx_b) < span_lo || fminf(sx_a, sx_b) > span_hi;
+      }
+    }
     // ---- phase 1: the tile's stretch codes, one row per lane of one wave -- a different one from block to block, so that
     // the extra work does not always land on the same SIMD of a CU
     if (REG || wv == (int)((blockIdx.x + blockIdx.y + frame) % (unsigned)WAVES)) {
@@ -1174,7 +1207,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         uint32_t row_sets = 0u;
         // lane <-> slot tile_row0 + lane = row rr of wave w; interleaved: that wave's rr-th row is w + W * rr (NtTarget::row_il)
         const int trow = tg.row_il > 0 ? ((int)blockIdx.y * WAVES + lane / R) + tg.row_il * (lane % R) : tile_row0 + lane;
-        if (lane < WAVES * R && trow < tg.row_count) {
+        if (!strip_out && lane < WAVES * R && trow < tg.row_count) {
             const int orow = tg.row_begin + trow;
             const int y = nt_image_row(tg, orow);
             if (y < tg.height) {
@@ -1613,6 +1646,7 @@ int launch_box_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget
     NtCameraFixed cf;
     cf.buf = cam.buf;
     cf.dots = cam.dots;
+    cf.span = cam.buf ? cam.span : nullptr;
     for (int k = 0; k < 4; ++k) cf.odots[k] = cam.odots[k];
     cf.n = N;
     for (int k = 0; k < 4 * N; ++k) cf.inl[k] = cam.inl[k];

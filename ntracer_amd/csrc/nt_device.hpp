@@ -91,6 +91,9 @@ struct NtTarget {
 struct NtCamera {
     const float *buf;         // nullptr => use `inl`; else [nframes][4][n] cameras of the launch's frames
     const float *dots;        // with buf: [nframes][4] dot products of the same frames (|o|^2, o.right, o.up, o.forward)
+    // with buf, or nullptr: [nframes][2], sx_lo and sx_hi of the same frames -- outside them no ray of the frame can hit BoxScene's
+    // cube (nt_box_span.hpp; box_tile_kernel, NT_BOX_STRIP_SPAN).  Only a camera table has them: nullptr says nothing about any frame.
+    const float *span = nullptr;
     int n;
     float odots[4];
     float inl[4 * NT_DEV_MAX_DIM];
@@ -98,6 +101,7 @@ struct NtCamera {
 struct NtCameraFixed {        // N <= 8: 4*8 floats inline
     const float *buf;
     const float *dots;
+    const float *span = nullptr;   // (NtCamera::span)
     int n;
     float odots[4];
     float inl[4 * NT_DEV_MAX_FIXED_BOX];

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def measure(world, rank, band_rows, steps, warmup, frames=160, n=6, W=1920, H=1080, f32=False, overlapped=False):
+def measure(world, rank, band_rows, steps, warmup, frames=160, n=6, W=1920, H=1080, f32=False, overlapped=False, table=False):
     import torch
     import ntracer_amd
     from ntracer_amd import _lib, tracern
@@ -48,7 +48,17 @@ def measure(world, rank, band_rows, steps, warmup, frames=160, n=6, W=1920, H=10
     st = torch.cuda.current_stream()
     L = _lib.lib()
 
+    # table: the cameras resident in device memory (nt_camera_table_create, as bench.py's headline call has them -- and with them
+    # the cameras' spans, nt_box_span.hpp); otherwise host cameras, staged by every call
+    tab = L.nt_camera_table_create(n, frames, origins.ctypes.data_as(_lib.f32p), axes.ctypes.data_as(_lib.f32p), torch.cuda.current_device()) if table else None
+    if table and not tab:
+        raise RuntimeError(_lib.last_error())
+
     def go():
+        if table:
+            _lib.check(L.nt_render_table_device(scene._handle, C.c_void_p(fb.data_ptr()), own * fmt.pitch, C.c_void_p(tab), 0, frames, C.byref(fst),
+                                                C.byref(opts), C.c_void_p(st.cuda_stream)))
+            return
         _lib.check(L.nt_render_frames_device(scene._handle, C.c_void_p(fb.data_ptr()), own * fmt.pitch, frames,
                                              origins.ctypes.data_as(_lib.f32p), axes.ctypes.data_as(_lib.f32p), C.byref(fst), C.byref(opts),
                                              C.c_void_p(st.cuda_stream)))
@@ -65,7 +75,9 @@ def measure(world, rank, band_rows, steps, warmup, frames=160, n=6, W=1920, H=10
     t_issue = time.perf_counter() - t0
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    return {"format": "rgbf32" if f32 else "rgbx8", "n": n, "world": world, "rank": rank, "band_rows": band_rows, "owned_rows": own, "frames": frames,
+    if table:
+        L.nt_camera_table_destroy(C.c_void_p(tab))
+    return {"cameras": "table" if table else "host", "format": "rgbf32" if f32 else "rgbx8", "n": n, "world": world, "rank": rank, "band_rows": band_rows, "owned_rows": own, "frames": frames,
             "event_us_per_call": round(e0.elapsed_time(e1) * 1e3 / steps, 2), "wall_us_per_call": round(wall * 1e6 / steps, 2),
             "host_issue_us_per_call": round(t_issue * 1e6 / steps, 2)}
 
@@ -80,6 +92,7 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=160)
     ap.add_argument("--n", type=int, default=6)
     ap.add_argument("--f32", action="store_true")
+    ap.add_argument("--table", action="store_true", help="the cameras in a camera table (nt_render_table_device) instead of host cameras")
     ap.add_argument("--overlapped", action="store_true", help="nt_render_opts.overlapped = 1: the launch shape of the two-stream legs")
     a = ap.parse_args()
-    print(json.dumps(measure(a.world, a.rank, a.band_rows, a.steps, a.warmup, frames=a.frames, n=a.n, f32=a.f32, overlapped=a.overlapped)))
+    print(json.dumps(measure(a.world, a.rank, a.band_rows, a.steps, a.warmup, frames=a.frames, n=a.n, f32=a.f32, overlapped=a.overlapped, table=a.table)))

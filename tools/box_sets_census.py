@@ -167,6 +167,102 @@ def _stretch(origin, axes, w, h, fov=0.8, rows=None, limit=TIE_SURE_MAX_ORIGIN):
     return code.reshape(len(ys), ncols), sets.reshape(len(ys), ncols), sure.reshape(len(ys), ncols)
 
 
+SPAN_MAX_N = 10             # NT_BOX_SPAN_MAX_N
+SPAN_SLACK = 1e-4           # NT_BOX_SPAN_SLACK
+SPAN_TAU_MIN = 1e-3         # NT_BOX_SPAN_TAU_MIN
+SPAN_NONE = (F(-np.inf), F(np.inf))
+SPAN_EMPTY = (F(np.inf), F(-np.inf))
+
+
+def strip_span(origin, axes):
+    """nt_box_strip_span (ntracer_amd/csrc/nt_box_span.hpp) in numpy, float64: the interval (lo, hi) of sx outside which no ray of
+    the camera comes within h of the cube at a tau > 0 -- the extremes of a / tau over the vertices of
+    P = { -h - o_j <= tau fwd_j + a right_j - b up_j <= h - o_j } -- as two fp32 numbers.  SPAN_NONE (-inf, inf): no statement;
+    SPAN_EMPTY (inf, -inf): no ray at all."""
+    import itertools
+    org = np.asarray(origin, F)
+    ax = np.asarray(axes, F)
+    n = len(org)
+    if n < 3 or n > SPAN_MAX_N or not (np.isfinite(org).all() and np.isfinite(ax[:3]).all()):
+        return SPAN_NONE
+    right, up, fwd = (ax[k].astype(np.float64) for k in range(3))
+    m = _margin(org)
+    h = np.float64(F(F(F(1.0) + F(F(2.0) * m)) + F(1e-3)))
+    omax = np.float64(np.max(np.abs(org)))
+    c = np.stack([fwd, right, -up], 1)                       # [n][3]
+    lo_b, hi_b = -h - org.astype(np.float64), h - org.astype(np.float64)
+    length = np.sqrt((c * c).sum(1))
+
+    def rel_of(i, j, k):
+        # (the C++ function's det3, operation for operation: whether a determinant is zero AS COMPUTED decides here)
+        a, b, d = c[i], c[j], c[k]
+        det = a[0] * (b[1] * d[2] - b[2] * d[1]) - a[1] * (b[0] * d[2] - b[2] * d[0]) + a[2] * (b[0] * d[1] - b[1] * d[0])
+        with np.errstate(all="ignore"):
+            r = abs(det) / (length[i] * length[j] * length[k])
+        return 0.0 if np.isnan(r) else r
+    # an axis that forms a badly conditioned triple with two axes already taken is left out, constraint and all: a larger P
+    keep = []
+    for q in range(n):
+        if not any(0.0 < rel_of(i, j, q) < 1e-6 for i, j in itertools.combinations(keep, 2)):
+            keep.append(q)
+    c, lo_b, hi_b, length = c[keep], lo_b[keep], hi_b[keep], length[keep]
+    n = len(keep)
+    gram = c.T @ c
+    gscale = gram[0, 0] * gram[1, 1] * gram[2, 2]
+    diag = np.diag(gram)
+    if not (gscale > 0 and diag.min() >= 1e-6 * diag.max() and np.linalg.det(gram) > 1e-6 * gscale):
+        return SPAN_NONE
+    tri = np.array(list(itertools.combinations(range(n), 3)))
+    mats = c[tri]                                             # [t][3][3]
+    with np.errstate(all="ignore"):
+        rel = np.abs(np.linalg.det(mats)) / length[tri].prod(1)
+    good = np.where(np.isnan(rel), 0.0, rel) >= 1e-9        # (among the axes kept: at least 1e-6, or zero up to rounding)
+    tri, mats = tri[good], mats[good]
+    if len(tri) == 0:
+        return SPAN_EMPTY
+    side = np.array(list(itertools.product((0, 1), repeat=3)))                      # [8][3]
+    rhs = np.where(side[None, :, :] == 1, hi_b[tri][:, None, :], lo_b[tri][:, None, :])   # [t][8][3]
+    pts = np.linalg.solve(mats[:, None, :, :], rhs[..., None])[..., 0]              # [t][8][3]: tau, a, b
+    val = pts @ c.T                                                                  # [t][8][n]
+    tol = 1e-7 * (h + omax)
+    own = np.zeros((len(tri), 1, n), bool)
+    np.put_along_axis(own, tri[:, None, :], True, 2)
+    inside = (own | ((val >= lo_b - tol) & (val <= hi_b + tol))).all(2)
+    v = pts[inside]
+    if len(v) == 0 or v[:, 0].max() <= -SPAN_TAU_MIN:
+        return SPAN_EMPTY
+    if not v[:, 0].min() > SPAN_TAU_MIN:
+        return SPAN_NONE
+    sx = v[:, 1] / v[:, 0]
+    lo, hi = sx.min(), sx.max()
+    lo -= SPAN_SLACK * (1.0 + abs(lo))
+    hi += SPAN_SLACK * (1.0 + abs(hi))
+    flo, fhi = F(lo), F(hi)
+    if np.float64(flo) > lo:
+        flo = np.nextafter(flo, F(-np.inf))
+    if np.float64(fhi) < hi:
+        fhi = np.nextafter(fhi, F(np.inf))
+    return flo, fhi
+
+
+def strip_sx(w, col, fov=0.8):
+    """the sx of the first and of the last pixel of column strip `col` of a w-wide frame, as box_tile_kernel forms them"""
+    half_w, _, fovI = screen(w, 1, fov)
+    x0, x1 = col * 64, min(col * 64 + 63, w - 1)
+    return F(fovI * F(F(x0) - half_w)), F(fovI * F(F(x1) - half_w))
+
+
+def strips_kept(origin, axes, w, fov=0.8):
+    """which of the ceil(w / 64) column strips box_tile_kernel's span test keeps: bool [ncols]"""
+    lo, hi = strip_span(origin, axes)
+    ncols = (w + 63) // 64
+    out = np.ones(ncols, bool)
+    for col in range(ncols):
+        s0, s1 = strip_sx(w, col, fov)
+        out[col] = not (max(s0, s1) < lo or min(s0, s1) > hi)
+    return out
+
+
 def popcount(x):
     x = np.asarray(x, np.uint32)
     return sum(((x >> np.uint32(k)) & 1).astype(np.int64) for k in range(10))

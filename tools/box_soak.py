@@ -62,9 +62,15 @@ def main():
             opts.overlapped = int(os.environ.get("OVERLAPPED", "0"))
             own = ntd.owned_rows(h, rank, world, brows)
         fb = torch.zeros((per_dim, len(own) * fmt.pitch), dtype=torch.uint8, device="cuda")
-        _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(fb.data_ptr()), len(own) * fmt.pitch, per_dim,
-                                                      o.ctypes.data_as(_lib.f32p), a.ctypes.data_as(_lib.f32p), C.byref(st), C.byref(opts) if opts is not None else None,
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if os.environ.get("TABLE"):
+            # TABLE=1: the cameras in a camera table (nt_render_table_device: the frames carry their spans, nt_box_span.hpp)
+            tab = ntracer_amd.render.CameraTable(n, o, a, device=torch.cuda.current_device())
+            _lib.check(_lib.lib().nt_render_table_device(sc._handle, C.c_void_p(fb.data_ptr()), len(own) * fmt.pitch, tab._h, 0, per_dim, C.byref(st),
+                                                         C.byref(opts) if opts is not None else None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        else:
+            _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(fb.data_ptr()), len(own) * fmt.pitch, per_dim,
+                                                          o.ctypes.data_as(_lib.f32p), a.ctypes.data_as(_lib.f32p), C.byref(st), C.byref(opts) if opts is not None else None,
+                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         torch.cuda.synchronize()
         got = fb.cpu().numpy().reshape(per_dim, len(own), fmt.pitch)
         osc = ob.OracleScene(n, o[0], a[0])
