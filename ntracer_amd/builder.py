@@ -141,11 +141,16 @@ def vertices_of_many(recs, n):
 
 def solid_bounds(type_cube, position, orientation):
     """World-space bounding box of a Solid: x = orientation * (u + position), u in [-1,1]^n (cube) or
-    |u| <= 1 (sphere) -- solid::intersects (tracer.hpp:257-260) read backwards."""
+    |u| <= 1 (sphere) -- solid::intersects (tracer.hpp:257-260) read backwards.  Computed in float64 and rounded to fp32
+    OUTWARD: a cast to nearest could leave the box half an ulp short of the Solid."""
     o = np.asarray(orientation, np.float64)
     c = o @ np.asarray(position, np.float64)
     ext = np.abs(o).sum(axis=1) if type_cube else np.sqrt((o * o).sum(axis=1))
-    return (c - ext).astype(f32), (c + ext).astype(f32)
+    lo64, hi64 = c - ext, c + ext
+    lo, hi = lo64.astype(f32), hi64.astype(f32)
+    lo = np.where(lo > lo64, np.nextafter(lo, f32(-np.inf)), lo).astype(f32)
+    hi = np.where(hi < hi64, np.nextafter(hi, f32(np.inf)), hi).astype(f32)
+    return lo, hi
 
 
 class _Item(object):
