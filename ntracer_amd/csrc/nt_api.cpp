@@ -1115,6 +1115,160 @@ int enqueue_supersampled(nt_scene *s, DeviceState *ds, const FrameJob &job) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// the whole-view settings -- clip planes, depth cues, outlines, ambient occlusion, BoxScene's face lines --
+// and what their passes and the adaptive one share
+// ---------------------------------------------------------------------------------------------
+int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_hit_buffers *out, long long frame_stride, const float *cam_buf,
+                 int nframes, bool strict, const int *abort_word, hipStream_t stream);
+
+// A setting whose render comes from a pass over the records of the whole pinhole view, one sample a pixel, no kernel of which
+// keeps counters.  The table is in the order of precedence: a scene with two of them on is refused by the one nearer the top,
+// in `while_on`'s words of the other, not drawn with one of them missing.  Face lines are BoxScene's: they neither refuse the
+// composite settings nor are refused by them (no `while_on`).  The next setting is one more row, and one more line of enqueue.
+struct ViewSetting {
+    bool (*on)(const nt_scene *s);
+    const char *subject;                 // of every message: "<subject> not available ..."
+    const char *band_suffix;             // what the row-band message adds
+    const char *while_on;                // how the rows above name this setting when they refuse it
+    int (*extra)(const nt_scene *s);     // a term of its own, after all the others, or nullptr
+};
+enum { VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_COUNT };
+const ViewSetting kViewSettings[VS_COUNT] = {
+    {[](const nt_scene *s) { return s->clip_count > 0; }, "clip planes are", "", nullptr,
+     // a Solid cut open needs a cap or an inner wall, which nothing defines: refused, not approximated
+     [](const nt_scene *s) {
+         return s->n_solids > 0 ? fail(NT_E_UNSUPPORTED, "clip planes are not available for a scene with Solids (a Solid cut open has no cap)") : (int)NT_OK;
+     }},
+    {[](const nt_scene *s) { return s->cue; }, "depth cues are", "", "depth cues are on", nullptr},
+    {[](const nt_scene *s) { return s->outlines; }, "outlines are", ": a pixel's mask needs its neighbours", "outlines are on", nullptr},
+    {[](const nt_scene *s) { return s->ao_count > 0; }, "ambient occlusion is", "", "ambient occlusion is on", nullptr},
+    {[](const nt_scene *s) { return s->box_lines && !s->composite; }, "face lines are", ": a pixel's mask needs its neighbours", nullptr, nullptr},
+};
+
+// What a render with the setting of `row` on refuses, checked by the entry points before a device is touched (render_checks) and
+// by the setting's enqueue again, for every way in.  The entry points hand over whole images: without bands their owned rows are
+// all of them, so the row-range answer cannot be reached through the ABI; it guards the enqueues against callers within this
+// file that split a job into rows.
+int whole_view_check(const nt_scene *s, const ViewSetting &row, const Bands &b, bool stats, int row_begin, int row_count, int height) {
+    if (!row.on(s)) return NT_OK;
+    const char *w = row.subject;
+    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "%s not available with a supersampling factor above 1 (%d)", w, s->supersampling);
+    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "%s not available with row bands (band_world %d)%s", w, b.world, row.band_suffix);
+    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "%s not available for a row range", w);
+    if (stats) return fail(NT_E_UNSUPPORTED, "%s not available with collect_stats", w);
+    if (s->lens) return fail(NT_E_UNSUPPORTED, "%s not available while a lens is set", w);
+    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "%s not available while the parallel projection is set", w);
+    // the settings further down the table, from the last to the first
+    for (const ViewSetting *below = kViewSettings + VS_COUNT - 1; below > &row; --below)
+        if (below->while_on && below->on(s)) return fail(NT_E_UNSUPPORTED, "%s not available while %s", w, below->while_on);
+    return row.extra ? row.extra(s) : (int)NT_OK;
+}
+
+// What such a pass starts from.  With job.fmt it is a render; without, the setting's buffer alone, of one view of job.view_w x
+// job.view_h.
+struct ViewPass {
+    bool draw;
+    bool nothing;                        // a render into a format without bytes: nothing to draw
+    int W, H;
+    long long px, px_limit;              // the view's pixels, and how many the kernels address
+    NtTarget tg;                         // the caller's image (fill_target), or the whole view (view_target)
+    Format bf;                           // plain fp32 x 3 of W x H: the base frame that a stage draws into scratch
+};
+
+// `row`: the setting whose check the job must pass (nullptr: none).  `noun` is the pass as its refusals name it.
+int begin_view_pass(const nt_scene *s, DeviceState *ds, const FrameJob &job, const ViewSetting *row, const char *noun, ViewPass &vp,
+                    long long px_limit = INT_MAX, const char *beyond = "beyond 2^31 - 1 pixels") {
+    vp.draw = job.fmt != nullptr;
+    vp.W = vp.draw ? job.fmt->width : job.view_w;
+    vp.H = vp.draw ? job.fmt->height : job.view_h;
+    if (row) {
+        if (int r = whole_view_check(s, *row, job.bands, job.stats, vp.draw ? job.row_begin : 0, vp.draw ? job.row_count : vp.H, vp.H)) return r;
+    }
+    vp.nothing = vp.draw && job.fmt->bpp == 0;
+    if (vp.nothing) return NT_OK;
+    vp.px = (long long)vp.W * vp.H;
+    vp.px_limit = px_limit;
+    if (vp.px > px_limit) return fail(NT_E_UNSUPPORTED, "%s of a %d x %d image: %s", noun, vp.W, vp.H, beyond);
+    if (vp.draw) {
+        if (int r = fill_target(s, ds, job, vp.tg)) return r;
+    } else {
+        view_target(s, vp.W, vp.H, job.abort_word, vp.tg);
+    }
+    return plain_f32_format(vp.W, vp.H, vp.bf);
+}
+
+// The whole frames of a chunk of the pass, whose scratch of `per_frame` bytes a frame sits under `cap`, the supersampling cap: as
+// many as fit, as the kernels' pixel indices reach and as `limit` allows, at least one.  `parts`: what one frame holds, where the
+// refusal lists it.
+int plan_scratch_frames(const ViewPass &vp, int nframes, const char *noun, const char *parts, long long per_frame, long long cap,
+                        long long limit, long long &chunk_frames) {
+    if (per_frame > cap)
+        return fail(NT_E_UNSUPPORTED, "%s of a %d x %d image: %s (%lld bytes) %s not fit the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)",
+                    noun, vp.W, vp.H, parts ? parts : "the scratch of one frame", per_frame, parts ? "do" : "does", cap >> 20);
+    chunk_frames = std::max<long long>(1, std::min<long long>(std::min<long long>(nframes, cap / per_frame), std::min<long long>(vp.px_limit / vp.px, limit)));
+    return NT_OK;
+}
+
+// the scratch of a pass (DeviceState::samples), handed out front to back
+struct Scratch {
+    char *at = nullptr;
+    int open(DeviceState *ds, size_t bytes) {
+        if (int e = ds->samples.ensure(bytes)) return e;
+        at = (char *)ds->samples.p;
+        return NT_OK;
+    }
+    template <typename T>
+    T *take(size_t bytes) {
+        T *p = (T *)at;
+        at += bytes;
+        return p;
+    }
+};
+
+// frames [f0, f0 + nf) of the job: what their launchers are told, their target -- of a render, the caller's frames from f0 on --
+// and their cameras in the caller's table (nullptr: the scene's own)
+struct ViewChunk {
+    int f0, nf;
+    NtLaunchInfo li;
+    NtTarget ft;
+    const float *cams;
+};
+
+ViewChunk view_chunk(const nt_scene *s, const DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, const ViewPass &vp, int f0,
+                     long long chunk_frames) {
+    ViewChunk ch;
+    ch.f0 = f0;
+    ch.nf = (int)std::min<long long>(chunk_frames, job.nframes - f0);
+    ch.li = launch_info(s, ds, sw, ch.nf, job.stream);
+    ch.ft = vp.tg;
+    if (vp.draw) ch.ft.dest = vp.tg.dest + (long long)f0 * vp.tg.frame_stride;
+    ch.cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * s->n : nullptr;
+    return ch;
+}
+
+// the packet walk's plane numerators and quad order, as hits_enqueue hands them over, and with `recs` the records' place
+int packet_records(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, int W, int H, int nf, void *recs, NtLaunchInfo &li) {
+    if (int e = numerator_scratch(s, ds, sw, nf, li)) return e;
+    if (sw.tile_order) {
+        if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
+    }
+    if (recs) {
+        li.hit_buf = recs;
+        li.hit_frames = nf;
+    }
+    return NT_OK;
+}
+
+// off the packet walk: the chunk's plain fp32 x 3 base frame into `base` (a render only), then its primary-hit pass into `hb`, both
+// in scratch -- every route of a plain render and of hits_enqueue comes with them
+int base_and_hits(nt_scene *s, DeviceState *ds, const FrameJob &job, const ViewPass &vp, const ViewChunk &ch, void *base, const nt_hit_buffers &hb) {
+    if (vp.draw) {
+        if (int e = enqueue(s, ds, base_frame_job(s, job, vp.bf, ch.f0, ch.nf, base, (size_t)vp.px * 12))) return e;
+    }
+    return hits_enqueue(s, ds, vp.W, vp.H, &hb, vp.px, ch.cams, ch.nf, job.strict, job.abort_word, job.stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // adaptive supersampling (nt_scene_set_adaptive_supersampling; kernels in nt_adaptive.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 int rays_scene(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, bool strict, long long count, long long lpb_fixed, long long max_fixed,
@@ -1123,11 +1277,15 @@ int rays_scene(const nt_scene *s, DeviceState *ds, const RenderSwitches &sw, boo
 // What an adaptive render refuses, checked by the entry points before a device is touched (and by enqueue_adaptive again, for
 // every way in): the contrast of a pixel needs its neighbours, which another rank's band holds, and the refine kernels keep no
 // counters
-int adaptive_check(const nt_scene *s, const Bands &b, bool stats) {
-    if (!s->adaptive || s->supersampling <= 1) return NT_OK;
+int adaptive_refusals(const Bands &b, bool stats) {
     if (b.world > 1) return fail(NT_E_UNSUPPORTED, "row bands (band_world %d) are not available with adaptive supersampling: a pixel's contrast needs its neighbours", b.world);
     if (stats) return fail(NT_E_UNSUPPORTED, "collect_stats is not available with adaptive supersampling");
     return NT_OK;
+}
+
+int adaptive_check(const nt_scene *s, const Bands &b, bool stats) {
+    if (!s->adaptive || s->supersampling <= 1) return NT_OK;
+    return adaptive_refusals(b, stats);
 }
 
 // An adaptive render, in three stages per chunk of whole frames (nt_adaptive.hpp): the job once more in the plain fp32 x 3 format
@@ -1137,40 +1295,34 @@ int adaptive_check(const nt_scene *s, const Bands &b, bool stats) {
 // bytes a pixel a frame, and one more for `mask_scratch`, the host form's mask -- sits under the supersampling cap.  Enqueue only.
 int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, uint8_t *mask_dev, bool mask_scratch,
                      uint8_t **mask_out) {
-    const bool draw = job.fmt != nullptr;
+    const char *noun = "adaptive supersampling";
     const int ss = s->supersampling;
-    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
-    if (job.bands.world > 1) return fail(NT_E_UNSUPPORTED, "row bands (band_world %d) are not available with adaptive supersampling: a pixel's contrast needs its neighbours", job.bands.world);
-    if (job.stats) return fail(NT_E_UNSUPPORTED, "collect_stats is not available with adaptive supersampling");
-    if (draw && (job.row_begin != 0 || job.row_count != H)) return fail(NT_E_UNSUPPORTED, "a row range is not available with adaptive supersampling");
-    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
-    const long long px = (long long)W * H;
-    const long long cap = (long long)s->ss_scratch_mb << 20;
+    if (int r = adaptive_refusals(job.bands, job.stats)) return r;
+    if (job.fmt && (job.row_begin != 0 || job.row_count != job.fmt->height)) return fail(NT_E_UNSUPPORTED, "a row range is not available with adaptive supersampling");
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, nullptr, noun, vp, INT_MAX / 4, "more pixels than the list of flagged pixels addresses")) return r;
+    if (vp.nothing) return NT_OK;
+    const bool draw = vp.draw;
+    const int W = vp.W, H = vp.H;
+    const long long px = vp.px;
     const long long per_frame = px * (mask_scratch ? 17 : 16);
-    if (px > INT_MAX / 4) return fail(NT_E_UNSUPPORTED, "adaptive supersampling of a %d x %d image: more pixels than the list of flagged pixels addresses", W, H);
-    if (per_frame > cap)
-        return fail(NT_E_UNSUPPORTED, "adaptive supersampling of a %d x %d image: the base frame and the list of one frame (%lld bytes) do not fit "
-                    "the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    long long chunk_frames;
+    if (int r = plan_scratch_frames(vp, job.nframes, noun, "the base frame and the list of one frame", per_frame, (long long)s->ss_scratch_mb << 20,
+                                    LLONG_MAX, chunk_frames)) return r;
     if (draw && ((long long)ss * W > INT_MAX / 12 || (long long)ss * H > INT_MAX))
         return fail(NT_E_UNSUPPORTED, "supersampling %d of a %d x %d image: beyond the views the kernels address", ss, W, H);
-    const int chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame), (INT_MAX / 4) / px));
-    if (int e = ds->samples.ensure((size_t)chunk_frames * per_frame)) return e;
+    Scratch at;
+    if (int e = at.open(ds, (size_t)chunk_frames * per_frame)) return e;
     if (int e = ds->refine_count.ensure(64)) return e;
-    char *scratch = (char *)ds->samples.p;
-    uint32_t *list = (uint32_t *)(scratch + (size_t)chunk_frames * px * 12);
-    if (mask_scratch) mask_dev = (uint8_t *)(scratch + (size_t)chunk_frames * px * 16);
+    const size_t fpx = (size_t)chunk_frames * px;
+    char *scratch = at.take<char>(fpx * 12);
+    uint32_t *list = at.take<uint32_t>(fpx * 4);
+    if (mask_scratch) mask_dev = at.take<uint8_t>(fpx);
     if (mask_out) *mask_out = mask_dev;
-    Format bf;
-    if (int r = plain_f32_format(W, H, bf)) return r;
-    NtTarget tg;
-    if (draw) {
-        if (int r = fill_target(s, ds, job, tg)) return r;
-    } else {
-        view_target(s, W, H, job.abort_word, tg);
-    }
-    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
-        const int nf = std::min(chunk_frames, job.nframes - f0);
-        const FrameJob bj = base_frame_job(s, job, bf, f0, nf, scratch, (size_t)px * 12);
+    for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
+        const ViewChunk ch = view_chunk(s, ds, job, sw, vp, f0, chunk_frames);
+        const int nf = ch.nf;
+        const FrameJob bj = base_frame_job(s, job, vp.bf, f0, nf, scratch, (size_t)px * 12);
         if (int e = enqueue(s, ds, bj)) return e;
         NtAdaptive ad{};
         ad.base = (const uint32_t *)scratch;
@@ -1180,8 +1332,7 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
         ad.count = (int *)ds->refine_count.p;
         ad.mask = mask_dev ? mask_dev + (size_t)f0 * px : nullptr;
         ad.draw = draw ? 1 : 0;
-        NtTarget ft = tg;
-        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        NtTarget ft = ch.ft;
         if (int r = nt_launch_adaptive_flag(job.stream, ad, ft)) return launch_failed(r);
         if (!draw || ss <= 1) continue;
         NtRefine rf{};
@@ -1200,12 +1351,11 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
         // consecutive lanes hold the list's pixels, not the aligned groups of one row that emit_pixel's shared dword stores of
         // 3- and 6-byte pixels count on: those formats go out pixel by pixel (as rays_image_target has it)
         if (ft.bpp == 3 || ft.bpp == 6) ft.aligned4 = 0;
-        const NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
         NtCompositeDev c;
         if (s->composite) {
             if (int e = rays_scene(s, ds, sw, job.strict, rf.max_count, 64, 4096, c)) return e;
         }
-        if (int r = nt_launch_refine(li, s->composite ? &c : nullptr, rf, ft)) return launch_failed(r);
+        if (int r = nt_launch_refine(ch.li, s->composite ? &c : nullptr, rf, ft)) return launch_failed(r);
     }
     return NT_OK;
 }
@@ -1213,24 +1363,7 @@ int enqueue_adaptive(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 // ---------------------------------------------------------------------------------------------
 // ambient occlusion (nt_scene_set_ambient_occlusion; kernels in nt_ao.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
-int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_hit_buffers *out, long long frame_stride, const float *cam_buf,
-                 int nframes, bool strict, const int *abort_word, hipStream_t stream);
 int query_enqueue(nt_scene *s, DeviceState *ds, NtQuery &q, bool strict, hipStream_t stream);
-
-// What a render with the setting on refuses, checked by the entry points before a device is touched (and by enqueue_ao again, for
-// every way in): the counts come from a primary-hit pass of the whole pinhole view, one sample a pixel, and no kernel of it
-// keeps counters.  The entry points hand over whole images: without bands their owned rows are all of them, so the row-range
-// answer cannot be reached through the ABI; it guards enqueue_ao against callers within this file that split a job into rows
-int ao_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
-    if (s->ao_count <= 0) return NT_OK;
-    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available with a supersampling factor above 1 (%d)", s->supersampling);
-    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available with row bands (band_world %d)", b.world);
-    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available for a row range");
-    if (stats) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available with collect_stats");
-    if (s->lens) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available while a lens is set");
-    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "ambient occlusion is not available while the parallel projection is set");
-    return NT_OK;
-}
 
 // The blocked counts of every pixel of the job's frames and, with job.fmt, the render that uses them, per chunk of whole frames:
 // the plain fp32 x 3 base frame into scratch (a render only), a primary-hit pass with normals into scratch (hits_enqueue: every
@@ -1240,22 +1373,21 @@ int ao_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int r
 // The scratch -- per pixel and frame 16 bytes of record, 8 n of normal rows, 12 of base frame and 4 of count; on the ray route
 // 8 n + 32 bytes a ray of a chunk behind them -- sits under the supersampling cap.  Enqueue only.
 int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, int *blocked_dev, int **blocked_out) {
-    const bool draw = job.fmt != nullptr;
-    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
-    if (int r = ao_check(s, job.bands, job.stats, draw ? job.row_begin : 0, draw ? job.row_count : H, H)) return r;
-    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
-    const int n = s->n, K = s->ao_count;
-    const long long px = (long long)W * H;
+    const char *noun = "ambient occlusion";
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, &kViewSettings[VS_AO], noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const bool draw = vp.draw;
+    const int W = vp.W, H = vp.H, n = s->n, K = s->ao_count;
+    const long long px = vp.px;
     const long long cap = (long long)s->ss_scratch_mb << 20;
     const long long per_frame = px * (16 + 8 * n + 12 + 4);
-    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
-    if (per_frame > cap)
-        return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d x %d image: the base frame, the hit records, the normal rows and the counts of one "
-                    "frame (%lld bytes) do not fit the scratch buffer of %lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
+    long long chunk_frames;
+    if (int r = plan_scratch_frames(vp, job.nframes, noun, "the base frame, the hit records, the normal rows and the counts of one frame", per_frame, cap,
+                                    LLONG_MAX, chunk_frames)) return r;
     // the opaque scenes the fixed-n kernels draw have a counting kernel of their own; every other scene takes the ray route
     const CompositeRoute rt = composite_route(s, sw);
     const bool fast = !rt.faithful && !rt.var;
-    long long chunk_frames = std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame), INT_MAX / px));
     // the ray route: the rays of whole pixel rows behind the frames, 16-byte aligned
     const long long row_bytes = (long long)W * K * (8 * n + 32);
     long long chunk_rows = 0;
@@ -1267,38 +1399,28 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
         chunk_rows = std::min<long long>(std::min<long long>((cap - 16 - chunk_frames * per_frame) / row_bytes, chunk_frames * H), INT_MAX / ((long long)W * K));
         if (chunk_rows < 1) return fail(NT_E_UNSUPPORTED, "ambient occlusion of a %d pixel wide image with %d samples: beyond 2^31 - 1 rays a pixel row", W, K);
     }
-    if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame + (fast ? 0 : 16 + chunk_rows * row_bytes)))) return e;
+    Scratch at;
+    if (int e = at.open(ds, (size_t)(chunk_frames * per_frame + (fast ? 0 : 16 + chunk_rows * row_bytes)))) return e;
     const size_t fpx = (size_t)chunk_frames * px;
-    char *at = (char *)ds->samples.p;
-    void *recs = at; at += fpx * 16;
-    float *no = (float *)at; at += fpx * n * 4;
-    float *nd = (float *)at; at += fpx * n * 4;
-    char *base = at; at += fpx * 12;
-    int *counts = (int *)at; at += fpx * 4;
-    char *rays = (char *)(((uintptr_t)at + 15) & ~(uintptr_t)15);
+    void *recs = at.take<void>(fpx * 16);
+    float *no = at.take<float>(fpx * n * 4);
+    float *nd = at.take<float>(fpx * n * 4);
+    char *base = at.take<char>(fpx * 12);
+    int *counts = at.take<int>(fpx * 4);
+    char *rays = (char *)(((uintptr_t)at.at + 15) & ~(uintptr_t)15);
     if (!draw && blocked_dev) counts = blocked_dev;
     if (blocked_out) *blocked_out = counts;
-    NtTarget tg;
-    if (draw) {
-        if (int r = fill_target(s, ds, job, tg)) return r;
-    } else {
-        view_target(s, W, H, job.abort_word, tg);
-    }
-    Format bf;
-    if (int r = plain_f32_format(W, H, bf)) return r;
+    const NtTarget &tg = vp.tg;
     for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
-        const int nf = std::min((int)chunk_frames, job.nframes - f0);
-        const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
-        if (draw) {
-            if (int e = enqueue(s, ds, base_frame_job(s, job, bf, f0, nf, base, (size_t)px * 12))) return e;
-        }
+        const ViewChunk ch = view_chunk(s, ds, job, sw, vp, f0, chunk_frames);
+        const int nf = ch.nf;
         nt_hit_buffers hb{};
         hb.hits = (nt_ray_hit *)recs;
         hb.normal_origin = no;
         hb.normal_dir = nd;
-        if (int e = hits_enqueue(s, ds, W, H, &hb, px, cams, nf, job.strict, job.abort_word, job.stream)) return e;
+        if (int e = base_and_hits(s, ds, job, vp, ch, base, hb)) return e;
         NtAo ao{};
-        ao.cams = cams ? cams : (const float *)ds->cams.p;              // (hits_enqueue has put the scene's own camera there)
+        ao.cams = ch.cams ? ch.cams : (const float *)ds->cams.p;        // (hits_enqueue has put the scene's own camera there)
         ao.nframes = nf;
         ao.recs = recs;
         ao.normal_origin = no;
@@ -1308,7 +1430,7 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
         ao.radius = s->ao_radius;
         ao.bias = s->ao_bias;
         ao.blocked = counts;
-        const NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
+        const NtLaunchInfo &li = ch.li;
         if (fast) {
             NtCompositeDev c;
             scene_dev(s, ds, sw, job.strict, false, c);
@@ -1344,9 +1466,7 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
             }
         }
         if (draw) {
-            NtTarget ft = tg;
-            ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
-            if (int r = nt_launch_ao_apply(job.stream, (const uint32_t *)base, counts, K, s->ao_strength, nf, ft)) return launch_failed(r);
+            if (int r = nt_launch_ao_apply(job.stream, (const uint32_t *)base, counts, K, s->ao_strength, nf, ch.ft)) return launch_failed(r);
         }
     }
     return NT_OK;
@@ -1359,22 +1479,6 @@ int enqueue_ao(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSw
 static_assert(NT_OUTLINE_SILHOUETTE == NT_DEV_OUTLINE_SILHOUETTE && NT_OUTLINE_CREASE == NT_DEV_OUTLINE_CREASE &&
               NT_OUTLINE_DEPTH == NT_DEV_OUTLINE_DEPTH, "the mask bits of the ABI are the kernels'");
 
-// What a render with the setting on refuses, checked by the entry points before a device is touched (and by enqueue_outlines
-// again, for every way in): the lines come from the records of the whole pinhole view, one sample a pixel, a pixel's mask needs
-// its neighbours, and no kernel of it keeps counters.  In front of ao_check: a scene with both settings on is refused here, not
-// drawn with one of them missing.  (The row-range answer guards against callers within this file, as ao_check's does.)
-int outline_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
-    if (!s->outlines) return NT_OK;
-    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "outlines are not available with a supersampling factor above 1 (%d)", s->supersampling);
-    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "outlines are not available with row bands (band_world %d): a pixel's mask needs its neighbours", b.world);
-    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "outlines are not available for a row range");
-    if (stats) return fail(NT_E_UNSUPPORTED, "outlines are not available with collect_stats");
-    if (s->lens) return fail(NT_E_UNSUPPORTED, "outlines are not available while a lens is set");
-    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "outlines are not available while the parallel projection is set");
-    if (s->ao_count > 0) return fail(NT_E_UNSUPPORTED, "outlines are not available while ambient occlusion is on");
-    return NT_OK;
-}
-
 // The mask bytes of every pixel of the job's frames and, with job.fmt, the render that draws them, per chunk of whole frames.
 // Opaque scenes that launch_composite_fixed would give the packet walk take one walk into hit records and outline_shade -- or
 // outline_mark_fixed for the mask alone -- (nt_launch_outline*); every other scene the plain fp32 x 3 base frame into scratch (a
@@ -1385,39 +1489,26 @@ int outline_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, 
 // frame) -- sits under the supersampling cap.  Enqueue only.
 int enqueue_outlines(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, uint8_t *mask_dev, bool mask_scratch,
                      uint8_t **mask_out) {
-    const bool draw = job.fmt != nullptr;
-    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
-    if (int r = outline_check(s, job.bands, job.stats, draw ? job.row_begin : 0, draw ? job.row_count : H, H)) return r;
-    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const char *noun = "outlines";
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, &kViewSettings[VS_OUTLINES], noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const bool draw = vp.draw;
     const int n = s->n;
-    const long long px = (long long)W * H;
-    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const long long px = vp.px;
     const bool fast = composite_route(s, sw).packet_walk;
     const long long per_frame = fast ? px * (16 + (mask_scratch ? 1 : 0)) : px * (16 + 4 * n + (draw ? 12 : 0) + 1);
-    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "outlines of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
-    if (per_frame > cap)
-        return fail(NT_E_UNSUPPORTED, "outlines of a %d x %d image: the scratch of one frame (%lld bytes) does not fit the scratch buffer of "
-                    "%lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
-    const int chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame),
-                                                                              std::min<long long>(INT_MAX / px, std::max(sw.chunk_frames, 1))));
-    if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame))) return e;
+    long long chunk_frames;
+    if (int r = plan_scratch_frames(vp, job.nframes, noun, nullptr, per_frame, (long long)s->ss_scratch_mb << 20, std::max(sw.chunk_frames, 1),
+                                    chunk_frames)) return r;
+    Scratch at;
+    if (int e = at.open(ds, (size_t)(chunk_frames * per_frame))) return e;
     const size_t fpx = (size_t)chunk_frames * px;
-    char *at = (char *)ds->samples.p;
-    void *recs = at; at += fpx * 16;
-    float *nd = nullptr;
-    char *base = nullptr;
-    if (!fast) {
-        nd = (float *)at; at += fpx * n * 4;
-        if (draw) { base = at; at += fpx * 12; }
-    }
-    if (!fast || mask_scratch) mask_dev = mask_dev ? mask_dev : (uint8_t *)at;
+    void *recs = at.take<void>(fpx * 16);
+    float *nd = fast ? nullptr : at.take<float>(fpx * n * 4);
+    char *base = !fast && draw ? at.take<char>(fpx * 12) : nullptr;
+    if (!fast || mask_scratch) mask_dev = mask_dev ? mask_dev : at.take<uint8_t>(fpx);
     if (mask_out) *mask_out = mask_dev;
-    NtTarget tg;
-    if (draw) {
-        if (int r = fill_target(s, ds, job, tg)) return r;
-    } else {
-        view_target(s, W, H, job.abort_word, tg);
-    }
     NtOutline ol{};
     ol.cc = s->ol_crease_cos * s->ol_crease_cos;
     ol.depth_gap = s->ol_depth_gap;
@@ -1426,43 +1517,28 @@ int enqueue_outlines(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
     ol.recs = recs;
     ol.normal_dir = nd;
     ol.mask = mask_dev;
-    Format bf;
-    if (int r = plain_f32_format(W, H, bf)) return r;
     const float *all_cams = nullptr;
     NtCompositeDev c;
     if (fast) {
         if (int e = device_camera(s, ds, job.cam_buf, job.stream, all_cams)) return e;
         scene_dev(s, ds, sw, job.strict, false, c);
     }
-    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
-        const int nf = std::min(chunk_frames, job.nframes - f0);
-        NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
-        NtTarget ft = tg;
-        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
-        ol.nframes = nf;
+    for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
+        ViewChunk ch = view_chunk(s, ds, job, sw, vp, f0, chunk_frames);
+        ol.nframes = ch.nf;
         if (fast) {
-            // the packet walk's plane numerators and quad order, as hits_enqueue hands them over, and the records' place
-            if (int e = numerator_scratch(s, ds, sw, nf, li)) return e;
-            if (sw.tile_order) {
-                if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
-            }
-            li.hit_buf = recs;
-            li.hit_frames = nf;
+            if (int e = packet_records(s, ds, sw, vp.W, vp.H, ch.nf, recs, ch.li)) return e;
             ol.cams = all_cams + (size_t)f0 * 4 * n;
-            if (int r = draw ? nt_launch_outline(li, c, ft, ol) : nt_launch_outline_mask(li, c, ft, ol)) return launch_failed(r);
+            if (int r = draw ? nt_launch_outline(ch.li, c, ch.ft, ol) : nt_launch_outline_mask(ch.li, c, ch.ft, ol)) return launch_failed(r);
             continue;
-        }
-        const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
-        if (draw) {
-            if (int e = enqueue(s, ds, base_frame_job(s, job, bf, f0, nf, base, (size_t)px * 12))) return e;
         }
         nt_hit_buffers hb{};
         hb.hits = (nt_ray_hit *)recs;
         hb.normal_dir = nd;
-        if (int e = hits_enqueue(s, ds, W, H, &hb, px, cams, nf, job.strict, job.abort_word, job.stream)) return e;
-        if (int r = nt_launch_outline_mark(li, ft, ol)) return launch_failed(r);
+        if (int e = base_and_hits(s, ds, job, vp, ch, base, hb)) return e;
+        if (int r = nt_launch_outline_mark(ch.li, ch.ft, ol)) return launch_failed(r);
         if (draw) {
-            if (int r = nt_launch_outline_apply(job.stream, (const uint32_t *)base, ol, ft)) return launch_failed(r);
+            if (int r = nt_launch_outline_apply(job.stream, (const uint32_t *)base, ol, ch.ft)) return launch_failed(r);
         }
     }
     return NT_OK;
@@ -1471,20 +1547,6 @@ int enqueue_outlines(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 // ---------------------------------------------------------------------------------------------
 // BoxScene face lines (nt_scene_set_box_lines; kernels in nt_boxhits.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
-
-// What a render with the setting on refuses, checked by the entry points before a device is touched (and by enqueue_box_lines
-// again, for every way in): a pixel's mask needs the records of its neighbours in the whole pinhole view, one sample a pixel, and
-// no kernel of it keeps counters.
-int box_lines_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
-    if (!s->box_lines || s->composite) return NT_OK;
-    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "face lines are not available with a supersampling factor above 1 (%d)", s->supersampling);
-    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "face lines are not available with row bands (band_world %d): a pixel's mask needs its neighbours", b.world);
-    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "face lines are not available for a row range");
-    if (stats) return fail(NT_E_UNSUPPORTED, "face lines are not available with collect_stats");
-    if (s->lens) return fail(NT_E_UNSUPPORTED, "face lines are not available while a lens is set");
-    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "face lines are not available while the parallel projection is set");
-    return NT_OK;
-}
 
 // the camera of frames [f0, ...) of a job as the BoxScene kernels take it
 void box_camera(const nt_scene *s, const float *cam_buf, const float *cam_dots, int f0, NtCamera &cam) {
@@ -1502,38 +1564,29 @@ void box_camera(const nt_scene *s, const float *cam_buf, const float *cam_dots, 
 // job.view_h, one frame.  Enqueue only.
 int enqueue_box_lines(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, uint8_t *mask_dev, bool mask_scratch,
                       uint8_t **mask_out) {
-    const bool draw = job.fmt != nullptr;
-    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
-    // (the mask is one sample a pixel of the whole view whatever the supersampling factor says, as nt_box_hits is)
-    if (draw) {
-        if (int r = box_lines_check(s, job.bands, job.stats, job.row_begin, job.row_count, H)) return r;
-    }
-    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
-    const long long px = (long long)W * H;
-    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "face lines of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
+    const char *noun = "face lines";
+    // (the mask is one sample a pixel of the whole view whatever the supersampling factor says, as nt_box_hits is: the check is the
+    // render's alone)
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, job.fmt ? &kViewSettings[VS_BOX_LINES] : nullptr, noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const bool draw = vp.draw;
+    const long long px = vp.px;
     const bool var = s->n > NT_MAX_FIXED_BOX_DIM || sw.force_var;
-    const long long cap = (long long)s->ss_scratch_mb << 20;
     const long long per_frame = px * ((var ? 16 : 0) + (mask_scratch ? 1 : 0));
-    if (per_frame > cap)
-        return fail(NT_E_UNSUPPORTED, "face lines of a %d x %d image: the scratch of one frame (%lld bytes) does not fit the scratch buffer of "
-                    "%lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
-    int chunk_frames = job.nframes;
-    if (var) chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame),
-                                                                             std::min<long long>(INT_MAX / px, std::max(sw.chunk_frames, 1))));
+    long long chunk_frames = job.nframes;                               // (the fixed-n kernel's frames need no scratch: one chunk)
     void *recs = nullptr;
     if (per_frame > 0) {
-        if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame))) return e;
-        char *at = (char *)ds->samples.p;
-        if (var) { recs = at; at += (size_t)chunk_frames * px * 16; }
-        if (mask_scratch) mask_dev = (uint8_t *)at;
+        long long fit;
+        if (int r = plan_scratch_frames(vp, job.nframes, noun, nullptr, per_frame, (long long)s->ss_scratch_mb << 20, std::max(sw.chunk_frames, 1),
+                                        fit)) return r;
+        if (var) chunk_frames = fit;
+        Scratch at;
+        if (int e = at.open(ds, (size_t)(chunk_frames * per_frame))) return e;
+        if (var) recs = at.take<void>((size_t)chunk_frames * px * 16);
+        if (mask_scratch) mask_dev = at.take<uint8_t>((size_t)chunk_frames * px);
     }
     if (mask_out) *mask_out = mask_dev;
-    NtTarget tg;
-    if (draw) {
-        if (int r = fill_target(s, ds, job, tg)) return r;
-    } else {
-        view_target(s, W, H, job.abort_word, tg);
-    }
     NtBoxFaces bf{};
     bf.mode = draw ? NT_BOX_FACES_DRAW : NT_BOX_FACES_MASK;
     bf.recs = recs;
@@ -1542,14 +1595,11 @@ int enqueue_box_lines(nt_scene *s, DeviceState *ds, const FrameJob &job, const R
     bf.kinds = s->box_lines;
     for (int k = 0; k < 3; ++k) bf.color[k] = s->bl_color[k];
     bf.strength = s->bl_strength;
-    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
-        const int nf = std::min(chunk_frames, job.nframes - f0);
-        const NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
-        NtTarget ft = tg;
-        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
+    for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
+        const ViewChunk ch = view_chunk(s, ds, job, sw, vp, f0, chunk_frames);
         NtCamera cam;
         box_camera(s, job.cam_buf, job.cam_dots, f0, cam);
-        if (int r = nt_launch_box_faces(li, cam, ft, bf)) return launch_failed(r);
+        if (int r = nt_launch_box_faces(ch.li, cam, ch.ft, bf)) return launch_failed(r);
     }
     return NT_OK;
 }
@@ -1557,23 +1607,6 @@ int enqueue_box_lines(nt_scene *s, DeviceState *ds, const FrameJob &job, const R
 // ---------------------------------------------------------------------------------------------
 // depth cues (nt_scene_set_depth_cue; kernels in nt_cue.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
-
-// What a render with the setting on refuses, checked by the entry points before a device is touched, in front of every other
-// setting's check (and by enqueue_cue again, for every way in): the factors come from the records of the whole pinhole view, one
-// sample a pixel, no kernel of it keeps counters, and a scene with another such setting on is refused here, not drawn with one
-// of them missing.  (The row-range answer guards against callers within this file, as ao_check's does.)
-int cue_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
-    if (!s->cue) return NT_OK;
-    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "depth cues are not available with a supersampling factor above 1 (%d)", s->supersampling);
-    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "depth cues are not available with row bands (band_world %d)", b.world);
-    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "depth cues are not available for a row range");
-    if (stats) return fail(NT_E_UNSUPPORTED, "depth cues are not available with collect_stats");
-    if (s->lens) return fail(NT_E_UNSUPPORTED, "depth cues are not available while a lens is set");
-    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "depth cues are not available while the parallel projection is set");
-    if (s->ao_count > 0) return fail(NT_E_UNSUPPORTED, "depth cues are not available while ambient occlusion is on");
-    if (s->outlines) return fail(NT_E_UNSUPPORTED, "depth cues are not available while outlines are on");
-    return NT_OK;
-}
 
 // The factors (f, g) of every pixel of the job's frames or, with job.fmt, the render they shape, per chunk of whole frames.
 // Opaque scenes that launch_composite_fixed would give the packet walk take one walk into hit records and cue_shade -- or
@@ -1584,35 +1617,25 @@ int cue_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int 
 // 12 of base frame off the packet walk, 8 of factors for the host form -- sits under the supersampling cap.  Enqueue only.
 int enqueue_cue(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, float *factors_dev, bool factors_scratch,
                 float **factors_out) {
-    const bool draw = job.fmt != nullptr;
-    const int W = draw ? job.fmt->width : job.view_w, H = draw ? job.fmt->height : job.view_h;
-    if (int r = cue_check(s, job.bands, job.stats, draw ? job.row_begin : 0, draw ? job.row_count : H, H)) return r;
-    if (draw && job.fmt->bpp == 0) return NT_OK;                        // nothing to draw
+    const char *noun = "depth cue";
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, &kViewSettings[VS_CUE], noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const bool draw = vp.draw;
     const int n = s->n;
-    const long long px = (long long)W * H;
-    const long long cap = (long long)s->ss_scratch_mb << 20;
+    const long long px = vp.px;
     const bool fast = composite_route(s, sw).packet_walk;
     const long long per_frame = px * (16 + (!fast && draw ? 12 : 0) + (factors_scratch ? 8 : 0));
-    if (px > INT_MAX) return fail(NT_E_UNSUPPORTED, "depth cue of a %d x %d image: beyond 2^31 - 1 pixels", W, H);
-    if (per_frame > cap)
-        return fail(NT_E_UNSUPPORTED, "depth cue of a %d x %d image: the scratch of one frame (%lld bytes) does not fit the scratch buffer of "
-                    "%lld MiB (nt_scene_set_supersampling_scratch_mb)", W, H, per_frame, cap >> 20);
-    const int chunk_frames = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(job.nframes, cap / per_frame),
-                                                                              std::min<long long>(INT_MAX / px, std::max(sw.chunk_frames, 1))));
-    if (int e = ds->samples.ensure((size_t)(chunk_frames * per_frame))) return e;
+    long long chunk_frames;
+    if (int r = plan_scratch_frames(vp, job.nframes, noun, nullptr, per_frame, (long long)s->ss_scratch_mb << 20, std::max(sw.chunk_frames, 1),
+                                    chunk_frames)) return r;
+    Scratch at;
+    if (int e = at.open(ds, (size_t)(chunk_frames * per_frame))) return e;
     const size_t fpx = (size_t)chunk_frames * px;
-    char *at = (char *)ds->samples.p;
-    void *recs = at; at += fpx * 16;
-    char *base = nullptr;
-    if (!fast && draw) { base = at; at += fpx * 12; }
-    if (factors_scratch) factors_dev = (float *)at;
+    void *recs = at.take<void>(fpx * 16);
+    char *base = !fast && draw ? at.take<char>(fpx * 12) : nullptr;
+    if (factors_scratch) factors_dev = at.take<float>(fpx * 8);
     if (factors_out) *factors_out = factors_dev;
-    NtTarget tg;
-    if (draw) {
-        if (int r = fill_target(s, ds, job, tg)) return r;
-    } else {
-        view_target(s, W, H, job.abort_word, tg);
-    }
     NtCue cu{};
     cu.recs = recs;
     cu.fog_near = s->cue_set.fog_near;
@@ -1629,41 +1652,26 @@ int enqueue_cue(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderS
     }
     for (int k = 0; k < n && s->cue_tint; ++k) cu.tint_axis[k] = s->cue_axis[k];
     cu.factors = factors_dev;
-    Format bf;
-    if (int r = plain_f32_format(W, H, bf)) return r;
     const float *all_cams = nullptr;
     NtCompositeDev c;
     if (fast) {
         if (int e = device_camera(s, ds, job.cam_buf, job.stream, all_cams)) return e;
         scene_dev(s, ds, sw, job.strict, false, c);
     }
-    for (int f0 = 0; f0 < job.nframes; f0 += chunk_frames) {
-        const int nf = std::min(chunk_frames, job.nframes - f0);
-        NtLaunchInfo li = launch_info(s, ds, sw, nf, job.stream);
-        NtTarget ft = tg;
-        if (draw) ft.dest = tg.dest + (long long)f0 * tg.frame_stride;
-        cu.nframes = nf;
+    for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
+        ViewChunk ch = view_chunk(s, ds, job, sw, vp, f0, chunk_frames);
+        cu.nframes = ch.nf;
         if (fast) {
-            // the packet walk's plane numerators and quad order, as hits_enqueue hands them over, and the records' place
-            if (int e = numerator_scratch(s, ds, sw, nf, li)) return e;
-            if (sw.tile_order) {
-                if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
-            }
-            li.hit_buf = recs;
-            li.hit_frames = nf;
+            if (int e = packet_records(s, ds, sw, vp.W, vp.H, ch.nf, recs, ch.li)) return e;
             cu.cams = all_cams + (size_t)f0 * 4 * n;
-            if (int r = draw ? nt_launch_cue(li, c, ft, cu) : nt_launch_cue_factors_fixed(li, c, ft, cu)) return launch_failed(r);
+            if (int r = draw ? nt_launch_cue(ch.li, c, ch.ft, cu) : nt_launch_cue_factors_fixed(ch.li, c, ch.ft, cu)) return launch_failed(r);
             continue;
-        }
-        const float *cams = job.cam_buf ? job.cam_buf + (size_t)f0 * 4 * n : nullptr;
-        if (draw) {
-            if (int e = enqueue(s, ds, base_frame_job(s, job, bf, f0, nf, base, (size_t)px * 12))) return e;
         }
         nt_hit_buffers hb{};
         hb.hits = (nt_ray_hit *)recs;
-        if (int e = hits_enqueue(s, ds, W, H, &hb, px, cams, nf, job.strict, job.abort_word, job.stream)) return e;
-        cu.cams = cams ? cams : (const float *)ds->cams.p;              // (hits_enqueue has put the scene's own camera there)
-        if (int r = draw ? nt_launch_cue_apply(li, (const uint32_t *)base, cu, ft) : nt_launch_cue_factors(li, ft, cu)) return launch_failed(r);
+        if (int e = base_and_hits(s, ds, job, vp, ch, base, hb)) return e;
+        cu.cams = ch.cams ? ch.cams : (const float *)ds->cams.p;        // (hits_enqueue has put the scene's own camera there)
+        if (int r = draw ? nt_launch_cue_apply(ch.li, (const uint32_t *)base, cu, ch.ft) : nt_launch_cue_factors(ch.li, ch.ft, cu)) return launch_failed(r);
     }
     return NT_OK;
 }
@@ -1672,26 +1680,7 @@ int enqueue_cue(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderS
 // clip planes (nt_scene_set_clip_planes; kernels in nt_clip.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
-// What a render with the setting on refuses, checked by the entry points before a device is touched, in front of every other
-// setting's check (and by enqueue_clip again, for every way in): the cutaway is one sample a pixel of the whole pinhole view, no
-// kernel of it keeps counters, and a scene with another such setting on is refused here, not drawn with one of them missing.
-// A Solid cut open needs a cap or an inner wall, which nothing defines: refused, not approximated.
-int clip_check(const nt_scene *s, const Bands &b, bool stats, int row_begin, int row_count, int height) {
-    if (s->clip_count <= 0) return NT_OK;
-    if (s->supersampling > 1) return fail(NT_E_UNSUPPORTED, "clip planes are not available with a supersampling factor above 1 (%d)", s->supersampling);
-    if (b.world > 1) return fail(NT_E_UNSUPPORTED, "clip planes are not available with row bands (band_world %d)", b.world);
-    if (row_begin != 0 || row_count != height) return fail(NT_E_UNSUPPORTED, "clip planes are not available for a row range");
-    if (stats) return fail(NT_E_UNSUPPORTED, "clip planes are not available with collect_stats");
-    if (s->lens) return fail(NT_E_UNSUPPORTED, "clip planes are not available while a lens is set");
-    if (s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "clip planes are not available while the parallel projection is set");
-    if (s->ao_count > 0) return fail(NT_E_UNSUPPORTED, "clip planes are not available while ambient occlusion is on");
-    if (s->outlines) return fail(NT_E_UNSUPPORTED, "clip planes are not available while outlines are on");
-    if (s->cue) return fail(NT_E_UNSUPPORTED, "clip planes are not available while depth cues are on");
-    if (s->n_solids > 0) return fail(NT_E_UNSUPPORTED, "clip planes are not available for a scene with Solids (a Solid cut open has no cap)");
-    return NT_OK;
-}
-
-// ... and what the entry points that do not honour the setting say while it is on
+// what the entry points that do not honour the setting say while it is on
 int clip_refuses(const nt_scene *s, const char *what) {
     if (s && s->composite && s->clip_count > 0) return fail(NT_E_UNSUPPORTED, "clip planes are set: %s is not available under them", what);
     return NT_OK;
@@ -1702,7 +1691,7 @@ int clip_refuses(const nt_scene *s, const char *what) {
 // see, whatever its dimension -- with the `checked` columns and ray_color frames of the faithful walks.  Enqueue only.
 int enqueue_clip(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw) {
     const int W = job.fmt->width, H = job.fmt->height;
-    if (int r = clip_check(s, job.bands, job.stats, job.row_begin, job.row_count, H)) return r;
+    if (int r = whole_view_check(s, kViewSettings[VS_CLIP], job.bands, job.stats, job.row_begin, job.row_count, H)) return r;
     if (job.fmt->bpp == 0) return NT_OK;                                // nothing to draw
     NtTarget tg;
     if (int r = fill_target(s, ds, job, tg)) return r;
@@ -1723,11 +1712,8 @@ int enqueue_clip(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
     cl.nframes = job.nframes;
     if (rt.packet_walk) {
         // the packet walk's plane numerators, record scratch and quad order, as plan_composite hands them over
-        if (int e = numerator_scratch(s, ds, sw, job.nframes, li)) return e;
+        if (int e = packet_records(s, ds, sw, W, H, job.nframes, nullptr, li)) return e;
         if (int e = hit_record_scratch(ds, sw, (size_t)16 * W * H, job.nframes, li)) return e;
-        if (sw.tile_order) {
-            if (int e = tile_order_for(ds, W, H, li.tile_order)) return e;
-        }
     } else if (rt.faithful) {
         const long long tiles = (long long)((W + 7) / 8) * ((H + 7) / 8) * job.nframes;
         long long blocks = std::min<long long>(std::max<long long>(tiles, 1), 8192);
@@ -1917,20 +1903,19 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
-    if (s->clip_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_clip(s, ds, job, sw);
-    if (s->cue && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
-        return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
-    if (s->outlines && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
-        return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
-    if (s->ao_count > 0 && s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
-        return enqueue_ao(s, ds, job, sw, nullptr, nullptr);
-    if (s->box_lines && !s->composite && !job.colors_out && !job.samples_pass && !job.counters_pass)
-        return enqueue_box_lines(s, ds, job, sw, nullptr, false, nullptr);
+    // the caller's own render: not the probes, nor a stage that another route has sent back here
+    const bool whole = !job.colors_out && !job.samples_pass && !job.counters_pass;
+    // the whole-view settings, one line a row of kViewSettings and in its order: the first that is on draws, as the first that is
+    // on refuses (tests/test_view_setting_refusals.py holds the refusals to that order, the settings' host tests these lines)
+    if (s->clip_count > 0 && s->composite && whole) return enqueue_clip(s, ds, job, sw);
+    if (s->cue && s->composite && whole) return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
+    if (s->outlines && s->composite && whole) return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
+    if (s->ao_count > 0 && s->composite && whole) return enqueue_ao(s, ds, job, sw, nullptr, nullptr);
+    if (s->box_lines && !s->composite && whole) return enqueue_box_lines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->lens) return enqueue_lens(s, ds, job, sw);
     if (s->parallel > 0.0f) return enqueue_parallel(s, ds, job, sw);
-    if (s->supersampling > 1 && s->adaptive && !job.colors_out && !job.samples_pass && !job.counters_pass)
-        return enqueue_adaptive(s, ds, job, sw, nullptr, false, nullptr);
-    if (s->supersampling > 1 && !job.colors_out && !job.samples_pass && !job.counters_pass) return enqueue_supersampled(s, ds, job);
+    if (s->supersampling > 1 && s->adaptive && whole) return enqueue_adaptive(s, ds, job, sw, nullptr, false, nullptr);
+    if (s->supersampling > 1 && whole) return enqueue_supersampled(s, ds, job);
     if (s->composite && job.stats && !job.counters_pass && !job.colors_out) {
         // Scenes with transparent materials or Solids are drawn by the kernels that reproduce the reference's o_hit.normal
         // handling (below), which keep no counters.  Asking for statistics must not change the pixels: the frame is drawn as
@@ -1985,11 +1970,9 @@ int prepare_stats(DeviceState *ds, hipStream_t st, bool on) {
 
 // what the scene's settings refuse of a render, in the order the render entry points say it, before they touch a device
 int render_checks(const nt_scene *s, const Format &f, const Bands &b, bool stats) {
-    if (int r = clip_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = cue_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = outline_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = ao_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
-    if (int r = box_lines_check(s, b, stats, 0, b.owned_rows, f.height)) return r;
+    for (const ViewSetting &row : kViewSettings) {
+        if (int r = whole_view_check(s, row, b, stats, 0, b.owned_rows, f.height)) return r;
+    }
     if (int r = lens_check(s, f.width, f.height, b, stats, false)) return r;
     if (int r = parallel_check(s, b, stats, false)) return r;
     return adaptive_check(s, b, stats);
@@ -2022,7 +2005,7 @@ FrameJob render_job(const Format &f, const Bands &b, void *dest_dev, size_t fram
 }
 
 // ... and of the entry points that draw nothing (nt_adaptive_mask, nt_ambient_occlusion, nt_outline_mask,
-// nt_depth_cue_factors): one whole view of w x h
+// nt_depth_cue_factors, nt_box_line_mask): one whole view of w x h
 FrameJob view_job(int w, int h, hipStream_t stream, const nt_render_opts *opts, bool device_form) {
     FrameJob job{};
     job.nframes = 1;
@@ -2599,6 +2582,118 @@ int rays_device(nt_scene *s, const nt_rays *rays, float *rgb, void *dest_dev, si
     return rays_enqueue(s, ds, job, rgb, &f, dest_dev, opts && opts->strict_reference, opts ? (const int *)opts->abort_device : nullptr,
                         (hipStream_t)hip_stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// the buffer of a setting alone, of one view of the scene's camera: nt_adaptive_mask, nt_ambient_occlusion, nt_outline_mask,
+// nt_depth_cue_factors, nt_box_line_mask and their _device forms
+// ---------------------------------------------------------------------------------------------
+
+// what tells the five apart; T is the buffer's element type
+template <typename T>
+struct ViewQuery {
+    size_t elem;                         // bytes a pixel
+    int kind;                            // the scenes it is of: 1 composite, 0 BoxScene, -1 either
+    const char *clip_what;               // clip_refuses' phrase of it (nullptr: not asked)
+    bool (*off)(const nt_scene *s);
+    const char *off_message;
+    const char *what;                    // subject and verb of the lens / projection refusal
+    bool adaptive_terms;                 // row bands and collect_stats, refused in the adaptive mask's words
+    bool pixel_term;                     // more than 2^31 - 1 pixels, refused here (face lines: no check_renderable term follows)
+    int (*device_options)(const nt_render_opts *opts);      // what the device form refuses of its options (nullptr: nothing)
+    // the setting's enqueue: into `dev`, or with `kept` into scratch, whose place it tells there
+    int (*enqueue)(nt_scene *s, DeviceState *ds, const FrameJob &job, T *dev, T **kept);
+};
+
+const ViewQuery<uint8_t> kAdaptiveMask = {
+    1, -1, "the adaptive mask", [](const nt_scene *s) { return !s->adaptive; }, "the adaptive threshold is off (nt_scene_set_adaptive_supersampling)",
+    "the adaptive mask is", true, false, nullptr,
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, uint8_t *dev, uint8_t **kept) {
+        return enqueue_adaptive(s, ds, job, read_switches(), dev, kept != nullptr, kept);
+    }};
+const ViewQuery<int> kAoCounts = {
+    sizeof(int32_t), 1, "the ambient occlusion count", [](const nt_scene *s) { return s->ao_count <= 0; }, "ambient occlusion is off (nt_scene_set_ambient_occlusion)",
+    "the ambient occlusion counts are", false, false,
+    [](const nt_render_opts *opts) { return only_device_strict_abort(opts, "the ambient occlusion counts read", "their"); },
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, int *dev, int **kept) { return enqueue_ao(s, ds, job, read_switches(), dev, kept); }};
+const ViewQuery<uint8_t> kOutlineMask = {
+    1, 1, "the outline mask", [](const nt_scene *s) { return !s->outlines; }, "outlines are off (nt_scene_set_outlines)",
+    "the outline mask is", false, false, [](const nt_render_opts *opts) { return only_device_strict_abort(opts, "the outline mask reads"); },
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, uint8_t *dev, uint8_t **kept) {
+        return enqueue_outlines(s, ds, job, read_switches(), dev, kept != nullptr, kept);
+    }};
+const ViewQuery<float> kCueFactors = {
+    2 * sizeof(float), 1, "the depth cue factors", [](const nt_scene *s) { return !s->cue; }, "the depth cue is off (nt_scene_set_depth_cue)",
+    "the depth cue factors are", false, false,
+    [](const nt_render_opts *opts) { return only_device_strict_abort(opts, "the depth cue factors read", "their"); },
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, float *dev, float **kept) {
+        return enqueue_cue(s, ds, job, read_switches(), dev, kept != nullptr, kept);
+    }};
+const ViewQuery<uint8_t> kBoxLineMask = {
+    1, 0, nullptr, [](const nt_scene *s) { return !s->box_lines; }, "face lines are off (nt_scene_set_box_lines)",
+    "the face-line mask is", false, true, [](const nt_render_opts *opts) { return only_device_abort(opts, "the face-line mask"); },
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, uint8_t *dev, uint8_t **kept) {
+        return enqueue_box_lines(s, ds, job, read_switches(), dev, kept != nullptr, kept);
+    }};
+
+// what both forms check before a device is touched
+template <typename T>
+int view_query_validate(const nt_scene *s, int width, int height, const void *out, const nt_render_opts *opts, const ViewQuery<T> &q) {
+    if (!s || !out) return fail(NT_E_INVALID, "NULL argument");
+    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (q.kind == 1 && !s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (q.kind == 0 && s->composite) return fail(NT_E_INVALID, "not a box scene");
+    if (q.clip_what) {
+        if (int r = clip_refuses(s, q.clip_what)) return r;
+    }
+    if (q.off(s)) return fail(NT_E_INVALID, "%s", q.off_message);
+    if (q.adaptive_terms) {
+        if (opts && opts->band_world > 1)
+            return fail(NT_E_UNSUPPORTED, "the adaptive mask is of the whole image: row bands (band_world %d) are not available", opts->band_world);
+        if (opts && opts->collect_stats) return fail(NT_E_UNSUPPORTED, "the adaptive mask keeps no counters: collect_stats is not available");
+    }
+    if (s->lens || s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "%s not available while a lens or the parallel projection is set", q.what);
+    if (q.pixel_term && (long long)width * height > INT_MAX)
+        return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 pixels", width, height);
+    return check_renderable(s);
+}
+
+// The host form: the renderer protocol (`guard` is the caller's, so that it holds while the caller reads more), the enqueue into
+// scratch on the scene's own stream, and the buffer's way back.  *ds_out: where it ran.
+template <typename T>
+int view_query_host(RenderGuard &guard, const ViewQuery<T> &q, int width, int height, T *out, const nt_render_opts *opts, DeviceState **ds_out = nullptr) {
+    nt_scene *s = guard.s;
+    if (int r = view_query_validate(s, width, height, out, opts, q)) return r;
+    if (int r = guard.acquire()) return r;
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_own_stream(ds)) return r;
+    const FrameJob job = view_job(width, height, ds->stream, opts, false);
+    T *kept = nullptr;
+    if (int r = q.enqueue(s, ds, job, nullptr, &kept)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    HIP_TRY(hipMemcpyAsync(out, kept, (size_t)width * height * q.elem, hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipStreamSynchronize(ds->stream));
+    if (ds_out) *ds_out = ds;
+    return NT_OK;
+}
+
+// the device form: `out_dev` is device memory; enqueue only
+template <typename T>
+int view_query_device(nt_scene *s, const ViewQuery<T> &q, int width, int height, void *out_dev, const nt_render_opts *opts, void *hip_stream) {
+    if (int r = view_query_validate(s, width, height, out_dev, opts, q)) return r;
+    if (q.device_options) {
+        if (int r = q.device_options(opts)) return r;
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
+    DeviceState *ds;
+    if (int r = scene_on_device(s, opts, -1, ds)) return r;
+    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
+    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: where options are refused, 0)
+    return q.enqueue(s, ds, job, (T *)out_dev, nullptr);
+}
+
+// the pixels of a mask that are marked
+long long marked_pixels(const uint8_t *mask, size_t count) { return (long long)(count - (size_t)std::count(mask, mask + count, (uint8_t)0)); }
 
 }  // namespace
 
@@ -3331,33 +3426,11 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     return enqueue(s, ds, job);
 }
 
-namespace {
-// what both forms of nt_adaptive_mask check before a device is touched
-int mask_validate(const nt_scene *s, int width, int height, const void *mask, const nt_render_opts *opts) {
-    if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
-    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
-    if (int r = clip_refuses(s, "the adaptive mask")) return r;
-    if (!s->adaptive) return fail(NT_E_INVALID, "the adaptive threshold is off (nt_scene_set_adaptive_supersampling)");
-    if (opts && opts->band_world > 1)
-        return fail(NT_E_UNSUPPORTED, "the adaptive mask is of the whole image: row bands (band_world %d) are not available", opts->band_world);
-    if (opts && opts->collect_stats) return fail(NT_E_UNSUPPORTED, "the adaptive mask keeps no counters: collect_stats is not available");
-    if (s->lens || s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "the adaptive mask is not available while a lens or the parallel projection is set");
-    return check_renderable(s);
-}
-}  // namespace
-
 int nt_adaptive_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *flagged, const nt_render_opts *opts) {
-    if (int r = mask_validate(s, width, height, mask, opts)) return r;
     RenderGuard guard(s);
-    if (int r = guard.acquire()) return r;
     DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_own_stream(ds)) return r;
-    const FrameJob job = view_job(width, height, ds->stream, opts, false);
-    uint8_t *mask_dev = nullptr;
-    if (int r = enqueue_adaptive(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
+    if (int r = view_query_host(guard, kAdaptiveMask, width, height, mask, opts, &ds)) return r;
     int count = 0;
-    HIP_TRY(hipMemcpyAsync(mask, mask_dev, (size_t)width * height, hipMemcpyDeviceToHost, ds->stream));
     HIP_TRY(hipMemcpyAsync(&count, ds->refine_count.p, sizeof(int), hipMemcpyDeviceToHost, ds->stream));
     HIP_TRY(hipStreamSynchronize(ds->stream));
     if (flagged) *flagged = count;
@@ -3365,182 +3438,47 @@ int nt_adaptive_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long l
 }
 
 int nt_adaptive_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream) {
-    if (int r = mask_validate(s, width, height, mask_dev, opts)) return r;
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);
-    return enqueue_adaptive(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
+    return view_query_device(s, kAdaptiveMask, width, height, mask_dev, opts, hip_stream);
 }
-
-namespace {
-// what both forms of nt_ambient_occlusion check before a device is touched
-int ao_validate(const nt_scene *s, int width, int height, const void *blocked) {
-    if (!s || !blocked) return fail(NT_E_INVALID, "NULL argument");
-    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
-    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
-    if (int r = clip_refuses(s, "the ambient occlusion count")) return r;
-    if (s->ao_count <= 0) return fail(NT_E_INVALID, "ambient occlusion is off (nt_scene_set_ambient_occlusion)");
-    if (s->lens || s->parallel > 0.0f)
-        return fail(NT_E_UNSUPPORTED, "the ambient occlusion counts are not available while a lens or the parallel projection is set");
-    return check_renderable(s);
-}
-}  // namespace
 
 int nt_ambient_occlusion(nt_scene_t *s, int width, int height, int32_t *blocked, const nt_render_opts *opts) {
-    if (int r = ao_validate(s, width, height, blocked)) return r;
     RenderGuard guard(s);
-    if (int r = guard.acquire()) return r;
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_own_stream(ds)) return r;
-    const FrameJob job = view_job(width, height, ds->stream, opts, false);
-    int *counts = nullptr;
-    if (int r = enqueue_ao(s, ds, job, read_switches(), nullptr, &counts)) { (void)hipStreamSynchronize(ds->stream); return r; }
-    HIP_TRY(hipMemcpyAsync(blocked, counts, (size_t)width * height * sizeof(int32_t), hipMemcpyDeviceToHost, ds->stream));
-    HIP_TRY(hipStreamSynchronize(ds->stream));
-    return NT_OK;
+    return view_query_host(guard, kAoCounts, width, height, blocked, opts);
 }
 
 int nt_ambient_occlusion_device(nt_scene_t *s, int width, int height, void *blocked_dev, const nt_render_opts *opts, void *hip_stream) {
-    if (int r = ao_validate(s, width, height, blocked_dev)) return r;
-    if (int r = only_device_strict_abort(opts, "the ambient occlusion counts read", "their")) return r;
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
-    return enqueue_ao(s, ds, job, read_switches(), (int *)blocked_dev, nullptr);
+    return view_query_device(s, kAoCounts, width, height, blocked_dev, opts, hip_stream);
 }
-
-namespace {
-// what both forms of nt_outline_mask check before a device is touched
-int outline_validate(const nt_scene *s, int width, int height, const void *mask) {
-    if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
-    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
-    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
-    if (int r = clip_refuses(s, "the outline mask")) return r;
-    if (!s->outlines) return fail(NT_E_INVALID, "outlines are off (nt_scene_set_outlines)");
-    if (s->lens || s->parallel > 0.0f)
-        return fail(NT_E_UNSUPPORTED, "the outline mask is not available while a lens or the parallel projection is set");
-    return check_renderable(s);
-}
-}  // namespace
 
 int nt_outline_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts) {
-    if (int r = outline_validate(s, width, height, mask)) return r;
     RenderGuard guard(s);
-    if (int r = guard.acquire()) return r;
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_own_stream(ds)) return r;
-    const FrameJob job = view_job(width, height, ds->stream, opts, false);
-    uint8_t *mask_dev = nullptr;
-    if (int r = enqueue_outlines(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
-    const size_t count = (size_t)width * height;
-    HIP_TRY(hipMemcpyAsync(mask, mask_dev, count, hipMemcpyDeviceToHost, ds->stream));
-    HIP_TRY(hipStreamSynchronize(ds->stream));
-    if (marked) *marked = (long long)(count - (size_t)std::count(mask, mask + count, (uint8_t)0));
+    if (int r = view_query_host(guard, kOutlineMask, width, height, mask, opts)) return r;
+    if (marked) *marked = marked_pixels(mask, (size_t)width * height);
     return NT_OK;
 }
 
 int nt_outline_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream) {
-    if (int r = outline_validate(s, width, height, mask_dev)) return r;
-    if (int r = only_device_strict_abort(opts, "the outline mask reads")) return r;
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
-    return enqueue_outlines(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
+    return view_query_device(s, kOutlineMask, width, height, mask_dev, opts, hip_stream);
 }
-
-namespace {
-// what both forms of nt_depth_cue_factors check before a device is touched
-int cue_validate(const nt_scene *s, int width, int height, const void *factors) {
-    if (!s || !factors) return fail(NT_E_INVALID, "NULL argument");
-    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
-    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
-    if (int r = clip_refuses(s, "the depth cue factors")) return r;
-    if (!s->cue) return fail(NT_E_INVALID, "the depth cue is off (nt_scene_set_depth_cue)");
-    if (s->lens || s->parallel > 0.0f)
-        return fail(NT_E_UNSUPPORTED, "the depth cue factors are not available while a lens or the parallel projection is set");
-    return check_renderable(s);
-}
-}  // namespace
 
 int nt_depth_cue_factors(nt_scene_t *s, int width, int height, float *factors, const nt_render_opts *opts) {
-    if (int r = cue_validate(s, width, height, factors)) return r;
     RenderGuard guard(s);
-    if (int r = guard.acquire()) return r;
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_own_stream(ds)) return r;
-    const FrameJob job = view_job(width, height, ds->stream, opts, false);
-    float *factors_dev = nullptr;
-    if (int r = enqueue_cue(s, ds, job, read_switches(), nullptr, true, &factors_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
-    HIP_TRY(hipMemcpyAsync(factors, factors_dev, (size_t)width * height * 8, hipMemcpyDeviceToHost, ds->stream));
-    HIP_TRY(hipStreamSynchronize(ds->stream));
-    return NT_OK;
+    return view_query_host(guard, kCueFactors, width, height, factors, opts);
 }
 
 int nt_depth_cue_factors_device(nt_scene_t *s, int width, int height, void *factors_dev, const nt_render_opts *opts, void *hip_stream) {
-    if (int r = cue_validate(s, width, height, factors_dev)) return r;
-    if (int r = only_device_strict_abort(opts, "the depth cue factors read", "their")) return r;
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: refused above unless 0)
-    return enqueue_cue(s, ds, job, read_switches(), (float *)factors_dev, false, nullptr);
+    return view_query_device(s, kCueFactors, width, height, factors_dev, opts, hip_stream);
 }
-
-namespace {
-// what both forms of nt_box_line_mask check before a device is touched
-int box_lines_validate(const nt_scene *s, int width, int height, const void *mask) {
-    if (!s || !mask) return fail(NT_E_INVALID, "NULL argument");
-    if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
-    if (s->composite) return fail(NT_E_INVALID, "not a box scene");
-    if (!s->box_lines) return fail(NT_E_INVALID, "face lines are off (nt_scene_set_box_lines)");
-    if (s->lens || s->parallel > 0.0f)
-        return fail(NT_E_UNSUPPORTED, "the face-line mask is not available while a lens or the parallel projection is set");
-    if ((long long)width * height > INT_MAX) return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 pixels", width, height);
-    return NT_OK;
-}
-}  // namespace
 
 int nt_box_line_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long long *marked, const nt_render_opts *opts) {
-    if (int r = box_lines_validate(s, width, height, mask)) return r;
     RenderGuard guard(s);
-    if (int r = guard.acquire()) return r;
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_own_stream(ds)) return r;
-    const FrameJob job = view_job(width, height, ds->stream, opts, false);
-    uint8_t *mask_dev = nullptr;
-    if (int r = enqueue_box_lines(s, ds, job, read_switches(), nullptr, true, &mask_dev)) { (void)hipStreamSynchronize(ds->stream); return r; }
-    const size_t count = (size_t)width * height;
-    HIP_TRY(hipMemcpyAsync(mask, mask_dev, count, hipMemcpyDeviceToHost, ds->stream));
-    HIP_TRY(hipStreamSynchronize(ds->stream));
-    if (marked) *marked = (long long)(count - (size_t)std::count(mask, mask + count, (uint8_t)0));
+    if (int r = view_query_host(guard, kBoxLineMask, width, height, mask, opts)) return r;
+    if (marked) *marked = marked_pixels(mask, (size_t)width * height);
     return NT_OK;
 }
 
 int nt_box_line_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream) {
-    if (int r = box_lines_validate(s, width, height, mask_dev)) return r;
-    if (int r = only_device_abort(opts, "the face-line mask")) return r;
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->busy) return fail(NT_E_BUSY, "the renderer is already running");
-    DeviceState *ds;
-    if (int r = scene_on_device(s, opts, -1, ds)) return r;
-    if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);
-    return enqueue_box_lines(s, ds, job, read_switches(), (uint8_t *)mask_dev, false, nullptr);
+    return view_query_device(s, kBoxLineMask, width, height, mask_dev, opts, hip_stream);
 }
 
 int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t *xs, const int32_t *ys, float *rgb, int device) {

@@ -942,32 +942,55 @@ class _SceneBase(Scene):
         """The pixels a width x height render of the scene's camera would refine under the adaptive threshold that is set
         (nt_adaptive_mask), whatever the factor: a numpy bool array [height][width] -- or, with `device` a torch device, a
         torch bool tensor there, enqueued on torch's current stream."""
+        mask = self._view_query("nt_adaptive_mask", width, height, device, np.uint8, "adaptive_supersampling",
+                                "the adaptive threshold is off (set_adaptive_supersampling)", strict_reference, counted=True, zeroed=True)
+        if device is None:
+            return mask.view(np.bool_)
+        import torch
+        return mask.view(torch.bool)
+
+    def _view_query(self, entry, width, height, device, dtype, setting, off_message, strict_reference=None, tail=(), counted=False,
+                    zeroed=False, plain=False):
+        """What refinement_mask, occlusion_counts, outline_mask, depth_cue_factors and face_line_mask share: the buffer of `entry`
+        (include/ntracer_hip.h) for a width x height view, `dtype` [height][width] + tail -- a numpy array through the host form,
+        or with `device` a torch device a tensor there (zeroed first, or as allocated) through the _device form on torch's current
+        stream.  `setting` is the property that is None while the setting is off, which the device path says in `off_message`.
+        `counted`: the host form takes a pointer for a count as well, not asked for.  `plain`: an entry without
+        strict_reference, whose options carry the device alone, and whose "off" answer needs no torch."""
         width, height = int(width), int(height)
         if width < 1 or height < 1:
             raise ValueError("the size of a view must be positive")
         L = _lib.lib()
+        shape = (height, width) + tuple(tail)
         if device is None:
             opts = _lib.NtRenderOpts()
             opts.device = -1
-            if strict_reference is None:
-                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
-            opts.strict_reference = 1 if strict_reference else 0
-            mask = np.zeros((height, width), np.uint8)
-            _lib.check(L.nt_adaptive_mask(self._handle, width, height, mask.ctypes.data, None, C.byref(opts)))
-            return mask.view(np.bool_)
+            if not plain:
+                if strict_reference is None:
+                    strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
+                opts.strict_reference = 1 if strict_reference else 0
+            out = np.zeros(shape, dtype)
+            _lib.check(getattr(L, entry)(self._handle, width, height, out.ctypes.data, *((None,) if counted else ()), C.byref(opts)))
+            return out
+        if plain and getattr(self, setting) is None:
+            raise ValueError(off_message)
         import torch
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError("device must be a HIP device")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        if self.adaptive_supersampling is None:
-            raise ValueError("the adaptive threshold is off (set_adaptive_supersampling)")
-        mask = torch.zeros((height, width), dtype=torch.uint8, device=dev)
-        opts = self._rays_opts(dev, strict_reference)
+        if not plain and getattr(self, setting) is None:
+            raise ValueError(off_message)
+        out = (torch.zeros if zeroed else torch.empty)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+        if plain:
+            opts = _lib.NtRenderOpts()
+            opts.device = dev.index
+        else:
+            opts = self._rays_opts(dev, strict_reference)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.nt_adaptive_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
-        return mask.view(torch.bool)
+        _lib.check(getattr(L, entry + "_device")(self._handle, width, height, C.c_void_p(out.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return out
 
     def set_ambient_occlusion(self, samples, radius=None, bias=None, strength=1.0):
         """Darken every pixel of a render by how enclosed its primary hit is (include/ntracer_hip.h): of K short
@@ -1019,32 +1042,8 @@ class _SceneBase(Scene):
         (nt_ambient_occlusion): int32 [height][width], -1 where the primary ray finds nothing opaque, else how many of the K
         samples are blocked -- a numpy array, or with `device` a torch device a torch tensor there, enqueued on torch's
         current stream."""
-        width, height = int(width), int(height)
-        if width < 1 or height < 1:
-            raise ValueError("the size of a view must be positive")
-        L = _lib.lib()
-        if device is None:
-            opts = _lib.NtRenderOpts()
-            opts.device = -1
-            if strict_reference is None:
-                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
-            opts.strict_reference = 1 if strict_reference else 0
-            counts = np.zeros((height, width), np.int32)
-            _lib.check(L.nt_ambient_occlusion(self._handle, width, height, counts.ctypes.data, C.byref(opts)))
-            return counts
-        import torch
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("device must be a HIP device")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if self.ambient_occlusion is None:
-            raise ValueError("ambient occlusion is off (set_ambient_occlusion)")
-        counts = torch.empty((height, width), dtype=torch.int32, device=dev)
-        opts = self._rays_opts(dev, strict_reference)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.nt_ambient_occlusion_device(self._handle, width, height, C.c_void_p(counts.data_ptr()), C.byref(opts), C.c_void_p(stream)))
-        return counts
+        return self._view_query("nt_ambient_occlusion", width, height, device, np.int32, "ambient_occlusion",
+                                "ambient occlusion is off (set_ambient_occlusion)", strict_reference)
 
     def set_outlines(self, crease_angle=0.1, depth_gap=0.02, color=(0, 0, 0), strength=1.0):
         """Draw a line along the silhouette, along every edge where two facets meet and along every jump in depth (DESIGN.md
@@ -1085,32 +1084,8 @@ class _SceneBase(Scene):
         """The outline mask of a width x height view of the scene's camera under the setting that is on (nt_outline_mask): uint8
         [height][width], 0 or an OR of NT_OUTLINE_SILHOUETTE, NT_OUTLINE_CREASE and NT_OUTLINE_DEPTH -- a numpy array, or with
         `device` a torch device a torch tensor there, enqueued on torch's current stream."""
-        width, height = int(width), int(height)
-        if width < 1 or height < 1:
-            raise ValueError("the size of a view must be positive")
-        L = _lib.lib()
-        if device is None:
-            opts = _lib.NtRenderOpts()
-            opts.device = -1
-            if strict_reference is None:
-                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
-            opts.strict_reference = 1 if strict_reference else 0
-            mask = np.zeros((height, width), np.uint8)
-            _lib.check(L.nt_outline_mask(self._handle, width, height, mask.ctypes.data, None, C.byref(opts)))
-            return mask
-        import torch
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("device must be a HIP device")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if self.outlines is None:
-            raise ValueError("outlines are off (set_outlines)")
-        mask = torch.empty((height, width), dtype=torch.uint8, device=dev)
-        opts = self._rays_opts(dev, strict_reference)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.nt_outline_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
-        return mask
+        return self._view_query("nt_outline_mask", width, height, device, np.uint8, "outlines", "outlines are off (set_outlines)",
+                                strict_reference, counted=True)
 
     def set_depth_cue(self, near=0.0, far=1.0, color=(0, 0, 0), strength=1.0, background=False, tint_axis=None, tint_range=None,
                       tint_colors=None):
@@ -1178,32 +1153,8 @@ class _SceneBase(Scene):
         """The two factors (f, g) of every pixel of a width x height view of the scene's camera under the setting that is on
         (nt_depth_cue_factors): float32 [height][width][2], f the fog factor and g the tint factor, -1 where the pixel carries
         none -- a numpy array, or with `device` a torch device a torch tensor there, enqueued on torch's current stream."""
-        width, height = int(width), int(height)
-        if width < 1 or height < 1:
-            raise ValueError("the size of a view must be positive")
-        L = _lib.lib()
-        if device is None:
-            opts = _lib.NtRenderOpts()
-            opts.device = -1
-            if strict_reference is None:
-                strict_reference = os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0")
-            opts.strict_reference = 1 if strict_reference else 0
-            factors = np.zeros((height, width, 2), f32)
-            _lib.check(L.nt_depth_cue_factors(self._handle, width, height, factors.ctypes.data, C.byref(opts)))
-            return factors
-        import torch
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("device must be a HIP device")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if self.depth_cue is None:
-            raise ValueError("the depth cue is off (set_depth_cue)")
-        factors = torch.empty((height, width, 2), dtype=torch.float32, device=dev)
-        opts = self._rays_opts(dev, strict_reference)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.nt_depth_cue_factors_device(self._handle, width, height, C.c_void_p(factors.data_ptr()), C.byref(opts), C.c_void_p(stream)))
-        return factors
+        return self._view_query("nt_depth_cue_factors", width, height, device, f32, "depth_cue", "the depth cue is off (set_depth_cue)",
+                                strict_reference, tail=(2,))
 
     def set_clip_planes(self, planes):
         """Cutaway views (include/ntracer_hip.h): `planes` is a sequence of up to 8 (normal, offset) pairs, a
@@ -1524,30 +1475,8 @@ class BoxScene(_SceneBase):
         """The face-line mask of a width x height view of the scene's camera under the setting that is on (nt_box_line_mask):
         uint8 [height][width], 0 or an OR of NT_OUTLINE_SILHOUETTE and NT_OUTLINE_CREASE -- a numpy array, or with `device` a
         torch device a torch tensor there, enqueued on torch's current stream."""
-        width, height = int(width), int(height)
-        if width < 1 or height < 1:
-            raise ValueError("the size of a view must be positive")
-        L = _lib.lib()
-        if device is None:
-            opts = _lib.NtRenderOpts()
-            opts.device = -1
-            mask = np.zeros((height, width), np.uint8)
-            _lib.check(L.nt_box_line_mask(self._handle, width, height, mask.ctypes.data, None, C.byref(opts)))
-            return mask
-        if self.face_lines is None:
-            raise ValueError("face lines are off (set_face_lines)")
-        import torch
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("device must be a HIP device")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        mask = torch.empty((height, width), dtype=torch.uint8, device=dev)
-        opts = _lib.NtRenderOpts()
-        opts.device = dev.index
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.nt_box_line_mask_device(self._handle, width, height, C.c_void_p(mask.data_ptr()), C.byref(opts), C.c_void_p(stream)))
-        return mask
+        return self._view_query("nt_box_line_mask", width, height, device, np.uint8, "face_lines", "face lines are off (set_face_lines)",
+                                counted=True, plain=True)
 
 
 _FLAT_KEYS = ("root", "node_axis", "node_split", "node_left", "node_right", "items", "batch_recs", "batch_mats",

@@ -354,7 +354,10 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     with pytest.raises(NotImplementedError, match="ambient occlusion"):
         sc.set_supersampling(3)
         ntracer_amd.BlockingRenderer().render(bytearray(size), fmt, sc)
-    # ao_check says each of them in its own words; the row range is a guard for callers inside nt_api.cpp (the entry points
-    # hand over whole images unless band_world > 1, which is refused first), so it can only be read, not reached
-    api = _body(_read("nt_api.cpp"), "int ao_check(")
-    assert len(re.findall(r'fail\(NT_E_UNSUPPORTED, "ambient occlusion is not available', api)) == 6 and "row range" in api
+    # each of them in the setting's own words, which tests/view_setting_refusals.py has byte for byte and
+    # tests/test_view_setting_refusals.py holds every render form to; the sixth, the row range, is a guard for callers inside
+    # nt_api.cpp (the entry points hand over whole images unless band_world > 1, which is refused first), so it can only be
+    # read, not reached: the same test reads it
+    import view_setting_refusals as vr
+    words = [m for (setting, _), m in vr.RENDER_REFUSALS.items() if setting == "ao"]
+    assert len(words) == 5 and all(m.startswith("ambient occlusion is not available") for m in words)

@@ -250,12 +250,16 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     with pytest.raises(NotImplementedError, match="face lines"):
         ntracer_amd.BlockingRenderer().render(bytearray(size), fmt, box)
     assert not box.locked
-    # box_lines_check says each of them in its own words; the row range is a guard for callers inside nt_api.cpp
-    api = _body(_read("nt_api.cpp"), "int box_lines_check(")
-    assert api.count('"face lines are not available') == 6 and "for a row range" in api
-    # ... and every render entry point reaches it through render_checks, ahead of the lens and the projection
+    # each of them in the setting's own words, which tests/view_setting_refusals.py has byte for byte and
+    # tests/test_view_setting_refusals.py holds every render form to; the sixth, the row range, is a guard for callers inside
+    # nt_api.cpp, which the same test reads
+    import view_setting_refusals as vr
+    words = [m for (setting, _), m in vr.RENDER_REFUSALS.items() if setting == "face lines"]
+    assert len(words) == 5 and all(m.startswith("face lines are not available") for m in words)
+    # ... and every render entry point reaches them through render_checks, whose walk of the settings' table stands ahead of the
+    # lens and the projection
     checks = _body(_read("nt_api.cpp"), "int render_checks(")
-    assert checks.index("box_lines_check(") < checks.index("lens_check(") < checks.index("parallel_check(")
+    assert checks.index("kViewSettings") < checks.index("whole_view_check(") < checks.index("lens_check(") < checks.index("parallel_check(")
 
 
 @pytest.mark.skipif(_lib.lib().nt_device_count() > 0, reason="checks the no-GPU behaviour")

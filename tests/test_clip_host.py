@@ -407,11 +407,16 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     origins, axes = np.zeros((1, n), np.float32), np.eye(n, dtype=np.float32)[None].copy()
     for status in forms(sc, None):
         assert status == _lib.NT_E_UNSUPPORTED and _lib.last_error().startswith("depth cue")
-    api = _body(_read("nt_api.cpp"), "int clip_check(")
-    assert len(re.findall(r'fail\(NT_E_UNSUPPORTED, "clip planes are not available', api)) == 10 and "row range" in api
-    # render_checks asks clip_check first, and enqueue sends the scene to enqueue_clip before any other setting's route
-    checks = _body(_read("nt_api.cpp"), "int render_checks(")
-    assert checks.index("clip_check(") < checks.index("cue_check(")
+    # each of them in the setting's own words, which tests/view_setting_refusals.py has byte for byte and
+    # tests/test_view_setting_refusals.py holds every render form to; the tenth, the row range, is a guard for callers inside
+    # nt_api.cpp, which the same test reads
+    import view_setting_refusals as vr
+    words = [m for (setting, _), m in vr.RENDER_REFUSALS.items() if setting == "clip"]
+    assert len(words) == 9 and all(m.startswith("clip planes are not available") for m in words)
+    # render_checks asks the planes first -- of the planes and the cue the planes refuse --, and enqueue sends the scene to
+    # enqueue_clip before any other setting's route
+    assert vr.RENDER_REFUSALS["clip", "cue"] == "clip planes are not available while depth cues are on"
+    assert ("cue", "clip") not in vr.RENDER_REFUSALS and "kViewSettings" in _body(_read("nt_api.cpp"), "int render_checks(")
     enq = _body(_read("nt_api.cpp"), "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert enq.index("enqueue_clip(") < enq.index("enqueue_cue(")
 

@@ -126,8 +126,11 @@ def test_every_cue_launch_has_a_row_and_every_row_a_gpu_case():
     # the cue's dispatch and its check stand in front of every other setting's
     body = _body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert 0 < body.index("return enqueue_cue(") < body.index("return enqueue_outlines(")
-    checks = _body(api, "int render_checks(")
-    assert 0 < checks.index("cue_check(") < checks.index("outline_check(")
+    # (render_checks walks the table of the settings, the cue above the outlines: of the two the cue refuses, as
+    # tests/test_view_setting_refusals.py finds of the library)
+    import view_setting_refusals as vr
+    assert vr.RENDER_REFUSALS["cue", "outlines"] == "depth cues are not available while outlines are on"
+    assert ("outlines", "cue") not in vr.RENDER_REFUSALS and "kViewSettings" in _body(api, "int render_checks(")
     # the rule is written once, for both routes
     hpp = _read("nt_cue.hpp")
     assert len(re.findall(r"void cue_pixel\(", hpp)) == 1 and len(re.findall(r"void cue_blend\(", hpp)) == 1
@@ -440,6 +443,9 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     sc.set_ambient_occlusion(4, 1.0)
     for status in forms(None):
         assert status == _lib.NT_E_UNSUPPORTED and _lib.last_error().startswith("outlines")
-    # cue_check says each of them in its own words; the row range is a guard for callers inside nt_api.cpp
-    api = _body(_read("nt_api.cpp"), "int cue_check(")
-    assert len(re.findall(r'fail\(NT_E_UNSUPPORTED, "depth cues are not available', api)) == 8 and "row range" in api
+    # each of them in the setting's own words, which tests/view_setting_refusals.py has byte for byte and
+    # tests/test_view_setting_refusals.py holds every render form to; the eighth, the row range, is a guard for callers inside
+    # nt_api.cpp, which the same test reads
+    import view_setting_refusals as vr
+    words = [m for (setting, _), m in vr.RENDER_REFUSALS.items() if setting == "cue"]
+    assert len(words) == 7 and all(m.startswith("depth cues are not available") for m in words)

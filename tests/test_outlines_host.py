@@ -125,11 +125,14 @@ def test_every_outline_launch_has_a_row_and_every_row_a_gpu_case():
     assert "const bool fast = composite_route(s, sw).packet_walk;" in enq and "all_opaque" not in enq and "getenv" not in enq
     for name in ("nt_outline.hpp", "nt_inst_outline.hip"):
         assert "getenv" not in _read(name)
-    # the outline dispatch stands in front of the ambient-occlusion one, and the check in front of ao_check
+    # the outline dispatch stands in front of the ambient-occlusion one, and the check in front of ambient occlusion's
     body = _body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert 0 < body.index("return enqueue_outlines(") < body.index("return enqueue_ao(")
-    checks = _body(api, "int render_checks(")
-    assert 0 < checks.index("outline_check(") < checks.index("ao_check(")
+    # (render_checks walks the table of the settings, outlines above ambient occlusion: of the two the outlines refuse, as
+    # tests/test_view_setting_refusals.py finds of the library)
+    import view_setting_refusals as vr
+    assert vr.RENDER_REFUSALS["outlines", "ao"] == "outlines are not available while ambient occlusion is on"
+    assert ("ao", "outlines") not in vr.RENDER_REFUSALS and "kViewSettings" in _body(api, "int render_checks(")
     # the pair rule is written once
     assert len(re.findall(r"int outline_pair\(", _read("nt_outline.hpp"))) == 1 and "outline_pair(" in var
     assert "NT_DEV_OUTLINE_CREASE" not in var and "c * c <" not in _body(var, "void outline_mark(")
@@ -403,6 +406,9 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     sc.set_lens(tracern.Lens.pinhole(w, h, 0.8))
     for status in forms(None):
         assert status == _lib.NT_E_UNSUPPORTED and _lib.last_error().startswith("ambient occlusion")
-    # outline_check says each of them in its own words; the row range is a guard for callers inside nt_api.cpp
-    api = _body(_read("nt_api.cpp"), "int outline_check(")
-    assert len(re.findall(r'fail\(NT_E_UNSUPPORTED, "outlines are not available', api)) == 7 and "row range" in api
+    # each of them in the setting's own words, which tests/view_setting_refusals.py has byte for byte and
+    # tests/test_view_setting_refusals.py holds every render form to; the seventh, the row range, is a guard for callers inside
+    # nt_api.cpp, which the same test reads
+    import view_setting_refusals as vr
+    words = [m for (setting, _), m in vr.RENDER_REFUSALS.items() if setting == "outlines"]
+    assert len(words) == 6 and all(m.startswith("outlines are not available") for m in words)
