@@ -763,6 +763,55 @@ int nt_box_line_mask(nt_scene_t *s, int width, int height, uint8_t *mask, long l
    every other field must be 0. */
 int nt_box_line_mask_device(nt_scene_t *s, int width, int height, void *mask_dev, const nt_render_opts *opts, void *hip_stream);
 
+/* ---- BoxScene face shading ---------------------------------------------------------------------------------------------
+   A colour of its own for each of the 2n faces of the cube, and the depth cues of CompositeScene -- distance fog and a
+   coordinate tint ("colour by w") -- from the face record of the render itself.  BoxScene only.  Everything below is fp32
+   without contraction, sums left to right, clamp01(v) = max(0, min(1, v)).  The host forms two reciprocals once, in fp32:
+   inv_fog = 1.0f / (fog_far - fog_near) and, with a tint, inv_tint = 1.0f / (tint_hi - tint_lo).
+   For pixel p of a W x H view let R(p) = (dist, i, l) be the record that nt_box_hits defines (item = i, lane = l), d the unit
+   direction formed there, o the camera's origin and T the face-colour table [n][2][3], T[i][l] the colour of the face at +1
+   (l = 1) or -1 (l = 0) of axis i; without a table of the caller's own every entry is (1.0f, 0.5f, 0.5f).
+     hit (i >= 0):  shade = fabsf(d_i) and B.c = shade * T[i][l][c];
+     no hit:        B = the plain background colour of d_0: d_0 > 0 ? (d_0, d_0, d_0) : (0, -d_0, -d_0);
+     P.c = clamp01(B.c), a zero as +0 (the background's -d_0 is -0 where d_0 is +0; the plain frame stores +0 there too);
+     the factors (f, g), the depth cues' rule with "item >= 0" read as "hit", n_transparent = 0 and t = dist:
+       hit:     f = clamp01((t - fog_near) * inv_fog); with a tint x_k = (d_k * t) + o_k, s = tint_axis_0 * x_0, then
+                s = s + (tint_axis_k * x_k) for k = 1 .. n - 1, and g = clamp01((s - tint_lo) * inv_tint); without a tint g = -1;
+       no hit:  with fog_background set f = 1, g = -1; otherwise f = -1, g = -1;
+       without a cue f = g = -1 everywhere;
+     Q = P;  if g >= 0:  Q.c = P.c * ((tint_color_lo.c * (1.0f - g)) + (tint_color_hi.c * g));
+             if f >= 0:  w = f * fog_strength and Q.c = (Q.c * (1.0f - w)) + (fog_color.c * w);
+     with face lines on as well (nt_scene_set_box_lines): the mask byte is exactly the face-line rule's, and a pixel with a
+     non-zero mask becomes (Q.c * (1.0f - strength)) + (color.c * strength) with the lines' own colour and strength;
+   and the result goes through the format's conversion and packing as always.  With no table, no tint and fog_strength = 0
+   the frame is the plain frame byte for byte, in every format -- with lines on, the face-line frame -- and likewise with only
+   a table equal to the default.
+   nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device honour the setting, and refuse with
+   NT_E_UNSUPPORTED ("face shading is not available ...") before a device is touched, drawing nothing, for a supersampling
+   factor above 1 (adaptive or not), row bands, collect_stats, a lens, the parallel projection (and a row range, which only a
+   caller inside the library can ask for); with face lines on as well, that setting's words answer.  nt_colors_at /
+   nt_calculate_color, nt_ray_colors*, nt_render_rays*, nt_adaptive_mask*, nt_box_hits* and nt_box_line_mask* ignore it.  There
+   is no buffer entry point of its own: the render in the plain fp32 format is the buffer.
+   Up to 24 dimensions one kernel forms the records and draws from them -- in registers, or with face lines in LDS as the
+   face-line kernel does: no record crosses device memory and nothing is allocated.  Above (and under NTRACER_FORCE_VAR=1) the
+   records of whole frames go through a scratch of 16 bytes a pixel and frame under the cap of
+   nt_scene_set_supersampling_scratch_mb, larger jobs in chunks of whole frames; a single frame that does not fit is
+   NT_E_UNSUPPORTED before anything is launched.
+
+   face_colors: [dimension][2][3] floats, finite and in [0, 1], or NULL for the default table.  cue and tint_axis are validated
+   exactly as nt_scene_set_depth_cue validates them (tint_axis == NULL means no tint; a tint_axis without a cue, which holds the
+   tint's range and colours, is NT_E_INVALID).  face_colors == NULL && cue == NULL takes the setting off.  NT_E_INVALID for a
+   CompositeScene ("not a box scene": nt_scene_set_depth_cue is its counterpart) and for a bad value -- the setting stays as it
+   was; NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it.  The setting is not part of a
+   pickled scene. */
+int nt_scene_set_box_shading(nt_scene_t *s, const float *face_colors /* [n][2][3] or NULL */,
+                             const nt_depth_cue *cue /* or NULL */, const float *tint_axis /* or NULL */);
+/* any out pointer may be NULL: *enabled, *has_colors, *has_cue, *has_tint 0 or 1; face_colors [dimension][2][3] floats (the
+   default table without one of the caller's); *cue zeroes without a cue, its tint fields zero without a tint; tint_axis
+   `dimension` floats (zeroes without a tint) */
+int nt_scene_get_box_shading(const nt_scene_t *s, int *enabled, int *has_colors, float *face_colors,
+                             int *has_cue, nt_depth_cue *cue, int *has_tint, float *tint_axis);
+
 #ifdef __cplusplus
 }
 #endif

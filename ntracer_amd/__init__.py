@@ -7,10 +7,10 @@ libntracer_hip.so (include/ntracer_hip.h); there is no CPU fallback.
 """
 from .render import (BlockingRenderer, CallbackRenderer, Channel, Color, ImageFormat, LockedError, Material,  # noqa: F401
                      Scene)
-from .tracern import CUBE, SPHERE, FaceHits, Lens, clip_plane_through, sphere_directions  # noqa: F401
+from .tracern import CUBE, SPHERE, FaceHits, Lens, clip_plane_through, face_palette, sphere_directions  # noqa: F401
 from ._lib import NT_OUTLINE_SILHOUETTE, NT_OUTLINE_CREASE, NT_OUTLINE_DEPTH  # noqa: F401
 from .wrapper import NTracer  # noqa: F401
 
 __all__ = ["NTracer", "Material", "ImageFormat", "Channel", "BlockingRenderer", "CallbackRenderer", "Color",
-           "LockedError", "Scene", "CUBE", "SPHERE", "Lens", "sphere_directions", "FaceHits", "clip_plane_through",
+           "LockedError", "Scene", "CUBE", "SPHERE", "Lens", "sphere_directions", "FaceHits", "clip_plane_through", "face_palette",
            "NT_OUTLINE_SILHOUETTE", "NT_OUTLINE_CREASE", "NT_OUTLINE_DEPTH"]

@@ -194,6 +194,9 @@ SYMBOLS = [
                                            C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_set_box_lines", C.c_int, [C.c_void_p, C.c_int, f32p, C.c_float]),
     ("nt_scene_get_box_lines", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p]),
+    ("nt_scene_set_box_shading", C.c_int, [C.c_void_p, f32p, C.POINTER(NtDepthCue), f32p]),
+    ("nt_scene_get_box_shading", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), f32p, C.POINTER(C.c_int),
+                                           C.POINTER(NtDepthCue), C.POINTER(C.c_int), f32p]),
     ("nt_box_line_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
     ("nt_box_line_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_ray_colors", C.c_int, [C.c_void_p, C.POINTER(NtRays), C.c_void_p, C.c_int]),

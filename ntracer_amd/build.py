@@ -3,8 +3,8 @@
 hipcc cross-compiles gfx950 code objects without a GPU.  The kernels are templates over the dimension; every
 dimension is its own translation unit: csrc/nt_inst_X.hip with -DNT_INST_N=N defines the one launcher nt_X_fixed<N> that
 csrc/nt_dispatch.hpp declares and csrc/nt_var.hip dispatches to (and does not compile without the macro).  N = 3..24 for
-nt_inst_box.hip, nt_inst_rays.hip, nt_inst_adaptive.hip (BoxScene's kernels; CompositeScene's up to 10) and nt_inst_boxhits.hip
-(whose launcher is nt_box_faces<N>), 3..10 for
+nt_inst_box.hip, nt_inst_rays.hip, nt_inst_adaptive.hip (BoxScene's kernels; CompositeScene's up to 10), nt_inst_boxhits.hip
+(whose launcher is nt_box_faces<N>) and nt_inst_boxshade.hip (nt_box_shade<N>), 3..10 for
 nt_inst_composite.hip, nt_inst_query.hip, nt_inst_hits.hip, nt_inst_lens.hip, nt_inst_parallel.hip, nt_inst_ao.hip,
 nt_inst_outline.hip, nt_inst_cue.hip (whose launcher is nt_cue_packet<N>) and nt_inst_clip.hip (nt_clip_packet<N>).  units() is
 the list, and
@@ -25,7 +25,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libntracer_hip.so")
 DIMS = range(3, 11)
 BOX_ONLY_DIMS = range(11, 25)         # BoxScene kernels alone are also compiled for N = 11..24
-HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_box_span.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp", "nt_cue.hpp", "nt_clip.hpp", "nt_boxhits.hpp", "nt_dispatch.hpp")] + \
+HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.hpp", "nt_box_span.hpp", "nt_composite.hpp", "nt_resolve.hpp", "nt_query.hpp", "nt_hits.hpp", "nt_rays.hpp", "nt_lens.hpp", "nt_parallel.hpp", "nt_adaptive.hpp", "nt_ao.hpp", "nt_outline.hpp", "nt_cue.hpp", "nt_clip.hpp", "nt_boxhits.hpp", "nt_boxshade.hpp", "nt_dispatch.hpp")] + \
       [os.path.join(HERE, "..", "include", "ntracer_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function"]
@@ -50,11 +50,13 @@ def units():
         u.append(("nt_cue_%d" % n, "nt_inst_cue.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_clip_%d" % n, "nt_inst_clip.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
     for n in BOX_ONLY_DIMS:
         u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))      # (BoxScene's kernel alone)
         u.append(("nt_adaptive_%d" % n, "nt_inst_adaptive.hip", ["-DNT_INST_N=%d" % n]))  # (likewise)
         u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
     return u
 
 

@@ -199,6 +199,12 @@ struct nt_scene {
     unsigned long long clip_version = 1; // counts the changes of clip_planes
     int box_lines = 0;                   // BoxScene: != 0, the kinds of face lines on the renders (nt_scene_set_box_lines)
     float bl_color[3] = {0, 0, 0}, bl_strength = 0.0f;
+    bool box_shading = false;            // BoxScene: face colours, fog and a tint on the renders (nt_scene_set_box_shading)
+    bool bs_colors = false, bs_cue = false, bs_tint = false;   // ... which of its three parts the caller gave,
+    std::vector<float> bs_table;         // ... the face colours [n][2][3], empty without a table of the caller's own,
+    nt_depth_cue bs_set{};               // ... the cue as the caller gave it, the tint's fields zero without a tint,
+    std::vector<float> bs_axis;          // ... the tint axis [n], empty without a tint,
+    float bs_inv_fog = 0.0f, bs_inv_tint = 0.0f;     // ... and the two reciprocals of the rule, formed once
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -1124,7 +1130,8 @@ int hits_enqueue(nt_scene *s, DeviceState *ds, int width, int height, const nt_h
 // A setting whose render comes from a pass over the records of the whole pinhole view, one sample a pixel, no kernel of which
 // keeps counters.  The table is in the order of precedence: a scene with two of them on is refused by the one nearer the top,
 // in `while_on`'s words of the other, not drawn with one of them missing.  Face lines are BoxScene's: they neither refuse the
-// composite settings nor are refused by them (no `while_on`).  The next setting is one more row, and one more line of enqueue.
+// composite settings nor are refused by them (no `while_on`), and neither is face shading, which draws the lines itself when both
+// are on.  The next setting is one more row, and one more line of enqueue.
 struct ViewSetting {
     bool (*on)(const nt_scene *s);
     const char *subject;                 // of every message: "<subject> not available ..."
@@ -1132,7 +1139,7 @@ struct ViewSetting {
     const char *while_on;                // how the rows above name this setting when they refuse it
     int (*extra)(const nt_scene *s);     // a term of its own, after all the others, or nullptr
 };
-enum { VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_COUNT };
+enum { VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_BOX_SHADING, VS_COUNT };
 const ViewSetting kViewSettings[VS_COUNT] = {
     {[](const nt_scene *s) { return s->clip_count > 0; }, "clip planes are", "", nullptr,
      // a Solid cut open needs a cap or an inner wall, which nothing defines: refused, not approximated
@@ -1143,6 +1150,7 @@ const ViewSetting kViewSettings[VS_COUNT] = {
     {[](const nt_scene *s) { return s->outlines; }, "outlines are", ": a pixel's mask needs its neighbours", "outlines are on", nullptr},
     {[](const nt_scene *s) { return s->ao_count > 0; }, "ambient occlusion is", "", "ambient occlusion is on", nullptr},
     {[](const nt_scene *s) { return s->box_lines && !s->composite; }, "face lines are", ": a pixel's mask needs its neighbours", nullptr, nullptr},
+    {[](const nt_scene *s) { return s->box_shading && !s->composite; }, "face shading is", "", nullptr, nullptr},
 };
 
 // What a render with the setting of `row` on refuses, checked by the entry points before a device is touched (render_checks) and
@@ -1605,6 +1613,76 @@ int enqueue_box_lines(nt_scene *s, DeviceState *ds, const FrameJob &job, const R
 }
 
 // ---------------------------------------------------------------------------------------------
+// BoxScene face shading (nt_scene_set_box_shading; kernels in nt_boxshade.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+// The render shaded from the face records, with the face lines on top when that setting is on too.  Up to NT_MAX_FIXED_BOX_DIM
+// dimensions one kernel forms the records and draws from them -- in registers, or with lines in LDS -- and needs no scratch.  At
+// run-time n (and under NTRACER_FORCE_VAR=1) box_hits_var writes 16 bytes a pixel and frame into scratch under the supersampling
+// cap and box_shaded_var reads them: per chunk of whole frames.  Enqueue only.
+int enqueue_box_shading(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw) {
+    const char *noun = "face shading";
+    // (with face lines on as well their row, nearer the top, answers first: for every way in, as for the entry points)
+    if (int r = whole_view_check(s, kViewSettings[VS_BOX_LINES], job.bands, job.stats, job.row_begin, job.row_count, job.fmt->height)) return r;
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, &kViewSettings[VS_BOX_SHADING], noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const int n = s->n;
+    const long long px = vp.px;
+    const bool var = n > NT_MAX_FIXED_BOX_DIM || sw.force_var;
+    long long chunk_frames = job.nframes;                               // (the fixed-n kernels' frames need no scratch: one chunk)
+    void *recs = nullptr;
+    if (var) {
+        if (int r = plan_scratch_frames(vp, job.nframes, noun, nullptr, px * 16, (long long)s->ss_scratch_mb << 20, std::max(sw.chunk_frames, 1),
+                                        chunk_frames)) return r;
+        Scratch at;
+        if (int e = at.open(ds, (size_t)(chunk_frames * px * 16))) return e;
+        recs = at.take<void>((size_t)chunk_frames * px * 16);
+    }
+    NtBoxShade bs{};
+    bool gb = true;
+    for (int k = 0; k < 2 * n; ++k) {
+        float *t = bs.colors + 3 * k;
+        t[0] = s->bs_colors ? s->bs_table[3 * k] : 1.0f;
+        t[1] = s->bs_colors ? s->bs_table[3 * k + 1] : 0.5f;
+        t[2] = s->bs_colors ? s->bs_table[3 * k + 2] : 0.5f;
+        gb = gb && t[1] == t[2];
+    }
+    NtCue &cu = bs.cue;
+    bs.cue_on = s->bs_cue ? 1 : 0;
+    if (s->bs_cue) {
+        cu.fog_near = s->bs_set.fog_near;
+        cu.inv_fog = s->bs_inv_fog;
+        cu.fog_strength = s->bs_set.fog_strength;
+        cu.fog_background = s->bs_set.fog_background != 0;
+        cu.tint = s->bs_tint ? 1 : 0;
+        cu.tint_lo = s->bs_set.tint_lo;
+        cu.inv_tint = s->bs_inv_tint;
+        for (int k = 0; k < 3; ++k) {
+            cu.fog_color[k] = s->bs_set.fog_color[k];
+            cu.tint_color_lo[k] = s->bs_set.tint_color_lo[k];
+            cu.tint_color_hi[k] = s->bs_set.tint_color_hi[k];
+        }
+        for (int k = 0; k < n && s->bs_tint; ++k) cu.tint_axis[k] = s->bs_axis[k];
+        gb = gb && cu.fog_color[1] == cu.fog_color[2];
+        if (s->bs_tint) gb = gb && cu.tint_color_lo[1] == cu.tint_color_lo[2] && cu.tint_color_hi[1] == cu.tint_color_hi[2];
+    }
+    bs.gb_equal = gb ? 1 : 0;
+    bs.kinds = s->box_lines;
+    for (int k = 0; k < 3; ++k) bs.line_color[k] = s->bl_color[k];
+    bs.line_strength = s->bl_strength;
+    bs.recs = recs;
+    bs.frame_stride = px;
+    for (int f0 = 0; f0 < job.nframes; f0 += (int)chunk_frames) {
+        const ViewChunk ch = view_chunk(s, ds, job, sw, vp, f0, chunk_frames);
+        NtCamera cam;
+        box_camera(s, job.cam_buf, job.cam_dots, f0, cam);
+        if (int r = nt_launch_box_shade(ch.li, cam, ch.ft, bs)) return launch_failed(r);
+    }
+    return NT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // depth cues (nt_scene_set_depth_cue; kernels in nt_cue.hpp and nt_var.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -1911,6 +1989,7 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     if (s->cue && s->composite && whole) return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
     if (s->outlines && s->composite && whole) return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->ao_count > 0 && s->composite && whole) return enqueue_ao(s, ds, job, sw, nullptr, nullptr);
+    if (s->box_shading && !s->composite && whole) return enqueue_box_shading(s, ds, job, sw);     // (and the lines, when both are on)
     if (s->box_lines && !s->composite && whole) return enqueue_box_lines(s, ds, job, sw, nullptr, false, nullptr);
     if (s->lens) return enqueue_lens(s, ds, job, sw);
     if (s->parallel > 0.0f) return enqueue_parallel(s, ds, job, sw);
@@ -3075,6 +3154,40 @@ int nt_scene_get_box_lines(const nt_scene_t *s, int *kinds, float color[3], floa
 
 namespace {
 bool cue_unit(float v) { return v >= 0.0f && v <= 1.0f; }          // (false for a NaN)
+
+// what nt_scene_set_depth_cue and nt_scene_set_box_shading check of a cue and its tint axis, and what they keep of them: the cue
+// with fog_background 0 or 1 and the tint's fields zero without a tint, the axis, the two reciprocals
+int cue_validate(int n, const nt_depth_cue *cue, const float *tint_axis, nt_depth_cue &set, std::vector<float> &axis, float &inv_fog, float &inv_tint) {
+    set = *cue;
+    set.fog_background = cue->fog_background != 0;
+    if (!std::isfinite(set.fog_near) || !std::isfinite(set.fog_far) || !(set.fog_near >= 0.0f) || !(set.fog_far > set.fog_near))
+        return fail(NT_E_INVALID, "the depth cue's fog range must be finite with 0 <= fog_near < fog_far");
+    inv_fog = 1.0f / (set.fog_far - set.fog_near);
+    if (!std::isfinite(inv_fog)) return fail(NT_E_INVALID, "the depth cue's fog range is too narrow: 1 / (fog_far - fog_near) is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!cue_unit(set.fog_color[k])) return fail(NT_E_INVALID, "the depth cue's fog colour components must lie in [0, 1]");
+    if (!cue_unit(set.fog_strength)) return fail(NT_E_INVALID, "the depth cue's fog_strength must lie in [0, 1]");
+    if (tint_axis) {
+        if (!std::isfinite(set.tint_lo) || !std::isfinite(set.tint_hi) || !(set.tint_hi > set.tint_lo))
+            return fail(NT_E_INVALID, "the depth cue's tint range must be finite with tint_lo < tint_hi");
+        inv_tint = 1.0f / (set.tint_hi - set.tint_lo);
+        if (!std::isfinite(inv_tint)) return fail(NT_E_INVALID, "the depth cue's tint range is too narrow: 1 / (tint_hi - tint_lo) is not finite");
+        for (int k = 0; k < 3; ++k)
+            if (!cue_unit(set.tint_color_lo[k]) || !cue_unit(set.tint_color_hi[k]))
+                return fail(NT_E_INVALID, "the depth cue's tint colour components must lie in [0, 1]");
+        axis.assign(tint_axis, tint_axis + n);
+        bool any = false;
+        for (float v : axis) {
+            if (!std::isfinite(v)) return fail(NT_E_INVALID, "the depth cue's tint_axis must be finite");
+            any = any || v != 0.0f;
+        }
+        if (!any) return fail(NT_E_INVALID, "the depth cue's tint_axis must not be all zero");
+    } else {
+        set.tint_lo = set.tint_hi = 0.0f;
+        for (int k = 0; k < 3; ++k) set.tint_color_lo[k] = set.tint_color_hi[k] = 0.0f;
+    }
+    return NT_OK;
+}
 }  // namespace
 
 int nt_scene_set_depth_cue(nt_scene_t *s, const nt_depth_cue *cue, const float *tint_axis) {
@@ -3084,34 +3197,7 @@ int nt_scene_set_depth_cue(nt_scene_t *s, const nt_depth_cue *cue, const float *
     std::vector<float> axis;
     float inv_fog = 0.0f, inv_tint = 0.0f;
     if (cue) {
-        set = *cue;
-        set.fog_background = cue->fog_background != 0;
-        if (!std::isfinite(set.fog_near) || !std::isfinite(set.fog_far) || !(set.fog_near >= 0.0f) || !(set.fog_far > set.fog_near))
-            return fail(NT_E_INVALID, "the depth cue's fog range must be finite with 0 <= fog_near < fog_far");
-        inv_fog = 1.0f / (set.fog_far - set.fog_near);
-        if (!std::isfinite(inv_fog)) return fail(NT_E_INVALID, "the depth cue's fog range is too narrow: 1 / (fog_far - fog_near) is not finite");
-        for (int k = 0; k < 3; ++k)
-            if (!cue_unit(set.fog_color[k])) return fail(NT_E_INVALID, "the depth cue's fog colour components must lie in [0, 1]");
-        if (!cue_unit(set.fog_strength)) return fail(NT_E_INVALID, "the depth cue's fog_strength must lie in [0, 1]");
-        if (tint_axis) {
-            if (!std::isfinite(set.tint_lo) || !std::isfinite(set.tint_hi) || !(set.tint_hi > set.tint_lo))
-                return fail(NT_E_INVALID, "the depth cue's tint range must be finite with tint_lo < tint_hi");
-            inv_tint = 1.0f / (set.tint_hi - set.tint_lo);
-            if (!std::isfinite(inv_tint)) return fail(NT_E_INVALID, "the depth cue's tint range is too narrow: 1 / (tint_hi - tint_lo) is not finite");
-            for (int k = 0; k < 3; ++k)
-                if (!cue_unit(set.tint_color_lo[k]) || !cue_unit(set.tint_color_hi[k]))
-                    return fail(NT_E_INVALID, "the depth cue's tint colour components must lie in [0, 1]");
-            axis.assign(tint_axis, tint_axis + s->n);
-            bool any = false;
-            for (float v : axis) {
-                if (!std::isfinite(v)) return fail(NT_E_INVALID, "the depth cue's tint_axis must be finite");
-                any = any || v != 0.0f;
-            }
-            if (!any) return fail(NT_E_INVALID, "the depth cue's tint_axis must not be all zero");
-        } else {
-            set.tint_lo = set.tint_hi = 0.0f;
-            for (int k = 0; k < 3; ++k) set.tint_color_lo[k] = set.tint_color_hi[k] = 0.0f;
-        }
+        if (int r = cue_validate(s->n, cue, tint_axis, set, axis, inv_fog, inv_tint)) return r;
     }
     std::lock_guard<std::mutex> g(s->mu);
     if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
@@ -3130,6 +3216,51 @@ int nt_scene_get_depth_cue(const nt_scene_t *s, int *enabled, nt_depth_cue *cue,
     if (cue) *cue = s->cue_set;
     if (has_tint) *has_tint = s->cue_tint ? 1 : 0;
     if (tint_axis) for (int k = 0; k < s->n; ++k) tint_axis[k] = s->cue_tint ? s->cue_axis[k] : 0.0f;
+    return NT_OK;
+}
+
+int nt_scene_set_box_shading(nt_scene_t *s, const float *face_colors, const nt_depth_cue *cue, const float *tint_axis) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (s->composite) return fail(NT_E_INVALID, "not a box scene: CompositeScene has depth cues (nt_scene_set_depth_cue)");
+    std::vector<float> table, axis;
+    nt_depth_cue set{};
+    float inv_fog = 0.0f, inv_tint = 0.0f;
+    if (face_colors) {
+        table.assign(face_colors, face_colors + (size_t)s->n * 6);
+        for (float v : table)
+            if (!cue_unit(v)) return fail(NT_E_INVALID, "the face colours' components must lie in [0, 1]");
+    }
+    if (cue) {
+        if (int r = cue_validate(s->n, cue, tint_axis, set, axis, inv_fog, inv_tint)) return r;
+    } else if (tint_axis) {
+        return fail(NT_E_INVALID, "face shading: a tint_axis needs a cue, which holds the tint's range and colours");
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->box_shading = face_colors || cue;
+    s->bs_colors = face_colors != nullptr;
+    s->bs_cue = cue != nullptr;
+    s->bs_tint = cue && tint_axis;
+    s->bs_table = std::move(table);
+    s->bs_set = set;
+    s->bs_axis = std::move(axis);
+    s->bs_inv_fog = inv_fog;
+    s->bs_inv_tint = inv_tint;
+    return NT_OK;
+}
+
+int nt_scene_get_box_shading(const nt_scene_t *s, int *enabled, int *has_colors, float *face_colors, int *has_cue, nt_depth_cue *cue,
+                             int *has_tint, float *tint_axis) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (s->composite) return fail(NT_E_INVALID, "not a box scene");
+    if (enabled) *enabled = s->box_shading ? 1 : 0;
+    if (has_colors) *has_colors = s->bs_colors ? 1 : 0;
+    if (face_colors)
+        for (int k = 0; k < 6 * s->n; ++k) face_colors[k] = s->bs_colors ? s->bs_table[k] : (k % 3 == 0 ? 1.0f : 0.5f);
+    if (has_cue) *has_cue = s->bs_cue ? 1 : 0;
+    if (cue) *cue = s->bs_set;
+    if (has_tint) *has_tint = s->bs_tint ? 1 : 0;
+    if (tint_axis) for (int k = 0; k < s->n; ++k) tint_axis[k] = s->bs_tint ? s->bs_axis[k] : 0.0f;
     return NT_OK;
 }
 

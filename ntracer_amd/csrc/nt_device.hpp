@@ -370,7 +370,25 @@ struct NtBoxFaces {
     float color[3], strength; // DRAW
 };
 
+// BoxScene face shading (nt_boxshade.hpp, nt_var.hip; the rule in full: ntracer_hip.h): the frame shaded from
+// the face record of every pixel -- a colour of its own for each of the 2n faces, the depth cues' fog and tint from the same
+// record, and the face lines of NtBoxFaces on top.  The table and the tint axis travel in the kernel arguments; the kernels read
+// the table from LDS, where a block stages it once (a by-value array indexed by a lane's face would go to scratch).
+struct NtBoxShade {
+    NtCue cue;                // the depth cues' constants; recs, cams, nframes and factors are not read
+    int cue_on;               // 0: f = g = -1 everywhere
+    int gb_equal;             // the table, the tint colours and the fog colour all have g == b: so has every unmarked pixel
+    int kinds;                // != 0: face lines as NtBoxFaces has them, with ...
+    float line_color[3], line_strength;
+    void *recs;               // run-time n alone: scratch for box_hits_var's records, li.nframes frames of ...
+    long long frame_stride;   // ... this many records
+    float colors[NT_DEV_MAX_DIM * 6];     // T[axis][side][channel]; (1, 0.5, 0.5) everywhere without a table of the caller's
+};
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
+// BoxScene face shading: box_shaded<N, LINES> of the scene's dimension, or box_hits_var into bs.recs and box_shaded_var behind
+// it.  tg is the whole image of every frame (no bands).  The cameras travel as for nt_launch_box.
+int nt_launch_box_shade(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxShade &bs);
 // BoxScene hit buffers and face lines: the kernels of nt_boxhits.hpp at the scene's dimension, or box_hits_var (and, behind it,
 // box_lines_var on bf.recs).  RECORDS, MASK: tg is the view and the abort word; DRAW: the whole image of every frame (no bands).
 // The cameras travel as for nt_launch_box.

@@ -18,6 +18,7 @@ struct NtAo;
 struct NtOutline;
 struct NtCue;
 struct NtBoxFaces;
+struct NtBoxShade;
 struct NtClip;
 
 // The compile-time-N launchers, one family a primary template.  Nothing defines the primary: every dimension is the explicit
@@ -41,6 +42,8 @@ template <int N> int nt_cue_packet(const NtLaunchInfo &li, const NtCompositeDev 
 template <int N> int nt_clip_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtClip &cl, bool draw);
 // (BoxScene hit buffers, nt_inst_boxhits.hip: N = 3..NT_DEV_MAX_FIXED_BOX like the other BoxScene families)
 template <int N> int nt_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxFaces &bf);
+// (BoxScene face shading, nt_inst_boxshade.hip: N = 3..NT_DEV_MAX_FIXED_BOX likewise)
+template <int N> int nt_box_shade(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxShade &bs);
 
 template <int LO, typename F, int... I>
 inline bool nt_dispatch_dim_seq(int n, int &r, F &f, std::integer_sequence<int, I...>) {

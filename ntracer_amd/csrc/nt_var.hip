@@ -12,6 +12,7 @@
 #include "nt_outline.hpp"
 #include "nt_cue.hpp"
 #include "nt_boxhits.hpp"
+#include "nt_boxshade.hpp"
 #include "nt_dispatch.hpp"
 #include <climits>
 
@@ -2211,6 +2212,60 @@ __global__ __launch_bounds__(256) void box_lines_var(NtCamera cam, NtTarget tg, 
     emit_pixel(tg, pr, p[0], p[1], p[2]);
 }
 
+// Face shading at run-time n (nt_boxshade.hpp has the compile-time-N kernels and the rule's one copy), behind box_hits_var:
+// box_lines_var's shape -- one lane a pixel reads its record from `bs.recs`, with LINES those of its four neighbours inside the
+// image too -- re-forms its own ray exactly as box_hits_var formed it, d_k = v_k / |v|, for the shade, the background and the
+// tint sum, and hands over to box_shade_emit.  A block: 64 x 4 pixels of frame blockIdx.z; the camera's rows and the face-colour
+// table staged in LDS once a block.
+static_assert(sizeof(NtCamera) + sizeof(NtTarget) + sizeof(NtBoxShade) <= 4096, "box_shaded_var's arguments fit the kernel argument segment");
+template <bool LINES>
+__global__ __launch_bounds__(256) void box_shaded_var(NtCamera cam, NtTarget tg, NtBoxShade bs) {
+    extern __shared__ float lds_vec[];    // [4][n] camera rows (broadcast reads), then [2 n][3] the table
+    if (nt_aborted(tg)) return;           // (the whole block leaves, ahead of the barrier)
+    const int tid = (int)threadIdx.x;
+    const int n = cam.n;
+    {
+        const float *src = cam.buf ? cam.buf + (size_t)blockIdx.z * 4 * n : nullptr;
+        for (int k = tid; k < 4 * n; k += 256) lds_vec[k] = src ? src[k] : cam.inl[k];
+    }
+    float *tab = lds_vec + 4 * n;
+    box_shade_stage(bs, n, tid, 256, tab);
+    __syncthreads();
+    const int x = (int)blockIdx.x * 64 + (tid & 63), y = (int)blockIdx.y * 4 + (tid >> 6);
+    if (x >= tg.width || y >= tg.height) return;
+    const int4 *fr = reinterpret_cast<const int4 *>(bs.recs) + (long long)blockIdx.z * bs.frame_stride;
+    const int4 rec = fr[(long long)y * tg.width + x];
+    const float pd = __int_as_float(rec.x);
+    const int code = rec.y >= 0 ? 2 * rec.y + rec.z : -1;
+    int m = 0;
+    if (LINES && rec.y >= 0) {
+        for (int k = 0; k < 4; ++k) {
+            const int qx = x + (k == 0 ? -1 : (k == 1 ? 1 : 0));
+            const int qy = y + (k == 2 ? -1 : (k == 3 ? 1 : 0));
+            if (qx < 0 || qy < 0 || qx >= tg.width || qy >= tg.height) continue;
+            const int4 q = fr[(long long)qy * tg.width + qx];
+            m |= box_line_pair(pd, code, __int_as_float(q.x), q.y < 0 ? -1 : 2 * q.y + q.z);
+        }
+        m &= bs.kinds;
+    }
+    const float *c = lds_vec;             // origin, right, up, forward
+    const float sx = tg.fovI * ((float)x - tg.half_w);
+    const float sy = tg.fovI * ((float)y - tg.half_h);
+    const int pick = rec.y >= 0 ? rec.y : 0;
+    float sq = 0.0f, vp = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float v = (c[3 * n + j] + c[n + j] * sx) - c[2 * n + j] * sy;
+        sq = j == 0 ? v * v : sq + v * v;
+        vp = j == pick ? v : vp;
+    }
+    const float len = sqrtf(sq);
+    const float xval = vp / len;
+    float s = 0.0f;
+    if (rec.y >= 0 && bs.cue_on && bs.cue.tint)
+        s = box_shade_tint_sum(bs, n, pd, [&](int k) { return ((c[3 * n + k] + c[n + k] * sx) - c[2 * n + k] * sy) / len; }, [&](int k) { return c[k]; });
+    box_shade_emit(tg, bs, tab, box_shade_pixel(tg, x, y), code, pd, xval, s, m);
+}
+
 // --------------------------------------------------------------------------------------
 // A render through a lens (nt_lens.hpp) on the ray-colour kernels above: every scene the packet walk does not take.  The table
 // and the frame's camera are expanded into the unnormalised directions v[j] = (fwd[j] * sz + right[j] * sx) - up[j] * sy of a
@@ -2780,6 +2835,33 @@ int nt_launch_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTar
     }
     if (r) return r;
     return finish_launch("box face kernel launch");
+}
+
+// BoxScene face shading (nt_boxshade.hpp): the fixed-n launcher of the scene's dimension, or at run-time n box_hits_var into
+// bs.recs and box_shaded_var behind it.  Kept apart from nt_launch_box as nt_launch_box_faces is: no route of a plain render.
+int nt_launch_box_shade(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxShade &bs) {
+    int r = var_dim_check(li.n);
+    if (r) return r;
+    if (!nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n, r, [&](auto N) { return nt_box_shade<decltype(N)::value>(li, cam, tg, bs); })) {
+        if (!bs.recs || bs.frame_stride < (long long)tg.width * tg.height || tg.row_begin != 0 || tg.row_count != tg.height || tg.band_world > 1 ||
+            tg.colors_out) {
+            snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a face-shading launch at run-time n without its records, or not for whole frames");
+            return -1;
+        }
+        hipStream_t st = (hipStream_t)li.stream;
+        NtBoxFaces bf{};
+        bf.mode = NT_BOX_FACES_RECORDS;
+        bf.recs = bs.recs;
+        bf.frame_stride = bs.frame_stride;
+        const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + NT_BOXROWS - 1) / NT_BOXROWS), (unsigned)li.nframes);
+        hipLaunchKernelGGL(box_hits_var, grid, dim3(64), ((size_t)li.n * 64 + (size_t)4 * li.n) * sizeof(float), st, cam, tg, bf);
+        const dim3 sgrid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)li.nframes);
+        const size_t lds = (size_t)10 * li.n * sizeof(float);
+        if (bs.kinds) hipLaunchKernelGGL(box_shaded_var<true>, sgrid, dim3(256), lds, st, cam, tg, bs);
+        else hipLaunchKernelGGL(box_shaded_var<false>, sgrid, dim3(256), lds, st, cam, tg, bs);
+    }
+    if (r) return r;
+    return finish_launch("box shading kernel launch");
 }
 
 // words per ray_color frame of composite_kernel_var_t (the host sizes NtCompositeDev::tframes with it)

@@ -1102,35 +1102,7 @@ class _SceneBase(Scene):
         if near is None:
             _lib.check(L.nt_scene_set_depth_cue(self._handle, None, None))
             return
-        for v in (near, far, strength):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise ValueError("near, far and strength must be numbers")
-
-        def colour(c, what):
-            col = [float(v) for v in c]
-            if len(col) != 3:
-                raise ValueError("%s must have three components" % what)
-            return col
-
-        cue = _lib.NtDepthCue()
-        cue.fog_near, cue.fog_far, cue.fog_strength = float(near), float(far), float(strength)
-        cue.fog_color[:] = colour(color, "color")
-        cue.fog_background = 1 if background else 0
-        axis = None
-        if tint_axis is None:
-            if tint_range is not None or tint_colors is not None:
-                raise ValueError("tint_range and tint_colors need a tint_axis")
-        else:
-            if tint_range is None or tint_colors is None:
-                raise ValueError("a tint_axis needs tint_range and tint_colors")
-            axis = np.ascontiguousarray([float(v) for v in tint_axis], f32)
-            if axis.shape != (self.dimension,):
-                raise ValueError("tint_axis must have %d components" % self.dimension)
-            lo, hi = tint_range
-            cue.tint_lo, cue.tint_hi = float(lo), float(hi)
-            c_lo, c_hi = tint_colors
-            cue.tint_color_lo[:] = colour(c_lo, "tint_colors[0]")
-            cue.tint_color_hi[:] = colour(c_hi, "tint_colors[1]")
+        cue, axis = _fog_and_tint(self.dimension, near, far, color, strength, background, tint_axis, tint_range, tint_colors)
         _lib.check(L.nt_scene_set_depth_cue(self._handle, C.byref(cue), None if axis is None else axis.ctypes.data_as(_lib.f32p)))
 
     @property
@@ -1142,12 +1114,7 @@ class _SceneBase(Scene):
         _lib.check(_lib.lib().nt_scene_get_depth_cue(self._handle, C.byref(on), C.byref(cue), C.byref(tint), axis.ctypes.data_as(_lib.f32p)))
         if not on.value:
             return None
-        d = dict(near=float(cue.fog_near), far=float(cue.fog_far), color=tuple(float(c) for c in cue.fog_color),
-                 strength=float(cue.fog_strength), background=bool(cue.fog_background), tint_axis=None, tint_range=None, tint_colors=None)
-        if tint.value:
-            d.update(tint_axis=tuple(float(v) for v in axis), tint_range=(float(cue.tint_lo), float(cue.tint_hi)),
-                     tint_colors=(tuple(float(c) for c in cue.tint_color_lo), tuple(float(c) for c in cue.tint_color_hi)))
-        return d
+        return _fog_and_tint_dict(cue, tint.value, axis)
 
     def depth_cue_factors(self, width, height, device=None, strict_reference=None):
         """The two factors (f, g) of every pixel of a width x height view of the scene's camera under the setting that is on
@@ -1471,12 +1438,122 @@ class BoxScene(_SceneBase):
         return dict(silhouette=bool(kinds.value & _lib.NT_OUTLINE_SILHOUETTE), edges=bool(kinds.value & _lib.NT_OUTLINE_CREASE),
                     color=tuple(float(c) for c in col), strength=float(st.value))
 
+    def set_face_shading(self, colors=None, *, near=None, far=None, color=(0, 0, 0), strength=1.0, background=False, tint_axis=None,
+                         tint_range=None, tint_colors=None):
+        """Shade the cube's faces from the face records of the render itself (include/ntracer_hip.h): `colors`, an
+        [n][2][3] array-like with components in [0, 1], gives each of the 2n faces a colour of its own -- colors[i][1] the face
+        at +1 of axis i, colors[i][0] the face at -1; face_palette(n) makes one -- in place of the one (1, 0.5, 0.5).  The other
+        arguments are CompositeScene.set_depth_cue's: fog from `near` to `far` towards `color` by `strength`, on the background
+        too with `background`, and a tint along `tint_axis` with tint_range = (lo, hi) and tint_colors = (colour_lo, colour_hi).
+        Without fog arguments the fog has strength 0 (near, far = 0, 1).  `near` without `far`, and `color`, `strength` or
+        `background` other than their defaults without `far`, are a ValueError: nothing is dropped silently.  With
+        set_face_lines on as well the lines are drawn on top. set_face_shading(None) with nothing else takes the setting off.  Supersampling, row bands, statistics, a lens and
+        the parallel projection are refused with it; calculate_color / colors_at, face_hits, face_line_mask, ray_colors,
+        render_rays and refinement_mask ignore it.  A view setting like fov: not pickled."""
+        L = _lib.lib()
+        table = None
+        if colors is not None:
+            table = np.ascontiguousarray(colors, f32)
+            if table.shape != (self.dimension, 2, 3):
+                raise ValueError("colors must have the shape (%d, 2, 3)" % self.dimension)
+        fog = near is not None or far is not None
+        if not fog and (tuple(color) != (0, 0, 0) or isinstance(strength, bool) or strength != 1.0 or background):
+            raise ValueError("color, strength and background are the fog's: they need far")
+        if not fog and tint_axis is None:
+            if tint_range is not None or tint_colors is not None:
+                raise ValueError("tint_range and tint_colors need a tint_axis")
+            _lib.check(L.nt_scene_set_box_shading(self._handle, None if table is None else table.ctypes.data_as(_lib.f32p), None, None))
+            return
+        if fog and far is None:
+            raise ValueError("a fog needs far (near is 0 without one)")
+        cue, axis = _fog_and_tint(self.dimension, (0.0 if near is None else near) if fog else 0.0, far if fog else 1.0, color,
+                                  strength if fog else 0.0, background if fog else False, tint_axis, tint_range, tint_colors)
+        _lib.check(L.nt_scene_set_box_shading(self._handle, None if table is None else table.ctypes.data_as(_lib.f32p), C.byref(cue),
+                                              None if axis is None else axis.ctypes.data_as(_lib.f32p)))
+
+    @property
+    def face_shading(self):
+        """None, or a dict of the setting: colors (an [n][2][3] float32 array, None without a table of the caller's own), and near,
+        far, color, strength, background, tint_axis, tint_range, tint_colors as CompositeScene.depth_cue has them (all None
+        without fog and tint; the tint's three None without a tint)"""
+        on, has_colors, has_fog, tint, cue = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), _lib.NtDepthCue()
+        table = np.zeros((self.dimension, 2, 3), f32)
+        axis = np.zeros(self.dimension, f32)
+        _lib.check(_lib.lib().nt_scene_get_box_shading(self._handle, C.byref(on), C.byref(has_colors), table.ctypes.data_as(_lib.f32p),
+                                                       C.byref(has_fog), C.byref(cue), C.byref(tint), axis.ctypes.data_as(_lib.f32p)))
+        if not on.value:
+            return None
+        d = dict(colors=table if has_colors.value else None)
+        if has_fog.value:
+            d.update(_fog_and_tint_dict(cue, tint.value, axis))
+        else:
+            d.update(near=None, far=None, color=None, strength=None, background=None, tint_axis=None, tint_range=None, tint_colors=None)
+        return d
+
     def face_line_mask(self, width, height, device=None):
         """The face-line mask of a width x height view of the scene's camera under the setting that is on (nt_box_line_mask):
         uint8 [height][width], 0 or an OR of NT_OUTLINE_SILHOUETTE and NT_OUTLINE_CREASE -- a numpy array, or with `device` a
         torch device a torch tensor there, enqueued on torch's current stream."""
         return self._view_query("nt_box_line_mask", width, height, device, np.uint8, "face_lines", "face lines are off (set_face_lines)",
                                 counted=True, plain=True)
+
+
+def face_palette(n):
+    """A face-colour table for BoxScene.set_face_shading: float32 [n][2][3], one hue per axis, spread evenly round the colour
+    circle from red; the face at +1 ([i][1]) at full value, the face at -1 ([i][0]) at half of it."""
+    import colorsys
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    table = np.zeros((n, 2, 3), f32)
+    for i in range(n):
+        table[i, 1] = colorsys.hsv_to_rgb(i / n, 1.0, 1.0)
+        table[i, 0] = colorsys.hsv_to_rgb(i / n, 1.0, 0.5)
+    return table
+
+
+def _fog_and_tint(dimension, near, far, color, strength, background, tint_axis, tint_range, tint_colors):
+    """(nt_depth_cue, the tint axis as a float32 array or None) of the fog and tint arguments that CompositeScene.set_depth_cue
+    and BoxScene.set_face_shading share"""
+    for v in (near, far, strength):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("near, far and strength must be numbers")
+
+    def colour(c, what):
+        col = [float(v) for v in c]
+        if len(col) != 3:
+            raise ValueError("%s must have three components" % what)
+        return col
+
+    cue = _lib.NtDepthCue()
+    cue.fog_near, cue.fog_far, cue.fog_strength = float(near), float(far), float(strength)
+    cue.fog_color[:] = colour(color, "color")
+    cue.fog_background = 1 if background else 0
+    axis = None
+    if tint_axis is None:
+        if tint_range is not None or tint_colors is not None:
+            raise ValueError("tint_range and tint_colors need a tint_axis")
+    else:
+        if tint_range is None or tint_colors is None:
+            raise ValueError("a tint_axis needs tint_range and tint_colors")
+        axis = np.ascontiguousarray([float(v) for v in tint_axis], f32)
+        if axis.shape != (dimension,):
+            raise ValueError("tint_axis must have %d components" % dimension)
+        lo, hi = tint_range
+        cue.tint_lo, cue.tint_hi = float(lo), float(hi)
+        c_lo, c_hi = tint_colors
+        cue.tint_color_lo[:] = colour(c_lo, "tint_colors[0]")
+        cue.tint_color_hi[:] = colour(c_hi, "tint_colors[1]")
+    return cue, axis
+
+
+def _fog_and_tint_dict(cue, tint, axis):
+    d = dict(near=float(cue.fog_near), far=float(cue.fog_far), color=tuple(float(c) for c in cue.fog_color),
+             strength=float(cue.fog_strength), background=bool(cue.fog_background), tint_axis=None, tint_range=None, tint_colors=None)
+    if tint:
+        d.update(tint_axis=tuple(float(v) for v in axis), tint_range=(float(cue.tint_lo), float(cue.tint_hi)),
+                 tint_colors=(tuple(float(c) for c in cue.tint_color_lo), tuple(float(c) for c in cue.tint_color_hi)))
+    return d
 
 
 _FLAT_KEYS = ("root", "node_axis", "node_split", "node_left", "node_right", "items", "batch_recs", "batch_mats",
