@@ -812,6 +812,62 @@ int nt_scene_set_box_shading(nt_scene_t *s, const float *face_colors /* [n][2][3
 int nt_scene_get_box_shading(const nt_scene_t *s, int *enabled, int *has_colors, float *face_colors,
                              int *has_cue, nt_depth_cue *cue, int *has_tint, float *tint_axis);
 
+/* ---- view stacks: depth of field, slabs and anaglyphs summed on the device -------------------------------------------------
+   One picture from K cameras that differ from the scene's camera by a small offset: the K plain pictures are added with weights.
+   A view setting of BoxScene and CompositeScene alike, off by default.  K = count, 1 <= K <= NT_STACK_MAX; sample k has an offset
+   e_k of `dimension` floats in the camera's own frame and a weight w_k of three floats; `focus` > 0, or 0 for none.  Everything
+   below is fp32, every product and sum rounded on its own (no fma).
+   For a camera (o, rows a_0 right, a_1 up, a_2 forward, a_3 ...) sample k is an ordinary camera:
+     s_k = e_k[0] * a_0, then for j = 1 .. n - 1: s_k = s_k + (e_k[j] * a_j), component by component;
+     o_k = o + s_k;
+     f_k = a_2 - (s_k * r), r = 1.0f / focus, one IEEE division done once by the setter; r = 0.0f without a focus;
+     every other row of the axes unchanged.
+   With a focus all K rays of pixel (x, y) pass through o + focus * (a_2 + c_x a_0 - c_y a_1): the sharp plane of a lens, the
+   zero-parallax plane of a stereo pair.  Without one the samples are translations: along a hidden axis (row 3 and up) they are
+   the neighbouring 3-D slices of n-space, a slab.  The sample cameras are sheared, not orthonormal; the renders take them as
+   they are.
+   c_k is the colour a plain render gives the pixel under camera k, each component clamped to [0, 1] as the fp32 packer clamps
+   it (clamping before the sum is deliberate: a view stack adds pictures, as a caller adding fp32 frames would).  The pixel is
+     acc = 0.0f;  for k = 0 .. K - 1:  acc.c = acc.c + (w_k[c] * c_k.c)
+   and goes through the format's conversion and packing as always.  K = 1 with a zero offset and weight 1 is the plain frame byte
+   for byte.
+   nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device honour the setting (for a frame of a `frames`
+   array or a camera table the rule starts from that frame's camera) and refuse with NT_E_UNSUPPORTED ("a view stack is not
+   available ...") before a device is touched, drawing nothing: a supersampling factor above 1 (adaptive or not), row bands,
+   collect_stats, a lens, the parallel projection, clip planes, depth cues, outlines, ambient occlusion, BoxScene's face lines and
+   face shading (and a row range, which only a caller inside the library can ask for).  nt_colors_at / nt_calculate_color,
+   nt_primary_hits*, nt_box_hits*, nt_ray_colors*, nt_render_rays*, the ray queries and the other settings' masks ignore it.
+   All of it runs on the device.  BoxScene up to 24 dimensions: one kernel keeps the K samples of a pixel in registers; no sample
+   crosses device memory and no scratch is needed (nt_scene_set_view_stack_route sends it the other way).  Every
+   other scene: the plain render of the sample cameras into fp32 x 3 scratch, 12 K bytes a pixel a frame under the cap of
+   nt_scene_set_supersampling_scratch_mb, and a resolve pass; larger jobs are cut into chunks of whole frames, and when the K
+   samples of one frame do not fit, into chunks of consecutive k whose sums pass through an fp32 accumulator frame -- the sum
+   stays in the order of k and not one bit changes.  When not even the accumulator and one sample fit (24 bytes a pixel) the
+   render fails with NT_E_UNSUPPORTED ("a view stack ...") before anything is launched.  Not part of a pickled scene. */
+#define NT_STACK_MAX 64
+/* offsets: [count][dimension]; weights: [count][3], or NULL for 1.0f / (float)count each; count == 0 takes the setting off.
+   NT_E_INVALID for a count outside 0..NT_STACK_MAX, NULL offsets with count > 0, an offset, weight or focus that is not
+   finite, a negative focus (both also with count == 0) and one whose reciprocal is not finite (the setting stays as it was); NT_E_LOCKED while a render
+   holds the scene.  No device is needed to set or get it. */
+int nt_scene_set_view_stack(nt_scene_t *s, int count, const float *offsets, float focus, const float *weights);
+/* any out pointer may be NULL: *count (0 when off), `count` rows of offsets, *focus (0: none), `count` rows of weights (room
+   for NT_STACK_MAX rows suffices) */
+int nt_scene_get_view_stack(const nt_scene_t *s, int *count, float *offsets, float *focus, float *weights);
+/* The K cameras the rule gives for one camera: origins_out [K][dimension], axes_out [K][dimension][dimension].  origin / axes
+   NULL: the scene's own.  Runs on the host, needs no device, and is bit for bit what the renders use.  NT_E_INVALID when the
+   setting is off. */
+int nt_view_stack_cameras(const nt_scene_t *s, const float *origin, const float *axes, float *origins_out, float *axes_out);
+/* A TESTING AND MEASURING HOOK, not a feature: applications have no reason to call it.  Which of the two routes a BoxScene of up
+   to 24 dimensions takes with a stack on: NT_STACK_ROUTE_AUTO (the default), the fused kernel; NT_STACK_ROUTE_FRAMES, the scratch
+   and the resolve pass of every other scene.  Same bytes either way: the hook lets the suite and tools/view_stack_time.py hold
+   the routes against each other (a setting of the scene, because the environment switches are a closed list).
+   Every other scene takes the frames route whatever is set.  NT_E_INVALID for another value, NT_E_LOCKED while a render holds
+   the scene.  Not part of a pickled scene. */
+#define NT_STACK_ROUTE_AUTO 0
+#define NT_STACK_ROUTE_FRAMES 1
+int nt_scene_set_view_stack_route(nt_scene_t *s, int route);
+int nt_scene_get_view_stack_route(const nt_scene_t *s);
+
 #ifdef __cplusplus
 }
 #endif

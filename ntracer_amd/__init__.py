@@ -7,10 +7,12 @@ libntracer_hip.so (include/ntracer_hip.h); there is no CPU fallback.
 """
 from .render import (BlockingRenderer, CallbackRenderer, Channel, Color, ImageFormat, LockedError, Material,  # noqa: F401
                      Scene)
-from .tracern import CUBE, SPHERE, FaceHits, Lens, clip_plane_through, face_palette, sphere_directions  # noqa: F401
+from .tracern import (CUBE, SPHERE, FaceHits, Lens, aperture_disc, clip_plane_through, face_palette, slab, sphere_directions,  # noqa: F401
+                      stereo_pair)
 from ._lib import NT_OUTLINE_SILHOUETTE, NT_OUTLINE_CREASE, NT_OUTLINE_DEPTH  # noqa: F401
 from .wrapper import NTracer  # noqa: F401
 
 __all__ = ["NTracer", "Material", "ImageFormat", "Channel", "BlockingRenderer", "CallbackRenderer", "Color",
            "LockedError", "Scene", "CUBE", "SPHERE", "Lens", "sphere_directions", "FaceHits", "clip_plane_through", "face_palette",
+           "aperture_disc", "slab", "stereo_pair",
            "NT_OUTLINE_SILHOUETTE", "NT_OUTLINE_CREASE", "NT_OUTLINE_DEPTH"]

@@ -83,6 +83,8 @@ NT_OUTLINE_SILHOUETTE = 1        # the bits of an outline mask byte (nt_outline_
 NT_OUTLINE_CREASE = 2
 NT_OUTLINE_DEPTH = 4
 NT_CLIP_MAX = 8
+NT_STACK_MAX = 64                 # samples of a view stack (nt_scene_set_view_stack)
+NT_STACK_ROUTE_AUTO, NT_STACK_ROUTE_FRAMES = 0, 1                  # nt_scene_set_view_stack_route
 
 
 class NtDepthCue(C.Structure):               # nt_depth_cue: 60 bytes
@@ -197,6 +199,11 @@ SYMBOLS = [
     ("nt_scene_set_box_shading", C.c_int, [C.c_void_p, f32p, C.POINTER(NtDepthCue), f32p]),
     ("nt_scene_get_box_shading", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), f32p, C.POINTER(C.c_int),
                                            C.POINTER(NtDepthCue), C.POINTER(C.c_int), f32p]),
+    ("nt_scene_set_view_stack", C.c_int, [C.c_void_p, C.c_int, f32p, C.c_float, f32p]),
+    ("nt_scene_get_view_stack", C.c_int, [C.c_void_p, C.POINTER(C.c_int), f32p, f32p, f32p]),
+    ("nt_view_stack_cameras", C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p]),
+    ("nt_scene_set_view_stack_route", C.c_int, [C.c_void_p, C.c_int]),
+    ("nt_scene_get_view_stack_route", C.c_int, [C.c_void_p]),
     ("nt_box_line_mask", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(NtRenderOpts)]),
     ("nt_box_line_mask_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_ray_colors", C.c_int, [C.c_void_p, C.POINTER(NtRays), C.c_void_p, C.c_int]),

@@ -4,7 +4,8 @@ hipcc cross-compiles gfx950 code objects without a GPU.  The kernels are templat
 dimension is its own translation unit: csrc/nt_inst_X.hip with -DNT_INST_N=N defines the one launcher nt_X_fixed<N> that
 csrc/nt_dispatch.hpp declares and csrc/nt_var.hip dispatches to (and does not compile without the macro).  N = 3..24 for
 nt_inst_box.hip, nt_inst_rays.hip, nt_inst_adaptive.hip (BoxScene's kernels; CompositeScene's up to 10), nt_inst_boxhits.hip
-(whose launcher is nt_box_faces<N>) and nt_inst_boxshade.hip (nt_box_shade<N>), 3..10 for
+(whose launcher is nt_box_faces<N>), nt_inst_boxshade.hip (nt_box_shade<N>) and nt_inst_stack.hip (nt_box_stack<N>; compiled once
+more with -DNT_INST_N=0 for the view stack's kernels that do not depend on the dimension and their launchers), 3..10 for
 nt_inst_composite.hip, nt_inst_query.hip, nt_inst_hits.hip, nt_inst_lens.hip, nt_inst_parallel.hip, nt_inst_ao.hip,
 nt_inst_outline.hip, nt_inst_cue.hip (whose launcher is nt_cue_packet<N>) and nt_inst_clip.hip (nt_clip_packet<N>).  units() is
 the list, and
@@ -30,12 +31,14 @@ HDR = [os.path.join(CSRC, h) for h in ("nt_device.hpp", "nt_pixel.hpp", "nt_box.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function"]
 EXTRA = os.environ.get("NTRACER_HIPCC_FLAGS", "").split()         # ablation builds (-DNT_EXP_...)
+# headers that one instantiation file alone includes: only its units are stale when they change
+UNIT_HDR = {"nt_inst_stack.hip": [os.path.join(CSRC, "nt_stack.hpp")]}
 
 
 def units():
     """(object name, source, extra flags)"""
     u = [("nt_api", "nt_api.cpp", []), ("nt_builder", "nt_builder.cpp", []), ("nt_launch", "nt_launch.cpp", []),
-         ("nt_var", "nt_var.hip", [])]
+         ("nt_var", "nt_var.hip", []), ("nt_stack_any", "nt_inst_stack.hip", ["-DNT_INST_N=0"])]
     for n in DIMS:
         u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_composite_%d" % n, "nt_inst_composite.hip", ["-DNT_INST_N=%d" % n]))
@@ -51,12 +54,14 @@ def units():
         u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_clip_%d" % n, "nt_inst_clip.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_stack_%d" % n, "nt_inst_stack.hip", ["-DNT_INST_N=%d" % n]))
     for n in BOX_ONLY_DIMS:
         u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))      # (BoxScene's kernel alone)
         u.append(("nt_adaptive_%d" % n, "nt_inst_adaptive.hip", ["-DNT_INST_N=%d" % n]))  # (likewise)
         u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_stack_%d" % n, "nt_inst_stack.hip", ["-DNT_INST_N=%d" % n]))
     return u
 
 
@@ -112,7 +117,7 @@ def build(force=False, verbose=False, out=None):
         o = os.path.join(OBJ, "%s.%s.o" % (name, tag))
         objs.append(o)
         s = os.path.join(CSRC, src)
-        if force or _stale(o, [s] + HDR):
+        if force or _stale(o, [s] + HDR + UNIT_HDR.get(src, [])):
             jobs.append([cc] + FLAGS + EXTRA + extra + ["-c", s, "-o", o])
     if jobs:
         def run(cmd):

@@ -116,6 +116,10 @@ struct DeviceState {
     unsigned long long ao_version = 0;
     DevBuf clip;                         // clip planes: [count][n + 1] floats, a plane's normal and then its offset
     unsigned long long clip_version = 0;
+    DevBuf stack_offsets;                // view stack: the table of offsets
+    unsigned long long stack_version = 0;
+    DevBuf stack_in;                     // ... the scene's own camera for stack_cameras: its four rows, then all its axes
+    DevBuf stack_cams;                   // ... the sample cameras of a launch's frames and their dot products (NtStack)
     DevBuf numer;                        // packet kernel: -(N.o + d) per (frame, simplex)
     DevBuf cull;                         // BoxScene: row culling bits
     bool cull_clean = false;             // `cull` is all zero (what the fused BoxScene path needs and leaves behind)
@@ -205,6 +209,12 @@ struct nt_scene {
     nt_depth_cue bs_set{};               // ... the cue as the caller gave it, the tint's fields zero without a tint,
     std::vector<float> bs_axis;          // ... the tint axis [n], empty without a tint,
     float bs_inv_fog = 0.0f, bs_inv_tint = 0.0f;     // ... and the two reciprocals of the rule, formed once
+    int stack_count = 0;                 // > 0: a view stack of that many sample cameras on the renders (nt_scene_set_view_stack)
+    std::vector<float> stack_offsets;    // ... their offsets [stack_count][n] in the camera's own frame,
+    std::vector<float> stack_weights;    // ... their weights [stack_count][3],
+    float stack_focus = 0.0f, stack_r = 0.0f;        // ... the focus (0: none) and r = 1.0f / focus, formed once (0 without a focus)
+    unsigned long long stack_version = 1;            // counts the changes of stack_offsets
+    int stack_route = NT_STACK_ROUTE_AUTO;           // NT_STACK_ROUTE_FRAMES: BoxScene's stacks through the frames route too (nt_scene_set_view_stack_route)
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -414,6 +424,14 @@ int upload(DevBuf &b, const std::vector<T> &v) {
 }
 
 int upload_scene(nt_scene *s, DeviceState *ds) {
+    if (s->stack_count > 0 && ds->stack_version != s->stack_version) {
+        // (a fresh allocation, as for the lights below)
+        DevBuf fresh;
+        if (int r = upload(fresh, s->stack_offsets)) return r;
+        if (ds->stack_offsets.p) { (void)hipDeviceSynchronize(); ds->stack_offsets.release(); }
+        ds->stack_offsets = fresh;
+        ds->stack_version = s->stack_version;
+    }
     if (!s->composite) return NT_OK;
     if (!ds->scene_uploaded) {
         if (int r = upload(ds->nodes, s->nodes)) return r;
@@ -687,6 +705,7 @@ struct FrameJob {
     const float *cam_buf;     // device [nframes][4][n] or nullptr
     const float *cam_dots = nullptr;   // with cam_buf: device [nframes][4], the cameras' dot products (camera_dots)
     const float *cam_span = nullptr;   // with cam_buf, from a camera table only: device [nframes][2], the cameras' spans (NtCamera::span)
+    const float *cam_axes = nullptr;   // with cam_buf, while a view stack is set: device [nframes][n][n], all the axes of the cameras
     hipStream_t stream;
     bool stats;
     bool strict = false;      // nt_render_opts.strict_reference
@@ -1139,9 +1158,16 @@ struct ViewSetting {
     const char *while_on;                // how the rows above name this setting when they refuse it
     int (*extra)(const nt_scene *s);     // a term of its own, after all the others, or nullptr
 };
-enum { VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_BOX_SHADING, VS_COUNT };
+enum { VS_STACK, VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_BOX_SHADING, VS_COUNT };
 const ViewSetting kViewSettings[VS_COUNT] = {
-    {[](const nt_scene *s) { return s->clip_count > 0; }, "clip planes are", "", nullptr,
+    {[](const nt_scene *s) { return s->stack_count > 0; }, "a view stack is", "", "a view stack is set",
+     // BoxScene's two settings have no `while_on`: they are refused here
+     [](const nt_scene *s) {
+         if (!s->composite && s->box_lines) return fail(NT_E_UNSUPPORTED, "a view stack is not available while face lines are set");
+         if (!s->composite && s->box_shading) return fail(NT_E_UNSUPPORTED, "a view stack is not available while face shading is set");
+         return (int)NT_OK;
+     }},
+    {[](const nt_scene *s) { return s->clip_count > 0; }, "clip planes are", "", "clip planes are set",
      // a Solid cut open needs a cap or an inner wall, which nothing defines: refused, not approximated
      [](const nt_scene *s) {
          return s->n_solids > 0 ? fail(NT_E_UNSUPPORTED, "clip planes are not available for a scene with Solids (a Solid cut open has no cap)") : (int)NT_OK;
@@ -1978,6 +2004,117 @@ int enqueue_parallel(nt_scene *s, DeviceState *ds, const FrameJob &job, const Re
     return NT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// view stacks (nt_scene_set_view_stack; kernels in nt_stack.hpp)
+// ---------------------------------------------------------------------------------------------
+
+// the K cameras the rule gives for one camera (ntracer_hip.h), operation by operation: stack_cameras is its copy on the device
+void stack_cameras_host(const nt_scene *s, const float *origin, const float *axes, float *origins_out, float *axes_out) {
+    const int n = s->n;
+    for (int k = 0; k < s->stack_count; ++k) {
+        const float *e = s->stack_offsets.data() + (size_t)k * n;
+        float *o = origins_out + (size_t)k * n, *a = axes_out + (size_t)k * n * n;
+        std::memcpy(a, axes, sizeof(float) * n * n);
+        for (int j = 0; j < n; ++j) {
+            float sj = e[0] * axes[j];
+            for (int i = 1; i < n; ++i) sj = sj + (e[i] * axes[(size_t)i * n + j]);
+            o[j] = origin[j] + sj;
+            a[2 * n + j] = axes[2 * n + j] - (sj * s->stack_r);
+        }
+    }
+}
+
+// A render with a view stack on.  stack_cameras expands the job's cameras -- the scene's own, which goes to device memory here
+// with all its axes, a `frames` array or a camera table -- into K sample cameras a frame.  BoxScene up to NT_MAX_FIXED_BOX_DIM
+// dimensions: box_stack<N>, one launch, no scratch (nt_scene_set_view_stack_route and NTRACER_FORCE_VAR=1 send it the other way).
+// Every other scene, the frames route: the plain render of the sample cameras in the plain fp32 x 3 format into scratch under the
+// supersampling cap -- every route of a plain render comes with it -- and stack_resolve into the caller's image, per chunk of
+// whole frames; when the K samples of one frame do not fit, frame by frame in chunks of consecutive k through an fp32 accumulator
+// frame, the sum still in the order of k.  Enqueue only.
+int enqueue_stack(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw) {
+    const char *noun = "a view stack";
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, &kViewSettings[VS_STACK], noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const int n = s->n, K = s->stack_count, F = job.nframes;
+    const long long px = vp.px;
+    const bool fused = !s->composite && n <= NT_MAX_FIXED_BOX_DIM && !sw.force_var && s->stack_route != NT_STACK_ROUTE_FRAMES;
+    // the frames route's plan, before anything is launched
+    const long long cap = (long long)s->ss_scratch_mb << 20, frame_bytes = px * 12;
+    long long chunk_frames = F, chunk_k = K;
+    bool through_acc = false;
+    if (!fused) {
+        if (K * frame_bytes <= cap) {
+            // whole frames, K samples each, as the other passes plan them; a launch's grid holds 65535 frames in its z, and the
+            // kernels' pixel indices reach vp.px_limit over all K samples of a chunk's frames
+            const long long limit = std::min<long long>(std::min<long long>(65535 / K, std::max(sw.chunk_frames, 1)), std::max<long long>(1, vp.px_limit / (px * K)));
+            if (int r = plan_scratch_frames(vp, F, noun, "the samples of one frame", K * frame_bytes, cap, limit, chunk_frames)) return r;
+        } else {
+            // one frame at a time, its samples in chunks of consecutive k behind an accumulator frame: the helper's refusal when
+            // not even the accumulator and one sample fit
+            if (int r = plan_scratch_frames(vp, 1, noun, "the accumulator and one sample", 2 * frame_bytes, cap, 1, chunk_frames)) return r;
+            through_acc = true;
+            chunk_k = std::min<long long>(std::min<long long>(K, cap / frame_bytes - 1), std::max<long long>(1, vp.px_limit / px));
+        }
+    }
+    // the sample cameras
+    const size_t cam_floats = (size_t)F * K * 4 * n;
+    if (int e = ds->stack_cams.ensure((cam_floats + (size_t)F * K * 4) * sizeof(float))) return e;
+    float *scams = (float *)ds->stack_cams.p, *sdots = scams + cam_floats;
+    const float *cams = job.cam_buf, *axes = job.cam_axes;
+    if (!cams) {
+        float packed[4 * NT_DEV_MAX_DIM];
+        pack_camera(n, s->origin.data(), s->axes.data(), packed);
+        if (int e = ds->stack_in.ensure(sizeof(float) * (4 * n + n * n))) return e;
+        float *in = (float *)ds->stack_in.p;
+        HIP_TRY(hipMemcpyAsync(in, packed, sizeof(float) * 4 * n, hipMemcpyHostToDevice, job.stream));
+        HIP_TRY(hipMemcpyAsync(in + 4 * n, s->axes.data(), sizeof(float) * n * n, hipMemcpyHostToDevice, job.stream));
+        cams = in;
+        axes = in + 4 * n;
+    } else if (!axes) {
+        return fail(NT_E_INVALID, "internal: a view stack render whose cameras came without their axes");
+    }
+    if (int r = nt_launch_stack_cameras(job.stream, n, F, cams, axes, (const float *)ds->stack_offsets.p, K, s->stack_r, scams, sdots)) return launch_failed(r);
+    NtStack sk{};
+    sk.count = K;
+    sk.cams = scams;
+    sk.dots = sdots;
+    for (int k = 0; k < 3 * K; ++k) sk.weights[k] = s->stack_weights[k];
+    if (fused) {
+        const NtLaunchInfo li = launch_info(s, ds, sw, F, job.stream);
+        if (int r = nt_launch_box_stack(li, vp.tg, sk)) return launch_failed(r);
+        return NT_OK;
+    }
+    Scratch at;
+    if (int e = at.open(ds, (size_t)(chunk_frames * chunk_k * frame_bytes + (through_acc ? frame_bytes : 0)))) return e;
+    char *samples = at.take<char>((size_t)(chunk_frames * chunk_k * frame_bytes));
+    float *acc = through_acc ? at.take<float>((size_t)frame_bytes) : nullptr;
+    for (int f0 = 0; f0 < F; f0 += (int)chunk_frames) {
+        const int nf = (int)std::min<long long>(chunk_frames, F - f0);
+        for (int k0 = 0; k0 < K; k0 += (int)chunk_k) {
+            const int kc = (int)std::min<long long>(chunk_k, K - k0);
+            // the plain frames of sample cameras [f0 * K + k0, ... + nf * kc): consecutive, as a chunk of k is of one frame alone
+            FrameJob bj = base_frame_job(s, job, vp.bf, 0, nf * kc, samples, (size_t)frame_bytes);
+            bj.cam_buf = scams + ((size_t)f0 * K + k0) * 4 * n;
+            bj.cam_dots = sdots + ((size_t)f0 * K + k0) * 4;
+            bj.cam_span = nullptr;
+            bj.cam_axes = nullptr;
+            if (int e = enqueue(s, ds, bj)) return e;
+            NtStackChunk ch{};
+            ch.samples = (const uint32_t *)samples;
+            ch.k0 = k0;
+            ch.kc = kc;
+            ch.nframes = nf;
+            ch.acc_in = through_acc && k0 > 0 ? acc : nullptr;
+            ch.acc_out = through_acc && k0 + kc < K ? acc : nullptr;
+            NtTarget ft = vp.tg;
+            ft.dest = vp.tg.dest + (long long)f0 * vp.tg.frame_stride;
+            if (int r = nt_launch_stack_resolve(job.stream, sk, ch, ft)) return launch_failed(r);
+        }
+    }
+    return NT_OK;
+}
+
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
@@ -1985,6 +2122,7 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const bool whole = !job.colors_out && !job.samples_pass && !job.counters_pass;
     // the whole-view settings, one line a row of kViewSettings and in its order: the first that is on draws, as the first that is
     // on refuses (tests/test_view_setting_refusals.py holds the refusals to that order, the settings' host tests these lines)
+    if (s->stack_count > 0 && whole) return enqueue_stack(s, ds, job, sw);
     if (s->clip_count > 0 && s->composite && whole) return enqueue_clip(s, ds, job, sw);
     if (s->cue && s->composite && whole) return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
     if (s->outlines && s->composite && whole) return enqueue_outlines(s, ds, job, sw, nullptr, false, nullptr);
@@ -3303,6 +3441,70 @@ int nt_scene_get_clip_planes(const nt_scene_t *s, int *count, float *normals, fl
     return NT_OK;
 }
 
+int nt_scene_set_view_stack(nt_scene_t *s, int count, const float *offsets, float focus, const float *weights) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (count < 0 || count > NT_STACK_MAX) return fail(NT_E_INVALID, "a view stack has between 0 and %d samples (%d)", NT_STACK_MAX, count);
+    if (count > 0 && !offsets) return fail(NT_E_INVALID, "the offsets of a view stack are NULL");
+    const int n = s->n;
+    std::vector<float> off, wts;
+    float r = 0.0f;
+    // (the focus is checked whatever the count: a call that takes the setting off with a bad focus is a mistake too)
+    if (!(focus >= 0.0f) || !std::isfinite(focus)) return fail(NT_E_INVALID, "the focus of a view stack must be finite and not negative (0: none)");
+    if (count > 0) {
+        if (focus > 0.0f) {
+            r = 1.0f / focus;
+            if (!std::isfinite(r)) return fail(NT_E_INVALID, "the focus of a view stack is too small: 1 / focus must be finite");
+        }
+        off.assign(offsets, offsets + (size_t)count * n);
+        for (size_t i = 0; i < off.size(); ++i)
+            if (!std::isfinite(off[i])) return fail(NT_E_INVALID, "offset %d of the view stack has a component that is not finite", (int)(i / n));
+        wts.assign((size_t)count * 3, 1.0f / (float)count);
+        if (weights) {
+            wts.assign(weights, weights + (size_t)count * 3);
+            for (size_t i = 0; i < wts.size(); ++i)
+                if (!std::isfinite(wts[i])) return fail(NT_E_INVALID, "weight %d of the view stack has a component that is not finite", (int)(i / 3));
+        }
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->stack_count = count;
+    s->stack_offsets = std::move(off);
+    s->stack_weights = std::move(wts);
+    s->stack_focus = count > 0 ? focus : 0.0f;
+    s->stack_r = r;
+    ++s->stack_version;
+    return NT_OK;
+}
+
+int nt_scene_get_view_stack(const nt_scene_t *s, int *count, float *offsets, float *focus, float *weights) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> g(const_cast<nt_scene_t *>(s)->mu);      // (the setter swaps the vectors under it)
+    if (count) *count = s->stack_count;
+    if (focus) *focus = s->stack_focus;
+    if (offsets && s->stack_count) std::memcpy(offsets, s->stack_offsets.data(), sizeof(float) * s->stack_offsets.size());
+    if (weights && s->stack_count) std::memcpy(weights, s->stack_weights.data(), sizeof(float) * s->stack_weights.size());
+    return NT_OK;
+}
+
+int nt_scene_set_view_stack_route(nt_scene_t *s, int route) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (route != NT_STACK_ROUTE_AUTO && route != NT_STACK_ROUTE_FRAMES) return fail(NT_E_INVALID, "the route of a view stack is NT_STACK_ROUTE_AUTO or NT_STACK_ROUTE_FRAMES (%d)", route);
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->stack_route = route;
+    return NT_OK;
+}
+
+int nt_scene_get_view_stack_route(const nt_scene_t *s) { return s ? s->stack_route : fail(NT_E_INVALID, "scene is NULL"); }
+
+int nt_view_stack_cameras(const nt_scene_t *s, const float *origin, const float *axes, float *origins_out, float *axes_out) {
+    if (!s || !origins_out || !axes_out) return fail(NT_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> g(const_cast<nt_scene_t *>(s)->mu);
+    if (s->stack_count < 1) return fail(NT_E_INVALID, "the view stack is off (nt_scene_set_view_stack)");
+    stack_cameras_host(s, origin ? origin : s->origin.data(), axes ? axes : s->axes.data(), origins_out, axes_out);
+    return NT_OK;
+}
+
 int nt_scene_set_params(nt_scene_t *s, const nt_scene_params *p) {
     if (!s || !p) return fail(NT_E_INVALID, "NULL argument");
     if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no lighting parameters");
@@ -3462,11 +3664,14 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     }
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
     const int n = s->n;
-    const size_t cam_floats = (size_t)nframes * 4 * n + (size_t)nframes * 4;
+    // (under a view stack all the axes travel behind the table: stack_cameras reads the hidden rows too)
+    const size_t table_floats = (size_t)nframes * 4 * n + (size_t)nframes * 4;
+    const size_t cam_floats = table_floats + (s->stack_count > 0 ? (size_t)nframes * n * n : 0);
     DeviceState::Stage *st = nullptr;
     if (int r = stage_slot(ds, cam_floats * sizeof(float), st)) return r;
     float *packed = (float *)st->host;
     pack_cameras(n, nframes, origins, axes, packed);
+    if (s->stack_count > 0) std::memcpy(packed + table_floats, axes, sizeof(float) * nframes * n * n);
     // a camera table that earlier launches may still read must not be overwritten: grow-only buffer,
     // refilled only after the stream that used it has drained (same-stream ordering)
     if (int r = ds->cams.ensure(cam_floats * sizeof(float))) return r;
@@ -3480,13 +3685,15 @@ int nt_render_frames_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, 
     FrameJob job = render_job(f, b, dest_dev, frame_stride, nframes, (hipStream_t)hip_stream, stats, opts, true);
     job.cam_buf = (const float *)ds->cams.p;
     job.cam_dots = job.cam_buf + (size_t)nframes * 4 * s->n;
+    if (s->stack_count > 0) job.cam_axes = job.cam_buf + table_floats;
     return enqueue(s, ds, job);
 }
 
 struct nt_camera_table {
     int n = 0, nframes = 0, device = -1;
     float *dev = nullptr;                // [nframes][4][n] camera rows, then [nframes][4] dot products (NtCamera::buf), then
-                                         // [nframes][2] spans (NtCamera::span)
+                                         // [nframes][2] spans (NtCamera::span), then [nframes][n][n], all the axes of the
+                                         // cameras, which a view stack's hidden offsets need (FrameJob::cam_axes)
 };
 
 nt_camera_table_t *nt_camera_table_create(int dimension, int nframes, const float *origins, const float *axes, int device) {
@@ -3498,9 +3705,11 @@ nt_camera_table_t *nt_camera_table_create(int dimension, int nframes, const floa
     if (pick_device(nullptr, device, dev)) return nullptr;
     const int n = dimension;
     const size_t span_at = (size_t)nframes * 4 * n + (size_t)nframes * 4;
-    const size_t cam_floats = span_at + (size_t)nframes * 2;
+    const size_t axes_at = span_at + (size_t)nframes * 2;
+    const size_t cam_floats = axes_at + (size_t)nframes * n * n;
     std::vector<float> packed(cam_floats);
     pack_cameras(n, nframes, origins, axes, packed.data());
+    std::memcpy(packed.data() + axes_at, axes, sizeof(float) * nframes * n * n);
     // the span of every camera (nt_box_span.hpp): once here, a few microseconds each, for the 510 waves of every frame that would
     // each work it out again in their stretch codes.  (The table does not know its scene: only BoxScene's tile kernel reads them.)
     for (int f = 0; f < nframes; ++f) {
@@ -3554,6 +3763,7 @@ int nt_render_table_device(nt_scene_t *s, void *dest_dev, size_t frame_stride, c
     job.cam_buf = table->dev + (size_t)first * 4 * table->n;                                  // (the table: all cameras, then all dot products)
     job.cam_dots = table->dev + (size_t)table->nframes * 4 * table->n + (size_t)first * 4;
     job.cam_span = table->dev + (size_t)table->nframes * (4 * table->n + 4) + (size_t)first * 2;
+    job.cam_axes = table->dev + (size_t)table->nframes * (4 * table->n + 6) + (size_t)first * table->n * table->n;
     return enqueue(s, ds, job);
 }
 

@@ -385,6 +385,35 @@ struct NtBoxShade {
     float colors[NT_DEV_MAX_DIM * 6];     // T[axis][side][channel]; (1, 0.5, 0.5) everywhere without a table of the caller's
 };
 
+// A view stack (nt_stack.hpp; the rule in full: ntracer_hip.h): K sample cameras a frame, whose plain pictures
+// are clamped, weighted and summed in the order of k.  Every pointer is device memory.  The sample cameras are stack_cameras'
+// output: camera f * count + k is sample k of frame f of the launch.
+#define NT_DEV_STACK_MAX 64
+struct NtStack {
+    int count;                // K
+    const float *cams;        // [nframes * count][4][n] camera rows of the samples (NtCamera::buf)
+    const float *dots;        // [nframes * count][4] their dot products (NtCamera::dots)
+    float weights[NT_DEV_STACK_MAX * 3];  // w_k[c]
+};
+// One chunk of the frames route: samples [k0, k0 + kc) of `nframes` frames, each a plain fp32 x 3 frame (NtAdaptive::base's
+// layout) of tg.width x tg.height pixels, sample kk of frame f at ((f * kc + kk) * width * height) pixels.  acc_in: nullptr (the
+// sum starts at 0.0f) or the running sums of the samples before k0, three native floats a pixel; acc_out: nullptr (the pixel goes
+// through the packer into tg, the whole image of every frame, no bands) or where the running sums go.  With either, nframes is 1.
+struct NtStackChunk {
+    const uint32_t *samples;
+    int k0, kc, nframes;
+    const float *acc_in;
+    float *acc_out;
+};
+// stack_cameras: the K sample cameras of each of `nframes` cameras -- rows `cams` [nframes][4][n], all their axes `axes`
+// [nframes][n][n] -- under the offsets [count][n] and r = 1 / focus (0: none), and their dot products, into out_cams / out_dots
+int nt_launch_stack_cameras(void *stream, int n, int nframes, const float *cams, const float *axes, const float *offsets, int count, float r,
+                            float *out_cams, float *out_dots);
+int nt_launch_stack_resolve(void *stream, const NtStack &sk, const NtStackChunk &ch, const NtTarget &tg);
+// box_stack<N> of the scene's dimension, N = 3..NT_DEV_MAX_FIXED_BOX (the host sends every other BoxScene through the frames
+// route): tg is the whole image of every frame (no bands)
+int nt_launch_box_stack(const NtLaunchInfo &li, const NtTarget &tg, const NtStack &sk);
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 // BoxScene face shading: box_shaded<N, LINES> of the scene's dimension, or box_hits_var into bs.recs and box_shaded_var behind
 // it.  tg is the whole image of every frame (no bands).  The cameras travel as for nt_launch_box.

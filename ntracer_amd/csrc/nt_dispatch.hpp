@@ -20,6 +20,7 @@ struct NtCue;
 struct NtBoxFaces;
 struct NtBoxShade;
 struct NtClip;
+struct NtStack;
 
 // The compile-time-N launchers, one family a primary template.  Nothing defines the primary: every dimension is the explicit
 // specialisation `template <> int nt_X_fixed<NT_INST_N>(...)` of its own translation unit (nt_inst_*.hip, compiled once per
@@ -44,6 +45,8 @@ template <int N> int nt_clip_packet(const NtLaunchInfo &li, const NtCompositeDev
 template <int N> int nt_box_faces(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxFaces &bf);
 // (BoxScene face shading, nt_inst_boxshade.hip: N = 3..NT_DEV_MAX_FIXED_BOX likewise)
 template <int N> int nt_box_shade(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg, const NtBoxShade &bs);
+// (view stacks, nt_inst_stack.hip: BoxScene's fused kernel, N = 3..NT_DEV_MAX_FIXED_BOX likewise)
+template <int N> int nt_box_stack(const NtLaunchInfo &li, const NtTarget &tg, const NtStack &sk);
 
 template <int LO, typename F, int... I>
 inline bool nt_dispatch_dim_seq(int n, int &r, F &f, std::integer_sequence<int, I...>) {

@@ -878,6 +878,53 @@ def sphere_directions(n, count, seed=0):
     return np.ascontiguousarray(v / np.sqrt((v * v).sum(axis=1))[:, None], f32)
 
 
+def aperture_disc(n, K, radius):
+    """(offsets float32 [K][n], weights float32 [K][3]) for set_view_stack: a lens of the given radius in the camera's right/up
+    plane -- sample 0 at the centre, samples 1 .. K - 1 a sunflower (radius * sqrt(k / (K - 1)), the golden angle apart), the
+    same table every time -- and weights 1 / K each.  Use it with a focus: depth of field."""
+    n, K = int(n), int(K)
+    if n < 3 or K < 1 or K > _lib.NT_STACK_MAX or not float(radius) >= 0.0:
+        raise ValueError("aperture_disc wants n >= 3, 1 <= K <= %d and a radius that is not negative" % _lib.NT_STACK_MAX)
+    off = np.zeros((K, n), f32)
+    golden = math.pi * (3.0 - math.sqrt(5.0))
+    for k in range(1, K):
+        r = float(radius) * math.sqrt(k / float(K - 1))
+        off[k, 0] = r * math.cos(k * golden)
+        off[k, 1] = r * math.sin(k * golden)
+    return off, np.full((K, 3), f32(1) / f32(K), f32)
+
+
+def slab(n, axis, half_thickness, K, colors=None):
+    """(offsets float32 [K][n], weights float32 [K][3]) for set_view_stack: K evenly spaced offsets from -half_thickness to
+    +half_thickness along the hidden axis `axis` >= 3 of the camera (K = 1: the slice itself), no focus.  colors None: weights
+    1 / K each, the projection view of the slab.  colors = (lo, mid, hi), three (r, g, b): an onion skin -- a sample's weight
+    is the colour interpolated from lo at -half_thickness over mid at 0 to hi at +half_thickness, divided by K."""
+    n, K, axis = int(n), int(K), int(axis)
+    if n < 4 or not 3 <= axis < n or K < 1 or K > _lib.NT_STACK_MAX or not float(half_thickness) >= 0.0:
+        raise ValueError("slab wants a hidden axis (3 <= axis < n), 1 <= K <= %d and a half_thickness that is not negative" % _lib.NT_STACK_MAX)
+    t = np.linspace(-1.0, 1.0, K) if K > 1 else np.zeros(1)
+    off = np.zeros((K, n), f32)
+    off[:, axis] = t * float(half_thickness)
+    if colors is None:
+        return off, np.full((K, 3), f32(1) / f32(K), f32)
+    lo, mid, hi = (np.asarray(c, np.float64).reshape(3) for c in colors)
+    w = np.where(t[:, None] < 0.0, mid + (lo - mid) * (-t[:, None]), mid + (hi - mid) * t[:, None]) / float(K)
+    return off, np.ascontiguousarray(w, f32)
+
+
+def stereo_pair(n, separation):
+    """(offsets float32 [2][n], weights float32 [2][3]) for set_view_stack: the left eye -separation / 2 and the right eye
+    +separation / 2 along the camera's right axis, the left in red and the right in cyan.  Use it with a focus, the distance at
+    which the two pictures coincide: an anaglyph."""
+    n = int(n)
+    if n < 3:
+        raise ValueError("stereo_pair wants n >= 3")
+    off = np.zeros((2, n), f32)
+    off[0, 0] = -float(separation) / 2.0
+    off[1, 0] = float(separation) / 2.0
+    return off, np.asarray([[1, 0, 0], [0, 1, 1]], f32)
+
+
 class _SceneBase(Scene):
     """Camera / fov handling shared by BoxScene and CompositeScene (ntracer_body.hpp:676-715)."""
 
@@ -1217,6 +1264,75 @@ class _SceneBase(Scene):
         sy = (k * (np.arange(height, dtype=f32) - half_h)).astype(f32)
         o = (org[None, None, :] + ax[0][None, None, :] * sx[None, :, None]) - ax[1][None, None, :] * sy[:, None, None]
         return np.ascontiguousarray(o.reshape(height * width, self._n), f32), ax[2].copy()
+
+    def set_view_stack(self, offsets, focus=None, weights=None):
+        """One picture from K cameras that differ from the scene's by a small offset, their plain pictures clamped, weighted and
+        summed in fp32 on the device (include/ntracer_hip.h has the rule).  offsets: K rows of n floats in the
+        camera's own frame (right, up, forward, the hidden axes); focus: None, or the distance of the plane on which all K rays of
+        a pixel meet; weights: None for 1 / K each, or K rows of (r, g, b).  aperture_disc, slab and stereo_pair make the usual
+        tables.  set_view_stack(None) takes the setting off.  A view setting like fov: not pickled."""
+        L = _lib.lib()
+        if offsets is None:
+            _lib.check(L.nt_scene_set_view_stack(self._handle, 0, None, 0.0, None))
+            return
+        off = np.ascontiguousarray(offsets, f32)
+        if off.ndim != 2 or off.shape[1] != self._n:
+            raise ValueError("the offsets of a view stack are rows of %d floats" % self._n)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, f32)
+            if w.shape != (off.shape[0], 3):
+                raise ValueError("the weights of a view stack are one (r, g, b) row a sample")
+        if focus is not None and (isinstance(focus, bool) or not isinstance(focus, (int, float, np.integer, np.floating))):
+            raise ValueError("focus must be a number or None")
+        if focus is not None and not float(focus) > 0.0:
+            raise ValueError("focus must be positive (None: no focus)")
+        _lib.check(L.nt_scene_set_view_stack(self._handle, off.shape[0], off.ctypes.data_as(_lib.f32p), 0.0 if focus is None else float(focus),
+                                             None if w is None else w.ctypes.data_as(_lib.f32p)))
+
+    @property
+    def view_stack(self):
+        """None, or the setting of set_view_stack: a dict of offsets float32 [K][n], focus (None without one), weights [K][3]"""
+        count, focus = C.c_int(0), C.c_float(0.0)
+        off = np.zeros((_lib.NT_STACK_MAX, self._n), f32)
+        w = np.zeros((_lib.NT_STACK_MAX, 3), f32)
+        _lib.check(_lib.lib().nt_scene_get_view_stack(self._handle, C.byref(count), off.ctypes.data_as(_lib.f32p), C.byref(focus),
+                                                      w.ctypes.data_as(_lib.f32p)))
+        if count.value == 0:
+            return None
+        return {"offsets": off[:count.value].copy(), "focus": float(focus.value) if focus.value > 0.0 else None,
+                "weights": w[:count.value].copy()}
+
+    def set_view_stack_route(self, route):
+        """A testing and measuring hook, not a feature.  None: a BoxScene of up to 24 dimensions draws its view stacks with the
+        fused kernel (the default); "frames": through the fp32 scratch and the resolve pass, the route of every other scene.
+        Same bytes either way: the suite and tools/view_stack_time.py hold the two routes against each other with it."""
+        if route not in (None, "frames"):
+            raise ValueError('the route of a view stack is None or "frames"')
+        _lib.check(_lib.lib().nt_scene_set_view_stack_route(self._handle, _lib.NT_STACK_ROUTE_FRAMES if route else _lib.NT_STACK_ROUTE_AUTO))
+
+    @property
+    def view_stack_route(self):
+        """None, or "frames" (set_view_stack_route)"""
+        return "frames" if _lib.lib().nt_scene_get_view_stack_route(self._handle) == _lib.NT_STACK_ROUTE_FRAMES else None
+
+    def view_stack_cameras(self, camera=None):
+        """(origins float32 [K][n], axes float32 [K][n][n]): the K cameras the view stack that is set gives for `camera`, or for
+        the scene's own -- computed on the host, bit for bit what the renders use"""
+        vs = self.view_stack
+        if vs is None:
+            raise ValueError("no view stack is set")
+        if camera is not None and (not isinstance(camera, Camera) or camera.dimension != self._n):
+            raise TypeError("the scene and camera must have the same dimension")
+        K = len(vs["offsets"])
+        origins = np.zeros((K, self._n), f32)
+        axes = np.zeros((K, self._n, self._n), f32)
+        o = None if camera is None else np.ascontiguousarray(camera._origin, f32)
+        a = None if camera is None else np.ascontiguousarray(camera._axes, f32)
+        _lib.check(_lib.lib().nt_view_stack_cameras(self._handle, None if o is None else o.ctypes.data_as(_lib.f32p),
+                                                    None if a is None else a.ctypes.data_as(_lib.f32p), origins.ctypes.data_as(_lib.f32p),
+                                                    axes.ctypes.data_as(_lib.f32p)))
+        return origins, axes
 
     def set_camera(self, camera):
         if not isinstance(camera, Camera) or camera.dimension != self._n:
