@@ -868,6 +868,60 @@ int nt_view_stack_cameras(const nt_scene_t *s, const float *origin, const float 
 int nt_scene_set_view_stack_route(nt_scene_t *s, int route);
 int nt_scene_get_view_stack_route(const nt_scene_t *s);
 
+/* ---- X-ray views: every surface a primary ray crosses, counted on the device ------------------------------------------------
+   A picture of the inside: every primitive the ray of a pixel crosses multiplies the background behind it by a per-material
+   transmittance.  A product commutes, so there is no hit list, no cap, no order and no nearest-hit cutoff.  A view setting of
+   CompositeScene, off by default.  Everything below is fp32, every product and sum rounded on its own (no fma).
+   For pixel (x, y) of a W x H view take (o, d), the pinhole's primary ray exactly as a render forms it, and dist0 =
+   aabb_distance(o, d) as a render forms it.  The crossing set S is empty when dist0 < 0; otherwise it is every primitive of the
+   scene -- whatever the k-d tree says, which only culls -- whose own test accepts the ray without a cutoff and with t != 0,
+   each primitive once:
+     a lane of a batch (the batch rule): denom = N[0] * d[0], then + N[k] * d[k] for k = 1 .. n - 1; no likewise from o;
+       t = -(no + dd) / denom, accepted when denom != 0 && t >= 0; pside = p1 - (o + t * d) component by component; every edge
+       coordinate area_e = E_e[0] * pside[0], then + E_e[k] * pside[k], is >= -NT_FUZZ, and tot = 0.0f + area_0 + area_1 + ...
+       is <= 1 + NT_FUZZ.  Every lane of a batch that passes counts (the reference's "nearest lane of a batch alone" is a
+       nearest-hit matter).  A lane whose record is bytewise equal to an earlier lane of the same batch is padding (the builder
+       fills the last batch by repeating its last simplex) and never counts: the library forms a 4-bit live mask a batch when
+       the scene is made (nt_scene_batch_live_masks);
+     an unbatched triangle (the scalar rule, with the cutoff FLT_MAX): denom != 0, 0 < t < FLT_MAX, every edge coordinate in
+       [-NT_FUZZ, 1 + NT_FUZZ] and their sum <= 1 + NT_FUZZ;
+     a Solid: the Solid's own intersection test with the cutoff FLT_MAX; it counts 1 or 0, and from inside it is not there, as in
+       a render.
+   Opacity, lights, shadows and reflections play no part.  From S:
+     count(x, y) = |S|, int32;
+     colour(x, y) = B(o, d) * prod over p in S of T[material(p)], per channel: f = 1.0f; f = f * T[m][c] for every crossing, in
+       no specified order; then B * f, and the format's conversion and packing as always.  B is the colour a render gives a ray
+       that hits nothing (the background gradient).
+     T[m][c] = clamp01(1.0f - absorbance * (1.0f - tint * color_m[c])), computed once a material by the setter, in that order.
+   tint = 0 is the grey X-ray (1 - absorbance)^count; tint = 1 is stained glass.
+   With the setting on nt_render, nt_render_device, nt_render_frames_device and nt_render_table_device draw this colour instead
+   of the shaded one, and refuse with NT_E_UNSUPPORTED ("X-ray is not available ...") before a device is touched, drawing
+   nothing: a supersampling factor above 1 (adaptive or not), row bands, collect_stats, a lens, the parallel projection, a view
+   stack, clip planes (a cut-away X-ray is not drawn without the cut), depth cues, outlines and ambient occlusion.
+   nt_colors_at / nt_calculate_color, nt_ray_colors*, nt_render_rays*, nt_adaptive_mask*, nt_ambient_occlusion*,
+   nt_outline_mask* and nt_depth_cue_factors* are refused while it is on; nt_primary_hits* and the ray queries ignore it.
+   All of it runs on the device.  Up to 10 dimensions, a tree of depth <= 32 and NT_XRAY_PACKET_ITEMS batches + triangles +
+   Solids: one wave-uniform packet walk a tile with an exact "seen" bit an item in LDS.  Every other scene, and
+   NTRACER_FORCE_VAR=1: a per-lane walk with an exact bit a lane and item in scratch (shared with the scene's renders on that
+   device).  Not part of a pickled scene. */
+#define NT_XRAY_PACKET_ITEMS 65536
+/* CompositeScene only.  NT_E_INVALID for a BoxScene, and with `enabled` for an absorbance or tint that is not finite or outside
+   [0, 1] (the setting stays as it was); NT_E_LOCKED while a render holds the scene.  No device is needed to set or get it. */
+int nt_scene_set_xray(nt_scene_t *s, int enabled, float absorbance, float tint);
+/* any out pointer may be NULL; `table`: the [n_materials][3] transmittances T as the kernels read them (untouched when off) */
+int nt_scene_get_xray(const nt_scene_t *s, int *enabled, float *absorbance, float *tint, float *table);
+/* The live masks of the rule: `masks` (may be NULL) receives one byte a batch, bit l set when lane l counts.  Returns the number
+   of batches, or NT_E_INVALID for a BoxScene.  No device is needed. */
+int nt_scene_batch_live_masks(const nt_scene_t *s, uint8_t *masks);
+/* The counts alone of one width x height view of the scene's camera, [height][width] int32, whether or not the setting is on (a
+   count has no parameters).  Host form: holds the scene like nt_colors_at; of `opts` (may be NULL) device is read and
+   strict_reference accepted and ignored (there is no pruning to switch).  Device form: `counts_dev` is device memory and the
+   call is only enqueued on hip_stream; it also reads abort_device, and every other field of `opts` must be 0.  NT_E_INVALID,
+   before any device is touched and leaving the buffer alone: NULL arguments, width or height < 1, a BoxScene, more than
+   2^31 - 1 pixels; NT_E_UNSUPPORTED while clip planes, a lens or the parallel projection are set. */
+int nt_crossing_counts(nt_scene_t *s, int width, int height, int32_t *counts, const nt_render_opts *opts);
+int nt_crossing_counts_device(nt_scene_t *s, int width, int height, void *counts_dev, const nt_render_opts *opts, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

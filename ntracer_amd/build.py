@@ -7,7 +7,8 @@ nt_inst_box.hip, nt_inst_rays.hip, nt_inst_adaptive.hip (BoxScene's kernels; Com
 (whose launcher is nt_box_faces<N>), nt_inst_boxshade.hip (nt_box_shade<N>) and nt_inst_stack.hip (nt_box_stack<N>; compiled once
 more with -DNT_INST_N=0 for the view stack's kernels that do not depend on the dimension and their launchers), 3..10 for
 nt_inst_composite.hip, nt_inst_query.hip, nt_inst_hits.hip, nt_inst_lens.hip, nt_inst_parallel.hip, nt_inst_ao.hip,
-nt_inst_outline.hip, nt_inst_cue.hip (whose launcher is nt_cue_packet<N>) and nt_inst_clip.hip (nt_clip_packet<N>).  units() is
+nt_inst_outline.hip, nt_inst_cue.hip (whose launcher is nt_cue_packet<N>), nt_inst_clip.hip (nt_clip_packet<N>) and
+nt_inst_xray.hip (nt_xray_packet<N>).  units() is
 the list, and
 tests/test_dispatch.py holds the library's exports to it.  They are
 compiled in parallel into build/*.o and linked with the host side.  -ffp-contract=off is part of the arithmetic
@@ -32,7 +33,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
          "-Wno-unused-function"]
 EXTRA = os.environ.get("NTRACER_HIPCC_FLAGS", "").split()         # ablation builds (-DNT_EXP_...)
 # headers that one instantiation file alone includes: only its units are stale when they change
-UNIT_HDR = {"nt_inst_stack.hip": [os.path.join(CSRC, "nt_stack.hpp")]}
+UNIT_HDR = {"nt_inst_stack.hip": [os.path.join(CSRC, "nt_stack.hpp")], "nt_inst_xray.hip": [os.path.join(CSRC, "nt_xray.hpp")]}
 
 
 def units():
@@ -55,6 +56,7 @@ def units():
         u.append(("nt_clip_%d" % n, "nt_inst_clip.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_stack_%d" % n, "nt_inst_stack.hip", ["-DNT_INST_N=%d" % n]))
+        u.append(("nt_xray_%d" % n, "nt_inst_xray.hip", ["-DNT_INST_N=%d" % n]))
     for n in BOX_ONLY_DIMS:
         u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
         u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))      # (BoxScene's kernel alone)

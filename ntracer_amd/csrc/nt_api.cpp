@@ -116,6 +116,9 @@ struct DeviceState {
     unsigned long long ao_version = 0;
     DevBuf clip;                         // clip planes: [count][n + 1] floats, a plane's normal and then its offset
     unsigned long long clip_version = 0;
+    DevBuf live;                         // X-ray views: the live masks, a byte a batch
+    DevBuf xr_table;                     // ... and the transmittances [n_materials][3]
+    unsigned long long xr_version = 0;
     DevBuf stack_offsets;                // view stack: the table of offsets
     unsigned long long stack_version = 0;
     DevBuf stack_in;                     // ... the scene's own camera for stack_cameras: its four rows, then all its axes
@@ -215,6 +218,11 @@ struct nt_scene {
     float stack_focus = 0.0f, stack_r = 0.0f;        // ... the focus (0: none) and r = 1.0f / focus, formed once (0 without a focus)
     unsigned long long stack_version = 1;            // counts the changes of stack_offsets
     int stack_route = NT_STACK_ROUTE_AUTO;           // NT_STACK_ROUTE_FRAMES: BoxScene's stacks through the frames route too (nt_scene_set_view_stack_route)
+    bool xray = false;                   // the renders draw the X-ray colour instead of the shaded one (nt_scene_set_xray)
+    float xr_absorbance = 0.0f, xr_tint = 0.0f;
+    std::vector<float> xr_table;         // ... the transmittances T [n_materials][3], formed by the setter
+    unsigned long long xr_version = 1;   // counts the changes of xr_table
+    std::vector<uint8_t> live_masks;     // the X-ray rule's live mask of every batch, formed when the scene is made
 
     // composite_scene (tracer.hpp:1713-1740)
     int root = -1;
@@ -445,7 +453,16 @@ int upload_scene(nt_scene *s, DeviceState *ds) {
         if (int r = upload(ds->solid_mats, s->solid_mats)) return r;
         if (int r = upload(ds->materials, s->materials)) return r;
         if (int r = upload(ds->aabb, s->aabb)) return r;
+        if (int r = upload(ds->live, s->live_masks)) return r;
         ds->scene_uploaded = true;
+    }
+    if (s->xray && ds->xr_version != s->xr_version) {
+        // (a fresh allocation, as for the lights below)
+        DevBuf fresh;
+        if (int r = upload(fresh, s->xr_table)) return r;
+        if (ds->xr_table.p) { (void)hipDeviceSynchronize(); ds->xr_table.release(); }
+        ds->xr_table = fresh;
+        ds->xr_version = s->xr_version;
     }
     if (ds->lights_version != s->lights_version) {
         std::vector<float> all;
@@ -1158,8 +1175,10 @@ struct ViewSetting {
     const char *while_on;                // how the rows above name this setting when they refuse it
     int (*extra)(const nt_scene *s);     // a term of its own, after all the others, or nullptr
 };
-enum { VS_STACK, VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_BOX_SHADING, VS_COUNT };
+enum { VS_XRAY, VS_STACK, VS_CLIP, VS_CUE, VS_OUTLINES, VS_AO, VS_BOX_LINES, VS_BOX_SHADING, VS_COUNT };
 const ViewSetting kViewSettings[VS_COUNT] = {
+    // (CompositeScene's alone, so BoxScene's two settings never meet it; a view stack is refused through its `while_on`)
+    {[](const nt_scene *s) { return s->xray; }, "X-ray is", "", "X-ray is on", nullptr},
     {[](const nt_scene *s) { return s->stack_count > 0; }, "a view stack is", "", "a view stack is set",
      // BoxScene's two settings have no `while_on`: they are refused here
      [](const nt_scene *s) {
@@ -2115,6 +2134,55 @@ int enqueue_stack(nt_scene *s, DeviceState *ds, const FrameJob &job, const Rende
     return NT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// X-ray views (nt_scene_set_xray, nt_crossing_counts; kernels in nt_xray.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+static_assert(NT_XRAY_PACKET_ITEMS == NT_DEV_XRAY_PACKET_ITEMS, "the packet walk's item limit of the ABI is the launcher's");
+
+// what the entry points that do not honour the setting say while it is on
+int xray_refuses(const nt_scene *s, const char *what) {
+    if (s && s->composite && s->xray) return fail(NT_E_UNSUPPORTED, "X-ray is on: %s is not available under it", what);
+    return NT_OK;
+}
+
+// The frames of a render with the setting on, or without job.fmt the counts of one view of job.view_w x job.view_h into
+// `counts_dev` -- with that nullptr into scratch under the supersampling cap: *counts_out.  One launch either way: the packet
+// walk where nt_xray_packet_route says so, with its numerators and quad order, else xray_var with the `checked` columns of as
+// many blocks as fit 512 MB.  Enqueue only.
+int enqueue_xray(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, int *counts_dev, int **counts_out) {
+    const char *noun = "X-ray";
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, job.fmt ? &kViewSettings[VS_XRAY] : nullptr, noun, vp)) return r;
+    if (vp.nothing) return NT_OK;
+    const bool draw = vp.draw;
+    if (!draw && !counts_dev) {
+        long long chunk_frames;
+        if (int r = plan_scratch_frames(vp, 1, noun, "the counts of one frame", vp.px * 4, (long long)s->ss_scratch_mb << 20, LLONG_MAX, chunk_frames)) return r;
+        Scratch at;
+        if (int e = at.open(ds, (size_t)vp.px * 4)) return e;
+        counts_dev = at.take<int>((size_t)vp.px * 4);
+    }
+    if (counts_out) *counts_out = counts_dev;
+    NtCompositeDev c;
+    scene_dev(s, ds, sw, job.strict, false, c);
+    NtLaunchInfo li = launch_info(s, ds, sw, job.nframes, job.stream);
+    NtXray xr{};
+    if (int e = device_camera(s, ds, job.cam_buf, job.stream, xr.cams)) return e;
+    xr.trans = draw ? (const float *)ds->xr_table.p : nullptr;
+    xr.live = (const uint8_t *)ds->live.p;
+    xr.counts = draw ? nullptr : counts_dev;
+    if (nt_xray_packet_route(li, c)) {
+        if (int e = packet_records(s, ds, sw, vp.W, vp.H, job.nframes, nullptr, li)) return e;
+    } else {
+        const long long tiles = (long long)((vp.W + 7) / 8) * ((vp.H + 7) / 8) * job.nframes;
+        long long blocks = std::min<long long>(std::max<long long>(tiles, 1), 8192);
+        if (int e = checked_scratch(s, ds, sw, c, 64, blocks, 1, 0, (long long)512 << 20)) return e;
+    }
+    if (int r = nt_launch_xray(li, c, vp.tg, xr)) return launch_failed(r);
+    return NT_OK;
+}
+
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
@@ -2122,6 +2190,7 @@ int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const bool whole = !job.colors_out && !job.samples_pass && !job.counters_pass;
     // the whole-view settings, one line a row of kViewSettings and in its order: the first that is on draws, as the first that is
     // on refuses (tests/test_view_setting_refusals.py holds the refusals to that order, the settings' host tests these lines)
+    if (s->xray && s->composite && whole) return enqueue_xray(s, ds, job, sw, nullptr, nullptr);
     if (s->stack_count > 0 && whole) return enqueue_stack(s, ds, job, sw);
     if (s->clip_count > 0 && s->composite && whole) return enqueue_clip(s, ds, job, sw);
     if (s->cue && s->composite && whole) return enqueue_cue(s, ds, job, sw, nullptr, false, nullptr);
@@ -2645,6 +2714,7 @@ int rays_validate(const nt_scene *s, const nt_rays *rays, const void *out, bool 
     if (!rays || !out || !rays->origins || !rays->directions) return fail(NT_E_INVALID, "NULL argument");
     if (rays->count < 0) return fail(NT_E_INVALID, "invalid ray count");
     if (int r = clip_refuses(s, "the colour of a caller's ray (nt_ray_colors / nt_render_rays)")) return r;
+    if (int r = xray_refuses(s, "the colour of a caller's ray (nt_ray_colors / nt_render_rays)")) return r;
     if (!host) return NT_OK;
     const size_t n = (size_t)s->n;
     for (size_t r = 0; r < (size_t)rays->count; ++r) {
@@ -2819,6 +2889,7 @@ struct ViewQuery {
     int (*device_options)(const nt_render_opts *opts);      // what the device form refuses of its options (nullptr: nothing)
     // the setting's enqueue: into `dev`, or with `kept` into scratch, whose place it tells there
     int (*enqueue)(nt_scene *s, DeviceState *ds, const FrameJob &job, T *dev, T **kept);
+    bool under_xray = false;             // answered while X-ray is on as well (the crossing counts alone)
 };
 
 const ViewQuery<uint8_t> kAdaptiveMask = {
@@ -2852,6 +2923,12 @@ const ViewQuery<uint8_t> kBoxLineMask = {
         return enqueue_box_lines(s, ds, job, read_switches(), dev, kept != nullptr, kept);
     }};
 
+const ViewQuery<int> kCrossingCounts = {
+    sizeof(int32_t), 1, "the crossing count", [](const nt_scene *) { return false; }, "", "the crossing counts are", false, true,
+    [](const nt_render_opts *opts) { return only_device_strict_abort(opts, "the crossing counts read", "their"); },
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, int *dev, int **kept) { return enqueue_xray(s, ds, job, read_switches(), dev, kept); },
+    true};
+
 // what both forms check before a device is touched
 template <typename T>
 int view_query_validate(const nt_scene *s, int width, int height, const void *out, const nt_render_opts *opts, const ViewQuery<T> &q) {
@@ -2861,6 +2938,9 @@ int view_query_validate(const nt_scene *s, int width, int height, const void *ou
     if (q.kind == 0 && s->composite) return fail(NT_E_INVALID, "not a box scene");
     if (q.clip_what) {
         if (int r = clip_refuses(s, q.clip_what)) return r;
+        if (!q.under_xray) {
+            if (int r = xray_refuses(s, q.clip_what)) return r;
+        }
     }
     if (q.off(s)) return fail(NT_E_INVALID, "%s", q.off_message);
     if (q.adaptive_terms) {
@@ -2991,6 +3071,17 @@ nt_scene_t *nt_composite_scene_create(const nt_scene_desc *d) {
     }
     s->has_scalar = false;
     for (int i = 0; i < d->n_items; ++i) if ((d->items[i] & 3) != NT_KIND_BATCH) s->has_scalar = true;
+    // the X-ray rule's live masks: a lane whose record is bytewise equal to an earlier lane of its batch is padding
+    s->live_masks.assign((size_t)d->n_batches, 0);
+    for (int b = 0; b < d->n_batches; ++b) {
+        const float *recs = d->batch_recs + (size_t)b * NT_BATCH_SIZE * s->rec_len;
+        for (int l = 0; l < NT_BATCH_SIZE; ++l) {
+            bool dup = false;
+            for (int e = 0; e < l && !dup; ++e)
+                dup = std::memcmp(recs + (size_t)l * s->rec_len, recs + (size_t)e * s->rec_len, sizeof(float) * s->rec_len) == 0;
+            if (!dup) s->live_masks[b] |= (uint8_t)(1u << l);
+        }
+    }
     s->aabb.assign(d->aabb_start, d->aabb_start + n);
     s->aabb.insert(s->aabb.end(), d->aabb_end, d->aabb_end + n);
     return s;
@@ -3004,7 +3095,7 @@ void nt_scene_destroy(nt_scene_t *s) {
         (void)hipDeviceSynchronize();
         for (DevBuf *b : {&ds->nodes, &ds->items, &ds->batch_recs, &ds->batch_mats, &ds->tri_recs, &ds->tri_mats, &ds->solid_recs,
                           &ds->solid_types, &ds->solid_mats, &ds->materials, &ds->aabb, &ds->lights, &ds->framebuffer, &ds->cams, &ds->counter,
-                          &ds->probes, &ds->stats, &ds->hits, &ds->stats_frame, &ds->samples, &ds->numer, &ds->cull, &ds->checked, &ds->tframes, &ds->ties, &ds->lens_dirs})
+                          &ds->probes, &ds->stats, &ds->hits, &ds->stats_frame, &ds->samples, &ds->numer, &ds->cull, &ds->checked, &ds->tframes, &ds->ties, &ds->lens_dirs, &ds->live, &ds->xr_table})
             b->release();
         for (auto &t : ds->chan_tables) if (t->dev) (void)hipFree(t->dev);
         for (auto &t : ds->row_tables) if (t->dev) (void)hipFree(t->dev);
@@ -3497,6 +3588,53 @@ int nt_scene_set_view_stack_route(nt_scene_t *s, int route) {
 
 int nt_scene_get_view_stack_route(const nt_scene_t *s) { return s ? s->stack_route : fail(NT_E_INVALID, "scene is NULL"); }
 
+int nt_scene_set_xray(nt_scene_t *s, int enabled, float absorbance, float tint) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!s->composite) return fail(NT_E_INVALID, "BoxScene has no X-ray: a ray crosses exactly two of its faces (nt_box_hits)");
+    std::vector<float> table;
+    if (enabled) {
+        if (!(absorbance >= 0.0f && absorbance <= 1.0f)) return fail(NT_E_INVALID, "the X-ray's absorbance must lie in [0, 1]");
+        if (!(tint >= 0.0f && tint <= 1.0f)) return fail(NT_E_INVALID, "the X-ray's tint must lie in [0, 1]");
+        // T[m][c] = clamp01(1.0f - absorbance * (1.0f - tint * color_m[c])), every operation rounded on its own
+        table.resize((size_t)s->n_materials * 3);
+        for (int m = 0; m < s->n_materials; ++m)
+            for (int c = 0; c < 3; ++c) {
+                const float tc = tint * s->materials[(size_t)m * 10 + c];
+                const float in = 1.0f - tc;
+                const float ab = absorbance * in;
+                float t = 1.0f - ab;
+                t = t > 0.0f ? t : 0.0f;
+                t = t < 1.0f ? t : 1.0f;
+                table[(size_t)m * 3 + c] = t;
+            }
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->locked) return fail(NT_E_LOCKED, "the scene is locked for reading");
+    s->xray = enabled != 0;
+    s->xr_absorbance = enabled ? absorbance : 0.0f;
+    s->xr_tint = enabled ? tint : 0.0f;
+    s->xr_table = std::move(table);
+    ++s->xr_version;
+    return NT_OK;
+}
+
+int nt_scene_get_xray(const nt_scene_t *s, int *enabled, float *absorbance, float *tint, float *table) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> g(const_cast<nt_scene_t *>(s)->mu);      // (the setter swaps the vector under it)
+    if (enabled) *enabled = s->xray ? 1 : 0;
+    if (absorbance) *absorbance = s->xr_absorbance;
+    if (tint) *tint = s->xr_tint;
+    if (table && s->xray && !s->xr_table.empty()) std::memcpy(table, s->xr_table.data(), sizeof(float) * s->xr_table.size());
+    return NT_OK;
+}
+
+int nt_scene_batch_live_masks(const nt_scene_t *s, uint8_t *masks) {
+    if (!s) return fail(NT_E_INVALID, "scene is NULL");
+    if (!s->composite) return fail(NT_E_INVALID, "not a composite scene");
+    if (masks && !s->live_masks.empty()) std::memcpy(masks, s->live_masks.data(), s->live_masks.size());
+    return s->n_batches;
+}
+
 int nt_view_stack_cameras(const nt_scene_t *s, const float *origin, const float *axes, float *origins_out, float *axes_out) {
     if (!s || !origins_out || !axes_out) return fail(NT_E_INVALID, "NULL argument");
     std::lock_guard<std::mutex> g(const_cast<nt_scene_t *>(s)->mu);
@@ -3802,6 +3940,15 @@ int nt_outline_mask_device(nt_scene_t *s, int width, int height, void *mask_dev,
     return view_query_device(s, kOutlineMask, width, height, mask_dev, opts, hip_stream);
 }
 
+int nt_crossing_counts(nt_scene_t *s, int width, int height, int32_t *counts, const nt_render_opts *opts) {
+    RenderGuard guard(s);
+    return view_query_host(guard, kCrossingCounts, width, height, counts, opts);
+}
+
+int nt_crossing_counts_device(nt_scene_t *s, int width, int height, void *counts_dev, const nt_render_opts *opts, void *hip_stream) {
+    return view_query_device(s, kCrossingCounts, width, height, counts_dev, opts, hip_stream);
+}
+
 int nt_depth_cue_factors(nt_scene_t *s, int width, int height, float *factors, const nt_render_opts *opts) {
     RenderGuard guard(s);
     return view_query_host(guard, kCueFactors, width, height, factors, opts);
@@ -3826,6 +3973,7 @@ int nt_colors_at(nt_scene_t *s, int width, int height, int count, const int32_t 
     if (!s || (count > 0 && (!xs || !ys || !rgb))) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1 || count < 0) return fail(NT_E_INVALID, "invalid view size or count");
     if (int r = clip_refuses(s, "the colour of single pixels (nt_colors_at / nt_calculate_color)")) return r;
+    if (int r = xray_refuses(s, "the colour of single pixels (nt_colors_at / nt_calculate_color)")) return r;
     if (count == 0) return NT_OK;
     if (int r = check_renderable(s)) return r;
     RenderGuard guard(s);   // Scene.calculate_color locks the scene for the call (render.cpp:599-603)

@@ -414,6 +414,25 @@ int nt_launch_stack_resolve(void *stream, const NtStack &sk, const NtStackChunk 
 // route): tg is the whole image of every frame (no bands)
 int nt_launch_box_stack(const NtLaunchInfo &li, const NtTarget &tg, const NtStack &sk);
 
+// X-ray views (nt_xray.hpp, nt_var.hip; the rule in full: ntracer_hip.h): every primitive a primary ray crosses,
+// counted, and the background times the product of their materials' transmittances.  Every pointer is device memory.
+#define NT_DEV_XRAY_PACKET_ITEMS 65536    // the packet walk's seen bitset: 8 KiB a wave, four waves a SIMD in 160 KiB of LDS
+struct NtXray {
+    const float *cams;        // [nframes][4][n] camera rows of the launch's frames (NtCamera::buf)
+    const float *trans;       // [n_materials][3] transmittances T (a render; the counts read none)
+    const uint8_t *live;      // [n_batches] live masks: bit l set when lane l of the batch counts
+    int *counts;              // not nullptr: the counts [frame][height][width] go here and nothing is drawn
+};
+// tg: the whole image of every frame (no bands), or with xr.counts the view and the abort word.  The packet walk xray_packet of
+// the scene's dimension where n <= 10, the tree's stack <= 32, kernel_choice 0, no force_var and at most NT_DEV_XRAY_PACKET_ITEMS
+// items; else xray_var, which needs sc.checked (with checked_lanes = blocks of the launch * 64)
+int nt_launch_xray(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtXray &xr);
+// the rule that picks the packet walk, for the host to size the scratch by
+static inline bool nt_xray_packet_route(const NtLaunchInfo &li, const NtCompositeDev &sc) {
+    return li.n <= NT_DEV_MAX_FIXED && sc.stack_depth <= 32 && li.kernel_choice == 0 && !li.force_var &&
+           (long long)sc.n_batches + sc.n_triangles + sc.n_solids <= NT_DEV_XRAY_PACKET_ITEMS;
+}
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 // BoxScene face shading: box_shaded<N, LINES> of the scene's dimension, or box_hits_var into bs.recs and box_shaded_var behind
 // it.  tg is the whole image of every frame (no bands).  The cameras travel as for nt_launch_box.

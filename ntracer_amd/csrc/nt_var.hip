@@ -1676,6 +1676,164 @@ __global__ __launch_bounds__(64) void composite_kernel_var(NtCamera cam, NtCompo
 }
 
 // --------------------------------------------------------------------------------------
+// X-ray views at run-time n (the rule in full: ntracer_hip.h; nt_xray.hpp has the packet walk): the general
+// route, for n = 11..64, trees deeper than the packet's stack, more items than its bitset holds and NTRACER_FORCE_VAR=1.  A
+// per-lane walk over the lane's own [dist0, FLT_MAX] window with no hit, hence no cutoff and nothing to prune: every far side is
+// resumed.  The exact per-lane `Checked` bitset of the transparent kernels keeps an item met in several leaves from counting
+// twice.  The blocks stride over the 8x8-pixel tiles as composite_kernel_var_t's do: the scratch is sized by the grid.
+// --------------------------------------------------------------------------------------
+template <bool COUNTS>
+__global__ __launch_bounds__(64) void xray_var(NtCompositeDev sc, NtTarget tg, NtXray xr, int n, int tiles_x, int tiles_y, int frames) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const long long slot = (long long)blockIdx.x * 64 + lane;
+    Checked ck;
+    ck.bits = sc.checked + slot;
+    ck.stride = sc.checked_lanes;
+    ck.words = sc.checked_words;
+    ck.n_batches = sc.n_batches;
+    ck.n_triangles = sc.n_triangles;
+    const VarCtx cx = {sc, L, w, n, lane};
+    const int max_sp = sc.stack_depth;
+    const long long total = (long long)tiles_x * tiles_y * frames;
+    for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
+        if (nt_aborted(tg)) return;                       // (one wave a block)
+        const int bz = (int)(tile / ((long long)tiles_x * tiles_y));
+        const int rem = (int)(tile - (long long)bz * tiles_x * tiles_y);
+        const int by = rem / tiles_x;
+        const int bx = rem - by * tiles_x;
+        const PixelRef pr = locate_pixel_at<8, 8>(tg, bx, by, bz, lane & 7, lane >> 3, lane);
+        if (!pr.valid) continue;
+        const float *c = xr.cams + (size_t)bz * 4 * n;
+        // ---- primary ray (tracer.hpp:60-76) becomes the current ray
+        const float sx = tg.fovI * ((float)pr.x - tg.half_w);
+        const float sy = tg.fovI * ((float)pr.y - tg.half_h);
+        float sq = 0.0f;
+        for (int k = 0; k < n; ++k) {
+            const float v = (c[3 * n + k] + c[n + k] * sx) - c[2 * n + k] * sy;
+            L.dv[k * 64 + lane] = v;
+            sq = k == 0 ? v * v : sq + v * v;
+        }
+        const float len = sqrtf(sq);
+        for (int k = 0; k < n; ++k) {
+            const float dk = L.dv[k * 64 + lane] / len;
+            L.dv[k * 64 + lane] = dk;
+            L.ray[k * 64 + lane] = make_float2(c[k], dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
+        }
+        int count = 0;
+        float fr = 1.0f, fg = 1.0f, fb = 1.0f;
+        float t_near = aabb_distance_var(cx);
+        if (t_near >= 0.0f) {
+            // the Solids, every one of them in front of the walk, as xray_packet has them: the rule knows no tree, and the trees of
+            // the reference's builder leave Solids out of cells they reach.  The leaves' own are skipped below.
+            for (int idx = 0; idx < sc.n_solids; ++idx) {
+                int lane_out;
+                const float t = test_item_var(cx, (idx << 2) | 2, FLT_MAX, -1, -1, lane_out);
+                if (t == 0.0f) continue;
+                ++count;
+                if (!COUNTS) {
+                    const float *tm = xr.trans + (size_t)sc.solid_mats[idx] * 3;
+                    fr = fr * tm[0]; fg = fg * tm[1]; fb = fb * tm[2];
+                }
+            }
+            checked_reset(ck);
+            int node = sc.root, sp = 0;
+            float t_far = FLT_MAX;
+            for (;;) {
+                while (node >= 0) {
+                    const NtNode nd = sc.nodes[node];
+                    if (nd.axis < 0) {
+                        for (int i = 0; i < nd.right; ++i) {
+                            const int item = sc.items[nd.left + i];
+                            const int kind = item & 3, idx = item >> 2;
+                            if (kind > 1 || checked_seen(ck, item)) continue;
+                            if (kind == 0) {
+                                const unsigned int lv = xr.live[idx];
+                                for (int l = 0; l < NT_DEV_BATCH; ++l) {
+                                    if (((lv >> l) & 1u) == 0u) continue;
+                                    const float t = simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, n, L, lane, false, 0.0f);
+                                    if (t == 0.0f) continue;
+                                    ++count;
+                                    if (!COUNTS) {
+                                        const float *tm = xr.trans + (size_t)sc.batch_mats[idx * NT_DEV_BATCH + l] * 3;
+                                        fr = fr * tm[0]; fg = fg * tm[1]; fb = fb * tm[2];
+                                    }
+                                }
+                                continue;
+                            }
+                            // (test_item_var: the scalar rule and the Solid's own test, each with the cutoff it is handed)
+                            int lane_out;
+                            const float t = test_item_var(cx, item, FLT_MAX, -1, -1, lane_out);
+                            if (t == 0.0f) continue;
+                            ++count;
+                            if (!COUNTS) {
+                                const float *tm = xr.trans + (size_t)(kind == 1 ? sc.tri_mats[idx] : sc.solid_mats[idx]) * 3;
+                                fr = fr * tm[0]; fg = fg * tm[1]; fb = fb * tm[2];
+                            }
+                        }
+                        node = -1;
+                        break;
+                    }
+                    // kd_node_intersection::operator() (tracer.hpp:1179-1243) without a hit: trace_closest_var's branch step
+                    const float2 oi = w.ray[nd.axis * 64 + lane];
+                    const float oa = oi.x, inv = oi.y;
+                    if (inv == inv) {
+                        if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; continue; }
+                        const float t = (nd.split - oa) * inv;
+                        const bool gt = oa > nd.split;
+                        const int n_near = gt ? nd.right : nd.left;
+                        const int n_far = gt ? nd.left : nd.right;
+                        if (t < 0.0f || t > t_far) { node = n_near; continue; }
+                        if (t < t_near) { node = n_far; continue; }
+                        if (n_near >= 0) {
+                            if (sp < max_sp) { w.stack[sp * 64 + lane] = node; ++sp; }
+                            t_far = t;
+                            node = n_near;
+                            continue;
+                        }
+                        node = n_far;
+                        t_near = t;
+                        continue;
+                    }
+                    node = oa >= nd.split ? nd.right : nd.left;
+                }
+                bool resumed = false;
+                while (sp > 0) {
+                    --sp;
+                    const NtNode nd = sc.nodes[w.stack[sp * 64 + lane]];
+                    bool gt;
+                    const float t = branch_t(w, lane, nd, gt);
+                    const int far = gt ? nd.left : nd.right;
+                    if (far < 0) continue;
+                    node = far;
+                    t_near = t;
+                    t_far = FLT_MAX;
+                    if (sp > 0) {
+                        const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
+                        bool g2;
+                        t_far = branch_t(w, lane, up, g2);
+                    }
+                    resumed = true;
+                    break;
+                }
+                if (!resumed) break;
+            }
+        }
+        if (COUNTS) {
+            xr.counts[((long long)bz * tg.height + pr.y) * tg.width + pr.x] = count;
+            continue;
+        }
+        const float iv = L.dv[sc.bg_axis * 64 + lane];
+        const Color3 bgc = iv >= 0.0f ? cadd(cscale(c3p(sc.bg1), iv), cscale(c3p(sc.bg2), 1.0f - iv))
+                                      : cadd(cscale(c3p(sc.bg3), -iv), cscale(c3p(sc.bg2), 1.0f + iv));
+        emit_pixel(tg, pr, bgc.r * fr, bgc.g * fg, bgc.b * fb);
+    }
+}
+
+// --------------------------------------------------------------------------------------
 // Ray queries at run-time n (n = 11..64, and every n under NTRACER_FORCE_VAR=1): the kernels of nt_query.hpp on the walks
 // above.  One lane per ray and one wave a block, as the run-time-n render kernels have it -- their n-vectors in LDS make
 // four waves' worth too much at the upper dimensions -- so lane l of block b takes ray 64 b + l, and the blocks stride on.
@@ -3234,4 +3392,38 @@ int nt_launch_cue_apply(const NtLaunchInfo &li, const uint32_t *base, const NtCu
     const dim3 grid((unsigned)((tg.width + 63) / 64), (unsigned)((tg.height + 3) / 4), (unsigned)cu.nframes);
     hipLaunchKernelGGL(cue_apply, grid, dim3(256), 0, (hipStream_t)li.stream, base, cu, tg, li.n);
     return finish_launch("depth cue drawing kernel launch");
+}
+
+namespace {
+// the general route of an X-ray launch: xray_var, as many one-wave blocks as the `checked` scratch has lane columns for
+int xray_var_launch(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtXray &xr) {
+    int r;
+    if ((r = var_dim_check(li.n))) return r;
+    if (!sc.checked || sc.checked_lanes < 64 || !xr.cams || (sc.n_batches > 0 && !xr.live) || (!xr.counts && !xr.trans)) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: an X-ray launch without its scratch, cameras, masks or table");
+        return -1;
+    }
+    size_t lds;
+    const void *kernel = xr.counts ? reinterpret_cast<const void *>(xray_var<true>) : reinterpret_cast<const void *>(xray_var<false>);
+    if ((r = var_walk_ready(li.n, sc, kernel, lds))) return r;
+    const int tiles_x = (tg.width + 7) / 8, tiles_y = (tg.height + 7) / 8;
+    const long long tiles = (long long)tiles_x * tiles_y * li.nframes;
+    const dim3 grid((unsigned)checked_blocks(sc, tiles));
+    if (xr.counts) hipLaunchKernelGGL(xray_var<true>, grid, dim3(64), lds, (hipStream_t)li.stream, sc, tg, xr, li.n, tiles_x, tiles_y, li.nframes);
+    else hipLaunchKernelGGL(xray_var<false>, grid, dim3(64), lds, (hipStream_t)li.stream, sc, tg, xr, li.n, tiles_x, tiles_y, li.nframes);
+    return 0;
+}
+}  // namespace
+
+// X-ray views.  The packet walk of the scene's dimension (nt_xray.hpp) where nt_xray_packet_route says so -- the item count is
+// checked there, before the launch, against the bitset the walk can hold -- and xray_var for every other scene.  Kept apart from
+// every launcher above: with the setting off and no count asked for, nothing here is reached.
+int nt_launch_xray(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtXray &xr) {
+    int r = 0;
+    if (!nt_xray_packet_route(li, sc) ||
+        !nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.n, r, [&](auto N) { return nt_xray_packet<decltype(N)::value>(li, sc, tg, xr); })) {
+        r = xray_var_launch(li, sc, tg, xr);
+    }
+    if (r) return r;
+    return finish_launch("X-ray kernel launch");
 }

@@ -1001,7 +1001,7 @@ class _SceneBase(Scene):
         """What refinement_mask, occlusion_counts, outline_mask, depth_cue_factors and face_line_mask share: the buffer of `entry`
         (include/ntracer_hip.h) for a width x height view, `dtype` [height][width] + tail -- a numpy array through the host form,
         or with `device` a torch device a tensor there (zeroed first, or as allocated) through the _device form on torch's current
-        stream.  `setting` is the property that is None while the setting is off, which the device path says in `off_message`.
+        stream.  `setting` is the property that is None while the setting is off, which the device path says in `off_message` (None: no setting is needed).
         `counted`: the host form takes a pointer for a count as well, not asked for.  `plain`: an entry without
         strict_reference, whose options carry the device alone, and whose "off" answer needs no torch."""
         width, height = int(width), int(height)
@@ -1019,7 +1019,7 @@ class _SceneBase(Scene):
             out = np.zeros(shape, dtype)
             _lib.check(getattr(L, entry)(self._handle, width, height, out.ctypes.data, *((None,) if counted else ()), C.byref(opts)))
             return out
-        if plain and getattr(self, setting) is None:
+        if plain and setting is not None and getattr(self, setting) is None:
             raise ValueError(off_message)
         import torch
         dev = torch.device(device)
@@ -1027,7 +1027,7 @@ class _SceneBase(Scene):
             raise ValueError("device must be a HIP device")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        if not plain and getattr(self, setting) is None:
+        if not plain and setting is not None and getattr(self, setting) is None:
             raise ValueError(off_message)
         out = (torch.zeros if zeroed else torch.empty)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
         if plain:
@@ -1133,6 +1133,42 @@ class _SceneBase(Scene):
         `device` a torch device a torch tensor there, enqueued on torch's current stream."""
         return self._view_query("nt_outline_mask", width, height, device, np.uint8, "outlines", "outlines are off (set_outlines)",
                                 strict_reference, counted=True)
+
+    def set_xray(self, absorbance=0.2, tint=1.0):
+        """Draw the inside (include/ntracer_hip.h): every primitive the primary ray of a pixel crosses -- all of
+        them, in no order, with no cap -- multiplies the background behind it by its material's transmittance
+        T = clamp01(1 - absorbance * (1 - tint * color)) per channel.  tint = 0 is the grey X-ray, (1 - absorbance) ** count;
+        tint = 1 is stained glass.  Opacity, lights, shadows and reflections play no part.  set_xray(None) takes the setting off.
+        CompositeScene only.  Supersampling, row bands, statistics, a lens, the parallel projection, a view stack, clip planes,
+        depth cues, outlines and ambient occlusion are refused with it, and so are calculate_color / colors_at, ray_colors,
+        render_rays, refinement_mask, occlusion_counts, outline_mask and depth_cue_factors while it is on; primary_hits and the
+        ray queries ignore it.  A view setting like fov: not pickled."""
+        L = _lib.lib()
+        if absorbance is None:
+            _lib.check(L.nt_scene_set_xray(self._handle, 0, 0.0, 0.0))
+            return
+        for v in (absorbance, tint):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("absorbance and tint must be numbers")
+        _lib.check(L.nt_scene_set_xray(self._handle, 1, float(absorbance), float(tint)))
+
+    @property
+    def xray(self):
+        """None, or a dict of the setting: absorbance, tint, transmittance (float32 [n_materials][3], the table the kernels read)"""
+        L = _lib.lib()
+        on, ab, ti = C.c_int(0), C.c_float(0.0), C.c_float(0.0)
+        _lib.check(L.nt_scene_get_xray(self._handle, C.byref(on), C.byref(ab), C.byref(ti), None))
+        if not on.value:
+            return None
+        table = np.zeros((len(self._flat["materials"]), 3), f32)
+        _lib.check(L.nt_scene_get_xray(self._handle, None, None, None, table.ctypes.data_as(_lib.f32p)))
+        return dict(absorbance=float(ab.value), tint=float(ti.value), transmittance=table)
+
+    def crossing_counts(self, width, height, device=None):
+        """How many primitives the primary ray of every pixel of a width x height view of the scene's camera crosses
+        (nt_crossing_counts; the rule: include/ntracer_hip.h), whether or not set_xray is on: int32 [height][width] -- a numpy
+        array, or with `device` a torch device a torch tensor there, enqueued on torch's current stream."""
+        return self._view_query("nt_crossing_counts", width, height, device, np.int32, None, None)
 
     def set_depth_cue(self, near=0.0, far=1.0, color=(0, 0, 0), strength=1.0, background=False, tint_axis=None, tint_range=None,
                       tint_colors=None):
