@@ -1,18 +1,12 @@
 """Build libntracer_hip.so in-tree:  python -m ntracer_amd.build
 
 hipcc cross-compiles gfx950 code objects without a GPU.  The kernels are templates over the dimension; every
-dimension is its own translation unit: csrc/nt_inst_X.hip with -DNT_INST_N=N defines the one launcher nt_X_fixed<N> that
-csrc/nt_dispatch.hpp declares and csrc/nt_var.hip dispatches to (and does not compile without the macro).  N = 3..24 for
-nt_inst_box.hip, nt_inst_rays.hip, nt_inst_adaptive.hip (BoxScene's kernels; CompositeScene's up to 10), nt_inst_boxhits.hip
-(whose launcher is nt_box_faces<N>), nt_inst_boxshade.hip (nt_box_shade<N>) and nt_inst_stack.hip (nt_box_stack<N>; compiled once
-more with -DNT_INST_N=0 for the view stack's kernels that do not depend on the dimension and their launchers), 3..10 for
-nt_inst_composite.hip, nt_inst_query.hip, nt_inst_hits.hip, nt_inst_lens.hip, nt_inst_parallel.hip, nt_inst_ao.hip,
-nt_inst_outline.hip, nt_inst_cue.hip (whose launcher is nt_cue_packet<N>), nt_inst_clip.hip (nt_clip_packet<N>) and
-nt_inst_xray.hip (nt_xray_packet<N>).  units() is
-the list, and
-tests/test_dispatch.py holds the library's exports to it.  They are
-compiled in parallel into build/*.o and linked with the host side.  -ffp-contract=off is part of the arithmetic
-contract with the oracle (see csrc/nt_pixel.hpp); -fno-slp-vectorize because packing pairs of independent fp32
+dimension is its own translation unit: csrc/nt_inst_X.hip with -DNT_INST_N=N defines the launchers of dimension N that
+csrc/nt_dispatch.hpp declares and csrc/nt_var.hip dispatches to (and does not compile without the macro).  FAMILIES below is
+the table of them: the source, the launcher templates it defines, and whether it is compiled for BoxScene's range
+(N = 3..24) or CompositeScene's (3..10).  units() is derived from it, and tests/test_dispatch.py holds the library's exports
+to it.  The units are compiled in parallel into build/*.o and linked with the host side.  -ffp-contract=off is part of the
+arithmetic contract with the oracle (see csrc/nt_pixel.hpp); -fno-slp-vectorize because packing pairs of independent fp32
 operations into v_pk_* costs more register shuffling than it saves here (measured: 2-4 %)."""
 import concurrent.futures
 import hashlib
@@ -36,34 +30,46 @@ EXTRA = os.environ.get("NTRACER_HIPCC_FLAGS", "").split()         # ablation bui
 UNIT_HDR = {"nt_inst_stack.hip": [os.path.join(CSRC, "nt_stack.hpp")], "nt_inst_xray.hip": [os.path.join(CSRC, "nt_xray.hpp")]}
 
 
+# The per-dimension families, in the order of one dimension's units (the link order follows it):
+# (instantiation source, the launcher templates it defines, compiled for BoxScene's range as well?).
+# Every unit nt_X_<N> is csrc/nt_inst_X.hip with -DNT_INST_N=N, N in DIMS, and in BOX_ONLY_DIMS too where the last column says so.
+FAMILIES = (
+    ("nt_inst_box.hip", ("nt_box_fixed",), True),
+    ("nt_inst_composite.hip", ("nt_composite_fixed",), False),
+    ("nt_inst_query.hip", ("nt_query_fixed",), False),
+    ("nt_inst_hits.hip", ("nt_hits_fixed",), False),
+    ("nt_inst_rays.hip", ("nt_rays_box_fixed", "nt_rays_fixed"), True),
+    ("nt_inst_adaptive.hip", ("nt_refine_box_fixed", "nt_refine_fixed"), True),
+    ("nt_inst_lens.hip", ("nt_lens_fixed",), False),
+    ("nt_inst_parallel.hip", ("nt_parallel_fixed",), False),
+    ("nt_inst_ao.hip", ("nt_ao_fixed",), False),
+    ("nt_inst_outline.hip", ("nt_outline_fixed",), False),
+    ("nt_inst_cue.hip", ("nt_cue_packet",), False),
+    ("nt_inst_boxhits.hip", ("nt_box_faces",), True),
+    ("nt_inst_clip.hip", ("nt_clip_packet",), False),
+    ("nt_inst_boxshade.hip", ("nt_box_shade",), True),
+    ("nt_inst_stack.hip", ("nt_box_stack",), True),
+    ("nt_inst_xray.hip", ("nt_xray_packet",), False),
+)
+# CompositeScene's launchers that share a unit with BoxScene's: their sources define them up to DIMS alone (#if NT_INST_N <= NT_DEV_MAX_FIXED)
+COMPOSITE_IN_BOX_UNITS = ("nt_rays_fixed", "nt_refine_fixed")
+
+
+def launcher_dims():
+    """{launcher template: the dimensions the library defines it for} (tests/test_dispatch.py holds the exports to it)"""
+    return {name: list(DIMS) + (list(BOX_ONLY_DIMS) if box and name not in COMPOSITE_IN_BOX_UNITS else [])
+            for _, names, box in FAMILIES for name in names}
+
+
 def units():
     """(object name, source, extra flags)"""
+    # nt_stack_any: the view stack's kernels that do not depend on the dimension, and their launchers
     u = [("nt_api", "nt_api.cpp", []), ("nt_builder", "nt_builder.cpp", []), ("nt_launch", "nt_launch.cpp", []),
          ("nt_var", "nt_var.hip", []), ("nt_stack_any", "nt_inst_stack.hip", ["-DNT_INST_N=0"])]
-    for n in DIMS:
-        u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_composite_%d" % n, "nt_inst_composite.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_query_%d" % n, "nt_inst_query.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_hits_%d" % n, "nt_inst_hits.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_adaptive_%d" % n, "nt_inst_adaptive.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_lens_%d" % n, "nt_inst_lens.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_parallel_%d" % n, "nt_inst_parallel.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_ao_%d" % n, "nt_inst_ao.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_outline_%d" % n, "nt_inst_outline.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_cue_%d" % n, "nt_inst_cue.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_clip_%d" % n, "nt_inst_clip.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_stack_%d" % n, "nt_inst_stack.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_xray_%d" % n, "nt_inst_xray.hip", ["-DNT_INST_N=%d" % n]))
-    for n in BOX_ONLY_DIMS:
-        u.append(("nt_box_%d" % n, "nt_inst_box.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_rays_%d" % n, "nt_inst_rays.hip", ["-DNT_INST_N=%d" % n]))      # (BoxScene's kernel alone)
-        u.append(("nt_adaptive_%d" % n, "nt_inst_adaptive.hip", ["-DNT_INST_N=%d" % n]))  # (likewise)
-        u.append(("nt_boxhits_%d" % n, "nt_inst_boxhits.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_boxshade_%d" % n, "nt_inst_boxshade.hip", ["-DNT_INST_N=%d" % n]))
-        u.append(("nt_stack_%d" % n, "nt_inst_stack.hip", ["-DNT_INST_N=%d" % n]))
+    for dims, box_only in ((DIMS, False), (BOX_ONLY_DIMS, True)):
+        for n in dims:
+            u += [("%s_%d" % (src[:-len(".hip")].replace("_inst", ""), n), src, ["-DNT_INST_N=%d" % n])
+                  for src, _, box in FAMILIES if box or not box_only]
     return u
 
 

@@ -41,6 +41,7 @@ import fixtures as fx
 import oracle_binding as ob
 import ray_color_cases as rc
 import ss_expected as sx
+import support as sup
 
 f32 = np.float32
 W, H = 203, 117
@@ -83,7 +84,7 @@ def box_route(n):
 
 def plain_colors(osc, w, h):
     """(h, w, 3) float32: the oracle's plain frame, clamped"""
-    return osc.render(w, h, fx.RGBF32, threads=sx.threads()).view(">f4").astype(f32).reshape(h, w, 3)
+    return osc.render(w, h, fx.RGBF32, threads=sup.worker_threads()).view(">f4").astype(f32).reshape(h, w, 3)
 
 
 def _neighbour_deltas(P):

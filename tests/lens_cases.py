@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import fixtures as fx
 import ray_color_cases as rc
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import tracern
 
 f32 = np.float32
@@ -223,10 +224,7 @@ def expected(case, cam=None):
 def scene(case, mp):
     """the case's scene on the library, its camera set and the switches in the environment of `mp`"""
     name, env, variant = case[:3]
-    for k in SWITCHES:
-        mp.delenv(k, raising=False)
-    for k, v in env.items():
-        mp.setenv(k, v)
+    sup.set_switches(mp, SWITCHES, env)
     if is_box(name):
         sc = tracern.BoxScene(int(name[3:]))
     else:

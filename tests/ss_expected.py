@@ -7,16 +7,12 @@ import numpy as np
 
 import fixtures as fx
 import oracle_binding as ob
-
-
-def threads():
-    import bench
-    return max(1, min(64, bench.cpu_quota_cores() - 1))
+import support as sup
 
 
 def mean_colors(osc, w, h, s):
     """(h, w, 3) float32: the box-filtered colours of the oracle scene's s*w x s*h frame"""
-    hi = osc.render(s * w, s * h, fx.RGBF32, threads=threads()).view(">f4").astype(np.float32).reshape(s * h, s * w, 3)
+    hi = osc.render(s * w, s * h, fx.RGBF32, threads=sup.worker_threads()).view(">f4").astype(np.float32).reshape(s * h, s * w, 3)
     acc = hi[0::s, 0::s]
     for j in range(s):
         for i in range(s):

@@ -14,6 +14,7 @@ import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -28,16 +29,6 @@ PACKED = [("rgbx8", fx.RGBX8, False), ("rgb24", RGB24, False), ("rgb565", RGB565
           ("rgb24-reversed", RGB24, True), ("rgbx8-reversed", fx.RGBX8, True)]
 
 
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene, fmt, **kw):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene, **kw)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
 def box_scene(n, camera, s, t):
     o, a = ac.box_cameras(n)[camera]
     sc = tracern.BoxScene(n)
@@ -49,10 +40,7 @@ def box_scene(n, camera, s, t):
 
 def composite_scene(case, mp):
     name, env = case[0], case[1]
-    for k in ac.SWITCHES:
-        mp.delenv(k, raising=False)
-    for k, v in env.items():
-        mp.setenv(k, v)
+    sup.set_switches(mp, ac.SWITCHES, env)
     n, flat, params, o, a, _ = ac.case_oracle(case)
     sc = tracern.CompositeScene.from_flat(n, flat)
     sc.set_params_flat(params)
@@ -70,7 +58,7 @@ def test_box_scene_equals_the_expected_image_and_mask_exactly(n, s):
         sc = box_scene(n, k, s, T)
         pick = [("rgbf32", fx.RGBF32, False), PACKED[(2 * j + s) % len(PACKED)], PACKED[(2 * j + s + 1) % len(PACKED)]]
         for name, chans, rev in pick:
-            img = render_host(sc, fmt_of(W, H, chans, rev=rev))
+            img = sup.render_host(sc, sup.fmt_of(W, H, chans, rev=rev))
             want = e.image(chans, rev)
             assert np.array_equal(img, want), (n, s, k, name, int((img != want).sum()))
         mask = sc.refinement_mask(W, H)
@@ -111,7 +99,7 @@ def test_composite_scene_within_the_projects_tolerances_of_the_expected_image(ca
     sc.set_adaptive_supersampling(T)
     e = ac.case_expected(case, s)
     for chans in (fx.RGBF32, fx.RGBX8):
-        img = render_host(sc, fmt_of(W, H, chans))
+        img = sup.render_host(sc, sup.fmt_of(W, H, chans))
         assert_decided_close(img, e, chans, "%s s=%d" % (ac.case_id(case), s))
     mask = sc.refinement_mask(W, H)
     assert np.array_equal(mask[~e.undecided], e.mask[~e.undecided]), int((mask != e.mask)[~e.undecided].sum())
@@ -129,17 +117,17 @@ def test_threshold_extremes_box_scene():
     for s in (2, 3):
         full.set_supersampling(s)
         for name, chans, rev in [("rgbf32", fx.RGBF32, False)] + PACKED[:3]:
-            fmt = fmt_of(W, H, chans, rev=rev)
+            fmt = sup.fmt_of(W, H, chans, rev=rev)
             sc = box_scene(n, k, s, -1.0)
-            assert np.array_equal(render_host(sc, fmt), render_host(full, fmt)), (s, name)
-            assert np.array_equal(render_host(sc, fmt), sx.expected(ob.OracleScene(n, o, a), W, H, s, chans, rev)), (s, name)
+            assert np.array_equal(sup.render_host(sc, fmt), sup.render_host(full, fmt)), (s, name)
+            assert np.array_equal(sup.render_host(sc, fmt), sx.expected(ob.OracleScene(n, o, a), W, H, s, chans, rev)), (s, name)
             assert sc.refinement_mask(W, H).all()
             sc.set_adaptive_supersampling(2.0)
-            assert np.array_equal(render_host(sc, fmt), render_host(plain, fmt)), (s, name)
+            assert np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt)), (s, name)
             assert not sc.refinement_mask(W, H).any()
             sc.set_adaptive_supersampling(T)
             sc.set_supersampling(1)
-            assert np.array_equal(render_host(sc, fmt), render_host(plain, fmt)), (s, name)
+            assert np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt)), (s, name)
             assert np.array_equal(sc.refinement_mask(W, H), ac.box_expected(n, 2, k).mask)        # the mask does not ask for the factor
 
 
@@ -148,11 +136,11 @@ def test_threshold_extremes_composite_scene(name, monkeypatch):
     case = [c for c in ac.CASES if c[0] == name and not c[1] and not c[2]][0]
     s = 2
     sc = composite_scene(case, monkeypatch)
-    plain = {chans is fx.RGBF32: render_host(sc, fmt_of(W, H, chans)) for chans in (fx.RGBF32, fx.RGBX8)}
+    plain = {chans is fx.RGBF32: sup.render_host(sc, sup.fmt_of(W, H, chans)) for chans in (fx.RGBF32, fx.RGBX8)}
     sc.set_supersampling(s)
-    full = render_host(sc, fmt_of(W, H, fx.RGBF32))
+    full = sup.render_host(sc, sup.fmt_of(W, H, fx.RGBF32))
     sc.set_adaptive_supersampling(-1.0)
-    img = render_host(sc, fmt_of(W, H, fx.RGBF32))
+    img = sup.render_host(sc, sup.fmt_of(W, H, fx.RGBF32))
     d = np.abs(img.view(">f4").astype(np.float32) - full.view(">f4").astype(np.float32)).max()
     print(name, "t = -1 against the supersampled render: max |delta| %.3g" % float(d))
     assert d <= TOL_ORACLE
@@ -161,11 +149,11 @@ def test_threshold_extremes_composite_scene(name, monkeypatch):
     assert d <= TOL_ORACLE
     sc.set_adaptive_supersampling(2.0)
     for chans in (fx.RGBF32, fx.RGBX8):
-        assert np.array_equal(render_host(sc, fmt_of(W, H, chans)), plain[chans is fx.RGBF32])
+        assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, chans)), plain[chans is fx.RGBF32])
     sc.set_adaptive_supersampling(T)
     sc.set_supersampling(1)
     for chans in (fx.RGBF32, fx.RGBX8):
-        assert np.array_equal(render_host(sc, fmt_of(W, H, chans)), plain[chans is fx.RGBF32])
+        assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, chans)), plain[chans is fx.RGBF32])
 
 
 # ------------------------------------------------------------------ 4. shapes
@@ -189,16 +177,16 @@ def test_shapes_formats_pitches_and_an_unaligned_destination(w, h):
     assert np.array_equal(sc.refinement_mask(w, h), e.mask)
     for name, chans, rev in [("rgbf32", fx.RGBF32, False)] + PACKED:
         bpp = len(e.image(chans, rev)[0]) // w
-        img = render_host(sc, fmt_of(w, h, chans, rev=rev))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans, rev=rev))
         assert np.array_equal(img, e.image(chans, rev)), (name, int((img != e.image(chans, rev)).sum()))
-        fmt = fmt_of(w, h, chans, pitch=w * bpp + 7, rev=rev)
+        fmt = sup.fmt_of(w, h, chans, pitch=w * bpp + 7, rev=rev)
         buf = bytearray(b"\xb3" * (fmt.pitch * h))
         assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
         got = np.frombuffer(bytes(buf), np.uint8).reshape(h, fmt.pitch)
         assert np.array_equal(got[:, :w * bpp], e.image(chans, rev)), name
         assert (got[:, w * bpp:] == 0xb3).all(), name
     for rev in (False, True):
-        fmt = fmt_of(w, h, RGB24, pitch=3 * w + 5, rev=rev)
+        fmt = sup.fmt_of(w, h, RGB24, pitch=3 * w + 5, rev=rev)
         buf = torch.full((fmt.pitch * h + 16,), 0x5C, dtype=torch.uint8, device="cuda")
         dest = buf[1:1 + fmt.pitch * h]
         fst = fmt._as_struct()
@@ -230,11 +218,11 @@ def test_three_frames_equal_single_renders_whatever_the_chunking(which, monkeypa
         cams = [(g["origins"][f], g["axes"][f]) for f in (0, 1, 2)]
     sc.set_supersampling(s)
     sc.set_adaptive_supersampling(T)
-    fmt = fmt_of(W, H, chans)
+    fmt = sup.fmt_of(W, H, chans)
     singles = []
     for o, a in cams:
         sc._set_camera_arrays(o, a)
-        singles.append(render_host(sc, fmt))
+        singles.append(sup.render_host(sc, fmt))
     if which == "box6":
         for j, k in enumerate(ac.BOX_CAMERAS):
             assert np.array_equal(singles[j], ac.box_expected(n, s, k).image(chans))
@@ -262,7 +250,7 @@ def test_three_frames_equal_single_renders_whatever_the_chunking(which, monkeypa
         assert np.array_equal(got[:, :fmt.pitch * H].reshape(nf, H, fmt.pitch), singles), mib
         assert (got[:, fmt.pitch * H:] == 0x3D).all()
         sc._set_camera_arrays(*cams[1])
-        assert np.array_equal(render_host(sc, fmt), singles[1])
+        assert np.array_equal(sup.render_host(sc, fmt), singles[1])
 
 
 def test_a_frame_that_does_not_fit_the_scratch_cap_is_refused_before_anything_is_launched():
@@ -271,17 +259,17 @@ def test_a_frame_that_does_not_fit_the_scratch_cap_is_refused_before_anything_is
     sc = box_scene(n, k, s, T)
     sc.set_supersampling_scratch_mb(1)
     L = _lib.lib()
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     fst = fmt._as_struct()
     dest = (C.c_char * (fmt.pitch * h))(*([0x4E] * (fmt.pitch * h)))
     assert L.nt_render(sc._handle, dest, fmt.pitch * h, C.byref(fst), None, None) == _lib.NT_E_UNSUPPORTED
     assert "adaptive" in _lib.last_error() and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error() and "1 MiB" in _lib.last_error()
     assert bytes(dest) == b"\x4e" * (fmt.pitch * h)
     with pytest.raises(NotImplementedError):
-        render_host(sc, fmt)
+        sup.render_host(sc, fmt)
     sc.set_supersampling_scratch_mb(1024)
     e = ac.box_expected(n, s, k, T, w, h)
-    img = render_host(sc, fmt)
+    img = sup.render_host(sc, fmt)
     assert np.array_equal(img, e.image(fx.RGBX8)), int((img != e.image(fx.RGBX8)).sum())
 
 
@@ -291,7 +279,7 @@ def test_a_torch_destination_and_a_device_mask_on_the_current_stream():
     n, k, s = 6, 7, 2
     sc = box_scene(n, k, s, T)
     e = ac.box_expected(n, s, k)
-    fmt = fmt_of(W, H, fx.RGBX8)
+    fmt = sup.fmt_of(W, H, fx.RGBX8)
     st = torch.cuda.Stream()
     with torch.cuda.stream(st):
         buf = torch.zeros(fmt.pitch * H, dtype=torch.uint8, device="cuda")
@@ -313,7 +301,7 @@ def test_an_adaptive_table_call_is_still_capturable():
     cams = [ac.box_cameras(n)[k] for k in ac.BOX_CAMERAS]
     origins = np.ascontiguousarray(np.stack([c[0] for c in cams]), np.float32)
     axes = np.ascontiguousarray(np.stack([c[1] for c in cams]), np.float32)
-    fmt = fmt_of(W, H, fx.RGBX8)
+    fmt = sup.fmt_of(W, H, fx.RGBX8)
     fst = fmt._as_struct()
     sc = tracern.BoxScene(n)
     sc.set_supersampling(s)
@@ -351,7 +339,7 @@ def test_an_abort_word_raised_before_the_call_and_the_refusals_draw_nothing(monk
     sc = composite_scene(case, monkeypatch)
     sc.set_supersampling(2)
     sc.set_adaptive_supersampling(T)
-    fmt = fmt_of(W, H, fx.RGBX8)
+    fmt = sup.fmt_of(W, H, fx.RGBX8)
     fst = fmt._as_struct()
     size = fmt.pitch * H
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -376,7 +364,7 @@ def test_an_abort_word_raised_before_the_call_and_the_refusals_draw_nothing(monk
     torch.cuda.synchronize()
     _lib.check(L.nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), C.byref(opts), stream))
     torch.cuda.synchronize()
-    assert np.array_equal(buf.cpu().numpy().reshape(H, fmt.pitch), render_host(sc, fmt))
+    assert np.array_equal(buf.cpu().numpy().reshape(H, fmt.pitch), sup.render_host(sc, fmt))
     # what the setting refuses leaves the destination as it was
     buf.fill_(0x6A)
     for field in ("band_world", "collect_stats"):
@@ -389,9 +377,9 @@ def test_an_abort_word_raised_before_the_call_and_the_refusals_draw_nothing(monk
     torch.cuda.synchronize()
     assert bool((buf == 0x6A).all()) and bytes(dest) == b"\x6a" * size
     with pytest.raises(NotImplementedError, match="adaptive"):
-        render_host(sc, fmt, band_rank=0, band_world=2)
+        sup.render_host(sc, fmt, band_rank=0, band_world=2)
     with pytest.raises(NotImplementedError, match="adaptive"):
-        render_host(sc, fmt, collect_stats=True)
+        sup.render_host(sc, fmt, collect_stats=True)
     # the probes, the primary hits and the caller's rays ignore the setting, as they ignore the factor: a scene with both set
     # answers as one with neither
     n, flat, params, o, a, osc = ac.case_oracle(case)
@@ -409,7 +397,7 @@ def test_an_abort_word_raised_before_the_call_and_the_refusals_draw_nothing(monk
     dirs = rc.camera_rays(a, xs, ys, W, H)
     assert np.array_equal(sc.ray_colors(o, dirs).view(np.uint32), plain.ray_colors(o, dirs).view(np.uint32))
     assert np.abs(sc.ray_colors(o, dirs) - osc.colors_at(xs, ys, W, H)).max() <= TOL_ORACLE
-    small = fmt_of(10, 10, fx.RGBX8)
+    small = sup.fmt_of(10, 10, fx.RGBX8)
     images = []
     for scene in (sc, plain):
         img = bytearray(small.pitch * 10)

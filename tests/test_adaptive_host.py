@@ -15,10 +15,10 @@ import adaptive_cases as ac
 import fixtures as fx
 import oracle_binding as ob
 import ss_expected as sx
+import support as sup
 from ntracer_amd import Channel, ImageFormat, _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 f32 = np.float32
 
 
@@ -227,7 +227,7 @@ def test_the_builder_at_the_extremes_of_the_threshold():
     o, a = ac.box_cameras(n)[7]
     osc = ob.OracleScene(n, o, a)
     mean = sx.mean_colors(osc, ac.W, ac.H, s)
-    plain = osc.render(ac.W, ac.H, fx.RGBF32, threads=sx.threads())
+    plain = osc.render(ac.W, ac.H, fx.RGBF32, threads=sup.worker_threads())
     e = ac.expected(osc, ac.W, ac.H, s, -1.0)
     assert e.mask.all() and not e.undecided.any()
     assert np.array_equal(e.pick.view(np.uint32), mean.view(np.uint32))
@@ -235,7 +235,7 @@ def test_the_builder_at_the_extremes_of_the_threshold():
     e = ac.expected(osc, ac.W, ac.H, s, 2.0)
     assert not e.mask.any() and not e.undecided.any()
     assert np.array_equal(e.image(fx.RGBF32), plain)
-    assert np.array_equal(e.image(fx.RGBX8), osc.render(ac.W, ac.H, fx.RGBX8, threads=sx.threads()))
+    assert np.array_equal(e.image(fx.RGBX8), osc.render(ac.W, ac.H, fx.RGBX8, threads=sup.worker_threads()))
     # in between it mixes the two, and the two differ
     e = ac.expected(osc, ac.W, ac.H, s, ac.T)
     assert np.array_equal(e.pick[e.mask].view(np.uint32), mean[e.mask].view(np.uint32))
@@ -281,28 +281,12 @@ def test_the_shares_the_cases_were_chosen_by():
 
 
 # ------------------------------------------------------------------ the launches
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_ray_colors_host.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
-
-
 def test_every_launch_of_the_new_launchers_is_reached_by_a_case():
-    hpp, var = _read("nt_adaptive.hpp"), _read("nt_var.hip")
-    launched = (_launches(_body(hpp, "int launch_refine_fixed(")) | _launches(_body(hpp, "int launch_refine_box_fixed(")) |
-                _launches(_body(hpp, "inline void launch_adaptive_flag(")) | _launches(_body(var, "int nt_launch_refine(")))
+    hpp, var = sup.source("nt_adaptive.hpp"), sup.source("nt_var.hip")
+    launched = (sup.launches(sup.function_body(hpp, "int launch_refine_fixed(")) | sup.launches(sup.function_body(hpp, "int launch_refine_box_fixed(")) |
+                sup.launches(sup.function_body(hpp, "inline void launch_adaptive_flag(")) | sup.launches(sup.function_body(var, "int nt_launch_refine(")))
     assert len(launched) >= 12, sorted(launched)             # the scan still finds the launches
-    assert launched == _launches(hpp) | _launches(_body(var, "int nt_launch_refine("))        # no launch of the header outside the launchers
+    assert launched == sup.launches(hpp) | sup.launches(sup.function_body(var, "int nt_launch_refine("))        # no launch of the header outside the launchers
     reached = {ac.route(case) for case in ac.CASES} | {ac.box_route(n) for n, _ in ac.BOX_CASES} | set(ac.FLAG_ROUTES)
     assert reached == launched, ("launched without a case: %s; routes nothing launches: %s"
                                  % (sorted(launched - reached), sorted(reached - launched)))
@@ -311,7 +295,7 @@ def test_every_launch_of_the_new_launchers_is_reached_by_a_case():
     # the launches stay out of the render and ray launchers, and route on the switches read_switches already reads
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("),
                       ("nt_var.hip", "int nt_launch_box("), ("nt_var.hip", "int nt_launch_rays(")):
-        assert not any(k.startswith(("refine_", "adaptive_")) for k in _launches(_body(_read(src), head)))
-    assert "getenv" not in hpp and "getenv" not in _body(var, "int nt_launch_refine(")
-    api = _read("nt_api.cpp")
-    assert "getenv" not in _body(api, "int enqueue_adaptive(")
+        assert not any(k.startswith(("refine_", "adaptive_")) for k in sup.launches(sup.function_body(sup.source(src), head)))
+    assert "getenv" not in hpp and "getenv" not in sup.function_body(var, "int nt_launch_refine(")
+    api = sup.source("nt_api.cpp")
+    assert "getenv" not in sup.function_body(api, "int enqueue_adaptive(")

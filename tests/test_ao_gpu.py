@@ -19,6 +19,7 @@ import ntracer_amd
 import primary_hit_cases as ph
 import ray_query_cases as rq
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -36,10 +37,7 @@ FORMATS = [("rgbx8", fx.RGBX8, False), ("rgb24", RGB24, False), ("rgb16", fx.RGB
 
 def _scene(case, mp, k=0):
     name, env = case
-    for key in ao.SWITCHES:
-        mp.delenv(key, raising=False)
-    for key, v in env.items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, ao.SWITCHES, env)
     g, n, flat = rq.scene(name)
     sc = tracern.CompositeScene.from_flat(n, flat)
     sc.set_params_flat(ao.scene_params(name))
@@ -54,21 +52,11 @@ def _standard(sc, n, **kw):
     sc.set_ambient_occlusion(args.pop("T", ao.table(n)), **args)
 
 
-def _opts(abort=None):
-    import os
-    opts = _lib.NtRenderOpts()
-    opts.device = -1
-    opts.strict_reference = 1 if os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0") else 0
-    if abort is not None:
-        opts.abort_device = abort.data_ptr()
-    return opts
-
-
 def _device_counts(sc, w, h, abort=None):
     """nt_ambient_occlusion_device on a sentinel-filled buffer with PAD dwords behind it: the raw buffer"""
     import torch
     buf = torch.full((w * h + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
-    opts = _opts(abort)
+    opts = sup.render_opts(abort, strict_reference=sup.strict_reference())
     _lib.check(_lib.lib().nt_ambient_occlusion_device(sc._handle, w, h, C.c_void_p(buf.data_ptr()), C.byref(opts),
                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
@@ -165,33 +153,10 @@ def test_k_and_the_parameters(label, case, size, kw):
 
 
 # ------------------------------------------------------------------ 4. renders
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene, fmt, **kw):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene, **kw)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
 def plain_colors(sc, w, h):
     """P: the library's plain fp32 x 3 frame of a scene whose setting is off, [h][w][3] float32, clamped by the packer"""
     assert sc.ambient_occlusion is None
-    return render_host(sc, fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
-
-
-def render_device(sc, fmt, opts=None, fill=0x3D):
-    import torch
-    size = fmt.pitch * fmt.height
-    buf = torch.full((size + 16,), fill, dtype=torch.uint8, device="cuda")
-    fst = fmt._as_struct()
-    status = _lib.lib().nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), None if opts is None else C.byref(opts),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[size:] == fill).all()
-    return status, got[:size].reshape(fmt.height, fmt.pitch)
+    return sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
 
 
 @pytest.mark.parametrize("name", ["feature5_n5", "cell120_n4"])
@@ -207,14 +172,14 @@ def test_renders_equal_the_plain_frame_times_the_oracles_factor(name):
         _standard(sc, n, strength=STRENGTH)
         for fname, chans, rev in FORMATS:
             want = sx.pack(want_rgb, chans, rev)
-            fmt = fmt_of(W, H, chans, rev=rev)
-            img = render_host(sc, fmt)
+            fmt = sup.fmt_of(W, H, chans, rev=rev)
+            img = sup.render_host(sc, fmt)
             assert np.array_equal(img, want), (name, fname, "BlockingRenderer", int((img != want).sum()))
-            status, img = render_device(sc, fmt)
+            status, img = sup.render_device(sc, fmt)
             assert status == 0 and np.array_equal(img, want), (name, fname, "nt_render_device", int((img != want).sum()))
         # a padded pitch keeps its padding
         bpp = 3
-        fmt = fmt_of(W, H, RGB24, pitch=W * bpp + 5)
+        fmt = sup.fmt_of(W, H, RGB24, pitch=W * bpp + 5)
         buf = bytearray(b"\xb3" * (fmt.pitch * H))
         assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
         got = np.frombuffer(bytes(buf), np.uint8).reshape(H, fmt.pitch)
@@ -233,11 +198,11 @@ def test_three_frames_of_a_camera_table_equal_three_single_renders(name):
         P = plain_colors(sc, W, H)
         _standard(sc, n, strength=STRENGTH)
         for fname, chans, rev in (FORMATS[0], FORMATS[1]):
-            fmt = fmt_of(W, H, chans, rev=rev)
+            fmt = sup.fmt_of(W, H, chans, rev=rev)
             singles = []
             for o, a in cams:
                 sc._set_camera_arrays(o, a)
-                singles.append(render_host(sc, fmt))
+                singles.append(sup.render_host(sc, fmt))
             singles = np.stack(singles)
             assert np.array_equal(singles[0], sx.pack(ao.shade(P, ao.expected(case, W, H)["blocked"], ao.K, STRENGTH), chans, rev))
             assert not np.array_equal(singles[0], singles[1])
@@ -275,7 +240,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes(name):
         sc = _scene(case, mp)
         _standard(sc, n, strength=STRENGTH)
         table = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
-        fmt = fmt_of(w, h, RGB24)
+        fmt = sup.fmt_of(w, h, RGB24)
         frame_bytes = fmt.pitch * h
         images, counts = [], []
         for mib in (1024, 1):
@@ -299,8 +264,8 @@ def test_a_frame_that_does_not_fit_the_scratch_cap_is_refused_before_anything_is
         sc = _scene(case, mp)
         _standard(sc, 4)
         sc.set_supersampling_scratch_mb(1)
-        fmt = fmt_of(w, h, fx.RGBX8)
-        status, img = render_device(sc, fmt, fill=0x4E)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        status, img = sup.render_device(sc, fmt, fill=0x4E)
         assert status == _lib.NT_E_UNSUPPORTED and (img == 0x4E).all()
         assert _lib.last_error().startswith("ambient occlusion") and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error()
         with pytest.raises(NotImplementedError, match="ambient occlusion"):
@@ -316,14 +281,14 @@ def test_strength_zero_and_a_scene_where_nothing_blocks_give_the_plain_bytes():
         n = rq.scene(name)[1]
         with pytest.MonkeyPatch.context() as mp:
             sc = _scene(case, mp)
-            plain = {f[0]: render_host(sc, fmt_of(W, H, f[1], rev=f[2])) for f in FORMATS}
+            plain = {f[0]: sup.render_host(sc, sup.fmt_of(W, H, f[1], rev=f[2])) for f in FORMATS}
             _standard(sc, n, **kw)
             for fname, chans, rev in FORMATS:
-                assert np.array_equal(render_host(sc, fmt_of(W, H, chans, rev=rev)), plain[fname]), (name, fname)
+                assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, chans, rev=rev)), plain[fname]), (name, fname)
             assert len(np.unique(plain["rgbx8"])) > 8
             # and taking the setting off again is the plain render
             sc.set_ambient_occlusion(None)
-            assert np.array_equal(render_host(sc, fmt_of(W, H, fx.RGBX8)), plain["rgbx8"])
+            assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, fx.RGBX8)), plain["rgbx8"])
 
 
 def test_the_probes_the_hits_and_the_queries_ignore_the_setting():
@@ -345,8 +310,8 @@ def test_the_colours_of_caller_rays_and_the_ray_queries_ignore_the_setting():
     with pytest.MonkeyPatch.context() as mp:
         sc, plain = _scene(case, mp), _scene(case, mp)
         _standard(sc, 4)
-        fmt = fmt_of(W, H, fx.RGBX8)
-        assert not np.array_equal(render_host(sc, fmt), render_host(plain, fmt))
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        assert not np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt))
         origin, axes = ph.camera("cell120_n4", 0)
         d = np.ascontiguousarray(ph.rays("cell120_n4", W, H, 0)[0].reshape(W * H, 4), np.float32)
         o = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, np.float32), d.shape))
@@ -375,15 +340,15 @@ def test_an_abort_word_raised_before_the_launch_leaves_the_buffers_untouched(nam
         torch.cuda.synchronize()
         raw = _device_counts(sc, W, H, abort=word)
         assert (raw == SENTINEL).all()
-        fmt = fmt_of(W, H, fx.RGBX8)
-        status, img = render_device(sc, fmt, opts=_opts(word), fill=0x6A)
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        status, img = sup.render_device(sc, fmt, opts=sup.render_opts(word, strict_reference=sup.strict_reference()), fill=0x6A)
         assert status == 0 and (img == 0x6A).all()
         word.zero_()
         torch.cuda.synchronize()
         raw = _device_counts(sc, W, H, abort=word)
         _assert_counts(raw[:W * H].reshape(H, W), ao.expected(case, W, H)["blocked"], name + " after the abort word went down")
-        status, img = render_device(sc, fmt, opts=_opts(word), fill=0x6A)
-        assert status == 0 and np.array_equal(img, render_host(sc, fmt))
+        status, img = sup.render_device(sc, fmt, opts=sup.render_opts(word, strict_reference=sup.strict_reference()), fill=0x6A)
+        assert status == 0 and np.array_equal(img, sup.render_host(sc, fmt))
 
 
 # ------------------------------------------------------------------ 8. repeat
@@ -403,8 +368,8 @@ def test_two_calls_in_a_row_agree_and_a_warm_table_render_is_capturable(name):
         a, b = _device_counts(sc, W, H), _device_counts(sc, W, H)
         assert np.array_equal(a, b)
         _assert_counts(b[:W * H].reshape(H, W), ao.expected(case, W, H)["blocked"], name + " second call")
-        fmt = fmt_of(W, H, fx.RGBX8)
-        assert np.array_equal(render_host(sc, fmt), render_host(sc, fmt))
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        assert np.array_equal(sup.render_host(sc, fmt), sup.render_host(sc, fmt))
         fst = fmt._as_struct()
         tab = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         st = torch.cuda.Stream()
@@ -428,4 +393,4 @@ def test_two_calls_in_a_row_agree_and_a_warm_table_render_is_capturable(name):
         assert torch.equal(fb, ref)
         del gr
         sc._set_camera_arrays(*cams[1])
-        assert np.array_equal(ref[1].cpu().numpy().reshape(H, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(ref[1].cpu().numpy().reshape(H, fmt.pitch), sup.render_host(sc, fmt))

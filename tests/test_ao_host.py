@@ -6,20 +6,16 @@ nt_launch_ao_expand, nt_launch_ao_reduce and nt_launch_ao_apply (nt_var.hip) has
 (scene, switches) cases that tests/test_ao_gpu.py runs."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
 import ao_cases as ao
-import fixtures as fx
 import ntracer_amd
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
 FAST = [("cell120_n4", {}), ("cell120_n4", {"NTRACER_STRICT_REFERENCE": "1"}), ("cell120_n4", {"NTRACER_COMPOSITE_KERNEL": "2"}),
         ("orthoplex5_n5", {})]
@@ -36,22 +32,6 @@ AO_ROUTES = [
 ]
 
 
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
-
-
 def _routes(name, env):
     """the counting kernels a (scene, switches) case launches, by the rule of enqueue_ao (nt_api.cpp) and launch_ao_fixed"""
     g, n, flat = rq.scene(name)
@@ -65,10 +45,10 @@ def _routes(name, env):
 
 
 def test_every_ao_launch_has_a_row_and_every_row_a_gpu_case():
-    var = _read("nt_var.hip")
-    launched = _launches(_body(_read("nt_ao.hpp"), "int launch_ao_fixed("))
+    var = sup.source("nt_var.hip")
+    launched = sup.launches(sup.function_body(sup.source("nt_ao.hpp"), "int launch_ao_fixed("))
     for head in ("int nt_launch_ao(", "int nt_launch_ao_expand(", "int nt_launch_ao_reduce(", "int nt_launch_ao_apply("):
-        launched |= _launches(_body(var, head))
+        launched |= sup.launches(sup.function_body(var, head))
     rows = [k for k, _ in AO_ROUTES]
     assert len(rows) == len(set(rows)) == 5
     assert set(rows) == launched, (sorted(launched - set(rows)), sorted(set(rows) - launched))
@@ -83,7 +63,7 @@ def test_every_ao_launch_has_a_row_and_every_row_a_gpu_case():
     for name, env in ao.CASES:
         assert _routes(name, env) <= set(rows), (name, env)
     # the rule above is enqueue_ao's own: the terms are composite_route's, which it asks, keeping none of its own
-    rule, api = _body(_read("nt_api.cpp"), "CompositeRoute composite_route("), _body(_read("nt_api.cpp"), "int enqueue_ao(")
+    rule, api = sup.function_body(sup.source("nt_api.cpp"), "CompositeRoute composite_route("), sup.function_body(sup.source("nt_api.cpp"), "int enqueue_ao(")
     assert "r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;" in rule
     assert "r.faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);" in rule
     assert "const CompositeRoute rt = composite_route(s, sw);" in api and "all_opaque" not in api
@@ -92,9 +72,9 @@ def test_every_ao_launch_has_a_row_and_every_row_a_gpu_case():
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("),
                       ("nt_query.hpp", "int launch_query_fixed("), ("nt_var.hip", "int nt_launch_query("),
                       ("nt_hits.hpp", "int launch_hits_fixed("), ("nt_var.hip", "int nt_launch_hits(")):
-        assert not any(k.startswith("ao_") for k in _launches(_body(_read(src), head))), head
+        assert not any(k.startswith("ao_") for k in sup.launches(sup.function_body(sup.source(src), head))), head
     # and route on the switches read_switches already reads: no getenv of their own
-    assert "getenv" not in _read("nt_ao.hpp") and "getenv" not in _read("nt_inst_ao.hip")
+    assert "getenv" not in sup.source("nt_ao.hpp") and "getenv" not in sup.source("nt_inst_ao.hip")
 
 
 # ------------------------------------------------------------------ the conditions that keep the GPU tests from being vacuous
@@ -255,10 +235,6 @@ def test_the_setting_round_trips_and_a_refused_set_leaves_it_as_it_was():
     assert box.ambient_occlusion is None
 
 
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_buffer_forms_validate_before_they_touch_a_device():
     L = _lib.lib()
     sc, n = _scene()
@@ -310,7 +286,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     sc, n = _scene()
     sc.set_ambient_occlusion(8, 1.0)
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))

@@ -22,6 +22,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 
@@ -94,11 +95,6 @@ def test_cameras_show_every_kind_of_ray_by_ray_row(n):
     check_kinds(n)
 
 
-def _threads():
-    import bench
-    return max(1, min(64, bench.cpu_quota_cores() - 1))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", range(3, 9))
 def test_rows_sorted_on_their_sets_equal_the_oracle(n):
@@ -117,7 +113,7 @@ def test_rows_sorted_on_their_sets_equal_the_oracle(n):
         frames = []
         for _, o, a in cams:
             osc.set_camera(o, a)
-            frames.append(osc.render(W, H, chans, threads=_threads()))
+            frames.append(osc.render(W, H, chans, threads=sup.worker_threads()))
         ref_all = torch.from_numpy(np.stack(frames)).cuda()             # (K, H, W * bpp)
         fmt = ntracer_amd.ImageFormat(W, H, [ntracer_amd.Channel(*c) for c in chans])
         assert fmt.pitch == W * bpp

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import box_hit_cases as bc
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -70,7 +71,7 @@ def _both_forms(n, label_env=""):
 @pytest.mark.parametrize("n", bc.DIMS)
 def test_records_equal_the_oracle(n):
     with pytest.MonkeyPatch.context() as mp:
-        mp.delenv("NTRACER_FORCE_VAR", raising=False)
+        sup.set_switches(mp, ("NTRACER_FORCE_VAR",), {})
         _both_forms(n)
 
 
@@ -92,9 +93,7 @@ def test_three_frames_of_a_camera_table_with_a_padded_stride(n, env):
     cams = [bc.camera(n, k) for k in ks]
     table = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
     with pytest.MonkeyPatch.context() as mp:
-        mp.delenv("NTRACER_FORCE_VAR", raising=False)
-        for key, v in env.items():
-            mp.setenv(key, v)
+        sup.set_switches(mp, ("NTRACER_FORCE_VAR",), env)
         sc = scene(n, 3)                                # the scene's own camera sees nothing: the table's are what counts
         for w, h in ((37, 21), bc.BIG):
             stride = w * h + PAD
@@ -172,9 +171,7 @@ def test_an_abort_word_raised_before_the_launch_leaves_the_records_untouched(env
     import torch
     n, k, (w, h) = 6, 2, (37, 21)
     with pytest.MonkeyPatch.context() as mp:
-        mp.delenv("NTRACER_FORCE_VAR", raising=False)
-        for key, v in env.items():
-            mp.setenv(key, v)
+        sup.set_switches(mp, ("NTRACER_FORCE_VAR",), env)
         sc = scene(n, k)
         word = torch.ones(1, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()

@@ -12,14 +12,10 @@ import pytest
 import box_hit_cases as bc
 import ntracer_amd
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, build, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
-
-
-def _read(name):
-    return open(os.path.join(CSRC, name)).read()
 
 
 @pytest.mark.parametrize("n", bc.DIMS)
@@ -166,16 +162,16 @@ def test_the_unit_the_dispatch_and_the_header():
     # one unit a dimension, 3..24, with the guard of its siblings; no launcher named nt_<something>_fixed<N>
     units = [(name, flags) for name, src, flags in build.units() if src == "nt_inst_boxhits.hip"]
     assert sorted(int(f[0].split("=")[1]) for _, f in units) == list(range(3, 25))
-    src = _read("nt_inst_boxhits.hip")
+    src = sup.source("nt_inst_boxhits.hip")
     assert "#ifndef NT_INST_N\n#error" in src and "nt_box_faces<NT_INST_N>" in src and "_fixed" not in src
-    assert _read("nt_inst_box.hip") .count("nt_boxhits") == 0 and "nt_boxhits" not in _read("nt_box.hpp")
-    var = _read("nt_var.hip")
+    assert sup.source("nt_inst_box.hip") .count("nt_boxhits") == 0 and "nt_boxhits" not in sup.source("nt_box.hpp")
+    var = sup.source("nt_var.hip")
     body = var[var.index("int nt_launch_box_faces("):]
     body = body[:body.index("\n}\n")]
     assert "nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n" in body and "box_hits_var" in body and "box_lines_var" in body
     # no switch of its own, nothing of the shared pool's list
     for name in ("nt_boxhits.hpp", "nt_inst_boxhits.hip"):
-        assert "getenv" not in _read(name) and "asm" not in _read(name), name
+        assert "getenv" not in sup.source(name) and "asm" not in sup.source(name), name
     # the header carries the rule
     header = open(os.path.join(ROOT, "include", "ntracer_hip.h")).read()
     sec = header[header.index("BoxScene hit buffers and face lines"):]

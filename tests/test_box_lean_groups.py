@@ -30,6 +30,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 
@@ -234,11 +235,6 @@ def test_launches_land_on_the_three_kinds_of_block_shape(tmp_path):
     assert IL == (H + 63) // 64 * 1 == 4
 
 
-def _threads():
-    import bench
-    return max(1, min(64, bench.cpu_quota_cores() - 1))
-
-
 def _render(sc, fmt, fo, fa, frames, rows, opts):
     import torch
     fst = fmt._as_struct()
@@ -280,7 +276,7 @@ def test_rows_rendered_in_groups_equal_the_oracle(n):
         frames = []
         for _, o, a in cams:
             osc.set_camera(o, a)
-            frames.append(osc.render(w, h, chans, threads=_threads()))
+            frames.append(osc.render(w, h, chans, threads=sup.worker_threads()))
         return torch.from_numpy(np.stack(frames)).cuda()             # (K, h, w * 4)
 
     def sequence(frames):

@@ -18,6 +18,7 @@ import fixtures as fx
 import ntracer_amd
 import outline_cases as oc
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -34,9 +35,7 @@ route_id = lambda r: "n%d%s" % (r[0], "-force-var" if r[1] else "")
 
 
 def scene(n, k, mp, env=None):
-    mp.delenv("NTRACER_FORCE_VAR", raising=False)
-    for key, v in (env or {}).items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, ("NTRACER_FORCE_VAR",), env or {})
     sc = tracern.BoxScene(n)
     sc.set_fov(bc.FOV)
     sc._set_camera_arrays(*bc.camera(n, k))
@@ -48,19 +47,11 @@ def _set(sc, kinds=3, color=COLOR, strength=0.75):
     _lib.check(_lib.lib().nt_scene_set_box_lines(sc._handle, kinds, col, strength))
 
 
-def _opts(abort=None):
-    opts = _lib.NtRenderOpts()
-    opts.device = -1
-    if abort is not None:
-        opts.abort_device = abort.data_ptr()
-    return opts
-
-
 def _device_mask(sc, w, h, abort=None):
     """nt_box_line_mask_device on a sentinel-filled buffer with PAD bytes behind it: the raw buffer"""
     import torch
     buf = torch.full((w * h + PAD,), SENTINEL, dtype=torch.uint8, device="cuda")
-    opts = _opts(abort)
+    opts = sup.render_opts(abort)
     _lib.check(_lib.lib().nt_box_line_mask_device(sc._handle, w, h, C.c_void_p(buf.data_ptr()), C.byref(opts),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
@@ -70,7 +61,7 @@ def _device_mask(sc, w, h, abort=None):
 def _host_mask(sc, w, h):
     mask = np.full((h, w), 0xEE, np.uint8)
     marked = C.c_longlong(-1)
-    opts = _opts()
+    opts = sup.render_opts()
     _lib.check(_lib.lib().nt_box_line_mask(sc._handle, w, h, mask.ctypes.data, C.byref(marked), C.byref(opts)))
     return mask, int(marked.value)
 
@@ -125,33 +116,10 @@ def test_the_python_forms():
 
 
 # ------------------------------------------------------------------ renders: helpers
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene_, fmt, **kw):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene_, **kw)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
 def plain_colors(sc, w, h):
     """P: the library's plain fp32 x 3 frame of a scene whose setting is off, [h][w][3] float32, clamped by the packer"""
     assert sc.face_lines is None
-    return render_host(sc, fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
-
-
-def render_device(sc, fmt, opts=None, fill=0x3D):
-    import torch
-    size = fmt.pitch * fmt.height
-    buf = torch.full((size + 16,), fill, dtype=torch.uint8, device="cuda")
-    fst = fmt._as_struct()
-    status = _lib.lib().nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), None if opts is None else C.byref(opts),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[size:] == fill).all()
-    return status, got[:size].reshape(fmt.height, fmt.pitch)
+    return sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
 
 
 # ------------------------------------------------------------------ 2. renders
@@ -168,7 +136,7 @@ def test_renders_equal_the_plain_frame_blended_by_the_oracles_mask(route):
                 P = plain_colors(sc, w, h)
                 clamped = np.clip(e["colors"], np.float32(0), np.float32(1))
                 assert np.array_equal(P.view(np.uint32), clamped.view(np.uint32)), "the plain frame is not the expected colours"
-                plain = {name: render_host(sc, fmt_of(w, h, chans)) for name, chans in FORMATS}
+                plain = {name: sup.render_host(sc, sup.fmt_of(w, h, chans)) for name, chans in FORMATS}
                 label = "n%d %s %dx%d%s" % (n, bc.CAMERA_NAMES[k], w, h, " force-var" if env else "")
                 for strength in (0.0, 1.0, 0.5):
                     _set(sc, 3, COLOR, strength)
@@ -177,13 +145,13 @@ def test_renders_equal_the_plain_frame_blended_by_the_oracles_mask(route):
                         assert (want_rgb != P).any(axis=2).sum() >= 10, label          # the setting shows
                     for name, chans in FORMATS:
                         want = plain[name] if strength == 0.0 else sx.pack(want_rgb, chans)
-                        fmt = fmt_of(w, h, chans)
-                        img = render_host(sc, fmt)
+                        fmt = sup.fmt_of(w, h, chans)
+                        img = sup.render_host(sc, fmt)
                         assert np.array_equal(img, want), (label, name, strength, "BlockingRenderer", int((img != want).sum()))
-                        status, img = render_device(sc, fmt)
+                        status, img = sup.render_device(sc, fmt)
                         assert status == 0 and np.array_equal(img, want), (label, name, strength, "nt_render_device", int((img != want).sum()))
                 sc.set_face_lines(None)
-                assert np.array_equal(render_host(sc, fmt_of(w, h, fx.RGBX8)), plain["rgbx8"]), label + ": off again"
+                assert np.array_equal(sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8)), plain["rgbx8"]), label + ": off again"
 
 
 def test_each_kind_alone_and_other_formats():
@@ -200,9 +168,9 @@ def test_each_kind_alone_and_other_formats():
                 _set(sc, kinds, COLOR, 1.0)
                 want_rgb = oc.blend(P, mask & np.uint8(kinds), COLOR, 1.0)
                 for chans, rev in ((fx.RGBX8, False), (RGB24, False), (RGB24, True)):
-                    img = render_host(sc, fmt_of(w, h, chans, rev=rev))
+                    img = sup.render_host(sc, sup.fmt_of(w, h, chans, rev=rev))
                     assert np.array_equal(img, sx.pack(want_rgb, chans, rev)), (env, kinds, chans, rev)
-            fmt = fmt_of(w, h, RGB24, pitch=w * 3 + 5)
+            fmt = sup.fmt_of(w, h, RGB24, pitch=w * 3 + 5)
             buf = bytearray(b"\xb3" * (fmt.pitch * h))
             assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
             got = np.frombuffer(bytes(buf), np.uint8).reshape(h, fmt.pitch)
@@ -229,11 +197,11 @@ def test_three_frames_equal_three_single_renders(route):
             P = plain_colors(sc, w, h)
             _set(sc)
             for name, chans in FORMATS[:2]:
-                fmt = fmt_of(w, h, chans)
+                fmt = sup.fmt_of(w, h, chans)
                 singles = []
                 for o, a in cams:
                     sc._set_camera_arrays(o, a)
-                    singles.append(render_host(sc, fmt))
+                    singles.append(sup.render_host(sc, fmt))
                 singles = np.stack(singles)
                 assert np.array_equal(singles[0], sx.pack(oc.blend(P, bc.expected(n, ks[0], w, h)["mask"], COLOR, 0.75), chans))
                 assert not np.array_equal(singles[0], singles[1])
@@ -275,7 +243,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         table = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         w, h = 256, 160
         assert w * h * 16 <= (1 << 20) < 2 * w * h * 16
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         frame_bytes = fmt.pitch * h
         images = []
         for mib in (1024, 1):
@@ -288,7 +256,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         frames = images[0].reshape(nf, -1)
         assert len(np.unique(images[0])) > 16 and not np.array_equal(frames[0], frames[1])
         sc._set_camera_arrays(*cams[2])
-        assert np.array_equal(frames[2].reshape(h, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(frames[2].reshape(h, fmt.pitch), sup.render_host(sc, fmt))
         # the fused kernel draws the same frames
         mp.delenv("NTRACER_FORCE_VAR")
         buf = torch.zeros((nf * frame_bytes,), dtype=torch.uint8, device="cuda")
@@ -298,17 +266,17 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         # too big for the cap: refused before anything is launched, at run-time n alone
         w, h = 320, 240
         assert w * h * 16 > (1 << 20)
-        fmt = fmt_of(w, h, fx.RGBX8)
-        status, fused = render_device(sc, fmt, fill=0x4E)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        status, fused = sup.render_device(sc, fmt, fill=0x4E)
         assert status == 0 and len(np.unique(fused)) > 16
         mp.setenv("NTRACER_FORCE_VAR", "1")
-        status, img = render_device(sc, fmt, fill=0x4E)
+        status, img = sup.render_device(sc, fmt, fill=0x4E)
         assert status == _lib.NT_E_UNSUPPORTED and (img == 0x4E).all()
         assert _lib.last_error().startswith("face lines") and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error()
         with pytest.raises(NotImplementedError, match="face lines"):
             sc.face_line_mask(w, h)
         sc.set_supersampling_scratch_mb(1024)
-        status, img = render_device(sc, fmt, fill=0x4E)
+        status, img = sup.render_device(sc, fmt, fill=0x4E)
         assert status == 0 and np.array_equal(img, fused)
 
 
@@ -323,15 +291,15 @@ def test_an_abort_word_raised_before_the_launch_leaves_the_buffers_untouched(env
         torch.cuda.synchronize()
         raw = _device_mask(sc, w, h, abort=word)
         assert (raw == SENTINEL).all()
-        fmt = fmt_of(w, h, fx.RGBX8)
-        status, img = render_device(sc, fmt, opts=_opts(word), fill=0x6A)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        status, img = sup.render_device(sc, fmt, opts=sup.render_opts(word), fill=0x6A)
         assert status == 0 and (img == 0x6A).all()
         word.zero_()
         torch.cuda.synchronize()
         raw = _device_mask(sc, w, h, abort=word)
         _assert_mask(raw[:w * h].reshape(h, w), bc.expected(n, k, w, h)["mask"], "after the abort word went down")
-        status, img = render_device(sc, fmt, opts=_opts(word), fill=0x6A)
-        assert status == 0 and np.array_equal(img, render_host(sc, fmt))
+        status, img = sup.render_device(sc, fmt, opts=sup.render_opts(word), fill=0x6A)
+        assert status == 0 and np.array_equal(img, sup.render_host(sc, fmt))
 
 
 def test_a_warm_table_render_is_capturable():
@@ -343,7 +311,7 @@ def test_a_warm_table_render_is_capturable():
     with pytest.MonkeyPatch.context() as mp:
         sc = scene(n, 2, mp)
         _set(sc)
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         fst = fmt._as_struct()
         tab = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         st = torch.cuda.Stream()
@@ -367,7 +335,7 @@ def test_a_warm_table_render_is_capturable():
         assert torch.equal(fb, ref)
         del gr
         sc._set_camera_arrays(*cams[1])
-        assert np.array_equal(ref[1].cpu().numpy().reshape(h, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(ref[1].cpu().numpy().reshape(h, fmt.pitch), sup.render_host(sc, fmt))
 
 
 # ------------------------------------------------------------------ 5. refusals, and the calls that ignore the setting
@@ -376,7 +344,7 @@ def test_the_python_surface_refuses_what_the_setting_excludes():
     with pytest.MonkeyPatch.context() as mp:
         sc = scene(n, k, mp)
         sc.set_face_lines()
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         size = fmt.pitch * h
 
         def refused(**kw):
@@ -400,7 +368,7 @@ def test_the_python_surface_refuses_what_the_setting_excludes():
         refused(band_rank=0, band_world=2)
         refused(collect_stats=True)
         # and with nothing in the way it draws
-        assert len(np.unique(render_host(sc, fmt))) > 8
+        assert len(np.unique(sup.render_host(sc, fmt))) > 8
 
 
 def test_the_probes_the_rays_and_the_other_mask_ignore_the_setting():
@@ -408,8 +376,8 @@ def test_the_probes_the_rays_and_the_other_mask_ignore_the_setting():
     with pytest.MonkeyPatch.context() as mp:
         sc, plain = scene(n, k, mp), scene(n, k, mp)
         _set(sc)
-        fmt = fmt_of(w, h, fx.RGBX8)
-        assert not np.array_equal(render_host(sc, fmt), render_host(plain, fmt))
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        assert not np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt))
         rng = np.random.default_rng(5)
         xs, ys = rng.integers(0, w, 60), rng.integers(0, h, 60)
         assert np.array_equal(sc.colors_at(xs, ys, w, h).view(np.uint32), plain.colors_at(xs, ys, w, h).view(np.uint32))

@@ -11,23 +11,13 @@ import numpy as np
 import pytest
 
 import box_hit_cases as bc
-import fixtures as fx
 import ntracer_amd
 import outline_cases as oc
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
-
-
-def _read(name):
-    return open(os.path.join(CSRC, name)).read()
-
-
-def _body(src, head):
-    at = src.index(head)
-    return src[at:src.index("\n}\n", at)]
 
 
 @pytest.mark.parametrize("n", bc.DIMS)
@@ -193,10 +183,6 @@ def test_the_mask_forms_validate_before_they_touch_a_device():
         box.face_line_mask(8, 4, device="cuda")
 
 
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device():
     """nt_render, nt_render_device, nt_render_frames_device: NT_E_UNSUPPORTED with a message that starts "face lines", the
     destination as it was (the table form needs a device to make its table: test_box_lines_gpu.py)"""
@@ -205,7 +191,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     box = tracern.BoxScene(n)
     box.set_face_lines()
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))
@@ -258,7 +244,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     assert len(words) == 5 and all(m.startswith("face lines are not available") for m in words)
     # ... and every render entry point reaches them through render_checks, whose walk of the settings' table stands ahead of the
     # lens and the projection
-    checks = _body(_read("nt_api.cpp"), "int render_checks(")
+    checks = sup.function_body(sup.source("nt_api.cpp"), "int render_checks(")
     assert checks.index("kViewSettings") < checks.index("whole_view_check(") < checks.index("lens_check(") < checks.index("parallel_check(")
 
 
@@ -269,21 +255,21 @@ def test_without_a_gpu_the_mask_and_the_render_fail_loudly():
     with pytest.raises(RuntimeError, match="no HIP device"):
         box.face_line_mask(8, 4)
     with pytest.raises(RuntimeError, match="no HIP device"):
-        ntracer_amd.BlockingRenderer().render(bytearray(8 * 4 * 4), _fmt(8, 4), box)
+        ntracer_amd.BlockingRenderer().render(bytearray(8 * 4 * 4), sup.fmt_of(8, 4), box)
     assert not box.locked
 
 
 def test_nothing_new_in_the_plain_routes_and_no_switch_of_its_own():
     # the plain BoxScene launchers launch what they launched: the face kernels have a dispatch of their own
-    var = _read("nt_var.hip")
+    var = sup.source("nt_var.hip")
     for head in ("int nt_launch_box(", "int nt_launch_composite("):
-        body = _body(var, head)
+        body = sup.function_body(var, head)
         assert "box_hits" not in body and "box_lines" not in body and "nt_box_faces" not in body, head
-    assert "nt_boxhits" not in _read("nt_box.hpp") and "nt_boxhits" not in _read("nt_composite.hpp") and "nt_boxhits" not in _read("nt_inst_box.hip")
+    assert "nt_boxhits" not in sup.source("nt_box.hpp") and "nt_boxhits" not in sup.source("nt_composite.hpp") and "nt_boxhits" not in sup.source("nt_inst_box.hip")
     # the routes obey NTRACER_FORCE_VAR and nothing of their own: no getenv in the kernels' files, the reader as it was
     for name in ("nt_boxhits.hpp", "nt_inst_boxhits.hip", "nt_var.hip"):
-        assert "getenv" not in _read(name), name
-    api = _read("nt_api.cpp")
+        assert "getenv" not in sup.source(name), name
+    api = sup.source("nt_api.cpp")
     assert api.count("getenv(") == 12
-    enq = _body(api, "int enqueue_box_lines(")
+    enq = sup.function_body(api, "int enqueue_box_lines(")
     assert "sw.force_var" in enq and "ss_scratch_mb" in enq and "nt_launch_box_faces(" in enq

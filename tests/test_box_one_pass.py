@@ -37,6 +37,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 
@@ -221,11 +222,6 @@ def test_launches_land_on_the_one_wave_shape(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _threads():
-    import bench
-    return max(1, min(64, bench.cpu_quota_cores() - 1))
-
-
 _ORACLE = {}
 
 
@@ -238,7 +234,7 @@ def oracle_frames(n, cams_key, cams, h, chans_key, chans):
         frames = []
         for _, o, a in cams:
             osc.set_camera(o, a)
-            frames.append(osc.render(W, h, chans, threads=_threads()))
+            frames.append(osc.render(W, h, chans, threads=sup.worker_threads()))
         _ORACLE[key] = torch.from_numpy(np.stack(frames)).cuda()
     return _ORACLE[key]
 

@@ -14,8 +14,8 @@ import pytest
 import box_hit_cases as bc
 import box_shading_cases as cases
 import fixtures as fx
-import ntracer_amd
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -26,9 +26,7 @@ ENVS = ({}, {"NTRACER_FORCE_VAR": "1"})
 
 
 def scene(n, k, mp, env=None):
-    mp.delenv("NTRACER_FORCE_VAR", raising=False)
-    for key, v in (env or {}).items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, ("NTRACER_FORCE_VAR",), env or {})
     sc = tracern.BoxScene(n)
     sc.set_fov(bc.FOV)
     sc._set_camera_arrays(*bc.camera(n, k))
@@ -42,29 +40,6 @@ def apply(sc, n, name, w, h, which):
         sc.set_face_lines(None)
     else:
         sc.set_face_lines(**lines)
-
-
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene_, fmt, fill=0):
-    buf = bytearray(bytes([fill]) * (fmt.pitch * fmt.height))
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene_)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
-def render_device(sc, fmt, opts=None, fill=0x3D):
-    import torch
-    size = fmt.pitch * fmt.height
-    buf = torch.full((size + 16,), fill, dtype=torch.uint8, device="cuda")
-    fst = fmt._as_struct()
-    status = _lib.lib().nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), None if opts is None else C.byref(opts),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[size:] == fill).all()
-    return status, got[:size].reshape(fmt.height, fmt.pitch)
 
 
 def as_rgb(img, w, h):
@@ -93,28 +68,28 @@ def test_frames_equal_the_rule(route):
                     apply(sc, n, name, w, h, which)
                     want = cases.expected(n, name, w, h, which)["rgb"]
                     label = "n%d%s %s %dx%d setting %s" % (n, " force-var" if env else "", name, w, h, which)
-                    f = fmt_of(w, h, fx.RGBF32)
-                    got = as_rgb(render_host(sc, f), w, h)
+                    f = sup.fmt_of(w, h, fx.RGBF32)
+                    got = as_rgb(sup.render_host(sc, f), w, h)
                     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (label, "fp32 host", _differ(got, want))
-                    status, img = render_device(sc, f)
+                    status, img = sup.render_device(sc, f)
                     got = as_rgb(img, w, h)
                     assert status == 0 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), (label, "fp32 device", _differ(got, want))
-                    f = fmt_of(w, h, fx.RGBX8)
+                    f = sup.fmt_of(w, h, fx.RGBX8)
                     packed = sx.pack(want, fx.RGBX8)
-                    img = render_host(sc, f)
+                    img = sup.render_host(sc, f)
                     assert np.array_equal(img, packed), (label, "rgbx8 host", int((img != packed).sum()))
-                    status, img = render_device(sc, f)
+                    status, img = sup.render_device(sc, f)
                     assert status == 0 and np.array_equal(img, packed), (label, "rgbx8 device", int((img != packed).sum()))
                     if which == "d":
-                        f = fmt_of(w, h, RGB24, pitch=w * 3 + 5)
-                        img = render_host(sc, f, fill=0xb3)
+                        f = sup.fmt_of(w, h, RGB24, pitch=w * 3 + 5)
+                        img = sup.render_host(sc, f, fill=0xb3)
                         assert np.array_equal(img[:, :w * 3], sx.pack(want, RGB24)) and (img[:, w * 3:] == 0xb3).all(), (label, "rgb24, padded")
-                        status, img = render_device(sc, f, fill=0xb3)
+                        status, img = sup.render_device(sc, f, fill=0xb3)
                         assert status == 0 and np.array_equal(img[:, :w * 3], sx.pack(want, RGB24)) and (img[:, w * 3:] == 0xb3).all(), label
-                        f = fmt_of(w, h, RGB24, rev=True)
-                        img = render_host(sc, f)
+                        f = sup.fmt_of(w, h, RGB24, rev=True)
+                        img = sup.render_host(sc, f)
                         assert np.array_equal(img, sx.pack(want, RGB24, True)), (label, "rgb24, reversed")
-                        status, img = render_device(sc, f)
+                        status, img = sup.render_device(sc, f)
                         assert status == 0 and np.array_equal(img, sx.pack(want, RGB24, True)), (label, "rgb24, reversed, device")
                     shown += 1
     assert shown == len(cases.CAMERAS) * len(cases.SIZES) * len(cases.SETTINGS)
@@ -137,20 +112,20 @@ def test_neutral_settings_give_the_plain_frame_and_with_lines_the_face_line_fram
                     if lines:
                         sc.set_face_lines(**lines)
                     assert sc.face_shading is None
-                    fmts = [fmt_of(w, h, fx.RGBX8), fmt_of(w, h, fx.RGBF32)]
-                    plain = [render_host(sc, f) for f in fmts]
+                    fmts = [sup.fmt_of(w, h, fx.RGBX8), sup.fmt_of(w, h, fx.RGBF32)]
+                    plain = [sup.render_host(sc, f) for f in fmts]
                     for kw in neutral:
                         sc.set_face_shading(**kw)
                         assert sc.face_shading is not None
                         for f, want in zip(fmts, plain):
                             label = (cases.route_id(route), name, w, h, bool(lines), sorted(kw))
-                            assert np.array_equal(render_host(sc, f), want), label
-                            status, img = render_device(sc, f)
+                            assert np.array_equal(sup.render_host(sc, f), want), label
+                            status, img = sup.render_device(sc, f)
                             assert status == 0 and np.array_equal(img, want), label
                 if name != "nothing":
                     sc.set_face_shading(None)
                     sc.set_face_lines(None)
-                    assert not np.array_equal(render_host(sc, fmts[0]), plain[0])          # (the lines show: two different comparisons)
+                    assert not np.array_equal(sup.render_host(sc, fmts[0]), plain[0])          # (the lines show: two different comparisons)
 
 
 # ------------------------------------------------------------------ 3. frames
@@ -171,11 +146,11 @@ def test_three_cameras_in_one_call_equal_three_single_renders(route):
         for which in ("d", "e"):
             apply(sc, n, names[0], w, h, which)
             for chans in (fx.RGBX8, fx.RGBF32):
-                fmt = fmt_of(w, h, chans)
+                fmt = sup.fmt_of(w, h, chans)
                 singles = []
                 for o, a in cams:
                     sc._set_camera_arrays(o, a)
-                    singles.append(render_host(sc, fmt))
+                    singles.append(sup.render_host(sc, fmt))
                 singles = np.stack(singles)
                 assert np.array_equal(singles[0], sx.pack(cases.expected(n, names[0], w, h, which)["rgb"], chans))
                 for i in range(nf):
@@ -229,7 +204,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         table = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         w, h = 256, 160
         assert w * h * 16 <= (1 << 20) < 2 * w * h * 16
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         frame_bytes = fmt.pitch * h
         images = []
         for mib in (1024, 1):
@@ -242,7 +217,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         frames = images[0].reshape(nf, -1)
         assert len(np.unique(images[0])) > 16 and not np.array_equal(frames[0], frames[1])
         sc._set_camera_arrays(*cams[2])
-        assert np.array_equal(frames[2].reshape(h, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(frames[2].reshape(h, fmt.pitch), sup.render_host(sc, fmt))
         # the fused kernel draws the same frames
         mp.delenv("NTRACER_FORCE_VAR")
         buf = torch.zeros((nf * frame_bytes,), dtype=torch.uint8, device="cuda")
@@ -252,15 +227,15 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         # too big for the cap: refused before anything is launched, at run-time n alone
         w, h = 320, 240
         assert w * h * 16 > (1 << 20)
-        fmt = fmt_of(w, h, fx.RGBX8)
-        status, fused = render_device(sc, fmt, fill=0x4E)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        status, fused = sup.render_device(sc, fmt, fill=0x4E)
         assert status == 0 and len(np.unique(fused)) > 16
         mp.setenv("NTRACER_FORCE_VAR", "1")
-        status, img = render_device(sc, fmt, fill=0x4E)
+        status, img = sup.render_device(sc, fmt, fill=0x4E)
         assert status == _lib.NT_E_UNSUPPORTED and (img == 0x4E).all()
         assert _lib.last_error().startswith("face shading") and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error()
         sc.set_supersampling_scratch_mb(1024)
-        status, img = render_device(sc, fmt, fill=0x4E)
+        status, img = sup.render_device(sc, fmt, fill=0x4E)
         assert status == 0 and np.array_equal(img, fused)
 
 
@@ -277,12 +252,12 @@ def test_an_abort_word_raised_before_the_launch_leaves_the_destination_untouched
             opts = _lib.NtRenderOpts()
             opts.device = -1
             opts.abort_device = word.data_ptr()
-            fmt = fmt_of(w, h, fx.RGBX8)
-            status, img = render_device(sc, fmt, opts=opts, fill=0x6A)
+            fmt = sup.fmt_of(w, h, fx.RGBX8)
+            status, img = sup.render_device(sc, fmt, opts=opts, fill=0x6A)
             assert status == 0 and (img == 0x6A).all()
             word.zero_()
             torch.cuda.synchronize()
-            status, img = render_device(sc, fmt, opts=opts, fill=0x6A)
+            status, img = sup.render_device(sc, fmt, opts=opts, fill=0x6A)
             assert status == 0 and np.array_equal(img, sx.pack(cases.expected(n, name, w, h, which)["rgb"], fx.RGBX8))
 
 
@@ -296,7 +271,7 @@ def test_a_warm_table_render_is_capturable(lines):
     with pytest.MonkeyPatch.context() as mp:
         sc = scene(n, 2, mp)
         _table_setting(sc, n, lines)
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         fst = fmt._as_struct()
         tab = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         st = torch.cuda.Stream()
@@ -320,7 +295,7 @@ def test_a_warm_table_render_is_capturable(lines):
         assert torch.equal(fb, ref)
         del gr
         sc._set_camera_arrays(*cams[1])
-        assert np.array_equal(ref[1].cpu().numpy().reshape(h, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(ref[1].cpu().numpy().reshape(h, fmt.pitch), sup.render_host(sc, fmt))
         assert len(np.unique(ref[1].cpu().numpy())) > 16
 
 
@@ -332,8 +307,8 @@ def test_the_probes_the_rays_the_records_and_the_masks_ignore_the_setting():
         sc, plain = scene(n, k, mp), scene(n, k, mp)
         _table_setting(sc, n, True)
         plain.set_face_lines(cases.LINE_COLOR, cases.LINE_STRENGTH)
-        fmt = fmt_of(w, h, fx.RGBX8)
-        assert not np.array_equal(render_host(sc, fmt), render_host(plain, fmt))
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        assert not np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt))
         rng = np.random.default_rng(5)
         xs, ys = rng.integers(0, w, 60), rng.integers(0, h, 60)
         assert np.array_equal(sc.colors_at(xs, ys, w, h).view(np.uint32), plain.colors_at(xs, ys, w, h).view(np.uint32))

@@ -13,24 +13,15 @@ import pytest
 
 import box_hit_cases as bc
 import box_shading_cases as sc_
-import fixtures as fx
 import ntracer_amd
 import ray_query_cases as rq
 import view_setting_refusals as vr
+import support as sup
 from ntracer_amd import _lib, build, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 f32 = np.float32
-
-
-def _read(name):
-    return open(os.path.join(CSRC, name)).read()
-
-
-def _body(src, head):
-    at = src.index(head)
-    return src[at:src.index("\n}\n", at)]
 
 
 # ------------------------------------------------------------------ the surface
@@ -265,10 +256,6 @@ def test_the_rule_with_the_default_table_is_the_plain_colour(n):
 
 
 # ------------------------------------------------------------------ refusals
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device():
     """nt_render, nt_render_device, nt_render_frames_device: NT_E_UNSUPPORTED in "face shading is not available ..." words, the
     destination as it was; with face lines on as well, face lines' recorded words"""
@@ -277,7 +264,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     box = tracern.BoxScene(n)
     box.set_face_shading(sc_.table(n), far=3.0)
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))
@@ -328,14 +315,14 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
         ntracer_amd.BlockingRenderer().render(bytearray(size), fmt, box)
     assert not box.locked
     # the row is the table's last, has no words for the rows above it, and enqueue asks it ahead of the face lines' line
-    api = _read("nt_api.cpp")
+    api = sup.source("nt_api.cpp")
     table = api[api.index("const ViewSetting kViewSettings[VS_COUNT] = {"):]
     table = table[:table.index("\n};")]
     assert table.rstrip().splitlines()[-1].strip() == \
         '{[](const nt_scene *s) { return s->box_shading && !s->composite; }, "face shading is", "", nullptr, nullptr},'
-    enq = _body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
+    enq = sup.function_body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert enq.index("enqueue_box_shading(") < enq.index("enqueue_box_lines(") < enq.index("enqueue_lens(")
-    assert "for a row range" in _body(api, "int whole_view_check(")
+    assert "for a row range" in sup.function_body(api, "int whole_view_check(")
 
 
 @pytest.mark.skipif(_lib.lib().nt_device_count() > 0, reason="checks the no-GPU behaviour")
@@ -346,7 +333,7 @@ def test_without_a_gpu_the_render_fails_loudly():
         if lines:
             box.set_face_lines()
         with pytest.raises(RuntimeError, match="no HIP device"):
-            ntracer_amd.BlockingRenderer().render(bytearray(8 * 4 * 4), _fmt(8, 4), box)
+            ntracer_amd.BlockingRenderer().render(bytearray(8 * 4 * 4), sup.fmt_of(8, 4), box)
         assert not box.locked
 
 
@@ -356,29 +343,29 @@ def test_the_units_the_dispatch_and_no_switch_of_its_own():
     assert sorted(int(f[0].split("=")[1]) for _, f in units) == list(range(3, 25))
     assert len({name for name, _ in units}) == 22
     assert os.path.join(CSRC, "nt_boxshade.hpp") in [os.path.normpath(p) for p in build.HDR]
-    src = _read("nt_inst_boxshade.hip")
+    src = sup.source("nt_inst_boxshade.hip")
     assert "#ifndef NT_INST_N\n#error" in src and "nt_box_shade<NT_INST_N>" in src and "_fixed" not in src
     out = os.popen("nm -D -C --defined-only %s" % _lib.LIB_PATH).read()
     assert sorted(int(v) for v in re.findall(r"\bnt_box_shade<(\d+)>\(", out)) == list(range(3, 25))
-    hpp = _read("nt_boxshade.hpp")
+    hpp = sup.source("nt_boxshade.hpp")
     assert '#include "nt_boxhits.hpp"' in hpp
     for reused in ("box_face<N>(", "box_line_pair(", "box_line_record<N, false>(", "NT_BOXLINES_PITCH", "box_may_hit("):
         assert reused in hpp, reused
-    var = _read("nt_var.hip")
-    body = _body(var, "int nt_launch_box_shade(")
+    var = sup.source("nt_var.hip")
+    body = sup.function_body(var, "int nt_launch_box_shade(")
     assert "nt_dispatch_dim<3, NT_DEV_MAX_FIXED_BOX>(li.force_var ? 0 : li.n" in body and "box_hits_var" in body and "box_shaded_var" in body
     # the plain launchers launch what they launched
     for head in ("int nt_launch_box(", "int nt_launch_composite(", "int nt_launch_box_faces("):
-        b = _body(var, head)
+        b = sup.function_body(var, head)
         assert "box_shade" not in b and "nt_box_shade" not in b, head
     for name in ("nt_box.hpp", "nt_composite.hpp", "nt_inst_box.hip", "nt_boxhits.hpp", "nt_inst_boxhits.hip"):
-        assert "boxshade" not in _read(name) and "box_shade" not in _read(name), name
+        assert "boxshade" not in sup.source(name) and "box_shade" not in sup.source(name), name
     # the routes obey NTRACER_FORCE_VAR and nothing of their own
     for name in ("nt_boxshade.hpp", "nt_inst_boxshade.hip"):
-        assert "getenv" not in _read(name) and "asm" not in _read(name), name
-    api = _read("nt_api.cpp")
+        assert "getenv" not in sup.source(name) and "asm" not in sup.source(name), name
+    api = sup.source("nt_api.cpp")
     assert api.count("getenv(") == 12
-    enq = _body(api, "int enqueue_box_shading(")
+    enq = sup.function_body(api, "int enqueue_box_shading(")
     assert "sw.force_var" in enq and "ss_scratch_mb" in enq and "nt_launch_box_shade(" in enq and "getenv" not in enq
     # the cue's arguments are validated by the one function nt_scene_set_depth_cue asks
-    assert "cue_validate(" in _body(api, "int nt_scene_set_depth_cue(") and "cue_validate(" in _body(api, "int nt_scene_set_box_shading(")
+    assert "cue_validate(" in sup.function_body(api, "int nt_scene_set_depth_cue(") and "cue_validate(" in sup.function_body(api, "int nt_scene_set_box_shading(")

@@ -25,6 +25,7 @@ import pytest
 
 import fixtures as fx
 import oracle_binding as ob
+import support as sup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -246,15 +247,10 @@ def test_the_probe_is_clean_under_the_sanitizers(tmp_path):
     _check_against_numpy(cams, _run_probe(exe, cams, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")))
 
 
-def _threads():
-    import bench
-    return max(1, min(64, bench.cpu_quota_cores() - 1))
-
-
 def oracle_hits(n, o, a, w, h):
     """[h][w] bool: the oracle's pixel is a hit -- in fp32 channels a hit is (s, s/2, s/2) with s > 0, the background (i, i, i)
     or (0, -i, -i)"""
-    img = ob.OracleScene(n, o, a).render(w, h, fx.RGBF32, threads=_threads())
+    img = ob.OracleScene(n, o, a).render(w, h, fx.RGBF32, threads=sup.worker_threads())
     rgb = np.ascontiguousarray(img).view(">f4").reshape(h, w, 3).astype(F)         # (the image formats are big-endian unless reversed)
     return (rgb[:, :, 0] > 0) & (rgb[:, :, 1] == rgb[:, :, 0] * F(0.5))
 

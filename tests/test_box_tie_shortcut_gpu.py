@@ -30,6 +30,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 
@@ -99,7 +100,7 @@ def _oracle_frames(n, cams, h, chans):
     frames = []
     for _, o, a in cams:
         osc.set_camera(o, a)
-        frames.append(osc.render(W, h, chans, threads=top._threads()))
+        frames.append(osc.render(W, h, chans, threads=sup.worker_threads()))
     return torch.from_numpy(np.stack(frames)).cuda()
 
 

@@ -20,6 +20,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 from ntracer_amd.render import CameraTable
@@ -37,11 +38,6 @@ RUN_TIME_N = (25, 33, 63, 64)
 
 def cam_of(f):
     return (3 * f) % K
-
-
-def _threads():
-    import bench
-    return max(1, min(64, bench.cpu_quota_cores() - 1))
 
 
 def cameras(n):
@@ -79,7 +75,7 @@ def oracle_frames(n, cams, w, h, name, chans):
         frames = []
         for o, a in cams:
             osc.set_camera(o, a)
-            frames.append(osc.render(w, h, chans, threads=_threads()))
+            frames.append(osc.render(w, h, chans, threads=sup.worker_threads()))
         _oracle[key] = torch.from_numpy(np.stack(frames)).cuda()
     return _oracle[key]
 
@@ -93,7 +89,7 @@ def check_rgb16_frame(sc, n, cams, k):
     buf = bytearray(fmt.pitch * h)
     assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
     got = np.frombuffer(bytes(buf), np.uint8).reshape(h, fmt.pitch)
-    ref = ob.OracleScene(n, o, a).render(w, h, fx.RGB16, threads=_threads())
+    ref = ob.OracleScene(n, o, a).render(w, h, fx.RGB16, threads=sup.worker_threads())
     assert np.array_equal(got, ref), (n, "rgb16", k, int((got != ref).sum()))
 
 

@@ -16,10 +16,10 @@ import pytest
 
 import clip_cases as cc
 import fixtures as fx
-import ntracer_amd
 import primary_hit_cases as ph
 import ray_color_cases as rc
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -31,10 +31,7 @@ SWITCHES = ("NTRACER_STRICT_REFERENCE", "NTRACER_CLEAN_NORMALS", "NTRACER_FORCE_
 
 
 def _env(mp, env):
-    for key in SWITCHES:
-        mp.delenv(key, raising=False)
-    for key, v in env.items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, SWITCHES, env)
 
 
 def _golden(name, mp, k=0, variant="", env=None):
@@ -52,18 +49,8 @@ def _pairs(planes):
     return [(tuple(float(v) for v in a), float(b)) for a, b in zip(normals, offsets)]
 
 
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene, fmt):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
 def frame_f32(sc, w, h):
-    return render_host(sc, fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
+    return sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
 
 
 def _records(sc, w, h, normals=False):
@@ -126,7 +113,7 @@ def test_cuts_through_primitives_equal_the_brute_force(name):
                     clamped = np.clip(ref, 0.0, 1.0)
                     err = np.abs(img - clamped).max(axis=2)
                     assert (err[sure] <= TOL).all(), (label, float(err[sure].max()), int((err[sure] > TOL).sum()))
-                    bytes_ = render_host(sc, fmt_of(w, h, fx.RGBX8)).reshape(h, w, 4)
+                    bytes_ = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8)).reshape(h, w, 4)
                     wantb = sx.pack(clamped, fx.RGBX8, False).reshape(h, w, 4)
                     assert (np.abs(bytes_.astype(int) - wantb.astype(int))[sure] <= 1).all(), label
 
@@ -223,7 +210,7 @@ def test_a_camera_table_in_chunks_of_two_frames(t):
         sc, cams = _twin_scene(t, mp, {"NTRACER_CHUNK_FRAMES": "2"})
         order = (0, 1, 0)
         table = CameraTable(sc.dimension, np.asarray([cams[k][0] for k in order]), np.asarray([cams[k][1] for k in order]))
-        fmt = fmt_of(W, H, fx.RGBF32)
+        fmt = sup.fmt_of(W, H, fx.RGBF32)
         size = fmt.pitch * H
         buf = torch.full((3 * size + 16,), 0x3D, dtype=torch.uint8, device="cuda")
         fst = fmt._as_struct()
@@ -286,12 +273,12 @@ def test_planes_that_keep_the_whole_box_change_nothing(scene):
         else:
             sc = _golden(name, mp, variant=variant, env=env)
             keep = cc.keep_all(name)
-        for fmt in (fmt_of(W, H, fx.RGBF32), fmt_of(W, H, fx.RGBX8)):
+        for fmt in (sup.fmt_of(W, H, fx.RGBF32), sup.fmt_of(W, H, fx.RGBX8)):
             sc.set_clip_planes(None)
-            plain = render_host(sc, fmt)
+            plain = sup.render_host(sc, fmt)
             r0 = sc.primary_hits(W, H, normals=True)
             sc.set_clip_planes(_pairs(keep))
-            assert np.array_equal(render_host(sc, fmt), plain), (name, variant)
+            assert np.array_equal(sup.render_host(sc, fmt), plain), (name, variant)
             r1 = sc.primary_hits(W, H, normals=True)
             for key in ("dist", "item", "lane", "n_transparent", "normal_origin", "normal_dir"):
                 a, b = np.asarray(getattr(r0, key)), np.asarray(getattr(r1, key))

@@ -19,34 +19,15 @@ import numpy as np
 import pytest
 
 import clip_cases as cc
-import fixtures as fx
 import ntracer_amd
 import primary_hit_cases as ph
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 W, H = cc.W, cc.H
-
-
-def _read(name):
-    return open(os.path.join(CSRC, name)).read()
-
-
-def _body(src, head):
-    at = src.index(head)
-    depth, i = 0, src.index("{", at)
-    for j in range(i, len(src)):
-        depth += {"{": 1, "}": -1}.get(src[j], 0)
-        if depth == 0:
-            return src[at:j + 1]
-    raise AssertionError(head)
-
-
-def _launches(body):
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return sorted({re.sub(r"\s+", "", n) for n in names})
 
 
 # ------------------------------------------------------------------ the references
@@ -206,7 +187,7 @@ def test_the_exported_symbols_the_header_and_the_python_signatures():
     assert "int nt_scene_set_clip_planes(nt_scene_t *s, int count, const float *normals, const float *offsets);" in code
     assert "int nt_scene_get_clip_planes(const nt_scene_t *s, int *count, float *normals, float *offsets);" in code
     assert re.search(r"#define NT_CLIP_MAX 8\b", code) and _lib.NT_CLIP_MAX == 8 == cc.CLIP_MAX
-    assert re.search(r"#define NT_DEV_CLIP_MAX 8\b", _read("nt_device.hpp"))
+    assert re.search(r"#define NT_DEV_CLIP_MAX 8\b", sup.source("nt_device.hpp"))
     # the header carries the rule ...
     for phrase in ("t0 = 0, t1 = FLT_MAX, empty = false", "p = a_k0 * o_0, then p = p + a_kj * o_j", "s = p - b_k",
                    "r = a_k0 * d_0, then r = r + a_kj * d_j", "q = (-s) / r, and if q < t1 then t1 = q", "q = (-s) / r, and if q > t0 then t0 = q",
@@ -327,10 +308,6 @@ def test_the_setting_round_trips_and_a_refused_set_leaves_it_as_it_was():
     assert box.clip_planes == ()
 
 
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device():
     """nt_render, nt_render_device, nt_render_frames_device: NT_E_UNSUPPORTED with a message that starts "clip planes", the
     destination as it was (the table form needs a device to make its table).  There is no device here: a refusal that reached
@@ -340,7 +317,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     ok = ((1.0, 0.0, 0.0, 0.0), 1.0)
     sc.set_clip_planes([ok])
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))
@@ -416,8 +393,8 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     # render_checks asks the planes first -- of the planes and the cue the planes refuse --, and enqueue sends the scene to
     # enqueue_clip before any other setting's route
     assert vr.RENDER_REFUSALS["clip", "cue"] == "clip planes are not available while depth cues are on"
-    assert ("cue", "clip") not in vr.RENDER_REFUSALS and "kViewSettings" in _body(_read("nt_api.cpp"), "int render_checks(")
-    enq = _body(_read("nt_api.cpp"), "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
+    assert ("cue", "clip") not in vr.RENDER_REFUSALS and "kViewSettings" in sup.function_body(sup.source("nt_api.cpp"), "int render_checks(")
+    enq = sup.function_body(sup.source("nt_api.cpp"), "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert enq.index("enqueue_clip(") < enq.index("enqueue_cue(")
 
 
@@ -431,7 +408,7 @@ def test_what_does_not_honour_the_setting_is_refused_while_it_is_on():
     rays = _lib.NtRays()
     o, d = np.zeros((2, n), np.float32), np.ones((2, n), np.float32)
     rays.count, rays.origins, rays.directions = 2, o.ctypes.data, d.ctypes.data
-    fmt = _fmt(2, 1)
+    fmt = sup.fmt_of(2, 1)
     fst = fmt._as_struct()
     sc.set_supersampling(2)
     sc.set_adaptive_supersampling(0.1)
@@ -472,19 +449,19 @@ def test_what_does_not_honour_the_setting_is_refused_while_it_is_on():
 
 # ------------------------------------------------------------------ the kernels' source
 def test_the_clip_launches_are_kept_apart_from_the_existing_launchers():
-    comp, var = _read("nt_composite.hpp"), _read("nt_var.hip")
+    comp, var = sup.source("nt_composite.hpp"), sup.source("nt_var.hip")
     for src, head in ((comp, "int launch_composite_fixed("), (var, "int nt_launch_composite("), (var, "int nt_launch_hits("),
-                      (_read("nt_hits.hpp"), "int launch_hits_fixed("), (_read("nt_cue.hpp"), "int launch_cue_fixed(")):
-        body = _body(src, head)
+                      (sup.source("nt_hits.hpp"), "int launch_hits_fixed("), (sup.source("nt_cue.hpp"), "int launch_cue_fixed(")):
+        body = sup.function_body(src, head)
         assert "clip" not in body.lower().replace("nt_clipplanes{nullptr,0}", "").replace("ntclipplanes{nullptr, 0}", ""), head
-    fixed = _launches(_body(_read("nt_clip.hpp"), "int launch_clip_fixed("))
+    fixed = sorted(sup.launches(sup.function_body(sup.source("nt_clip.hpp"), "int launch_clip_fixed(")))
     assert fixed == sorted(["packet_numerators<N>", "composite_packet<N,32,false,true,true,false,true>", "composite_packet<N,32,false,false,true,false,true>",
                             "clip_shade<N,false,false>", "clip_shade<N,true,true>", "clip_shade<N,true,false>", "hits_normals<N,true>",
                             "hits_normals<N,false>"])
-    general = _launches(_body(var, "int clip_var_launch("))
+    general = sorted(sup.launches(sup.function_body(var, "int clip_var_launch(")))
     assert general == sorted(["composite_kernel_var", "composite_kernel_var_t<true>", "composite_kernel_var_t<false>", "hits_closest_var",
                               "hits_closest_var_t<true>", "hits_closest_var_t<false>"])
-    assert not _launches(_body(var, "int nt_launch_clip("))
+    assert not sup.launches(sup.function_body(var, "int nt_launch_clip("))
     # composite_packet's CLIP is a trailing parameter with a default, and the walks' a trailing type with one
     assert "template <int N, int DEPTH, bool FEAT, bool SCAL, bool HITS = false, bool LENS = false, bool CLIP = false>" in comp
     assert comp.count("typename CLIP = ClipOff>") == 3 and comp.count("typename WIN = ClipOff::Win>") == 2
@@ -493,6 +470,6 @@ def test_the_clip_launches_are_kept_apart_from_the_existing_launchers():
     units = [u for u in build.units() if u[1] == "nt_inst_clip.hip"]
     assert sorted(int(u[2][0].split("=")[1]) for u in units) == list(range(3, 11))
     assert os.path.join(CSRC, "nt_clip.hpp") in [os.path.normpath(p) for p in build.HDR]
-    assert '#ifndef NT_INST_N\n#error' in _read("nt_inst_clip.hip")
+    assert '#ifndef NT_INST_N\n#error' in sup.source("nt_inst_clip.hip")
     out = os.popen("nm -D -C --defined-only %s" % _lib.LIB_PATH).read()
     assert sorted(int(v) for v in re.findall(r"\bnt_clip_packet<(\d+)>\(", out)) == list(range(3, 11))

@@ -20,6 +20,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -38,7 +39,7 @@ MATERIALS = np.array([[0.9, 0.35, 0.2, 1, 1, 1, 1, 0, 0.6, 12],
 
 def _fmt(w=W, h=H, chans=fx.RGBF32, pad=PAD):
     bpp = sum(c[0] for c in chans) // 8
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], w * bpp + pad)
+    return sup.fmt_of(w, h, chans, w * bpp + pad)
 
 
 def _render(sc, **kw):
@@ -302,8 +303,7 @@ SWITCHES = sorted({k for _, ways in fx.COMPOSITE_ROUTES for _, _, env, _ in ways
 
 
 def _clear_switches(mp):
-    for k in SWITCHES:
-        mp.delenv(k, raising=False)
+    sup.set_switches(mp, SWITCHES, {})
 
 
 def run_way(n, scene_key, flat, kind, env, mode, cam, groups, failures, label):

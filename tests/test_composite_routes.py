@@ -7,42 +7,26 @@ import os
 import re
 
 import fixtures as fx
+import support as sup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
 
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    """the text of the function that starts with `head`, up to its closing brace in column 0"""
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """instantiations launched in `body`, spaces dropped: `hipLaunchKernelGGL((name<...>), ...` or `hipLaunchKernelGGL(name, ...`"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
-
-
 def _fixed():
-    return _body(_read("nt_composite.hpp"), "int launch_composite_fixed(")
+    return sup.function_body(sup.source("nt_composite.hpp"), "int launch_composite_fixed(")
 
 
 def _var():
-    return _body(_read("nt_var.hip"), "int nt_launch_composite(")
+    return sup.function_body(sup.source("nt_var.hip"), "int nt_launch_composite(")
 
 
 def _reader():
-    return _body(_read("nt_api.cpp"), "RenderSwitches read_switches(")
+    return sup.function_body(sup.source("nt_api.cpp"), "RenderSwitches read_switches(")
 
 
 def test_every_composite_launch_has_a_matrix_row():
-    launched = _launches(_fixed()) | _launches(_var())
+    launched = sup.launches(_fixed()) | sup.launches(_var())
     assert len(launched) >= 14, sorted(launched)            # the scan still finds the launches
     rows = [k for k, _ in fx.COMPOSITE_ROUTES]
     assert len(rows) == len(set(rows)), "duplicate rows"
@@ -78,7 +62,7 @@ def test_the_reader_reads_exactly_the_render_switches_and_nothing_else_calls_get
     reader = re.findall(r"\bgetenv\s*\(([^)]*)\)", _reader())
     assert sorted(reader) == sorted('"%s"' % k for k in RENDER_SWITCHES), reader
     for name in sorted(os.listdir(CSRC)):
-        calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", _read(name))
+        calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", sup.source(name))
         want = {"nt_api.cpp": reader, "nt_builder.cpp": ['"NTRACER_BUILD_THREADS"']}.get(name, [])
         assert calls == want, (name, calls)
 
@@ -87,10 +71,10 @@ def test_every_enqueue_takes_its_route_from_composite_route():
     """the host allocates the scratch the chosen kernel reads, so it must choose as the launchers do: the rule is written once, in
     composite_route, and the enqueues that size `checked` columns, frame stacks or the packet walk's scratch ask it and keep no
     terms of their own (enqueue_lens, enqueue_parallel and enqueue_ao: test_lens_host, test_parallel_host, test_ao_host)"""
-    api = _read("nt_api.cpp")
+    api = sup.source("nt_api.cpp")
     for head in ("int plan_composite(", "int hits_enqueue(", "int query_enqueue(", "int rays_scene("):
         start = api.rindex(head)                                      # (the definition: some are declared further up)
-        body = _body(api[start:], head)
+        body = sup.function_body(api[start:], head)
         assert body.count("\n") > 5 and "composite_route(" in body, head
         assert "all_opaque" not in body, head
 
@@ -100,7 +84,7 @@ def test_the_thresholds_the_deep_rows_are_built_around():
     # the packet kernel takes trees of stack_depth <= 32 only: its uniform stack has 32 entries and a 32-bit `bothbits`
     assert re.search(r"li\.kernel_choice == 0 && sc\.stack_depth <= 32\)", fixed)
     # (launched as composite_packet<N, 32, ...>: DEPTH = 32, pinned by the rows' names)
-    hpp = _read("nt_composite.hpp")
+    hpp = sup.source("nt_composite.hpp")
     assert re.search(r"if \(m_far != 0ull && sp < DEPTH\)", hpp)
     # the per-lane kernels' LDS: 256 lanes x (4 stack_depth + 8 N + 4 NT_MBOX) bytes, refused beyond 160 KiB
     assert re.search(r"lds = \(size_t\)4 \* 64 \* \(\(size_t\)sc\.stack_depth \* 4 \+ \(size_t\)N \* 8 \+ \(size_t\)NT_MBOX \* 4\);", fixed)

@@ -9,7 +9,6 @@ suite) blended by cue_cases.blend with the oracle-derived factors and packed by 
 
 Each test runs its GPU work once; nothing is retried."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ import ntracer_amd
 import primary_hit_cases as ph
 import ray_color_cases as rc
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -38,10 +38,7 @@ SETTINGS = [(False, False), (True, True), (False, True), (True, False)]
 
 def _scene(case, mp, k=0, variant=""):
     name, env = case
-    for key in cc.SWITCHES:
-        mp.delenv(key, raising=False)
-    for key, v in env.items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, cc.SWITCHES, env)
     n, flat, params = rc.case_scene((name, env, variant))
     sc = tracern.CompositeScene.from_flat(n, flat)
     sc.set_params_flat(params)
@@ -65,20 +62,11 @@ def _set(sc, st):
     _lib.check(_lib.lib().nt_scene_set_depth_cue(sc._handle, C.byref(cue), axis))
 
 
-def _opts(abort=None):
-    opts = _lib.NtRenderOpts()
-    opts.device = -1
-    opts.strict_reference = 1 if os.environ.get("NTRACER_STRICT_REFERENCE", "0") not in ("", "0") else 0
-    if abort is not None:
-        opts.abort_device = abort.data_ptr()
-    return opts
-
-
 def _device_factors(sc, w, h, abort=None):
     """nt_depth_cue_factors_device on a sentinel-filled buffer with PAD bytes behind it: the raw buffer"""
     import torch
     buf = torch.full((w * h * 8 + PAD,), SENTINEL, dtype=torch.uint8, device="cuda")
-    opts = _opts(abort)
+    opts = sup.render_opts(abort, strict_reference=sup.strict_reference())
     _lib.check(_lib.lib().nt_depth_cue_factors_device(sc._handle, w, h, C.c_void_p(buf.data_ptr()), C.byref(opts),
                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
@@ -87,7 +75,7 @@ def _device_factors(sc, w, h, abort=None):
 
 def _host_factors(sc, w, h):
     out = np.full((h, w, 2), 77, np.float32)
-    opts = _opts()
+    opts = sup.render_opts(strict_reference=sup.strict_reference())
     _lib.check(_lib.lib().nt_depth_cue_factors(sc._handle, w, h, out.ctypes.data, C.byref(opts)))
     return out
 
@@ -152,33 +140,10 @@ def test_the_python_forms():
 
 
 # ------------------------------------------------------------------ renders: helpers
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene, fmt, **kw):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene, **kw)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
 def plain_colors(sc, w, h):
     """P: the library's plain fp32 x 3 frame of a scene whose setting is off, [h][w][3] float32, clamped by the packer"""
     assert sc.depth_cue is None
-    return render_host(sc, fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
-
-
-def render_device(sc, fmt, opts=None, fill=0x3D):
-    import torch
-    size = fmt.pitch * fmt.height
-    buf = torch.full((size + 16,), fill, dtype=torch.uint8, device="cuda")
-    fst = fmt._as_struct()
-    status = _lib.lib().nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), None if opts is None else C.byref(opts),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[size:] == fill).all()
-    return status, got[:size].reshape(fmt.height, fmt.pitch)
+    return sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h, w, 3)
 
 
 def _want_rgb(name, P, k=0, **kw):
@@ -197,7 +162,7 @@ def test_the_routes_give_equal_factors_and_equal_bytes():
             sc = _scene(("cell120_n4", env), mp, k=1)
             _set(sc, st)
             factors.append(_host_factors(sc, w, h))
-            images.append([render_host(sc, fmt_of(w, h, chans, rev=rev)) for _, chans, rev in FORMATS])
+            images.append([sup.render_host(sc, sup.fmt_of(w, h, chans, rev=rev)) for _, chans, rev in FORMATS])
     _assert_factors(factors[1], factors[0], "NTRACER_FORCE_VAR=1 against the packet walk")
     _assert_factors(factors[2], factors[0], "NTRACER_COMPOSITE_KERNEL=2 against the packet walk")
     _assert_factors(factors[0], cc.expected(("cell120_n4", {}), w, h, 1, st), "cell120_n4 64x48")
@@ -220,18 +185,18 @@ def test_renders_equal_the_plain_frame_blended_by_the_oracles_factors(scene):
             _set(sc, cc.setting(name, background=background))
             for fname, chans, rev in FORMATS:
                 want = sx.pack(want_rgb, chans, rev)
-                fmt = fmt_of(W, H, chans, rev=rev)
-                img = render_host(sc, fmt)
+                fmt = sup.fmt_of(W, H, chans, rev=rev)
+                img = sup.render_host(sc, fmt)
                 assert np.array_equal(img, want), (name, fname, background, "BlockingRenderer", int((img != want).sum()))
-                status, img = render_device(sc, fmt)
+                status, img = sup.render_device(sc, fmt)
                 assert status == 0 and np.array_equal(img, want), (name, fname, background, "nt_render_device", int((img != want).sum()))
         # fog alone
         want_rgb = _want_rgb(name, P, tint=False)
         _set(sc, cc.setting(name, tint=False))
-        assert np.array_equal(render_host(sc, fmt_of(W, H, fx.RGBF32)), sx.pack(want_rgb, fx.RGBF32, False)), (name, "fog alone")
+        assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, fx.RGBF32)), sx.pack(want_rgb, fx.RGBF32, False)), (name, "fog alone")
         # a padded pitch keeps its padding
         bpp = 3
-        fmt = fmt_of(W, H, RGB24, pitch=W * bpp + 5)
+        fmt = sup.fmt_of(W, H, RGB24, pitch=W * bpp + 5)
         buf = bytearray(b"\xb3" * (fmt.pitch * H))
         assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc)
         got = np.frombuffer(bytes(buf), np.uint8).reshape(H, fmt.pitch)
@@ -244,20 +209,20 @@ def test_the_empty_setting_and_the_setting_taken_off_give_the_plain_bytes():
     for name in ("cell120_n4", "feature5_n5"):
         with pytest.MonkeyPatch.context() as mp:
             sc = _scene((name, {}), mp)
-            plain = {f[0]: render_host(sc, fmt_of(W, H, f[1], rev=f[2])) for f in FORMATS}
-            tiny = {f[0]: render_host(sc, fmt_of(1, 1, f[1], rev=f[2])) for f in FORMATS}
+            plain = {f[0]: sup.render_host(sc, sup.fmt_of(W, H, f[1], rev=f[2])) for f in FORMATS}
+            tiny = {f[0]: sup.render_host(sc, sup.fmt_of(1, 1, f[1], rev=f[2])) for f in FORMATS}
             _set(sc, cc.setting(name, tint=False, background=True, strength=0.0))
             for fname, chans, rev in FORMATS:
-                assert np.array_equal(render_host(sc, fmt_of(W, H, chans, rev=rev)), plain[fname]), (name, fname)
-                assert np.array_equal(render_host(sc, fmt_of(1, 1, chans, rev=rev)), tiny[fname]), (name, fname, "1 x 1")
+                assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, chans, rev=rev)), plain[fname]), (name, fname)
+                assert np.array_equal(sup.render_host(sc, sup.fmt_of(1, 1, chans, rev=rev)), tiny[fname]), (name, fname, "1 x 1")
             assert len(np.unique(plain["rgbx8"])) > 8
             _set(sc, cc.setting(name, background=True))
-            assert not np.array_equal(render_host(sc, fmt_of(W, H, fx.RGBX8)), plain["rgbx8"])
-            assert render_host(sc, fmt_of(1, 1, fx.RGBX8)).shape == (1, 4)
+            assert not np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, fx.RGBX8)), plain["rgbx8"])
+            assert sup.render_host(sc, sup.fmt_of(1, 1, fx.RGBX8)).shape == (1, 4)
             # and taking the setting off again is the plain render
             sc.set_depth_cue(None)
             for fname, chans, rev in FORMATS:
-                assert np.array_equal(render_host(sc, fmt_of(W, H, chans, rev=rev)), plain[fname]), (name, fname, "off")
+                assert np.array_equal(sup.render_host(sc, sup.fmt_of(W, H, chans, rev=rev)), plain[fname]), (name, fname, "off")
 
 
 # ------------------------------------------------------------------ 5. frames
@@ -276,11 +241,11 @@ def test_three_frames_equal_three_single_renders(scene):
         P = plain_colors(sc, W, H)
         _set(sc, cc.setting(name, background=True))
         for fname, chans, rev in (FORMATS[0], FORMATS[1]):
-            fmt = fmt_of(W, H, chans, rev=rev)
+            fmt = sup.fmt_of(W, H, chans, rev=rev)
             singles = []
             for o, a in cams:
                 sc._set_camera_arrays(o, a)
-                singles.append(render_host(sc, fmt))
+                singles.append(sup.render_host(sc, fmt))
             singles = np.stack(singles)
             assert np.array_equal(singles[0], sx.pack(_want_rgb(name, P, background=True), chans, rev))
             assert not np.array_equal(singles[0], singles[1])
@@ -328,7 +293,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes(name, per_pixel, size, too_big
         n = sc.dimension
         _set(sc, cc.setting(name, background=True))
         table = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
-        fmt = fmt_of(w, h, RGB24)
+        fmt = sup.fmt_of(w, h, RGB24)
         frame_bytes = fmt.pitch * h
         images = []
         for mib in (1024, 1):
@@ -341,7 +306,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes(name, per_pixel, size, too_big
         frames = images[0].reshape(nf, -1)
         assert len(np.unique(images[0])) > 16 and not np.array_equal(frames[0], frames[1])
         sc._set_camera_arrays(*cams[2])
-        assert np.array_equal(frames[2].reshape(h, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(frames[2].reshape(h, fmt.pitch), sup.render_host(sc, fmt))
 
 
 @pytest.mark.parametrize("name,per_pixel,size,too_big", CAPPED, ids=[c[0] for c in CAPPED])
@@ -352,8 +317,8 @@ def test_a_frame_that_does_not_fit_the_scratch_cap_is_refused_before_anything_is
         sc = _scene((name, {}), mp)
         _set(sc, cc.setting(name))
         sc.set_supersampling_scratch_mb(1)
-        fmt = fmt_of(w, h, fx.RGBX8)
-        status, img = render_device(sc, fmt, fill=0x4E)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        status, img = sup.render_device(sc, fmt, fill=0x4E)
         assert status == _lib.NT_E_UNSUPPORTED and (img == 0x4E).all()
         assert _lib.last_error().startswith("depth cue") and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error()
         with pytest.raises(NotImplementedError, match="depth cue"):
@@ -375,15 +340,15 @@ def test_an_abort_word_raised_before_the_launch_leaves_the_buffers_untouched(nam
         torch.cuda.synchronize()
         raw = _device_factors(sc, W, H, abort=word)
         assert (raw == SENTINEL).all()
-        fmt = fmt_of(W, H, fx.RGBX8)
-        status, img = render_device(sc, fmt, opts=_opts(word), fill=0x6A)
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        status, img = sup.render_device(sc, fmt, opts=sup.render_opts(word, strict_reference=sup.strict_reference()), fill=0x6A)
         assert status == 0 and (img == 0x6A).all()
         word.zero_()
         torch.cuda.synchronize()
         raw = _device_factors(sc, W, H, abort=word)
         _assert_factors(raw[:W * H * 8].view(np.float32).reshape(H, W, 2), cc.expected(case, W, H, 0, st), name + " after the abort word went down")
-        status, img = render_device(sc, fmt, opts=_opts(word), fill=0x6A)
-        assert status == 0 and np.array_equal(img, render_host(sc, fmt))
+        status, img = sup.render_device(sc, fmt, opts=sup.render_opts(word, strict_reference=sup.strict_reference()), fill=0x6A)
+        assert status == 0 and np.array_equal(img, sup.render_host(sc, fmt))
 
 
 @pytest.mark.parametrize("name", ["cell120_n4", "feature5_n5"])
@@ -399,8 +364,8 @@ def test_two_calls_in_a_row_agree_and_a_warm_table_render_is_capturable(name):
         _set(sc, cc.setting(name, background=True))
         a, b = _device_factors(sc, W, H), _device_factors(sc, W, H)
         assert np.array_equal(a, b)
-        fmt = fmt_of(W, H, fx.RGBX8)
-        assert np.array_equal(render_host(sc, fmt), render_host(sc, fmt))
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        assert np.array_equal(sup.render_host(sc, fmt), sup.render_host(sc, fmt))
         fst = fmt._as_struct()
         tab = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         st = torch.cuda.Stream()
@@ -424,7 +389,7 @@ def test_two_calls_in_a_row_agree_and_a_warm_table_render_is_capturable(name):
         assert torch.equal(fb, ref)
         del gr
         sc._set_camera_arrays(*cams[1])
-        assert np.array_equal(ref[1].cpu().numpy().reshape(H, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(ref[1].cpu().numpy().reshape(H, fmt.pitch), sup.render_host(sc, fmt))
 
 
 # ------------------------------------------------------------------ 9. refusals, and the calls that ignore the setting
@@ -432,7 +397,7 @@ def test_the_python_surface_refuses_what_the_setting_excludes():
     with pytest.MonkeyPatch.context() as mp:
         sc = _scene(("cell120_n4", {}), mp)
         _set(sc, cc.setting("cell120_n4"))
-        fmt = fmt_of(W, H, fx.RGBX8)
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
         size = fmt.pitch * H
 
         def refused(**kw):
@@ -462,15 +427,15 @@ def test_the_python_surface_refuses_what_the_setting_excludes():
         refused(band_rank=0, band_world=2)
         refused(collect_stats=True)
         # and with nothing in the way it draws
-        assert len(np.unique(render_host(sc, fmt))) > 8
+        assert len(np.unique(sup.render_host(sc, fmt))) > 8
 
 
 def test_the_probes_the_hits_and_the_masks_ignore_the_setting():
     with pytest.MonkeyPatch.context() as mp:
         sc, plain = _scene(("cell120_n4", {}), mp), _scene(("cell120_n4", {}), mp)
         _set(sc, cc.setting("cell120_n4", background=True))
-        fmt = fmt_of(W, H, fx.RGBX8)
-        assert not np.array_equal(render_host(sc, fmt), render_host(plain, fmt))
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        assert not np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt))
         rng = np.random.default_rng(5)
         xs, ys = rng.integers(0, W, 60), rng.integers(0, H, 60)
         assert np.array_equal(sc.colors_at(xs, ys, W, H).view(np.uint32), plain.colors_at(xs, ys, W, H).view(np.uint32))

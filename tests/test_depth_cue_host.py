@@ -18,10 +18,10 @@ import fixtures as fx
 import ntracer_amd
 import ray_color_cases as rc
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
 PLAIN = [("cell120_n4", {}), ("cell120_n4", {"NTRACER_STRICT_REFERENCE": "1"})]
 SCALAR = [("simplex10_n10", {})]
@@ -42,22 +42,6 @@ CUE_ROUTES = [
     ("cue_apply", [("feature5_n5", "")]),
 ]
 RENDER_ROWS = ("cue_shade<N,false,false>", "cue_shade<N,true,false>", "cue_shade<N,true,true>", "cue_apply")
-
-
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
 
 
 def _traits(n, flat, params, env):
@@ -91,12 +75,12 @@ def _render_route(name, variant):
 
 
 def test_every_cue_launch_has_a_row_and_every_row_a_gpu_case():
-    var = _read("nt_var.hip")
-    launched = _launches(_body(_read("nt_cue.hpp"), "int launch_cue_fixed("))
+    var = sup.source("nt_var.hip")
+    launched = sup.launches(sup.function_body(sup.source("nt_cue.hpp"), "int launch_cue_fixed("))
     assert len(launched) == 7
     for head in ("int nt_launch_cue(", "int nt_launch_cue_factors_fixed(", "static int nt_launch_cue_packet(", "int nt_launch_cue_factors(",
                  "int nt_launch_cue_apply("):
-        launched |= _launches(_body(var, head))
+        launched |= sup.launches(sup.function_body(var, head))
     rows = [k for k, _ in CUE_ROUTES]
     assert len(rows) == len(set(rows)) == 9
     assert set(rows) == launched, (sorted(launched - set(rows)), sorted(set(rows) - launched))
@@ -116,23 +100,23 @@ def test_every_cue_launch_has_a_row_and_every_row_a_gpu_case():
         assert _factor_routes(name, env) <= set(rows), (name, env)
     assert {_render_route(*r) for r in cc.RENDERED} == set(RENDER_ROWS)
     # the rule above is enqueue_cue's own: composite_route's answer, no term of its own, no getenv of its own
-    api = _read("nt_api.cpp")
-    rule, enq = _body(api, "CompositeRoute composite_route("), _body(api, "int enqueue_cue(")
+    api = sup.source("nt_api.cpp")
+    rule, enq = sup.function_body(api, "CompositeRoute composite_route("), sup.function_body(api, "int enqueue_cue(")
     assert "r.packet_walk = !r.faithful && !r.var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32;" in rule
     assert "const bool fast = composite_route(s, sw).packet_walk;" in enq and "all_opaque" not in enq and "getenv" not in enq
     for name in ("nt_cue.hpp", "nt_inst_cue.hip"):
-        assert "getenv" not in _read(name)
-    assert api.count("getenv(") == _body(api, "RenderSwitches read_switches(").count("getenv(")
+        assert "getenv" not in sup.source(name)
+    assert api.count("getenv(") == sup.function_body(api, "RenderSwitches read_switches(").count("getenv(")
     # the cue's dispatch and its check stand in front of every other setting's
-    body = _body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
+    body = sup.function_body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert 0 < body.index("return enqueue_cue(") < body.index("return enqueue_outlines(")
     # (render_checks walks the table of the settings, the cue above the outlines: of the two the cue refuses, as
     # tests/test_view_setting_refusals.py finds of the library)
     import view_setting_refusals as vr
     assert vr.RENDER_REFUSALS["cue", "outlines"] == "depth cues are not available while outlines are on"
-    assert ("outlines", "cue") not in vr.RENDER_REFUSALS and "kViewSettings" in _body(api, "int render_checks(")
+    assert ("outlines", "cue") not in vr.RENDER_REFUSALS and "kViewSettings" in sup.function_body(api, "int render_checks(")
     # the rule is written once, for both routes
-    hpp = _read("nt_cue.hpp")
+    hpp = sup.source("nt_cue.hpp")
     assert len(re.findall(r"void cue_pixel\(", hpp)) == 1 and len(re.findall(r"void cue_blend\(", hpp)) == 1
     assert "cue_pixel(" in var and "cue_blend(" in var and "inv_fog" not in var and "fog_strength" not in var
     # the new launches stay out of the launchers that were there
@@ -141,8 +125,8 @@ def test_every_cue_launch_has_a_row_and_every_row_a_gpu_case():
                       ("nt_lens.hpp", "int launch_lens_fixed("), ("nt_outline.hpp", "int launch_outline_fixed("),
                       ("nt_var.hip", "int nt_launch_outline_mark("), ("nt_var.hip", "int nt_launch_outline_apply("),
                       ("nt_ao.hpp", "int launch_ao_fixed("), ("nt_var.hip", "int nt_launch_ao(")):
-        assert not any(k.startswith("cue_") for k in _launches(_body(_read(src), head))), head
-    assert "cue" not in _read("nt_composite.hpp")                       # the headline kernel is untouched
+        assert not any(k.startswith("cue_") for k in sup.launches(sup.function_body(sup.source(src), head))), head
+    assert "cue" not in sup.source("nt_composite.hpp")                       # the headline kernel is untouched
 
 
 # ------------------------------------------------------------------ the conditions that keep the GPU tests from being vacuous
@@ -335,10 +319,6 @@ def test_the_setting_round_trips_and_a_refused_set_leaves_it_as_it_was():
     assert box.depth_cue is None
 
 
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_factor_forms_validate_before_they_touch_a_device():
     L = _lib.lib()
     sc, n = _scene()
@@ -390,7 +370,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     sc, n = _scene()
     sc.set_depth_cue(1.0, 2.0)
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))

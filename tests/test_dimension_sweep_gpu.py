@@ -7,8 +7,9 @@ import pytest
 
 import dimension_sweep_cases as dc
 import fixtures as fx
+import support as sup
 from ntracer_amd import tracern
-from test_adaptive_gpu import box_scene, fmt_of, render_host
+from test_adaptive_gpu import box_scene
 from test_primary_hits_gpu import _check as check_hits
 from test_ray_colors_gpu import TOL as TOL_COLOURS
 from test_ray_queries_gpu import QUERY_SWITCHES, _check_intersect, _check_occludes
@@ -28,7 +29,7 @@ def test_box_rays_and_refine_at_every_fixed_dimension(n):
     e = dc.box_refine(n)
     sc = box_scene(n, dc.BOX_CAMERA, 2, e.t)
     for chans in (fx.RGBF32, fx.RGBX8):
-        img = render_host(sc, fmt_of(w, h, chans))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans))
         want = e.image(chans)
         assert np.array_equal(img, want), (n, int((img != want).sum()))
     assert np.array_equal(sc.refinement_mask(w, h), e.mask), n
@@ -37,8 +38,7 @@ def test_box_rays_and_refine_at_every_fixed_dimension(n):
 @pytest.mark.parametrize("n", range(3, 11))
 def test_composite_rays_queries_and_hits_at_every_fixed_dimension(n, monkeypatch):
     c = dc.composite(n)
-    for k in QUERY_SWITCHES + ("NTRACER_COMPOSITE_KERNEL",):         # the default routes: the fixed-n launchers
-        monkeypatch.delenv(k, raising=False)
+    sup.set_switches(monkeypatch, QUERY_SWITCHES + ("NTRACER_COMPOSITE_KERNEL",), {})         # the default routes: the fixed-n launchers
     sc = tracern.CompositeScene.from_flat(n, c.flat)
     sc.set_params_flat(c.params)
     sc.set_fov(c.fov)

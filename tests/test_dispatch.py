@@ -14,13 +14,6 @@ from ntracer_amd import _lib, build
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
-# the families each instantiation unit defines; the CompositeScene ones stop at NT_DEV_MAX_FIXED where a unit is compiled beyond it
-FAMILIES = {"nt_inst_box.hip": ("box",), "nt_inst_composite.hip": ("composite",), "nt_inst_query.hip": ("query",),
-            "nt_inst_hits.hip": ("hits",), "nt_inst_rays.hip": ("rays_box", "rays"), "nt_inst_adaptive.hip": ("refine_box", "refine"),
-            "nt_inst_lens.hip": ("lens",), "nt_inst_parallel.hip": ("parallel",), "nt_inst_ao.hip": ("ao",),
-            "nt_inst_outline.hip": ("outline",)}
-BOX_FAMILIES = ("box", "rays_box", "refine_box")
-
 
 def _bound(name):
     src = open(os.path.join(CSRC, "nt_device.hpp")).read()
@@ -47,37 +40,52 @@ def test_the_helper_calls_the_callee_of_n_once_and_nothing_out_of_range(tmp_path
 
 
 def _symbols(*flags):
+    """((launcher template, N) of every launcher of build.FAMILIES in the listing, the listing)"""
     out = subprocess.check_output(["nm", "-D", "-C"] + list(flags) + [_lib.LIB_PATH]).decode()
-    return re.findall(r"\bnt_(\w+)_fixed<(\d+)>\(", out), out
+    names = "|".join(re.escape(name) for name in build.launcher_dims())
+    return [(name, int(n)) for name, n in re.findall(r"\b(%s)<(\d+)>\(" % names, out)], out
 
 
 def test_no_launcher_of_a_dimension_is_left_undefined():
     """a shared library links with an explicit specialisation missing and fails when that dimension is first called: this
     stands in for the link error"""
-    _, out = _symbols("--undefined-only")
-    bad = [line for line in out.splitlines() if "_fixed<" in line]
+    bad, out = _symbols("--undefined-only")
     assert not bad, bad
     assert "hipLaunchKernel" in out                      # (the listing is the library's)
 
 
 def test_every_family_exports_the_dimensions_the_build_compiles():
-    want = {}
-    for _, src, flags in build.units():
-        for fam in FAMILIES.get(src, ()):
-            (n,) = [int(f.split("=")[1]) for f in flags if f.startswith("-DNT_INST_N=")]
-            if fam in BOX_FAMILIES or n <= _bound("NT_DEV_MAX_FIXED"):
-                want.setdefault(fam, []).append(n)
-    assert set(want) == {f for fams in FAMILIES.values() for f in fams}
-    # what the build compiles is what the dispatch can call: 3 .. the bound of the family, each once
-    for fam, dims in want.items():
-        hi = _bound("NT_DEV_MAX_FIXED_BOX" if fam in BOX_FAMILIES else "NT_DEV_MAX_FIXED")
-        assert sorted(dims) == list(range(3, hi + 1)), (fam, sorted(dims))
+    sources = {src: box for src, _, box in build.FAMILIES}
+    assert len(sources) == len(build.FAMILIES)
+    his = {False: _bound("NT_DEV_MAX_FIXED"), True: _bound("NT_DEV_MAX_FIXED_BOX")}
+    # what the build compiles is what the dispatch can call: a unit for 3 .. the bound of its family, each once, and no
+    # unit of a dimension that the table does not explain
+    compiled = {}
+    for name, src, flags in build.units():
+        ns = [int(f.split("=")[1]) for f in flags if f.startswith("-DNT_INST_N=")]
+        if ns and ns[0] > 0:
+            assert src in sources and len(ns) == 1, (name, src, flags)
+            compiled.setdefault(src, []).append(ns[0])
+    assert set(compiled) == set(sources)
+    for src, dims in compiled.items():
+        assert sorted(dims) == list(range(3, his[sources[src]] + 1)), (src, sorted(dims))
+    # every launcher is defined for 3 .. one of the two bounds, and some launcher of a unit for every dimension the unit is compiled for
+    # (CompositeScene's stop at NT_DEV_MAX_FIXED where they share a unit with BoxScene's)
+    want = build.launcher_dims()
+    assert sorted(want) == sorted(name for _, names, _ in build.FAMILIES for name in names)
+    # (the table names every launcher template the dispatch header declares)
+    declared = re.findall(r"^template <int N> int (nt_\w+)\(", open(os.path.join(CSRC, "nt_dispatch.hpp")).read(), re.M)
+    assert sorted(declared) == sorted(want) and len(declared) == len(set(declared))
+    for src, names, box in build.FAMILIES:
+        for name in names:
+            assert list(want[name]) == list(range(3, want[name][-1] + 1)) and want[name][-1] in his.values(), (name, want[name])
+        assert max(want[name][-1] for name in names) == his[box], src
     got = {}
-    for fam, n in _symbols("--defined-only")[0]:
-        got.setdefault(fam, []).append(int(n))
+    for name, n in _symbols("--defined-only")[0]:
+        got.setdefault(name, []).append(n)
     assert {f: sorted(d) for f, d in got.items()} == {f: sorted(d) for f, d in want.items()}
     # and every unit is a source that exists, with the one guard against a build without the dimension
-    for src in FAMILIES:
+    for src in sources:
         assert '#ifndef NT_INST_N\n#error' in open(os.path.join(CSRC, src)).read(), src
 
 

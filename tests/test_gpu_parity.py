@@ -19,6 +19,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 
@@ -26,16 +27,6 @@ pytestmark = pytest.mark.gpu
 
 TOL_ORACLE = 1e-5
 TOL_REF = 1e-4
-
-
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene, fmt, **kw):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene, **kw)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
 
 
 def test_extension_is_loaded_and_sees_the_gpu():
@@ -67,7 +58,7 @@ def test_config1_box3_256_bytes_equal_reference_image():
     g = fx.load("box_cfg1_n3_256")
     sc = tracern.BoxScene(3)
     sc._set_camera_arrays(g["origin"], g["axes"])
-    img = render_host(sc, fmt_of(256, 256, fx.RGBX8))
+    img = sup.render_host(sc, sup.fmt_of(256, 256, fx.RGBX8))
     assert np.array_equal(img, g["image_rgbx8"])
     c = sc.calculate_color(128, 128, 256, 256)
     o = ob.OracleScene(3, g["origin"], g["axes"]).colors_at([128], [128], 256, 256)[0]
@@ -80,7 +71,7 @@ def test_box_full_frame_bytes_equal_oracle(n, w, h):
     sc = tracern.BoxScene(n)
     for f in (0, 93):
         sc._set_camera_arrays(g["origins"][f], g["axes"][f])
-        img = render_host(sc, fmt_of(w, h, fx.RGBX8))
+        img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8))
         ref = ob.OracleScene(n, g["origins"][f], g["axes"][f]).render(w, h, fx.RGBX8, threads=7)
         assert np.array_equal(img, ref)
 
@@ -102,7 +93,7 @@ def test_box_stress_cameras_bytes_and_floats_equal_oracle(n):
         sc._set_camera_arrays(origin, axes)
         osc = ob.OracleScene(n, origin, axes)
         chans = formats[k % len(formats)] if k % 3 else fx.RGBX8
-        img = render_host(sc, fmt_of(w, h, chans))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans))
         ref = osc.render(w, h, chans, threads=7)
         assert np.array_equal(img, ref), (n, k, int((img != ref).sum()))
         if k % 5 == 0:
@@ -128,7 +119,7 @@ def test_box_byte_orders_of_packed_rgb(rev):
     for k, chans in enumerate(layouts):
         f = 20 * k + 3
         sc._set_camera_arrays(g["origins"][f], g["axes"][f])
-        img = render_host(sc, fmt_of(w, h, chans, 0, rev))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans, 0, rev))
         ref = ob.OracleScene(6, g["origins"][f], g["axes"][f]).render(w, h, chans, reversed_=rev, threads=7)
         assert np.array_equal(img, ref), (k, rev, int((img != ref).sum()))
 
@@ -141,7 +132,7 @@ def test_run_time_n_rows_kernel_on_the_bench_frames(monkeypatch):
     import torch
     g = fx.load("box_n6_1920x1080")
     w, h = 1920, 1080
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     frames = [0, 17, 40, 77, 93, 120, 141, 159]
     o = np.ascontiguousarray(g["origins"][frames], np.float32)
     a = np.ascontiguousarray(g["axes"][frames], np.float32)
@@ -175,10 +166,10 @@ def test_box_wide_rows_and_the_kernel_without_stretch_codes(monkeypatch):
         sc = tracern.BoxScene(n)
         sc._set_camera_arrays(origin, axes)
         ref = ob.OracleScene(n, origin, axes).render(w, h, fx.RGBX8, threads=7)
-        img = render_host(sc, fmt_of(w, h, fx.RGBX8))
+        img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8))
         assert np.array_equal(img, ref), (n, w, h, int((img != ref).sum()))
         monkeypatch.setenv("NTRACER_BOX_CULL", "0")
-        img0 = render_host(sc, fmt_of(w, h, fx.RGBX8))
+        img0 = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8))
         monkeypatch.delenv("NTRACER_BOX_CULL")
         assert np.array_equal(img0, ref), (n, w, h)
 
@@ -193,10 +184,10 @@ def test_box10_4096_both_kernels_properties_and_samples(monkeypatch):
     w = h = 4096
     sc = tracern.BoxScene(10)
     sc._set_camera_arrays(g["origins"][40], g["axes"][40])
-    fmt = fmt_of(w, h, fx.RGBX8)
-    img = render_host(sc, fmt)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
+    img = sup.render_host(sc, fmt)
     monkeypatch.setenv("NTRACER_FORCE_VAR", "1")
-    assert np.array_equal(render_host(sc, fmt), img)
+    assert np.array_equal(sup.render_host(sc, fmt), img)
     monkeypatch.delenv("NTRACER_FORCE_VAR")
     osc = ob.OracleScene(10, g["origins"][40], g["axes"][40])
     for y in (0, 1777, 2048, 4095):
@@ -231,7 +222,7 @@ def test_pixel_packing_all_formats_bit_exact_vs_reference():
         pitch, rev, bpp = [int(v) for v in g["fmt_%s_meta" % name]]
         chans = ob.channels_from_table(g["fmt_%s_channels" % name])
         buf = bytearray(b"\xAB" * (pitch * h))
-        assert ntracer_amd.BlockingRenderer().render(buf, fmt_of(w, h, chans, pitch, bool(rev)), sc)
+        assert ntracer_amd.BlockingRenderer().render(buf, sup.fmt_of(w, h, chans, pitch, bool(rev)), sc)
         got = np.frombuffer(bytes(buf), np.uint8).reshape(h, pitch)
         assert np.array_equal(got[:, :w * bpp], g["fmt_%s_image" % name][:, :w * bpp]), str(name)
         assert (got[:, w * bpp:] == 0xAB).all(), "pitch padding must not be touched: %s" % name
@@ -270,7 +261,7 @@ def test_random_channel_layouts_match_oracle_bytes():
         rev = bool(rnd.rand() < 0.5)
         live = sum(1 for c in chans if any(c[1:5]) or (len(c) > 5 and c[5]))
         seen_modes.add("w32" if bits <= 32 and live <= 4 else "w64" if bits <= 64 and live <= 4 else "gen")
-        img = render_host(sc, fmt_of(w, h, chans, pitch, rev))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans, pitch, rev))
         ref = osc.render(w, h, chans, pitch, rev)
         assert np.array_equal(img[:, :w * bpp], ref[:, :w * bpp]), (trial, chans, rev)
     assert seen_modes == {"w32", "w64", "gen"}
@@ -283,7 +274,7 @@ def test_ragged_and_tiny_images():
     osc = ob.OracleScene(6, g["origins"][17], g["axes"][17])
     for (w, h) in [(1, 1), (1, 7), (63, 5), (65, 3), (257, 33), (31, 129)]:
         for chans in (fx.RGBX8, fx.RGB16, fx.RGBF32):
-            img = render_host(sc, fmt_of(w, h, chans))
+            img = sup.render_host(sc, sup.fmt_of(w, h, chans))
             assert np.array_equal(img, osc.render(w, h, chans)), (w, h)
 
 
@@ -298,16 +289,16 @@ def test_row_tables_of_many_launch_geometries():
     sizes = [(200, 40 + 3 * k) for k in range(12)] + [(200, 40), (200, 43)]
     for (w, h) in sizes:
         for pitch in (0, 4 * w + 64):
-            img = render_host(sc, fmt_of(w, h, fx.RGBX8, pitch))
+            img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8, pitch))
             ref = osc.render(w, h, fx.RGBX8)
             assert np.array_equal(img[:, :4 * w], ref), (w, h, pitch)
     sc.set_fov(1.1)
     osc2 = ob.OracleScene(6, g["origins"][23], g["axes"][23], 1.1)
-    assert np.array_equal(render_host(sc, fmt_of(200, 40, fx.RGBX8)), osc2.render(200, 40, fx.RGBX8))
+    assert np.array_equal(sup.render_host(sc, sup.fmt_of(200, 40, fx.RGBX8)), osc2.render(200, 40, fx.RGBX8))
     # rows dealt in bands, into a full-size frame (rows of a wave are not `pitch` apart) and into a compact one
     import torch
     w, h = 320, 200
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     full = osc2.render(w, h, fx.RGBX8)
     fst = fmt._as_struct()
     o1 = np.ascontiguousarray(g["origins"][23:24], np.float32)
@@ -341,10 +332,10 @@ def test_simplex10_fixed_and_run_time_n_kernels_agree(monkeypatch):
     sc = tracern.CompositeScene.from_flat(10, fx.flat_of(g))
     f = g["frames"][2]
     sc._set_camera_arrays(g["origins"][f], g["axes"][f])
-    fmt = fmt_of(320, 200, fx.RGBF32)
-    a = render_host(sc, fmt)
+    fmt = sup.fmt_of(320, 200, fx.RGBF32)
+    a = sup.render_host(sc, fmt)
     monkeypatch.setenv("NTRACER_FORCE_VAR", "1")
-    b = render_host(sc, fmt)
+    b = sup.render_host(sc, fmt)
     assert np.abs(a.view(">f4") - b.view(">f4")).max() < 1e-6
     assert a.view(">f4").max() > 0.2
 
@@ -370,8 +361,8 @@ def test_lit_reflective_scene_in_ten_dimensions_vs_oracle(monkeypatch, force_var
     sc.set_params_flat(params)
     f = g["frames"][1]
     sc._set_camera_arrays(g["origins"][f], g["axes"][f])
-    fmt = fmt_of(160, 100, fx.RGBF32)
-    img = render_host(sc, fmt)
+    fmt = sup.fmt_of(160, 100, fx.RGBF32)
+    img = sup.render_host(sc, fmt)
     ref = ob.OracleScene(n, g["origins"][f], g["axes"][f], flat=flat, params=params, clean_normals=True).render(160, 100, fx.RGBF32, threads=7)
     d = np.abs(img.view(">f4") - ref.view(">f4"))
     assert d.max() < 1e-4, float(d.max())
@@ -404,7 +395,7 @@ def test_twelve_dimensional_lit_scene_vs_reference_and_oracle(monkeypatch):
         assert bad <= 0.002 * total, (bad, clean)
         # image path
         sc._set_camera_arrays(g["origins"][7], g["axes"][7])
-        img = render_host(sc, fmt_of(160, 100, fx.RGBF32))
+        img = sup.render_host(sc, sup.fmt_of(160, 100, fx.RGBF32))
         ref = ob.OracleScene(12, g["origins"][7], g["axes"][7], flat=flat, params=p, clean_normals=clean).render(160, 100, fx.RGBF32, threads=7)
         assert np.abs(img.view(">f4") - ref.view(">f4")).max() < TOL_ORACLE, clean
 
@@ -471,11 +462,11 @@ def test_run_time_n_transparency_kernel_vs_oracle_and_the_fixed_kernel(monkeypat
     assert np.abs(c5 - fixed5).max() <= 1e-6
     assert np.abs(c5 - g5["colors"][1]).max() < TOL_REF
     # image renders: one frame through nt_render, three through one device launch
-    img = render_host(sc, fmt_of(w, h, fx.RGB16), strict_reference=True)
+    img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGB16), strict_reference=True)
     ref = ob.OracleScene(3, g["origin"], g["axes"], flat=flat, params=p).render(w, h, fx.RGB16, threads=3)
     assert np.abs(img.astype(int) - ref.astype(int)).max() <= 1
     import torch
-    fmt = fmt_of(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     fb = torch.zeros((3, fmt.pitch * h), dtype=torch.uint8, device="cuda")
     o3 = np.ascontiguousarray(np.stack([g["origin"]] * 3), np.float32)
     a3 = np.ascontiguousarray(np.stack([g["axes"]] * 3), np.float32)
@@ -514,7 +505,7 @@ def test_eleven_dimensional_feature_scene_vs_reference(monkeypatch):
                 assert np.abs(c - g["colors"][k]).max() < TOL_REF, int(f)
     monkeypatch.delenv("NTRACER_CLEAN_NORMALS")
     sc._set_camera_arrays(g["origins"][9], g["axes"][9])
-    img = render_host(sc, fmt_of(160, 100, fx.RGBF32))
+    img = sup.render_host(sc, sup.fmt_of(160, 100, fx.RGBF32))
     ref = ob.OracleScene(11, g["origins"][9], g["axes"][9], flat=flat, params=p).render(160, 100, fx.RGBF32, threads=7)
     assert np.abs(img.view(">f4") - ref.view(">f4")).max() < TOL_ORACLE
 
@@ -534,7 +525,7 @@ def test_sixteen_dimensional_feature_scene_vs_reference():
         assert np.abs(c - o).max() < TOL_ORACLE, int(f)
         assert np.abs(c - g["colors"][k]).max() < TOL_REF, int(f)
     f = int(g["frames"][1])
-    img = render_host(sc, fmt_of(160, 100, fx.RGBF32))
+    img = sup.render_host(sc, sup.fmt_of(160, 100, fx.RGBF32))
     ref = ob.OracleScene(16, g["origins"][f], g["axes"][f], flat=flat, params=p).render(160, 100, fx.RGBF32, threads=7)
     assert np.abs(img.view(">f4") - ref.view(">f4")).max() < TOL_ORACLE
 
@@ -578,7 +569,7 @@ def test_reflection_among_transparent_things_to_any_depth():
     sc._set_camera_arrays(origin, axes)
     c = sc.colors_at(xs.ravel(), ys.ravel(), w, h)
     assert np.abs(c - o).max() < TOL_ORACLE
-    img = render_host(sc, fmt_of(w, h, fx.RGBF32)).view(">f4").reshape(h, w, 3)
+    img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").reshape(h, w, 3)
     assert np.abs(img - np.clip(o, 0, 1).reshape(h, w, 3)).max() < TOL_ORACLE
     params["max_reflect_depth"] = 5
     sc.set_params_flat(params)
@@ -603,7 +594,7 @@ def test_polytope_vs_oracle_and_reference(name):
         assert np.abs(c - g["colors"][k]).max() < TOL_REF, (name, int(f))
     f0 = g["frames"][0]
     sc._set_camera_arrays(g["origins"][f0], g["axes"][f0])
-    img = render_host(sc, fmt_of(160, 90, fx.RGBX8))
+    img = sup.render_host(sc, sup.fmt_of(160, 90, fx.RGBX8))
     assert np.abs(img.astype(int) - g["image160x90_rgbx8"].astype(int)).max() <= 1    # powf last-bit rounding
 
 
@@ -612,7 +603,7 @@ def test_cell600_full_1080p_frame_vs_oracle():
     flat = fx.flat_of(g)
     sc = tracern.CompositeScene.from_flat(4, flat)
     sc._set_camera_arrays(g["origins"][33], g["axes"][33])
-    img = render_host(sc, fmt_of(1920, 1080, fx.RGBX8))
+    img = sup.render_host(sc, sup.fmt_of(1920, 1080, fx.RGBX8))
     ref = ob.OracleScene(4, g["origins"][33], g["axes"][33], flat=flat).render(1920, 1080, fx.RGBX8, threads=7)
     d = np.abs(img.astype(int) - ref.astype(int))
     assert d.max() <= 1 and (d > 0).sum() < 1e-4 * d.size
@@ -627,9 +618,9 @@ def test_cell120_full_size_properties_and_counters():
     flat = fx.flat_of(g)
     sc = tracern.CompositeScene.from_flat(4, flat)
     w, h = 1920, 1080
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     sc._set_camera_arrays(g["origins"][11], g["axes"][11])
-    img = render_host(sc, fmt, collect_stats=True)
+    img = sup.render_host(sc, fmt, collect_stats=True)
     st = sc.last_stats()
     assert st["rays"] == w * h
     re = np.empty_like(img)
@@ -651,16 +642,16 @@ def test_cell120_full_size_properties_and_counters():
     torch.cuda.synchronize()
     assert np.array_equal(fb[0].cpu().numpy().reshape(h, fmt.pitch), img)
     sc._set_camera_arrays(g["origins"][52], g["axes"][52])
-    assert np.array_equal(fb[1].cpu().numpy().reshape(h, fmt.pitch), render_host(sc, fmt))
+    assert np.array_equal(fb[1].cpu().numpy().reshape(h, fmt.pitch), sup.render_host(sc, fmt))
     # counters: same tree walk as the oracle (branches/leaves identical; the device's mailbox is small, so it
     # tests at least as many simplices) -- for the reference's exact walk (strict) and for the default walk that
     # drops cells beyond the current hit
     sc._set_camera_arrays(g["origins"][0], g["axes"][0])
-    lat = fmt_of(w, h, fx.RGBX8)
+    lat = sup.fmt_of(w, h, fx.RGBX8)
     per = lambda d, k: d[k] / d["rays"]
     walks = {}
     for strict in (True, False):
-        img0 = render_host(sc, lat, collect_stats=True, strict_reference=strict)
+        img0 = sup.render_host(sc, lat, collect_stats=True, strict_reference=strict)
         st = sc.last_stats()
         _, oc = ob.OracleScene(4, g["origins"][0], g["axes"][0], flat=flat, prune=not strict).colors_at(g["xs"], g["ys"], w, h, counters=True)
         assert abs(per(st, "branches") - per(oc, "branches")) < 0.05 * per(oc, "branches")
@@ -680,10 +671,10 @@ def test_pruned_walk_renders_the_reference_walks_bytes():
     kernel with solids and loose triangles)."""
     g = fx.load("cell120_n4")
     sc = tracern.CompositeScene.from_flat(4, fx.flat_of(g))
-    fmt = fmt_of(1920, 1080, fx.RGBX8)
+    fmt = sup.fmt_of(1920, 1080, fx.RGBX8)
     for f in (40, 120):
         sc._set_camera_arrays(g["origins"][f], g["axes"][f])
-        assert np.array_equal(render_host(sc, fmt, strict_reference=True), render_host(sc, fmt, strict_reference=False))
+        assert np.array_equal(sup.render_host(sc, fmt, strict_reference=True), sup.render_host(sc, fmt, strict_reference=False))
     g = fx.load("cell600_n4")
     flat = fx.flat_of(g)
     m = np.array(flat["materials"], np.float32).copy()
@@ -695,16 +686,16 @@ def test_pruned_walk_renders_the_reference_walks_bytes():
                             point_light_pos=[[20.0, 15.0, -25.0, 5.0]], point_light_color=[[900.0, 800.0, 700.0]],
                             global_light_dir=[[0.2, -0.9, 0.3, 0.1]], global_light_color=[[.4, .4, .5]]))
     sc._set_camera_arrays(g["origins"][5], g["axes"][5])
-    fmt = fmt_of(480, 270, fx.RGBF32)
-    assert np.array_equal(render_host(sc, fmt, strict_reference=True), render_host(sc, fmt, strict_reference=False))
+    fmt = sup.fmt_of(480, 270, fx.RGBF32)
+    assert np.array_equal(sup.render_host(sc, fmt, strict_reference=True), sup.render_host(sc, fmt, strict_reference=False))
     g = fx.load("feature3d")
     flat = fx.flat_of(g, opaque=True)                  # transparency always walks strictly
     for v in g["variants"]:
         sc = tracern.CompositeScene.from_flat(3, flat)
         sc.set_params_flat(fx.params_of(g, "%s__" % v))
         sc._set_camera_arrays(g["origin"], g["axes"])
-        fmt = fmt_of(320, 240, fx.RGBF32)
-        assert np.array_equal(render_host(sc, fmt, strict_reference=True), render_host(sc, fmt, strict_reference=False))
+        fmt = sup.fmt_of(320, 240, fx.RGBF32)
+        assert np.array_equal(sup.render_host(sc, fmt, strict_reference=True), sup.render_host(sc, fmt, strict_reference=False))
 
 
 def test_three_composite_kernels_render_identical_frames(monkeypatch):
@@ -713,13 +704,13 @@ def test_three_composite_kernels_render_identical_frames(monkeypatch):
     reference order, so their frames must be byte-identical (and equal the oracle's up to powf rounding)."""
     g = fx.load("cell600_n4")
     flat = fx.flat_of(g)
-    fmt = fmt_of(333, 217, fx.RGBF32)          # ragged size, float channels: colours compared bit for bit
+    fmt = sup.fmt_of(333, 217, fx.RGBF32)          # ragged size, float channels: colours compared bit for bit
     frames = {}
     for choice in ("0", "1", "2"):
         monkeypatch.setenv("NTRACER_COMPOSITE_KERNEL", choice)
         sc = tracern.CompositeScene.from_flat(4, flat)
         sc._set_camera_arrays(g["origins"][77], g["axes"][77])
-        frames[choice] = render_host(sc, fmt)
+        frames[choice] = sup.render_host(sc, fmt)
     assert np.array_equal(frames["0"], frames["1"])
     assert np.array_equal(frames["0"], frames["2"])
     ref = ob.OracleScene(4, g["origins"][77], g["axes"][77], flat=flat).render(333, 217, fx.RGBF32, threads=7)
@@ -740,14 +731,14 @@ def test_lit_reflective_polytope_packet_vs_tile_vs_oracle(monkeypatch):
                   ambient=[.02, .02, .03], bg1=[1, 1, 1], bg2=[0, 0, 0], bg3=[0, 1, 1],
                   point_light_pos=[[20.0, 15.0, -25.0, 5.0]], point_light_color=[[900.0, 800.0, 700.0]],
                   global_light_dir=[[0.2, -0.9, 0.3, 0.1]], global_light_color=[[.4, .4, .5]])
-    fmt = fmt_of(240, 135, fx.RGBF32)
+    fmt = sup.fmt_of(240, 135, fx.RGBF32)
     frames = {}
     for choice in ("0", "2"):
         monkeypatch.setenv("NTRACER_COMPOSITE_KERNEL", choice)
         sc = tracern.CompositeScene.from_flat(4, flat)
         sc.set_params_flat(params)
         sc._set_camera_arrays(g["origins"][5], g["axes"][5])
-        frames[choice] = render_host(sc, fmt)
+        frames[choice] = sup.render_host(sc, fmt)
     assert np.array_equal(frames["0"], frames["2"])
     ref = ob.OracleScene(4, g["origins"][5], g["axes"][5], flat=flat, params=params).render(240, 135, fx.RGBF32, threads=7)
     assert np.abs(frames["0"].view(">f4") - ref.view(">f4")).max() < TOL_ORACLE
@@ -760,7 +751,7 @@ def test_multi_frame_launches_in_chunks(monkeypatch):
     Forcing one- and two-frame chunks must not change a byte, lit or not."""
     import torch
     g = fx.load("cell600_n4")
-    fmt = fmt_of(320, 180, fx.RGBF32)
+    fmt = sup.fmt_of(320, 180, fx.RGBF32)
     frames = [3, 40, 77, 111, 150]
     o = np.ascontiguousarray(g["origins"][frames], np.float32)
     a = np.ascontiguousarray(g["axes"][frames], np.float32)
@@ -788,7 +779,7 @@ def test_multi_frame_launches_in_chunks(monkeypatch):
         assert np.array_equal(out[""], out["1"]) and np.array_equal(out[""], out["2"])
         monkeypatch.delenv("NTRACER_CHUNK_FRAMES", raising=False)
         sc._set_camera_arrays(g["origins"][77], g["axes"][77])
-        assert np.array_equal(out[""][2].reshape(fmt.height, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(out[""][2].reshape(fmt.height, fmt.pitch), sup.render_host(sc, fmt))
         assert out[""].view(">f4").max() > 0.3
 
 
@@ -802,15 +793,15 @@ def test_rebuilt_tree_renders_the_same_bytes():
         sc = tracern.CompositeScene.from_flat(4, fx.flat_of(g))
         reb = sc.with_rebuilt_tree()
         assert len(reb._flat["batch_recs"]) == len(sc._flat["batch_recs"])
-        fmt = fmt_of(1920, 1080, fx.RGBX8)
+        fmt = sup.fmt_of(1920, 1080, fx.RGBX8)
         for f in frames:
             sc._set_camera_arrays(g["origins"][f], g["axes"][f])
             reb._set_camera_arrays(g["origins"][f], g["axes"][f])
-            a = render_host(sc, fmt).reshape(1080, 1920, 4)
-            b = render_host(reb, fmt).reshape(1080, 1920, 4)
+            a = sup.render_host(sc, fmt).reshape(1080, 1920, 4)
+            b = sup.render_host(reb, fmt).reshape(1080, 1920, 4)
             ties = (a != b).any(axis=2).sum()
             assert ties <= 2e-4 * 1920 * 1080, (name, f, int(ties))
-            assert np.array_equal(b, render_host(reb, fmt, strict_reference=True).reshape(1080, 1920, 4)), (name, f)
+            assert np.array_equal(b, sup.render_host(reb, fmt, strict_reference=True).reshape(1080, 1920, 4)), (name, f)
 
 
 def test_scenes_with_solids_and_loose_triangles_take_the_packet_walk(monkeypatch):
@@ -821,7 +812,7 @@ def test_scenes_with_solids_and_loose_triangles_take_the_packet_walk(monkeypatch
     g = fx.load("feature3d")
     flat = fx.flat_of(g, opaque=True)
     w, h = int(g["width"]), int(g["height"])
-    fmt = fmt_of(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     # (by default a scene with Solids is rendered with the reference's o_hit.normal handling by composite_kernel_t<N, true>;
     # the packet walk serves the intended-semantics mode)
     monkeypatch.setenv("NTRACER_CLEAN_NORMALS", "1")
@@ -833,20 +824,20 @@ def test_scenes_with_solids_and_loose_triangles_take_the_packet_walk(monkeypatch
             sc = tracern.CompositeScene.from_flat(3, flat)
             sc.set_params_flat(p)
             sc._set_camera_arrays(g["origin"], g["axes"])
-            frames[choice] = render_host(sc, fmt)
+            frames[choice] = sup.render_host(sc, fmt)
         assert np.array_equal(frames["0"], frames["2"]), str(v)
         ref = ob.OracleScene(3, g["origin"], g["axes"], flat=flat, params=p, clean_normals=True).render(w, h, fx.RGBF32, threads=7)
         assert np.abs(frames["0"].view(">f4") - ref.view(">f4")).max() < TOL_ORACLE, str(v)
     g = fx.load("simplex10_n10")
     flat = fx.flat_of(g)
     assert len(flat["tri_recs"]) == 3
-    fmt = fmt_of(200, 120, fx.RGBF32)
+    fmt = sup.fmt_of(200, 120, fx.RGBF32)
     frames = {}
     for choice in ("0", "2"):
         monkeypatch.setenv("NTRACER_COMPOSITE_KERNEL", choice)
         sc = tracern.CompositeScene.from_flat(10, flat)
         sc._set_camera_arrays(g["origins"][9], g["axes"][9])
-        frames[choice] = render_host(sc, fmt)
+        frames[choice] = sup.render_host(sc, fmt)
     assert np.array_equal(frames["0"], frames["2"])
 
 
@@ -861,9 +852,9 @@ def test_band_heights_other_than_32(band_rows, world):
     scenes[1]._set_camera_arrays(g["origins"][33], g["axes"][33])
     g12 = fx.load("box_n12_320x200")                     # (run-time-n rows kernel)
     scenes[2]._set_camera_arrays(g12["origins"][g12["frames"][1]], g12["axes"][g12["frames"][1]])
-    fmt = fmt_of(500, 301, fx.RGBX8)
+    fmt = sup.fmt_of(500, 301, fx.RGBX8)
     for sc in scenes:
-        whole = render_host(sc, fmt)
+        whole = sup.render_host(sc, fmt)
         re = np.zeros_like(whole)
         for r in range(world):
             rows = ntd.owned_rows(fmt.height, r, world, band_rows)
@@ -881,7 +872,7 @@ def test_three_byte_pixels_are_packed_across_lanes(w, h, pitch, rev):
     the oracle either way: BoxScene (exact) and a composite scene through the packet and tile kernels (+-1)."""
     rgb24 = [(8, 1, 0, 0), (8, 0, 1, 0), (8, 0, 0, 1)]
     gb = fx.load("box_n6_1920x1080")
-    fmt = fmt_of(w, h, rgb24, pitch, rev)
+    fmt = sup.fmt_of(w, h, rgb24, pitch, rev)
     sc = tracern.BoxScene(6)
     sc._set_camera_arrays(gb["origins"][17], gb["axes"][17])
     buf = bytearray(b"\xa5" * (fmt.pitch * h))
@@ -907,7 +898,7 @@ def test_six_byte_pixels_are_packed_across_lane_pairs(w, h, pitch, rev):
     pixels on aligned rows (store_word64_narrow); the bytes are the oracle's."""
     rgb48 = [(16, 1, 0, 0), (16, 0, 1, 0), (16, 0, 0, 1)]
     gb = fx.load("box_n6_1920x1080")
-    fmt = fmt_of(w, h, rgb48, pitch, rev)
+    fmt = sup.fmt_of(w, h, rgb48, pitch, rev)
     sc = tracern.BoxScene(6)
     sc._set_camera_arrays(gb["origins"][17], gb["axes"][17])
     buf = bytearray(b"\x5a" * (fmt.pitch * h))
@@ -938,7 +929,7 @@ def test_bench_workload_every_frame_equals_the_oracle():
     import torch
     g = fx.load("box_n6_1920x1080")
     w, h = 1920, 1080
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     sc = tracern.BoxScene(6)
     o = np.ascontiguousarray(g["origins"], np.float32)
     a = np.ascontiguousarray(g["axes"], np.float32)
@@ -973,7 +964,7 @@ def test_tall_launches_take_sixty_four_rows_a_wave(n, chans):
     import torch
     rng = np.random.default_rng(700 + n)
     w, h, nf = 1920, 1080, 72
-    fmt = fmt_of(w, h, fx.RGBX8 if chans == "rgbx8" else fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBX8 if chans == "rgbx8" else fx.RGBF32)
     origins, axes = [], []
     for k in range(nf):
         q, _ = np.linalg.qr(rng.standard_normal((n, n)))
@@ -1021,7 +1012,7 @@ def test_bench_workload_in_bands_and_in_float_channels():
         torch.cuda.synchronize()
         return fb.cpu().numpy().reshape(len(frames), rows, fmt.pitch)
 
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     whole = launch(fmt, list(range(nf)), None, h)
     for rank in (0, 5):
         opts = _lib.NtRenderOpts()
@@ -1030,7 +1021,7 @@ def test_bench_workload_in_bands_and_in_float_channels():
         part = launch(fmt, list(range(nf)), opts, len(rows))
         assert np.array_equal(part, whole[:, rows, :]), rank
     frames = list(range(0, nf, 4))                        # 40 frames: still the large-launch shape
-    fmt32 = fmt_of(w, h, fx.RGBF32)
+    fmt32 = sup.fmt_of(w, h, fx.RGBF32)
     got = launch(fmt32, frames, None, h)
     threads = max(1, min(63, (os.cpu_count() or 2) - 1))
     osc = ob.OracleScene(6, o[0], a[0])
@@ -1048,7 +1039,7 @@ def test_cell120_full_1080p_frames_vs_oracle(frame):
     flat = fx.flat_of(g)
     sc = tracern.CompositeScene.from_flat(4, flat)
     sc._set_camera_arrays(g["origins"][frame], g["axes"][frame])
-    img = render_host(sc, fmt_of(1920, 1080, fx.RGBX8))
+    img = sup.render_host(sc, sup.fmt_of(1920, 1080, fx.RGBX8))
     threads = max(1, min(63, (os.cpu_count() or 2) - 1))
     ref = ob.OracleScene(4, g["origins"][frame], g["axes"][frame], flat=flat, prune=True).render(1920, 1080, fx.RGBX8, threads=threads)
     d = np.abs(img.astype(int) - ref.astype(int))
@@ -1064,8 +1055,8 @@ def test_three_float_channels_fast_path(order, rev):
     gb = fx.load("box_n6_1920x1080")
     sc = tracern.BoxScene(6)
     sc._set_camera_arrays(gb["origins"][29], gb["axes"][29])
-    fmt = fmt_of(401, 33, chans, 0, rev)
-    got = render_host(sc, fmt)
+    fmt = sup.fmt_of(401, 33, chans, 0, rev)
+    got = sup.render_host(sc, fmt)
     ref = ob.OracleScene(6, gb["origins"][29], gb["axes"][29]).render(401, 33, chans, reversed_=rev)
     assert np.array_equal(got, ref)
     assert got.max() > 0
@@ -1078,7 +1069,7 @@ def test_config4_whole_rotation_default_walk_equals_reference_walk():
     for name in ("cell120_n4", "cell600_n4"):
         g = fx.load(name)
         sc = tracern.CompositeScene.from_flat(4, fx.flat_of(g))
-        fmt = fmt_of(1920, 1080, fx.RGBX8)
+        fmt = sup.fmt_of(1920, 1080, fx.RGBX8)
         st_ = fmt._as_struct()
         o = np.ascontiguousarray(g["origins"], np.float32)
         a = np.ascontiguousarray(g["axes"], np.float32)
@@ -1148,7 +1139,7 @@ def test_lights_shadows_reflection_solids_vs_oracle(monkeypatch):
             other = ob.OracleScene(3, g["origin"], g["axes"], flat=flat, params=p, clean_normals=not clean).colors_at(xs.ravel(), ys.ravel(), w, h)
             differ += int((np.abs(c - other).max(axis=1) > TOL_REF).sum())
             # strict_reference changes nothing here (scenes with Solids are always walked strictly)
-            img = render_host(sc, fmt_of(w, h, fx.RGBF32), strict_reference=True).view(">f4").reshape(h, w, 3)
+            img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32), strict_reference=True).view(">f4").reshape(h, w, 3)
             assert np.abs(img - np.clip(o, 0, 1).reshape(h, w, 3)).max() < TOL_ORACLE, (str(v), clean)      # (channels clamp)
         assert differ > 0            # the two modes are not the same thing on this scene
 
@@ -1175,12 +1166,12 @@ def test_transparency_vs_oracle(monkeypatch):
         dr = np.abs(c.reshape(h, w, 3) - g["%s__colors" % v]).max(axis=2)
         assert (dr > TOL_REF).sum() <= 0.005 * dr.size, (str(v), int((dr > TOL_REF).sum()))
         assert np.median(dr) < 1e-6
-    img = render_host(sc, fmt_of(w, h, fx.RGB16), strict_reference=True)
+    img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGB16), strict_reference=True)
     ref = ob.OracleScene(3, g["origin"], g["axes"], flat=flat, params=p).render(w, h, fx.RGB16, threads=3)
     assert np.abs(img.astype(int) - ref.astype(int)).max() <= 1
     # a multi-frame device launch takes the same path (blocks striding over the tiles of all frames)
     import torch
-    fmt = fmt_of(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     fb = torch.zeros((3, fmt.pitch * h), dtype=torch.uint8, device="cuda")
     o3 = np.ascontiguousarray(np.stack([g["origin"]] * 3), np.float32)
     a3 = np.ascontiguousarray(np.stack([g["axes"]] * 3), np.float32)
@@ -1244,7 +1235,7 @@ def test_reflection_deeper_than_the_level_stack(monkeypatch):
         sc2._set_camera_arrays(origin, axes)
         c = sc2.colors_at(xs.ravel(), ys.ravel(), w, h)
         assert np.abs(c - o).max() < TOL_ORACLE, force_var
-        img = render_host(sc2, fmt_of(w, h, fx.RGBF32)).view(">f4").reshape(h, w, 3)
+        img = sup.render_host(sc2, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").reshape(h, w, 3)
         assert np.abs(img - np.clip(o, 0, 1).reshape(h, w, 3)).max() < TOL_ORACLE, force_var
 
 
@@ -1269,7 +1260,7 @@ def test_five_dimensional_feature_scene_vs_reference(monkeypatch):
                 assert np.abs(c - g["colors"][k]).max() < TOL_REF, int(f)
     monkeypatch.delenv("NTRACER_CLEAN_NORMALS")
     sc._set_camera_arrays(g["origins"][9], g["axes"][9])
-    img = render_host(sc, fmt_of(160, 100, fx.RGBF32))
+    img = sup.render_host(sc, sup.fmt_of(160, 100, fx.RGBF32))
     ref = ob.OracleScene(5, g["origins"][9], g["axes"][9], flat=flat, params=p).render(160, 100, fx.RGBF32, threads=7)
     assert np.abs(img.view(">f4") - ref.view(">f4")).max() < TOL_ORACLE
 
@@ -1280,7 +1271,7 @@ def test_shadow_rays_are_counted():
     sc = tracern.CompositeScene.from_flat(3, flat)
     sc._set_camera_arrays(g["origin"], g["axes"])
     sc.set_params_flat(fx.params_of(g, "shadows__"))
-    render_host(sc, fmt_of(96, 64, fx.RGBX8), collect_stats=True)
+    sup.render_host(sc, sup.fmt_of(96, 64, fx.RGBX8), collect_stats=True)
     st = sc.last_stats()
     assert st["shadow_rays"] > 0 and st["rays"] > 96 * 64      # primary + reflection
 
@@ -1333,7 +1324,7 @@ def test_box_soak_slice(n):
     sc = tracern.BoxScene(n)
     osc = ob.OracleScene(n, o[0], a[0])
     for chans in (fx.RGBX8, fx.RGBF32):
-        fmt = fmt_of(W, H, chans)
+        fmt = sup.fmt_of(W, H, chans)
         fst = fmt._as_struct()
         fb = torch.zeros((F, H * fmt.pitch), dtype=torch.uint8, device="cuda")
         _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(fb.data_ptr()), H * fmt.pitch, F, o.ctypes.data_as(_lib.f32p),
@@ -1357,7 +1348,7 @@ def test_camera_table_renders_the_same_frames():
     o = np.ascontiguousarray(g["origins"][10:10 + F], np.float32)
     a = np.ascontiguousarray(g["axes"][10:10 + F], np.float32)
     sc = tracern.BoxScene(6)
-    fmt = fmt_of(1920, 1080, fx.RGBX8)
+    fmt = sup.fmt_of(1920, 1080, fx.RGBX8)
     fst = fmt._as_struct()
     tab = CameraTable(6, o, a)
     assert tab.frames == F
@@ -1394,7 +1385,7 @@ def test_camera_table_renders_the_same_frames():
     o10 = np.ascontiguousarray(g10["origins"][[5, 60, 61, 130, 140]], np.float32)
     a10 = np.ascontiguousarray(g10["axes"][[5, 60, 61, 130, 140]], np.float32)
     sc10 = tracern.BoxScene(10)
-    fmt10 = fmt_of(1024, 640, fx.RGBX8)
+    fmt10 = sup.fmt_of(1024, 640, fx.RGBX8)
     tab10 = CameraTable(10, o10, a10)
     whole10 = torch.zeros((5, 640 * fmt10.pitch), dtype=torch.uint8, device="cuda")
     part10 = torch.zeros((2, 640 * fmt10.pitch), dtype=torch.uint8, device="cuda")
@@ -1407,7 +1398,7 @@ def test_camera_table_renders_the_same_frames():
     sc4 = tracern.CompositeScene.from_flat(4, fx.flat_of(g4))
     o4 = np.ascontiguousarray(g4["origins"][[0, 40, 93]], np.float32)
     a4 = np.ascontiguousarray(g4["axes"][[0, 40, 93]], np.float32)
-    fmt4 = fmt_of(640, 360, fx.RGBX8)
+    fmt4 = sup.fmt_of(640, 360, fx.RGBX8)
     fst4 = fmt4._as_struct()
     x = torch.zeros((3, 360 * fmt4.pitch), dtype=torch.uint8, device="cuda")
     y = torch.zeros_like(x)
@@ -1438,7 +1429,7 @@ def test_box_fused_and_general_paths_alternate_on_one_scene(monkeypatch):
                 monkeypatch.delenv("NTRACER_BOX_INTERLEAVE", raising=False)
             else:
                 monkeypatch.setenv("NTRACER_BOX_INTERLEAVE", il)
-            fmt = fmt_of(W, H, chans[f])
+            fmt = sup.fmt_of(W, H, chans[f])
             fst = fmt._as_struct()
             fb = torch.full((len(sel), fmt.pitch * H), 0x5a, dtype=torch.uint8, device="cuda")
             _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(fb.data_ptr()), fmt.pitch * H, len(sel), o.ctypes.data_as(_lib.f32p),
@@ -1463,7 +1454,7 @@ def test_render_calls_captured_in_a_hip_graph():
         F = 6
         o = np.ascontiguousarray(g["origins"][20:20 + F], np.float32)
         a = np.ascontiguousarray(g["axes"][20:20 + F], np.float32)
-        fmt = fmt_of(W, H, fx.RGBX8)
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
         fst = fmt._as_struct()
         sc = tracern.BoxScene(n)
         tab = CameraTable(n, o, a)
@@ -1505,7 +1496,7 @@ def test_overlapped_hint_changes_the_launch_shape_not_the_bytes():
     W, H, F = 1920, 1080, 160
     o = np.ascontiguousarray(g["origins"][:F], np.float32)
     a = np.ascontiguousarray(g["axes"][:F], np.float32)
-    fmt = fmt_of(W, H, fx.RGBX8)
+    fmt = sup.fmt_of(W, H, fx.RGBX8)
     fst = fmt._as_struct()
     L = _lib.lib()
     for world, brows in ((8, 8), (1, 32)):
@@ -1546,16 +1537,16 @@ def test_asking_for_statistics_does_not_change_the_pixels():
     sc = tracern.CompositeScene.from_flat(3, flat)
     sc._set_camera_arrays(g["origin"], g["axes"])
     sc.set_params_flat(fx.params_of(g, "shadows__"))
-    fmt = fmt_of(96, 64, fx.RGBF32)
-    plain = render_host(sc, fmt)
-    counted = render_host(sc, fmt, collect_stats=True)
+    fmt = sup.fmt_of(96, 64, fx.RGBF32)
+    plain = sup.render_host(sc, fmt)
+    counted = sup.render_host(sc, fmt, collect_stats=True)
     assert np.array_equal(plain, counted)
     st = sc.last_stats()
     assert st["rays"] > 96 * 64 and st["solid_tests"] > 0
     tr = tracern.CompositeScene.from_flat(3, fx.flat_of(g))            # the fixture as it is: transparent materials
     tr._set_camera_arrays(g["origin"], g["axes"])
     with pytest.raises(NotImplementedError, match="collect_stats"):
-        render_host(tr, fmt, collect_stats=True)
+        sup.render_host(tr, fmt, collect_stats=True)
     assert not tr.locked
 
 
@@ -1565,8 +1556,8 @@ def _long_scene():
     g = fx.load("cell120_n4")
     sc = tracern.CompositeScene.from_flat(4, fx.flat_of(g))
     sc._set_camera_arrays(g["origins"][0], g["axes"][0])
-    fmt = fmt_of(4096, 4096, fx.RGBX8)
-    render_host(sc, fmt_of(64, 64, fx.RGBX8))            # scene upload, code load: not part of what is timed below
+    fmt = sup.fmt_of(4096, 4096, fx.RGBX8)
+    sup.render_host(sc, sup.fmt_of(64, 64, fx.RGBX8))            # scene upload, code load: not part of what is timed below
     return sc, fmt
 
 
@@ -1630,7 +1621,7 @@ def test_abort_word_on_the_batched_device_path():
     import torch
     g = fx.load("box_n6_1920x1080")
     sc = tracern.BoxScene(6)
-    fmt = fmt_of(1920, 1080, fx.RGBX8)
+    fmt = sup.fmt_of(1920, 1080, fx.RGBX8)
     fst = fmt._as_struct()
     F = 8
     word = torch.zeros(16, dtype=torch.int32, device="cuda")
@@ -1661,7 +1652,7 @@ def test_abort_word_on_the_batched_device_path():
     sc4 = tracern.CompositeScene.from_flat(4, fx.flat_of(g4))
     o4 = np.ascontiguousarray(g4["origins"][:2], np.float32)
     a4 = np.ascontiguousarray(g4["axes"][:2], np.float32)
-    fmt4 = fmt_of(640, 360, fx.RGBX8)
+    fmt4 = sup.fmt_of(640, 360, fx.RGBX8)
     fst4 = fmt4._as_struct()
     fb4 = torch.full((2, fmt4.pitch * 360), 0xab, dtype=torch.uint8, device="cuda")
     word.fill_(1)
@@ -1708,7 +1699,7 @@ def test_second_render_on_a_busy_renderer_or_scene_is_refused():
 def test_callback_renderer_invokes_callback_and_locks_scene():
     import threading
     sc = tracern.BoxScene(4)
-    fmt = fmt_of(320, 200, fx.RGBX8)
+    fmt = sup.fmt_of(320, 200, fx.RGBX8)
     buf = bytearray(fmt.pitch * 200)
     done = threading.Event()
     r = ntracer_amd.CallbackRenderer()

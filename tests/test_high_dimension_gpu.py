@@ -14,6 +14,7 @@ import pytest
 import adaptive_cases as ac
 import fixtures as fx
 import high_dimension_cases as hd
+import support as sup
 import ntracer_amd
 import test_composite_matrix as tcm
 from ntracer_amd import tracern
@@ -34,10 +35,7 @@ TOO_DEEP = r"scene too deep for the LDS budget \(n 64, depth 369\)"
 def _scene(case, mp, flat=None):
     """the case's scene with the switches set before it is made"""
     s = hd.scene(case)
-    for k in SWITCHES:
-        mp.delenv(k, raising=False)
-    for k, v in hd.env_of(case).items():
-        mp.setenv(k, v)
+    sup.set_switches(mp, SWITCHES, hd.env_of(case))
     sc = tracern.CompositeScene.from_flat(s.n, s.flat if flat is None else flat)
     sc.set_params_flat(s.params)
     sc._set_camera_arrays(s.origin, s.axes)
@@ -152,7 +150,7 @@ def test_the_five_settings_on_their_general_routes_at_n64(case):
     c = hd.settings(case)
     w, h = hd.SMALL_VIEW
     label = hd.case_id(case)
-    fmt = tcue.fmt_of(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     with pytest.MonkeyPatch.context() as mp:
         sc = _scene(case, mp)
         sc._set_camera_arrays(c.origin, c.axes)
@@ -175,19 +173,19 @@ def test_the_five_settings_on_their_general_routes_at_n64(case):
         sc.set_ambient_occlusion(c.ao_table, radius=ao.RADIUS, bias=ao.BIAS, strength=0.75)
         tao._both_forms(sc, w, h, c.ao["blocked"], label + " ambient occlusion")
         want = sx.pack(ao.shade(P, c.ao["blocked"], hd.AO_K, 0.75), fx.RGBF32, False)
-        assert np.array_equal(tcue.render_host(sc, fmt), want), label + ": the render under ambient occlusion"
+        assert np.array_equal(sup.render_host(sc, fmt), want), label + ": the render under ambient occlusion"
         sc.set_ambient_occlusion(None)
         # ---- outlines: the mask equal, the render the plain frame with the lines drawn
         tout._set(sc, oc.A)
         tout._both_forms(sc, w, h, c.outline, label + " outlines")
         want = sx.pack(oc.blend(P, c.outline, tout.COLOR, tout.STRENGTH), fx.RGBF32, False)
-        assert np.array_equal(tcue.render_host(sc, fmt), want), label + ": the render with outlines"
+        assert np.array_equal(sup.render_host(sc, fmt), want), label + ": the render with outlines"
         sc.set_outlines(None)
         # ---- depth cues, the tint axis non-zero in coordinate 63: the factors bit for bit, the render their blend
         tcue._set(sc, c.cue)
         tcue._both_forms(sc, w, h, c.cue_factors, label + " depth cue")
         want = sx.pack(cc.blend(P, c.cue_factors[..., 0], c.cue_factors[..., 1], c.cue), fx.RGBF32, False)
-        assert np.array_equal(tcue.render_host(sc, fmt), want), label + ": the render under the depth cue"
+        assert np.array_equal(sup.render_host(sc, fmt), want), label + ": the render under the depth cue"
         sc.set_depth_cue(None)
     print("%s, 9 x 7, five settings: worst difference from the oracle: plain frame %g (< %g), fisheye %g, parallel %g (<= 1e-05); "
           "occlusion counts, outline mask and cue factors equal" % (label, worst_plain, TOL_ORACLE, worst_lens, worst_parallel))

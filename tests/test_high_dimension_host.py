@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import high_dimension_cases as hd
+import support as sup
 from ntracer_amd import tracern
-from test_ray_queries_host import _body, _launches, _read
 
 W, H = hd.VIEW
 
@@ -115,22 +115,22 @@ def test_lds_sizes_of_the_cases():
 
 
 def test_var_lds_bytes_is_that_expression_and_the_limits_are_where_the_cases_put_them():
-    src = _read("nt_var.hip")
-    body = _body(src, "__host__ __device__ __forceinline__ size_t var_lds_bytes(int depth, int n)")
+    src = sup.source("nt_var.hip")
+    body = sup.function_body(src, "__host__ __device__ __forceinline__ size_t var_lds_bytes(int depth, int n)")
     assert re.search(r"return \(size_t\)64 \* \(\(size_t\)n \* 16 \+ \(size_t\)depth \* 4 \+ \(size_t\)NT_MBOX \* 4\);", body), body
-    mbox = re.search(r"#define\s+NT_MBOX\s+(\d+)", _read("nt_composite.hpp") + _read("nt_device.hpp"))
+    mbox = re.search(r"#define\s+NT_MBOX\s+(\d+)", sup.source("nt_composite.hpp") + sup.source("nt_device.hpp"))
     assert mbox and int(mbox.group(1)) == 16                        # 64 bytes a lane
-    ready = _body(src, "int var_walk_ready(")
+    ready = sup.function_body(src, "int var_walk_ready(")
     assert re.search(r"lds = var_lds_bytes\(sc\.stack_depth, n\);", ready)
     assert re.search(r"if \(lds > 160 \* 1024\) \{\s*snprintf\([^;]*\"scene too deep for the LDS budget \(n %d, depth %d\)\", n, sc\.stack_depth\);\s*return -1;", ready), ready
     assert re.search(r"if \(lds > 64 \* 1024\) \(void\)hipFuncSetAttribute\(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, \(int\)lds\);", ready), ready
     # the refusal comes before the attribute, and the launchers launch nothing before var_walk_ready has answered
     assert ready.index("160 * 1024") < ready.index("hipFuncSetAttribute")
     for head in WALK_LAUNCHERS:
-        b = _body(src, "int %s(" % head)
+        b = sup.function_body(src, "int %s(" % head)
         first = min(m.start() for m in re.finditer(r"hipLaunchKernelGGL\(\s*\w*(?:composite_kernel|query_|hits_|rays_color|refine_color)\w*_var", b))
         assert b.index("var_walk_ready(") < first, head
-    assert "std::max(s->depth + 1, 2)" in _body(_read("nt_api.cpp"), "void fill_composite(")
+    assert "std::max(s->depth + 1, 2)" in sup.function_body(sup.source("nt_api.cpp"), "void fill_composite(")
 
 
 def _named_kernels(body):
@@ -149,15 +149,15 @@ def _lds_launches(body):
 
 
 def test_every_launcher_hands_var_walk_ready_the_kernels_it_launches():
-    src = _read("nt_var.hip")
-    launchers = [h for h in re.findall(r"\nint (nt_launch_\w+)\(", src) if "var_walk_ready(" in _body(src, "int %s(" % h)]
+    src = sup.source("nt_var.hip")
+    launchers = [h for h in re.findall(r"\nint (nt_launch_\w+)\(", src) if "var_walk_ready(" in sup.function_body(src, "int %s(" % h)]
     assert sorted(launchers) == sorted(WALK_LAUNCHERS)
     union = set()
     for head in launchers:
-        body = _body(src, "int %s(" % head)
+        body = sup.function_body(src, "int %s(" % head)
         named, launched = _named_kernels(body), _lds_launches(body)
         assert named and named == launched, (head, sorted(named - launched), sorted(launched - named))
-        assert launched <= _launches(body)
+        assert launched <= sup.launches(body)
         # every var_walk_ready of the launcher takes a kernel the launcher names, never a null or a cached pointer
         for arg in re.findall(r"var_walk_ready\(li\.n, \*?sc, (.*?), lds\)", body):
             assert arg == "kernel" or arg.startswith("alias_kernel(") or arg.startswith("reinterpret_cast<const void *>("), (head, arg)
@@ -195,7 +195,7 @@ def test_every_walk_kernel_has_cases_below_and_above_64_kib():
         sizes = reached[kernel]
         assert min(sizes) <= hd.LDS_ATTRIBUTE < max(sizes) <= hd.LDS_LIMIT, (kernel, sorted(set(sizes)))
     # the rule itself: composite_route's `faithful` and `var` (nt_api.cpp)
-    api = _read("nt_api.cpp")
+    api = sup.source("nt_api.cpp")
     assert "r.faithful = !s->all_opaque || (s->n_solids > 0 && !sw.clean_normals);" in api
     assert "r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;" in api and "c.alias_normals = sw.clean_normals ? 0 : 1;" in api
 

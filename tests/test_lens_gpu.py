@@ -14,6 +14,7 @@ import pytest
 import fixtures as fx
 import lens_cases as lc
 import oracle_binding as ob
+import support as sup
 import ntracer_amd
 from ntracer_amd import Lens, _lib, tracern
 from ntracer_amd.render import CameraTable
@@ -26,15 +27,6 @@ RGB24 = [(8, 1, 0, 0), (8, 0, 1, 0), (8, 0, 0, 1)]
 # fp32 x 3 at a quarter of the colour: the lit scenes' colours reach 3.1 under the close cameras of lens_cases, and a format clamps at
 # 1 -- a comparison of clamped colours would pass on white.  A quarter is exact in fp32, so nothing is lost: got * 4 is the colour.
 QUARTER = [(32, 0.25, 0, 0, 0, True), (32, 0, 0.25, 0, 0, True), (32, 0, 0, 0.25, 0, True)]
-
-
-def _device():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _fmt(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
 
 
 def _bpp(chans):
@@ -88,7 +80,7 @@ def test_the_pinhole_lens_is_the_plain_render_byte_for_byte(scene):
     with pytest.MonkeyPatch.context() as mp:
         sc = lc.scene(scene, mp)
         for chans, _ in PINHOLE_FORMATS:
-            fmt = _fmt(w, h, chans)
+            fmt = sup.fmt_of(w, h, chans)
             sc.set_lens(None)
             plain = _render(sc, fmt)
             sc.set_lens(Lens.pinhole(w, h, lc.FOV))
@@ -110,13 +102,13 @@ def test_lens_renders_equal_the_oracle_on_every_pixel(case):
         sc = lc.scene(case, mp)
         sc.set_lens(ln)
         assert want.max() < 4.0
-        got = _floats(_render(sc, _fmt(w, h, QUARTER)), w, h)
+        got = _floats(_render(sc, sup.fmt_of(w, h, QUARTER)), w, h)
         worst = _check(case, got, want, scale=4.0)
         assert (got[masked].view(np.uint32) == 0).all()                 # masked pixels: exactly (0, 0, 0)
-        plain = _floats(_render(sc, _fmt(w, h, fx.RGBF32)), w, h)       # ... and the plain fp32 x 3 format: the same colours, clamped
+        plain = _floats(_render(sc, sup.fmt_of(w, h, fx.RGBF32)), w, h)       # ... and the plain fp32 x 3 format: the same colours, clamped
         worst = max(worst, _check(case, plain, want))
         assert (plain[masked].view(np.uint32) == 0).all()
-        img = _render(sc, _fmt(w, h, fx.RGBX8))
+        img = _render(sc, sup.fmt_of(w, h, fx.RGBX8))
         ref = _packed(want, fx.RGBX8, False, w, h)
         diff = np.abs(img.astype(int) - ref.astype(int)).max()
         assert diff <= (0 if lc.is_box(case[0]) else 1), (lc.case_id(case), int(diff))
@@ -154,14 +146,14 @@ def test_shapes_and_formats(scene):
                 ln = lc.LENSES[name](w, h)
                 want = _expected_for(scene, ln)
                 sc.set_lens(ln)
-                worst = max(worst, _check(case, _floats(_render(sc, _fmt(w, h, fx.RGBF32)), w, h), want, " %dx%d %s" % (w, h, name)))
+                worst = max(worst, _check(case, _floats(_render(sc, sup.fmt_of(w, h, fx.RGBF32)), w, h), want, " %dx%d %s" % (w, h, name)))
         for (w, h), chans, pad, rev in (((9, 17), RGB24, 1, False), ((37, 29), RGB24, 0, True), ((37, 29), RGB24, 1, False),
                                         ((9, 17), fx.RGBX8, 0, True), ((37, 29), fx.RGB16, 7, False), ((9, 17), fx.RGBF32, 12, True)):
             ln = lc.LENSES["fisheye"](w, h)
             want = _expected_for(scene, ln)
             bpp = _bpp(chans)
             pitch = w * bpp + pad
-            fmt = _fmt(w, h, chans, pitch if pad else 0, rev)
+            fmt = sup.fmt_of(w, h, chans, pitch if pad else 0, rev)
             sc.set_lens(ln)
             buf = bytearray(b"\xab" * (pitch * h))
             assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc) is True
@@ -192,15 +184,15 @@ def test_masked_pixels_and_the_bytes_outside_the_image(scene):
         for chans in (fx.RGBF32, fx.RGBX8, RGB24):
             bpp = _bpp(chans)
             pitch = w * bpp + 8
-            fmt = _fmt(w, h, chans, pitch)
-            dest = torch.full((h + 3, pitch), 0xab, dtype=torch.uint8, device=_device())
+            fmt = sup.fmt_of(w, h, chans, pitch)
+            dest = torch.full((h + 3, pitch), 0xab, dtype=torch.uint8, device=sup.cuda_device())
             assert ntracer_amd.BlockingRenderer().render(dest, fmt, sc) is True
             torch.cuda.synchronize()
             got = dest.cpu().numpy()
             assert (got[h:] == 0xab).all() and (got[:h, w * bpp:] == 0xab).all(), chans[0]
             px = got[:h, :w * bpp].reshape(h, w, bpp)
             assert not px[masked].any(), chans[0]
-            assert np.array_equal(got[:h, :w * bpp], _render(sc, _fmt(w, h, chans))), chans[0]       # the host path: the same bytes
+            assert np.array_equal(got[:h, :w * bpp], _render(sc, sup.fmt_of(w, h, chans))), chans[0]       # the host path: the same bytes
             assert px[~masked].any()
 
 
@@ -220,7 +212,7 @@ def test_a_camera_table_with_a_padded_frame_stride(scene, chunk):
     ln = lc.lens(case)
     cams = _three_cameras(scene[0])
     n = len(cams[0][0])
-    fmt = _fmt(w, h, QUARTER)
+    fmt = sup.fmt_of(w, h, QUARTER)
     frame = w * h * 12
     stride = frame + 20
     worst = 0.0
@@ -231,8 +223,8 @@ def test_a_camera_table_with_a_padded_frame_stride(scene, chunk):
         sc.set_lens(ln)
         origins = np.stack([c[0] for c in cams]).astype(f32)
         axes = np.stack([c[1] for c in cams]).astype(f32)
-        table = CameraTable(n, origins, axes, _device().index)
-        dest = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=_device())
+        table = CameraTable(n, origins, axes, sup.cuda_device().index)
+        dest = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         assert table.render(sc, dest, fmt, frame_bytes=stride) is True
         torch.cuda.synchronize()
         got = dest.cpu().numpy().reshape(3, stride)
@@ -242,11 +234,11 @@ def test_a_camera_table_with_a_padded_frame_stride(scene, chunk):
             worst = max(worst, _check(case, px, lc.expected(case, cam), " frame %d" % k, scale=4.0))
         assert not np.array_equal(got[0, :frame], got[1, :frame]) and not np.array_equal(got[1, :frame], got[2, :frame])
         # host cameras
-        dest2 = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=_device())
+        dest2 = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         fst = fmt._as_struct()
         opts = _lib.NtRenderOpts()
-        opts.device = _device().index
-        stream = torch.cuda.current_stream(_device()).cuda_stream
+        opts.device = sup.cuda_device().index
+        stream = torch.cuda.current_stream(sup.cuda_device()).cuda_stream
         _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(dest2.data_ptr()), stride, 3, origins.ctypes.data_as(_lib.f32p),
                                                       axes.ctypes.data_as(_lib.f32p), C.byref(fst), C.byref(opts), C.c_void_p(stream)))
         torch.cuda.synchronize()
@@ -267,7 +259,7 @@ def test_the_ray_path_gives_the_lens_renders_bytes(scene):
             assert not ln.masked.any()
             v = ln.directions(lc.camera_of(o, q))
             for chans in (fx.RGBF32, fx.RGBX8):
-                fmt = _fmt(w, h, chans)
+                fmt = sup.fmt_of(w, h, chans)
                 sc.set_lens(ln)
                 through = _render(sc, fmt)
                 sc.set_lens(None)
@@ -284,7 +276,7 @@ def test_state(scene):
     render on the same scene and stream is right (the hit and `checked` scratch is shared); the abort word on the device path"""
     import torch
     w, h = lc.W, lc.H
-    fmt = _fmt(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     with pytest.MonkeyPatch.context() as mp:
         sc = lc.scene(scene, mp)
         plain = _render(sc, fmt)
@@ -300,7 +292,7 @@ def test_state(scene):
         sc.set_lens(big)
         with pytest.raises(ValueError, match="the lens is for 64 x 48 pixels"):
             _render(sc, fmt)
-        big_img = _render(sc, _fmt(64, 48, fx.RGBF32))
+        big_img = _render(sc, sup.fmt_of(64, 48, fx.RGBF32))
         _check(scene + ("",), _floats(big_img, 64, 48), _expected_for(scene, big), " 64x48")
         sc.set_lens(ln)
         assert np.array_equal(_render(sc, fmt), through)
@@ -308,7 +300,7 @@ def test_state(scene):
         assert np.array_equal(_render(sc, fmt), plain)
         # the abort word, raised before the call: nothing is written; lowered: the lens render's bytes
         sc.set_lens(ln)
-        dev = _device()
+        dev = sup.cuda_device()
         word = torch.ones(1, dtype=torch.int32, device=dev)
         dest = torch.full((h, fmt.pitch), 0xab, dtype=torch.uint8, device=dev)
         fst = fmt._as_struct()
@@ -332,11 +324,11 @@ def test_state(scene):
 def test_refusals_draw_nothing(scene):
     import torch
     w, h = lc.W, lc.H
-    fmt = _fmt(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     with pytest.MonkeyPatch.context() as mp:
         sc = lc.scene(scene, mp)
         sc.set_lens(lc.lens_at("fisheye", w, h))
-        dest = torch.full((h, fmt.pitch), 0xab, dtype=torch.uint8, device=_device())
+        dest = torch.full((h, fmt.pitch), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         r = ntracer_amd.BlockingRenderer()
         sc.set_supersampling(2)
         with pytest.raises(NotImplementedError, match="supersampling"):
@@ -354,7 +346,7 @@ def test_refusals_draw_nothing(scene):
             with pytest.raises(NotImplementedError, match="lens"):
                 sc.primary_hits(w, h)
         with pytest.raises(ValueError, match="the lens is for"):
-            r.render(torch.zeros((h, 4 * (w + 1)), dtype=torch.uint8, device=_device()), _fmt(w + 1, h, fx.RGBX8), sc)
+            r.render(torch.zeros((h, 4 * (w + 1)), dtype=torch.uint8, device=sup.cuda_device()), sup.fmt_of(w + 1, h, fx.RGBX8), sc)
         torch.cuda.synchronize()
         assert bool((dest == 0xab).all())
         # the ray entry points ignore the lens

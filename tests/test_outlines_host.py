@@ -18,10 +18,10 @@ import ntracer_amd
 import outline_cases as oc
 import ray_color_cases as rc
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
 PLAIN = [("cell120_n4", {}), ("cell120_n4", {"NTRACER_STRICT_REFERENCE": "1"}), ("cell600_n4", {}), ("orthoplex5_n5", {})]
 SCALAR = [("simplex10_n10", {})]
@@ -44,22 +44,6 @@ OUTLINE_ROUTES = [
     ("outline_apply", [("feature5_n5", "")]),
 ]
 RENDER_ROWS = ("outline_shade<N,false,false>", "outline_shade<N,true,false>", "outline_shade<N,true,true>", "outline_apply")
-
-
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
 
 
 def _traits(n, flat, params, env):
@@ -94,12 +78,12 @@ def _render_route(name, variant):
 
 
 def test_every_outline_launch_has_a_row_and_every_row_a_gpu_case():
-    var = _read("nt_var.hip")
-    launched = _launches(_body(_read("nt_outline.hpp"), "int launch_outline_fixed("))
+    var = sup.source("nt_var.hip")
+    launched = sup.launches(sup.function_body(sup.source("nt_outline.hpp"), "int launch_outline_fixed("))
     assert len(launched) == 8
     for head in ("int nt_launch_outline(", "int nt_launch_outline_mask(", "static int nt_launch_outline_fixed(", "int nt_launch_outline_mark(",
                  "int nt_launch_outline_apply("):
-        launched |= _launches(_body(var, head))
+        launched |= sup.launches(sup.function_body(var, head))
     rows = [k for k, _ in OUTLINE_ROUTES]
     assert len(rows) == len(set(rows)) == 10
     assert set(rows) == launched, (sorted(launched - set(rows)), sorted(set(rows) - launched))
@@ -119,29 +103,29 @@ def test_every_outline_launch_has_a_row_and_every_row_a_gpu_case():
         assert _mask_routes(name, env) <= set(rows), (name, env)
     assert {_render_route(*r) for r in oc.RENDERED} == set(RENDER_ROWS)
     # the rule above is enqueue_outlines' own: composite_route's answer, no term of its own, no getenv of its own
-    api = _read("nt_api.cpp")
-    rule, enq = _body(api, "CompositeRoute composite_route("), _body(api, "int enqueue_outlines(")
+    api = sup.source("nt_api.cpp")
+    rule, enq = sup.function_body(api, "CompositeRoute composite_route("), sup.function_body(api, "int enqueue_outlines(")
     assert "r.packet_walk = !r.faithful && !r.var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32;" in rule
     assert "const bool fast = composite_route(s, sw).packet_walk;" in enq and "all_opaque" not in enq and "getenv" not in enq
     for name in ("nt_outline.hpp", "nt_inst_outline.hip"):
-        assert "getenv" not in _read(name)
+        assert "getenv" not in sup.source(name)
     # the outline dispatch stands in front of the ambient-occlusion one, and the check in front of ambient occlusion's
-    body = _body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
+    body = sup.function_body(api, "int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {")
     assert 0 < body.index("return enqueue_outlines(") < body.index("return enqueue_ao(")
     # (render_checks walks the table of the settings, outlines above ambient occlusion: of the two the outlines refuse, as
     # tests/test_view_setting_refusals.py finds of the library)
     import view_setting_refusals as vr
     assert vr.RENDER_REFUSALS["outlines", "ao"] == "outlines are not available while ambient occlusion is on"
-    assert ("ao", "outlines") not in vr.RENDER_REFUSALS and "kViewSettings" in _body(api, "int render_checks(")
+    assert ("ao", "outlines") not in vr.RENDER_REFUSALS and "kViewSettings" in sup.function_body(api, "int render_checks(")
     # the pair rule is written once
-    assert len(re.findall(r"int outline_pair\(", _read("nt_outline.hpp"))) == 1 and "outline_pair(" in var
-    assert "NT_DEV_OUTLINE_CREASE" not in var and "c * c <" not in _body(var, "void outline_mark(")
+    assert len(re.findall(r"int outline_pair\(", sup.source("nt_outline.hpp"))) == 1 and "outline_pair(" in var
+    assert "NT_DEV_OUTLINE_CREASE" not in var and "c * c <" not in sup.function_body(var, "void outline_mark(")
     # the new launches stay out of the render, query, hits, lens and ambient-occlusion launchers
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("),
                       ("nt_query.hpp", "int launch_query_fixed("), ("nt_var.hip", "int nt_launch_query("),
                       ("nt_hits.hpp", "int launch_hits_fixed("), ("nt_var.hip", "int nt_launch_hits("),
                       ("nt_lens.hpp", "int launch_lens_fixed("), ("nt_ao.hpp", "int launch_ao_fixed("), ("nt_var.hip", "int nt_launch_ao(")):
-        assert not any(k.startswith("outline_") for k in _launches(_body(_read(src), head))), head
+        assert not any(k.startswith("outline_") for k in sup.launches(sup.function_body(sup.source(src), head))), head
 
 
 # ------------------------------------------------------------------ the conditions that keep the GPU tests from being vacuous
@@ -298,10 +282,6 @@ def test_the_setting_round_trips_and_a_refused_set_leaves_it_as_it_was():
     assert box.outlines is None
 
 
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_mask_forms_validate_before_they_touch_a_device():
     L = _lib.lib()
     sc, n = _scene()
@@ -352,7 +332,7 @@ def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device
     sc, n = _scene()
     sc.set_outlines()
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))

@@ -15,6 +15,7 @@ import pytest
 import fixtures as fx
 import oracle_binding as ob
 import parallel_cases as pc
+import support as sup
 import ntracer_amd
 from ntracer_amd import _lib
 from ntracer_amd.render import CameraTable
@@ -28,15 +29,6 @@ RGB24 = [(8, 1, 0, 0), (8, 0, 1, 0), (8, 0, 0, 1)]
 # comparison of clamped colours would pass on white.  A quarter is exact in fp32, so nothing is lost: got * 4 is the colour (five
 # pixels of the lit 600-cell exceed 4, up to 4.18, and are compared at the clamp).
 QUARTER = [(32, 0.25, 0, 0, 0, True), (32, 0, 0.25, 0, 0, True), (32, 0, 0, 0.25, 0, True)]
-
-
-def _device():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _fmt(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
 
 
 def _bpp(chans):
@@ -85,9 +77,9 @@ def _against_the_oracle(case, sc, want, what=""):
     """the case in three formats: a quarter-scale fp32 (unclamped colours), plain fp32 x 3 and RGBX8"""
     w, h = pc.W, pc.H
     assert (want.max(axis=1) >= 4.0).mean() < 0.01             # (the lit 600-cell: 5 of 1 073 pixels reach the quarter format's clamp)
-    worst = _check(case, _floats(_render(sc, _fmt(w, h, QUARTER)), w, h), want, what, scale=4.0)
-    worst = max(worst, _check(case, _floats(_render(sc, _fmt(w, h, fx.RGBF32)), w, h), want, what))
-    img = _render(sc, _fmt(w, h, fx.RGBX8))
+    worst = _check(case, _floats(_render(sc, sup.fmt_of(w, h, QUARTER)), w, h), want, what, scale=4.0)
+    worst = max(worst, _check(case, _floats(_render(sc, sup.fmt_of(w, h, fx.RGBF32)), w, h), want, what))
+    img = _render(sc, sup.fmt_of(w, h, fx.RGBX8))
     diff = np.abs(img.astype(int) - _packed(want, fx.RGBX8, False, w, h).astype(int)).max()
     assert diff <= (0 if pc.is_box(case[0]) else 1), (pc.case_id(case), what, int(diff))
     return worst, int(diff)
@@ -133,13 +125,13 @@ def test_shapes_and_formats(scene):
         sc = pc.scene(scene, mp)
         for w, h in SHAPES:
             want = pc.expected(scene, size=(w, h))
-            worst = max(worst, _check(scene, _floats(_render(sc, _fmt(w, h, QUARTER)), w, h), want, " %dx%d" % (w, h), scale=4.0))
+            worst = max(worst, _check(scene, _floats(_render(sc, sup.fmt_of(w, h, QUARTER)), w, h), want, " %dx%d" % (w, h), scale=4.0))
         for (w, h), chans, pad, rev in (((9, 17), RGB24, 1, False), ((37, 29), RGB24, 0, True), ((37, 29), RGB24, 1, False),
                                         ((9, 17), fx.RGBX8, 0, True), ((37, 29), fx.RGB16, 7, False), ((9, 17), fx.RGBF32, 12, True)):
             want = pc.expected(scene, size=(w, h))
             bpp = _bpp(chans)
             pitch = w * bpp + pad
-            fmt = _fmt(w, h, chans, pitch if pad else 0, rev)
+            fmt = sup.fmt_of(w, h, chans, pitch if pad else 0, rev)
             buf = bytearray(b"\xab" * (pitch * h))
             assert ntracer_amd.BlockingRenderer().render(buf, fmt, sc) is True
             img = np.frombuffer(bytes(buf), np.uint8).reshape(h, pitch)
@@ -163,13 +155,13 @@ def test_the_device_path_leaves_the_bytes_outside_the_image(scene):
         for chans in (fx.RGBF32, fx.RGBX8, RGB24):
             bpp = _bpp(chans)
             pitch = w * bpp + 8
-            fmt = _fmt(w, h, chans, pitch)
-            dest = torch.full((h + 3, pitch), 0xab, dtype=torch.uint8, device=_device())
+            fmt = sup.fmt_of(w, h, chans, pitch)
+            dest = torch.full((h + 3, pitch), 0xab, dtype=torch.uint8, device=sup.cuda_device())
             assert ntracer_amd.BlockingRenderer().render(dest, fmt, sc) is True
             torch.cuda.synchronize()
             got = dest.cpu().numpy()
             assert (got[h:] == 0xab).all() and (got[:h, w * bpp:] == 0xab).all(), chans[0]
-            assert np.array_equal(got[:h, :w * bpp], _render(sc, _fmt(w, h, chans))), chans[0]       # the host path: the same bytes
+            assert np.array_equal(got[:h, :w * bpp], _render(sc, sup.fmt_of(w, h, chans))), chans[0]       # the host path: the same bytes
 
 
 def _three_cameras(name):
@@ -186,7 +178,7 @@ def test_a_camera_table_with_a_padded_frame_stride(scene, chunk):
     w, h = pc.W, pc.H
     cams = _three_cameras(scene[0])
     n = len(cams[0][0])
-    fmt = _fmt(w, h, QUARTER)
+    fmt = sup.fmt_of(w, h, QUARTER)
     frame = w * h * 12
     stride = frame + 20
     worst = 0.0
@@ -196,8 +188,8 @@ def test_a_camera_table_with_a_padded_frame_stride(scene, chunk):
             mp.setenv("NTRACER_CHUNK_FRAMES", chunk)
         origins = np.stack([c[0] for c in cams]).astype(f32)
         axes = np.stack([c[1] for c in cams]).astype(f32)
-        table = CameraTable(n, origins, axes, _device().index)
-        dest = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=_device())
+        table = CameraTable(n, origins, axes, sup.cuda_device().index)
+        dest = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         assert table.render(sc, dest, fmt, frame_bytes=stride) is True
         torch.cuda.synchronize()
         got = dest.cpu().numpy().reshape(3, stride)
@@ -207,11 +199,11 @@ def test_a_camera_table_with_a_padded_frame_stride(scene, chunk):
             worst = max(worst, _check(scene, px, pc.expected(scene, cam), " frame %d" % k, scale=4.0))
         assert not np.array_equal(got[0, :frame], got[1, :frame]) and not np.array_equal(got[1, :frame], got[2, :frame])
         # host cameras
-        dest2 = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=_device())
+        dest2 = torch.full((3 * stride,), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         fst = fmt._as_struct()
         opts = _lib.NtRenderOpts()
-        opts.device = _device().index
-        stream = torch.cuda.current_stream(_device()).cuda_stream
+        opts.device = sup.cuda_device().index
+        stream = torch.cuda.current_stream(sup.cuda_device()).cuda_stream
         _lib.check(_lib.lib().nt_render_frames_device(sc._handle, C.c_void_p(dest2.data_ptr()), stride, 3, origins.ctypes.data_as(_lib.f32p),
                                                       axes.ctypes.data_as(_lib.f32p), C.byref(fst), C.byref(opts), C.c_void_p(stream)))
         torch.cuda.synchronize()
@@ -231,7 +223,7 @@ def test_the_ray_path_gives_the_parallel_renders_bytes(scene):
         assert np.array_equal(org.view(np.uint32), want_o.view(np.uint32)) and np.array_equal(fwd, want_f)
         rays = (org, np.broadcast_to(fwd, org.shape))                       # (the ray entry points take a direction a ray)
         for chans in (fx.RGBF32, fx.RGBX8):
-            fmt = _fmt(w, h, chans)
+            fmt = sup.fmt_of(w, h, chans)
             through = _render(sc, fmt)
             buf = bytearray(fmt.pitch * h)
             assert sc.render_rays(buf, fmt, *rays) is True                  # (the ray entry points ignore the setting)
@@ -249,7 +241,7 @@ def test_state(scene):
     and stream is right (the hit and `checked` scratch is shared); the abort word on the device path"""
     import torch
     w, h = pc.W, pc.H
-    fmt = _fmt(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     with pytest.MonkeyPatch.context() as mp:
         sc = pc.scene(scene, mp)
         sc.set_parallel_projection(None)
@@ -265,7 +257,7 @@ def test_state(scene):
         sc.set_parallel_projection(pc.half_width(scene[0]))
         assert np.array_equal(_render(sc, fmt), through)
         # the abort word, raised before the call: nothing is written; lowered: the parallel render's bytes
-        dev = _device()
+        dev = sup.cuda_device()
         word = torch.ones(1, dtype=torch.int32, device=dev)
         dest = torch.full((h, fmt.pitch), 0xab, dtype=torch.uint8, device=dev)
         fst = fmt._as_struct()
@@ -291,10 +283,10 @@ def test_state(scene):
 def test_refusals_draw_nothing(scene):
     import torch
     w, h = pc.W, pc.H
-    fmt = _fmt(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     with pytest.MonkeyPatch.context() as mp:
         sc = pc.scene(scene, mp)
-        dest = torch.full((h, fmt.pitch), 0xab, dtype=torch.uint8, device=_device())
+        dest = torch.full((h, fmt.pitch), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         r = ntracer_amd.BlockingRenderer()
         sc.set_supersampling(2)
         with pytest.raises(NotImplementedError, match="supersampling"):

@@ -11,30 +11,14 @@ import pytest
 
 import parallel_cases as pc
 import ray_query_cases as rq
+import support as sup
 import ntracer_amd
 from ntracer_amd import Channel, ImageFormat, Lens, _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 SYMBOLS = ("nt_scene_set_parallel", "nt_scene_get_parallel")
 f32 = np.float32
 RGBX8 = [Channel(8, 1, 0, 0), Channel(8, 0, 1, 0), Channel(8, 0, 0, 1), Channel(8, 0, 0, 0)]
-
-
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
 
 
 def test_the_header_declares_and_the_library_exports_the_entry_points():
@@ -56,30 +40,30 @@ def test_the_header_declares_and_the_library_exports_the_entry_points():
 
 
 def test_every_parallel_launch_is_reached_by_a_case():
-    hpp, var = _read("nt_parallel.hpp"), _read("nt_var.hip")
-    packet = _launches(_body(hpp, "int launch_parallel_fixed("))
-    helper = _launches(_body(var, "int nt_launch_parallel_expand("))
+    hpp, var = sup.source("nt_parallel.hpp"), sup.source("nt_var.hip")
+    packet = sup.launches(sup.function_body(hpp, "int launch_parallel_fixed("))
+    helper = sup.launches(sup.function_body(var, "int nt_launch_parallel_expand("))
     assert packet == {"parallel_packet<N,32,true>", "parallel_packet<N,32,false>",
                       "parallel_shade<N,false,false>", "parallel_shade<N,true,true>", "parallel_shade<N,true,false>"}, sorted(packet)
     assert helper == {"parallel_expand"}, sorted(helper)
-    assert not _launches(_body(var, "int nt_launch_parallel("))       # the dispatcher launches through the fixed-n units alone
+    assert not sup.launches(sup.function_body(var, "int nt_launch_parallel("))       # the dispatcher launches through the fixed-n units alone
     reached = set()
     for case in pc.CASES:
         reached |= set(pc.route(case))
     missing = (packet | helper) - reached
     assert not missing, sorted(missing)
     # the ray route ends in nt_launch_rays: every kernel it can launch is reached under the projection as well
-    rays = (_launches(_body(_read("nt_rays.hpp"), "int launch_rays_fixed(")) | _launches(_body(_read("nt_rays.hpp"), "int launch_rays_box_fixed(")) |
-            _launches(_body(var, "int nt_launch_rays(")))
+    rays = (sup.launches(sup.function_body(sup.source("nt_rays.hpp"), "int launch_rays_fixed(")) | sup.launches(sup.function_body(sup.source("nt_rays.hpp"), "int launch_rays_box_fixed(")) |
+            sup.launches(sup.function_body(var, "int nt_launch_rays(")))
     assert len(rays) >= 10 and rays <= reached, sorted(rays - reached)
     # the new kernels stay out of the render and lens launchers
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_lens.hpp", "int launch_lens_fixed("),
                       ("nt_var.hip", "int nt_launch_composite("), ("nt_var.hip", "int nt_launch_box("), ("nt_var.hip", "int nt_launch_rays(")):
-        assert not any("parallel" in k for k in _launches(_body(_read(src), head)))
+        assert not any("parallel" in k for k in sup.launches(sup.function_body(sup.source(src), head)))
     assert "getenv" not in hpp
     # what enqueue_parallel sends to the packet walk is what enqueue_lens sends to its own: pinned text of the conditions, which
     # are composite_route's -- enqueue_parallel asks it and keeps no terms of its own
-    rule, api = _body(_read("nt_api.cpp"), "CompositeRoute composite_route("), _body(_read("nt_api.cpp"), "int enqueue_parallel(")
+    rule, api = sup.function_body(sup.source("nt_api.cpp"), "CompositeRoute composite_route("), sup.function_body(sup.source("nt_api.cpp"), "int enqueue_parallel(")
     assert "r.packet_walk = !r.faithful && !r.var && sw.composite_kernel == 0 && std::max(s->depth + 1, 2) <= 32;" in rule
     assert "r.var = s->n > NT_MAX_FIXED_DIM || sw.force_var;" in rule
     assert "s->composite && composite_route(s, sw).packet_walk" in api and "all_opaque" not in api

@@ -17,6 +17,7 @@ import fixtures as fx
 import oracle_binding as ob
 import primary_hit_cases as ph
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import Material, _lib, render, tracern
 from ntracer_amd.wrapper import NTracer
 
@@ -32,10 +33,7 @@ bits = lambda a: np.ascontiguousarray(a).view(np.int32)
 
 def _scene(case, mp, k=0):
     name, env = case
-    for key in ph.SWITCHES:
-        mp.delenv(key, raising=False)
-    for key, v in env.items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, ph.SWITCHES, env)
     g, n, flat = rq.scene(name)
     sc = tracern.CompositeScene.from_flat(n, flat)
     sc.set_fov(ph.fov_of(name))
@@ -264,8 +262,7 @@ def test_intersection_answers_with_the_objects_put_in_the_leaves():
     t0 = ph.aabb_distance(flat["aabb_start"], flat["aabb_end"], origin, d)
     orc = rq.Oracle(3, flat, False, True)
     with pytest.MonkeyPatch.context() as mp:
-        for key in ph.SWITCHES:
-            mp.delenv(key, raising=False)
+        sup.set_switches(mp, ph.SWITCHES, {})
         got = scene.primary_hits(w, h, normals=True)
         seen = set()
         for y in range(h):

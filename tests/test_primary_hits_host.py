@@ -6,7 +6,6 @@ nt_launch_hits (nt_var.hip) has a row in HITS_ROUTES, and every row names (scene
 tests/test_primary_hits_gpu.py runs."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
@@ -16,10 +15,9 @@ import fixtures as fx
 import oracle_binding as ob
 import primary_hit_cases as ph
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
 PACKET_LEAN = [("cell600_n4", {}), ("cell600_n4", {"NTRACER_STRICT_REFERENCE": "1"}), ("simplex7_n7", {})]
 PACKET_SCAL = [("simplex10_n10", {})]
@@ -38,22 +36,6 @@ HITS_ROUTES = [
     ("hits_closest_var_t<true>", [("feature5_n5", {"NTRACER_FORCE_VAR": "1"}), ("feature11_n11", {}), ("lit12_n12", {}), ("feature16_n16", {})]),
     ("hits_closest_var_t<false>", [("feature11_n11", {"NTRACER_CLEAN_NORMALS": "1"})]),
 ]
-
-
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
 
 
 def _depth(flat):
@@ -87,7 +69,7 @@ def _routes(name, env):
 
 
 def test_every_hits_launch_has_a_row_and_every_row_a_gpu_case():
-    launched = _launches(_body(_read("nt_hits.hpp"), "int launch_hits_fixed(")) | _launches(_body(_read("nt_var.hip"), "int nt_launch_hits("))
+    launched = sup.launches(sup.function_body(sup.source("nt_hits.hpp"), "int launch_hits_fixed(")) | sup.launches(sup.function_body(sup.source("nt_var.hip"), "int nt_launch_hits("))
     rows = [k for k, _ in HITS_ROUTES]
     assert len(rows) == len(set(rows)) == 12
     assert set(rows) == launched, (sorted(launched - set(rows)), sorted(set(rows) - launched))
@@ -103,10 +85,10 @@ def test_every_hits_launch_has_a_row_and_every_row_a_gpu_case():
     # the launches stay out of the render and query launchers, whose every launch wants a row of their own matrices
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("),
                       ("nt_query.hpp", "int launch_query_fixed("), ("nt_var.hip", "int nt_launch_query(")):
-        names = _launches(_body(_read(src), head))
+        names = sup.launches(sup.function_body(sup.source(src), head))
         assert not any(k.startswith("hits_") or re.match(r"composite_packet<N,32,\w+,\w+,true>", k) for k in names), (head, names)
     # and route on the switches read_switches already reads: no getenv of their own
-    assert "getenv" not in _read("nt_hits.hpp") and "getenv" not in _body(_read("nt_var.hip"), "int nt_launch_hits(")
+    assert "getenv" not in sup.source("nt_hits.hpp") and "getenv" not in sup.function_body(sup.source("nt_var.hip"), "int nt_launch_hits(")
 
 
 @pytest.mark.parametrize("size", [(37, 21), (64, 48)], ids=lambda s: "%dx%d" % s)

@@ -16,6 +16,7 @@ import fixtures as fx
 import oracle_binding as ob
 import ray_color_cases as rc
 import ray_query_cases as rq
+import support as sup
 import ntracer_amd
 from ntracer_amd import _lib, tracern
 
@@ -34,32 +35,20 @@ DEVICE_BOX = (6, 24, 25, 40)
 
 def _scene(case, mp):
     name, env, variant = case
-    for k in rc.SWITCHES:
-        mp.delenv(k, raising=False)
-    for k, v in env.items():
-        mp.setenv(k, v)
+    sup.set_switches(mp, rc.SWITCHES, env)
     n, flat, params = rc.case_scene(case)
     sc = tracern.CompositeScene.from_flat(n, flat)
     sc.set_params_flat(params)
     return sc
 
 
-def _device():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _dev(a):
     import torch
-    return torch.from_numpy(np.array(a)).to(_device())
+    return torch.from_numpy(np.array(a)).to(sup.cuda_device())
 
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _fmt(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
 
 
 @pytest.mark.parametrize("case", rc.CASES, ids=rc.case_id)
@@ -221,14 +210,14 @@ def test_render_rays_of_a_box_scene_equals_the_oracles_render(n):
     for chans, pad, rev in BOX_FORMATS:
         bpp = sum(c[0] for c in chans) // 8
         pitch = w * bpp + pad
-        fmt = _fmt(w, h, chans, pitch if pad else 0, rev)
+        fmt = sup.fmt_of(w, h, chans, pitch if pad else 0, rev)
         ref = orc.render(w, h, chans, pitch=pitch if pad else 0, reversed_=rev)
         buf = bytearray(pitch * h)
         assert sc.render_rays(buf, fmt, o, v) is True
         got = np.frombuffer(bytes(buf), np.uint8).reshape(h, pitch)
         assert np.array_equal(got, ref), (n, chans, pad, rev, int((got != ref).sum()))
         # the device form: the padding keeps the caller's bytes
-        dest = torch.full((h, pitch), 0xab, dtype=torch.uint8, device=_device())
+        dest = torch.full((h, pitch), 0xab, dtype=torch.uint8, device=sup.cuda_device())
         assert sc.render_rays(dest, fmt, _dev(o), _dev(v)) is True
         torch.cuda.synchronize()
         dgot = dest.cpu().numpy()
@@ -255,7 +244,7 @@ def test_render_rays_of_a_composite_scene_packs_its_own_colours():
         for chans, pad, rev in ((fx.RGBX8, 0, False), (fx.RGB16, 7, True)):
             bpp = sum(c[0] for c in chans) // 8
             pitch = w * bpp + pad
-            fmt = _fmt(w, h, chans, pitch if pad else 0, rev)
+            fmt = sup.fmt_of(w, h, chans, pitch if pad else 0, rev)
             buf = bytearray(pitch * h)
             assert sc.render_rays(buf, fmt, o, v) is True
             got = np.frombuffer(bytes(buf), np.uint8).reshape(h, pitch)
@@ -268,21 +257,21 @@ def test_render_rays_of_a_composite_scene_packs_its_own_colours():
             else:
                 words = lambda a: np.ascontiguousarray(a[:, :w * bpp]).view("<u2" if rev else ">u2").astype(int)
                 assert np.abs(words(got) - words(ref)).max() <= 1
-            dest = torch.zeros((h, pitch), dtype=torch.uint8, device=_device())
+            dest = torch.zeros((h, pitch), dtype=torch.uint8, device=sup.cuda_device())
             assert sc.render_rays(dest, fmt, _dev(o), _dev(v)) is True
             torch.cuda.synchronize()
             assert np.array_equal(dest.cpu().numpy(), got)
         with pytest.raises(ValueError):
-            sc.render_rays(bytearray(w * h * 4), _fmt(w, h, fx.RGBX8), _dev(o), _dev(v))       # host bytes, device rays
+            sc.render_rays(bytearray(w * h * 4), sup.fmt_of(w, h, fx.RGBX8), _dev(o), _dev(v))       # host bytes, device rays
 
 
 def test_abort_word_raised_before_the_call_nothing_is_written():
     """the pattern of test_abort_word_on_the_batched_device_path: raised, no block writes; lowered, the same call answers"""
     import torch
-    dev = _device()
+    dev = sup.cuda_device()
     word = torch.ones(1, dtype=torch.int32, device=dev)
     w, h = 50, 20
-    fmt = _fmt(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     fst = fmt._as_struct()
     stream = torch.cuda.current_stream(dev).cuda_stream
     L = _lib.lib()
@@ -330,7 +319,7 @@ def test_a_render_after_a_ray_call_still_gives_the_golden_frame(name):
     w, h = int(g["width"]), int(g["height"])
     k = 1
     f = int(g["frames"][k])
-    fmt = _fmt(w, h, fx.RGBF32)
+    fmt = sup.fmt_of(w, h, fx.RGBF32)
     r = rc.rays(case)
     with pytest.MonkeyPatch.context() as mp:
         sc = _scene(case, mp)

@@ -15,33 +15,17 @@ import fixtures as fx
 import oracle_binding as ob
 import ray_color_cases as rc
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import Channel, ImageFormat, _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 SYMBOLS = ("nt_ray_colors", "nt_ray_colors_device", "nt_render_rays", "nt_render_rays_device")
 
 
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
-
-
 def test_every_ray_launch_is_reached_by_a_case():
-    hpp, var = _read("nt_rays.hpp"), _read("nt_var.hip")
-    launched = (_launches(_body(hpp, "int launch_rays_fixed(")) | _launches(_body(hpp, "int launch_rays_box_fixed(")) |
-                _launches(_body(var, "int nt_launch_rays(")))
+    hpp, var = sup.source("nt_rays.hpp"), sup.source("nt_var.hip")
+    launched = (sup.launches(sup.function_body(hpp, "int launch_rays_fixed(")) | sup.launches(sup.function_body(hpp, "int launch_rays_box_fixed(")) |
+                sup.launches(sup.function_body(var, "int nt_launch_rays(")))
     assert len(launched) >= 10, sorted(launched)             # the scan still finds the launches
     reached = {rc.route(case) for case in rc.CASES} | {rc.box_route(n) for n in rc.BOX_DIMS}
     assert reached == launched, ("launched without a case: %s; routes nothing launches: %s"
@@ -52,9 +36,9 @@ def test_every_ray_launch_is_reached_by_a_case():
     # the launches stay out of the render launchers, whose every launch wants a row of the render matrix
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite("),
                       ("nt_var.hip", "int nt_launch_box(")):
-        assert not any(k.startswith("rays_") for k in _launches(_body(_read(src), head)))
+        assert not any(k.startswith("rays_") for k in sup.launches(sup.function_body(sup.source(src), head)))
     # and route on the switches read_switches already reads: no getenv of their own
-    assert "getenv" not in hpp and "getenv" not in _body(var, "int nt_launch_rays(")
+    assert "getenv" not in hpp and "getenv" not in sup.function_body(var, "int nt_launch_rays(")
 
 
 def test_the_header_declares_and_the_library_exports_the_entry_points():

@@ -19,6 +19,7 @@ import pytest
 import fixtures as fx
 import oracle_binding as ob
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.wrapper import NTracer
 
@@ -38,10 +39,7 @@ MIN_BLOCKED = {"cell600_n4": 10, "feature5_n5": 10, "lit12_n12": 10}
 
 def _scene(case, mp):
     name, env = case
-    for k in QUERY_SWITCHES:
-        mp.delenv(k, raising=False)
-    for k, v in env.items():
-        mp.setenv(k, v)
+    sup.set_switches(mp, QUERY_SWITCHES, env)
     g, n, flat = rq.scene(name)
     return tracern.CompositeScene.from_flat(n, flat)
 

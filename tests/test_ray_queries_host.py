@@ -7,18 +7,15 @@ pairs that tests/test_ray_queries_gpu.py runs."""
 import ctypes as C
 import importlib
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
 import ray_query_cases as rq
+import support as sup
 from ntracer_amd import Material, _lib, compat, tracern
 from ntracer_amd.wrapper import NTracer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ntracer_amd", "csrc")
 
 # kernel instantiation as its hipLaunchKernelGGL spells it (spaces dropped) -> cases of ray_query_cases.CASES that reach it, and
 # through which query.  Lean: opaque, no Solids (cell600_n4: batches alone; simplex10_n10: loose triangles too).
@@ -41,22 +38,6 @@ QUERY_ROUTES = [
 ]
 
 
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
-def _launches(body):
-    """the regular expression of tests/test_composite_routes.py"""
-    names = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", body)
-    return {re.sub(r"\s+", "", n) for n in names}
-
-
 def _route(name, env, query):
     """the kernel a (scene, switches, query) lands on, by the rules of query_enqueue (nt_api.cpp) and the two launchers"""
     g, n, flat = rq.scene(name)
@@ -75,7 +56,7 @@ def _route(name, env, query):
 
 
 def test_every_query_launch_has_a_row_and_every_row_a_gpu_case():
-    launched = _launches(_body(_read("nt_query.hpp"), "int launch_query_fixed(")) | _launches(_body(_read("nt_var.hip"), "int nt_launch_query("))
+    launched = sup.launches(sup.function_body(sup.source("nt_query.hpp"), "int launch_query_fixed(")) | sup.launches(sup.function_body(sup.source("nt_var.hip"), "int nt_launch_query("))
     assert len(launched) >= 12, sorted(launched)
     rows = [k for k, _ in QUERY_ROUTES]
     assert len(rows) == len(set(rows))
@@ -88,9 +69,9 @@ def test_every_query_launch_has_a_row_and_every_row_a_gpu_case():
             assert _route(name, env, query) == kernel, (kernel, name, env, query, _route(name, env, query))
     # the launches stay out of the render launchers, whose every launch wants a row of the render matrix
     for src, head in (("nt_composite.hpp", "int launch_composite_fixed("), ("nt_var.hip", "int nt_launch_composite(")):
-        assert not any(k.startswith("query_") for k in _launches(_body(_read(src), head)))
+        assert not any(k.startswith("query_") for k in sup.launches(sup.function_body(sup.source(src), head)))
     # and route on the switches read_switches already reads: no getenv of their own
-    assert "getenv" not in _read("nt_query.hpp") and "getenv" not in _body(_read("nt_var.hip"), "int nt_launch_query(")
+    assert "getenv" not in sup.source("nt_query.hpp") and "getenv" not in sup.function_body(sup.source("nt_var.hip"), "int nt_launch_query(")
 
 
 def test_the_python_surface_is_the_references():

@@ -11,6 +11,7 @@ import pytest
 import fixtures as fx
 import ntracer_amd
 import solid_cases as sc
+import support as sup
 from ntracer_amd import _lib, tracern
 
 pytestmark = pytest.mark.gpu
@@ -31,10 +32,7 @@ def _label(name, n, kind, env, cam=None):
 
 def _scene(name, n, kind, env, mp, cam=0):
     """the scene with the switches set before it is made"""
-    for k in sc.SWITCHES:
-        mp.delenv(k, raising=False)
-    for k, v in env.items():
-        mp.setenv(k, v)
+    sup.set_switches(mp, sc.SWITCHES, env)
     s = tracern.CompositeScene.from_flat(n, sc.scene_flat(name, n, "transparent" if kind == "default" else kind))
     if kind not in ("default", "opaque"):
         s.set_params_flat(sc.params(name, n, kind))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import solid_cases as sc
+import support as sup
 from ntracer_amd import _lib, builder, tracern
 
 f32 = np.float32
@@ -204,11 +205,6 @@ def test_orientations_are_what_their_names_say():
 
 
 # ------------------------------------------------------------------ 5. the route table
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
-
-
 CALL = re.compile(r"\b(solid_intersects_marks|solid_intersects|solid_marks_var|solid_var)\s*(<[^<>]*>)?\s*\(")
 HEAD = re.compile(r"^(?:__device__|__global__).*?\b(?:void|float|bool|int|Color3)\s+([A-Za-z_]\w*)\s*\(", re.M)
 
@@ -217,7 +213,7 @@ def _sites():
     """{enclosing function: file} of every call of the four functions in csrc (their own definitions left out)"""
     out = {}
     for name in sorted(os.listdir(CSRC)):
-        src = _read(name)
+        src = sup.source(name)
         heads = [(m.start(), m.group(1)) for m in HEAD.finditer(src)]
         for m in CALL.finditer(src):
             line_start = src.rfind("\n", 0, m.start()) + 1
@@ -243,7 +239,7 @@ def test_every_call_site_of_the_solid_functions_is_in_a_family_the_route_table_r
 def test_every_row_is_a_kernel_the_sources_launch_and_every_solid_capable_launch_has_a_row():
     launched = set()
     for name in sorted(os.listdir(CSRC)):
-        for k in re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", _read(name)):
+        for k in re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:\s*<[^<>]*>)?)", sup.source(name)):
             launched.add(re.sub(r"\s+", "", k))
     rows = {k for k, _ in sc.ROUTES}
     assert rows <= launched, sorted(rows - launched)

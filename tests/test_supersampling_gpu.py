@@ -13,6 +13,7 @@ import fixtures as fx
 import ntracer_amd
 import oracle_binding as ob
 import ss_expected as sx
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd import distributed as ntd
 from ntracer_amd.render import CameraTable
@@ -26,16 +27,6 @@ RGB565 = [(5, 1, 0, 0), (6, 0, 1, 0), (5, 0, 0, 1)]
 # (name, channels, reversed)
 FORMATS = [("rgbx8", fx.RGBX8, False), ("rgbf32", fx.RGBF32, False), ("rgb24", RGB24, False), ("rgb565", RGB565, False),
            ("rgb16", fx.RGB16, False), ("rgb24-reversed", RGB24, True), ("rgbx8-reversed", fx.RGBX8, True)]
-
-
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene, fmt, **kw):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene, **kw)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
 
 
 def box_cameras(n):
@@ -94,7 +85,7 @@ def test_box_scene_equals_the_oracle_byte_for_byte(n, s):
         assert np.isfinite(mean).all() and mean.min() >= 0.0 and mean.max() <= 1.0
         todo = [("rgbf32", fx.RGBF32, False), packed[(2 * j) % len(packed)], packed[(2 * j + 1) % len(packed)]]
         for name, chans, rev in todo:
-            img = render_host(sc, fmt_of(W, H, chans, rev=rev))
+            img = sup.render_host(sc, sup.fmt_of(W, H, chans, rev=rev))
             want = sx.pack(mean, chans, rev)
             assert np.array_equal(img, want), (n, s, k, name, int((img != want).sum()))
 
@@ -109,7 +100,7 @@ def test_box_scene_other_factors(s, n):
     for k, (name, chans, rev) in ((5, FORMATS[0]), (12, FORMATS[1]), (9, FORMATS[4])):
         o, a = cams[k]
         sc._set_camera_arrays(o, a)
-        img = render_host(sc, fmt_of(W, H, chans, rev=rev))
+        img = sup.render_host(sc, sup.fmt_of(W, H, chans, rev=rev))
         want = sx.expected(ob.OracleScene(n, o, a), W, H, s, chans, rev)
         assert np.array_equal(img, want), (n, s, k, name, int((img != want).sum()))
 
@@ -124,9 +115,9 @@ def test_a_wide_frame_takes_the_aligned_loads_and_an_unaligned_destination_the_b
     sc._set_camera_arrays(o, a)
     mean = sx.mean_colors(ob.OracleScene(n, o, a), w, h, s)
     for name, chans, rev in FORMATS:
-        img = render_host(sc, fmt_of(w, h, chans, rev=rev))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans, rev=rev))
         assert np.array_equal(img, sx.pack(mean, chans, rev)), name
-    fmt = fmt_of(w, h, RGB24, pitch=3 * w + 5)
+    fmt = sup.fmt_of(w, h, RGB24, pitch=3 * w + 5)
     buf = torch.full((fmt.pitch * h + 16,), 0x5C, dtype=torch.uint8, device="cuda")
     dest = buf[1:1 + fmt.pitch * h]
     fst = fmt._as_struct()
@@ -144,29 +135,29 @@ def test_factor_one_is_the_identity():
     n = 6
     o, a = box_cameras(n)[4]
     for chans in (fx.RGBX8, fx.RGBF32, fx.RGB16):
-        fmt = fmt_of(W, H, chans)
+        fmt = sup.fmt_of(W, H, chans)
         plain = tracern.BoxScene(n)
         plain._set_camera_arrays(o, a)
-        want = render_host(plain, fmt)
+        want = sup.render_host(plain, fmt)
         sc = tracern.BoxScene(n)
         sc._set_camera_arrays(o, a)
         sc.set_supersampling(1)
-        assert np.array_equal(render_host(sc, fmt), want)
+        assert np.array_equal(sup.render_host(sc, fmt), want)
         sc.set_supersampling(3)
-        assert not np.array_equal(render_host(sc, fmt), want)
+        assert not np.array_equal(sup.render_host(sc, fmt), want)
         sc.set_supersampling(1)
-        assert np.array_equal(render_host(sc, fmt), want)
+        assert np.array_equal(sup.render_host(sc, fmt), want)
     plain, _, _ = composite("cell600_n4")
     sc, _, _ = composite("cell600_n4")
     for chans in (fx.RGBX8, fx.RGBF32):
-        fmt = fmt_of(160, 90, chans)
-        want = render_host(plain, fmt)
+        fmt = sup.fmt_of(160, 90, chans)
+        want = sup.render_host(plain, fmt)
         sc.set_supersampling(1)
-        assert np.array_equal(render_host(sc, fmt), want)
+        assert np.array_equal(sup.render_host(sc, fmt), want)
         sc.set_supersampling(3)
-        assert not np.array_equal(render_host(sc, fmt), want)
+        assert not np.array_equal(sup.render_host(sc, fmt), want)
         sc.set_supersampling(1)
-        assert np.array_equal(render_host(sc, fmt), want)
+        assert np.array_equal(sup.render_host(sc, fmt), want)
 
 
 # ------------------------------------------------------------------ 3. CompositeScene
@@ -189,7 +180,7 @@ def test_composite_scene_within_the_projects_tolerances_of_the_oracle(name, para
         unlit = sx.mean_colors(composite(name)[1], w, h, s)
         assert np.abs(unlit - mean).max() > 0.05            # the light and its shadows are in the picture
     for chans in (fx.RGBF32, fx.RGBX8):
-        img = render_host(sc, fmt_of(w, h, chans))
+        img = sup.render_host(sc, sup.fmt_of(w, h, chans))
         assert_close_to(img, sx.pack(mean, chans), chans, "%s s=%d" % (name, s))
 
 
@@ -212,11 +203,11 @@ def test_bands_put_together_are_the_whole_frame(which, world, band_rows):
         sc, osc, _ = composite(which)
         sc.set_supersampling(s)
         chans = fx.RGBF32 if world != 3 else fx.RGBX8
-        whole = render_host(sc, fmt_of(w, h, chans))
+        whole = sup.render_host(sc, sup.fmt_of(w, h, chans))
         assert_close_to(whole, sx.expected(osc, w, h, s, chans), chans, which)
     bpp = whole.shape[1] // w
     pad = 20 if band_rows == 8 else 0                     # a pitch larger than W * bpp
-    fmt = fmt_of(w, h, chans, pitch=w * bpp + pad)
+    fmt = sup.fmt_of(w, h, chans, pitch=w * bpp + pad)
     for compact in (True, False):
         seen = np.zeros(h, bool)
         for rank in range(world):
@@ -255,12 +246,12 @@ def test_many_frames_equal_single_renders_whatever_the_chunking(which, scratch_m
         sc, _, g = composite(which)
         cams = [(g["origins"][f], g["axes"][f]) for f in range(0, 8 * nf, 8)]
     sc.set_supersampling(s)
-    fmt = fmt_of(W, H, chans)
+    fmt = sup.fmt_of(W, H, chans)
     assert sc.supersampling_scratch_mb == 1024
     singles = []
     for o, a in cams:
         sc._set_camera_arrays(o, a)
-        singles.append(render_host(sc, fmt))
+        singles.append(sup.render_host(sc, fmt))
     if which == "box6":
         assert np.array_equal(singles[5], sx.expected(ob.OracleScene(n, *cams[5]), W, H, s, chans))
     singles = np.stack(singles)
@@ -289,7 +280,7 @@ def test_many_frames_equal_single_renders_whatever_the_chunking(which, scratch_m
     assert (got[:count, fmt.pitch * H:] == 0x3D).all() and (got[count:] == 0x3D).all()
     # the single render as well, under the same cap
     sc._set_camera_arrays(*cams[7])
-    assert np.array_equal(render_host(sc, fmt), singles[7])
+    assert np.array_equal(sup.render_host(sc, fmt), singles[7])
 
 
 def test_a_supersampled_table_call_is_still_capturable():
@@ -301,7 +292,7 @@ def test_a_supersampled_table_call_is_still_capturable():
     cams = box_cameras(n)[:nf]
     origins = np.ascontiguousarray(np.stack([c[0] for c in cams]), np.float32)
     axes = np.ascontiguousarray(np.stack([c[1] for c in cams]), np.float32)
-    fmt = fmt_of(W, H, fx.RGBX8)
+    fmt = sup.fmt_of(W, H, fx.RGBX8)
     fst = fmt._as_struct()
     sc = tracern.BoxScene(n)
     sc.set_supersampling(s)
@@ -337,7 +328,7 @@ def test_the_drop_in_call_and_the_probes():
     scene = tracern.BoxScene(n)
     scene._set_camera_arrays(o, a)
     scene.set_supersampling(2)
-    fmt = fmt_of(W, H, fx.RGBX8)
+    fmt = sup.fmt_of(W, H, fx.RGBX8)
     dest = bytearray(fmt.pitch * H)
     assert ntracer_amd.BlockingRenderer().render(dest, fmt, scene)
     osc = ob.OracleScene(n, o, a)
@@ -359,7 +350,7 @@ def test_abort_leaves_the_destination_alone_and_statistics_count_every_sample():
     sc, _, _ = composite("cell600_n4")
     sc.set_supersampling(2)
     w, h = 160, 90
-    fmt = fmt_of(w, h, fx.RGBX8)
+    fmt = sup.fmt_of(w, h, fx.RGBX8)
     fst = fmt._as_struct()
     # the flag is already up: NT_ABORTED, nothing drawn
     dest = (C.c_char * (fmt.pitch * h))(*([0x6A] * (fmt.pitch * h)))
@@ -382,13 +373,13 @@ def test_abort_leaves_the_destination_alone_and_statistics_count_every_sample():
     _lib.check(L.nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), fmt.pitch * h, C.byref(fst), C.byref(opts),
                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
-    assert np.array_equal(buf.cpu().numpy().reshape(h, fmt.pitch), render_host(sc, fmt))
+    assert np.array_equal(buf.cpu().numpy().reshape(h, fmt.pitch), sup.render_host(sc, fmt))
     # cell600_n4 is opaque, unlit and reflects nothing: one ray a sample
-    render_host(sc, fmt, collect_stats=True)
+    sup.render_host(sc, fmt, collect_stats=True)
     st = sc.last_stats()
     assert st["rays"] == 4 * w * h and st["shadow_rays"] == 0, st
     sc.set_supersampling(1)
-    render_host(sc, fmt, collect_stats=True)
+    sup.render_host(sc, fmt, collect_stats=True)
     assert sc.last_stats()["rays"] == w * h
 
 
@@ -406,21 +397,21 @@ def test_the_samples_of_one_row_must_fit_the_scratch_buffer():
     sc.set_supersampling(s)
     sc.set_supersampling_scratch_mb(1)
     L = _lib.lib()
-    fmt = fmt_of(w_ok + 1, h, fx.RGBX8)
+    fmt = sup.fmt_of(w_ok + 1, h, fx.RGBX8)
     fst = fmt._as_struct()
     dest = (C.c_char * (fmt.pitch * h))(*([0x4E] * (fmt.pitch * h)))
     assert L.nt_render(sc._handle, dest, fmt.pitch * h, C.byref(fst), None, None) == _lib.NT_E_UNSUPPORTED
     assert "nt_scene_set_supersampling_scratch_mb" in _lib.last_error() and "1 MiB" in _lib.last_error()
     assert bytes(dest) == b"\x4e" * (fmt.pitch * h)
     with pytest.raises(NotImplementedError):
-        render_host(sc, fmt)
-    img = render_host(sc, fmt_of(w_ok, h, fx.RGBX8))
+        sup.render_host(sc, fmt)
+    img = sup.render_host(sc, sup.fmt_of(w_ok, h, fx.RGBX8))
     want = sx.expected(ob.OracleScene(n, o, a), w_ok, h, s, fx.RGBX8)
     assert np.array_equal(img, want), int((img != want).sum())
     # the refused width is fine without supersampling, and with a larger cap
     sc.set_supersampling(1)
-    render_host(sc, fmt)
+    sup.render_host(sc, fmt)
     sc.set_supersampling(s)
     sc.set_supersampling_scratch_mb(2)
-    img = render_host(sc, fmt)
+    img = sup.render_host(sc, fmt)
     assert np.array_equal(img, sx.expected(ob.OracleScene(n, o, a), w_ok + 1, h, s, fx.RGBX8))

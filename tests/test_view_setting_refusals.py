@@ -4,7 +4,6 @@ answer byte for byte against tests/view_setting_refusals.py, which was written d
 functions became one table.  No GPU: a refusal that reached a device would show as another error here."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import fixtures as fx
 import ntracer_amd
 import ray_query_cases as rq
 import view_setting_refusals as vr
+import support as sup
 from ntracer_amd import _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,14 +36,6 @@ OFF = {
     "adaptive": lambda s: s.set_adaptive_supersampling(None),
 }
 COMPOSITE = ("clip", "cue", "outlines", "ao")          # in the order of precedence
-
-
-def _opts(**fields):
-    opts = _lib.NtRenderOpts()
-    opts.device = -1
-    for k, v in fields.items():
-        setattr(opts, k, v)
-    return opts
 
 
 # cause -> (what sets it up on the scene, what takes it away again, the options of the call)
@@ -80,7 +72,7 @@ class _Renders:
     def answers(self, fields):
         """[(status, message)] of the three forms"""
         L, h = _lib.lib(), self.scene._handle
-        opts = None if fields is None else _opts(**fields)
+        opts = None if fields is None else sup.render_opts(**fields)
         po = None if opts is None else C.byref(opts)
         out = []
         for call in (lambda: L.nt_render(h, self.dest, self.size, C.byref(self.fst), po, None),
@@ -202,7 +194,7 @@ def query_answers(entry, cause):
         fields = {cause[len("options: "):]: 1}
     else:
         raise KeyError(cause)
-    opts = None if fields is None else _opts(**fields)
+    opts = None if fields is None else sup.render_opts(**fields)
     forms = _calls(entry)
     if cause.startswith("options: "):
         forms = forms[1:]
@@ -241,17 +233,12 @@ def test_the_table_of_entry_point_refusals_is_whole():
 
 # ------------------------------------------------------------------ what can only be read
 
-def _body(src, head):
-    start = src.index(head)
-    return src[start:re.compile(r"\n\}(\n|$)").search(src, start).start()]
-
-
 def test_one_check_one_table_and_the_row_range_guard():
     with open(os.path.join(ROOT, "ntracer_amd", "csrc", "nt_api.cpp")) as f:
         api = f.read()
     # the row range is a guard for callers inside nt_api.cpp: the entry points hand over whole images unless band_world > 1,
     # which is refused first, so it can only be read, not reached
     assert api.count("int whole_view_check(") == 1
-    assert "for a row range" in _body(api, "int whole_view_check(")
+    assert "for a row range" in sup.function_body(api, "int whole_view_check(")
     for gone in ("ao_check", "outline_check", "box_lines_check", "cue_check", "clip_check"):
         assert gone not in api, gone

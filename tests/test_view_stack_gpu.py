@@ -15,10 +15,10 @@ import pytest
 
 import box_hit_cases as bc
 import fixtures as fx
-import ntracer_amd
 import primary_hit_cases as ph
 import ray_color_cases as rc
 import view_stack_cases as vc
+import support as sup
 from ntracer_amd import _lib, tracern
 from ntracer_amd.render import CameraTable
 
@@ -34,10 +34,7 @@ def route_id(r):
 
 
 def _env(mp, env):
-    for key in vc.SWITCHES:
-        mp.delenv(key, raising=False)
-    for key, v in (env or {}).items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, vc.SWITCHES, env or {})
 
 
 def box_scene(n, k, mp, env=None):
@@ -59,29 +56,6 @@ def composite_scene(case, mp):
     sc.set_fov(ph.fov_of(case[0]))
     sc._set_camera_arrays(*vc.composite_camera(case))
     return sc
-
-
-def fmt_of(w, h, chans, pitch=0, rev=False):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans], pitch, rev)
-
-
-def render_host(scene_, fmt, fill=0):
-    buf = bytearray(bytes([fill]) * (fmt.pitch * fmt.height))
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene_)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
-def render_device(sc, fmt, opts=None, fill=0x3D):
-    import torch
-    size = fmt.pitch * fmt.height
-    buf = torch.full((size + 16,), fill, dtype=torch.uint8, device="cuda")
-    fst = fmt._as_struct()
-    status = _lib.lib().nt_render_device(sc._handle, C.c_void_p(buf.data_ptr()), size, C.byref(fst), None if opts is None else C.byref(opts),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[size:] == fill).all()
-    return status, got[:size].reshape(fmt.height, fmt.pitch)
 
 
 def as_rgb(img, w, h):
@@ -115,24 +89,24 @@ def test_box_frames_equal_the_rule_byte_for_byte(route):
                 for w, h in vc.SIZES:
                     want = vc.box_expected(n, k, name, w, h)
                     label = "%s camera %d %s %dx%d" % (route_id(route), k, name, w, h)
-                    f = fmt_of(w, h, fx.RGBF32)
-                    got, clamped = as_rgb(render_host(sc, f), w, h), vc.clamp01(want)
+                    f = sup.fmt_of(w, h, fx.RGBF32)
+                    got, clamped = as_rgb(sup.render_host(sc, f), w, h), vc.clamp01(want)
                     assert np.array_equal(got.view(np.uint32), clamped.view(np.uint32)), (label, "fp32 host", _differ(got, clamped))
-                    f = fmt_of(w, h, fx.RGBX8)
+                    f = sup.fmt_of(w, h, fx.RGBX8)
                     packed = vc.pack(want, fx.RGBX8)
-                    img = render_host(sc, f)
+                    img = sup.render_host(sc, f)
                     assert np.array_equal(img, packed), (label, "rgbx8 host", _differ(img.reshape(h, w, 4), packed.reshape(h, w, 4)))
-                    status, img = render_device(sc, f)
+                    status, img = sup.render_device(sc, f)
                     assert status == 0 and np.array_equal(img, packed), (label, "rgbx8 device", int((img != packed).sum()))
                     if (w, h) != vc.SHOW_SIZE:
                         continue
                     if name != "one":
                         vc.check_box_shows(n, k, name)          # (the expectation just met is not the plain frame's)
                     for fname, chans, rev in vc.FORMATS:
-                        status, img = render_device(sc, fmt_of(w, h, chans, rev=rev))
+                        status, img = sup.render_device(sc, sup.fmt_of(w, h, chans, rev=rev))
                         assert status == 0 and np.array_equal(img, vc.pack(want, chans, rev)), (label, fname)
-                    f = fmt_of(w, h, vc.RGB24, pitch=w * 3 + 5)
-                    for img in (render_host(sc, f, fill=0xb3), render_device(sc, f, fill=0xb3)[1]):
+                    f = sup.fmt_of(w, h, vc.RGB24, pitch=w * 3 + 5)
+                    for img in (sup.render_host(sc, f, fill=0xb3), sup.render_device(sc, f, fill=0xb3)[1]):
                         assert np.array_equal(img[:, :w * 3], vc.pack(want, vc.RGB24)) and (img[:, w * 3:] == 0xb3).all(), (label, "rgb24, padded")
 
 
@@ -140,15 +114,15 @@ def test_both_box_routes_give_identical_bytes_and_one_sample_is_the_plain_frame(
     n, k, (w, h) = 6, 2, vc.SIZES[3]
     with pytest.MonkeyPatch.context() as mp:
         sc = box_scene(n, k, mp)
-        fmts = [fmt_of(w, h, fx.RGBX8), fmt_of(w, h, fx.RGBF32), fmt_of(w, h, vc.RGB24)]
-        plain = [render_host(sc, f) for f in fmts]
+        fmts = [sup.fmt_of(w, h, fx.RGBX8), sup.fmt_of(w, h, fx.RGBF32), sup.fmt_of(w, h, vc.RGB24)]
+        plain = [sup.render_host(sc, f) for f in fmts]
         for name in vc.stacks_of(n):
             _set(sc, vc.box_stack(n, k, name))
             sc.set_view_stack_route(None)
-            fused = [render_device(sc, f)[1] for f in fmts]
+            fused = [sup.render_device(sc, f)[1] for f in fmts]
             sc.set_view_stack_route("frames")
             assert sc.view_stack_route == "frames"
-            frames = [render_device(sc, f)[1] for f in fmts]
+            frames = [sup.render_device(sc, f)[1] for f in fmts]
             for a, b, p in zip(fused, frames, plain):
                 assert np.array_equal(a, b), name
                 # K = 1 with a zero offset and weight 1: the plain render's bytes; every other stack shows
@@ -156,7 +130,7 @@ def test_both_box_routes_give_identical_bytes_and_one_sample_is_the_plain_frame(
         # taking the setting off gives the plain bytes again, on either route
         sc.set_view_stack(None)
         for f, p in zip(fmts, plain):
-            assert np.array_equal(render_device(sc, f)[1], p)
+            assert np.array_equal(sup.render_device(sc, f)[1], p)
 
 
 # ------------------------------------------------------------------ 2. composite scenes
@@ -174,11 +148,11 @@ def test_composite_frames_equal_the_sum_of_the_plain_frames(case):
             for w, h in sizes:
                 label = "%s %s %dx%d" % (vc.composite_id(case), name, w, h)
                 sc.set_view_stack(None)
-                f32fmt = fmt_of(w, h, fx.RGBF32)
+                f32fmt = sup.fmt_of(w, h, fx.RGBF32)
                 P = np.zeros((len(origins), h, w, 3), np.float32)
                 for i in range(len(origins)):
                     sc._set_camera_arrays(origins[i], axes[i])
-                    P[i] = as_rgb(render_device(sc, f32fmt)[1], w, h)
+                    P[i] = as_rgb(sup.render_device(sc, f32fmt)[1], w, h)
                 oracle = vc.composite_frames(case, name, w, h)
                 err = float(np.abs(P.astype(np.float64) - oracle).max())
                 assert err <= 1e-5, (label, "a plain frame under a sample camera is not the oracle's", err)
@@ -187,17 +161,17 @@ def test_composite_frames_equal_the_sum_of_the_plain_frames(case):
                 _set(sc, st)
                 formats = vc.FORMATS if (w, h) == vc.SHOW_SIZE else vc.FORMATS[:1]
                 for fname, chans, rev in formats:
-                    status, img = render_device(sc, fmt_of(w, h, chans, rev=rev))
+                    status, img = sup.render_device(sc, sup.fmt_of(w, h, chans, rev=rev))
                     assert status == 0 and np.array_equal(img, vc.pack(want, chans, rev)), (label, fname)
-                img = render_host(sc, fmt_of(w, h, fx.RGBX8))
+                img = sup.render_host(sc, sup.fmt_of(w, h, fx.RGBX8))
                 assert np.array_equal(img, vc.pack(want, fx.RGBX8)), (label, "host")
         # K = 1 with a zero offset gives the plain render's bytes, and so does taking the setting off
         w, h = vc.SHOW_SIZE
-        f = fmt_of(w, h, fx.RGBX8)
+        f = sup.fmt_of(w, h, fx.RGBX8)
         _set(sc, vc.composite_stack(case, "one"))
-        one = render_device(sc, f)[1]
+        one = sup.render_device(sc, f)[1]
         sc.set_view_stack(None)
-        assert np.array_equal(one, render_device(sc, f)[1]) and len(np.unique(one)) > 8
+        assert np.array_equal(one, sup.render_device(sc, f)[1]) and len(np.unique(one)) > 8
 
 
 # ------------------------------------------------------------------ 3. frames
@@ -205,11 +179,11 @@ def _three_frames(sc, n, cams, w, h, chans, label):
     import torch
     origins, axes = np.ascontiguousarray(np.stack([c[0] for c in cams])), np.ascontiguousarray(np.stack([c[1] for c in cams]))
     nf = len(cams)
-    fmt = fmt_of(w, h, chans)
+    fmt = sup.fmt_of(w, h, chans)
     singles = []
     for o, a in cams:
         sc._set_camera_arrays(o, a)
-        singles.append(render_host(sc, fmt))
+        singles.append(sup.render_host(sc, fmt))
     singles = np.stack(singles)
     for i in range(nf):
         for j in range(i):
@@ -285,7 +259,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         images = []
         for mib in (1024, 1):
             sc.set_supersampling_scratch_mb(mib)
-            images.append([render_device(sc, fmt_of(w, h, chans))[1] for chans in (fx.RGBX8, fx.RGBF32)])
+            images.append([sup.render_device(sc, sup.fmt_of(w, h, chans))[1] for chans in (fx.RGBX8, fx.RGBF32)])
         for a, b in zip(*images):
             assert np.array_equal(a, b)
         assert len(np.unique(images[0][0])) > 16
@@ -293,7 +267,7 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         cams = [sc.get_camera()._origin, sc.get_camera()._axes]
         import torch
         table = CameraTable(sc.dimension, np.stack([cams[0], cams[0]]), np.stack([cams[1], cams[1]]))
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         buf = torch.zeros((2 * fmt.pitch * h,), dtype=torch.uint8, device="cuda")
         assert table.render(sc, buf, fmt, frame_bytes=fmt.pitch * h, first=0, count=2)
         torch.cuda.synchronize()
@@ -302,16 +276,16 @@ def test_a_small_scratch_cap_gives_the_same_bytes_and_a_frame_that_does_not_fit_
         # nothing fits: refused before anything is launched
         w, h = 320, 240
         assert 2 * w * h * 12 > (1 << 20)
-        status, img = render_device(sc, fmt_of(w, h, fx.RGBX8), fill=0x4E)
+        status, img = sup.render_device(sc, sup.fmt_of(w, h, fx.RGBX8), fill=0x4E)
         assert status == _lib.NT_E_UNSUPPORTED and (img == 0x4E).all()
         assert _lib.last_error().startswith("a view stack") and "nt_scene_set_supersampling_scratch_mb" in _lib.last_error()
         if kind == "box":                                               # the fused kernel needs no scratch and draws
             sc.set_view_stack_route(None)
-            status, fused = render_device(sc, fmt_of(w, h, fx.RGBX8), fill=0x4E)
+            status, fused = sup.render_device(sc, sup.fmt_of(w, h, fx.RGBX8), fill=0x4E)
             assert status == 0 and len(np.unique(fused)) > 16
             sc.set_view_stack_route("frames")
             sc.set_supersampling_scratch_mb(1024)
-            status, img = render_device(sc, fmt_of(w, h, fx.RGBX8), fill=0x4E)
+            status, img = sup.render_device(sc, sup.fmt_of(w, h, fx.RGBX8), fill=0x4E)
             assert status == 0 and np.array_equal(img, fused)
 
 
@@ -333,13 +307,13 @@ def test_an_abort_word_raised_before_the_launch_leaves_the_destination_untouched
         opts = _lib.NtRenderOpts()
         opts.device = -1
         opts.abort_device = word.data_ptr()
-        fmt = fmt_of(w, h, fx.RGBX8)
-        status, img = render_device(sc, fmt, opts=opts, fill=0x6A)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        status, img = sup.render_device(sc, fmt, opts=opts, fill=0x6A)
         assert status == 0 and (img == 0x6A).all()
         word.zero_()
         torch.cuda.synchronize()
-        status, img = render_device(sc, fmt, opts=opts, fill=0x6A)
-        assert status == 0 and (np.array_equal(img, want) if want is not None else np.array_equal(img, render_host(sc, fmt)))
+        status, img = sup.render_device(sc, fmt, opts=opts, fill=0x6A)
+        assert status == 0 and (np.array_equal(img, want) if want is not None else np.array_equal(img, sup.render_host(sc, fmt)))
 
 
 @pytest.mark.parametrize("kind", ("box-fused", "box-frames", "composite"))
@@ -359,7 +333,7 @@ def test_a_warm_table_render_is_capturable(kind):
             _set(sc, vc.box_stack(6, 2, "slab"))
             cams = [bc.camera(6, k) for k in (2, 4)]
         n = sc.dimension
-        fmt = fmt_of(w, h, fx.RGBX8)
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
         fst = fmt._as_struct()
         tab = CameraTable(n, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]))
         st = torch.cuda.Stream()
@@ -383,7 +357,7 @@ def test_a_warm_table_render_is_capturable(kind):
         assert torch.equal(fb, ref)
         del gr
         sc._set_camera_arrays(*cams[1])
-        assert np.array_equal(ref[1].cpu().numpy().reshape(h, fmt.pitch), render_host(sc, fmt))
+        assert np.array_equal(ref[1].cpu().numpy().reshape(h, fmt.pitch), sup.render_host(sc, fmt))
         assert len(np.unique(ref[1].cpu().numpy())) > 16
 
 
@@ -396,8 +370,8 @@ def test_the_probes_the_records_and_the_rays_ignore_the_setting():
         n, k = 6, 2
         sc, plain = box_scene(n, k, mp), box_scene(n, k, mp)
         _set(sc, vc.box_stack(n, k, "disc"))
-        fmt = fmt_of(w, h, fx.RGBX8)
-        assert not np.array_equal(render_host(sc, fmt), render_host(plain, fmt))
+        fmt = sup.fmt_of(w, h, fx.RGBX8)
+        assert not np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt))
         assert np.array_equal(sc.colors_at(xs, ys, w, h).view(np.uint32), plain.colors_at(xs, ys, w, h).view(np.uint32))
         assert np.array_equal(sc.face_hits(w, h).records, plain.face_hits(w, h).records)
         d = np.ascontiguousarray(bc.expected(n, k, w, h)["dirs"].reshape(w * h, n), np.float32)
@@ -406,7 +380,7 @@ def test_the_probes_the_records_and_the_rays_ignore_the_setting():
         case = vc.COMPOSITE[0]
         sc, plain = composite_scene(case, mp), composite_scene(case, mp)
         _set(sc, vc.composite_stack(case, "disc"))
-        assert not np.array_equal(render_host(sc, fmt), render_host(plain, fmt))
+        assert not np.array_equal(sup.render_host(sc, fmt), sup.render_host(plain, fmt))
         assert np.array_equal(sc.colors_at(xs, ys, w, h).view(np.uint32), plain.colors_at(xs, ys, w, h).view(np.uint32))
         a, b = sc.primary_hits(w, h), plain.primary_hits(w, h)
         assert np.array_equal(a.hits, b.hits)

@@ -15,9 +15,9 @@ import numpy as np
 import pytest
 
 import fixtures as fx
-import ntracer_amd
 import oracle_binding as ob
 import xray_cases as xc
+import support as sup
 from ntracer_amd import _lib, tracern
 
 pytestmark = pytest.mark.gpu
@@ -29,10 +29,7 @@ W, H = 37, 21
 
 
 def _scene(name, mp, env=None, k=0):
-    for key in SWITCHES:
-        mp.delenv(key, raising=False)
-    for key, v in (env or {}).items():
-        mp.setenv(key, v)
+    sup.set_switches(mp, SWITCHES, env or {})
     n, flat, params, fov, cam = xc.scene(name)
     sc = tracern.CompositeScene.from_flat(n, flat)
     if params is not None:
@@ -104,18 +101,8 @@ def test_the_general_route_counts_what_the_packet_walk_counts(name, sizes):
 
 
 # ------------------------------------------------------------------ renders
-def fmt_of(w, h, chans):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
-def render_host(scene, fmt):
-    buf = bytearray(fmt.pitch * fmt.height)
-    assert ntracer_amd.BlockingRenderer().render(buf, fmt, scene)
-    return np.frombuffer(bytes(buf), np.uint8).reshape(fmt.height, fmt.pitch)
-
-
 def colours_of(sc, w, h):
-    return render_host(sc, fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h * w, 3)
+    return sup.render_host(sc, sup.fmt_of(w, h, fx.RGBF32)).view(">f4").astype(np.float32).reshape(h * w, 3)
 
 
 def _assert_colours(got, name, a, t, label):
@@ -142,7 +129,7 @@ def test_colours_against_the_float64_expectation(name, tint):
         want = _assert_colours(got, name, a, tint, "%s tint %g" % (name, tint))
         assert np.abs(got - r["B"]).max() > 0.05                            # the crossings show
         # RGBX8: every byte within 1 of the oracle's packing of the expectation
-        rgbx = render_host(sc, fmt_of(W, H, fx.RGBX8)).reshape(H * W, 4).astype(np.int32)
+        rgbx = sup.render_host(sc, sup.fmt_of(W, H, fx.RGBX8)).reshape(H * W, 4).astype(np.int32)
         packed = np.array([list(ob.pack_pixel(want[i].astype(np.float32), fx.RGBX8)) for i in range(H * W)], np.int32)
         o = r["ordinary"]
         assert np.abs(rgbx - packed)[o].max() <= 1
@@ -170,12 +157,12 @@ def test_two_cameras_in_one_call_equal_their_single_renders():
         with pytest.MonkeyPatch.context() as mp:
             sc = _scene(name, mp, env)
             sc.set_xray(0.3, 1.0)
-            fmt = fmt_of(W, H, fx.RGBX8)
+            fmt = sup.fmt_of(W, H, fx.RGBX8)
             cams = [xc.scene(name)[4](k) for k in range(2)]
             singles = []
             for o, axes in cams:
                 sc._set_camera_arrays(o, axes)
-                singles.append(render_host(sc, fmt))
+                singles.append(sup.render_host(sc, fmt))
             assert not np.array_equal(singles[0], singles[1])
             frame_bytes = fmt.pitch * H + 64
             buf = torch.full((2 * frame_bytes,), 0x3D, dtype=torch.uint8, device="cuda")
@@ -195,10 +182,10 @@ def test_two_cameras_in_one_call_equal_their_single_renders():
 def test_the_setting_off_again_leaves_the_plain_render_as_it_was():
     with pytest.MonkeyPatch.context() as mp:
         sc = _scene("cell600_n4", mp)
-        fmt = fmt_of(W, H, fx.RGBX8)
-        before = render_host(sc, fmt)
+        fmt = sup.fmt_of(W, H, fx.RGBX8)
+        before = sup.render_host(sc, fmt)
         sc.set_xray(0.3, 1.0)
-        xray = render_host(sc, fmt)
+        xray = sup.render_host(sc, fmt)
         assert not np.array_equal(before, xray)
         sc.set_xray(None)
-        assert np.array_equal(render_host(sc, fmt), before)
+        assert np.array_equal(sup.render_host(sc, fmt), before)

@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 import fixtures as fx
-import ntracer_amd
 import ray_query_cases as rq
 import primary_hit_cases as ph
 import xray_cases as xc
+import support as sup
 from ntracer_amd import _lib, tracern
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -209,16 +209,12 @@ def test_the_setting_round_trips_and_a_refused_set_leaves_it_as_it_was():
 
 
 # ------------------------------------------------------------------ refusals, before a device is touched
-def _fmt(w, h, chans=fx.RGBX8):
-    return ntracer_amd.ImageFormat(w, h, [ntracer_amd.Channel(*c) for c in chans])
-
-
 def test_the_renders_refuse_what_the_setting_excludes_before_they_touch_a_device():
     L = _lib.lib()
     sc, n, _ = _scene()
     sc.set_xray()
     w, h = 8, 4
-    fmt = _fmt(w, h)
+    fmt = sup.fmt_of(w, h)
     fst = fmt._as_struct()
     size = fmt.pitch * h
     dest = (C.c_char * size)(*([0x4E] * size))
