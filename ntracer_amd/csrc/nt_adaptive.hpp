@@ -226,8 +226,7 @@ __global__ __launch_bounds__(64) void refine_box(NtRefine rf, NtTarget tg) {
 
 // the grid of a refine launch: a wave for every 64 pixels that could be flagged, capped as the rays_* kernels cap theirs
 inline long long refine_blocks(const NtRefine &rf) {
-    long long blocks = (rf.max_count + 63) / 64;
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
+    const long long blocks = strided_blocks((rf.max_count + 63) / 64);
     return blocks < 1 ? 1 : blocks;
 }
 
@@ -236,16 +235,12 @@ int launch_refine_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const 
     // one wave's share of what launch_rays_fixed asks for: stack [depth + 1][64], ray table, mailbox.  A block is one wave, so
     // this is the block's whole allocation, held to the 64 KiB a launch gets without asking for more: at N = 10 that is a stack
     // of 220 levels, beyond what the base frame's own kernels take (their four-wave blocks stop at 124)
-    const size_t lds = (size_t)64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    if (lds > 64 * 1024) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
-        return -1;
-    }
+    size_t lds;
+    if (const int r = lane_walk_lds(sc, N, 1, 64 * 1024, lds)) return r;
     hipStream_t s = (hipStream_t)li.stream;
-    long long blocks = refine_blocks(rf);
+    const long long blocks = refine_blocks(rf);
     if (sc.checked) {
-        if (blocks > sc.checked_lanes / 64) blocks = sc.checked_lanes / 64;
-        const dim3 tgrid((unsigned)blocks);
+        const dim3 tgrid((unsigned)checked_column_blocks(sc, 64, blocks));
         if (sc.alias_normals) hipLaunchKernelGGL((refine_color_t<N, true>), tgrid, dim3(64), lds, s, sc, rf, tg);
         else hipLaunchKernelGGL((refine_color_t<N, false>), tgrid, dim3(64), lds, s, sc, rf, tg);
         return 0;
@@ -255,7 +250,7 @@ int launch_refine_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const 
         return -1;
     }
     const dim3 grid((unsigned)blocks);
-    const bool feat = sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+    const bool feat = scene_feat(sc);
     if (feat && !sc.has_scalar_prims) hipLaunchKernelGGL((refine_color<N, true, false>), grid, dim3(64), lds, s, sc, rf, tg);
     else if (feat) hipLaunchKernelGGL((refine_color<N, true, true>), grid, dim3(64), lds, s, sc, rf, tg);
     else hipLaunchKernelGGL((refine_color<N, false, false>), grid, dim3(64), lds, s, sc, rf, tg);

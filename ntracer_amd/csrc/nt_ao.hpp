@@ -86,18 +86,15 @@ __global__ __launch_bounds__(256) void ao_kernel(NtCompositeDev sc, NtTarget tg,
 template <int N>
 int launch_ao_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtAo &ao) {
     // per wave what the query kernels use (launch_query_fixed): stack [depth + 1][64], ray table, mailbox
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    if (lds > 160 * 1024) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
-        return -1;
-    }
+    size_t lds;
+    if (const int r = lane_walk_lds(sc, N, 4, 160 * 1024, lds)) return r;
     if (!sc.all_opaque || sc.checked) {
         snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: the ambient occlusion kernel is for opaque scenes on the mailbox walk");
         return -1;
     }
     const int tiles_x = (tg.width + 15) / 16, tiles_y = (tg.height + 15) / 16;
     const long long tiles = (long long)tiles_x * tiles_y * ao.nframes;
-    const dim3 grid((unsigned)(tiles < (1 << 20) ? tiles : (1 << 20)));
+    const dim3 grid((unsigned)strided_blocks(tiles));
     hipStream_t s = (hipStream_t)li.stream;
     if (sc.has_scalar_prims) hipLaunchKernelGGL((ao_kernel<N, true>), grid, dim3(256), lds, s, sc, tg, ao, tiles_x, tiles_y);
     else hipLaunchKernelGGL((ao_kernel<N, false>), grid, dim3(256), lds, s, sc, tg, ao, tiles_x, tiles_y);

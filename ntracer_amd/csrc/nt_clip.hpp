@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) NT_SHADE_OCC void clip_shade(NtCompositeDev sc
 // draw: tg is the whole image of every frame (row_begin 0, row_count = height, no bands) and li.hit_buf holds li.hit_frames
 // frames of width * height records; otherwise tg is the view alone and the records go to cl.hits, cl.frame_stride of them a
 // frame, with the normal rows of the pixels that hit behind them.  Frames are chunked by what the hit and numerator scratch
-// hold, and the walk is set up, exactly as launch_cue_fixed has it.
+// hold (packet_chunk); the walk is set up by packet_args and packet_chunk_head of nt_composite.hpp.
 template <int N>
 int launch_clip_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtClip &cl, bool draw) {
     if (!sc.all_opaque || sc.checked || sc.stack_depth > 32 || li.kernel_choice != 0 || !cl.cams || !cl.planes || cl.count < 1 ||
@@ -63,39 +63,18 @@ int launch_clip_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a clip launch that is not for the packet walk");
         return -1;
     }
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    const bool feat = sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+    const size_t lds = 4 * wave_lds_bytes(sc.stack_depth, N);
+    const bool feat = scene_feat(sc);
     hipStream_t s = (hipStream_t)li.stream;
-    PacketArgs pk;
-    pk.tiles_x = (tg.width + 7) / 8;
-    pk.tiles_y = (tg.height + 7) / 8;
-    pk.quads_x = (pk.tiles_x + 1) / 2;
-    pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
-    pk.order = li.tile_order;
-    pk.frame_major = li.frame_major;
-    pk.numer = nullptr;
-    pk.n_batches = sc.n_batches;
-    pk.lds_per_wave = (int)((size_t)NT_WM * 16 + (size_t)32 * 32);
-    pk.lens = nullptr;
+    PacketArgs pk = packet_args(li, sc, tg.width, tg.height);
     pk.clip = cl.planes;
     pk.clip_count = cl.count;
-    int chunk = li.nframes;
-    if (draw && li.hit_frames < chunk) chunk = li.hit_frames;
-    if (li.numer_buf && li.numer_frames > 0 && li.numer_frames < chunk) chunk = li.numer_frames;
-    NtTarget th = tg;                                      // the walk's view of the records: a frame of them every ...
-    th.frame_stride = draw ? (long long)16 * tg.width * tg.height : (long long)16 * cl.frame_stride;    // ... this many bytes
+    const int chunk = packet_chunk(li, li.nframes, draw);
+    const NtTarget th = packet_record_view(tg, draw ? (long long)tg.width * tg.height : cl.frame_stride);
     for (int f0 = 0; f0 < li.nframes; f0 += chunk) {
-        const int cnt = li.nframes - f0 < chunk ? li.nframes - f0 : chunk;
-        pk.cams = cl.cams + (size_t)f0 * 4 * N;
-        pk.nframes = cnt;
+        const int cnt = packet_chunk_head<N>(li, sc, pk, cl.cams, f0, chunk, li.nframes);
         pk.hits_out = draw ? (float4 *)li.hit_buf : reinterpret_cast<float4 *>(cl.hits) + (long long)f0 * cl.frame_stride;
-        if (li.numer_buf && li.numer_frames > 0 && sc.n_batches > 0) {
-            const long long total = (long long)sc.n_batches * NT_DEV_BATCH;
-            hipLaunchKernelGGL((packet_numerators<N>), dim3((unsigned)((total + 255) / 256), (unsigned)cnt), dim3(256), 0, s,
-                               sc, pk.cams, li.numer_buf);
-            pk.numer = li.numer_buf;
-        }
-        const dim3 pgrid((unsigned)((long long)pk.quads * cnt));
+        const dim3 pgrid = packet_grid(pk, cnt);
         if (sc.has_scalar_prims) hipLaunchKernelGGL((composite_packet<N, 32, false, true, true, false, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, th, pk);
         else hipLaunchKernelGGL((composite_packet<N, 32, false, false, true, false, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, th, pk);
         if (!draw) continue;
@@ -103,8 +82,7 @@ int launch_clip_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         c2.cams = pk.cams;
         c2.nframes = cnt;
         c2.hits = li.hit_buf;
-        NtTarget t2 = tg;
-        t2.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        const NtTarget t2 = chunk_target(tg, f0);
         dim3 g2;
         grid_for(t2, 16, 16, cnt, g2);
         if (!feat) hipLaunchKernelGGL((clip_shade<N, false, false>), g2, dim3(256), 0, s, sc, t2, c2);
@@ -122,7 +100,7 @@ int launch_clip_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         h.normal_dir = cl.normal_dir;
         const int tiles_x = (tg.width + 15) / 16, tiles_y = (tg.height + 15) / 16;
         const long long tiles = (long long)tiles_x * tiles_y * li.nframes;
-        const dim3 grid((unsigned)(tiles < (1 << 20) ? tiles : (1 << 20)));
+        const dim3 grid((unsigned)strided_blocks(tiles));
         if (sc.has_scalar_prims) hipLaunchKernelGGL((hits_normals<N, true>), grid, dim3(256), 0, s, sc, tg, h, tiles_x, tiles_y);
         else hipLaunchKernelGGL((hits_normals<N, false>), grid, dim3(256), 0, s, sc, tg, h, tiles_x, tiles_y);
     }

@@ -232,7 +232,8 @@ struct WaveLds {
     int *mbox;         // mbox[slot*64 + lane]
 };
 
-__device__ __forceinline__ size_t wave_lds_bytes(int stack_depth, int n) {
+// (the launchers size their launches by the function the kernels carve by: lane_walk_lds below)
+__host__ __device__ __forceinline__ size_t wave_lds_bytes(int stack_depth, int n) {
     return (size_t)64 * ((size_t)stack_depth * 4 + (size_t)n * 8 + (size_t)NT_MBOX * 4);
 }
 
@@ -2313,6 +2314,103 @@ __global__ __launch_bounds__(256, FEAT ? 1 : ((N <= 4 && !SCAL) ? NT_PACKET_WAVE
     }
 }
 
+// --------------------------------------------------------------------------------------
+// What the fixed-n launchers share (host code; nt_var.hip has the run-time-n unit's own, beside var_lds_bytes).  The LDS of a
+// launch whose blocks are `waves` waves of the per-lane walk -- wave_lds carves wave_lds_bytes a wave -- refused beyond `limit`
+// bytes: 0 and `lds`, or -1 and the launch error.
+// --------------------------------------------------------------------------------------
+inline int lane_walk_lds(const NtCompositeDev &sc, int n, int waves, size_t limit, size_t &lds) {
+    lds = (size_t)waves * wave_lds_bytes(sc.stack_depth, n);
+    if (lds <= limit) return 0;
+    snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
+    return -1;
+}
+
+// the kernels that shade with lights, reflections or unbatched primitives
+inline bool scene_feat(const NtCompositeDev &sc) {
+    return sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+}
+
+// at most this many blocks of the kernels that keep no per-lane scratch (the rays_* kernels and every one after them): beyond it
+// they stride over their `work`
+#define NT_RAYS_MAX_BLOCKS (1 << 20)
+inline long long strided_blocks(long long work) {
+    return work < NT_RAYS_MAX_BLOCKS ? work : NT_RAYS_MAX_BLOCKS;
+}
+
+// the kernels with the exact `checked` list: as many blocks of `block` lanes as the scratch has lane columns for, striding over
+// their `work`
+inline long long checked_column_blocks(const NtCompositeDev &sc, int block, long long work) {
+    const long long have = sc.checked_lanes / block;
+    return work < have ? work : have;
+}
+
+// The packet walk.  A wave of the lean kernels has the wave mailbox and 32 levels of the uniform frame stack in LDS ...
+#define NT_PACKET_LDS_LEAN (NT_WM * 16 + 32 * 32)
+
+// ... and a launch the walk of an image of `width` x `rows`: the quads, their order, the lean LDS.  Everything else is zero; a
+// launcher sets what is its own (hits_out, lens, clip and clip_count, another lds_per_wave) and the chunk head the rest.
+inline PacketArgs packet_args(const NtLaunchInfo &li, const NtCompositeDev &sc, int width, int rows) {
+    PacketArgs pk = {};
+    pk.tiles_x = (width + 7) / 8;
+    pk.tiles_y = (rows + 7) / 8;
+    pk.quads_x = (pk.tiles_x + 1) / 2;
+    pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
+    pk.order = li.tile_order;
+    pk.frame_major = li.frame_major;
+    pk.n_batches = sc.n_batches;
+    pk.lds_per_wave = NT_PACKET_LDS_LEAN;
+    return pk;
+}
+
+// frames per launch: what the scratch buffers hold -- li.hit_buf where the route writes its records there, li.numer_buf
+inline int packet_chunk(const NtLaunchInfo &li, int nframes, bool uses_hit_buf) {
+    int chunk = nframes;
+    if (uses_hit_buf && li.hit_frames < chunk) chunk = li.hit_frames;
+    if (li.numer_buf && li.numer_frames > 0 && li.numer_frames < chunk) chunk = li.numer_frames;
+    return chunk;
+}
+
+// The head of a chunk loop, once a chunk: frames [f0, f0 + cnt) of the `nframes` behind `cams` go into pk, and cnt comes back ...
+template <int N>
+int packet_frames(PacketArgs &pk, const float *cams, int f0, int chunk, int nframes) {
+    const int cnt = nframes - f0 < chunk ? nframes - f0 : chunk;
+    pk.cams = cams + (size_t)f0 * 4 * N;
+    pk.nframes = cnt;
+    return cnt;
+}
+
+// ... with, for the walks that read them, -(N.o + d) of every simplex for every camera of the chunk: the same for all rays of a frame
+template <int N>
+int packet_chunk_head(const NtLaunchInfo &li, const NtCompositeDev &sc, PacketArgs &pk, const float *cams, int f0, int chunk, int nframes) {
+    const int cnt = packet_frames<N>(pk, cams, f0, chunk, nframes);
+    if (li.numer_buf && li.numer_frames > 0 && sc.n_batches > 0) {
+        const long long total = (long long)sc.n_batches * NT_DEV_BATCH;
+        hipLaunchKernelGGL((packet_numerators<N>), dim3((unsigned)((total + 255) / 256), (unsigned)cnt), dim3(256), 0, (hipStream_t)li.stream,
+                           sc, pk.cams, li.numer_buf);
+        pk.numer = li.numer_buf;
+    }
+    return cnt;
+}
+
+inline dim3 packet_grid(const PacketArgs &pk, int cnt) {
+    return dim3((unsigned)((long long)pk.quads * cnt));
+}
+
+// the walk's view of hit records, `records` of them a frame: tg with that many 16-byte records between frames
+inline NtTarget packet_record_view(const NtTarget &tg, long long records) {
+    NtTarget th = tg;
+    th.frame_stride = 16 * records;
+    return th;
+}
+
+// tg from frame f0 on: what the pass that draws a chunk writes to
+inline NtTarget chunk_target(const NtTarget &tg, int f0) {
+    NtTarget t2 = tg;
+    t2.dest = tg.dest + (long long)f0 * tg.frame_stride;
+    return t2;
+}
+
 template <int N>
 int launch_composite_fixed(const NtLaunchInfo &li, const NtCamera &cam, const NtCompositeDev &sc, const NtTarget &tg) {
     NtCameraFixed cf;
@@ -2323,19 +2421,14 @@ int launch_composite_fixed(const NtLaunchInfo &li, const NtCamera &cam, const Nt
     for (int k = 0; k < 4 * N; ++k) cf.inl[k] = cam.inl[k];
     dim3 grid;
     grid_for(tg, 16, 16, li.nframes, grid);
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    if (lds > 160 * 1024) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
-        return -1;
-    }
-    const bool feat = sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+    size_t lds;
+    if (const int r = lane_walk_lds(sc, N, 4, 160 * 1024, lds)) return r;
+    const bool feat = scene_feat(sc);
     hipStream_t s = (hipStream_t)li.stream;
     if (sc.checked) {
         // transparent materials, or the reference's o_hit.normal handling for scenes with Solids: the kernel with the exact
-        // `checked` list -- as many blocks as the scratch has lane columns for, striding over the tiles
-        const long long tiles = (long long)grid.x * grid.y * grid.z;
-        long long blocks = sc.checked_lanes / 256;
-        if (blocks > tiles) blocks = tiles;
+        // `checked` list
+        const long long blocks = checked_column_blocks(sc, 256, (long long)grid.x * grid.y * grid.z);
         if (sc.alias_normals)
             hipLaunchKernelGGL((composite_kernel_t<N, true>), dim3((unsigned)blocks), dim3(256), lds, s, cf, sc, tg, (int)grid.x, (int)grid.y, (int)grid.z);
         else
@@ -2348,52 +2441,25 @@ int launch_composite_fixed(const NtLaunchInfo &li, const NtCamera &cam, const Nt
     }
     // scenes with unbatched triangles or solids take the packet walk only as the first of two passes (their hits
     // are shaded by the general kernel)
-    const bool two_pass_ok = feat && li.hit_buf && li.hit_frames > 0;
-    if ((!sc.has_scalar_prims || two_pass_ok) && !sc.stats && !tg.colors_out && li.persist_cams && li.kernel_choice == 0 && sc.stack_depth <= 32) {
+    const bool two_pass = feat && li.hit_buf && li.hit_frames > 0;
+    if ((!sc.has_scalar_prims || two_pass) && !sc.stats && !tg.colors_out && li.persist_cams && li.kernel_choice == 0 && sc.stack_depth <= 32) {
         // packet kernel: one wave per 8x8 tile, wave-uniform tree walk for the primary rays
-        PacketArgs pk;
-        pk.cams = li.persist_cams;
-        pk.tiles_x = (tg.width + 7) / 8;
-        pk.tiles_y = (tg.row_count + 7) / 8;
-        pk.quads_x = (pk.tiles_x + 1) / 2;
-        pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
-        pk.nframes = li.nframes;
-        pk.order = li.tile_order;
-        pk.frame_major = li.frame_major;
-        pk.hits_out = nullptr;
-        pk.numer = nullptr;
-        pk.n_batches = sc.n_batches;
-        const bool two_pass = feat && li.hit_buf && li.hit_frames > 0;
+        PacketArgs pk = packet_args(li, sc, tg.width, tg.row_count);
         const bool single_feat = feat && !two_pass;
-        // frames per launch: what the scratch buffers (primary hits, plane numerators) hold
-        int chunk = li.nframes;
-        if (two_pass && li.hit_frames < chunk) chunk = li.hit_frames;
-        if (li.numer_buf && li.numer_frames > 0 && li.numer_frames < chunk) chunk = li.numer_frames;
-        const size_t lds_lean = (size_t)NT_WM * 16 + (size_t)32 * 32;
-        const size_t lds_feat = (size_t)64 * ((size_t)N * 8 + (size_t)sc.stack_depth * 4 + NT_MBOX * 4) + NT_WM * 16 + (size_t)32 * 32;
+        const int chunk = packet_chunk(li, li.nframes, two_pass);
         for (int f0 = 0; f0 < li.nframes; f0 += chunk) {
-            const int cnt = li.nframes - f0 < chunk ? li.nframes - f0 : chunk;
-            NtTarget t2 = tg;
-            t2.dest = tg.dest + (long long)f0 * tg.frame_stride;
-            pk.cams = li.persist_cams + (size_t)f0 * 4 * N;
-            pk.nframes = cnt;
-            if (li.numer_buf && li.numer_frames > 0 && sc.n_batches > 0) {
-                // -(N.o + d) of every simplex for every camera of the chunk: the same for all rays of a frame
-                const long long total = (long long)sc.n_batches * NT_DEV_BATCH;
-                hipLaunchKernelGGL((packet_numerators<N>), dim3((unsigned)((total + 255) / 256), (unsigned)cnt), dim3(256), 0, s,
-                                   sc, pk.cams, li.numer_buf);
-                pk.numer = li.numer_buf;
-            }
-            const dim3 pgrid((unsigned)((long long)pk.quads * cnt));
+            const int cnt = packet_chunk_head<N>(li, sc, pk, li.persist_cams, f0, chunk, li.nframes);
+            NtTarget t2 = chunk_target(tg, f0);
+            const dim3 pgrid = packet_grid(pk, cnt);
             if (single_feat) {
-                pk.lds_per_wave = (int)lds_feat;
+                // (the per-lane walks of the shading behind the packet's own LDS)
+                pk.lds_per_wave = (int)(wave_lds_bytes(sc.stack_depth, N) + NT_PACKET_LDS_LEAN);
                 hipLaunchKernelGGL((composite_packet<N, 32, true, false>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, t2, pk);
                 continue;
             }
             // Lit scenes in two passes: the lean packet kernel (47 VGPRs, 6 waves/SIMD) finds the primary hits, then
             // the per-lane shading kernel (250 VGPRs: lights, shadow and reflection rays) starts from them.  One
             // kernel doing both ran its primary walk at the shading code's occupancy (1 wave/SIMD).
-            pk.lds_per_wave = (int)lds_lean;
             pk.hits_out = two_pass ? (float4 *)li.hit_buf : nullptr;
             if (sc.has_scalar_prims)
                 hipLaunchKernelGGL((composite_packet<N, 32, false, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, t2, pk);
@@ -2402,7 +2468,7 @@ int launch_composite_fixed(const NtLaunchInfo &li, const NtCamera &cam, const Nt
             if (two_pass) {
                 t2.hits = li.hit_buf;
                 NtCameraFixed c2 = cf;
-                c2.buf = li.persist_cams + (size_t)f0 * 4 * N;
+                c2.buf = pk.cams;
                 dim3 g2;
                 grid_for(t2, 16, 16, cnt, g2);
                 // (scenes made of batches alone: the instantiation without unbatched triangles and solids in its leaf loops)

@@ -166,33 +166,16 @@ int launch_hits_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
     hipStream_t s = (hipStream_t)li.stream;
     const int tiles_x = (tg.width + 15) / 16, tiles_y = (tg.height + 15) / 16;
     const long long tiles = (long long)tiles_x * tiles_y * h.nframes;
-    const dim3 grid((unsigned)(tiles < (1 << 20) ? tiles : (1 << 20)));
+    const dim3 grid((unsigned)strided_blocks(tiles));
     if (sc.all_opaque && !sc.checked && li.kernel_choice == 0 && sc.stack_depth <= 32) {
-        // the packet walk, as launch_composite_fixed sets it up; frames per launch: what the numerator scratch holds
-        PacketArgs pk;
-        pk.tiles_x = (tg.width + 7) / 8;
-        pk.tiles_y = (tg.height + 7) / 8;
-        pk.quads_x = (pk.tiles_x + 1) / 2;
-        pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
-        pk.order = li.tile_order;
-        pk.frame_major = li.frame_major;
-        pk.numer = nullptr;
-        pk.n_batches = sc.n_batches;
-        pk.lds_per_wave = (int)((size_t)NT_WM * 16 + (size_t)32 * 32);
-        int chunk = h.nframes;
-        if (li.numer_buf && li.numer_frames > 0 && li.numer_frames < chunk) chunk = li.numer_frames;
+        // the packet walk (packet_args, packet_chunk and packet_chunk_head of nt_composite.hpp); frames per launch: what the
+        // numerator scratch holds
+        PacketArgs pk = packet_args(li, sc, tg.width, tg.height);
+        const int chunk = packet_chunk(li, h.nframes, false);
         for (int f0 = 0; f0 < h.nframes; f0 += chunk) {
-            const int cnt = h.nframes - f0 < chunk ? h.nframes - f0 : chunk;
-            pk.cams = h.cams + (size_t)f0 * 4 * N;
-            pk.nframes = cnt;
+            const int cnt = packet_chunk_head<N>(li, sc, pk, h.cams, f0, chunk, h.nframes);
             pk.hits_out = reinterpret_cast<float4 *>(h.hits) + (long long)f0 * h.frame_stride;
-            if (li.numer_buf && li.numer_frames > 0 && sc.n_batches > 0) {
-                const long long total = (long long)sc.n_batches * NT_DEV_BATCH;
-                hipLaunchKernelGGL((packet_numerators<N>), dim3((unsigned)((total + 255) / 256), (unsigned)cnt), dim3(256), 0, s,
-                                   sc, pk.cams, li.numer_buf);
-                pk.numer = li.numer_buf;
-            }
-            const dim3 pgrid((unsigned)((long long)pk.quads * cnt));
+            const dim3 pgrid = packet_grid(pk, cnt);
             if (sc.has_scalar_prims) hipLaunchKernelGGL((composite_packet<N, 32, false, true, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, tg, pk);
             else hipLaunchKernelGGL((composite_packet<N, 32, false, false, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, tg, pk);
         }
@@ -203,16 +186,10 @@ int launch_hits_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         return 0;
     }
     // per wave what the per-lane render kernels use: stack [depth + 1][64], ray table, mailbox
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    if (lds > 160 * 1024) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
-        return -1;
-    }
+    size_t lds;
+    if (const int r = lane_walk_lds(sc, N, 4, 160 * 1024, lds)) return r;
     if (sc.checked) {
-        // as many blocks as the `checked` scratch has lane columns for, striding over the tiles
-        long long blocks = sc.checked_lanes / 256;
-        if (blocks > tiles) blocks = tiles;
-        const dim3 tgrid((unsigned)blocks);
+        const dim3 tgrid((unsigned)checked_column_blocks(sc, 256, tiles));
         if (sc.alias_normals) hipLaunchKernelGGL((hits_closest_t<N, true>), tgrid, dim3(256), lds, s, sc, tg, h, tiles_x, tiles_y);
         else hipLaunchKernelGGL((hits_closest_t<N, false>), tgrid, dim3(256), lds, s, sc, tg, h, tiles_x, tiles_y);
         return 0;

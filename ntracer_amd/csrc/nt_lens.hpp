@@ -62,8 +62,8 @@ __global__ __launch_bounds__(256) NT_SHADE_OCC void lens_shade(NtCompositeDev sc
 }
 
 // tg: the whole image of every frame (row_begin 0, row_count = height, no bands); li.hit_buf: li.hit_frames frames of
-// width * height records.  Frames are chunked by what the hit and numerator scratch hold, as launch_composite_fixed chunks
-// its two-pass route.
+// width * height records.  Frames are chunked by what the hit and numerator scratch hold (packet_chunk), and the
+// walk is set up by packet_args and packet_chunk_head of nt_composite.hpp.
 template <int N>
 int launch_lens_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLens &ln) {
     if (!sc.all_opaque || sc.checked || sc.stack_depth > 32 || !li.hit_buf || li.hit_frames < 1 || !ln.cams || !ln.table ||
@@ -71,41 +71,20 @@ int launch_lens_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a lens render that is not for the packet walk");
         return -1;
     }
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    const bool feat = sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+    const size_t lds = 4 * wave_lds_bytes(sc.stack_depth, N);
+    const bool feat = scene_feat(sc);
     hipStream_t s = (hipStream_t)li.stream;
-    PacketArgs pk;
-    pk.tiles_x = (tg.width + 7) / 8;
-    pk.tiles_y = (tg.height + 7) / 8;
-    pk.quads_x = (pk.tiles_x + 1) / 2;
-    pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
-    pk.order = li.tile_order;
-    pk.frame_major = li.frame_major;
-    pk.numer = nullptr;
-    pk.n_batches = sc.n_batches;
-    pk.lds_per_wave = (int)((size_t)NT_WM * 16 + (size_t)32 * 32);
+    PacketArgs pk = packet_args(li, sc, tg.width, tg.height);
     pk.hits_out = (float4 *)li.hit_buf;
     pk.lens = ln.table;
-    int chunk = li.nframes;
-    if (li.hit_frames < chunk) chunk = li.hit_frames;
-    if (li.numer_buf && li.numer_frames > 0 && li.numer_frames < chunk) chunk = li.numer_frames;
-    NtTarget th = tg;                                      // the walk's view of the records: a frame of them every ...
-    th.frame_stride = (long long)16 * tg.width * tg.height;    // ... this many bytes
+    const int chunk = packet_chunk(li, li.nframes, true);
+    const NtTarget th = packet_record_view(tg, (long long)tg.width * tg.height);
     for (int f0 = 0; f0 < li.nframes; f0 += chunk) {
-        const int cnt = li.nframes - f0 < chunk ? li.nframes - f0 : chunk;
-        pk.cams = ln.cams + (size_t)f0 * 4 * N;
-        pk.nframes = cnt;
-        if (li.numer_buf && li.numer_frames > 0 && sc.n_batches > 0) {
-            const long long total = (long long)sc.n_batches * NT_DEV_BATCH;
-            hipLaunchKernelGGL((packet_numerators<N>), dim3((unsigned)((total + 255) / 256), (unsigned)cnt), dim3(256), 0, s,
-                               sc, pk.cams, li.numer_buf);
-            pk.numer = li.numer_buf;
-        }
-        const dim3 pgrid((unsigned)((long long)pk.quads * cnt));
+        const int cnt = packet_chunk_head<N>(li, sc, pk, ln.cams, f0, chunk, li.nframes);
+        const dim3 pgrid = packet_grid(pk, cnt);
         if (sc.has_scalar_prims) hipLaunchKernelGGL((composite_packet<N, 32, false, true, true, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, th, pk);
         else hipLaunchKernelGGL((composite_packet<N, 32, false, false, true, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, th, pk);
-        NtTarget t2 = tg;
-        t2.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        const NtTarget t2 = chunk_target(tg, f0);
         NtLens l2 = ln;
         l2.cams = pk.cams;
         l2.hits = li.hit_buf;

@@ -317,34 +317,20 @@ int launch_parallel_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, cons
         snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a parallel render that is not for the packet walk");
         return -1;
     }
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    const bool feat = sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+    const size_t lds = 4 * wave_lds_bytes(sc.stack_depth, N);
+    const bool feat = scene_feat(sc);
     hipStream_t s = (hipStream_t)li.stream;
-    PacketArgs pk;
-    pk.tiles_x = (tg.width + 7) / 8;
-    pk.tiles_y = (tg.height + 7) / 8;
-    pk.quads_x = (pk.tiles_x + 1) / 2;
-    pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
-    pk.order = li.tile_order;
-    pk.frame_major = li.frame_major;
-    pk.numer = nullptr;
-    pk.n_batches = sc.n_batches;
-    pk.lds_per_wave = (int)((size_t)NT_WM * 16 + (size_t)32 * 32);
+    PacketArgs pk = packet_args(li, sc, tg.width, tg.height);
     pk.hits_out = (float4 *)li.hit_buf;
-    pk.lens = nullptr;
-    int chunk = li.nframes;
-    if (li.hit_frames < chunk) chunk = li.hit_frames;
-    NtTarget th = tg;                                      // the walk's view of the records: a frame of them every ...
-    th.frame_stride = (long long)16 * tg.width * tg.height;    // ... this many bytes
+    // (this walk reads no numerators: the hit scratch alone decides the chunk, and packet_frames is the whole chunk head)
+    const int chunk = li.hit_frames < li.nframes ? li.hit_frames : li.nframes;
+    const NtTarget th = packet_record_view(tg, (long long)tg.width * tg.height);
     for (int f0 = 0; f0 < li.nframes; f0 += chunk) {
-        const int cnt = li.nframes - f0 < chunk ? li.nframes - f0 : chunk;
-        pk.cams = pl.cams + (size_t)f0 * 4 * N;
-        pk.nframes = cnt;
-        const dim3 pgrid((unsigned)((long long)pk.quads * cnt));
+        const int cnt = packet_frames<N>(pk, pl.cams, f0, chunk, li.nframes);
+        const dim3 pgrid = packet_grid(pk, cnt);
         if (sc.has_scalar_prims) hipLaunchKernelGGL((parallel_packet<N, 32, true>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, th, pk);
         else hipLaunchKernelGGL((parallel_packet<N, 32, false>), pgrid, dim3(256), (size_t)4 * pk.lds_per_wave, s, sc, th, pk);
-        NtTarget t2 = tg;
-        t2.dest = tg.dest + (long long)f0 * tg.frame_stride;
+        const NtTarget t2 = chunk_target(tg, f0);
         NtParallel p2 = pl;
         p2.cams = pk.cams;
         p2.hits = li.hit_buf;

@@ -193,11 +193,8 @@ __global__ __launch_bounds__(256) void query_occluded_t(NtCompositeDev sc, NtQue
 template <int N>
 int launch_query_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtQuery &q) {
     // per wave what the per-lane render kernels use: stack [depth + 1][64], ray table, mailbox
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    if (lds > 160 * 1024) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
-        return -1;
-    }
+    size_t lds;
+    if (const int r = lane_walk_lds(sc, N, 4, 160 * 1024, lds)) return r;
     hipStream_t s = (hipStream_t)li.stream;
     const dim3 grid((unsigned)(((long long)q.count + 255) / 256));
     if (q.occlusion) {

@@ -118,23 +118,15 @@ __global__ __launch_bounds__(256) void rays_box(NtRayJob job, NtTarget tg) {
     }
 }
 
-// at most this many blocks of the kernels that keep no per-lane scratch: beyond it they stride
-#define NT_RAYS_MAX_BLOCKS (1 << 20)
-
 template <int N>
 int launch_rays_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtRayJob &job, const NtTarget &tg) {
     // per wave what the per-lane render kernels use: stack [depth + 1][64], ray table, mailbox
-    const size_t lds = (size_t)4 * 64 * ((size_t)sc.stack_depth * 4 + (size_t)N * 8 + (size_t)NT_MBOX * 4);
-    if (lds > 160 * 1024) {
-        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "k-d tree too deep for the LDS traversal stack (depth %d)", sc.stack_depth);
-        return -1;
-    }
+    size_t lds;
+    if (const int r = lane_walk_lds(sc, N, 4, 160 * 1024, lds)) return r;
     hipStream_t s = (hipStream_t)li.stream;
-    long long blocks = ((long long)job.count + 255) / 256;
+    const long long blocks = ((long long)job.count + 255) / 256;
     if (sc.checked) {
-        // as many blocks as the `checked` scratch has lane columns for, striding over the rays
-        if (blocks > sc.checked_lanes / 256) blocks = sc.checked_lanes / 256;
-        const dim3 tgrid((unsigned)blocks);
+        const dim3 tgrid((unsigned)checked_column_blocks(sc, 256, blocks));
         if (sc.alias_normals) hipLaunchKernelGGL((rays_color_t<N, true>), tgrid, dim3(256), lds, s, sc, job, tg);
         else hipLaunchKernelGGL((rays_color_t<N, false>), tgrid, dim3(256), lds, s, sc, job, tg);
         return 0;
@@ -143,9 +135,8 @@ int launch_rays_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: transparent scene without the checked-list scratch");
         return -1;
     }
-    if (blocks > NT_RAYS_MAX_BLOCKS) blocks = NT_RAYS_MAX_BLOCKS;
-    const dim3 grid((unsigned)blocks);
-    const bool feat = sc.n_point_lights || sc.n_global_lights || sc.any_reflective || sc.has_scalar_prims;
+    const dim3 grid((unsigned)strided_blocks(blocks));
+    const bool feat = scene_feat(sc);
     if (feat && !sc.has_scalar_prims) hipLaunchKernelGGL((rays_color<N, true, false>), grid, dim3(256), lds, s, sc, job, tg);
     else if (feat) hipLaunchKernelGGL((rays_color<N, true, true>), grid, dim3(256), lds, s, sc, job, tg);
     else hipLaunchKernelGGL((rays_color<N, false, false>), grid, dim3(256), lds, s, sc, job, tg);

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256, 4) void xray_packet(NtCompositeDev sc, NtTarge
 }
 
 // tg: the whole image of every frame (row_begin 0, row_count = height, no bands), or with xr.counts the view alone.  Frames are
-// chunked by what the numerator scratch holds, as launch_outline_fixed chunks them.
+// chunked by what the numerator scratch holds (packet_chunk); the walk is set up by packet_args and packet_chunk_head of nt_composite.hpp.
 template <int N>
 int launch_xray_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtXray &xr) {
     const long long items = (long long)sc.n_batches + sc.n_triangles + sc.n_solids;
@@ -293,41 +293,19 @@ int launch_xray_fixed(const NtLaunchInfo &li, const NtCompositeDev &sc, const Nt
         return -1;
     }
     hipStream_t s = (hipStream_t)li.stream;
-    PacketArgs pk;
-    pk.tiles_x = (tg.width + 7) / 8;
-    pk.tiles_y = (tg.height + 7) / 8;
-    pk.quads_x = (pk.tiles_x + 1) / 2;
-    pk.quads = pk.quads_x * ((pk.tiles_y + 1) / 2);
-    pk.order = li.tile_order;
-    pk.frame_major = li.frame_major;
-    pk.hits_out = nullptr;
-    pk.numer = nullptr;
-    pk.n_batches = sc.n_batches;
+    PacketArgs pk = packet_args(li, sc, tg.width, tg.height);
     pk.lds_per_wave = (int)xray_lds_per_wave(items);
-    pk.lens = nullptr;
-    pk.clip = nullptr;
-    pk.clip_count = 0;
     const int seen_words = (int)((items + 127) / 128) * 4;
     const size_t lds = (size_t)4 * pk.lds_per_wave;          // at most 4 * (1 + 8) KiB: under the 64 KiB a kernel gets unasked
     const bool scal = sc.has_scalar_prims || sc.n_solids > 0;      // (a Solid counts even where no leaf holds it)
-    int chunk = li.nframes;
-    if (li.numer_buf && li.numer_frames > 0 && li.numer_frames < chunk) chunk = li.numer_frames;
+    const int chunk = packet_chunk(li, li.nframes, false);
     const long long px = (long long)tg.width * tg.height;
     for (int f0 = 0; f0 < li.nframes; f0 += chunk) {
-        const int cnt = li.nframes - f0 < chunk ? li.nframes - f0 : chunk;
-        pk.cams = xr.cams + (size_t)f0 * 4 * N;
-        pk.nframes = cnt;
-        if (li.numer_buf && li.numer_frames > 0 && sc.n_batches > 0) {
-            const long long total = (long long)sc.n_batches * NT_DEV_BATCH;
-            hipLaunchKernelGGL((packet_numerators<N>), dim3((unsigned)((total + 255) / 256), (unsigned)cnt), dim3(256), 0, s,
-                               sc, pk.cams, li.numer_buf);
-            pk.numer = li.numer_buf;
-        }
-        NtTarget t2 = tg;
+        const int cnt = packet_chunk_head<N>(li, sc, pk, xr.cams, f0, chunk, li.nframes);
+        const NtTarget t2 = xr.counts ? tg : chunk_target(tg, f0);
         NtXray x2 = xr;
         if (xr.counts) x2.counts = xr.counts + (long long)f0 * px;
-        else t2.dest = tg.dest + (long long)f0 * tg.frame_stride;
-        const dim3 pgrid((unsigned)((long long)pk.quads * cnt));
+        const dim3 pgrid = packet_grid(pk, cnt);
         if (xr.counts) {
             if (scal) hipLaunchKernelGGL((xray_packet<N, 32, true, true>), pgrid, dim3(256), lds, s, sc, t2, pk, x2, seen_words);
             else hipLaunchKernelGGL((xray_packet<N, 32, false, true>), pgrid, dim3(256), lds, s, sc, t2, pk, x2, seen_words);

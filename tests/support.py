@@ -35,6 +35,20 @@ def launches(body):
     return {re.sub(r"\s+", "", n) for n in names}
 
 
+# the helpers of the fixed-n launchers' shared set-up (nt_composite.hpp) that launch a kernel themselves
+SHARED_LAUNCHERS = ("packet_chunk_head",)
+
+
+def launches_through(src, head):
+    """launches() of the function that starts with `head`, and of every shared helper that its body calls"""
+    body = function_body(src, head)
+    names = launches(body)
+    for helper in SHARED_LAUNCHERS:
+        if re.search(r"\b%s\s*(<[^<>;()]*>)?\s*\(" % helper, body):
+            names |= launches(function_body(source("nt_composite.hpp"), "int %s(" % helper))
+    return names
+
+
 # ---- formats and renders
 
 def fmt_of(w, h, chans=fx.RGBX8, pitch=0, rev=False):

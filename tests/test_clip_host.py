@@ -454,7 +454,7 @@ def test_the_clip_launches_are_kept_apart_from_the_existing_launchers():
                       (sup.source("nt_hits.hpp"), "int launch_hits_fixed("), (sup.source("nt_cue.hpp"), "int launch_cue_fixed(")):
         body = sup.function_body(src, head)
         assert "clip" not in body.lower().replace("nt_clipplanes{nullptr,0}", "").replace("ntclipplanes{nullptr, 0}", ""), head
-    fixed = sorted(sup.launches(sup.function_body(sup.source("nt_clip.hpp"), "int launch_clip_fixed(")))
+    fixed = sorted(sup.launches_through(sup.source("nt_clip.hpp"), "int launch_clip_fixed("))
     assert fixed == sorted(["packet_numerators<N>", "composite_packet<N,32,false,true,true,false,true>", "composite_packet<N,32,false,false,true,false,true>",
                             "clip_shade<N,false,false>", "clip_shade<N,true,true>", "clip_shade<N,true,false>", "hits_normals<N,true>",
                             "hits_normals<N,false>"])

@@ -26,7 +26,7 @@ def _reader():
 
 
 def test_every_composite_launch_has_a_matrix_row():
-    launched = sup.launches(_fixed()) | sup.launches(_var())
+    launched = sup.launches_through(sup.source("nt_composite.hpp"), "int launch_composite_fixed(") | sup.launches(_var())
     assert len(launched) >= 14, sorted(launched)            # the scan still finds the launches
     rows = [k for k, _ in fx.COMPOSITE_ROUTES]
     assert len(rows) == len(set(rows)), "duplicate rows"
@@ -86,9 +86,14 @@ def test_the_thresholds_the_deep_rows_are_built_around():
     # (launched as composite_packet<N, 32, ...>: DEPTH = 32, pinned by the rows' names)
     hpp = sup.source("nt_composite.hpp")
     assert re.search(r"if \(m_far != 0ull && sp < DEPTH\)", hpp)
-    # the per-lane kernels' LDS: 256 lanes x (4 stack_depth + 8 N + 4 NT_MBOX) bytes, refused beyond 160 KiB
-    assert re.search(r"lds = \(size_t\)4 \* 64 \* \(\(size_t\)sc\.stack_depth \* 4 \+ \(size_t\)N \* 8 \+ \(size_t\)NT_MBOX \* 4\);", fixed)
-    assert re.search(r"if \(lds > 160 \* 1024\) \{\s*snprintf\([^;]*\"k-d tree too deep for the LDS traversal stack", fixed)
+    # the per-lane kernels' LDS: 256 lanes x (4 stack_depth + 8 N + 4 NT_MBOX) bytes, refused beyond 160 KiB -- four waves of
+    # wave_lds_bytes, the function the kernels carve by, through lane_walk_lds, which holds the refusal
+    assert re.search(r"if \(const int r = lane_walk_lds\(sc, N, 4, 160 \* 1024, lds\)\) return r;", fixed)
+    per_wave = sup.function_body(hpp, "__host__ __device__ __forceinline__ size_t wave_lds_bytes(int stack_depth, int n)")
+    assert re.search(r"return \(size_t\)64 \* \(\(size_t\)stack_depth \* 4 \+ \(size_t\)n \* 8 \+ \(size_t\)NT_MBOX \* 4\);", per_wave)
+    walk = sup.function_body(hpp, "inline int lane_walk_lds(const NtCompositeDev &sc, int n, int waves, size_t limit, size_t &lds)")
+    assert re.search(r"lds = \(size_t\)waves \* wave_lds_bytes\(sc\.stack_depth, n\);\s*if \(lds <= limit\) return 0;\s*"
+                     r"snprintf\([^;]*\"k-d tree too deep for the LDS traversal stack \(depth %d\)\", sc\.stack_depth\);\s*return -1;", walk)
     assert re.search(r"#define NT_MBOX 16\b", hpp)
     # ... so the deepest tree that fits at N = 10 has stack_depth 124
     n, sd = 10, fx.COMPOSITE_MAX_DEPTH_N10

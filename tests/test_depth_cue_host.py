@@ -76,7 +76,7 @@ def _render_route(name, variant):
 
 def test_every_cue_launch_has_a_row_and_every_row_a_gpu_case():
     var = sup.source("nt_var.hip")
-    launched = sup.launches(sup.function_body(sup.source("nt_cue.hpp"), "int launch_cue_fixed("))
+    launched = sup.launches_through(sup.source("nt_cue.hpp"), "int launch_cue_fixed(")
     assert len(launched) == 7
     for head in ("int nt_launch_cue(", "int nt_launch_cue_factors_fixed(", "static int nt_launch_cue_packet(", "int nt_launch_cue_factors(",
                  "int nt_launch_cue_apply("):

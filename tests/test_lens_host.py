@@ -16,6 +16,7 @@ import lens_cases as lc
 import oracle_binding as ob
 import ray_color_cases as rc
 import ray_query_cases as rq
+import support as sup
 import ntracer_amd
 from ntracer_amd import Channel, ImageFormat, Lens, _lib, tracern
 
@@ -63,7 +64,7 @@ def test_the_header_declares_and_the_library_exports_the_entry_points():
 
 def test_every_lens_launch_is_reached_by_a_case():
     hpp, var = _read("nt_lens.hpp"), _read("nt_var.hip")
-    packet = _launches(_body(hpp, "int launch_lens_fixed("))
+    packet = sup.launches_through(hpp, "int launch_lens_fixed(")      # (with the numerators of the shared chunk head)
     helpers = _launches(_body(var, "int nt_launch_lens_expand(")) | _launches(_body(var, "int nt_launch_lens_mask("))
     assert packet == {"packet_numerators<N>", "composite_packet<N,32,false,true,true,true>", "composite_packet<N,32,false,false,true,true>",
                       "lens_shade<N,false,false>", "lens_shade<N,true,true>", "lens_shade<N,true,false>"}, sorted(packet)

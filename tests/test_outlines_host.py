@@ -79,7 +79,7 @@ def _render_route(name, variant):
 
 def test_every_outline_launch_has_a_row_and_every_row_a_gpu_case():
     var = sup.source("nt_var.hip")
-    launched = sup.launches(sup.function_body(sup.source("nt_outline.hpp"), "int launch_outline_fixed("))
+    launched = sup.launches_through(sup.source("nt_outline.hpp"), "int launch_outline_fixed(")
     assert len(launched) == 8
     for head in ("int nt_launch_outline(", "int nt_launch_outline_mask(", "static int nt_launch_outline_fixed(", "int nt_launch_outline_mark(",
                  "int nt_launch_outline_apply("):

@@ -41,7 +41,7 @@ def test_the_header_declares_and_the_library_exports_the_entry_points():
 
 def test_every_parallel_launch_is_reached_by_a_case():
     hpp, var = sup.source("nt_parallel.hpp"), sup.source("nt_var.hip")
-    packet = sup.launches(sup.function_body(hpp, "int launch_parallel_fixed("))
+    packet = sup.launches_through(hpp, "int launch_parallel_fixed(")          # (no numerators: not through the shared chunk head)
     helper = sup.launches(sup.function_body(var, "int nt_launch_parallel_expand("))
     assert packet == {"parallel_packet<N,32,true>", "parallel_packet<N,32,false>",
                       "parallel_shade<N,false,false>", "parallel_shade<N,true,true>", "parallel_shade<N,true,false>"}, sorted(packet)

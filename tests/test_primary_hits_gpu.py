@@ -146,10 +146,11 @@ def test_hits_equal_the_oracle(case):
             assert np.array_equal(hits2, hits), label + ": the records depend on whether normals were asked for"
 
 
-@pytest.mark.parametrize("case", [("cell600_n4", {}), ("feature5_n5", {})], ids=ph.case_id)
+@pytest.mark.parametrize("case", [("cell600_n4", {}), ("cell600_n4", {"NTRACER_CHUNK_FRAMES": "1"}), ("feature5_n5", {})], ids=ph.case_id)
 def test_frames_of_a_camera_table(case):
     """three golden cameras in a table, frames [1, 3) of it in one launch, more than a frame's records between the frames: the
-    packet walk and a per-lane walk"""
+    packet walk, the packet walk a frame a chunk (launch_hits_fixed's own loop: the offsets of the second chunk into the
+    records, the cameras and the numerator scratch) and a per-lane walk"""
     import torch
     name, env = case
     g, n, flat = rq.scene(name)

@@ -69,7 +69,7 @@ def _routes(name, env):
 
 
 def test_every_hits_launch_has_a_row_and_every_row_a_gpu_case():
-    launched = sup.launches(sup.function_body(sup.source("nt_hits.hpp"), "int launch_hits_fixed(")) | sup.launches(sup.function_body(sup.source("nt_var.hip"), "int nt_launch_hits("))
+    launched = sup.launches_through(sup.source("nt_hits.hpp"), "int launch_hits_fixed(") | sup.launches(sup.function_body(sup.source("nt_var.hip"), "int nt_launch_hits("))
     rows = [k for k, _ in HITS_ROUTES]
     assert len(rows) == len(set(rows)) == 12
     assert set(rows) == launched, (sorted(launched - set(rows)), sorted(set(rows) - launched))
