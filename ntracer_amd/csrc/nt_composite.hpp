@@ -421,6 +421,97 @@ struct RootWindow {
     __device__ __forceinline__ float t_far() const { return tf; }
 };
 
+// ---- The per-lane k-d walk's control, shared by trace_closest_t here and by the four run-time-n walkers of nt_var.hip
+// (trace_closest_var, trace_occluded_var and their _t forms): nothing in it depends on the dimension.  The wave-uniform walks
+// (composite_packet, xray_packet) are another algorithm -- ballots over `go_near` -- and keep their own text.  So do, for what
+// the helpers cost them when measured, trace_closest<N>, trace_occluded<N>, trace_occluded_t<N> and the walk of xray_var
+// (profiles/kd_walk_ab.jsonl, profiles/kd_walk_codeobjects.txt; tests/test_kd_walk_host.py lists them), and composite_persistent,
+// whose state machine pops one frame a turn: a correction to the step or to a pop is made in those as well.
+//
+// One step at branch `nd` (tracer.hpp:1191-1240, :1264-1304): which child the frame goes on with.  Where the ray enters both
+// sides the branch is pushed (`tag` ORed into the entry: 0u on a plain stack) and the near child is next, up to the split.
+// `crossed` when the ray crosses the split at `t` and there is NO near child: `node` is the far child then, and the caller applies
+// its own rule -- the closest walks go on with t_near = t, the occlusion walks first leave the frame if t < ldistance (:1298).
+// The reference's quirks live here: the `oa == split` tie, NaN in the table for direction[axis] == 0, and the order of the tests.
+// (The form is the one the register allocation tolerates.  `t` comes back by value: handed back through a reference it stayed
+// live around the whole walk, leaf loops included.  And the walkers call kd_t_far_below after their pop: nested inside the pop
+// helpers it took trace_closest<4> from 120 to 149 VGPRs.)
+struct KdStep { bool crossed; float t; };
+__device__ __forceinline__ KdStep kd_descend(const WaveLds &w, int lane, const NtNode &nd, int &node, int &sp, int max_sp, float t_near,
+                                             float &t_far, unsigned tag) {
+    const float2 oi = w.ray[nd.axis * 64 + lane];
+    const float oa = oi.x, inv = oi.y;
+    if (inv == inv) {                       // direction[axis] != 0
+        if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; return {false, 0.0f}; }
+        const float t = (nd.split - oa) * inv;
+        const bool gt = oa > nd.split;
+        const int n_near = gt ? nd.right : nd.left;
+        const int n_far = gt ? nd.left : nd.right;
+        if (t < 0.0f || t > t_far) { node = n_near; return {false, t}; }
+        if (t < t_near) { node = n_far; return {false, t}; }
+        if (n_near >= 0) {
+            if (sp < max_sp) {              // always true: depth <= tree depth (host-checked)
+                w.stack[sp * 64 + lane] = (int)((unsigned)node | tag);
+                ++sp;
+            }
+            t_far = t;
+            node = n_near;
+            return {false, t};
+        }
+        node = n_far;
+        return {true, t};
+    }
+    node = oa >= nd.split ? nd.right : nd.left;
+    return {false, 0.0f};
+}
+
+// t_far of a frame resumed with `sp` entries left on a plain stack: the split of the branch below it, or the root's
+__device__ __forceinline__ float kd_t_far_below(const NtCompositeDev &sc, const WaveLds &w, int lane, int sp, float t_far_root) {
+    if (sp > 0) {
+        const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
+        bool g2;
+        return branch_t(w, lane, up, g2);
+    }
+    return t_far_root;
+}
+
+// The current frame has returned: resume the innermost continuation of a closest-hit walk (tracer.hpp:1213-1237).  A frame
+// whose near side found a hit no farther than its split, or that has no far child, returns in turn.  False: the root returned.
+__device__ __forceinline__ bool kd_resume_closest(const NtCompositeDev &sc, const WaveLds &w, int lane, int &node, int &sp, int &dirty,
+                                                  const float &hit_dist, float &t_near) {
+    while (sp > 0) {
+        --sp;
+        const NtNode nd = sc.nodes[w.stack[sp * 64 + lane]];
+        bool gt;
+        const float t = branch_t(w, lane, nd, gt);
+        const int far = gt ? nd.left : nd.right;
+        const bool near_hit = sp < dirty;
+        if (dirty > sp) dirty = sp;
+        if ((near_hit && hit_dist <= t) || far < 0) continue;     // frame returns `hit`
+        node = far;
+        t_near = t;
+        return true;
+    }
+    return false;
+}
+
+// The same for an occlusion walk (tracer.hpp:1294-1301): the far child is skipped whenever the split lies nearer than the light.
+__device__ __forceinline__ bool kd_resume_occluded(const NtCompositeDev &sc, const WaveLds &w, int lane, int &node, int &sp, float ldistance,
+                                                   float &t_near) {
+    while (sp > 0) {
+        --sp;
+        const NtNode nd = sc.nodes[w.stack[sp * 64 + lane]];
+        bool gt;
+        const float t = branch_t(w, lane, nd, gt);
+        const int far = gt ? nd.left : nd.right;
+        if (t < ldistance || far < 0) continue;             // frame returns false
+        node = far;
+        t_near = t;
+        return true;
+    }
+    return false;
+}
+
 template <int N, bool FEAT, bool STATS, bool SCALP = FEAT, typename CLIP = ClipOff>
 __device__ __noinline__ bool trace_closest(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
                                               float t_near, float t_far_root, int skip_item, int skip_lane, Hit &hit, Stats &st) {
@@ -1190,6 +1281,51 @@ __device__ __noinline__ bool leaf_closest_t(const NtCompositeDev &sc, const Wave
 // kd_node_intersection::operator() with the transparent-list trims (tracer.hpp:1211-1231).  Stack entries:
 // branch index | list size at the push << 24; NT_STK_MARK marks "far side of this branch is being walked
 // after a near hit: trim the list when it returns with a closer hit".
+//
+// t_far of a frame resumed on the tagged stack: the split of the nearest pending (non-marker) branch at or below entry `k`
+__device__ __forceinline__ float kd_t_far_below_tagged(const NtCompositeDev &sc, const WaveLds &w, int lane, int k, float t_far_root) {
+    for (; k >= 0; --k) {
+        const unsigned ek = (unsigned)w.stack[k * 64 + lane];
+        if (!(ek & NT_STK_MARK)) {
+            const NtNode up = sc.nodes[ek & 0xffffffu];
+            bool g2;
+            return branch_t(w, lane, up, g2);
+        }
+    }
+    return t_far_root;
+}
+
+// kd_resume_closest on the tagged stack (tracer.hpp:1212-1237)
+__device__ __forceinline__ bool kd_resume_tagged(const NtCompositeDev &sc, const WaveLds &w, int lane, int &node, int &sp, int &dirty,
+                                                 const float &hit_dist, TList &th, float &t_near, float &t_far, float t_far_root) {
+    while (sp > 0) {
+        --sp;
+        const unsigned e = (unsigned)w.stack[sp * 64 + lane];
+        const bool improved = sp < dirty;
+        if (dirty > sp) dirty = sp;
+        const int h_start = (int)((e >> 24) & 0x7fu);
+        if (e & NT_STK_MARK) {
+            // the far call of tracer.hpp:1225 has returned
+            if (improved) tl_trim(th, hit_dist, h_start);
+            continue;                                           // return true
+        }
+        const NtNode nd = sc.nodes[e & 0xffffffu];
+        bool gt;
+        const float t = branch_t(w, lane, nd, gt);
+        const int far = gt ? nd.left : nd.right;
+        if ((improved && hit_dist <= t) || far < 0) continue;   // return hit
+        if (improved) {                                         // near hit beyond the split: walk far, then trim
+            w.stack[sp * 64 + lane] = (int)(e | NT_STK_MARK);
+            ++sp;
+        }
+        node = far;
+        t_near = t;
+        t_far = kd_t_far_below_tagged(sc, w, lane, improved ? sp - 2 : sp - 1, t_far_root);
+        return true;
+    }
+    return false;
+}
+
 template <int N, bool ALIAS, typename ROOT = RootWhole>
 __device__ __noinline__ bool trace_closest_t(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
                                              float t_near, int skip_item, int skip_lane, Hit &hit, TList &th, const Checked &ck,
@@ -1212,74 +1348,17 @@ __device__ __noinline__ bool trace_closest_t(const NtCompositeDev &sc, const Wav
                 node = -1;
                 break;
             }
-            const float2 oi = w.ray[nd.axis * 64 + lane];
-            const float oa = oi.x, inv = oi.y;
-            if (inv == inv) {
-                if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; continue; }
-                const float t = (nd.split - oa) * inv;
-                const bool gt = oa > nd.split;
-                const int n_near = gt ? nd.right : nd.left;
-                const int n_far = gt ? nd.left : nd.right;
-                if (t < 0.0f || t > t_far) { node = n_near; continue; }
-                if (t < t_near) { node = n_far; continue; }
-                if (n_near >= 0) {
-                    if (sp < max_sp) {
-                        w.stack[sp * 64 + lane] = (int)((unsigned)node | ((unsigned)th.n << 24));
-                        ++sp;
-                    }
-                    t_far = t;
-                    node = n_near;
-                    continue;
-                }
-                node = n_far;
-                t_near = t;
-                continue;
-            }
-            node = oa >= nd.split ? nd.right : nd.left;
+            const KdStep s = kd_descend(w, lane, nd, node, sp, max_sp, t_near, t_far, (unsigned)th.n << 24);
+            if (s.crossed) t_near = s.t;
         }
-        bool resumed = false;
-        while (sp > 0) {
-            --sp;
-            const unsigned e = (unsigned)w.stack[sp * 64 + lane];
-            const bool improved = sp < dirty;
-            if (dirty > sp) dirty = sp;
-            const int h_start = (int)((e >> 24) & 0x7fu);
-            if (e & NT_STK_MARK) {
-                // the far call of tracer.hpp:1225 has returned
-                if (improved) tl_trim(th, hit.dist, h_start);
-                continue;                                           // return true
-            }
-            const NtNode nd = sc.nodes[e & 0xffffffu];
-            bool gt;
-            const float t = branch_t(w, lane, nd, gt);
-            const int far = gt ? nd.left : nd.right;
-            if ((improved && hit.dist <= t) || far < 0) continue;   // return hit
-            if (improved) {                                         // near hit beyond the split: walk far, then trim
-                w.stack[sp * 64 + lane] = (int)(e | NT_STK_MARK);
-                ++sp;
-            }
-            node = far;
-            t_near = t;
-            // t_far of this frame: the split of the nearest pending (non-marker) branch below
-            t_far = root.t_far();
-            for (int k = (improved ? sp - 2 : sp - 1); k >= 0; --k) {
-                const unsigned ek = (unsigned)w.stack[k * 64 + lane];
-                if (!(ek & NT_STK_MARK)) {
-                    const NtNode up = sc.nodes[ek & 0xffffffu];
-                    bool g2;
-                    t_far = branch_t(w, lane, up, g2);
-                    break;
-                }
-            }
-            resumed = true;
-            break;
-        }
-        if (!resumed) break;
+        if (!kd_resume_tagged(sc, w, lane, node, sp, dirty, hit.dist, th, t_near, t_far, root.t_far())) break;
     }
     return hit.item >= 0;
 }
 
 // _occludes + kd_leaf::occludes with transparent hits collected (tracer.hpp:1088-1124, 1258-1307)
+// (Carries the text of kd_descend / kd_resume_occluded itself: on the helpers the four query_occluded_t<N> kernels saved 16
+// SGPRs around its call that they had not -- see the note at kd_descend.)
 template <int N, typename ROOT = RootWhole>
 __device__ __noinline__ bool trace_occluded_t(const NtCompositeDev &sc, const WaveLds &w, int lane, const float (&o)[N], const float (&d)[N],
                                               float ldistance, int skip_item, int skip_lane, TList &sh, const ROOT root = ROOT()) {

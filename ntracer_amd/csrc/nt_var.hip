@@ -639,7 +639,7 @@ __device__ __forceinline__ bool leaf_closest_var(const VarCtx &cx, int start, in
     return improved;
 }
 
-// kd_node_intersection::operator() (tracer.hpp:1179-1243): the continuation stack of trace_closest (nt_composite.hpp)
+// kd_node_intersection::operator() (tracer.hpp:1179-1243): the continuation stack of kd_descend / kd_resume_closest (nt_composite.hpp)
 template <typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
@@ -662,50 +662,11 @@ __device__ __noinline__ bool trace_closest_var(const VarCtx &cx, float t_near, i
                 node = -1;
                 break;
             }
-            const float2 oi = w.ray[nd.axis * 64 + lane];
-            const float oa = oi.x, inv = oi.y;
-            if (inv == inv) {
-                if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; continue; }
-                const float t = (nd.split - oa) * inv;
-                const bool gt = oa > nd.split;
-                const int n_near = gt ? nd.right : nd.left;
-                const int n_far = gt ? nd.left : nd.right;
-                if (t < 0.0f || t > t_far) { node = n_near; continue; }
-                if (t < t_near) { node = n_far; continue; }
-                if (n_near >= 0) {
-                    if (sp < max_sp) { w.stack[sp * 64 + lane] = node; ++sp; }
-                    t_far = t;
-                    node = n_near;
-                    continue;
-                }
-                node = n_far;
-                t_near = t;
-                continue;
-            }
-            node = oa >= nd.split ? nd.right : nd.left;
+            const KdStep s = kd_descend(w, lane, nd, node, sp, max_sp, t_near, t_far, 0u);
+            if (s.crossed) t_near = s.t;
         }
-        bool resumed = false;
-        while (sp > 0) {
-            --sp;
-            const NtNode nd = sc.nodes[w.stack[sp * 64 + lane]];
-            bool gt;
-            const float t = branch_t(w, lane, nd, gt);
-            const int far = gt ? nd.left : nd.right;
-            const bool near_hit = sp < dirty;
-            if (dirty > sp) dirty = sp;
-            if ((near_hit && hit.dist <= t) || far < 0) continue;
-            node = far;
-            t_near = t;
-            t_far = root.t_far();
-            if (sp > 0) {
-                const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
-                bool g2;
-                t_far = branch_t(w, lane, up, g2);
-            }
-            resumed = true;
-            break;
-        }
-        if (!resumed) break;
+        if (!kd_resume_closest(sc, w, lane, node, sp, dirty, hit.dist, t_near)) break;
+        t_far = kd_t_far_below(sc, w, lane, sp, root.t_far());
     }
     return hit.item >= 0;
 }
@@ -735,7 +696,8 @@ __device__ __forceinline__ bool leaf_occludes_var(const VarCtx &cx, int start, i
     return false;
 }
 
-// _occludes (tracer.hpp:1258-1307) for the current ray, `if(t < ldistance) return false;` (:1298) included
+// _occludes (tracer.hpp:1258-1307) for the current ray on kd_descend / kd_resume_occluded (nt_composite.hpp),
+// `if(t < ldistance) return false;` (:1298) included
 template <typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistance, int skip_item, int skip_lane, const ROOT root = ROOT()) {
     const NtCompositeDev &sc = cx.sc;
@@ -753,49 +715,14 @@ __device__ __noinline__ bool trace_occluded_var(const VarCtx &cx, float ldistanc
                 node = -1;
                 break;
             }
-            const float2 oi = w.ray[nd.axis * 64 + lane];
-            const float oa = oi.x, inv = oi.y;
-            if (inv == inv) {
-                if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; continue; }
-                const float t = (nd.split - oa) * inv;
-                const bool gt = oa > nd.split;
-                const int n_near = gt ? nd.right : nd.left;
-                const int n_far = gt ? nd.left : nd.right;
-                if (t < 0.0f || t > t_far) { node = n_near; continue; }
-                if (t < t_near) { node = n_far; continue; }
-                if (n_near >= 0) {
-                    if (sp < max_sp) { w.stack[sp * 64 + lane] = node; ++sp; }
-                    t_far = t;
-                    node = n_near;
-                    continue;
-                }
-                if (t < ldistance) { node = -1; break; }
-                t_near = t;
-                node = n_far;
-                continue;
+            const KdStep s = kd_descend(w, lane, nd, node, sp, max_sp, t_near, t_far, 0u);
+            if (s.crossed) {
+                if (s.t < ldistance) { node = -1; break; }
+                t_near = s.t;
             }
-            node = oa >= nd.split ? nd.right : nd.left;
         }
-        bool resumed = false;
-        while (sp > 0) {
-            --sp;
-            const NtNode nd = sc.nodes[w.stack[sp * 64 + lane]];
-            bool gt;
-            const float t = branch_t(w, lane, nd, gt);
-            const int far = gt ? nd.left : nd.right;
-            if (t < ldistance || far < 0) continue;
-            node = far;
-            t_near = t;
-            t_far = root.t_far();
-            if (sp > 0) {
-                const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
-                bool g2;
-                t_far = branch_t(w, lane, up, g2);
-            }
-            resumed = true;
-            break;
-        }
-        if (!resumed) return false;
+        if (!kd_resume_occluded(sc, w, lane, node, sp, ldistance, t_near)) return false;
+        t_far = kd_t_far_below(sc, w, lane, sp, root.t_far());
     }
 }
 
@@ -1199,7 +1126,7 @@ __device__ __noinline__ bool leaf_closest_var_t(const VarCtx &cx, int start, int
     return found;
 }
 
-// trace_closest_t (nt_composite.hpp) for the current ray
+// trace_closest_t (nt_composite.hpp) for the current ray, on the same kd_descend / kd_resume_tagged
 template <bool ALIAS, typename ROOT = RootWhole, bool CLIP = false>
 __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near, int skip_item, int skip_lane, Hit &hit, TList &th,
                                                  const Checked &ck, float *hn_o, float *hn_d, float *nn_o, float *nn_d, const ROOT root = ROOT()) {
@@ -1223,67 +1150,10 @@ __device__ __noinline__ bool trace_closest_var_t(const VarCtx &cx, float t_near,
                 node = -1;
                 break;
             }
-            const float2 oi = w.ray[nd.axis * 64 + lane];
-            const float oa = oi.x, inv = oi.y;
-            if (inv == inv) {
-                if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; continue; }
-                const float t = (nd.split - oa) * inv;
-                const bool gt = oa > nd.split;
-                const int n_near = gt ? nd.right : nd.left;
-                const int n_far = gt ? nd.left : nd.right;
-                if (t < 0.0f || t > t_far) { node = n_near; continue; }
-                if (t < t_near) { node = n_far; continue; }
-                if (n_near >= 0) {
-                    if (sp < max_sp) {
-                        w.stack[sp * 64 + lane] = (int)((unsigned)node | ((unsigned)th.n << 24));
-                        ++sp;
-                    }
-                    t_far = t;
-                    node = n_near;
-                    continue;
-                }
-                node = n_far;
-                t_near = t;
-                continue;
-            }
-            node = oa >= nd.split ? nd.right : nd.left;
+            const KdStep s = kd_descend(w, lane, nd, node, sp, max_sp, t_near, t_far, (unsigned)th.n << 24);
+            if (s.crossed) t_near = s.t;
         }
-        bool resumed = false;
-        while (sp > 0) {
-            --sp;
-            const unsigned e = (unsigned)w.stack[sp * 64 + lane];
-            const bool improved = sp < dirty;
-            if (dirty > sp) dirty = sp;
-            const int h_start = (int)((e >> 24) & 0x7fu);
-            if (e & NT_STK_MARK) {
-                if (improved) tl_trim(th, hit.dist, h_start);
-                continue;
-            }
-            const NtNode nd = sc.nodes[e & 0xffffffu];
-            bool gt;
-            const float t = branch_t(w, lane, nd, gt);
-            const int far = gt ? nd.left : nd.right;
-            if ((improved && hit.dist <= t) || far < 0) continue;
-            if (improved) {
-                w.stack[sp * 64 + lane] = (int)(e | NT_STK_MARK);
-                ++sp;
-            }
-            node = far;
-            t_near = t;
-            t_far = root.t_far();
-            for (int k = (improved ? sp - 2 : sp - 1); k >= 0; --k) {
-                const unsigned ek = (unsigned)w.stack[k * 64 + lane];
-                if (!(ek & NT_STK_MARK)) {
-                    const NtNode up = sc.nodes[ek & 0xffffffu];
-                    bool g2;
-                    t_far = branch_t(w, lane, up, g2);
-                    break;
-                }
-            }
-            resumed = true;
-            break;
-        }
-        if (!resumed) break;
+        if (!kd_resume_tagged(sc, w, lane, node, sp, dirty, hit.dist, th, t_near, t_far, root.t_far())) break;
     }
     return hit.item >= 0;
 }
@@ -1316,49 +1186,14 @@ __device__ __noinline__ bool trace_occluded_var_t(const VarCtx &cx, float ldista
                 node = -1;
                 break;
             }
-            const float2 oi = w.ray[nd.axis * 64 + lane];
-            const float oa = oi.x, inv = oi.y;
-            if (inv == inv) {
-                if (oa == nd.split) { node = inv > 0.0f ? nd.right : nd.left; continue; }
-                const float t = (nd.split - oa) * inv;
-                const bool gt = oa > nd.split;
-                const int n_near = gt ? nd.right : nd.left;
-                const int n_far = gt ? nd.left : nd.right;
-                if (t < 0.0f || t > t_far) { node = n_near; continue; }
-                if (t < t_near) { node = n_far; continue; }
-                if (n_near >= 0) {
-                    if (sp < max_sp) { w.stack[sp * 64 + lane] = node; ++sp; }
-                    t_far = t;
-                    node = n_near;
-                    continue;
-                }
-                if (t < ldistance) { node = -1; break; }
-                t_near = t;
-                node = n_far;
-                continue;
+            const KdStep s = kd_descend(w, lane, nd, node, sp, max_sp, t_near, t_far, 0u);
+            if (s.crossed) {
+                if (s.t < ldistance) { node = -1; break; }
+                t_near = s.t;
             }
-            node = oa >= nd.split ? nd.right : nd.left;
         }
-        bool resumed = false;
-        while (sp > 0) {
-            --sp;
-            const NtNode nd = sc.nodes[w.stack[sp * 64 + lane]];
-            bool gt;
-            const float t = branch_t(w, lane, nd, gt);
-            const int far = gt ? nd.left : nd.right;
-            if (t < ldistance || far < 0) continue;
-            node = far;
-            t_near = t;
-            t_far = root.t_far();
-            if (sp > 0) {
-                const NtNode up = sc.nodes[w.stack[(sp - 1) * 64 + lane]];
-                bool g2;
-                t_far = branch_t(w, lane, up, g2);
-            }
-            resumed = true;
-            break;
-        }
-        if (!resumed) return false;
+        if (!kd_resume_occluded(sc, w, lane, node, sp, ldistance, t_near)) return false;
+        t_far = kd_t_far_below(sc, w, lane, sp, root.t_far());
     }
 }
 
