@@ -287,9 +287,12 @@ constexpr bool nt_box_tie_shortcut() { return NT_BOX_TIE_SHORTCUT != 0 && N >= N
 #ifndef NT_BOX_CLASSIFY_SETS_MAX_N
 #define NT_BOX_CLASSIFY_SETS_MAX_N 7
 #endif
-template <int N>
+// FIXED != 0 (box_tile_kernel's edge rows, NT_BOX_EDGE_ROWS): the sets word is that compile-time constant, whatever `sets` says, and
+// the per-axis tests fold away.
+template <int N, uint32_t FIXED = 0u>
 __device__ __forceinline__ void box_classify_sets(const float (&o)[N], const float (&v)[N], float m, uint32_t sets, bool &hit, bool &unclear,
                                                   float &x) {
+    if constexpr (FIXED != 0u) sets = FIXED;
     // (nt_vmax & co.: these values cross basic blocks -- see there; the empty asm keeps the compiler from turning a skipped axis
     // into computed-and-discarded)
     float tn = -INFINITY, tn2 = -INFINITY, vK = 0.0f;
@@ -318,7 +321,7 @@ __device__ __forceinline__ void box_classify_sets(const float (&o)[N], const flo
     // masks -- five scalar instructions a test instead of a bit test and a branch, and six register pairs held across the loops
     // of a kernel that already parks scalar registers in a vector one; -DNT_EXP_SETS_MASKS: without, the build to measure against)
 #ifndef NT_EXP_SETS_MASKS
-    asm volatile("" : "+s"(sets));
+    if constexpr (FIXED == 0u) asm volatile("" : "+s"(sets));
 #endif
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -1092,6 +1095,34 @@ __device__ __forceinline__ float row_dir(const float (&base)[N], const float (&u
     for (int j = 1; j < N; ++j) sq = sq + dir[j] * dir[j];
     return sq;
 }
+// Edge rows (packed RGB, N = 6, the 64 x 1 kernel of launches of NT_BOX_TIE_SHORTCUT_MIN_WAVES waves or more -- the one with TIE;
+// why only there: below): a row sorted ray by ray whose stretch has valid sets with two coordinates in C -- a < b -- and T = C or one of the two: the cube's outline, or an edge between two faces
+// (63 % of the code-15 rows of the bench's cameras, tools/box_sets_census.py).  Set by set, as the one-face rows go face by face:
+// the first such row's sets word is read, one vector compare finds the rows that share it, the components a, b of `base`, `up`
+// and the origin are picked once, and a row of the set computes dir[a], dir[b], dir[0] alone -- the mul and sub of row_dir, bit
+// for bit its values -- and asks box_classify_sets<2> on those two axes, its sets word a compile-time constant (three cases: T =
+// {a}, {b}, {a, b}).  The verdicts are the N-axis call's, lane for lane: the argument above box_classify_sets (last axis, second
+// entry, inside sum, miss) carries over unchanged on one added premise -- the two arrays hold exactly the axes of C, in ascending
+// order, so that every max, min and sum runs over the same values in the same order, and the sum is set against 2 c = |C| c.
+// A row with an unclear lane stores nothing here and stays with the general loop.  A clear row is x = v_K (hit) or dir[0]
+// (background) through the lean rows' quotient behind their guard of 2^-18 (guard_clear: t, and t/2 of a hit), whose error
+// budget holds for any component (face_row uses it for dir[K], culled_row for dir[0]); a row with a lane inside the guard stays
+// with the general loop as well.  No floating-point operation that reaches a pixel is new.
+// (No cap on the sets a wave takes: picking the components costs about thirty vector instructions a set, so even a set of one
+// row is cheaper here than in the general loop; of the bench's cameras and of 3000 random ones no wave held more than four.)
+// Where.  The code needs box_classify_sets (N = 6 and 7) and is in the kernel that launch_box_fixed takes for large launches
+// only, as the near-tie short cut is and for its reason: built into box_tile_kernel<6, false, 64, 1, false> as well it cost a
+// rank's eighth of the headline call (14 400 waves) 67.97 -> 68.67 us, spreads 0.05 and 0.15, while the headline call (81 600
+// waves, the kernel with TIE) gained 292.4 -> 288.0 us.  N = 7 has no such kernel (nt_inst_box.hip) and goes without.
+// -DNT_BOX_EDGE_ROWS=0: without, the device code as it was: the build to measure and to test against.
+#ifndef NT_BOX_EDGE_ROWS
+#define NT_BOX_EDGE_ROWS 1
+#endif
+// (the dimensions whose kernels sort a row on its stretch's sets; which of their kernels: EDGE in box_tile_kernel)
+template <int N>
+constexpr bool nt_box_edge_rows() {
+    return NT_BOX_EDGE_ROWS != 0 && N >= NT_BOX_CLASSIFY_SETS_MIN_N && N <= NT_BOX_CLASSIFY_SETS_MAX_N && N <= NT_BOX_SETS_MAX_N && N <= NT_BOX_INLINE_MAX_N;
+}
 // Rows a pass of the row phase covers in the 64 x 1 shape: all 64 (masks of 64 row bits in scalar register pairs), or 16 -- the
 // sixteen-row passes the kernel had while its codes went through a qword of LDS, four a wave, each with its own header: the build
 // to measure against.  The 16- and 8-row shapes take their rows in one pass either way.
@@ -1268,6 +1299,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         typedef uint32_t nt_u32x16 __attribute__((ext_vector_type(16), aligned(16)));
         typedef __attribute__((address_space(4))) const nt_u32x16 *nt_rowtab4;
         constexpr bool GROUPS = !F32 && N <= NT_BOX_LEAN_GROUPS_MAX_N;
+        constexpr bool EDGE = TIE && !F32 && REG && PASS == 64 && nt_box_edge_rows<N>();
         uint8_t *const frame_base = tg.dest + (long long)frame * tg.frame_stride;
         // What a row loop needs to know about its row -- sy of the ray source and the row's byte offset in a frame -- comes
         // from a table the host wrote (NtTarget::rowtab, 16 bytes per owned row: sy, -, offset), read through the scalar
@@ -1550,6 +1582,75 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                     }
                 }
                 todo |= same & ~same_stored;
+            }
+            // ---- 5. the edge rows, set by set (NT_BOX_EDGE_ROWS, see there)
+            if constexpr (EDGE) {
+                mask_t edge = fastsq ? (mask_t)rows_rays & valid : (mask_t)0u;
+                if (edge != 0u) {
+                    // the lane's own word: valid, T inside C, |C| = 2, and T = C or |T| = 1
+                    const uint32_t lT = lane_cs & 0x3ffu, lC = (lane_cs >> 10) & 0x3ffu;
+                    const bool two = (lane_cs & 0x80000000u) != 0u && (lT & ~lC) == 0u && __builtin_popcount(lC) == 2 && (lT == lC || __builtin_popcount(lT) == 1);
+                    edge &= (mask_t)__builtin_amdgcn_ballot_w64(two);
+                }
+                // the packed pixel of a clear row: t of x, tgb its half for a hit, red unless the background looks down dir[0]
+                auto put_edge = [&](nt_gptr out, float t, float tgb, bool red) {
+                    if (SEL8) {
+                        const uint32_t q8r = __float_as_uint(t + 8388608.0f), q8gb = __float_as_uint(tgb + 8388608.0f);
+                        NT_EXP_STORE_IF NT_G32(out) = __builtin_amdgcn_perm(red ? q8r : 0u, q8gb, tg.plain_sel);
+                        return;
+                    }
+                    uint32_t qr = (uint32_t)(t + 0.5f), qgb = (uint32_t)(tgb + 0.5f);
+                    qr = qr < tg.plain_maxval ? qr : tg.plain_maxval;
+                    qgb = qgb < tg.plain_maxval ? qgb : tg.plain_maxval;
+                    const uint32_t w = (red ? qr : 0u) * tg.plain_mul[0] + qgb * (tg.plain_mul[1] + tg.plain_mul[2]);
+                    NT_EXP_STORE_IF NT_G32(out) = tg.reversed ? w : bswap32(w);
+                };
+                mask_t edge_stored = 0u;
+                while (edge != 0u) {
+                    const uint32_t w0 = slot_word(nt_low_bit(edge)) & 0x800fffffu;
+                    const mask_t same = edge & (mask_t)__builtin_amdgcn_ballot_w64((lane_cs & 0x800fffffu) == w0);
+                    edge &= ~same;
+                    const uint32_t c0 = (w0 >> 10) & 0x3ffu;
+                    const uint32_t ja = (uint32_t)__builtin_ctz(c0), jb = 31u - (uint32_t)__builtin_clz(c0);          // C = {ja < jb}
+                    float bA, uA, bB, uB;
+                    pick_component<N>(ja, base, upv, bA, uA);
+                    pick_component<N>(jb, base, upv, bB, uB);
+                    float oA = org[0], oB = org[0];
+#pragma unroll
+                    for (int j = 1; j < N; ++j) {
+                        oA = ja == (uint32_t)j ? org[j] : oA;
+                        oB = jb == (uint32_t)j ? org[j] : oB;
+                    }
+                    // the rows of the set; TSEL: which of the two axes are in T (bit 0: ja, bit 1: jb)
+                    auto set_rows = [&](auto tsel) {
+                        constexpr uint32_t WORD = 0x80000000u | (3u << 10) | decltype(tsel)::value;
+                        for (mask_t rest = same; rest != 0u;) {
+                            const int rr = nt_low_bit(rest);
+                            NT_CLEAR_BIT(rest, rr);
+                            NT_ROW_LOAD(rr);
+                            const float o2[2] = {oA, oB};
+                            const float v2[2] = {bA - uA * sy, bB - uB * sy};            // dir[ja], dir[jb], bit for bit
+                            const float v0 = base[0] - upv[0] * sy;                     // dir[0]
+                            bool hit, unclear;
+                            float x;
+                            box_classify_sets<2, WORD>(o2, v2, margin, WORD, hit, unclear, x);
+                            x = hit ? x : v0;
+                            const float t = lean_quotient(x, sy, uu, m2bu, bb);
+                            const float tgb = hit ? t * 0.5f : t;
+                            // (& on ints for &&: three lane masks and two scalar ands, where && was laid out as two branches on exec)
+                            const bool ok = ((int)!unclear & (int)guard_clear(t) & (int)guard_clear(tgb)) != 0;
+                            if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) == 0ull, 1)) {
+                                put_edge(NT_ROW_PTR() + NT_LANE_OFF(), t, tgb, hit || x > 0.0f);
+                                NT_SET_BIT(edge_stored, rr);
+                            }
+                        }
+                    };
+                    const bool inA = ((w0 >> ja) & 1u) != 0u, inB = ((w0 >> jb) & 1u) != 0u;
+                    if (inA && inB) set_rows(std::integral_constant<uint32_t, 3u>{});
+                    else if (inA) set_rows(std::integral_constant<uint32_t, 1u>{});
+                    else set_rows(std::integral_constant<uint32_t, 2u>{});
+                }
+                todo &= ~edge_stored;
             }
             };
             if (tg.plain_sel != 0u) lean_rows(std::true_type{});
