@@ -1067,9 +1067,52 @@ __global__ __launch_bounds__(256) void box_cull_kernel(NtCameraFixed cam, NtTarg
 #ifndef NT_BOX_LEAN_GROUPS_MAX_N
 #define NT_BOX_LEAN_GROUPS_MAX_N 20
 #endif
-// The lean rows' guard: t keeps 2^-18 * (1 + t) clear of every k + 1/2, so that the cheap quotient and the reference's round to
-// the same integer (box_tile_kernel, packed RGB)
-__device__ __forceinline__ bool guard_clear(float t) { return fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, 0x1p-18f, 0x1p-18f); }
+// The lean rows' guard: t keeps G * (1 + t) clear of every k + 1/2, so that the cheap quotient and the reference's round to
+// the same integer (box_tile_kernel, packed RGB).  G is sized per dimension from the distance between the two quotients.
+//
+// The budget, in units of u = 2^-24 (one fp32 rounding, relative), first order in u; everything is relative to the exact
+// T = |d| maxval / sqrt(S), S = sum_j (base_j - up_j sy)^2 = BB - 2 BU sy + UU sy^2 over the fp32 values base_j, up_j, sy that
+// both sides start from, and d = dir[K] is the same fp32 number on both sides.  Write a = BB, b = UU sy^2, X = 2 |BU sy|.
+// fastsq (bu^2 <= bb uu / 16) gives X <= sqrt(ab) / 2, hence S >= a + b - sqrt(ab) / 2 >= 3/4 (a + b), and b <= 16/15 S.
+//   lean_quotient
+//     bb, uu: N fma each, sums of squares: N a, N b.   bu: N fma, by Cauchy-Schwarz N sqrt(BB UU), times 2 |sy|: 2N sqrt(ab).
+//     The three products with 1/maxval^2: a, b and X.   Without the X: (N + 1)(a + b) + 2N sqrt(ab), which over S grows with
+//     sqrt(ab) / (a + b) and is largest at a = b:                                 (8N + 4) / 3
+//     the two fma of the evaluation: |sy| |sy uu + m2bu| <= b + X, and S; with the X above (2X + b) / S + 1 <=    2.52
+//     (2X <= sqrt(ab); over S that is largest near a = b / 3, 1.51)
+//     1/maxval^2 itself (a square and a reciprocal, common to the three):         2
+//     rsq halves the sum: (4N + 2) / 3 + 2.26; v_rsq_f32 at 1 ulp: 2; |d| * rsq: 1 (the half of a hit's t is exact)
+//                                                                            =>   4N/3 + 5.93
+//   the reference
+//     dir_j = fl(base_j - fl(up_j sy)) is off by (|up_j sy| + |dir_j|) u, its square's sum by 2 (sqrt(S b) + S) <= 4.07 S;
+//     N products and N - 1 additions left to right: N.   sqrtf halves the sum: N/2 + 2.04; sqrtf: 1; the division: 1; the
+//     product with maxval is exact (quantize multiplies the mantissa as an integer)
+//                                                                            =>   N/2 + 4.04
+// Sum: 11N/6 + 9.97 <= 11N/6 + 10 -- 21 at N = 6, 54 at N = 24.  (The worst cases above do not meet: over the
+// culled and one-face pixels of tests/test_box_lean_guard_host.py's cameras, which it holds to the budget one by one, the largest
+// distance is 6.7 at N = 8.)
+constexpr double nt_lean_budget_ulps(int n) { return 11.0 * n / 6.0 + 10.0; }
+// The width: the smallest power of two that leaves 1.5 times the budget, not below 2^-20 (box_pixel's guard for an exact sq) and
+// not above 2^-18, the one width every kernel had: 2^-19 for N = 3..6, 2^-18 beyond.  At the cap the factor is less than 1.5 from
+// N = 18 on (1.19 at N = 24), as it always was; the budget itself fits at every N.
+// -DNT_BOX_LEAN_GUARD_LOG2=18: that width everywhere, the device code as it was -- the build to measure and to test against.
+constexpr int nt_lean_guard_log2(int n) {
+#ifdef NT_BOX_LEAN_GUARD_LOG2
+    return NT_BOX_LEAN_GUARD_LOG2;
+#else
+    for (int k = 20; k > 18; --k)
+        if ((double)(1 << (24 - k)) >= 1.5 * nt_lean_budget_ulps(n)) return k;
+    return 18;
+#endif
+}
+template <int N>
+__device__ __forceinline__ bool guard_clear(float t) {
+    constexpr int K = nt_lean_guard_log2(N);
+    static_assert(K >= 18 && K <= 20, "the lean rows' guard: 2^-20 .. 2^-18");
+    static_assert((double)(1 << (24 - K)) >= (K == 18 ? 1.0 : 1.5) * nt_lean_budget_ulps(N), "the lean rows' guard holds 1.5 times the budget below the cap, the budget at it");
+    constexpr float G = 1.0f / (float)(1 << K);
+    return fabsf(__builtin_amdgcn_fractf(t) - 0.5f) > fmaf(t, G, G);
+}
 // ... and their quotient |d| * maxval / |dir| from the quadratic in sy (uu, m2bu, bb: |dir|^2 / maxval^2 = bb + m2bu sy + uu sy^2)
 __device__ __forceinline__ float lean_quotient(float d, float sy, float uu, float m2bu, float bb) {
     return fabsf(d) * __builtin_amdgcn_rsqf(fmaf(sy, fmaf(sy, uu, m2bu), bb));
@@ -1105,7 +1148,7 @@ __device__ __forceinline__ float row_dir(const float (&base)[N], const float (&u
 // entry, inside sum, miss) carries over unchanged on one added premise -- the two arrays hold exactly the axes of C, in ascending
 // order, so that every max, min and sum runs over the same values in the same order, and the sum is set against 2 c = |C| c.
 // A row with an unclear lane stores nothing here and stays with the general loop.  A clear row is x = v_K (hit) or dir[0]
-// (background) through the lean rows' quotient behind their guard of 2^-18 (guard_clear: t, and t/2 of a hit), whose error
+// (background) through the lean rows' quotient behind their guard (guard_clear<N>, 2^-19 at N = 6: t, and t/2 of a hit), whose error
 // budget holds for any component (face_row uses it for dir[K], culled_row for dir[0]); a row with a lane inside the guard stays
 // with the general loop as well.  No floating-point operation that reaches a pixel is new.
 // (No cap on the sets a wave takes: picking the components costs about thirty vector instructions a set, so even a set of one
@@ -1354,7 +1397,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
         }
         const float maxv = (float)tg.plain_maxval;
         // ... scaled by 1/maxval^2, so that rsq of it is maxval/|dir|: the multiplication by maxval costs three instructions a
-        // wave instead of one a row (three more roundings of 2^-24 each in a budget that had 2.6x room, see the guard)
+        // wave instead of one a row (three more roundings of 2^-24 each, counted in the guard's budget: guard_clear)
         const float inv_maxv2 = 1.0f / (maxv * maxv);
         const float m2bu = (-2.0f * bu) * inv_maxv2;
         bb = bb * inv_maxv2;
@@ -1429,8 +1472,9 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
 #endif
         if (!F32) {
             // ---- packed RGB: guarded rsq quantisation.  round(|dir[K]|/len * maxval) (and its half for a hit), as in box_pixel,
-            // with the guard widened for the quadratic |dir|^2: that is within (3.7n+4)*2^-24 of the reference's sum, so t is
-            // within ~22*2^-24 < 2^-19.4 of its value at n = 8; guard 2^-18.  A wave with a lane inside it takes the row ray by ray.
+            // with the guard widened for the quadratic |dir|^2: t is within nt_lean_budget_ulps(N) * 2^-24 (1 + t) of the
+            // reference's quotient (derived at guard_clear: 21 at N = 6, 54 at N = 24), and the guard is sized from that per
+            // dimension -- 2^-19 up to N = 6, 2^-18 beyond.  A wave with a lane inside it takes the row ray by ray.
             if (!fastsq) {
                 todo |= quick | inner;
                 quick = 0u;
@@ -1517,14 +1561,14 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                 d0 = base[0] - upv[0] * sy;                               // dir[0], bit for bit
 #endif
                 t = lean_quotient(d0, sy, uu, m2bu, bb);
-                return guard_clear(t);
+                return guard_clear<N>(t);
             };
             // a row of one face, bK and uK its components of `base` and `up`: t and its half
             auto face_row = [&](float bK, float uK, float sy, float &t, float &th) {
                 const float dK = bK - uK * sy;                            // dir[K], bit for bit
                 t = lean_quotient(dK, sy, uu, m2bu, bb);
                 th = t * 0.5f;
-                return guard_clear(t) && guard_clear(th);
+                return guard_clear<N>(t) && guard_clear<N>(th);
             };
             // ---- 1. aligned groups of four culled rows (groups that are mixed or cut by `valid` are left to 2.)
             if (GROUPS) {
@@ -1638,7 +1682,7 @@ __global__ __launch_bounds__(64 * WAVES) NT_TILE_OCC void box_tile_kernel(NtCame
                             const float t = lean_quotient(x, sy, uu, m2bu, bb);
                             const float tgb = hit ? t * 0.5f : t;
                             // (& on ints for &&: three lane masks and two scalar ands, where && was laid out as two branches on exec)
-                            const bool ok = ((int)!unclear & (int)guard_clear(t) & (int)guard_clear(tgb)) != 0;
+                            const bool ok = ((int)!unclear & (int)guard_clear<N>(t) & (int)guard_clear<N>(tgb)) != 0;
                             if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) == 0ull, 1)) {
                                 put_edge(NT_ROW_PTR() + NT_LANE_OFF(), t, tgb, hit || x > 0.0f);
                                 NT_SET_BIT(edge_stored, rr);

@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void box_rows_kernel_var(NtCamera cam, NtTarge
     const float m2bu = -2.0f * bu;
     // (the quadratic's error grows with n: (3.7n + 4) * 2^-24 relative -- the guard below is sized for it)
     const bool fastsq = __builtin_amdgcn_ballot_w64(!(bu * bu <= bb * uu * 0.0625f)) == 0ull;
-    const float guard = (5.55f * (float)n + 21.0f) * 0x1p-24f;         // three times the error bound (1.85n + 7) * 2^-24 of t: 2^-18 at n = 8
+    const float guard = (5.55f * (float)n + 21.0f) * 0x1p-24f;         // three times (1.85n + 7) * 2^-24: at every n more than 1.5 times nt_lean_budget_ulps(n) (nt_box.hpp, guard_clear)
     const float maxv = (float)tg.plain_maxval;
     float dots[4];
     if (cam.buf) {
