@@ -471,7 +471,8 @@ typedef struct {                 /* 16 bytes: one dwordx4 store a ray */
     float dist;                  /* nearest opaque hit, in units of |direction|; FLT_MAX when none */
     int32_t item;                /* (index << 2) | NT_KIND_*, the leaf-item code; -1: no opaque hit */
     int32_t lane;                /* simplex inside the batch; -1 otherwise */
-    int32_t n_transparent;       /* transparent hits left in the reference's list when the walk ends */
+    int32_t n_transparent;       /* transparent hits left in the reference's list when the walk ends; in the records of
+                                    nt_hit_layers this word is `count` (NT_LAYER_COUNT below) */
 } nt_ray_hit;
 
 typedef struct {
@@ -921,6 +922,42 @@ int nt_scene_batch_live_masks(const nt_scene_t *s, uint8_t *masks);
    2^31 - 1 pixels; NT_E_UNSUPPORTED while clip planes, a lens or the parallel projection are set. */
 int nt_crossing_counts(nt_scene_t *s, int width, int height, int32_t *counts, const nt_render_opts *opts);
 int nt_crossing_counts_device(nt_scene_t *s, int width, int height, void *counts_dev, const nt_render_opts *opts, void *hip_stream);
+
+/* ---- hit layers: the K nearest surfaces of every pixel, in order -------------------------------------------------------------
+   What lies under a pixel behind the first surface: the crossings of the pixel's primary ray, nearest first, with their
+   identity.  CompositeScene only.  Everything below is fp32, every product and sum rounded on its own (no fma).
+   For pixel (x, y) of a W x H view take (o, d), dist0 and the crossing set S exactly as the X-ray rule above defines them: the
+   batch rule with the live mask, the scalar rule for unbatched triangles with the cutoff FLT_MAX, a Solid's own test with the
+   cutoff FLT_MAX, S empty for dist0 < 0, and t != 0.  Each member of S carries
+     t:    the rule's own quotient -(no + dd) / denom for a simplex (one IEEE division); for a Solid its entering distance: a
+           cube's as the Solid's own fp32 test gives it; a sphere's, once that test has accepted it, evaluated again in float64
+           on the fp32 ray and record -- local ray lo = O^-1 o - p, ld = O^-1 d, a = ld.ld, b = 2 ld.lo, c = lo.lo - 1,
+           t = (-b - sqrt(b b - 4 a c)) / (2 a), sums in ascending index, no fma -- and rounded to fp32 once (the fp32 quadratic
+           cancels nearly all its digits from many radii away; without an entering root in float64 the fp32 distance stays);
+     item: the leaf-item code (index << 2) | NT_KIND_* of nt_ray_hit;
+     lane: 0..3 inside a batch, -1 otherwise.
+   Order S by t ascending; ties by item ascending, then lane ascending (t > 0, so the bits of t order as t does: the key is
+   (bits of t, item, lane)).  Layer l, l = 0 .. layers - 1, is the l-th member.  Its record is an nt_ray_hit
+     {dist = t, item, lane, count}
+   whose fourth word is count = |S|, the pixel's full crossing count -- nt_crossing_counts' number -- the same in every layer of
+   the pixel: count > layers says the list was cut.  A layer beyond |S| is {FLT_MAX, -1, -1, count}.  Every record of every
+   pixel is written.  Opacity, lights, shadows, reflections and the X-ray setting play no part; one ray a pixel.
+   `records` is planar, [layers][height][width]: the record of layer l of pixel (x, y) is at index (l * height + y) * width + x,
+   so a layer is a contiguous image.
+   Host form: holds the scene like nt_colors_at; of `opts` (may be NULL) device is read and strict_reference accepted and ignored
+   (there is no pruning to switch).  Device form: `records_dev` is device memory and the call is only enqueued on hip_stream; it
+   also reads abort_device, and every other field of `opts` must be 0.  Both are answered whether or not X-ray is on.  After a
+   warm-up call of the same shape nothing is allocated.  Before any device is touched and leaving the buffer alone:
+   NT_E_INVALID for NULL arguments, width or height < 1, `layers` outside 1..NT_LAYERS_MAX, a BoxScene, more than 2^31 - 1
+   records, and NT_E_UNSUPPORTED while clip planes, a lens or the parallel projection are set, and for a scene with more than
+   2^26 batches, triangles or Solids (the key keeps an item and its lane in 32 bits).
+   The routes are the X-ray's: up to 10 dimensions, a tree of depth <= 32 and NT_XRAY_PACKET_ITEMS items take the wave-uniform
+   packet walk, each lane keeping its 2, 4 or 8 nearest in registers; every other scene, and NTRACER_FORCE_VAR=1, the per-lane
+   walk.  Same bytes either way. */
+#define NT_LAYERS_MAX 8
+#define NT_LAYER_COUNT(rec) ((rec).n_transparent)      /* count = |S| of a hit-layer record */
+int nt_hit_layers(nt_scene_t *s, int width, int height, int layers, nt_ray_hit *records, const nt_render_opts *opts);
+int nt_hit_layers_device(nt_scene_t *s, int width, int height, int layers, void *records_dev, const nt_render_opts *opts, void *hip_stream);
 
 #ifdef __cplusplus
 }

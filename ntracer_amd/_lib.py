@@ -161,6 +161,8 @@ SYMBOLS = [
     ("nt_scene_batch_live_masks", C.c_int, [C.c_void_p, C.c_void_p]),
     ("nt_crossing_counts", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),
     ("nt_crossing_counts_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
+    ("nt_hit_layers", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),
+    ("nt_hit_layers_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts), C.c_void_p]),
     ("nt_scene_set_depth_cue", C.c_int, [C.c_void_p, C.POINTER(NtDepthCue), f32p]),
     ("nt_scene_get_depth_cue", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(NtDepthCue), C.POINTER(C.c_int), f32p]),
     ("nt_depth_cue_factors", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(NtRenderOpts)]),

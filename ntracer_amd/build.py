@@ -27,7 +27,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
          "-Wno-unused-function"]
 EXTRA = os.environ.get("NTRACER_HIPCC_FLAGS", "").split()         # ablation builds (-DNT_EXP_...)
 # headers that one instantiation file alone includes: only its units are stale when they change
-UNIT_HDR = {"nt_inst_stack.hip": [os.path.join(CSRC, "nt_stack.hpp")], "nt_inst_xray.hip": [os.path.join(CSRC, "nt_xray.hpp")]}
+UNIT_HDR = {"nt_inst_stack.hip": [os.path.join(CSRC, "nt_stack.hpp")], "nt_inst_xray.hip": [os.path.join(CSRC, "nt_xray.hpp")],
+            "nt_inst_layers.hip": [os.path.join(CSRC, h) for h in ("nt_xray.hpp", "nt_layers.hpp", "nt_layer_list.hpp")],
+            "nt_var.hip": [os.path.join(CSRC, "nt_layer_list.hpp")]}
 
 
 # The per-dimension families, in the order of one dimension's units (the link order follows it):
@@ -50,6 +52,7 @@ FAMILIES = (
     ("nt_inst_boxshade.hip", ("nt_box_shade",), True),
     ("nt_inst_stack.hip", ("nt_box_stack",), True),
     ("nt_inst_xray.hip", ("nt_xray_packet",), False),
+    ("nt_inst_layers.hip", ("nt_layers_packet",), False),
 )
 # CompositeScene's launchers that share a unit with BoxScene's: their sources define them up to DIMS alone (#if NT_INST_N <= NT_DEV_MAX_FIXED)
 COMPOSITE_IN_BOX_UNITS = ("nt_rays_fixed", "nt_refine_fixed")

@@ -736,6 +736,7 @@ struct FrameJob {
     const int *xs = nullptr, *ys = nullptr;
     int probe_count = 0;
     int view_w = 0, view_h = 0;
+    int layers = 1;                    // (nt_hit_layers alone) the planes of records a pixel gets
 };
 
 // The NTRACER_* render switches, read once per enqueue and never cached: a process may change its
@@ -2183,6 +2184,48 @@ int enqueue_xray(nt_scene *s, DeviceState *ds, const FrameJob &job, const Render
     return NT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// hit layers (nt_hit_layers; kernels in nt_layers.hpp and nt_var.hip)
+// ---------------------------------------------------------------------------------------------
+
+static_assert(NT_LAYERS_MAX == NT_DEV_LAYERS_MAX, "the layer limit of the ABI is the launcher's");
+
+// The job.layers planes of records of one view of job.view_w x job.view_h into `recs_dev` -- with that nullptr into scratch under
+// the supersampling cap: *recs_out.  No view setting plays a part.  One launch, on enqueue_xray's routes: the packet walk where
+// nt_xray_packet_route says so, with its numerators and quad order, else layers_var with the `checked` columns of as many blocks
+// as fit 512 MB.  Enqueue only.
+int enqueue_layers(nt_scene *s, DeviceState *ds, const FrameJob &job, const RenderSwitches &sw, nt_ray_hit *recs_dev, nt_ray_hit **recs_out) {
+    const char *noun = "the hit layers";
+    ViewPass vp;
+    if (int r = begin_view_pass(s, ds, job, nullptr, noun, vp)) return r;
+    const size_t bytes = (size_t)vp.px * job.layers * sizeof(nt_ray_hit);
+    if (!recs_dev) {
+        long long chunk_frames;
+        if (int r = plan_scratch_frames(vp, 1, noun, "the records of the view", (long long)bytes, (long long)s->ss_scratch_mb << 20, LLONG_MAX, chunk_frames)) return r;
+        Scratch at;
+        if (int e = at.open(ds, bytes)) return e;
+        recs_dev = at.take<nt_ray_hit>(bytes);
+    }
+    if (recs_out) *recs_out = recs_dev;
+    NtCompositeDev c;
+    scene_dev(s, ds, sw, job.strict, false, c);
+    NtLaunchInfo li = launch_info(s, ds, sw, 1, job.stream);
+    NtLayers ly{};
+    if (int e = device_camera(s, ds, job.cam_buf, job.stream, ly.cams)) return e;
+    ly.live = (const uint8_t *)ds->live.p;
+    ly.records = recs_dev;
+    ly.layers = job.layers;
+    if (nt_xray_packet_route(li, c)) {
+        if (int e = packet_records(s, ds, sw, vp.W, vp.H, 1, nullptr, li)) return e;
+    } else {
+        const long long tiles = (long long)((vp.W + 7) / 8) * ((vp.H + 7) / 8);
+        long long blocks = std::min<long long>(std::max<long long>(tiles, 1), 8192);
+        if (int e = checked_scratch(s, ds, sw, c, 64, blocks, 1, 0, (long long)512 << 20)) return e;
+    }
+    if (int r = nt_launch_layers(li, c, vp.tg, ly)) return launch_failed(r);
+    return NT_OK;
+}
+
 int enqueue(nt_scene *s, DeviceState *ds, const FrameJob &job_in) {
     const RenderSwitches sw = read_switches();
     FrameJob job = job_in;
@@ -2889,7 +2932,9 @@ struct ViewQuery {
     int (*device_options)(const nt_render_opts *opts);      // what the device form refuses of its options (nullptr: nothing)
     // the setting's enqueue: into `dev`, or with `kept` into scratch, whose place it tells there
     int (*enqueue)(nt_scene *s, DeviceState *ds, const FrameJob &job, T *dev, T **kept);
-    bool under_xray = false;             // answered while X-ray is on as well (the crossing counts alone)
+    bool under_xray = false;             // answered while X-ray is on as well (the crossing counts, the hit layers)
+    const char *layered = nullptr;       // not nullptr: the call brings a `layers` factor, 1..NT_LAYERS_MAX planes of `elem` bytes a
+                                         // pixel, and this is the noun of its refusals (the hit layers alone)
 };
 
 const ViewQuery<uint8_t> kAdaptiveMask = {
@@ -2929,11 +2974,18 @@ const ViewQuery<int> kCrossingCounts = {
     [](nt_scene *s, DeviceState *ds, const FrameJob &job, int *dev, int **kept) { return enqueue_xray(s, ds, job, read_switches(), dev, kept); },
     true};
 
-// what both forms check before a device is touched
+const ViewQuery<nt_ray_hit> kHitLayers = {
+    sizeof(nt_ray_hit), 1, "the hit layers", [](const nt_scene *) { return false; }, "", "the hit layers are", false, false,      // (the records term of `layered` covers the pixels)
+    [](const nt_render_opts *opts) { return only_device_strict_abort(opts, "the hit layers read", "their"); },
+    [](nt_scene *s, DeviceState *ds, const FrameJob &job, nt_ray_hit *dev, nt_ray_hit **kept) { return enqueue_layers(s, ds, job, read_switches(), dev, kept); },
+    true, "the hit layers"};
+
+// what both forms check before a device is touched; `layers`: the call's factor where q.layered (else 1)
 template <typename T>
-int view_query_validate(const nt_scene *s, int width, int height, const void *out, const nt_render_opts *opts, const ViewQuery<T> &q) {
+int view_query_validate(const nt_scene *s, int width, int height, int layers, const void *out, const nt_render_opts *opts, const ViewQuery<T> &q) {
     if (!s || !out) return fail(NT_E_INVALID, "NULL argument");
     if (width < 1 || height < 1) return fail(NT_E_INVALID, "invalid view size");
+    if (q.layered && (layers < 1 || layers > NT_LAYERS_MAX)) return fail(NT_E_INVALID, "%s take 1 to %d layers (%d)", q.layered, NT_LAYERS_MAX, layers);
     if (q.kind == 1 && !s->composite) return fail(NT_E_INVALID, "not a composite scene");
     if (q.kind == 0 && s->composite) return fail(NT_E_INVALID, "not a box scene");
     if (q.clip_what) {
@@ -2949,6 +3001,11 @@ int view_query_validate(const nt_scene *s, int width, int height, const void *ou
         if (opts && opts->collect_stats) return fail(NT_E_UNSUPPORTED, "the adaptive mask keeps no counters: collect_stats is not available");
     }
     if (s->lens || s->parallel > 0.0f) return fail(NT_E_UNSUPPORTED, "%s not available while a lens or the parallel projection is set", q.what);
+    // (a key of the layers' sorted lists keeps an item code and its lane in 32 bits)
+    if (q.layered && std::max(std::max(s->n_batches, s->n_triangles), s->n_solids) > NT_DEV_LAYERS_INDEX_MAX)
+        return fail(NT_E_UNSUPPORTED, "%s take scenes of up to 2^26 batches, triangles or Solids each", q.layered);
+    if (q.layered && (long long)width * height * layers > INT_MAX)
+        return fail(NT_E_INVALID, "%d layers of %d x %d pixels are beyond 2^31 - 1 records", layers, width, height);
     if (q.pixel_term && (long long)width * height > INT_MAX)
         return fail(NT_E_INVALID, "a view of %d x %d pixels is beyond 2^31 - 1 pixels", width, height);
     return check_renderable(s);
@@ -2957,17 +3014,19 @@ int view_query_validate(const nt_scene *s, int width, int height, const void *ou
 // The host form: the renderer protocol (`guard` is the caller's, so that it holds while the caller reads more), the enqueue into
 // scratch on the scene's own stream, and the buffer's way back.  *ds_out: where it ran.
 template <typename T>
-int view_query_host(RenderGuard &guard, const ViewQuery<T> &q, int width, int height, T *out, const nt_render_opts *opts, DeviceState **ds_out = nullptr) {
+int view_query_host(RenderGuard &guard, const ViewQuery<T> &q, int width, int height, T *out, const nt_render_opts *opts, DeviceState **ds_out = nullptr,
+                    int layers = 1) {
     nt_scene *s = guard.s;
-    if (int r = view_query_validate(s, width, height, out, opts, q)) return r;
+    if (int r = view_query_validate(s, width, height, layers, out, opts, q)) return r;
     if (int r = guard.acquire()) return r;
     DeviceState *ds;
     if (int r = scene_on_device(s, opts, -1, ds)) return r;
     if (int r = use_own_stream(ds)) return r;
-    const FrameJob job = view_job(width, height, ds->stream, opts, false);
+    FrameJob job = view_job(width, height, ds->stream, opts, false);
+    job.layers = layers;
     T *kept = nullptr;
     if (int r = q.enqueue(s, ds, job, nullptr, &kept)) { (void)hipStreamSynchronize(ds->stream); return r; }
-    HIP_TRY(hipMemcpyAsync(out, kept, (size_t)width * height * q.elem, hipMemcpyDeviceToHost, ds->stream));
+    HIP_TRY(hipMemcpyAsync(out, kept, (size_t)width * height * layers * q.elem, hipMemcpyDeviceToHost, ds->stream));
     HIP_TRY(hipStreamSynchronize(ds->stream));
     if (ds_out) *ds_out = ds;
     return NT_OK;
@@ -2975,8 +3034,9 @@ int view_query_host(RenderGuard &guard, const ViewQuery<T> &q, int width, int he
 
 // the device form: `out_dev` is device memory; enqueue only
 template <typename T>
-int view_query_device(nt_scene *s, const ViewQuery<T> &q, int width, int height, void *out_dev, const nt_render_opts *opts, void *hip_stream) {
-    if (int r = view_query_validate(s, width, height, out_dev, opts, q)) return r;
+int view_query_device(nt_scene *s, const ViewQuery<T> &q, int width, int height, void *out_dev, const nt_render_opts *opts, void *hip_stream,
+                      int layers = 1) {
+    if (int r = view_query_validate(s, width, height, layers, out_dev, opts, q)) return r;
     if (q.device_options) {
         if (int r = q.device_options(opts)) return r;
     }
@@ -2985,7 +3045,8 @@ int view_query_device(nt_scene *s, const ViewQuery<T> &q, int width, int height,
     DeviceState *ds;
     if (int r = scene_on_device(s, opts, -1, ds)) return r;
     if (int r = use_stream(ds, (hipStream_t)hip_stream)) return r;
-    const FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: where options are refused, 0)
+    FrameJob job = view_job(width, height, (hipStream_t)hip_stream, opts, true);      // (overlapped: where options are refused, 0)
+    job.layers = layers;
     return q.enqueue(s, ds, job, (T *)out_dev, nullptr);
 }
 
@@ -3947,6 +4008,15 @@ int nt_crossing_counts(nt_scene_t *s, int width, int height, int32_t *counts, co
 
 int nt_crossing_counts_device(nt_scene_t *s, int width, int height, void *counts_dev, const nt_render_opts *opts, void *hip_stream) {
     return view_query_device(s, kCrossingCounts, width, height, counts_dev, opts, hip_stream);
+}
+
+int nt_hit_layers(nt_scene_t *s, int width, int height, int layers, nt_ray_hit *records, const nt_render_opts *opts) {
+    RenderGuard guard(s);
+    return view_query_host(guard, kHitLayers, width, height, records, opts, nullptr, layers);
+}
+
+int nt_hit_layers_device(nt_scene_t *s, int width, int height, int layers, void *records_dev, const nt_render_opts *opts, void *hip_stream) {
+    return view_query_device(s, kHitLayers, width, height, records_dev, opts, hip_stream, layers);
 }
 
 int nt_depth_cue_factors(nt_scene_t *s, int width, int height, float *factors, const nt_render_opts *opts) {

@@ -433,6 +433,21 @@ static inline bool nt_xray_packet_route(const NtLaunchInfo &li, const NtComposit
            (long long)sc.n_batches + sc.n_triangles + sc.n_solids <= NT_DEV_XRAY_PACKET_ITEMS;
 }
 
+// Hit layers (nt_layers.hpp, nt_var.hip; the rule in full: ntracer_hip.h): the `layers` nearest crossings of every
+// pixel's primary ray, ordered by (t, item, lane), as nt_ray_hit records whose fourth word is the pixel's crossing count.  Every
+// pointer is device memory.
+#define NT_DEV_LAYERS_MAX 8
+#define NT_DEV_LAYERS_INDEX_MAX (1 << 26)      // an item code and its lane share the 32 low bits of a key: (item << 3) | (lane + 1)
+struct NtLayers {
+    const float *cams;        // [4][n] camera rows of the view (NtCamera::buf)
+    const uint8_t *live;      // [n_batches] live masks, as NtXray has them
+    void *records;            // nt_ray_hit [layers][height][width]
+    int layers;               // 1..NT_DEV_LAYERS_MAX
+};
+// tg: the view and the abort word; one frame.  The routes are nt_launch_xray's: layers_packet where nt_xray_packet_route says so,
+// else layers_var, which needs sc.checked (with checked_lanes = blocks of the launch * 64)
+int nt_launch_layers(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLayers &ly);
+
 int nt_launch_box(const NtLaunchInfo &li, const NtCamera &cam, const NtTarget &tg);
 // BoxScene face shading: box_shaded<N, LINES> of the scene's dimension, or box_hits_var into bs.recs and box_shaded_var behind
 // it.  tg is the whole image of every frame (no bands).  The cameras travel as for nt_launch_box.

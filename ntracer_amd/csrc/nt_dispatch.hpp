@@ -22,6 +22,7 @@ struct NtBoxShade;
 struct NtClip;
 struct NtStack;
 struct NtXray;
+struct NtLayers;
 
 // The compile-time-N launchers, one family a primary template.  Nothing defines the primary: every dimension is the explicit
 // specialisation `template <> int nt_X_fixed<NT_INST_N>(...)` of its own translation unit (nt_inst_*.hip, compiled once per
@@ -50,6 +51,8 @@ template <int N> int nt_box_shade(const NtLaunchInfo &li, const NtCamera &cam, c
 template <int N> int nt_box_stack(const NtLaunchInfo &li, const NtTarget &tg, const NtStack &sk);
 // (X-ray views, nt_inst_xray.hip: N = 3..NT_DEV_MAX_FIXED; named for the walk it launches, as the depth cues' family is)
 template <int N> int nt_xray_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtXray &xr);
+// (hit layers, nt_inst_layers.hip: N = 3..NT_DEV_MAX_FIXED; named for the walk it launches likewise)
+template <int N> int nt_layers_packet(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLayers &ly);
 
 template <int LO, typename F, int... I>
 inline bool nt_dispatch_dim_seq(int n, int &r, F &f, std::integer_sequence<int, I...>) {

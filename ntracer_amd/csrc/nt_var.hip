@@ -13,6 +13,7 @@
 #include "nt_cue.hpp"
 #include "nt_boxhits.hpp"
 #include "nt_boxshade.hpp"
+#include "nt_layer_list.hpp"
 #include "nt_dispatch.hpp"
 #include <climits>
 
@@ -1669,6 +1670,114 @@ __global__ __launch_bounds__(64) void xray_var(NtCompositeDev sc, NtTarget tg, N
 }
 
 // --------------------------------------------------------------------------------------
+// Hit layers at run-time n (the rule in full: ntracer_hip.h; nt_layers.hpp has the packet walk): xray_var's
+// per-lane walk with its exact `checked` columns -- its control through kd_descend and kd_resume_closest with nothing ever
+// "dirty", which resumes every far side as xray_var's own text does; where xray_var counts a crossing the lane also inserts its
+// key into the sorted list of nt_layer_list.hpp -- always the 8-key list, of which the first ly.layers planes are stored.  One frame.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void layers_var(NtCompositeDev sc, NtTarget tg, NtLayers ly, int n, int tiles_x, int tiles_y) {
+    extern __shared__ float2 lds_raw[];
+    const int lane = (int)threadIdx.x;
+    VarLds L;
+    WaveLds w;
+    var_lds_carve(reinterpret_cast<char *>(lds_raw), n, sc.stack_depth, L, w);
+    const long long slot = (long long)blockIdx.x * 64 + lane;
+    Checked ck;
+    ck.bits = sc.checked + slot;
+    ck.stride = sc.checked_lanes;
+    ck.words = sc.checked_words;
+    ck.n_batches = sc.n_batches;
+    ck.n_triangles = sc.n_triangles;
+    const VarCtx cx = {sc, L, w, n, lane};
+    const int max_sp = sc.stack_depth;
+    const long long total = (long long)tiles_x * tiles_y;
+    const long long px = (long long)tg.width * tg.height;
+    for (long long tile = (long long)blockIdx.x; tile < total; tile += gridDim.x) {
+        if (nt_aborted(tg)) return;                       // (one wave a block)
+        const int by = (int)(tile / tiles_x);
+        const int bx = (int)(tile - (long long)by * tiles_x);
+        const PixelRef pr = locate_pixel_at<8, 8>(tg, bx, by, 0, lane & 7, lane >> 3, lane);
+        if (!pr.valid) continue;
+        const float *c = ly.cams;
+        // ---- primary ray (tracer.hpp:60-76) becomes the current ray
+        const float sx = tg.fovI * ((float)pr.x - tg.half_w);
+        const float sy = tg.fovI * ((float)pr.y - tg.half_h);
+        float sq = 0.0f;
+        for (int k = 0; k < n; ++k) {
+            const float v = (c[3 * n + k] + c[n + k] * sx) - c[2 * n + k] * sy;
+            L.dv[k * 64 + lane] = v;
+            sq = k == 0 ? v * v : sq + v * v;
+        }
+        const float len = sqrtf(sq);
+        for (int k = 0; k < n; ++k) {
+            const float dk = L.dv[k * 64 + lane] / len;
+            L.dv[k * 64 + lane] = dk;
+            L.ray[k * 64 + lane] = make_float2(c[k], dk != 0.0f ? 1.0f / dk : __int_as_float(0x7fc00000));
+        }
+        int count = 0;
+        LayerList<NT_DEV_LAYERS_MAX> ls;
+        ls.clear();
+        float t_near = aabb_distance_var(cx);
+        if (t_near >= 0.0f) {
+            // the Solids, every one of them in front of the walk, as xray_var has them; the leaves' own are skipped below
+            for (int idx = 0; idx < sc.n_solids; ++idx) {
+                int lane_out;
+                float t = test_item_var(cx, (idx << 2) | 2, FLT_MAX, -1, -1, lane_out);
+                if (t == 0.0f) continue;
+                ++count;
+                // (a sphere's distance once more in float64: layer_sphere_t says why)
+                if (sc.solid_types[idx] != 1)
+                    t = layer_sphere_t(sc.solid_recs + (size_t)idx * (2 * n * n + n), n, t, [&](int k) { return L.ray[k * 64 + lane].x; },
+                                       [&](int k) { return L.dv[k * 64 + lane]; });
+                ls.insert(layer_key(true, t, (idx << 2) | 2, -1));
+            }
+            checked_reset(ck);
+            int node = sc.root, sp = 0;
+            int dirty = 0;
+            float t_far = FLT_MAX;
+            const float none = FLT_MAX;
+            for (;;) {
+                while (node >= 0) {
+                    const NtNode nd = sc.nodes[node];
+                    if (nd.axis < 0) {
+                        for (int i = 0; i < nd.right; ++i) {
+                            const int item = sc.items[nd.left + i];
+                            const int kind = item & 3, idx = item >> 2;
+                            if (kind > 1 || checked_seen(ck, item)) continue;
+                            if (kind == 0) {
+                                const unsigned int lv = ly.live[idx];
+                                for (int l = 0; l < NT_DEV_BATCH; ++l) {
+                                    if (((lv >> l) & 1u) == 0u) continue;
+                                    const float t = simplex_var(sc.batch_recs + ((size_t)idx * NT_DEV_BATCH + l) * sc.rec_stride, n, L, lane, false, 0.0f);
+                                    if (t == 0.0f) continue;
+                                    ++count;
+                                    ls.insert(layer_key(true, t, item, l));
+                                }
+                                continue;
+                            }
+                            // (test_item_var: the scalar rule with the cutoff it is handed)
+                            int lane_out;
+                            const float t = test_item_var(cx, item, FLT_MAX, -1, -1, lane_out);
+                            if (t == 0.0f) continue;
+                            ++count;
+                            ls.insert(layer_key(true, t, item, -1));
+                        }
+                        node = -1;
+                        break;
+                    }
+                    const KdStep s = kd_descend(w, lane, nd, node, sp, max_sp, t_near, t_far, 0u);
+                    if (s.crossed) t_near = s.t;
+                }
+                // (no hit, so nothing prunes: every far side is resumed)
+                if (!kd_resume_closest(sc, w, lane, node, sp, dirty, none, t_near)) break;
+                t_far = kd_t_far_below(sc, w, lane, sp, FLT_MAX);
+            }
+        }
+        layers_store<NT_DEV_LAYERS_MAX>(ly.records, (long long)pr.y * tg.width + pr.x, px, ly.layers, ls, count);
+    }
+}
+
+// --------------------------------------------------------------------------------------
 // Ray queries at run-time n (n = 11..64, and every n under NTRACER_FORCE_VAR=1): the kernels of nt_query.hpp on the walks
 // above.  One lane per ray and one wave a block, as the run-time-n render kernels have it -- their n-vectors in LDS make
 // four waves' worth too much at the upper dimensions -- so lane l of block b takes ray 64 b + l, and the blocks stride on.
@@ -3249,6 +3358,36 @@ int xray_var_launch(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTa
     return 0;
 }
 }  // namespace
+
+namespace {
+// the general route of a hit-layer launch: layers_var, as many one-wave blocks as the `checked` scratch has lane columns for
+int layers_var_launch(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLayers &ly) {
+    int r;
+    if ((r = var_dim_check(li.n))) return r;
+    if (!sc.checked || sc.checked_lanes < 64 || !ly.cams || (sc.n_batches > 0 && !ly.live) || !ly.records || ly.layers < 1 ||
+        ly.layers > NT_DEV_LAYERS_MAX || li.nframes != 1) {
+        snprintf(nt_launch_error_buf(), NT_LAUNCH_ERROR_LEN, "internal: a hit-layer launch without its scratch, cameras, masks or records");
+        return -1;
+    }
+    size_t lds;
+    if ((r = var_walk_ready(li.n, sc, reinterpret_cast<const void *>(layers_var), lds))) return r;
+    const int tiles_x = (tg.width + 7) / 8, tiles_y = (tg.height + 7) / 8;
+    const dim3 grid((unsigned)checked_blocks(sc, (long long)tiles_x * tiles_y));
+    hipLaunchKernelGGL(layers_var, grid, dim3(64), lds, (hipStream_t)li.stream, sc, tg, ly, li.n, tiles_x, tiles_y);
+    return 0;
+}
+}  // namespace
+
+// Hit layers: the routes of nt_launch_xray, with layers_packet (nt_layers.hpp) and layers_var
+int nt_launch_layers(const NtLaunchInfo &li, const NtCompositeDev &sc, const NtTarget &tg, const NtLayers &ly) {
+    int r = 0;
+    if (!nt_xray_packet_route(li, sc) ||
+        !nt_dispatch_dim<3, NT_DEV_MAX_FIXED>(li.n, r, [&](auto N) { return nt_layers_packet<decltype(N)::value>(li, sc, tg, ly); })) {
+        r = layers_var_launch(li, sc, tg, ly);
+    }
+    if (r) return r;
+    return finish_launch("hit-layer kernel launch");
+}
 
 // X-ray views.  The packet walk of the scene's dimension (nt_xray.hpp) where nt_xray_packet_route says so -- the item count is
 // checked there, before the launch, against the bitset the walk can hold -- and xray_var for every other scene.  Kept apart from

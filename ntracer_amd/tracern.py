@@ -625,6 +625,35 @@ class FaceHits(object):
         return Vector.axis(self.dimension, axis, 1.0 if int(self.side[at]) else -1.0)
 
 
+class HitLayers(object):
+    """What CompositeScene.hit_layers answers with: the `layers` nearest surfaces under every pixel of a view, nearest first
+    (include/ntracer_hip.h has the rule), as numpy arrays or as torch tensors on the device, views of the records the library
+    wrote.  records is the raw buffer, int32 [layers][height][width][4] (dist's bits, item, lane, count); dist (FLT_MAX: no such
+    layer), item, kind, index and lane (-1: no such layer) are [layers][height][width]; count [height][width] is the pixel's
+    full crossing count -- crossing_counts' number -- and cut says where it exceeds `layers`, so that the list was cut."""
+
+    def __init__(self, scene, width, height, layers, records):
+        self._scene = scene
+        self.width, self.height, self.layers = width, height, layers
+        self.records = records
+        self.dist = _as_f32(records[..., 0])
+        self.item, self.lane = records[..., 1], records[..., 2]
+        self.count = records[0, :, :, 3]
+        self.cut = self.count > layers
+
+    kind = PrimaryHits.kind
+    index = PrimaryHits.index
+
+    def primitive(self, x, y, layer=0):
+        """(the scene's own object, batch_index) of layer `layer` under pixel (x, y) -- batch_index is the simplex inside a
+        TriangleBatch, -1 otherwise -- or None where the pixel has no such layer"""
+        at = (int(layer), int(y), int(x))
+        item = int(self.item[at])
+        if item < 0:
+            return None
+        return self._scene._object_of(item & 3, item >> 2), int(self.lane[at])
+
+
 def _as_f32(a):
     """the same 32 bits as fp32: numpy or torch"""
     if hasattr(a, "is_cuda"):
@@ -1169,6 +1198,36 @@ class _SceneBase(Scene):
         (nt_crossing_counts; the rule: include/ntracer_hip.h), whether or not set_xray is on: int32 [height][width] -- a numpy
         array, or with `device` a torch device a torch tensor there, enqueued on torch's current stream."""
         return self._view_query("nt_crossing_counts", width, height, device, np.int32, None, None)
+
+    def hit_layers(self, width, height, layers=4, device=None):
+        """The `layers` (1..8) nearest surfaces under every pixel of a width x height view of the scene's camera, nearest first,
+        with what each one is and the pixel's full crossing count (nt_hit_layers; the rule: include/ntracer_hip.h): a HitLayers
+        of numpy arrays, or with `device` a torch device of torch tensors there, enqueued on torch's current stream.  One walk
+        of the tree whatever `layers` is; opacity and every view setting but the camera play no part.  CompositeScene only."""
+        if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or not 1 <= layers <= 8:
+            raise ValueError("layers must be an int in 1..8")
+        layers = int(layers)
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("the size of a view must be positive")
+        L = _lib.lib()
+        opts = _lib.NtRenderOpts()
+        if device is None:
+            opts.device = -1
+            out = np.zeros((layers, height, width, 4), np.int32)
+            _lib.check(L.nt_hit_layers(self._handle, width, height, layers, out.ctypes.data, C.byref(opts)))
+            return HitLayers(self, width, height, layers, out)
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("device must be a HIP device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        opts.device = dev.index
+        out = torch.empty((layers, height, width, 4), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.nt_hit_layers_device(self._handle, width, height, layers, C.c_void_p(out.data_ptr()), C.byref(opts), C.c_void_p(stream)))
+        return HitLayers(self, width, height, layers, out)
 
     def set_depth_cue(self, near=0.0, far=1.0, color=(0, 0, 0), strength=1.0, background=False, tint_axis=None, tint_range=None,
                       tint_colors=None):

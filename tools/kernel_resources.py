@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """VGPR / SGPR / scratch / LDS of every kernel in the built objects: python3 tools/kernel_resources.py [substring]
-(reads the gfx950 code objects out of ntracer_amd/build/*.o with clang-offload-bundler + llvm-readelf --notes)."""
+(reads the gfx950 code objects out of ntracer_amd/build/*.o with clang-offload-bundler + llvm-readelf --notes).
+The substring picks a family: `xray` the table of DESIGN.md 4.17, `layers` that of 4.18 (layers_packet<N, 32, SCAL, KCAP> and
+layers_var; profiles/layers_kernel_resources.txt is its output)."""
 import glob
 import os
 import re
